@@ -34,14 +34,20 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md "HBM3E peak BW"
+HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec peak bandwidth
 CONFIG4_TOTAL_BLOCKS = 1 << 20  # BASELINE.json configs[3]: 1 M x 128 KB blocks over 8 GPUs
+# --dump-outputs stays under 64 MB: per-block values of at most 2^18 blocks (52 bytes each: index, status, size and two 64-bit
+# checksums, each as two float64 halves) and at most 4 MiB of sampled bytes per byte array (16 MiB as float32; two arrays)
+DUMP_ROWS = 1 << 18
+DUMP_SAMPLE_BYTES = 4 << 20
+DUMP_LIMIT_BYTES = 64 * 10**6
 
 
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200, help="default: a timed region of about 2 s")
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed steps (default: 200 for the decode workloads, about 2 s; 20 for lz4 / zstd, 50 for mixed)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--blocks", type=int, default=0, help="cryo blocks per GPU (default: 65536 at N=1, 131072 at N>1, 16384 for mixed)")
     ap.add_argument("--block-size", type=int, default=131072)
@@ -62,7 +68,16 @@ def parse_args():
                     help="one-GPU rate of the same per-GPU share: per_gpu_efficiency_vs_n1 = slowest rank's rate / this (N > 1)")
     ap.add_argument("--lz4-walkers", type=int, default=0, help="diagnostic: CRYO_OPT_LZ4_INDEX_WALKERS (0 auto)")
     ap.add_argument("--lz4-waves", type=int, default=0, help="diagnostic: CRYO_OPT_LZ4_DECODE_WAVES (0 auto, 1 one wave per block, 2 two)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last step returned to its caller as DIR/<name>.npy (float32 / "
+                         "float64, rank 0's share): per-block status, sizes and 64-bit checksums, and the bytes of a fixed "
+                         "seeded sample of blocks; at most 64 MB in all")
+    a = ap.parse_args()
+    if a.steps is None:
+        a.steps = {"lz4": 20, "zstd": 20, "mixed": 50}.get(a.workload, 200)   # an encode pass is 10-50x a decode pass
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 # ------------------------------------------------------------------------------------------------
@@ -311,6 +326,42 @@ def main():
         mismatch = int(d_mis.download(dtype=np.uint64)[0])
         assert a.no_verify or mismatch == 0, "decoded blocks differ from originals: %d" % mismatch
 
+    # --dump-outputs: the same seeded block choice in every run with the same arguments, so that two builds compare file by file
+    rng = np.random.default_rng(0)
+    dump_rows = np.arange(n) if n <= DUMP_ROWS else np.sort(rng.choice(n, DUMP_ROWS, replace=False))
+    dump_idx = np.sort(rng.choice(n, max(1, min(n, DUMP_SAMPLE_BYTES // B)), replace=False))
+
+    def checksums(d_src, stride, d_sizes=None):
+        """64-bit checksum of every block (device), as two exact float64 halves [hi, lo] of the dumped rows"""
+        d_sums = alloc(8 * n)
+        codec.checksum_batch(d_src, stride, n, d_sums, d_sizes, B if d_sizes is None else 0)
+        codec.sync()
+        s = d_sums.download(dtype=np.uint64)[dump_rows]
+        return np.stack([s >> np.uint64(32), s & np.uint64(0xFFFFFFFF)], axis=1).astype(np.float64)
+
+    def sample(d_src, stride, sizes=None):
+        """the bytes of the sampled blocks (at most DUMP_SAMPLE_BYTES of each), concatenated, as float32"""
+        return np.concatenate([d_src.download(min(B if sizes is None else int(sizes[i]), DUMP_SAMPLE_BYTES), offset=int(i) * stride)
+                               for i in dump_idx]).astype(np.float32)
+
+    def dump_outputs(status, d_dec, dec_stride, d_comp=None, comp_stride=0, d_sizes=None):
+        """rank 0 writes its share of the last timed step's results: per block (the dumped rows) status, checksum of the
+        decoded block and, for the encode workloads, compressed size and checksum of the stream; the bytes of the sampled
+        blocks (decoded, and compressed streams back to back)"""
+        out = {"block_index": dump_rows.astype(np.float64), "status": status[dump_rows].astype(np.float32),
+               "decoded_checksum64": checksums(d_dec, dec_stride),
+               "sample_block_index": dump_idx.astype(np.float64), "decoded_sample": sample(d_dec, dec_stride)}
+        if d_comp is not None:
+            sizes = d_sizes.download(dtype=np.uint32)
+            out.update({"compressed_size": sizes[dump_rows].astype(np.float64),
+                        "compressed_checksum64": checksums(d_comp, comp_stride, d_sizes),
+                        "compressed_sample": sample(d_comp, comp_stride, sizes)})
+        total = sum(x.nbytes for x in out.values())
+        assert total <= DUMP_LIMIT_BYTES, "--dump-outputs: %d bytes" % total
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for name, x in out.items():
+            np.save(os.path.join(a.dump_outputs, name + ".npy"), x)
+
     # =============================== decode workloads (headline) ===============================
     if a.workload.endswith("_decode"):
         is_lz4 = a.workload == "lz4_decode"
@@ -356,6 +407,8 @@ def main():
         barrier()
         elapsed = max_over_ranks((sum(kernel_ms) * 1e-3) if flush else (time.perf_counter() - t0))
         verify_all()
+        if a.dump_outputs and rank == 0:
+            dump_outputs(d_status.download(dtype=np.int32), d_out, ostride)
         if rank == 0 and os.environ.get("CRYO_BENCH_TRACE"):   # diagnostic: the per-step times, ten per line
             print("[bench trace] device pointers: comp %#x out %#x raw %#x" % tuple(int(getattr(x, "ptr", 0) or 0) for x in (d_comp, d_out, d_raw)), file=sys.stderr)
             for i in range(0, len(kernel_ms), 10):
@@ -413,7 +466,7 @@ def main():
             if timed:
                 enc_ms.append(t1)
                 dec_ms.append(t2)
-        steps = min(a.steps, 20) if a.steps == 200 else a.steps   # an encode pass is 10-50x a decode pass
+        steps = a.steps
         for _ in range(min(a.warmup, 2)):
             step(False)
         barrier()
@@ -424,6 +477,8 @@ def main():
         barrier()
         elapsed = max_over_ranks(time.perf_counter() - t0)
         verify_all()
+        if a.dump_outputs and rank == 0:
+            dump_outputs(d_status.download(dtype=np.int32), d_out, B, d_comp, stride, d_sizes)
         if rank == 0 and os.environ.get("CRYO_BENCH_TRACE"):
             print("[bench trace] encode ms: %s" % " ".join("%.2f" % x for x in enc_ms), file=sys.stderr)
             print("[bench trace] decode ms: %s" % " ".join("%.2f" % x for x in dec_ms), file=sys.stderr)
@@ -501,7 +556,7 @@ def main():
         def step():
             codec._chk(codec.L.cryo_codec_decompress_batch(codec.h, METHOD_ZSTD, d_zs.ptr, d_zso.ptr, d_zss.ptr, d_out.ptr, 2 * B, B, ne, d_zsst.ptr), "decompress_batch")
             codec._chk(codec.L.cryo_codec_decompress_batch(codec.h, METHOD_LZ4, d_lz.ptr, d_lzo.ptr, d_lzs.ptr, d_out.ptr + B, 2 * B, B, no, d_lzst.ptr), "decompress_batch")
-        steps = min(a.steps, 50) if a.steps == 200 else a.steps
+        steps = a.steps
         for _ in range(min(a.warmup, 2)):
             step()
         codec.sync()
@@ -515,9 +570,14 @@ def main():
         codec.sync()
         barrier()
         elapsed = max_over_ranks(time.perf_counter() - t0)
-        assert (d_zsst.download(dtype=np.int32) == 0).all() and (d_lzst.download(dtype=np.int32) == 0).all(), "decode status"
+        zst, lst = d_zsst.download(dtype=np.int32), d_lzst.download(dtype=np.int32)
+        assert (zst == 0).all() and (lst == 0).all(), "decode status"
         d_status.memset(0)
         verify_all()
+        if a.dump_outputs and rank == 0:
+            st = np.empty(n, np.int32)
+            st[0::2], st[1::2] = zst, lst   # even slots zstd, odd slots lz4, as in d_out
+            dump_outputs(st, d_out, B)
         if rank == 0:
             zbytes, lbytes = int(zsz.astype(np.uint64).sum()), int(lzsz.astype(np.uint64).sum())
             algo = zbytes + lbytes + n * B

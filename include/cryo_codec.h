@@ -4,7 +4,7 @@
  * This is the drop-in boundary underneath pg_cryogen's compression.h
  * (reference compression.h:7-24).  The reference reaches its codec through
  * six third-party calls; each entry point below names the call (file:line in
- * /root/reference) it replaces.  Plain C, plain pointers and sizes, no HIP or
+ * adjust/pg_cryogen) it replaces.  Plain C, plain pointers and sizes, no HIP or
  * torch types.  Nothing here ever calls elog()/exit()/throws: every function
  * returns a cryo_status (0 = ok, negative = error) so that the PG-side C shim
  * (pg_cryogen_amd/host/compression.c) can raise ereport(ERROR) itself without a

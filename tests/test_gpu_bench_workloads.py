@@ -62,6 +62,39 @@ def test_bench_full_size_configs(workload, blocks):
     assert 0 < j["roofline"]["frac"] < 1 and j["cpu_baseline"]["value"] > 0
 
 
+def test_bench_dump_outputs(tmp_path, oracle):
+    """--dump-outputs writes what the last timed step returned: float32 / float64 files, 64 MB at most; statuses, sizes and
+    checksums of every block and the sampled blocks' bytes agree with the generator and the oracle; a second run with the
+    same arguments writes the same files, and the headline decode workload writes the same decoded results.  --steps 200
+    is the number of timed steps of an encode workload too."""
+    from pg_cryogen_amd.codec import checksum64
+    B, n = 131072, 256
+    args = ["--blocks", str(n), "--warmup", "1", "--no-cpu-baseline", "--dump-outputs"]
+    runs = []
+    for k, (workload, steps) in enumerate((("lz4", 200), ("lz4", 200), ("lz4_decode", 3))):
+        d = tmp_path / str(k)
+        j = run_bench("--workload", workload, "--steps", str(steps), *args, str(d))
+        assert j["steps"] == steps
+        files = sorted(d.iterdir())
+        assert sum(f.stat().st_size for f in files) <= 64 * 10**6
+        runs.append({f.stem: np.load(f) for f in files})
+        assert all(x.dtype in (np.float32, np.float64) for x in runs[-1].values())
+    r = runs[0]
+    assert sorted(r) == sorted(runs[1]) and all(np.array_equal(r[k], runs[1][k]) for k in r)
+    assert all(np.array_equal(r[k], runs[2][k]) for k in ("block_index", "status", "decoded_checksum64", "sample_block_index", "decoded_sample"))
+    assert np.array_equal(r["block_index"], np.arange(n)) and (r["status"] == 0).all()
+    raws = [oracle.synth(0, i, B, 0) for i in range(n)]
+    comps = [oracle.lz4_compress(x, 1) for x in raws]
+    halves = lambda s: [s >> 32, s & 0xFFFFFFFF]
+    assert r["decoded_checksum64"].tolist() == [halves(checksum64(x)) for x in raws]
+    assert r["compressed_checksum64"].tolist() == [halves(checksum64(c)) for c in comps]
+    assert r["compressed_size"].tolist() == [len(c) for c in comps]
+    idx = r["sample_block_index"].astype(np.int64)
+    assert len(idx) == min(n, (4 << 20) // B) and (np.diff(idx) > 0).all() and 0 <= idx[0] and idx[-1] < n
+    assert np.array_equal(r["decoded_sample"], np.concatenate([raws[i] for i in idx]))
+    assert np.array_equal(r["compressed_sample"], np.concatenate([comps[i] for i in idx]))
+
+
 def test_automatic_walkers_batch_against_oracle(codec, oracle):
     """A 16 384-block batch takes the index pass at its AUTOMATIC setting (four walkers per block, lz4_decode_plan) --
     the other tests force the walker count on a few dozen blocks.  Blocks are generated and compressed on the device;
