@@ -95,7 +95,17 @@ typedef enum {
     CRYO_OPT_NUMA_LOCAL = 8,
     /* waves per block of the indexed LZ4 decoder: 0 = automatic (two for batches that leave most of the chip idle: up to
      * 3 072 blocks; one otherwise), 1 = k_lz4_dec_seq, 2 = k_lz4_dec_dual whatever the batch size */
-    CRYO_OPT_LZ4_DECODE_WAVES = 9
+    CRYO_OPT_LZ4_DECODE_WAVES = 9,
+    /* segment-parallel encode, for calls of few blocks (the access method's write path hands over one block per call):
+     * 0 (default) = the byte-identical encoders; a power of two S from 4 096 to 131 072 = every block of more than S bytes
+     * is cut into ceil(B / S) segments, each encoded by its own wave (LZ4: any acceleration, blocks up to 16 MiB; zstd: the
+     * `fast` strategy, levels -5 .. 2 -- other levels, and blocks of at most S bytes, take the byte-identical path).  The
+     * result is ONE valid LZ4 block / ONE zstd frame per cryo block (matches reach back into earlier segments; a zstd frame
+     * holds ceil(B / S) blocks, each with its own entropy tables) that liblz4 1.9.3 / libzstd 1.4.8 decode to the input,
+     * of at most cryo_codec_bound() bytes, and deterministic -- the same bytes for the same block whatever the call or the
+     * batch -- but NOT the libraries' own output.  Applies to every compress entry point (cryo_codec_compress_batch,
+     * _block, _blocks, cryo_multi_compress_blocks via cryo_multi_set_option).  Other values: CRYO_E_ARG. */
+    CRYO_OPT_ENCODE_SEGMENT_BYTES = 10
 } cryo_option;
 int cryo_codec_set_option(cryo_codec *c, int option, int64_t value);
 /* a long-lived backend between bursts: waits for the handle's queued work, then frees its device workspace, the device and

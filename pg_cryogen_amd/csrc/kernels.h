@@ -152,6 +152,25 @@ hipError_t launch_zstd_compress(hipStream_t s, const uint8_t *d_src, uint64_t sr
 size_t zstd_compress_workspace(uint64_t n_blocks, int level, uint32_t block_size);
 bool zstd_compress_supported(int level, uint32_t block_size);
 
+/* segment-parallel encode (CRYO_OPT_ENCODE_SEGMENT_BYTES; enc_seg.hip): ceil(block_size / seg_bytes) waves per block, one
+ * valid stream per block that is not the libraries' own output */
+uint32_t enc_seg_count(uint32_t block_size, uint32_t seg_bytes);
+size_t lz4_compress_segmented_workspace(uint64_t n_blocks, uint32_t block_size, uint32_t seg_bytes);
+hipError_t launch_lz4_compress_segmented(hipStream_t s, const uint8_t *d_src, uint64_t src_stride, uint32_t block_size,
+                                         uint64_t n_blocks, uint8_t *d_dst, uint64_t dst_stride, int accel, uint32_t seg_bytes,
+                                         uint32_t *d_out_size, int32_t *d_status, void *d_ws, size_t ws_bytes);
+bool zstd_segment_supported(int level, uint32_t block_size); /* strategy `fast` (levels -5 .. 2 at cryo block sizes) */
+size_t zstd_compress_segmented_workspace(uint64_t n_blocks, int level, uint32_t block_size, uint32_t seg_bytes);
+hipError_t launch_zstd_compress_segmented(hipStream_t s, const uint8_t *d_src, uint64_t src_stride, uint32_t block_size,
+                                          uint64_t n_blocks, uint8_t *d_dst, uint64_t dst_stride, int level, uint32_t seg_bytes,
+                                          uint32_t *d_out_size, int32_t *d_status, void *d_workspace, size_t workspace_bytes);
+/* enc_seg.hip internals shared with zstd_enc.hip */
+size_t zstd_seg_scratch_bytes(uint64_t items, uint32_t seg_bytes);
+uint64_t zstd_seg_slot_stride(uint32_t seg_bytes);
+hipError_t launch_zstd_seg_concat(hipStream_t s, uint64_t n_blocks, uint32_t nseg, uint32_t seg_bytes, const uint8_t *d_seg,
+                                  const uint32_t *d_seg_size, uint32_t *d_seg_off, const uint8_t *head, uint32_t head_len,
+                                  uint32_t bound, uint8_t *d_dst, uint64_t dst_stride, uint32_t *d_out_size, int32_t *d_status);
+
 } // namespace cryo
 
 #define CRYO_WAVE 64

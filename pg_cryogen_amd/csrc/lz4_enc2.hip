@@ -153,22 +153,34 @@ __device__ unsigned long long g_lz4e_prof[16];
 #define LZT(k) do { } while (0)
 #endif
 
-template <uint32_t kW, int PB, bool TG>
+/* SEG (the segment-parallel mode, CRYO_OPT_ENCODE_SEGMENT_BYTES; lz4_enc_seg.hip stitches its output): workgroup x encodes
+ * segment x % nseg of block x / nseg -- positions [s0, s1), s0 = segment * seg_bytes -- into its own slot of dst_base
+ * (dst_stride apart), and records (out_size[x], seg_rec[x]) = (bytes written, {start of the trailing literal run's token,
+ * the run's first position}).  The table is seeded with positions before s0 (kSegSeedBytes back, every kSegSeedStride-th),
+ * so that matches reach into earlier segments; an interior segment's matches end at or before s1, and only the last one
+ * keeps the block's end rules.  Positions stay block-relative.  !SEG: the byte-identical encoder, one block per workgroup. */
+constexpr uint32_t kSegSeedBytes = 16384, kSegSeedStride = 2;
+
+template <uint32_t kW, int PB, bool TG, bool SEG>
 __global__ void __launch_bounds__(64)
 k_lz4_enc2(const uint8_t *__restrict__ src_base, uint64_t src_stride, uint32_t n, uint64_t n_blocks,
            uint8_t *__restrict__ dst_base, uint64_t dst_stride, int accel_in,
-           uint32_t *__restrict__ out_size, int32_t *__restrict__ status, uint32_t dbg)
+           uint32_t *__restrict__ out_size, int32_t *__restrict__ status, uint32_t dbg,
+           uint32_t seg_bytes = 0, uint32_t nseg = 1, uint2 *__restrict__ seg_rec = nullptr)
 {
     constexpr uint32_t kStage = kW >= 2048u ? kEncStage : kW / 2u; /* the ring's refill: half of it at most */
     __shared__ __attribute__((aligned(16))) EncLds<kW, PB, TG> L;
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t blk = blockIdx.x;
+    const uint64_t item = blockIdx.x; /* SEG: (block, segment); else the block */
+    const uint64_t blk = SEG ? item / nseg : item;
     if (blk >= n_blocks) return;
+    const uint32_t s0 = SEG ? (uint32_t)(item - blk * nseg) * seg_bytes : 0u;
+    const uint32_t s1 = SEG ? (n - s0 > seg_bytes ? s0 + seg_bytes : n) : n; /* end of the positions this workgroup encodes */
 
     Enc<kW, kStage, PB, TG> e;
     using E = Enc<kW, kStage, PB, TG>;
     e.L = &L;
-    e.dst = dst_base + uni64(blk * dst_stride);
+    e.dst = dst_base + uni64(item * dst_stride);
     e.op = 0;
     const uint32_t accel = accel_in < 1 ? 1u : (accel_in > 65537 ? 65537u : (uint32_t)accel_in);
     const uint8_t *src = src_base + uni64(blk * src_stride);
@@ -185,16 +197,47 @@ k_lz4_enc2(const uint8_t *__restrict__ src_base, uint64_t src_stride, uint32_t n
         for (uint32_t i = lane; i < sizeof(L.thi) / 16u; i += 64u) reinterpret_cast<uint4 *>(L.thi)[i] = make_uint4(0, 0, 0, 0);
     }
     e.open(L.win, src, n, lane);
-    e.ensure(kW);
+    if (SEG && s0) e.reopen(s0);
+    e.ensure((SEG ? s0 & ~(kStage - 1u) : 0u) + kW);
     __builtin_amdgcn_wave_barrier();
     /* the owner marks (in the byte plane, or -- packed high bits -- in the low halves): every access is one the wave really
      * makes (explicit LDS pointers: a volatile generic one becomes FLAT accesses with a wait behind each) */
     volatile __attribute__((address_space(3))) uint8_t *vthi = (volatile __attribute__((address_space(3))) uint8_t *)L.thi;
     volatile __attribute__((address_space(3))) uint16_t *vtlo = (volatile __attribute__((address_space(3))) uint16_t *)L.tlo;
     constexpr bool kByteMarks = TG || PB == 8;
+    if constexpr (SEG) {
+        /* seed the table with positions of the earlier segments, ascending, 64 per round; of the lanes of a round that share a
+         * slot the highest (latest position) writes it, as a serial walk would leave it */
+        const uint32_t from = s0 > kSegSeedBytes ? s0 - kSegSeedBytes : 0u;
+        for (uint32_t p0 = from; p0 < s0; p0 += 64u * kSegSeedStride) {
+            const uint32_t p = p0 + lane * kSegSeedStride;
+            const bool valid = p < s0 && p + 8u <= n;
+            uint32_t h = 0, v4 = 0;
+            if (valid) {
+                uint64_t v;
+                __builtin_memcpy(&v, src + p, 8);
+                v4 = (uint32_t)v;
+                const uint32_t x_lo = v4 << 24, x_hi = (v4 >> 8) | ((uint32_t)(v >> 32) << 24);
+                h = (__umulhi(x_lo, 0x1BBCDCBBu) + x_lo * 0xCFu + x_hi * 0x1BBCDCBBu) >> 20; /* Enc::hash */
+                vtlo[h] = (uint16_t)(0xFF00u | lane);
+            }
+            __builtin_amdgcn_wave_barrier();
+            bool w = valid && vtlo[h] == (uint16_t)(0xFF00u | lane);
+            __builtin_amdgcn_wave_barrier();
+            unsigned long long losers = __ballot(valid && !w);
+            while (losers) {
+                const uint32_t hj = lane_get(h, ctz64(losers));
+                const unsigned long long G = __ballot(valid && h == hj);
+                if ((G >> lane) & 1ull) w = lane == 63u - (uint32_t)__builtin_clzll(G);
+                losers &= ~G;
+            }
+            if (w) e.tab_put(h, p, E::tag_of(v4));
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
 
     const unsigned long long lt_mask = lane ? (~0ull >> (64u - lane)) : 0ull; /* lanes below this one */
-    uint32_t anchor = 0;
+    uint32_t anchor = s0;
 #ifdef CRYO_LZ4E_PROF
     unsigned long long pt[8] = {0}, t0 = __builtin_amdgcn_s_memtime(), nseq_p = 0, nbatch_p = 0;
 #endif
@@ -313,10 +356,12 @@ k_lz4_enc2(const uint8_t *__restrict__ src_base, uint64_t src_stride, uint32_t n
     };
 
     if (n >= kMinLength) {
-        const uint32_t mflimit_p1 = n - kMfLimit + 1u;
-        const uint32_t matchlimit = n - kLastLiterals;
+        /* SEG: an interior segment's last probe is s1 - 4 (a match's first four bytes lie inside it) and its matches end at
+         * s1 at the latest; the block's own limits hold for every segment */
+        const uint32_t mflimit_p1 = SEG && s1 - 3u < n - kMfLimit + 1u ? s1 - 3u : n - kMfLimit + 1u;
+        const uint32_t matchlimit = SEG && s1 < n - kLastLiterals ? s1 : n - kLastLiterals;
         /* position 0 goes into the table as index 0: the table is zero already */
-        uint32_t ip = 1;
+        uint32_t ip = s0 ? s0 : 1u;
         bool done = false, pre = false; /* pre: a match just ended at ip (table update at ip-2 and re-test at ip pending) */
         uint32_t fwd = ip, step = 1, nb = accel << kSkipTrigger;
         while (!done) {
@@ -447,7 +492,10 @@ k_lz4_enc2(const uint8_t *__restrict__ src_base, uint64_t src_stride, uint32_t n
                         /* a long match on a far candidate: the next 64 bytes are on their way while the probes are committed */
                         if (fq == 8u && !(dbg & 2u)) {
                             have_win = true;
-                            wf = src[lane_get(cand, K - 1u) + 12u + lane]; /* below ip + 12 + lane: a far candidate lies a ring's length back */
+                            /* below ip + 12 + lane: a far candidate lies a ring's length back (SEG: a seeded one may lie just
+                             * before the ring's floor, so the block's end bounds the read) */
+                            const uint32_t wp = lane_get(cand, K - 1u) + 12u + lane;
+                            wf = !SEG || wp < n ? src[wp] : 0u;
                         }
                     } else fq = lane_get(fq_near, K - 1u);
                 }
@@ -539,15 +587,18 @@ k_lz4_enc2(const uint8_t *__restrict__ src_base, uint64_t src_stride, uint32_t n
     }
     if (qn) { emit_queue(); qn = 0; }
     /* ================= last literals ================= */
+    const uint32_t tail = e.op;
     {
-        const uint32_t lit = n - anchor;
+        const uint32_t lit = s1 - anchor;
         if (lane == 0) e.dst[e.op] = (uint8_t)((lit < 15u ? lit : 15u) << 4);
         e.op++;
         if (lit >= 15u) e.put_len(lit - 15u);
-        e.ensure(n);
+        e.ensure(s1);
         e.put_literals(anchor, lit);
     }
-    if (lane == 0) { out_size[blk] = e.op; status[blk] = CRYO_ST_OK; }
+    if constexpr (SEG) {
+        if (lane == 0) { out_size[item] = e.op; seg_rec[item] = make_uint2(tail, anchor); }
+    } else if (lane == 0) { out_size[blk] = e.op; status[blk] = CRYO_ST_OK; }
 #ifdef CRYO_LZ4E_PROF
     if (lane == 0) { for (int k = 0; k < 7; k++) atomicAdd(&g_lz4e_prof[k], pt[k]); atomicAdd(&g_lz4e_prof[8], nseq_p); atomicAdd(&g_lz4e_prof[9], nbatch_p); }
 #endif
@@ -562,23 +613,23 @@ hipError_t launch_lz4_compress_batch64(hipStream_t s, const uint8_t *d_src, uint
     static const int wkb = cryo_tuning_env("CRYO_LZ4_ENC_WINDOW") ? atoi(cryo_tuning_env("CRYO_LZ4_ENC_WINDOW")) : 2; /* KiB; tuning aid */
     const dim3 grid((uint32_t)n_blocks), wg(64);
     if (wkb >= 64)
-        hipLaunchKernelGGL((k_lz4_enc2<65536, 8, true>), grid, wg, 0, s, d_src, src_stride, block_size, n_blocks, d_dst, dst_stride,
+        hipLaunchKernelGGL((k_lz4_enc2<65536, 8, true, false>), grid, wg, 0, s, d_src, src_stride, block_size, n_blocks, d_dst, dst_stride,
                            accel, d_out_size, d_status, dbg);
     else if (wkb >= 32)
-        hipLaunchKernelGGL((k_lz4_enc2<32768, 8, true>), grid, wg, 0, s, d_src, src_stride, block_size, n_blocks, d_dst, dst_stride,
+        hipLaunchKernelGGL((k_lz4_enc2<32768, 8, true, false>), grid, wg, 0, s, d_src, src_stride, block_size, n_blocks, d_dst, dst_stride,
                            accel, d_out_size, d_status, dbg);
     else if (wkb >= 16)
-        hipLaunchKernelGGL((k_lz4_enc2<16384, 8, true>), grid, wg, 0, s, d_src, src_stride, block_size, n_blocks, d_dst, dst_stride,
+        hipLaunchKernelGGL((k_lz4_enc2<16384, 8, true, false>), grid, wg, 0, s, d_src, src_stride, block_size, n_blocks, d_dst, dst_stride,
                            accel, d_out_size, d_status, dbg);
     else if (wkb >= 8)
-        hipLaunchKernelGGL((k_lz4_enc2<8192, 8, true>), grid, wg, 0, s, d_src, src_stride, block_size, n_blocks, d_dst, dst_stride,
+        hipLaunchKernelGGL((k_lz4_enc2<8192, 8, true, false>), grid, wg, 0, s, d_src, src_stride, block_size, n_blocks, d_dst, dst_stride,
                            accel, d_out_size, d_status, dbg);
     else if (wkb >= 4)
-        hipLaunchKernelGGL((k_lz4_enc2<4096, 8, true>), grid, wg, 0, s, d_src, src_stride, block_size, n_blocks, d_dst, dst_stride,
+        hipLaunchKernelGGL((k_lz4_enc2<4096, 8, true, false>), grid, wg, 0, s, d_src, src_stride, block_size, n_blocks, d_dst, dst_stride,
                            accel, d_out_size, d_status, dbg);
     else {
         /* 1 KiB ring; tags (12 workgroups per CU at 128 KiB) or packed high bits without tags (16 per CU): tuning aid CRYO_LZ4_ENC_TAGS */
-#define LZ4E_LAUNCH(KW, PBV, TGV) hipLaunchKernelGGL((k_lz4_enc2<KW, PBV, TGV>), grid, wg, 0, s, d_src, src_stride, block_size, n_blocks, d_dst, dst_stride, accel, d_out_size, d_status, dbg)
+#define LZ4E_LAUNCH(KW, PBV, TGV) hipLaunchKernelGGL((k_lz4_enc2<KW, PBV, TGV, false>), grid, wg, 0, s, d_src, src_stride, block_size, n_blocks, d_dst, dst_stride, accel, d_out_size, d_status, dbg)
         static const int tags_env = cryo_tuning_env("CRYO_LZ4_ENC_TAGS") ? atoi(cryo_tuning_env("CRYO_LZ4_ENC_TAGS")) : -1;
         const bool tags = tags_env >= 0 ? tags_env != 0 : kLz4EncTagsDefault;
         const bool ring2k = wkb >= 2 && cryo_tuning_env("CRYO_LZ4_ENC_WINDOW") != nullptr;
@@ -602,6 +653,26 @@ hipError_t launch_lz4_compress_batch64(hipStream_t s, const uint8_t *d_src, uint
         (void)hipMemcpyToSymbol(HIP_SYMBOL(g_lz4e_prof), z, sizeof z);
     }
 #endif
+    return hipGetLastError();
+}
+
+/* the segment pass of lz4_enc_seg.hip: n_blocks * nseg workgroups, the ring and table layout of the identical path's default */
+hipError_t launch_lz4_enc_segments(hipStream_t s, const uint8_t *d_src, uint64_t src_stride, uint32_t block_size,
+                                   uint64_t n_blocks, uint32_t seg_bytes, uint32_t nseg, uint8_t *d_seg, uint64_t seg_stride,
+                                   int accel, uint32_t *d_seg_size, uint2 *d_seg_rec)
+{
+    const uint64_t items = n_blocks * nseg;
+    if (items > 0x7fffffffull) return hipErrorInvalidValue;
+    const dim3 grid((uint32_t)items), wg(64);
+    if (block_size <= (128u << 10))
+        hipLaunchKernelGGL((k_lz4_enc2<1024, 1, false, true>), grid, wg, 0, s, d_src, src_stride, block_size, n_blocks, d_seg, seg_stride,
+                           accel, d_seg_size, nullptr, 0u, seg_bytes, nseg, d_seg_rec);
+    else if (block_size <= (1u << 20))
+        hipLaunchKernelGGL((k_lz4_enc2<1024, 4, false, true>), grid, wg, 0, s, d_src, src_stride, block_size, n_blocks, d_seg, seg_stride,
+                           accel, d_seg_size, nullptr, 0u, seg_bytes, nseg, d_seg_rec);
+    else
+        hipLaunchKernelGGL((k_lz4_enc2<2048, 8, true, true>), grid, wg, 0, s, d_src, src_stride, block_size, n_blocks, d_seg, seg_stride,
+                           accel, d_seg_size, nullptr, 0u, seg_bytes, nseg, d_seg_rec);
     return hipGetLastError();
 }
 

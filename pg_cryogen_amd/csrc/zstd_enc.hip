@@ -42,6 +42,8 @@ constexpr uint32_t kZBlk = 128u << 10;
 constexpr uint32_t kMaxSeq = kZBlk / 3u + 8u;
 constexpr uint32_t kMaxLL = 35, kMaxML = 52, kMaxOff = 31, kDefMaxOff = 28;
 constexpr int kHufLogMaxE = 12;
+/* segment mode: positions before a segment that go into its table (the last kZSegSeedBytes, every kZSegSeedStride-th) */
+constexpr uint32_t kZSegSeedBytes = 16384, kZSegSeedStride = 2;
 
 /* per-workgroup global workspace layout */
 constexpr size_t kWsSeq = 0;                                   /* uint2 {off, ll | ml<<16} x kMaxSeq */
@@ -1238,7 +1240,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4)))
 k_zstd_enc(const uint8_t *__restrict__ src_base, uint64_t src_stride, uint32_t n, uint64_t n_blocks,
            uint8_t *__restrict__ dst_base, uint64_t dst_stride, int wlog, int hlog, int clog, int mml, int tlen,
            int finder, uint32_t width, uint32_t *__restrict__ out_size, int32_t *__restrict__ status,
-           uint8_t *workspace, uint64_t ws_stride, unsigned long long *stats)
+           uint8_t *workspace, uint64_t ws_stride, unsigned long long *stats, uint32_t seg_bytes = 0, uint32_t nseg = 1)
 {
     __shared__ __attribute__((aligned(16))) EncLds L;
     /* the finders' mark array lies over the entropy stage's scratch (histogram + tree nodes: dead while a finder runs) */
@@ -1261,17 +1263,59 @@ k_zstd_enc(const uint8_t *__restrict__ src_base, uint64_t src_stride, uint32_t n
     uint2 *opt_matches = reinterpret_cast<uint2 *>(reinterpret_cast<uint8_t *>(opt_tab) + kOptTabBytes);
     uint32_t *opt_saved = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(opt_matches) + kOptMatchBytes);
 
-    for (uint64_t blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {
+    /* segment mode (seg_bytes != 0, `fast` only; enc_seg.hip): work item x is segment x % nseg of block x / nseg, encoded as
+     * ONE zstd block (last-block bit only on the block's final segment) into slot x of dst_base, without a frame header; it
+     * starts as the first block of a frame does (no previous Huffman / FSE tables: none are repeated) but with no repeat
+     * offsets (0 disables them until the block's own raw offsets set them), and the table is seeded with positions before
+     * the segment, so that matches reach into the earlier ones */
+    const bool seg = seg_bytes != 0u;
+    const uint64_t n_items = seg ? n_blocks * nseg : n_blocks;
+    for (uint64_t item = blockIdx.x; item < n_items; item += gridDim.x) {
+        const uint64_t blk = seg ? item / nseg : item;
+        const uint32_t s0 = seg ? (uint32_t)(item - blk * nseg) * seg_bytes : 0u;
+        const uint32_t s1 = seg && n - s0 > seg_bytes ? s0 + seg_bytes : n;
         const uint8_t *src = src_base + blk * src_stride;
-        uint8_t *dst = dst_base + blk * dst_stride;
+        uint8_t *dst = dst_base + item * dst_stride;
         {
             const uint32_t quads = ((1u << hlog) + (two_tables ? 1u << clog : 0u) + (hlog3 ? 1u << hlog3 : 0u)) / 4u;
             for (uint32_t i = lane; i < quads; i += 64u) reinterpret_cast<uint4 *>(table)[i] = make_uint4(0, 0, 0, 0);
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        uint32_t op;
-        {
+        if (seg && s0) {
+            /* entries as block_fast_gbatch writes them (index = position + 1, the tag above the index bits), ascending, 64 per
+             * round; of the lanes of a round that share a slot the highest writes it (marks in the finder's LDS array) */
+            const int mls = mml < 4 ? 4 : (mml > 7 ? 7 : mml);
+            const uint32_t ib = (uint32_t)cp.ib, im = (1u << ib) - 1u;
+            volatile uint8_t *vmark = df_mark;
+            const uint32_t from = s0 > kZSegSeedBytes ? s0 - kZSegSeedBytes : 0u;
+            for (uint32_t p0 = from; p0 < s0; p0 += 64u * kZSegSeedStride) {
+                const uint32_t p = p0 + lane * kZSegSeedStride;
+                const bool valid = p < s0 && p + 8u <= n;
+                uint32_t h = 0, ent = 0;
+                if (valid) {
+                    const uint64_t v = ld64v(src + p);
+                    h = hashs_v(v, hlog, mls);
+                    ent = ((p + 1u) & im) | ((fast_tag((uint32_t)v) >> ib) << ib);
+                    vmark[h & (kDfMark - 1u)] = (uint8_t)lane;
+                }
+                __builtin_amdgcn_wave_barrier();
+                bool w = valid && vmark[h & (kDfMark - 1u)] == (uint8_t)lane;
+                __builtin_amdgcn_wave_barrier();
+                unsigned long long losers = __ballot(valid && !w);
+                while (losers) {
+                    const uint32_t hj = lane_get(h, ctz64(losers));
+                    const unsigned long long G = __ballot(valid && h == hj);
+                    if ((G >> lane) & 1ull) w = lane == 63u - (uint32_t)__builtin_clzll(G);
+                    losers &= ~G;
+                }
+                if (w) table[h] = ent;
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        }
+        uint32_t op = 0;
+        if (!seg) {
             const uint64_t wsize = 1ull << wlog;
             const uint32_t single = wsize >= n ? 1u : 0u;
             const uint32_t fcs = (n >= 256u) + (n >= 65536u + 256u);
@@ -1286,6 +1330,7 @@ k_zstd_enc(const uint8_t *__restrict__ src_base, uint64_t src_stride, uint32_t n
             else { if (lane == 0) { dst[op] = (uint8_t)n; dst[op + 1] = (uint8_t)(n >> 8); dst[op + 2] = (uint8_t)(n >> 16); dst[op + 3] = (uint8_t)(n >> 24); } op += 4; }
         }
         uint32_t rep[3] = {1, 4, 8};
+        if (seg) rep[0] = rep[1] = rep[2] = 0;
         uint32_t dict_limit = 1;
         const uint8_t *base = src - 1; /* moves once for btultra2 (below) */
         bool first = true;
@@ -1299,9 +1344,9 @@ k_zstd_enc(const uint8_t *__restrict__ src_base, uint64_t src_stride, uint32_t n
         SeqTabs tb;
         tb.prev = reinterpret_cast<FseCt *>(ws + kWsTabs);
         tb.rep[0] = tb.rep[1] = tb.rep[2] = 0;
-        uint32_t ip = 0;
-        while (ip < n) {
-            const uint32_t bs = (n - ip < kZBlk) ? n - ip : kZBlk;
+        uint32_t ip = s0;
+        while (ip < s1) {
+            const uint32_t bs = (s1 - ip < kZBlk) ? s1 - ip : kZBlk;
             const uint32_t last = (ip + bs == n) ? 1u : 0u;
             uint32_t csize = 0;
             /* window.dictLimit stays 1 for the whole frame (libzstd 1.4.8: ZSTD_compress_frameChunk only checks
@@ -1406,7 +1451,8 @@ k_zstd_enc(const uint8_t *__restrict__ src_base, uint64_t src_stride, uint32_t n
             first = false;
             __builtin_amdgcn_wave_barrier();
         }
-        if (lane == 0) { out_size[blk] = op; status[blk] = CRYO_ST_OK; }
+        if (seg) { if (lane == 0) out_size[item] = op; }
+        else if (lane == 0) { out_size[blk] = op; status[blk] = CRYO_ST_OK; }
         __builtin_amdgcn_wave_barrier();
     }
     if (PROF && stats && lane == 0) {
@@ -1490,6 +1536,67 @@ bool zstd_compress_supported(int level, uint32_t block_size)
 {
     int a, b, c, d;
     return zstd_fast_cparams(level, block_size, &a, &b, &c, &d);
+}
+
+/* ---- segment-parallel encode (CRYO_OPT_ENCODE_SEGMENT_BYTES): strategy `fast` only, enc_seg.hip concatenates ---- */
+bool zstd_segment_supported(int level, uint32_t block_size)
+{
+    int wlog, hlog, mml, tlen, clog, strategy = 0;
+    return zstd_fast_cparams(level, block_size, &wlog, &hlog, &mml, &tlen, &clog, nullptr, &strategy) && strategy == 1;
+}
+static size_t zstd_seg_enc_bytes(uint64_t items, int level, uint32_t block_size)
+{
+    int wlog, hlog, mml, tlen, clog;
+    if (!zstd_fast_cparams(level, block_size, &wlog, &hlog, &mml, &tlen, &clog)) return 0;
+    const size_t stride = zstd_enc_stride(hlog, clog, false);
+    return ((size_t)zstd_enc_grid(items, stride) * stride + 255u) & ~(size_t)255u;
+}
+size_t zstd_compress_segmented_workspace(uint64_t n_blocks, int level, uint32_t block_size, uint32_t seg_bytes)
+{
+    const uint64_t items = n_blocks * enc_seg_count(block_size, seg_bytes);
+    return zstd_seg_enc_bytes(items, level, block_size) + zstd_seg_scratch_bytes(items, seg_bytes);
+}
+hipError_t launch_zstd_compress_segmented(hipStream_t s, const uint8_t *d_src, uint64_t src_stride, uint32_t block_size,
+                                          uint64_t n_blocks, uint8_t *d_dst, uint64_t dst_stride, int level, uint32_t seg_bytes,
+                                          uint32_t *d_out_size, int32_t *d_status, void *d_workspace, size_t workspace_bytes)
+{
+    if (n_blocks == 0) return hipSuccess;
+    int wlog, hlog, mml, tlen, clog, strategy = 0;
+    if (!zstd_fast_cparams(level, block_size, &wlog, &hlog, &mml, &tlen, &clog, nullptr, &strategy) || strategy != 1)
+        return hipErrorNotSupported;
+    const uint32_t nseg = enc_seg_count(block_size, seg_bytes);
+    const uint64_t items = n_blocks * nseg;
+    if (items > 0x7fffffffull) return hipErrorInvalidValue;
+    const size_t stride = zstd_enc_stride(hlog, clog, false);
+    const uint32_t grid = zstd_enc_grid(items, stride);
+    const size_t enc_bytes = zstd_seg_enc_bytes(items, level, block_size);
+    if (workspace_bytes < enc_bytes + zstd_seg_scratch_bytes(items, seg_bytes)) return hipErrorInvalidValue;
+    uint8_t *ws = (uint8_t *)d_workspace;
+    uint8_t *d_seg = ws + enc_bytes;
+    const uint64_t slot = zstd_seg_slot_stride(seg_bytes);
+    uint32_t *d_seg_size = (uint32_t *)(d_seg + (((size_t)items * slot + 255u) & ~(size_t)255u));
+    uint32_t *d_seg_off = d_seg_size + (((size_t)items * 4u + 255u) & ~(size_t)255u) / 4u;
+    hipLaunchKernelGGL((k_zstd_enc<false, false>), dim3(grid), dim3(64), 0, s, d_src, src_stride, block_size, n_blocks, d_seg, slot, wlog,
+                       hlog, clog, mml, tlen, 0, 16u, d_seg_size, d_status, ws, (uint64_t)stride, nullptr, seg_bytes, nseg);
+    /* the frame header of the byte-identical path (k_zstd_enc): content size, no checksum */
+    uint8_t head[16];
+    uint32_t hl = 0;
+    {
+        const uint32_t n = block_size;
+        const uint32_t single = (1ull << wlog) >= n ? 1u : 0u;
+        const uint32_t fcs = (n >= 256u) + (n >= 65536u + 256u);
+        head[0] = 0x28; head[1] = 0xB5; head[2] = 0x2F; head[3] = 0xFD;
+        head[4] = (uint8_t)((single << 5) + (fcs << 6));
+        hl = 5;
+        if (!single) head[hl++] = (uint8_t)((wlog - 10) << 3);
+        if (fcs == 0u) { if (single) head[hl++] = (uint8_t)n; }
+        else if (fcs == 1u) { head[hl++] = (uint8_t)(n - 256u); head[hl++] = (uint8_t)((n - 256u) >> 8); }
+        else { head[hl++] = (uint8_t)n; head[hl++] = (uint8_t)(n >> 8); head[hl++] = (uint8_t)(n >> 16); head[hl++] = (uint8_t)(n >> 24); }
+    }
+    const size_t b = block_size;
+    const uint32_t bound = (uint32_t)(b + (b >> 8) + (b < (128u << 10) ? ((128u << 10) - b) >> 11 : 0u));
+    return launch_zstd_seg_concat(s, n_blocks, nseg, seg_bytes, d_seg, d_seg_size, d_seg_off, head, hl, bound, d_dst, dst_stride,
+                                  d_out_size, d_status);
 }
 
 hipError_t launch_zstd_compress(hipStream_t s, const uint8_t *d_src, uint64_t src_stride, uint32_t block_size,

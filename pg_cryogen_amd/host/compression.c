@@ -30,6 +30,7 @@ int cryo_gpu_device_guc = 0;
 int cryo_gpu_count_guc = 1;
 int cryo_gpu_pool_mb_guc = 0;
 int cryo_gpu_workspace_keep_mb_guc = 1024; /* device workspace a backend keeps between calls (-1: everything) */
+int cryo_gpu_encode_segment_kb_guc = 0;    /* segment-parallel encode, KiB (0: the byte-identical encoders) */
 int cryo_gpu_readahead_blocks_guc = 8;    /* cryo blocks a sequential scan's cache miss decodes with one codec call (1: only the block asked for) */
 Size cryo_blcksz = (Size)1 << 20; /* CRYO_BLCKSZ, reference storage.h:18 */
 
@@ -38,7 +39,7 @@ Size cryo_blcksz = (Size)1 << 20; /* CRYO_BLCKSZ, reference storage.h:18 */
  * device numbers, wrapping).  With more than one, the K-block calls of the staging and cache code go through the
  * dispatcher of include/cryo_codec.h (block i of a call -> GPU i mod G, one host thread per GPU). */
 static cryo_multi *hip_multi;
-static int hip_multi_first = -1, hip_multi_count = 0, hip_pool_mb = 0, hip_keep_mb = -2;
+static int hip_multi_first = -1, hip_multi_count = 0, hip_pool_mb = 0, hip_keep_mb = -2, hip_seg_kb = 0;
 /* A failed open is remembered until the GUCs change -- for good when the machine has no GPU (deterministic), for
  * CRYO_OPEN_RETRY_SECONDS when devices exist but cryo_multi_open failed (out of device memory, a busy device: transient;
  * a pooled backend must not refuse every cryo table for the rest of its life because of one bad moment). */
@@ -121,6 +122,7 @@ const CryoCodecOps *cryo_host_codec_ops(void)
         hip_multi_count = cryo_gpu_count_guc;
         hip_pool_mb = 0;
         hip_keep_mb = -2;
+        hip_seg_kb = 0;
         hip_ops.ctx = hip_multi;
     }
     if (hip_keep_mb != cryo_gpu_workspace_keep_mb_guc) { /* a backend is long-lived: one large call must not pin its workspace for good */
@@ -130,6 +132,10 @@ const CryoCodecOps *cryo_host_codec_ops(void)
     if (hip_pool_mb != cryo_gpu_pool_mb_guc) { /* the GUC changed: resize (0 frees the pool) */
         hip_pool_mb = cryo_gpu_pool_mb_guc;
         (void)cryo_multi_set_option(hip_multi, CRYO_OPT_POOL_BYTES, (int64_t)(hip_pool_mb < 0 ? 0 : hip_pool_mb) << 20);
+    }
+    if (hip_seg_kb != cryo_gpu_encode_segment_kb_guc && cryo_encode_segment_kb_valid(cryo_gpu_encode_segment_kb_guc)) {
+        hip_seg_kb = cryo_gpu_encode_segment_kb_guc; /* a value the option refuses is never stored: the encoders stay as they are */
+        (void)cryo_multi_set_option(hip_multi, CRYO_OPT_ENCODE_SEGMENT_BYTES, (int64_t)hip_seg_kb << 10);
     }
     return &hip_ops;
 }
@@ -168,6 +174,20 @@ void cryo_host_codec_trim(void)
 }
 
 /* ---------------- GUCs ---------------- */
+/* pg_cryogen.gpu_encode_segment_kb: 0, or a power of two from 4 to 128 (CRYO_OPT_ENCODE_SEGMENT_BYTES) */
+int cryo_encode_segment_kb_valid(int kb)
+{
+    return kb == 0 || (kb >= 4 && kb <= 128 && (kb & (kb - 1)) == 0);
+}
+#ifdef CRYO_HAVE_POSTGRES
+static bool check_encode_segment_kb(int *newval, void **extra, GucSource source)
+{
+    (void)extra;
+    (void)source;
+    return cryo_encode_segment_kb_valid(*newval) != 0; /* false: "invalid value for parameter" */
+}
+#endif
+
 void cryo_define_compression_gucs(void)
 {
 #ifdef CRYO_HAVE_POSTGRES
@@ -191,6 +211,12 @@ void cryo_define_compression_gucs(void)
     DefineCustomIntVariable("pg_cryogen.gpu_readahead_blocks",
                             "Cryo blocks a sequential scan's cache miss decodes with one codec call (1 = only the block asked for).",
                             NULL, &cryo_gpu_readahead_blocks_guc, 8, 1, 64, PGC_USERSET, 0, NULL, NULL, NULL);
+    DefineCustomIntVariable("pg_cryogen.gpu_encode_segment_kb",
+                            "Segment size (KiB) of the segment-parallel GPU encoders: each segment of a block gets its own wave "
+                            "(0 = the encoders whose output equals liblz4's / libzstd's; 4 .. 128, a power of two = valid streams "
+                            "the stock libraries decode, but not byte-identical to theirs).",
+                            NULL, &cryo_gpu_encode_segment_kb_guc, 0, 0, 128, PGC_USERSET, 0, check_encode_segment_kb,
+                            NULL, NULL);
 #else
     /* no GUC machinery without PostgreSQL: the variables keep the reference's defaults */
     compression_method_guc = COMP_ZSTD;
