@@ -76,6 +76,19 @@ class Oracle:
         return d[:r].copy()
 
 
+class _ZstdBounds(C.Structure):
+    _fields_ = [("error", C.c_size_t), ("lowerBound", C.c_int), ("upperBound", C.c_int)]
+
+
+# ZSTD_cParameter numbers of zstd.h (1.4.x) and the bounds libzstd 1.4.8 reports for them on a 64-bit build
+ZSTD_C_COMPRESSION_LEVEL, ZSTD_C_WINDOWLOG, ZSTD_C_MINMATCH = 100, 101, 105
+ZSTD_C_ENABLE_LDM, ZSTD_C_CONTENTSIZE_FLAG, ZSTD_C_CHECKSUM_FLAG = 160, 200, 201
+ZSTD_C_LITERAL_COMPRESSION_MODE, ZSTD_C_TARGET_CBLOCK_SIZE = 1002, 1003
+ZSTD_PARAM_BOUNDS = {ZSTD_C_WINDOWLOG: (10, 31), ZSTD_C_MINMATCH: (3, 7), ZSTD_C_ENABLE_LDM: (0, 1),
+                     ZSTD_C_CONTENTSIZE_FLAG: (0, 1), ZSTD_C_CHECKSUM_FLAG: (0, 1),
+                     ZSTD_C_LITERAL_COMPRESSION_MODE: (0, 2), ZSTD_C_TARGET_CBLOCK_SIZE: (64, 131072)}
+
+
 class StockLibs:
     """liblz4.so.1 / libzstd.so.1 if they can be dlopen'ed (they are base-OS packages)."""
 
@@ -101,6 +114,14 @@ class StockLibs:
             Z.ZSTD_compressBound.restype = C.c_size_t
             Z.ZSTD_compressBound.argtypes = [C.c_size_t]
             Z.ZSTD_isError.argtypes = [C.c_size_t]
+            Z.ZSTD_createCCtx.restype = C.c_void_p
+            Z.ZSTD_freeCCtx.argtypes = [C.c_void_p]
+            Z.ZSTD_CCtx_setParameter.restype = C.c_size_t
+            Z.ZSTD_CCtx_setParameter.argtypes = [C.c_void_p, C.c_int, C.c_int]
+            Z.ZSTD_compress2.restype = C.c_size_t
+            Z.ZSTD_compress2.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+            Z.ZSTD_cParam_getBounds.restype = _ZstdBounds
+            Z.ZSTD_cParam_getBounds.argtypes = [C.c_int]
             self.zstd = Z
             self.zstd_version = Z.ZSTD_versionString().decode()
         except OSError:
@@ -125,6 +146,34 @@ class StockLibs:
         d = np.empty(max(cap, 1), np.uint8)
         r = self.zstd.ZSTD_compress(d.ctypes.data, cap, a.ctypes.data, a.nbytes, level)
         assert not self.zstd.ZSTD_isError(r)
+        return d[:r].copy()
+
+    def zstd_check_param_bounds(self):
+        """the parameter numbers zstd_compress2 takes mean what this module says in the loaded library: a library with
+        other numbers or ranges fails here, loudly, instead of writing other frames"""
+        Z = self.zstd
+        for p, (lo, hi) in ZSTD_PARAM_BOUNDS.items():
+            b = Z.ZSTD_cParam_getBounds(p)
+            assert not Z.ZSTD_isError(b.error) and (b.lowerBound, b.upperBound) == (lo, hi), (p, b.lowerBound, b.upperBound)
+        b = Z.ZSTD_cParam_getBounds(ZSTD_C_COMPRESSION_LEVEL)
+        assert not Z.ZSTD_isError(b.error) and b.lowerBound < -5 and b.upperBound == 22, (b.lowerBound, b.upperBound)
+
+    def zstd_compress2(self, a, params):
+        """ZSTD_compress2 with {ZSTD_cParameter: value} set on a fresh context; None when the library refuses"""
+        Z = self.zstd
+        a = np.ascontiguousarray(a, dtype=np.uint8)
+        cap = Z.ZSTD_compressBound(a.nbytes)
+        d = np.empty(max(cap, 1), np.uint8)
+        cctx = Z.ZSTD_createCCtx()
+        assert cctx
+        try:
+            for p, v in params.items():
+                assert not Z.ZSTD_isError(Z.ZSTD_CCtx_setParameter(cctx, p, v)), (p, v)
+            r = Z.ZSTD_compress2(cctx, d.ctypes.data, cap, a.ctypes.data, a.nbytes)
+        finally:
+            Z.ZSTD_freeCCtx(cctx)
+        if Z.ZSTD_isError(r):
+            return None
         return d[:r].copy()
 
     def zstd_decompress(self, c, cap, fill=0):
