@@ -99,13 +99,23 @@ typedef enum {
     /* segment-parallel encode, for calls of few blocks (the access method's write path hands over one block per call):
      * 0 (default) = the byte-identical encoders; a power of two S from 4 096 to 131 072 = every block of more than S bytes
      * is cut into ceil(B / S) segments, each encoded by its own wave (LZ4: any acceleration, blocks up to 16 MiB; zstd: the
-     * `fast` strategy, levels -5 .. 2 -- other levels, and blocks of at most S bytes, take the byte-identical path).  The
+     * levels whose strategy is at most CRYO_OPT_ENCODE_SEGMENT_ZSTD_STRATEGY -- by default `fast`, levels -5 .. 2 -- other
+     * levels, and blocks of at most S bytes, take the byte-identical path).  The
      * result is ONE valid LZ4 block / ONE zstd frame per cryo block (matches reach back into earlier segments; a zstd frame
      * holds ceil(B / S) blocks, each with its own entropy tables) that liblz4 1.9.3 / libzstd 1.4.8 decode to the input,
      * of at most cryo_codec_bound() bytes, and deterministic -- the same bytes for the same block whatever the call or the
      * batch -- but NOT the libraries' own output.  Applies to every compress entry point (cryo_codec_compress_batch,
      * _block, _blocks, cryo_multi_compress_blocks via cryo_multi_set_option).  Other values: CRYO_E_ARG. */
-    CRYO_OPT_ENCODE_SEGMENT_BYTES = 10
+    CRYO_OPT_ENCODE_SEGMENT_BYTES = 10,
+    /* the highest zstd strategy segment mode takes, in libzstd's ZSTD_strategy numbering: 1 = `fast` (default: exactly the
+     * behaviour before this option existed, so that levels 3 and up stay byte-identical under CRYO_OPT_ENCODE_SEGMENT_BYTES),
+     * 2 = `dfast`, 3 = `greedy`, 4 = `lazy`, 5 = `lazy2`, 6 = `btlazy2`.  By strategy, not by level: which strategy a level
+     * maps to depends on the block size (libzstd's parameter tables).  A segment of a deeper strategy is that strategy's
+     * zstd block over the segment's bytes with a seeded history of the 16 KiB before it (instead of everything before it),
+     * repeat offsets that start disabled and fresh entropy tables; the stream properties are those above.  The optimal
+     * parsers (`btopt`, `btultra`, `btultra2`: levels 13 / 16 and up) carry statistics from block to block and always take
+     * the byte-identical path.  No effect while CRYO_OPT_ENCODE_SEGMENT_BYTES is 0.  Other values: CRYO_E_ARG. */
+    CRYO_OPT_ENCODE_SEGMENT_ZSTD_STRATEGY = 11
 } cryo_option;
 int cryo_codec_set_option(cryo_codec *c, int option, int64_t value);
 /* a long-lived backend between bursts: waits for the handle's queued work, then frees its device workspace, the device and

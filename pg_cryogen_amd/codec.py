@@ -25,6 +25,7 @@ OPT_LZ4_DECODE_PATH, OPT_LZ4_INDEX_WALKERS, OPT_PIPE_MIN_BYTES, OPT_POOL_BYTES, 
 OPT_LZ4_DECODE_WAVES = 9
 OPT_WORKSPACE_KEEP_BYTES, OPT_WORKSPACE_MAX_BYTES, OPT_NUMA_LOCAL = 6, 7, 8
 OPT_ENCODE_SEGMENT_BYTES = 10  # 0 = byte-identical encoders; 4 KiB .. 128 KiB (power of two) = segment-parallel encode
+OPT_ENCODE_SEGMENT_ZSTD_STRATEGY = 11  # highest zstd strategy of segment mode: 1 fast (default) .. 6 btlazy2
 LZ4_PATH_AUTO, LZ4_PATH_RING, LZ4_PATH_INDEXED, LZ4_PATH_FEW_BLOCKS = 0, 1, 2, 3
 
 DIST_WIDE, DIST_NARROW, DIST_INT4, DIST_RANDOM, DIST_ZEROS = range(5)

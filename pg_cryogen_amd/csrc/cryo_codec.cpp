@@ -140,6 +140,7 @@ struct cryo_codec {
     bool lz4_side_failed = false; /* the optional side stream could not be created: not tried again */
     int zstd_path = 0;
     uint32_t enc_seg = 0;   /* CRYO_OPT_ENCODE_SEGMENT_BYTES: 0 = the byte-identical encoders */
+    int enc_seg_zstd_strategy = 1; /* CRYO_OPT_ENCODE_SEGMENT_ZSTD_STRATEGY: the highest zstd strategy segment mode takes */
     size_t pipe_min_bytes = (size_t)64 << 20;
     /* NUMA: the cpus of the node this GPU hangs on (sysfs local_cpulist of its PCI function, cut to what the process may
      * use); the staging workers run there and the pinned buffers are allocated from there */
@@ -533,6 +534,10 @@ int cryo_codec_set_option(cryo_codec *c, int option, int64_t value)
         if (value != 0 && (value < 4096 || value > 131072 || (value & (value - 1)) != 0)) return CRYO_E_ARG;
         c->enc_seg = (uint32_t)value;
         return CRYO_OK;
+    case CRYO_OPT_ENCODE_SEGMENT_ZSTD_STRATEGY:
+        if (value < 1 || value > 6) return CRYO_E_ARG;
+        c->enc_seg_zstd_strategy = (int)value;
+        return CRYO_OK;
     case CRYO_OPT_POOL_BYTES: {
         if (value < 0) return CRYO_E_ARG;
         DevGuard dev_(c);
@@ -559,6 +564,7 @@ int cryo_codec_get_option(const cryo_codec *c, int option, int64_t *value)
     case CRYO_OPT_WORKSPACE_MAX_BYTES: *value = (int64_t)c->ws_max; return CRYO_OK;
     case CRYO_OPT_NUMA_LOCAL: *value = c->numa_local && c->have_local_cpus ? 1 : 0; return CRYO_OK;
     case CRYO_OPT_ENCODE_SEGMENT_BYTES: *value = c->enc_seg; return CRYO_OK;
+    case CRYO_OPT_ENCODE_SEGMENT_ZSTD_STRATEGY: *value = c->enc_seg_zstd_strategy; return CRYO_OK;
     default: return CRYO_E_ARG;
     }
 }
@@ -644,8 +650,8 @@ int cryo_codec_compress_batch(cryo_codec *c, int method, int param, const void *
     if (n_blocks == 0) return CRYO_OK;
     if (!d_src || !d_dst || !d_out_size || !d_status || src_stride < block_size) return CRYO_E_ARG;
     if (dst_stride < cryo_codec_bound(method, block_size)) return CRYO_E_DSTSIZE;
-    /* segment-parallel encode: blocks of more than S bytes (LZ4 up to 16 MiB; zstd with strategy `fast`); everything else
-     * takes the byte-identical encoders below */
+    /* segment-parallel encode: blocks of more than S bytes (LZ4 up to 16 MiB; zstd with a strategy from `fast` up to the
+     * handle's CRYO_OPT_ENCODE_SEGMENT_ZSTD_STRATEGY); everything else takes the byte-identical encoders below */
     const uint32_t S = c->enc_seg;
     if (S && block_size > S && method == CRYO_METHOD_LZ4 && block_size <= (16u << 20)) {
         int rc = ensure_ws(c, cryo::lz4_compress_segmented_workspace(n_blocks, block_size, S));
@@ -653,7 +659,7 @@ int cryo_codec_compress_batch(cryo_codec *c, int method, int param, const void *
         HIP_TRY(c, cryo::launch_lz4_compress_segmented(c->stream, (const uint8_t *)d_src, src_stride, block_size, n_blocks,
                                                        (uint8_t *)d_dst, dst_stride, param, S, d_out_size, d_status, c->d_ws,
                                                        c->ws_cap));
-    } else if (S && block_size > S && method == CRYO_METHOD_ZSTD && cryo::zstd_segment_supported(param, block_size)) {
+    } else if (S && block_size > S && method == CRYO_METHOD_ZSTD && cryo::zstd_segment_supported(param, block_size, c->enc_seg_zstd_strategy)) {
         int rc = ensure_ws(c, cryo::zstd_compress_segmented_workspace(n_blocks, param, block_size, S));
         if (rc != CRYO_OK) return rc;
         HIP_TRY(c, cryo::launch_zstd_compress_segmented(c->stream, (const uint8_t *)d_src, src_stride, block_size, n_blocks,

@@ -159,7 +159,8 @@ size_t lz4_compress_segmented_workspace(uint64_t n_blocks, uint32_t block_size, 
 hipError_t launch_lz4_compress_segmented(hipStream_t s, const uint8_t *d_src, uint64_t src_stride, uint32_t block_size,
                                          uint64_t n_blocks, uint8_t *d_dst, uint64_t dst_stride, int accel, uint32_t seg_bytes,
                                          uint32_t *d_out_size, int32_t *d_status, void *d_ws, size_t ws_bytes);
-bool zstd_segment_supported(int level, uint32_t block_size); /* strategy `fast` (levels -5 .. 2 at cryo block sizes) */
+/* the level's strategy lies in 1 (`fast`) .. max_strategy (at most 6, `btlazy2`; CRYO_OPT_ENCODE_SEGMENT_ZSTD_STRATEGY) */
+bool zstd_segment_supported(int level, uint32_t block_size, int max_strategy);
 size_t zstd_compress_segmented_workspace(uint64_t n_blocks, int level, uint32_t block_size, uint32_t seg_bytes);
 hipError_t launch_zstd_compress_segmented(hipStream_t s, const uint8_t *d_src, uint64_t src_stride, uint32_t block_size,
                                           uint64_t n_blocks, uint8_t *d_dst, uint64_t dst_stride, int level, uint32_t seg_bytes,

@@ -44,6 +44,9 @@ constexpr uint32_t kMaxLL = 35, kMaxML = 52, kMaxOff = 31, kDefMaxOff = 28;
 constexpr int kHufLogMaxE = 12;
 /* segment mode: positions before a segment that go into its table (the last kZSegSeedBytes, every kZSegSeedStride-th) */
 constexpr uint32_t kZSegSeedBytes = 16384, kZSegSeedStride = 2;
+/* the same window W for `dfast` (both tables) and the lazy family (hash chain / binary tree), every position of it; the
+ * segment's tables are sized for W + S bytes (zstd_seg_cparams) -- profiles/r08_encode_segment_strategies.txt */
+constexpr uint32_t kZSegSeedBytesDfast = 16384, kZSegSeedBytesLazy = 16384;
 
 /* per-workgroup global workspace layout */
 constexpr size_t kWsSeq = 0;                                   /* uint2 {off, ll | ml<<16} x kMaxSeq */
@@ -1226,6 +1229,24 @@ __device__ uint32_t block_fast(uint32_t *table, const CPar &cp, const uint8_t *b
 #include "zstd_lazy.h"
 #include "zstd_opt.h"
 
+/* segment-mode seeding, one round of 64 ascending positions: true for the lane that writes slot h -- of the valid lanes
+ * that share it, the highest, as a serial insertion in position order leaves it (marks in the finder's LDS array, then
+ * exact among the lanes whose mark was overwritten by another slot's) */
+__device__ inline bool seed_last_writer(volatile uint8_t *vmark, uint32_t h, bool valid, uint32_t lane)
+{
+    if (valid) vmark[h & (kDfMark - 1u)] = (uint8_t)lane;
+    __builtin_amdgcn_wave_barrier();
+    bool w = valid && vmark[h & (kDfMark - 1u)] == (uint8_t)lane;
+    __builtin_amdgcn_wave_barrier();
+    unsigned long long losers = __ballot(valid && !w);
+    while (losers) {
+        const uint32_t hj = lane_get(h, ctz64(losers));
+        const unsigned long long G = __ballot(valid && h == hj);
+        if ((G >> lane) & 1ull) w = lane == 63u - (uint32_t)__builtin_clzll(G);
+        losers &= ~G;
+    }
+    return w;
+}
 
 
 } // namespace
@@ -1240,7 +1261,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4)))
 k_zstd_enc(const uint8_t *__restrict__ src_base, uint64_t src_stride, uint32_t n, uint64_t n_blocks,
            uint8_t *__restrict__ dst_base, uint64_t dst_stride, int wlog, int hlog, int clog, int mml, int tlen,
            int finder, uint32_t width, uint32_t *__restrict__ out_size, int32_t *__restrict__ status,
-           uint8_t *workspace, uint64_t ws_stride, unsigned long long *stats, uint32_t seg_bytes = 0, uint32_t nseg = 1)
+           uint8_t *workspace, uint64_t ws_stride, unsigned long long *stats, uint32_t seg_bytes = 0, uint32_t nseg = 1,
+           uint32_t seg_seed = 0)
 {
     __shared__ __attribute__((aligned(16))) EncLds L;
     /* the finders' mark array lies over the entropy stage's scratch (histogram + tree nodes: dead while a finder runs) */
@@ -1263,11 +1285,13 @@ k_zstd_enc(const uint8_t *__restrict__ src_base, uint64_t src_stride, uint32_t n
     uint2 *opt_matches = reinterpret_cast<uint2 *>(reinterpret_cast<uint8_t *>(opt_tab) + kOptTabBytes);
     uint32_t *opt_saved = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(opt_matches) + kOptMatchBytes);
 
-    /* segment mode (seg_bytes != 0, `fast` only; enc_seg.hip): work item x is segment x % nseg of block x / nseg, encoded as
-     * ONE zstd block (last-block bit only on the block's final segment) into slot x of dst_base, without a frame header; it
-     * starts as the first block of a frame does (no previous Huffman / FSE tables: none are repeated) but with no repeat
-     * offsets (0 disables them until the block's own raw offsets set them), and the table is seeded with positions before
-     * the segment, so that matches reach into the earlier ones */
+    /* segment mode (seg_bytes != 0, finders 0, 1, 3 .. 6; enc_seg.hip): work item x is segment x % nseg of block x / nseg,
+     * encoded as ONE zstd block (last-block bit only on the block's final segment) into slot x of dst_base, without a frame
+     * header; it starts as the first block of a frame does (no previous Huffman / FSE tables: none are repeated) but with no
+     * repeat offsets (0 disables them until the block's own raw offsets set them), and the tables are seeded with positions
+     * before the segment, so that matches reach into the earlier ones (`fast`: the last kZSegSeedBytes, every second
+     * position; the others: every position of the last seg_seed bytes).  Tables hold nothing else: they start zeroed, and
+     * the finder inserts only positions below the one it searches, which lies before the segment's end */
     const bool seg = seg_bytes != 0u;
     const uint64_t n_items = seg ? n_blocks * nseg : n_blocks;
     for (uint64_t item = blockIdx.x; item < n_items; item += gridDim.x) {
@@ -1282,34 +1306,29 @@ k_zstd_enc(const uint8_t *__restrict__ src_base, uint64_t src_stride, uint32_t n
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        if (seg && s0) {
-            /* entries as block_fast_gbatch writes them (index = position + 1, the tag above the index bits), ascending, 64 per
-             * round; of the lanes of a round that share a slot the highest writes it (marks in the finder's LDS array) */
+        if (!OPT && seg && s0 && finder <= 1) { /* (segment mode never runs the optimal parsers) */
+            /* entries as the finder writes them, ascending, 64 per round; of the lanes of a round that share a slot the highest
+             * writes it.  `fast` (block_fast_gbatch): index = position + 1 with the tag above the index bits, every second
+             * position of the last kZSegSeedBytes.  `dfast` (block_dfast_batch): index = position + 1, no tag, in the long
+             * table (8-byte hash) and the short one (minMatch bytes), every position of the last seg_seed bytes */
+            const bool df = finder == 1;
             const int mls = mml < 4 ? 4 : (mml > 7 ? 7 : mml);
             const uint32_t ib = (uint32_t)cp.ib, im = (1u << ib) - 1u;
-            volatile uint8_t *vmark = df_mark;
-            const uint32_t from = s0 > kZSegSeedBytes ? s0 - kZSegSeedBytes : 0u;
-            for (uint32_t p0 = from; p0 < s0; p0 += 64u * kZSegSeedStride) {
-                const uint32_t p = p0 + lane * kZSegSeedStride;
-                const bool valid = p < s0 && p + 8u <= n;
-                uint32_t h = 0, ent = 0;
-                if (valid) {
-                    const uint64_t v = ld64v(src + p);
-                    h = hashs_v(v, hlog, mls);
-                    ent = ((p + 1u) & im) | ((fast_tag((uint32_t)v) >> ib) << ib);
-                    vmark[h & (kDfMark - 1u)] = (uint8_t)lane;
+            const uint32_t span = df ? seg_seed : kZSegSeedBytes, step = df ? 1u : kZSegSeedStride;
+            const uint32_t from = s0 > span ? s0 - span : 0u;
+            for (uint32_t t = 0; t < (df ? 2u : 1u); t++) { /* dfast: the long table, then the short one */
+                uint32_t *tab = t ? tshort : table;
+                for (uint32_t p0 = from; p0 < s0; p0 += 64u * step) {
+                    const uint32_t p = p0 + lane * step;
+                    const bool valid = p < s0 && p + 8u <= n;
+                    uint32_t h = 0, ent = 0;
+                    if (valid) {
+                        const uint64_t v = ld64v(src + p);
+                        h = df && !t ? hash8_v(v, hlog) : hashs_v(v, t ? clog : hlog, mls);
+                        ent = df ? p + 1u : ((p + 1u) & im) | ((fast_tag((uint32_t)v) >> ib) << ib);
+                    }
+                    if (seed_last_writer(df_mark, h, valid, lane)) tab[h] = ent;
                 }
-                __builtin_amdgcn_wave_barrier();
-                bool w = valid && vmark[h & (kDfMark - 1u)] == (uint8_t)lane;
-                __builtin_amdgcn_wave_barrier();
-                unsigned long long losers = __ballot(valid && !w);
-                while (losers) {
-                    const uint32_t hj = lane_get(h, ctz64(losers));
-                    const unsigned long long G = __ballot(valid && h == hj);
-                    if ((G >> lane) & 1ull) w = lane == 63u - (uint32_t)__builtin_clzll(G);
-                    losers &= ~G;
-                }
-                if (w) table[h] = ent;
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
@@ -1340,7 +1359,9 @@ k_zstd_enc(const uint8_t *__restrict__ src_base, uint64_t src_stride, uint32_t n
         ost.lit_base = ost.ll_base = ost.ml_base = ost.of_base = 0; ost.predef = false;
         HufState hs;
         hs.prev_valid = false; hs.next_new = false; hs.prof = PROF ? stats : nullptr; hs.t = 0; hs.strat = finder >= 3 ? (uint32_t)finder : (dfast ? 2u : 1u);
-        HcState hc = {table, tshort, 1u, table3, hlog3, 1u};
+        /* the lazy family in segment mode: the finder's first search inserts the seed window (every position of the last
+         * seg_seed bytes; btlazy2: unsorted into the tree, sorted when a search reaches them) and nothing below it */
+        HcState hc = {table, tshort, !OPT && seg && s0 > seg_seed ? s0 - seg_seed + 1u : 1u, table3, hlog3, 1u};
         SeqTabs tb;
         tb.prev = reinterpret_cast<FseCt *>(ws + kWsTabs);
         tb.rep[0] = tb.rep[1] = tb.rep[2] = 0;
@@ -1388,8 +1409,9 @@ k_zstd_enc(const uint8_t *__restrict__ src_base, uint64_t src_stride, uint32_t n
                 }
                 else if (finder == 1) last_ll = block_dfast_batch<PROF>(table, tshort, df_mark, cp, base, src + ip, bs, nrep, ws, ss, dict_limit, lane, width, stats);
                 else if (finder >= 3) {
-                    const uint32_t cur = ip + 1u; /* ZSTD_buildSeqStore: limited catch-up after a very long match */
-                    if (cur > hc.next_to_update + 384u) {
+                    const uint32_t cur = ip + 1u; /* ZSTD_buildSeqStore: limited catch-up after a very long match (a segment is
+                                                   * one block: its seed window is not skipped) */
+                    if (!seg && cur > hc.next_to_update + 384u) {
                         const uint32_t d = cur - hc.next_to_update - 384u;
                         hc.next_to_update = cur - (d < 192u ? d : 192u);
                     }
@@ -1538,38 +1560,67 @@ bool zstd_compress_supported(int level, uint32_t block_size)
     return zstd_fast_cparams(level, block_size, &a, &b, &c, &d);
 }
 
-/* ---- segment-parallel encode (CRYO_OPT_ENCODE_SEGMENT_BYTES): strategy `fast` only, enc_seg.hip concatenates ---- */
-bool zstd_segment_supported(int level, uint32_t block_size)
+/* ---- segment-parallel encode (CRYO_OPT_ENCODE_SEGMENT_BYTES): strategies `fast` .. `btlazy2` up to the handle's
+ * CRYO_OPT_ENCODE_SEGMENT_ZSTD_STRATEGY (the optimal parsers carry statistics from block to block: never), enc_seg.hip
+ * concatenates ---- */
+bool zstd_segment_supported(int level, uint32_t block_size, int max_strategy)
 {
     int wlog, hlog, mml, tlen, clog, strategy = 0;
-    return zstd_fast_cparams(level, block_size, &wlog, &hlog, &mml, &tlen, &clog, nullptr, &strategy) && strategy == 1;
+    return zstd_fast_cparams(level, block_size, &wlog, &hlog, &mml, &tlen, &clog, nullptr, &strategy) && strategy >= 1 &&
+           strategy <= max_strategy && strategy <= 6;
 }
-static size_t zstd_seg_enc_bytes(uint64_t items, int level, uint32_t block_size)
+/* a segment item's parameters: the identical path's (wlog stays the frame's window), and above `fast` the seed window W
+ * (never more than the window minus S) and tables sized for a source of W + S bytes, as ZSTD_adjustCParams sizes them
+ * for a source that small -- every item zeroes its tables first.  `fast` keeps the full-size table (its bytes stay). */
+struct ZSegPar { int wlog, hlog, mml, tlen, clog, strategy, slog; uint32_t seed; };
+static bool zstd_seg_cparams(int level, uint32_t block_size, uint32_t seg_bytes, ZSegPar *q)
 {
-    int wlog, hlog, mml, tlen, clog;
-    if (!zstd_fast_cparams(level, block_size, &wlog, &hlog, &mml, &tlen, &clog)) return 0;
-    const size_t stride = zstd_enc_stride(hlog, clog, false);
+    q->strategy = 0; q->slog = 0; q->seed = 0;
+    if (!zstd_fast_cparams(level, block_size, &q->wlog, &q->hlog, &q->mml, &q->tlen, &q->clog, nullptr, &q->strategy, &q->slog))
+        return false;
+    if (q->strategy < 2 || q->strategy > 6) return true;
+    static const uint32_t seed_env = cryo_tuning_env("CRYO_ZSTD_SEG_SEED") ? (uint32_t)atoi(cryo_tuning_env("CRYO_ZSTD_SEG_SEED")) : 0u; /* tuning aid */
+    uint64_t w = seed_env ? seed_env : (q->strategy == 2 ? kZSegSeedBytesDfast : kZSegSeedBytesLazy);
+    const uint64_t win = 1ull << q->wlog;
+    if (w + seg_bytes > win) w = win > seg_bytes ? win - seg_bytes : 0u;
+    q->seed = (uint32_t)w;
+    int tl = 0;
+    for (uint64_t v = w + seg_bytes - 1u; v; v >>= 1) tl++;
+    if (tl > q->wlog) tl = q->wlog;
+    if (q->hlog > tl + 1) q->hlog = tl + 1;
+    const int btscale = q->strategy == 6 ? 1 : 0;
+    if (q->clog - btscale > tl) q->clog = tl + btscale;
+    return true;
+}
+static size_t zstd_seg_enc_bytes(uint64_t items, int level, uint32_t block_size, uint32_t seg_bytes)
+{
+    ZSegPar q;
+    if (!zstd_seg_cparams(level, block_size, seg_bytes, &q)) return 0;
+    const size_t stride = zstd_enc_stride(q.hlog, q.clog, q.strategy >= 2);
     return ((size_t)zstd_enc_grid(items, stride) * stride + 255u) & ~(size_t)255u;
 }
 size_t zstd_compress_segmented_workspace(uint64_t n_blocks, int level, uint32_t block_size, uint32_t seg_bytes)
 {
     const uint64_t items = n_blocks * enc_seg_count(block_size, seg_bytes);
-    return zstd_seg_enc_bytes(items, level, block_size) + zstd_seg_scratch_bytes(items, seg_bytes);
+    return zstd_seg_enc_bytes(items, level, block_size, seg_bytes) + zstd_seg_scratch_bytes(items, seg_bytes);
 }
 hipError_t launch_zstd_compress_segmented(hipStream_t s, const uint8_t *d_src, uint64_t src_stride, uint32_t block_size,
                                           uint64_t n_blocks, uint8_t *d_dst, uint64_t dst_stride, int level, uint32_t seg_bytes,
                                           uint32_t *d_out_size, int32_t *d_status, void *d_workspace, size_t workspace_bytes)
 {
     if (n_blocks == 0) return hipSuccess;
-    int wlog, hlog, mml, tlen, clog, strategy = 0;
-    if (!zstd_fast_cparams(level, block_size, &wlog, &hlog, &mml, &tlen, &clog, nullptr, &strategy) || strategy != 1)
-        return hipErrorNotSupported;
+    ZSegPar q;
+    if (!zstd_seg_cparams(level, block_size, seg_bytes, &q) || q.strategy < 1 || q.strategy > 6) return hipErrorNotSupported;
+    const int wlog = q.wlog, hlog = q.hlog, clog = q.clog, mml = q.mml, tlen = q.tlen;
+    /* the identical path's finder and step width (launch_zstd_compress), in the same instantiation */
+    const int finder = q.strategy >= 3 ? q.strategy : q.strategy - 1; /* 0 fast, 1 dfast, 3 .. 6 greedy .. btlazy2 */
+    const uint32_t width = q.strategy >= 3 ? (uint32_t)q.slog : (q.strategy == 2 ? 32u : 16u);
     const uint32_t nseg = enc_seg_count(block_size, seg_bytes);
     const uint64_t items = n_blocks * nseg;
     if (items > 0x7fffffffull) return hipErrorInvalidValue;
-    const size_t stride = zstd_enc_stride(hlog, clog, false);
+    const size_t stride = zstd_enc_stride(hlog, clog, q.strategy >= 2);
     const uint32_t grid = zstd_enc_grid(items, stride);
-    const size_t enc_bytes = zstd_seg_enc_bytes(items, level, block_size);
+    const size_t enc_bytes = zstd_seg_enc_bytes(items, level, block_size, seg_bytes);
     if (workspace_bytes < enc_bytes + zstd_seg_scratch_bytes(items, seg_bytes)) return hipErrorInvalidValue;
     uint8_t *ws = (uint8_t *)d_workspace;
     uint8_t *d_seg = ws + enc_bytes;
@@ -1577,7 +1628,8 @@ hipError_t launch_zstd_compress_segmented(hipStream_t s, const uint8_t *d_src, u
     uint32_t *d_seg_size = (uint32_t *)(d_seg + (((size_t)items * slot + 255u) & ~(size_t)255u));
     uint32_t *d_seg_off = d_seg_size + (((size_t)items * 4u + 255u) & ~(size_t)255u) / 4u;
     hipLaunchKernelGGL((k_zstd_enc<false, false>), dim3(grid), dim3(64), 0, s, d_src, src_stride, block_size, n_blocks, d_seg, slot, wlog,
-                       hlog, clog, mml, tlen, 0, 16u, d_seg_size, d_status, ws, (uint64_t)stride, nullptr, seg_bytes, nseg);
+                       hlog, clog, mml, tlen, finder, width, d_seg_size, d_status, ws, (uint64_t)stride, nullptr, seg_bytes, nseg,
+                       q.seed);
     /* the frame header of the byte-identical path (k_zstd_enc): content size, no checksum */
     uint8_t head[16];
     uint32_t hl = 0;

@@ -32,10 +32,8 @@ __device__ inline uint32_t count_back(const uint8_t *a, const uint8_t *b, uint32
     }
 }
 
-/* ZSTD_insertAndFindFirstIndex: positions next_to_update .. target-1 go into the tables; returns the head of
- * target's chain */
-__device__ inline uint32_t hc_insert_find(HcState &hc, uint8_t *mark, const CPar &cp, const uint8_t *base, uint32_t target, int mls,
-                                          uint32_t lane)
+/* positions next_to_update .. target-1 go into the tables (reads the 8 bytes at each) */
+__device__ inline void hc_insert(HcState &hc, uint8_t *mark, const CPar &cp, const uint8_t *base, uint32_t target, int mls, uint32_t lane)
 {
     const uint32_t cmask = (1u << cp.clog) - 1u;
     uint32_t idx = hc.next_to_update;
@@ -49,6 +47,14 @@ __device__ inline uint32_t hc_insert_find(HcState &hc, uint8_t *mark, const CPar
         idx += (uint32_t)__builtin_popcountll(__ballot(on));
     }
     hc.next_to_update = target;
+}
+
+/* ZSTD_insertAndFindFirstIndex: positions next_to_update .. target-1 go into the tables; returns the head of
+ * target's chain */
+__device__ inline uint32_t hc_insert_find(HcState &hc, uint8_t *mark, const CPar &cp, const uint8_t *base, uint32_t target, int mls,
+                                          uint32_t lane)
+{
+    hc_insert(hc, mark, cp, base, target, mls, lane);
     return uni(hc.hash[hashs_v(ld64u(base + target), cp.hlog, mls)]);
 }
 

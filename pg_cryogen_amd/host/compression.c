@@ -31,6 +31,7 @@ int cryo_gpu_count_guc = 1;
 int cryo_gpu_pool_mb_guc = 0;
 int cryo_gpu_workspace_keep_mb_guc = 1024; /* device workspace a backend keeps between calls (-1: everything) */
 int cryo_gpu_encode_segment_kb_guc = 0;    /* segment-parallel encode, KiB (0: the byte-identical encoders) */
+int cryo_gpu_encode_segment_zstd_strategy_guc = 1; /* highest zstd strategy segment mode takes (1: `fast`) */
 int cryo_gpu_readahead_blocks_guc = 8;    /* cryo blocks a sequential scan's cache miss decodes with one codec call (1: only the block asked for) */
 Size cryo_blcksz = (Size)1 << 20; /* CRYO_BLCKSZ, reference storage.h:18 */
 
@@ -39,7 +40,8 @@ Size cryo_blcksz = (Size)1 << 20; /* CRYO_BLCKSZ, reference storage.h:18 */
  * device numbers, wrapping).  With more than one, the K-block calls of the staging and cache code go through the
  * dispatcher of include/cryo_codec.h (block i of a call -> GPU i mod G, one host thread per GPU). */
 static cryo_multi *hip_multi;
-static int hip_multi_first = -1, hip_multi_count = 0, hip_pool_mb = 0, hip_keep_mb = -2, hip_seg_kb = 0;
+static int hip_multi_first = -1, hip_multi_count = 0, hip_pool_mb = 0, hip_keep_mb = -2, hip_seg_kb = 0,
+           hip_seg_strategy = 1;
 /* A failed open is remembered until the GUCs change -- for good when the machine has no GPU (deterministic), for
  * CRYO_OPEN_RETRY_SECONDS when devices exist but cryo_multi_open failed (out of device memory, a busy device: transient;
  * a pooled backend must not refuse every cryo table for the rest of its life because of one bad moment). */
@@ -123,6 +125,7 @@ const CryoCodecOps *cryo_host_codec_ops(void)
         hip_pool_mb = 0;
         hip_keep_mb = -2;
         hip_seg_kb = 0;
+        hip_seg_strategy = 1;
         hip_ops.ctx = hip_multi;
     }
     if (hip_keep_mb != cryo_gpu_workspace_keep_mb_guc) { /* a backend is long-lived: one large call must not pin its workspace for good */
@@ -136,6 +139,11 @@ const CryoCodecOps *cryo_host_codec_ops(void)
     if (hip_seg_kb != cryo_gpu_encode_segment_kb_guc && cryo_encode_segment_kb_valid(cryo_gpu_encode_segment_kb_guc)) {
         hip_seg_kb = cryo_gpu_encode_segment_kb_guc; /* a value the option refuses is never stored: the encoders stay as they are */
         (void)cryo_multi_set_option(hip_multi, CRYO_OPT_ENCODE_SEGMENT_BYTES, (int64_t)hip_seg_kb << 10);
+    }
+    if (hip_seg_strategy != cryo_gpu_encode_segment_zstd_strategy_guc &&
+        cryo_encode_segment_zstd_strategy_valid(cryo_gpu_encode_segment_zstd_strategy_guc)) {
+        hip_seg_strategy = cryo_gpu_encode_segment_zstd_strategy_guc;
+        (void)cryo_multi_set_option(hip_multi, CRYO_OPT_ENCODE_SEGMENT_ZSTD_STRATEGY, (int64_t)hip_seg_strategy);
     }
     return &hip_ops;
 }
@@ -179,6 +187,12 @@ int cryo_encode_segment_kb_valid(int kb)
 {
     return kb == 0 || (kb >= 4 && kb <= 128 && (kb & (kb - 1)) == 0);
 }
+/* pg_cryogen.gpu_encode_segment_zstd_strategy: libzstd's ZSTD_strategy number, 1 (`fast`) .. 6 (`btlazy2`)
+ * (CRYO_OPT_ENCODE_SEGMENT_ZSTD_STRATEGY) */
+int cryo_encode_segment_zstd_strategy_valid(int strategy)
+{
+    return strategy >= 1 && strategy <= 6;
+}
 #ifdef CRYO_HAVE_POSTGRES
 static bool check_encode_segment_kb(int *newval, void **extra, GucSource source)
 {
@@ -217,6 +231,15 @@ void cryo_define_compression_gucs(void)
                             "the stock libraries decode, but not byte-identical to theirs).",
                             NULL, &cryo_gpu_encode_segment_kb_guc, 0, 0, 128, PGC_USERSET, 0, check_encode_segment_kb,
                             NULL, NULL);
+    static const struct config_enum_entry encode_segment_zstd_strategy_options[] = {
+        {"fast", 1, false}, {"dfast", 2, false}, {"greedy", 3, false}, {"lazy", 4, false},
+        {"lazy2", 5, false}, {"btlazy2", 6, false}, {NULL, 0, false}};
+    DefineCustomEnumVariable("pg_cryogen.gpu_encode_segment_zstd_strategy",
+                             "Deepest zstd strategy the segment-parallel GPU encoder takes when gpu_encode_segment_kb is set "
+                             "(fast = levels up to 2 only, as before; dfast .. btlazy2 = deeper levels too, whose output then "
+                             "stops being byte-identical to libzstd's).",
+                             NULL, &cryo_gpu_encode_segment_zstd_strategy_guc, 1, encode_segment_zstd_strategy_options,
+                             PGC_USERSET, 0, NULL, NULL, NULL);
 #else
     /* no GUC machinery without PostgreSQL: the variables keep the reference's defaults */
     compression_method_guc = COMP_ZSTD;

@@ -51,6 +51,10 @@ extern int cryo_gpu_workspace_keep_mb_guc; /* pg_cryogen.gpu_workspace_keep_mb (
  * encode, CRYO_OPT_ENCODE_SEGMENT_BYTES -- for the write path's one-block calls) */
 extern int cryo_gpu_encode_segment_kb_guc;
 int cryo_encode_segment_kb_valid(int kb);
+/* pg_cryogen.gpu_encode_segment_zstd_strategy (enum fast, dfast, greedy, lazy, lazy2, btlazy2 = 1 .. 6, default fast): the
+ * deepest zstd strategy segment mode takes (CRYO_OPT_ENCODE_SEGMENT_ZSTD_STRATEGY; no effect while the segment size is 0) */
+extern int cryo_gpu_encode_segment_zstd_strategy_guc;
+int cryo_encode_segment_zstd_strategy_valid(int strategy);
 extern int cryo_gpu_readahead_blocks_guc;  /* pg_cryogen.gpu_readahead_blocks (default 8, 1 = off): host/cache.c, cryo_read_data_rel */
 /* bytes the codec moved towards the device / back, blocks served from the pool / decoded (0 when no GPU codec is bound) */
 void cryo_host_transfer_counters(uint64_t *h2d_bytes, uint64_t *d2h_bytes, uint64_t *pool_hits, uint64_t *pool_misses);
