@@ -41,7 +41,8 @@ typedef enum {
     CRYO_E_CORRUPT = -4,     /* malformed compressed block, or decoded size != block_size */
     CRYO_E_DSTSIZE = -5,     /* destination capacity below cryo_codec_bound()           */
     CRYO_E_UNSUPPORTED = -6, /* valid request this build has no kernel for              */
-    CRYO_E_NOMEM = -7
+    CRYO_E_NOMEM = -7,
+    CRYO_E_VERIFY = -8       /* a compressed block failed verification (CRYO_OPT_ENCODE_VERIFY, cryo_codec_verify_batch) */
 } cryo_status;
 
 typedef struct cryo_codec cryo_codec; /* opaque: device id, stream, workspace */
@@ -115,7 +116,15 @@ typedef enum {
      * repeat offsets that start disabled and fresh entropy tables; the stream properties are those above.  The optimal
      * parsers (`btopt`, `btultra`, `btultra2`: levels 13 / 16 and up) carry statistics from block to block and always take
      * the byte-identical path.  No effect while CRYO_OPT_ENCODE_SEGMENT_BYTES is 0.  Other values: CRYO_E_ARG. */
-    CRYO_OPT_ENCODE_SEGMENT_ZSTD_STRATEGY = 11
+    CRYO_OPT_ENCODE_SEGMENT_ZSTD_STRATEGY = 11,
+    /* write verification: 0 (default) = none, exactly the behaviour before this option existed; 1 = every compress entry point
+     * (cryo_codec_compress_batch, _block, _blocks, cryo_multi_compress_blocks via cryo_multi_set_option) decodes what it
+     * encoded, with the automatic decode routes a later read takes, into handle workspace and compares it with the input
+     * (cryo_codec_verify_batch below) on the device before it returns or before its statuses become visible.  A block that fails gets
+     * CRYO_E_VERIFY: d_status[i] of cryo_codec_compress_batch; the return value of the host-buffer calls, with the block's
+     * index and first differing byte in cryo_codec_last_error() and cryo_codec_last_verify_failure().  The output bytes are
+     * the same with verification on or off.  Other values: CRYO_E_ARG. */
+    CRYO_OPT_ENCODE_VERIFY = 12
 } cryo_option;
 int cryo_codec_set_option(cryo_codec *c, int option, int64_t value);
 /* a long-lived backend between bursts: waits for the handle's queued work, then frees its device workspace, the device and
@@ -186,6 +195,29 @@ int cryo_codec_decompress_batch(cryo_codec *c, int method,
                                 uint32_t block_size, uint64_t n_blocks,
                                 int32_t *d_status);
 
+/*
+ * Verify n_blocks compressed blocks against their raw input: raw block i is the block_size bytes at d_raw + i*raw_stride,
+ * its stream the d_comp_size[i] bytes at d_comp + d_comp_off[i] (the slack rule of cryo_dev_alloc above applies, as for
+ * cryo_codec_decompress_batch).  Each stream is decoded with the automatic decode routes of cryo_codec_decompress_batch
+ * (whatever the handle's decode-path options say) into handle workspace -- never into caller memory -- in chunks that keep
+ * the decoded blocks and the decoders' workspace within CRYO_OPT_WORKSPACE_MAX_BYTES -- and compared byte for byte.
+ *   d_status[i] (out)          CRYO_OK, or CRYO_E_VERIFY: the stream is malformed, decodes to other than block_size bytes,
+ *                              or decodes to other bytes
+ *   d_first_mismatch[i] (out)  offset of the first byte that differs; 0xFFFFFFFF when the block verified, and when the
+ *                              decoders rejected its stream (no decoded bytes to compare).  May be NULL.
+ * Asynchronous on the handle's stream, like cryo_codec_decompress_batch.  The decodes do not count in
+ * cryo_codec_counters (blocks_decompressed, bytes_out).
+ *
+ * What verification proves: that the project's OWN decoders turn the DEVICE copy of the stream back into the input.  It
+ * catches encoder faults.  It checks nothing after that copy: the host-buffer calls copy the verified slots to host memory
+ * afterwards, and that copy is not compared again.  It does not compare against liblz4 / libzstd, so a mistake made
+ * identically in an encoder and its decoder would pass.  The decoders are
+ * pinned to the stock libraries' streams separately, by the test suite.
+ */
+int cryo_codec_verify_batch(cryo_codec *c, int method, const void *d_raw, uint64_t raw_stride, uint32_t block_size,
+                            uint64_t n_blocks, const void *d_comp, const uint64_t *d_comp_off, const uint32_t *d_comp_size,
+                            int32_t *d_status, uint32_t *d_first_mismatch);
+
 /* ---- single block, HOST buffers: what cryo_compress()/cryo_decompress()
  *      (compression.c:125-159) call.  Synchronous: H2D, kernel, D2H. ---- */
 int cryo_codec_compress_block(cryo_codec *c, int method, int param,
@@ -237,6 +269,11 @@ typedef struct {
 } cryo_codec_transfer_counters;
 int cryo_codec_get_transfer_counters(const cryo_codec *c, cryo_codec_transfer_counters *out);
 
+/* the block that made the handle's last host-buffer compress call return CRYO_E_VERIFY (index within that call) and its
+ * first differing byte (0xFFFFFFFF: the decoders rejected its stream).  1 when that call failed verification, 0 when it
+ * did not, or a negative cryo_status. */
+int cryo_codec_last_verify_failure(const cryo_codec *c, uint64_t *block, uint32_t *first_mismatch);
+
 /* ---- several GPUs behind one call: the dispatcher of BASELINE's "independent cryo blocks from a COPY multi_insert
  *      or a seq-scan shard embarrassingly across the 8 GPUs of one node (round-robin dispatch, no collective)".
  *      One codec handle per listed device (a device may be listed more than once), block i of a call goes to
@@ -268,6 +305,9 @@ int cryo_multi_set_option(cryo_multi *m, int option, int64_t value);
 int cryo_multi_pool_invalidate(cryo_multi *m, uint32_t key_hi, int all_entries);
 int cryo_multi_trim(cryo_multi *m);
 int cryo_multi_get_transfer_counters(const cryo_multi *m, cryo_codec_transfer_counters *out);
+/* cryo_codec_last_verify_failure of the last cryo_multi_compress_blocks call (block: the index within the whole call; the
+ * lowest one when several handles failed) */
+int cryo_multi_last_verify_failure(const cryo_multi *m, uint64_t *block, uint32_t *first_mismatch);
 
 /* ---- batch helpers used by staging, tests and the benchmark ---- */
 

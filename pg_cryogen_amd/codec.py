@@ -15,10 +15,10 @@ METHOD_LZ4 = 0   # COMP_LZ4, reference compression.h:9
 METHOD_ZSTD = 1  # COMP_ZSTD, reference compression.h:10
 
 OK = 0
-E_ARG, E_HIP, E_NODEV, E_CORRUPT, E_DSTSIZE, E_UNSUPPORTED, E_NOMEM = -1, -2, -3, -4, -5, -6, -7
+E_ARG, E_HIP, E_NODEV, E_CORRUPT, E_DSTSIZE, E_UNSUPPORTED, E_NOMEM, E_VERIFY = -1, -2, -3, -4, -5, -6, -7, -8
 _ERR_NAMES = {0: "CRYO_OK", -1: "CRYO_E_ARG", -2: "CRYO_E_HIP", -3: "CRYO_E_NODEV",
               -4: "CRYO_E_CORRUPT", -5: "CRYO_E_DSTSIZE", -6: "CRYO_E_UNSUPPORTED",
-              -7: "CRYO_E_NOMEM"}
+              -7: "CRYO_E_NOMEM", -8: "CRYO_E_VERIFY"}
 
 # cryo_option (include/cryo_codec.h)
 OPT_LZ4_DECODE_PATH, OPT_LZ4_INDEX_WALKERS, OPT_PIPE_MIN_BYTES, OPT_POOL_BYTES, OPT_ZSTD_DECODE_PATH = 1, 2, 3, 4, 5
@@ -26,6 +26,8 @@ OPT_LZ4_DECODE_WAVES = 9
 OPT_WORKSPACE_KEEP_BYTES, OPT_WORKSPACE_MAX_BYTES, OPT_NUMA_LOCAL = 6, 7, 8
 OPT_ENCODE_SEGMENT_BYTES = 10  # 0 = byte-identical encoders; 4 KiB .. 128 KiB (power of two) = segment-parallel encode
 OPT_ENCODE_SEGMENT_ZSTD_STRATEGY = 11  # highest zstd strategy of segment mode: 1 fast (default) .. 6 btlazy2
+OPT_ENCODE_VERIFY = 12  # 0 (default) = none; 1 = every compress call decodes its output and compares it with the input
+VERIFY_NONE = 0xFFFFFFFF  # first-mismatch offset of a block that verified (or whose stream the decoders reject)
 LZ4_PATH_AUTO, LZ4_PATH_RING, LZ4_PATH_INDEXED, LZ4_PATH_FEW_BLOCKS = 0, 1, 2, 3
 
 DIST_WIDE, DIST_NARROW, DIST_INT4, DIST_RANDOM, DIST_ZEROS = range(5)
@@ -49,6 +51,7 @@ ABI_SYMBOLS = [
     "cryo_codec_synth_batch", "cryo_codec_checksum_batch",
     "cryo_codec_compare_batch", "cryo_checksum64", "cryo_codec_timer_start",
     "cryo_codec_timer_stop", "cryo_codec_get_counters",
+    "cryo_codec_verify_batch", "cryo_codec_last_verify_failure", "cryo_multi_last_verify_failure",
 ]
 
 
@@ -130,6 +133,9 @@ def lib():
     L.cryo_codec_timer_start.argtypes = [vp]
     L.cryo_codec_timer_stop.argtypes = [vp, C.POINTER(C.c_float)]
     L.cryo_codec_get_counters.argtypes = [vp, C.POINTER(Counters)]
+    L.cryo_codec_verify_batch.argtypes = [vp, i32, vp, u64, u32, u64, vp, vp, vp, vp, vp]
+    L.cryo_codec_last_verify_failure.argtypes = [vp, C.POINTER(u64), C.POINTER(u32)]
+    L.cryo_multi_last_verify_failure.argtypes = [vp, C.POINTER(u64), C.POINTER(u32)]
     _bound = True
     return L
 
@@ -281,6 +287,21 @@ class Codec:
         self._chk(self.L.cryo_codec_decompress_batch(self.h, method, d_src.ptr, d_off.ptr, d_sizes.ptr, d_dst.ptr,
                                                      dst_stride, block_size, n, d_status.ptr),
                   "decompress_batch")
+
+    def verify_batch(self, method, d_raw, raw_stride, block_size, n, d_comp, d_off, d_sizes, d_status, d_first=None):
+        """decode the n streams (d_comp + d_off[i], d_sizes[i] bytes) and compare them with the raw blocks: d_status[i] = OK /
+        E_VERIFY, d_first[i] = first differing byte (VERIFY_NONE: none, or the stream does not decode).  Asynchronous."""
+        self._chk(self.L.cryo_codec_verify_batch(self.h, method, d_raw.ptr, raw_stride, block_size, n, d_comp.ptr, d_off.ptr,
+                                                 d_sizes.ptr, d_status.ptr, d_first.ptr if d_first else None),
+                  "verify_batch")
+
+    def last_verify_failure(self):
+        """(block, first mismatch) that made the last host-buffer compress call fail verification, or None"""
+        b, o = C.c_uint64(), C.c_uint32()
+        r = self.L.cryo_codec_last_verify_failure(self.h, C.byref(b), C.byref(o))
+        if r < 0:
+            self._chk(r, "last_verify_failure")
+        return (b.value, o.value) if r == 1 else None
 
     def checksum_batch(self, d_src, stride, n, d_sums, d_sizes=None, fixed_size=0):
         self._chk(self.L.cryo_codec_checksum_batch(self.h, d_src.ptr, stride, d_sizes.ptr if d_sizes else None,

@@ -159,6 +159,16 @@ struct cryo_codec {
     std::unordered_map<uint64_t, uint32_t> pool_index; /* key -> slot */
     uint32_t pool_head = 0;                            /* next slot to fill */
     cryo_codec_transfer_counters xfer_ctr = {};
+    /* write verification (CRYO_OPT_ENCODE_VERIFY, cryo_codec_verify_batch): decoded blocks, stream tables and statuses of
+     * the verification decodes (grow-only, given back like the host-buffer staging); the per-block first-mismatch words of
+     * the last verified compress; the failure the last host-buffer compress call returned */
+    int verify = 0;
+    uint8_t *d_vfy = nullptr;
+    size_t vfy_cap = 0;
+    uint32_t *vfy_first = nullptr;
+    bool vfy_failed = false;
+    uint64_t vfy_block = 0;
+    uint32_t vfy_off = 0;
 };
 
 static void pool_drop(cryo_codec *c);
@@ -306,7 +316,7 @@ void ws_trim_after_call(cryo_codec *c)
 {
     if (c->ws_keep < 0) return;
     const size_t keep = (size_t)c->ws_keep;
-    const size_t hb = c->hb_src_cap + c->hb_dst_cap + c->hb_meta_cap;
+    const size_t hb = c->hb_src_cap + c->hb_dst_cap + c->hb_meta_cap + c->vfy_cap;
     const bool drop_ws = c->d_ws && c->ws_cap > keep;
     const bool drop_hb = hb != 0 && hb + (drop_ws ? 0 : c->ws_cap) > keep;
     if (!drop_ws && !drop_hb) return;
@@ -323,6 +333,8 @@ void ws_trim_after_call(cryo_codec *c)
         drop(c->hb_src, c->hb_src_cap);
         drop(c->hb_dst, c->hb_dst_cap);
         drop(c->hb_meta, c->hb_meta_cap);
+        drop(c->d_vfy, c->vfy_cap);
+        c->vfy_first = nullptr;
     }
 }
 
@@ -442,6 +454,7 @@ void cryo_codec_close(cryo_codec *c)
     if (c->hb_src) (void)hipFree(c->hb_src);
     if (c->hb_dst) (void)hipFree(c->hb_dst);
     if (c->hb_meta) (void)hipFree(c->hb_meta);
+    if (c->d_vfy) (void)hipFree(c->d_vfy);
     if (c->pin) (void)hipHostFree(c->pin);
     for (int i = 0; i < 4; i++) if (c->pipe_pin[i]) (void)hipHostFree(c->pipe_pin[i]);
     if (c->xfer) { (void)hipStreamSynchronize(c->xfer); (void)hipStreamDestroy(c->xfer); }
@@ -488,6 +501,8 @@ int cryo_codec_trim(cryo_codec *c)
     drop(c->hb_src, c->hb_src_cap);
     drop(c->hb_dst, c->hb_dst_cap);
     drop(c->hb_meta, c->hb_meta_cap);
+    drop(c->d_vfy, c->vfy_cap);
+    c->vfy_first = nullptr;
     if (c->pin) { (void)hipHostFree(c->pin); c->pin = nullptr; c->pin_cap = 0; }
     for (int i = 0; i < 4; i++)
         if (c->pipe_pin[i]) { (void)hipHostFree(c->pipe_pin[i]); c->pipe_pin[i] = nullptr; c->pipe_pin_cap[i] = 0; }
@@ -538,6 +553,10 @@ int cryo_codec_set_option(cryo_codec *c, int option, int64_t value)
         if (value < 1 || value > 6) return CRYO_E_ARG;
         c->enc_seg_zstd_strategy = (int)value;
         return CRYO_OK;
+    case CRYO_OPT_ENCODE_VERIFY:
+        if (value != 0 && value != 1) return CRYO_E_ARG;
+        c->verify = (int)value;
+        return CRYO_OK;
     case CRYO_OPT_POOL_BYTES: {
         if (value < 0) return CRYO_E_ARG;
         DevGuard dev_(c);
@@ -565,6 +584,7 @@ int cryo_codec_get_option(const cryo_codec *c, int option, int64_t *value)
     case CRYO_OPT_NUMA_LOCAL: *value = c->numa_local && c->have_local_cpus ? 1 : 0; return CRYO_OK;
     case CRYO_OPT_ENCODE_SEGMENT_BYTES: *value = c->enc_seg; return CRYO_OK;
     case CRYO_OPT_ENCODE_SEGMENT_ZSTD_STRATEGY: *value = c->enc_seg_zstd_strategy; return CRYO_OK;
+    case CRYO_OPT_ENCODE_VERIFY: *value = c->verify; return CRYO_OK;
     default: return CRYO_E_ARG;
     }
 }
@@ -640,6 +660,10 @@ int cryo_dev_memset(cryo_codec *c, void *d_dst, int value, size_t bytes)
 }
 
 /* ---- batch codec ---- */
+static int verify_pass(cryo_codec *c, int method, const uint8_t *d_raw, uint64_t raw_stride, uint32_t B, uint64_t n,
+                       const uint8_t *d_comp, const uint64_t *d_comp_off, uint64_t comp_stride, const uint32_t *d_comp_size,
+                       int32_t *d_status, bool has_enc_status, uint32_t *d_first_user);
+
 int cryo_codec_compress_batch(cryo_codec *c, int method, int param, const void *d_src,
                               uint64_t src_stride, uint32_t block_size, uint64_t n_blocks,
                               void *d_dst, uint64_t dst_stride, uint32_t *d_out_size,
@@ -682,21 +706,40 @@ int cryo_codec_compress_batch(cryo_codec *c, int method, int param, const void *
     c->ctr.blocks_compressed += n_blocks;
     c->ctr.bytes_in += n_blocks * (uint64_t)block_size;
     c->ctr.launches++;
+#ifdef CRYO_DEBUG
+    /* fault injection for the tests of the failure paths (debug builds only): CRYO_VERIFY_FAULT="block:byte" flips one byte
+     * of that block's encoded slot before it is verified */
+    if (const char *e = cryo_tuning_env("CRYO_VERIFY_FAULT")) {
+        unsigned long long fb = 0, fo = 0;
+        if (c->verify && sscanf(e, "%llu:%llu", &fb, &fo) == 2 && fb < n_blocks && fo < dst_stride) {
+            uint8_t v = 0;
+            uint8_t *p = (uint8_t *)d_dst + fb * dst_stride + fo;
+            HIP_TRY(c, hipMemcpyAsync(&v, p, 1, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            v ^= 0x5A;
+            HIP_TRY(c, hipMemcpyAsync(p, &v, 1, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+        }
+    }
+#endif
+    if (c->verify)
+        return guarded([&] {
+            return verify_pass(c, method, (const uint8_t *)d_src, src_stride, block_size, n_blocks, (const uint8_t *)d_dst, nullptr,
+                               dst_stride, d_out_size, d_status, true, nullptr);
+        });
     return CRYO_OK;
 }
 
-int cryo_codec_decompress_batch(cryo_codec *c, int method, const void *d_src,
-                                const uint64_t *d_src_off, const uint32_t *d_src_size, void *d_dst,
-                                uint64_t dst_stride, uint32_t block_size, uint64_t n_blocks,
-                                int32_t *d_status)
+/* the decode of cryo_codec_decompress_batch.  verification: the automatic routes whatever the handle's decode-path options say,
+ * the zstd pipeline planned within zstd_max bytes of workspace, and the counters left alone (they count the caller's decodes) */
+static int decompress_routed(cryo_codec *c, int method, const void *d_src, const uint64_t *d_src_off, const uint32_t *d_src_size,
+                             void *d_dst, uint64_t dst_stride, uint32_t block_size, uint64_t n_blocks, int32_t *d_status,
+                             bool verification, size_t zstd_max)
 {
-    DevGuard dev_(c);
-    if (!c || !method_ok(method) || block_size == 0) return CRYO_E_ARG;
-    if (n_blocks == 0) return CRYO_OK;
-    if (!d_src || !d_src_off || !d_src_size || !d_dst || !d_status || dst_stride < block_size)
-        return CRYO_E_ARG;
     if (method == CRYO_METHOD_LZ4) {
-        const size_t need = cryo::lz4_decompress_workspace(n_blocks, block_size, c->lz4_opts);
+        cryo::Lz4DecodeOpts opts = c->lz4_opts;
+        if (verification) opts.path = opts.walkers = opts.waves = 0;
+        const size_t need = cryo::lz4_decompress_workspace(n_blocks, block_size, opts);
         if (need != 0) {
             int rc = ensure_ws(c, need);
             if (rc != CRYO_OK) return rc;
@@ -720,11 +763,13 @@ int cryo_codec_decompress_batch(cryo_codec *c, int method, const void *d_src,
                 c->lz4_side_failed = true;
             }
         }
+        opts.side = c->lz4_opts.side; opts.fork = c->lz4_opts.fork; opts.join = c->lz4_opts.join;
         HIP_TRY(c, cryo::launch_lz4_decompress(c->stream, (const uint8_t *)d_src, d_src_off, d_src_size,
                                                (uint8_t *)d_dst, dst_stride, block_size, n_blocks,
-                                               d_status, need ? c->d_ws : nullptr, need ? c->ws_cap : 0, c->lz4_opts));
+                                               d_status, need ? c->d_ws : nullptr, need ? c->ws_cap : 0, opts));
     } else {
-        const size_t need = cryo::zstd_decompress_workspace(n_blocks, block_size, c->zstd_path, ws_budget(c));
+        const int zpath = verification ? 0 : c->zstd_path;
+        const size_t need = cryo::zstd_decompress_workspace(n_blocks, block_size, zpath, verification ? zstd_max : ws_budget(c));
         int rc = ensure_ws(c, need);
         if (rc != CRYO_OK) return rc;
         if (!c->have_aux) {
@@ -740,12 +785,159 @@ int cryo_codec_decompress_batch(cryo_codec *c, int method, const void *d_src,
         }
         HIP_TRY(c, cryo::launch_zstd_decompress(c->stream, (const uint8_t *)d_src, d_src_off, d_src_size,
                                                 (uint8_t *)d_dst, dst_stride, block_size, n_blocks,
-                                                d_status, c->d_ws, c->ws_cap, &c->aux, c->zstd_path));
+                                                d_status, c->d_ws, c->ws_cap, &c->aux, zpath));
     }
-    c->ctr.blocks_decompressed += n_blocks;
-    c->ctr.bytes_out += n_blocks * (uint64_t)block_size;
+    if (!verification) {
+        c->ctr.blocks_decompressed += n_blocks;
+        c->ctr.bytes_out += n_blocks * (uint64_t)block_size;
+    }
     c->ctr.launches++;
     return CRYO_OK;
+}
+
+int cryo_codec_decompress_batch(cryo_codec *c, int method, const void *d_src,
+                                const uint64_t *d_src_off, const uint32_t *d_src_size, void *d_dst,
+                                uint64_t dst_stride, uint32_t block_size, uint64_t n_blocks,
+                                int32_t *d_status)
+{
+    DevGuard dev_(c);
+    if (!c || !method_ok(method) || block_size == 0) return CRYO_E_ARG;
+    if (n_blocks == 0) return CRYO_OK;
+    if (!d_src || !d_src_off || !d_src_size || !d_dst || !d_status || dst_stride < block_size)
+        return CRYO_E_ARG;
+    return decompress_routed(c, method, d_src, d_src_off, d_src_size, d_dst, dst_stride, block_size, n_blocks, d_status, false, 0);
+}
+
+/* ---- write verification ----
+ * Decode the streams of n blocks with the automatic routes into handle workspace (c->d_vfy), compare with the raw blocks
+ * (verify.hip), fold the verdict into d_status, in chunks of K blocks that keep the decoded blocks, the stream tables and the
+ * decoders' workspace within the call's budget (CRYO_OPT_WORKSPACE_MAX_BYTES, else what ws_budget allows).
+ * Streams come either from a table (d_comp_off: the caller's, who keeps the slack of cryo_dev_alloc) or from the slots of a
+ * compress call (d_comp + i * comp_stride, an area of exactly n * comp_stride bytes as far as we know).  The decoders read
+ * aligned 16-byte pieces, so up to 15 bytes beyond a stream's end, and before its start when it is not aligned: the last slot's
+ * stream -- and the first's when the area is not 16-byte aligned -- may end at the area's bound, so those "edge" slots are
+ * copied (slot bytes only: in bounds) into padded workspace and decoded from there.  Every other slot is followed by a whole
+ * slot of at least 16 bytes (stride >= bound >= 16) and, in an aligned area, preceded by the area's own bytes. */
+static int verify_pass(cryo_codec *c, int method, const uint8_t *d_raw, uint64_t raw_stride, uint32_t B, uint64_t n,
+                       const uint8_t *d_comp, const uint64_t *d_comp_off, uint64_t comp_stride, const uint32_t *d_comp_size,
+                       int32_t *d_status, bool has_enc_status, uint32_t *d_first_user)
+{
+    constexpr uint64_t kNone = ~0ull;
+    auto al = [](uint64_t x) { return (x + 255u) & ~(uint64_t)255u; };
+    const uint64_t Bp = ((uint64_t)B + 15u) & ~(uint64_t)15u; /* decoded block stride: 16-byte rows for the compare */
+    uint64_t e0 = kNone, e1 = kNone;
+    if (!d_comp_off) {
+        if ((uintptr_t)d_comp & 15u) e0 = 0;
+        if (n - 1 != e0) e1 = n - 1;
+    }
+    const uint64_t E = d_comp_off ? 0 : al(comp_stride + 64u); /* one padded edge copy */
+    const uint64_t first_bytes = d_first_user ? 0 : al(n * 4u);
+    auto meta = [&](uint64_t K) { return al((K + 2) * 4u) + al((K + 2) * 8u) + al((K + 2) * 4u) + 2 * E; };
+    size_t budget = c->ws_max;
+    if (!budget) {
+        size_t fr = 0, tot = 0;
+        if (hipMemGetInfo(&fr, &tot) != hipSuccess) { (void)hipGetLastError(); fr = ~(size_t)0 / 2; }
+        budget = fr / 10u * 7u + c->ws_cap + c->vfy_cap;
+    }
+    cryo::Lz4DecodeOpts auto_opts = c->lz4_opts;
+    auto_opts.path = auto_opts.walkers = auto_opts.waves = 0;
+    uint64_t K = n < (1ull << 24) ? n : (1ull << 24);
+    size_t zstd_max = 0;
+    for (;;) {
+        const uint64_t fixed = first_bytes + meta(K) + K * Bp + 256u;
+        size_t dec_ws = 0;
+        if (method == CRYO_METHOD_LZ4) dec_ws = cryo::lz4_decompress_workspace(K, B, auto_opts);
+        else {
+            zstd_max = budget > fixed ? budget - fixed : 0;
+            dec_ws = cryo::zstd_decompress_workspace(K, B, 0, zstd_max);
+        }
+        if (fixed + dec_ws <= budget || K == 1) break;
+        K = (K + 1) / 2;
+    }
+    if (method == CRYO_METHOD_ZSTD && K == 1 && zstd_max == 0) zstd_max = ~(size_t)0; /* one block: whatever it takes */
+    int rc = ensure(c, &c->d_vfy, &c->vfy_cap, first_bytes + meta(K) + K * Bp + 256u + 64u);
+    if (rc != CRYO_OK) return rc;
+    uint8_t *p = c->d_vfy;
+    uint32_t *first = d_first_user ? d_first_user : (uint32_t *)p;
+    p += first_bytes;
+    int32_t *dec_st = (int32_t *)p;   p += al((K + 2) * 4u);
+    uint64_t *off = (uint64_t *)p;    p += al((K + 2) * 8u);
+    uint32_t *sz = (uint32_t *)p;     p += al((K + 2) * 4u);
+    uint8_t *edge = p;                p += 2 * E;
+    uint8_t *dec = p;
+    c->vfy_first = d_first_user ? nullptr : first;
+    for (uint64_t lo = 0; lo < n; lo += K) {
+        const uint32_t cnt = (uint32_t)(n - lo < K ? n - lo : K);
+        const uint64_t ce0 = e0 != kNone && e0 >= lo && e0 < lo + cnt ? e0 : kNone;
+        const uint64_t ce1 = e1 != kNone && e1 >= lo && e1 < lo + cnt ? e1 : kNone;
+        if (ce0 != kNone) HIP_TRY(c, hipMemcpyAsync(edge, d_comp + ce0 * comp_stride, comp_stride, hipMemcpyDeviceToDevice, c->stream));
+        if (ce1 != kNone) HIP_TRY(c, hipMemcpyAsync(edge + E, d_comp + ce1 * comp_stride, comp_stride, hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(c, cryo::launch_verify_prep(c->stream, lo, cnt, d_comp_off, comp_stride, d_comp_size, has_enc_status ? d_status : nullptr,
+                                            ce0, ce1, E, off, sz, first));
+        const uint64_t b_lo = lo + (ce0 != kNone ? 1u : 0u), b_hi = lo + cnt - (ce1 != kNone ? 1u : 0u);
+        if (b_hi > b_lo) {
+            const uint64_t k0 = b_lo - lo;
+            rc = decompress_routed(c, method, d_comp, off + k0, sz + k0, dec + k0 * Bp, Bp, B, b_hi - b_lo, dec_st + k0, true, zstd_max);
+            if (rc != CRYO_OK) return rc;
+        }
+        if (ce0 != kNone || ce1 != kNone) {
+            const uint64_t a = ce0 != kNone ? ce0 : ce1;
+            const uint32_t t = ce0 != kNone ? cnt : cnt + 1u;       /* table entry of the first edge decoded */
+            const uint64_t ne = (ce0 != kNone) + (ce1 != kNone);
+            const uint64_t stride = ne == 2 ? (ce1 - ce0) * Bp : Bp;
+            rc = decompress_routed(c, method, edge, off + t, sz + t, dec + (a - lo) * Bp, stride, B, ne, dec_st + t, true, zstd_max);
+            if (rc != CRYO_OK) return rc;
+        }
+        HIP_TRY(c, cryo::launch_verify_compare(c->stream, d_raw, raw_stride, dec, Bp, B, lo, cnt, sz, dec_st, ce0, ce1, first));
+        HIP_TRY(c, cryo::launch_verify_fold(c->stream, lo, cnt, sz, dec_st, ce0, ce1, has_enc_status, d_status, first));
+    }
+    return CRYO_OK;
+}
+
+/* a host-buffer compress call found block `at` (index into the last verified batch) failed: its first differing byte, the
+ * error text; `block` is the index the caller knows it by */
+static void set_verify_failure(cryo_codec *c, uint64_t block, uint32_t off)
+{
+    c->vfy_failed = true;
+    c->vfy_block = block;
+    c->vfy_off = off;
+    if (off == 0xffffffffu)
+        snprintf(c->err, sizeof c->err, "block %llu failed verification: the decoders reject its stream", (unsigned long long)block);
+    else
+        snprintf(c->err, sizeof c->err, "block %llu failed verification at byte %u", (unsigned long long)block, off);
+}
+static int verify_failure(cryo_codec *c, uint64_t at)
+{
+    uint32_t off = 0xffffffffu;
+    if (c->vfy_first) {
+        HIP_TRY(c, hipMemcpyAsync(&off, c->vfy_first + at, sizeof off, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    set_verify_failure(c, at, off);
+    return CRYO_E_VERIFY;
+}
+
+int cryo_codec_verify_batch(cryo_codec *c, int method, const void *d_raw, uint64_t raw_stride, uint32_t block_size,
+                            uint64_t n_blocks, const void *d_comp, const uint64_t *d_comp_off, const uint32_t *d_comp_size,
+                            int32_t *d_status, uint32_t *d_first_mismatch)
+{
+    DevGuard dev_(c);
+    if (!c || !method_ok(method) || block_size == 0) return CRYO_E_ARG;
+    if (n_blocks == 0) return CRYO_OK;
+    if (!d_raw || !d_comp || !d_comp_off || !d_comp_size || !d_status || raw_stride < block_size) return CRYO_E_ARG;
+    return guarded([&] {
+        return verify_pass(c, method, (const uint8_t *)d_raw, raw_stride, block_size, n_blocks, (const uint8_t *)d_comp, d_comp_off,
+                           0, d_comp_size, d_status, false, d_first_mismatch);
+    });
+}
+
+int cryo_codec_last_verify_failure(const cryo_codec *c, uint64_t *block, uint32_t *first_mismatch)
+{
+    if (!c) return CRYO_E_ARG;
+    if (!c->vfy_failed) return 0;
+    if (block) *block = c->vfy_block;
+    if (first_mismatch) *first_mismatch = c->vfy_off;
+    return 1;
 }
 
 /* ---- single block, host buffers ---- */
@@ -760,6 +952,7 @@ int cryo_codec_compress_block(cryo_codec *c, int method, int param, const void *
     int rc;
     if ((rc = ensure(c, &c->d_in, &c->in_cap, block_size)) != CRYO_OK) return rc;
     if ((rc = ensure(c, &c->d_out, &c->out_cap, bound)) != CRYO_OK) return rc;
+    c->vfy_failed = false;
     HIP_TRY(c, hipMemcpyAsync(c->d_in, h_src, block_size, hipMemcpyHostToDevice, c->stream));
     rc = cryo_codec_compress_batch(c, method, param, c->d_in, block_size, (uint32_t)block_size, 1,
                                    c->d_out, bound, c->d_size, c->d_status);
@@ -769,6 +962,7 @@ int cryo_codec_compress_block(cryo_codec *c, int method, int param, const void *
     HIP_TRY(c, hipMemcpyAsync(&csize, c->d_size, sizeof csize, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(&st, c->d_status, sizeof st, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (st == CRYO_E_VERIFY) return verify_failure(c, 0);
     if (st != CRYO_OK) return st;
     if (csize == 0 || csize > bound) return CRYO_E_HIP;
     HIP_TRY(c, hipMemcpyAsync(h_dst, c->d_out, csize, hipMemcpyDeviceToHost, c->stream));
@@ -873,6 +1067,7 @@ static int compress_blocks_piped(cryo_codec *c, int method, int param, const uin
     HIP_TRY(c, hipMemcpyAsync(p_st, d_st, n * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (size_t i = 0; i < n; i++) {
+        if (p_st[i] == CRYO_E_VERIFY) return verify_failure(c, i);
         if (p_st[i] != CRYO_OK) return p_st[i];
         if (p_sz[i] == 0 || p_sz[i] > bound) return CRYO_E_HIP;
         h_out_size[i] = p_sz[i];
@@ -1040,6 +1235,7 @@ static int compress_blocks_body(cryo_codec *c, int method, int param, const void
     const size_t bound = cryo_codec_bound(method, block_size);
     if (dst_stride < bound) return CRYO_E_DSTSIZE;
     ScopedLocalCpus numa_(n * block_size >= ((size_t)8 << 20) ? c : nullptr); /* the caller's share of the copies next to the GPU */
+    c->vfy_failed = false;
     if (pipe_worth_it(c, n, block_size)) {
         const int rc = compress_blocks_piped(c, method, param, (const uint8_t *)h_src, nullptr, block_size, n, (uint8_t *)h_dst, nullptr, dst_stride, h_out_size);
         if (rc != CRYO_OK) { (void)hipStreamSynchronize(c->stream); if (c->xfer) (void)hipStreamSynchronize(c->xfer); }
@@ -1066,6 +1262,7 @@ static int compress_blocks_body(cryo_codec *c, int method, int param, const void
     if (bulk) HIP_TRY(c, hipMemcpyAsync(h_dst, c->hb_dst, (n - 1) * dstride + bound, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (size_t i = 0; i < n; i++) {
+        if (h_st[i] == CRYO_E_VERIFY) return verify_failure(c, i);
         if (h_st[i] != CRYO_OK) return h_st[i];
         if (h_out_size[i] == 0 || h_out_size[i] > bound) return CRYO_E_HIP;
     }
@@ -1411,6 +1608,7 @@ static int compress_blocks_ptrs(cryo_codec *c, int method, int param, const void
     const size_t bound = cryo_codec_bound(method, block_size);
     const size_t dstride = (bound + 15) & ~(size_t)15;
     ScopedLocalCpus numa_(n * block_size >= ((size_t)8 << 20) ? c : nullptr);
+    c->vfy_failed = false;
     if (pipe_worth_it(c, n, block_size)) { /* the single-handle path's staging: pinned double buffers, second stream, worker threads */
         const int rc = compress_blocks_piped(c, method, param, nullptr, h_src, block_size, n, nullptr, h_dst, dstride, out_size);
         if (rc != CRYO_OK) { (void)hipStreamSynchronize(c->stream); if (c->xfer) (void)hipStreamSynchronize(c->xfer); }
@@ -1439,6 +1637,7 @@ static int compress_blocks_ptrs(cryo_codec *c, int method, int param, const void
     HIP_TRY(c, hipMemcpyAsync(h_st, d_st, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (size_t i = 0; i < n; i++) {
+        if (h_st[i] == CRYO_E_VERIFY) return verify_failure(c, i);
         if (h_st[i] != CRYO_OK) return h_st[i];
         if (h_sz[i] == 0 || h_sz[i] > bound) return CRYO_E_HIP;
         out_size[i] = h_sz[i];
@@ -1515,6 +1714,7 @@ int cryo_multi_compress_blocks(cryo_multi *m, int method, int param, const void 
     if (n == 0) return CRYO_OK;
     if (!h_src || !h_dst || !h_out_size) return CRYO_E_ARG;
     if (dst_stride < cryo_codec_bound(method, block_size)) return CRYO_E_DSTSIZE;
+    for (cryo_codec *c : m->h) c->vfy_failed = false; /* a handle with no share in this call reports nothing */
     if (m->h.size() == 1) return cryo_codec_compress_blocks(m->h[0], method, param, h_src, block_size, n, h_dst, dst_stride, h_out_size);
     return guarded([&] {
         return multi_run(m, n, [&](size_t g, const std::vector<size_t> &idx) {
@@ -1527,6 +1727,8 @@ int cryo_multi_compress_blocks(cryo_multi *m, int method, int param, const void 
             }
             const int rc = compress_blocks_ptrs(m->h[g], method, param, src.data(), block_size, idx.size(), dst.data(), sz.data());
             if (rc == CRYO_OK) for (size_t k = 0; k < idx.size(); k++) h_out_size[idx[k]] = sz[k];
+            if (rc == CRYO_E_VERIFY && m->h[g]->vfy_failed) /* the block's index in the whole call */
+                set_verify_failure(m->h[g], idx[m->h[g]->vfy_block], m->h[g]->vfy_off);
             return rc;
         });
     });
@@ -1643,6 +1845,15 @@ int cryo_multi_pool_invalidate(cryo_multi *m, uint32_t key_hi, int all_entries)
         if (rc != CRYO_OK) return rc;
     }
     return CRYO_OK;
+}
+
+int cryo_multi_last_verify_failure(const cryo_multi *m, uint64_t *block, uint32_t *first_mismatch)
+{
+    if (!m) return CRYO_E_ARG;
+    const cryo_codec *hit = nullptr;
+    for (const cryo_codec *c : m->h)
+        if (c->vfy_failed && (!hit || c->vfy_block < hit->vfy_block)) hit = c;
+    return hit ? cryo_codec_last_verify_failure(hit, block, first_mismatch) : 0;
 }
 
 int cryo_multi_get_transfer_counters(const cryo_multi *m, cryo_codec_transfer_counters *out)

@@ -172,6 +172,17 @@ hipError_t launch_zstd_seg_concat(hipStream_t s, uint64_t n_blocks, uint32_t nse
                                   const uint32_t *d_seg_size, uint32_t *d_seg_off, const uint8_t *head, uint32_t head_len,
                                   uint32_t bound, uint8_t *d_dst, uint64_t dst_stride, uint32_t *d_out_size, int32_t *d_status);
 
+/* write verification (verify.hip): the stream table of a chunk's decode, the compare, the per-block verdict.  e0 / e1: the
+ * "edge" blocks whose slots were copied into padded workspace (~0: none) */
+hipError_t launch_verify_prep(hipStream_t s, uint64_t lo, uint32_t cnt, const uint64_t *d_comp_off, uint64_t comp_stride,
+                              const uint32_t *d_comp_size, const int32_t *d_enc_status, uint64_t e0, uint64_t e1,
+                              uint64_t edge_stride, uint64_t *d_off, uint32_t *d_size, uint32_t *d_first);
+hipError_t launch_verify_compare(hipStream_t s, const uint8_t *d_raw, uint64_t raw_stride, const uint8_t *d_dec,
+                                 uint64_t dec_stride, uint32_t block_size, uint64_t lo, uint32_t cnt, const uint32_t *d_size,
+                                 const int32_t *d_dec_status, uint64_t e0, uint64_t e1, uint32_t *d_first);
+hipError_t launch_verify_fold(hipStream_t s, uint64_t lo, uint32_t cnt, const uint32_t *d_size, const int32_t *d_dec_status,
+                              uint64_t e0, uint64_t e1, bool has_enc_status, int32_t *d_status, uint32_t *d_first);
+
 } // namespace cryo
 
 #define CRYO_WAVE 64

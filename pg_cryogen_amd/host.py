@@ -22,12 +22,14 @@ COMPRESS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c
 DECOMPRESS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_size_t,
                             C.c_void_p, C.c_size_t, C.POINTER(C.c_int32))
 ERROR_HANDLER = C.CFUNCTYPE(None, C.c_int, C.c_char_p)
+VERIFY_FAILURE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32))
 
 
 class CryoCodecOps(C.Structure):
     _fields_ = [("bound", BOUND_FN), ("compress_blocks", COMPRESS_FN), ("decompress_blocks", DECOMPRESS_FN),
                 ("ctx", C.c_void_p), ("decompress_blocks_scatter", C.c_void_p),      # optional members: NULL in test doubles
-                ("decompress_blocks_keyed", C.c_void_p), ("pool_invalidate", C.c_void_p)]
+                ("decompress_blocks_keyed", C.c_void_p), ("pool_invalidate", C.c_void_p),
+                ("last_verify_failure", C.c_void_p)]
 
 
 class CryoRel(C.Structure):

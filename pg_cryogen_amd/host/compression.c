@@ -32,6 +32,7 @@ int cryo_gpu_pool_mb_guc = 0;
 int cryo_gpu_workspace_keep_mb_guc = 1024; /* device workspace a backend keeps between calls (-1: everything) */
 int cryo_gpu_encode_segment_kb_guc = 0;    /* segment-parallel encode, KiB (0: the byte-identical encoders) */
 int cryo_gpu_encode_segment_zstd_strategy_guc = 1; /* highest zstd strategy segment mode takes (1: `fast`) */
+int cryo_gpu_verify_writes_guc = 0;       /* write verification (0: off) */
 int cryo_gpu_readahead_blocks_guc = 8;    /* cryo blocks a sequential scan's cache miss decodes with one codec call (1: only the block asked for) */
 Size cryo_blcksz = (Size)1 << 20; /* CRYO_BLCKSZ, reference storage.h:18 */
 
@@ -41,7 +42,7 @@ Size cryo_blcksz = (Size)1 << 20; /* CRYO_BLCKSZ, reference storage.h:18 */
  * dispatcher of include/cryo_codec.h (block i of a call -> GPU i mod G, one host thread per GPU). */
 static cryo_multi *hip_multi;
 static int hip_multi_first = -1, hip_multi_count = 0, hip_pool_mb = 0, hip_keep_mb = -2, hip_seg_kb = 0,
-           hip_seg_strategy = 1;
+           hip_seg_strategy = 1, hip_verify = 0;
 /* A failed open is remembered until the GUCs change -- for good when the machine has no GPU (deterministic), for
  * CRYO_OPEN_RETRY_SECONDS when devices exist but cryo_multi_open failed (out of device memory, a busy device: transient;
  * a pooled backend must not refuse every cryo table for the rest of its life because of one bad moment). */
@@ -76,9 +77,13 @@ static int hip_decompress_blocks_keyed(void *ctx, int method, const uint64_t *ke
 }
 /* relid 0 (InvalidOid): PostgreSQL's relcache callback after a sinval-queue reset -- "anything may have changed": every entry */
 static void hip_pool_invalidate(void *ctx, uint32_t relid) { (void)cryo_multi_pool_invalidate((cryo_multi *)ctx, relid, relid == 0u); }
+static int hip_last_verify_failure(void *ctx, uint64_t *block, uint32_t *first_mismatch)
+{
+    return cryo_multi_last_verify_failure((cryo_multi *)ctx, block, first_mismatch);
+}
 
 static CryoCodecOps hip_ops = {hip_bound, hip_compress_blocks, hip_decompress_blocks, NULL, hip_decompress_blocks_scatter,
-                               hip_decompress_blocks_keyed, hip_pool_invalidate};
+                               hip_decompress_blocks_keyed, hip_pool_invalidate, hip_last_verify_failure};
 static const CryoCodecOps *bound_ops; /* CPU-only plumbing tests bind a double here (CRYO_HOST_TEST_HOOKS builds only) */
 
 #ifdef CRYO_HOST_TEST_HOOKS
@@ -126,6 +131,7 @@ const CryoCodecOps *cryo_host_codec_ops(void)
         hip_keep_mb = -2;
         hip_seg_kb = 0;
         hip_seg_strategy = 1;
+        hip_verify = 0;
         hip_ops.ctx = hip_multi;
     }
     if (hip_keep_mb != cryo_gpu_workspace_keep_mb_guc) { /* a backend is long-lived: one large call must not pin its workspace for good */
@@ -144,6 +150,10 @@ const CryoCodecOps *cryo_host_codec_ops(void)
         cryo_encode_segment_zstd_strategy_valid(cryo_gpu_encode_segment_zstd_strategy_guc)) {
         hip_seg_strategy = cryo_gpu_encode_segment_zstd_strategy_guc;
         (void)cryo_multi_set_option(hip_multi, CRYO_OPT_ENCODE_SEGMENT_ZSTD_STRATEGY, (int64_t)hip_seg_strategy);
+    }
+    if (hip_verify != (cryo_gpu_verify_writes_guc != 0)) {
+        hip_verify = cryo_gpu_verify_writes_guc != 0;
+        (void)cryo_multi_set_option(hip_multi, CRYO_OPT_ENCODE_VERIFY, (int64_t)hip_verify);
     }
     return &hip_ops;
 }
@@ -240,6 +250,19 @@ void cryo_define_compression_gucs(void)
                              "stops being byte-identical to libzstd's).",
                              NULL, &cryo_gpu_encode_segment_zstd_strategy_guc, 1, encode_segment_zstd_strategy_options,
                              PGC_USERSET, 0, NULL, NULL, NULL);
+    /* a boolean, spelt as PostgreSQL's own on/off enums are (synchronous_commit, huge_pages).  The hidden entries are every
+     * other spelling parse_bool() takes -- true / false / yes / no and their unique prefixes, "of", 1 / 0 -- so that any value
+     * a bool GUC accepts is accepted here too (enum names match case-insensitively, as bool values do) */
+    static const struct config_enum_entry verify_writes_options[] = {
+        {"off", 0, false}, {"on", 1, false},
+        {"true", 1, true}, {"tru", 1, true}, {"tr", 1, true}, {"t", 1, true},
+        {"false", 0, true}, {"fals", 0, true}, {"fal", 0, true}, {"fa", 0, true}, {"f", 0, true},
+        {"yes", 1, true}, {"ye", 1, true}, {"y", 1, true}, {"no", 0, true}, {"n", 0, true},
+        {"of", 0, true}, {"1", 1, true}, {"0", 0, true}, {NULL, 0, false}};
+    DefineCustomEnumVariable("pg_cryogen.gpu_verify_writes",
+                             "Decode every block the GPU compressed and compare it with the input before it is written "
+                             "(a block that fails raises ERROR, so the transaction aborts before any page is written).",
+                             NULL, &cryo_gpu_verify_writes_guc, 0, verify_writes_options, PGC_USERSET, 0, NULL, NULL, NULL);
 #else
     /* no GUC machinery without PostgreSQL: the variables keep the reference's defaults */
     compression_method_guc = COMP_ZSTD;
@@ -272,8 +295,15 @@ char *cryo_compress(CompressionMethod method, const char *data, Size *compressed
     rc = ops->compress_blocks(ops->ctx, (int)method, method_param(method), data, cryo_blcksz, 1, compressed,
                               estimate, &csize);
     if (rc != 0 || csize == 0) {
+        uint64_t vblock = 0;
+        uint32_t voff = 0xFFFFFFFFu;
         pfree(compressed);
-        if (rc == CRYO_E_UNSUPPORTED)   /* same ERROR as the reference, with the reason (this build has no kernel for it) */
+        if (rc == CRYO_E_VERIFY) {   /* pg_cryogen.gpu_verify_writes: the block never reaches a page */
+            if (ops->last_verify_failure && ops->last_verify_failure(ops->ctx, &vblock, &voff) == 1 && voff != 0xFFFFFFFFu)
+                elog(ERROR, "pg_cryogen: compressed block failed verification at byte %u", voff);
+            else
+                elog(ERROR, "pg_cryogen: compressed block failed verification (its stream does not decode)");
+        } else if (rc == CRYO_E_UNSUPPORTED)   /* same ERROR as the reference, with the reason (this build has no kernel for it) */
             elog(ERROR, "pg_cryogen: compression failed (no GPU kernel for %s parameter %d at block size %lu)",
                  method == COMP_LZ4 ? "lz4" : "zstd", method_param(method), (unsigned long)cryo_blcksz);
         else

@@ -55,6 +55,9 @@ int cryo_encode_segment_kb_valid(int kb);
  * deepest zstd strategy segment mode takes (CRYO_OPT_ENCODE_SEGMENT_ZSTD_STRATEGY; no effect while the segment size is 0) */
 extern int cryo_gpu_encode_segment_zstd_strategy_guc;
 int cryo_encode_segment_zstd_strategy_valid(int strategy);
+/* pg_cryogen.gpu_verify_writes (on/off, default off): every compress call decodes what the GPU encoded and compares it with
+ * the input before the block is handed back (CRYO_OPT_ENCODE_VERIFY); a block that fails raises ERROR */
+extern int cryo_gpu_verify_writes_guc;
 extern int cryo_gpu_readahead_blocks_guc;  /* pg_cryogen.gpu_readahead_blocks (default 8, 1 = off): host/cache.c, cryo_read_data_rel */
 /* bytes the codec moved towards the device / back, blocks served from the pool / decoded (0 when no GPU codec is bound) */
 void cryo_host_transfer_counters(uint64_t *h2d_bytes, uint64_t *d2h_bytes, uint64_t *pool_hits, uint64_t *pool_misses);
@@ -78,6 +81,9 @@ typedef struct CryoCodecOps {
                                    size_t n, void *const *dst, size_t block_size, int32_t *status);
     /* optional (may be NULL): forget the pooled blocks of a relation (reference: relcache callback, pg_cryogen.c:163-167) */
     void (*pool_invalidate)(void *ctx, uint32_t relid);
+    /* optional (may be NULL): after compress_blocks returned CRYO_E_VERIFY, the failing block and its first differing byte
+     * (0xFFFFFFFF: the decoders reject its stream); 1 when there is one (cryo_multi_last_verify_failure) */
+    int (*last_verify_failure)(void *ctx, uint64_t *block, uint32_t *first_mismatch);
 } CryoCodecOps;
 #ifdef CRYO_HOST_TEST_HOOKS
 void cryo_host_set_codec_ops(const CryoCodecOps *ops); /* test builds only: bind a double; NULL restores the HIP binding */
