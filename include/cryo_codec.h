@@ -124,7 +124,19 @@ typedef enum {
      * CRYO_E_VERIFY: d_status[i] of cryo_codec_compress_batch; the return value of the host-buffer calls, with the block's
      * index and first differing byte in cryo_codec_last_error() and cryo_codec_last_verify_failure().  The output bytes are
      * the same with verification on or off.  Other values: CRYO_E_ARG. */
-    CRYO_OPT_ENCODE_VERIFY = 12
+    CRYO_OPT_ENCODE_VERIFY = 12,
+    /* zstd content checksums: 0 (default) = none, exactly the bytes written before this option existed; 1 = every zstd frame
+     * written by every compress entry point (cryo_codec_compress_batch, _block, _blocks, cryo_multi_compress_blocks via
+     * cryo_multi_set_option) carries one: the checksum flag in its frame header and the low 32 bits of XXH64 (seed 0) of the
+     * block's input after its last block (RFC 8878 3.1.1), 4 bytes more per block.  The frames are libzstd's with
+     * ZSTD_c_checksumFlag = 1, byte for byte, wherever the byte-identical encoders write them; segment mode
+     * (CRYO_OPT_ENCODE_SEGMENT_BYTES) adds the same flag and trailer to its own frames.  Stock ZSTD_decompress checks the
+     * checksum of every frame it reads, and so do the decoders here, on every route.  It costs one pass over the input after
+     * the encode (bound by memory reads on large calls) and one over the output after a decode; a single frame of B bytes
+     * is hashed by one quad of lanes: about 2 ms for a lone 1 MiB frame.  cryo_codec_bound is unchanged: the frame and its
+     * checksum stay within ZSTD_compressBound.  LZ4 blocks have no checksum field: no effect on them.  Other values:
+     * CRYO_E_ARG. */
+    CRYO_OPT_ZSTD_CHECKSUM = 13
 } cryo_option;
 int cryo_codec_set_option(cryo_codec *c, int option, int64_t value);
 /* a long-lived backend between bursts: waits for the handle's queued work, then frees its device workspace, the device and

@@ -27,6 +27,7 @@ OPT_WORKSPACE_KEEP_BYTES, OPT_WORKSPACE_MAX_BYTES, OPT_NUMA_LOCAL = 6, 7, 8
 OPT_ENCODE_SEGMENT_BYTES = 10  # 0 = byte-identical encoders; 4 KiB .. 128 KiB (power of two) = segment-parallel encode
 OPT_ENCODE_SEGMENT_ZSTD_STRATEGY = 11  # highest zstd strategy of segment mode: 1 fast (default) .. 6 btlazy2
 OPT_ENCODE_VERIFY = 12  # 0 (default) = none; 1 = every compress call decodes its output and compares it with the input
+OPT_ZSTD_CHECKSUM = 13  # 0 (default) = none; 1 = every zstd frame written carries a content checksum (XXH64)
 VERIFY_NONE = 0xFFFFFFFF  # first-mismatch offset of a block that verified (or whose stream the decoders reject)
 LZ4_PATH_AUTO, LZ4_PATH_RING, LZ4_PATH_INDEXED, LZ4_PATH_FEW_BLOCKS = 0, 1, 2, 3
 

@@ -163,6 +163,7 @@ struct cryo_codec {
      * the verification decodes (grow-only, given back like the host-buffer staging); the per-block first-mismatch words of
      * the last verified compress; the failure the last host-buffer compress call returned */
     int verify = 0;
+    int zstd_checksum = 0;  /* CRYO_OPT_ZSTD_CHECKSUM */
     uint8_t *d_vfy = nullptr;
     size_t vfy_cap = 0;
     uint32_t *vfy_first = nullptr;
@@ -557,6 +558,10 @@ int cryo_codec_set_option(cryo_codec *c, int option, int64_t value)
         if (value != 0 && value != 1) return CRYO_E_ARG;
         c->verify = (int)value;
         return CRYO_OK;
+    case CRYO_OPT_ZSTD_CHECKSUM:
+        if (value != 0 && value != 1) return CRYO_E_ARG;
+        c->zstd_checksum = (int)value;
+        return CRYO_OK;
     case CRYO_OPT_POOL_BYTES: {
         if (value < 0) return CRYO_E_ARG;
         DevGuard dev_(c);
@@ -585,6 +590,7 @@ int cryo_codec_get_option(const cryo_codec *c, int option, int64_t *value)
     case CRYO_OPT_ENCODE_SEGMENT_BYTES: *value = c->enc_seg; return CRYO_OK;
     case CRYO_OPT_ENCODE_SEGMENT_ZSTD_STRATEGY: *value = c->enc_seg_zstd_strategy; return CRYO_OK;
     case CRYO_OPT_ENCODE_VERIFY: *value = c->verify; return CRYO_OK;
+    case CRYO_OPT_ZSTD_CHECKSUM: *value = c->zstd_checksum; return CRYO_OK;
     default: return CRYO_E_ARG;
     }
 }
@@ -688,7 +694,7 @@ int cryo_codec_compress_batch(cryo_codec *c, int method, int param, const void *
         if (rc != CRYO_OK) return rc;
         HIP_TRY(c, cryo::launch_zstd_compress_segmented(c->stream, (const uint8_t *)d_src, src_stride, block_size, n_blocks,
                                                         (uint8_t *)d_dst, dst_stride, param, S, d_out_size, d_status, c->d_ws,
-                                                        c->ws_cap));
+                                                        c->ws_cap, c->zstd_checksum ? 4u : 0u));
     } else if (method == CRYO_METHOD_LZ4) {
         HIP_TRY(c, cryo::launch_lz4_compress(c->stream, (const uint8_t *)d_src, src_stride, block_size,
                                              n_blocks, (uint8_t *)d_dst, dst_stride, param,
@@ -703,6 +709,10 @@ int cryo_codec_compress_batch(cryo_codec *c, int method, int param, const void *
                                               (uint8_t *)d_dst, dst_stride, param, d_out_size, d_status, c->d_ws,
                                               c->ws_cap));
     }
+    /* content checksums (CRYO_OPT_ZSTD_CHECKSUM): the frames above plus the flag and XXH64 of the input, both zstd paths */
+    if (method == CRYO_METHOD_ZSTD && c->zstd_checksum)
+        HIP_TRY(c, cryo::launch_zstd_checksum_append(c->stream, (const uint8_t *)d_src, src_stride, block_size, n_blocks,
+                                                     (uint8_t *)d_dst, dst_stride, d_out_size, d_status));
     c->ctr.blocks_compressed += n_blocks;
     c->ctr.bytes_in += n_blocks * (uint64_t)block_size;
     c->ctr.launches++;

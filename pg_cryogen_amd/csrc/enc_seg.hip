@@ -213,7 +213,7 @@ k_lz4_seg_copy(const uint8_t *__restrict__ src_base, uint64_t src_stride, uint64
 struct ZHead { uint8_t b[16]; uint32_t len; };
 __global__ void __launch_bounds__(64)
 k_zstd_seg_plan(uint64_t n_blocks, uint32_t nseg, const uint32_t *__restrict__ seg_size, uint32_t *__restrict__ seg_off,
-                ZHead head, uint32_t bound, uint8_t *__restrict__ dst_base, uint64_t dst_stride, uint32_t *__restrict__ out_size,
+                ZHead head, uint32_t bound, uint32_t trailer, uint8_t *__restrict__ dst_base, uint64_t dst_stride, uint32_t *__restrict__ out_size,
                 int32_t *__restrict__ status)
 {
     const uint32_t lane = threadIdx.x & 63u;
@@ -229,7 +229,8 @@ k_zstd_seg_plan(uint64_t n_blocks, uint32_t nseg, const uint32_t *__restrict__ s
         if (i < nseg) seg_off[first + i] = off + incl - sz;
         off += lane_get(incl, 63u);
     }
-    const bool fits = off <= bound; /* ceil(B / S) block headers of 3 bytes, raw blocks at worst: always within bound */
+    /* ceil(B / S) block headers of 3 bytes, raw blocks at worst, and a content checksum (trailer): always within bound */
+    const bool fits = off + trailer <= bound;
     if (!fits)
         for (uint32_t i = lane; i < nseg; i += 64u) seg_off[first + i] = 0xFFFFFFFFu;
     if (lane == 0) { out_size[blk] = fits ? off : 0u; status[blk] = fits ? CRYO_ST_OK : -5 /* CRYO_E_DSTSIZE */; }
@@ -310,13 +311,14 @@ uint64_t zstd_seg_slot_stride(uint32_t seg_bytes) { return zstd_seg_stride(seg_b
 
 hipError_t launch_zstd_seg_concat(hipStream_t s, uint64_t n_blocks, uint32_t nseg, uint32_t seg_bytes, const uint8_t *d_seg,
                                   const uint32_t *d_seg_size, uint32_t *d_seg_off, const uint8_t *head, uint32_t head_len,
-                                  uint32_t bound, uint8_t *d_dst, uint64_t dst_stride, uint32_t *d_out_size, int32_t *d_status)
+                                  uint32_t bound, uint32_t trailer, uint8_t *d_dst, uint64_t dst_stride, uint32_t *d_out_size,
+                                  int32_t *d_status)
 {
     ZHead h = {};
     for (uint32_t i = 0; i < head_len && i < 16u; i++) h.b[i] = head[i];
     h.len = head_len;
     hipLaunchKernelGGL(k_zstd_seg_plan, dim3((uint32_t)n_blocks), dim3(64), 0, s, n_blocks, nseg, d_seg_size, d_seg_off, h, bound,
-                       d_dst, dst_stride, d_out_size, d_status);
+                       trailer, d_dst, dst_stride, d_out_size, d_status);
     hipLaunchKernelGGL(k_zstd_seg_copy, dim3((uint32_t)(n_blocks * nseg)), dim3(64), 0, s, n_blocks, nseg, d_seg,
                        zstd_seg_stride(seg_bytes), d_seg_size, d_seg_off, d_dst, dst_stride);
     return hipGetLastError();

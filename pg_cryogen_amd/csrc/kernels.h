@@ -162,15 +162,24 @@ hipError_t launch_lz4_compress_segmented(hipStream_t s, const uint8_t *d_src, ui
 /* the level's strategy lies in 1 (`fast`) .. max_strategy (at most 6, `btlazy2`; CRYO_OPT_ENCODE_SEGMENT_ZSTD_STRATEGY) */
 bool zstd_segment_supported(int level, uint32_t block_size, int max_strategy);
 size_t zstd_compress_segmented_workspace(uint64_t n_blocks, int level, uint32_t block_size, uint32_t seg_bytes);
+/* trailer: bytes the frame must leave room for behind its last block within the bound (4: a content checksum follows) */
 hipError_t launch_zstd_compress_segmented(hipStream_t s, const uint8_t *d_src, uint64_t src_stride, uint32_t block_size,
                                           uint64_t n_blocks, uint8_t *d_dst, uint64_t dst_stride, int level, uint32_t seg_bytes,
-                                          uint32_t *d_out_size, int32_t *d_status, void *d_workspace, size_t workspace_bytes);
+                                          uint32_t *d_out_size, int32_t *d_status, void *d_workspace, size_t workspace_bytes,
+                                          uint32_t trailer = 0);
 /* enc_seg.hip internals shared with zstd_enc.hip */
 size_t zstd_seg_scratch_bytes(uint64_t items, uint32_t seg_bytes);
 uint64_t zstd_seg_slot_stride(uint32_t seg_bytes);
 hipError_t launch_zstd_seg_concat(hipStream_t s, uint64_t n_blocks, uint32_t nseg, uint32_t seg_bytes, const uint8_t *d_seg,
                                   const uint32_t *d_seg_size, uint32_t *d_seg_off, const uint8_t *head, uint32_t head_len,
-                                  uint32_t bound, uint8_t *d_dst, uint64_t dst_stride, uint32_t *d_out_size, int32_t *d_status);
+                                  uint32_t bound, uint32_t trailer, uint8_t *d_dst, uint64_t dst_stride, uint32_t *d_out_size,
+                                  int32_t *d_status);
+
+/* content checksums of zstd frames (xxh64.hip, CRYO_OPT_ZSTD_CHECKSUM): for every block whose status is CRYO_OK, the frame's
+ * checksum flag, XXH64 of its B input bytes (low 32 bits) at d_dst + out_size[i], and out_size[i] + 4 */
+hipError_t launch_zstd_checksum_append(hipStream_t s, const uint8_t *d_src, uint64_t src_stride, uint32_t block_size,
+                                       uint64_t n_blocks, uint8_t *d_dst, uint64_t dst_stride, uint32_t *d_out_size,
+                                       int32_t *d_status);
 
 /* write verification (verify.hip): the stream table of a chunk's decode, the compare, the per-block verdict.  e0 / e1: the
  * "edge" blocks whose slots were copied into padded workspace (~0: none) */

@@ -511,7 +511,8 @@ __device__ int huf_read_table(LT &L, uint16_t *table, const uint8_t *src, const 
     return used;
 }
 
-/* XXH64 of the decoded frame (content checksum); wave-uniform, rare path */
+/* XXH64 of the decoded frame (content checksum) in one wave, every lane the same value: the fused decoder's frames only (the
+ * pipeline checks its frames in batches, k_zck in zstd_pipe.hip) */
 __device__ inline uint64_t rotl64(uint64_t x, int r) { return (x << r) | (x >> (64 - r)); }
 __device__ uint64_t xxh64_dev(const uint8_t *p, uint32_t len)
 {

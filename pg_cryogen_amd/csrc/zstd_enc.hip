@@ -1606,7 +1606,8 @@ size_t zstd_compress_segmented_workspace(uint64_t n_blocks, int level, uint32_t 
 }
 hipError_t launch_zstd_compress_segmented(hipStream_t s, const uint8_t *d_src, uint64_t src_stride, uint32_t block_size,
                                           uint64_t n_blocks, uint8_t *d_dst, uint64_t dst_stride, int level, uint32_t seg_bytes,
-                                          uint32_t *d_out_size, int32_t *d_status, void *d_workspace, size_t workspace_bytes)
+                                          uint32_t *d_out_size, int32_t *d_status, void *d_workspace, size_t workspace_bytes,
+                                          uint32_t trailer)
 {
     if (n_blocks == 0) return hipSuccess;
     ZSegPar q;
@@ -1630,7 +1631,8 @@ hipError_t launch_zstd_compress_segmented(hipStream_t s, const uint8_t *d_src, u
     hipLaunchKernelGGL((k_zstd_enc<false, false>), dim3(grid), dim3(64), 0, s, d_src, src_stride, block_size, n_blocks, d_seg, slot, wlog,
                        hlog, clog, mml, tlen, finder, width, d_seg_size, d_status, ws, (uint64_t)stride, nullptr, seg_bytes, nseg,
                        q.seed);
-    /* the frame header of the byte-identical path (k_zstd_enc): content size, no checksum */
+    /* the frame header of the byte-identical path (k_zstd_enc): content size, no checksum (launch_zstd_checksum_append adds
+     * one behind the `trailer` bytes the plan leaves room for) */
     uint8_t head[16];
     uint32_t hl = 0;
     {
@@ -1647,7 +1649,7 @@ hipError_t launch_zstd_compress_segmented(hipStream_t s, const uint8_t *d_src, u
     }
     const size_t b = block_size;
     const uint32_t bound = (uint32_t)(b + (b >> 8) + (b < (128u << 10) ? ((128u << 10) - b) >> 11 : 0u));
-    return launch_zstd_seg_concat(s, n_blocks, nseg, seg_bytes, d_seg, d_seg_size, d_seg_off, head, hl, bound, d_dst, dst_stride,
+    return launch_zstd_seg_concat(s, n_blocks, nseg, seg_bytes, d_seg, d_seg_size, d_seg_off, head, hl, bound, trailer, d_dst, dst_stride,
                                   d_out_size, d_status);
 }
 

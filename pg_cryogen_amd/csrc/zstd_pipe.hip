@@ -22,6 +22,7 @@
  *   K4  k_zexec   wave per frame   sequence execution with the shared LZ copy engine (lz_common.h): 8-byte records
  *                                  loaded 64 at a time, literals stream through the LDS input ring, output ring in
  *                                  LDS, 1 KiB coalesced flushes
+ *   K5  k_zck     quad per frame   content checksums of the frames that carry one (XXH64, xxh64.h), 16 frames per wave
  *
  * Anything K1 does not recognise as "one well-formed frame of at most nbmax blocks" (concatenated or
  * skippable frames, malformed headers, pool exhaustion) is put on an irregular list and decoded by the
@@ -34,6 +35,7 @@
 #include "lz4_copy.h"
 #include "kernels.h"
 #include "lat_copy.h"
+#include "xxh64.h"
 #include <cstdio>
 #include <cstdlib>
 
@@ -1724,14 +1726,7 @@ __global__ void __launch_bounds__(64, kZexecOcc) k_zexec(ZPipe P)
         const uint64_t fcs = (uint64_t)uni(P.frames[f].fcs_lo) | ((uint64_t)uni(P.frames[f].fcs_hi) << 32);
         if ((uint64_t)w.op != fcs) bad = true;
     }
-    if (!bad && (flags & F_CK)) {
-        w.flush();
-        w.flush_tail();
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        uint32_t want;
-        __builtin_memcpy(&want, src + uni(P.frames[f].ck_off), 4);
-        if ((uint32_t)xxh64_dev(w.dst, w.op) != uni(want)) bad = true;
-    }
+    if (!bad && (flags & F_CK)) { w.flush(); w.flush_tail(); } /* the checksum: k_zck, once the call's frames are out */
     if (!bad && w.op != B) bad = true;
     if (!bad) { w.flush(); w.flush_tail(); }
     if (lane == 0) P.status[blk] = bad ? CRYO_ST_CORRUPT : CRYO_ST_OK;
@@ -1743,7 +1738,7 @@ __global__ void __launch_bounds__(64, kZexecOcc) k_zexec(ZPipe P)
  * the sequences explicit, executing them is the problem lz4_lat.hip solves for LZ4 blocks: output positions by a prefix sum,
  * literal bytes placed and every match byte pointed at its source, pointer jumping, gather (lat_copy.h).  For calls of up
  * to 64 frames and 64 MiB:
- *   k_zlat_count  per frame: is it one this path takes (no checksum to verify, no RLE literals, it says B bytes), the
+ *   k_zlat_count  per frame: is it one this path takes (no RLE literals, it says B bytes; a checksum is k_zck's), the
  *                 place of every zstd block's sequences in the frame's flat list
  *   k_zlat_build  per zstd block: its records -> ll / ml / offset / where the literals lie (input: raw literals, raw and
  *                 RLE blocks; bit 31: the frame's pool of Huffman literals), by a scan of the literal lengths; the block's
@@ -1759,7 +1754,7 @@ __global__ void __launch_bounds__(64) k_zlat_count(ZPipe P, LatArgs A, uint32_t 
     const uint32_t f = blockIdx.x;
     if (threadIdx.x != 0u) return;
     const ZFrame fr = P.frames[f];
-    bool ok = (fr.flags & (F_IRREG | F_BAD | F_CK)) == 0u;
+    bool ok = (fr.flags & (F_IRREG | F_BAD)) == 0u;
     if ((fr.flags & F_FCS) && !(fr.fcs_hi == 0u && fr.fcs_lo == P.B)) ok = false;
     uint32_t total = 0;
     for (uint32_t k = 0; k < fr.nblk; k++) {
@@ -1868,6 +1863,25 @@ __global__ void __launch_bounds__(256) k_zlat_place(LatArgs A)
         const uint32_t off = A.off[q];
         if (ml != 0u && (off == 0u || off > op + ll)) A.ok[f] = 0u; /* k_zexec's rule: the offset may not reach before the output */
     }
+}
+
+/* ------------------------------------------------------------------------------------------- content checksums
+ * A frame with a checksum is decoded like one without (k_zexec or the few-frames route), then this checks it: a quad of lanes
+ * per frame, 16 frames per wave (xxh64.h), XXH64 of the B bytes out against the 4 bytes the frame carries.  A frame whose
+ * status is CRYO_OK has put out exactly B bytes; a mismatch turns it into CRYO_E_CORRUPT.  Irregular frames are the fused
+ * decoder's, which checks them itself. */
+__global__ void __launch_bounds__(64) k_zck(ZPipe P)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t lds[kXxLdsPerWave];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t f = blockIdx.x * kXxBlocksPerWave + (lane >> 2);
+    const uint64_t blk = P.first + f;
+    const bool on = f < P.F && (P.frames[f].flags & (F_CK | F_IRREG | F_BAD)) == F_CK && P.status[blk] == CRYO_ST_OK;
+    const uint64_t h = xxh64_quad(on ? P.dst_base + blk * P.dst_stride : P.dst_base, on ? P.B : 0u, lds, lane);
+    if (!on || (lane & 3u) != 0u) return;
+    uint32_t want;
+    __builtin_memcpy(&want, P.src_base + P.src_off[blk] + P.frames[f].ck_off, 4);
+    if ((uint32_t)h != want) P.status[blk] = CRYO_ST_CORRUPT;
 }
 
 } // namespace
@@ -2189,6 +2203,7 @@ hipError_t launch_zstd_decompress(hipStream_t s, const uint8_t *d_src, const uin
             P.done = A.done;
         }
         hipLaunchKernelGGL(k_zexec, dim3(P.F), dim3(64), 0, st, P);
+        hipLaunchKernelGGL(k_zck, dim3((P.F + kXxBlocksPerWave - 1u) / kXxBlocksPerWave), dim3(64), 0, st, P);
         const uint64_t fg = P.F < kFusedGridForIrregular ? P.F : kFusedGridForIrregular;
         static const bool skip_fused = cryo_tuning_env("CRYO_ZSTD_SKIP_FALLBACKS") != nullptr;
         if (!skip_fused)

@@ -33,6 +33,7 @@ int cryo_gpu_workspace_keep_mb_guc = 1024; /* device workspace a backend keeps b
 int cryo_gpu_encode_segment_kb_guc = 0;    /* segment-parallel encode, KiB (0: the byte-identical encoders) */
 int cryo_gpu_encode_segment_zstd_strategy_guc = 1; /* highest zstd strategy segment mode takes (1: `fast`) */
 int cryo_gpu_verify_writes_guc = 0;       /* write verification (0: off) */
+int cryo_gpu_zstd_checksum_guc = 0;       /* content checksums in the zstd frames the GPU writes (0: off) */
 int cryo_gpu_readahead_blocks_guc = 8;    /* cryo blocks a sequential scan's cache miss decodes with one codec call (1: only the block asked for) */
 Size cryo_blcksz = (Size)1 << 20; /* CRYO_BLCKSZ, reference storage.h:18 */
 
@@ -42,7 +43,7 @@ Size cryo_blcksz = (Size)1 << 20; /* CRYO_BLCKSZ, reference storage.h:18 */
  * dispatcher of include/cryo_codec.h (block i of a call -> GPU i mod G, one host thread per GPU). */
 static cryo_multi *hip_multi;
 static int hip_multi_first = -1, hip_multi_count = 0, hip_pool_mb = 0, hip_keep_mb = -2, hip_seg_kb = 0,
-           hip_seg_strategy = 1, hip_verify = 0;
+           hip_seg_strategy = 1, hip_verify = 0, hip_zstd_checksum = 0;
 /* A failed open is remembered until the GUCs change -- for good when the machine has no GPU (deterministic), for
  * CRYO_OPEN_RETRY_SECONDS when devices exist but cryo_multi_open failed (out of device memory, a busy device: transient;
  * a pooled backend must not refuse every cryo table for the rest of its life because of one bad moment). */
@@ -132,6 +133,7 @@ const CryoCodecOps *cryo_host_codec_ops(void)
         hip_seg_kb = 0;
         hip_seg_strategy = 1;
         hip_verify = 0;
+        hip_zstd_checksum = 0;
         hip_ops.ctx = hip_multi;
     }
     if (hip_keep_mb != cryo_gpu_workspace_keep_mb_guc) { /* a backend is long-lived: one large call must not pin its workspace for good */
@@ -154,6 +156,10 @@ const CryoCodecOps *cryo_host_codec_ops(void)
     if (hip_verify != (cryo_gpu_verify_writes_guc != 0)) {
         hip_verify = cryo_gpu_verify_writes_guc != 0;
         (void)cryo_multi_set_option(hip_multi, CRYO_OPT_ENCODE_VERIFY, (int64_t)hip_verify);
+    }
+    if (hip_zstd_checksum != (cryo_gpu_zstd_checksum_guc != 0)) {
+        hip_zstd_checksum = cryo_gpu_zstd_checksum_guc != 0;
+        (void)cryo_multi_set_option(hip_multi, CRYO_OPT_ZSTD_CHECKSUM, (int64_t)hip_zstd_checksum);
     }
     return &hip_ops;
 }
@@ -263,6 +269,10 @@ void cryo_define_compression_gucs(void)
                              "Decode every block the GPU compressed and compare it with the input before it is written "
                              "(a block that fails raises ERROR, so the transaction aborts before any page is written).",
                              NULL, &cryo_gpu_verify_writes_guc, 0, verify_writes_options, PGC_USERSET, 0, NULL, NULL, NULL);
+    DefineCustomEnumVariable("pg_cryogen.zstd_checksum",
+                             "Write a content checksum into every zstd frame the GPU compresses (stock zstd and every GPU decode "
+                             "route check it on each read; off = the frames libzstd writes by default).",
+                             NULL, &cryo_gpu_zstd_checksum_guc, 0, verify_writes_options, PGC_USERSET, 0, NULL, NULL, NULL);
 #else
     /* no GUC machinery without PostgreSQL: the variables keep the reference's defaults */
     compression_method_guc = COMP_ZSTD;

@@ -58,6 +58,9 @@ int cryo_encode_segment_zstd_strategy_valid(int strategy);
 /* pg_cryogen.gpu_verify_writes (on/off, default off): every compress call decodes what the GPU encoded and compares it with
  * the input before the block is handed back (CRYO_OPT_ENCODE_VERIFY); a block that fails raises ERROR */
 extern int cryo_gpu_verify_writes_guc;
+/* pg_cryogen.zstd_checksum (on/off, default off): every zstd frame the GPU writes carries a content checksum, which stock
+ * ZSTD_decompress and the GPU decoders check on every read (CRYO_OPT_ZSTD_CHECKSUM); no effect on LZ4 */
+extern int cryo_gpu_zstd_checksum_guc;
 extern int cryo_gpu_readahead_blocks_guc;  /* pg_cryogen.gpu_readahead_blocks (default 8, 1 = off): host/cache.c, cryo_read_data_rel */
 /* bytes the codec moved towards the device / back, blocks served from the pool / decoded (0 when no GPU codec is bound) */
 void cryo_host_transfer_counters(uint64_t *h2d_bytes, uint64_t *d2h_bytes, uint64_t *pool_hits, uint64_t *pool_misses);
