@@ -230,6 +230,48 @@ int cryo_codec_verify_batch(cryo_codec *c, int method, const void *d_raw, uint64
                             uint64_t n_blocks, const void *d_comp, const uint64_t *d_comp_off, const uint32_t *d_comp_size,
                             int32_t *d_status, uint32_t *d_first_mismatch);
 
+/* ---- checking stored blocks ----
+ * A decoded cryo block is checked against the layout that cryo_init_page / cryo_storage_insert (pg_cryogen_amd/host/
+ * storage.c; reference storage.c:15-50, include/cryo_synth.h) give every byte of a block except the tuple bodies.  The
+ * rules, for a block of B bytes (B a multiple of 8, at least 16; all fields LE u32):
+ *   lower at byte 0, upper at byte 4, n = (lower - 8) / 8; item i (0-based) is off_i at 8 + 8i and len_i at 12 + 8i;
+ *   MAXALIGN(x) = (x + 7) & ~7.
+ *   1. HEADER: lower >= 8, (lower - 8) % 8 == 0, n <= 290 (MaxHeapTuplesPerPage - 1), lower <= upper <= B, and upper == B
+ *      when n == 0.
+ *   2. ITEM i fails (in 64-bit arithmetic) when len_i == 0, or off_i + MAXALIGN(len_i) != (i == 0 ? B : off_{i-1}) --
+ *      off_{i-1} as stored in item i - 1 --, or i == n - 1 and off_i != upper.
+ *   3. NONZERO: a byte in [lower, upper) or in a pad [off_i + len_i, off_i + MAXALIGN(len_i)) is not zero.
+ * Each block gets one {reason, offset}; the first failing class wins:
+ *   CRYO_CHECK_OK       every rule holds                                      offset 0xFFFFFFFF
+ *   CRYO_CHECK_STREAM   the decoders reject the stream: malformed, other than   offset 0xFFFFFFFF
+ *                       B bytes, or a zstd content checksum mismatch
+ *   CRYO_CHECK_HEADER   rule 1                                                offset 0
+ *   CRYO_CHECK_ITEM     rule 2                                                offset 8 + 8i of the lowest failing item
+ *   CRYO_CHECK_NONZERO  rule 3, checked when rules 1 and 2 hold               offset of the lowest such byte
+ * What the check does not see: tuple bodies.  An LZ4 block has no checksum field, so a damaged LZ4 stream that still
+ * decodes to B bytes with an intact header, item array, gap and pads passes; a zstd frame written with
+ * CRYO_OPT_ZSTD_CHECKSUM has its whole content covered by the checksum (STREAM).  A checksum mismatch is not told apart
+ * from a malformed stream.  Tuple headers are not checked. */
+typedef enum {
+    CRYO_CHECK_OK = 0,
+    CRYO_CHECK_STREAM = 1,
+    CRYO_CHECK_HEADER = 2,
+    CRYO_CHECK_ITEM = 3,
+    CRYO_CHECK_NONZERO = 4
+} cryo_check_reason;
+typedef struct {
+    uint32_t reason, offset;
+} cryo_check_result;
+/* Check n_blocks stored blocks: stream i is the d_src_size[i] bytes at d_src + d_src_off[i] (the slack rule of
+ * cryo_dev_alloc applies, as for cryo_codec_decompress_batch); d_result[i] (device) gets its {reason, offset}.  Decoded
+ * with the automatic decode routes whatever the handle's decode-path options say, into handle workspace -- never into
+ * caller memory -- in chunks within CRYO_OPT_WORKSPACE_MAX_BYTES, as cryo_codec_verify_batch; the device pool is neither
+ * read nor filled, and nothing counts in cryo_codec_counters.  Asynchronous on the handle's stream.  CRYO_E_ARG: an
+ * unknown method, a block_size that is not a multiple of 8 or is below 16, a null pointer; n_blocks == 0: CRYO_OK. */
+int cryo_codec_check_batch(cryo_codec *c, int method, const void *d_src, const uint64_t *d_src_off,
+                           const uint32_t *d_src_size, uint32_t block_size, uint64_t n_blocks,
+                           cryo_check_result *d_result);
+
 /* ---- single block, HOST buffers: what cryo_compress()/cryo_decompress()
  *      (compression.c:125-159) call.  Synchronous: H2D, kernel, D2H. ---- */
 int cryo_codec_compress_block(cryo_codec *c, int method, int param,
@@ -260,6 +302,12 @@ int cryo_codec_decompress_blocks(cryo_codec *c, int method,
 int cryo_codec_decompress_blocks_to(cryo_codec *c, int method,
                                     const void *const *h_src, const uint32_t *h_src_size, size_t n_blocks,
                                     void *const *h_dst, size_t block_size, int32_t *h_status);
+/* cryo_codec_check_batch on host buffers (stream i: h_src[i], h_src_size[i] bytes), synchronous: the streams are staged
+ * and uploaded as by cryo_codec_decompress_blocks (pinned buffers, pipelined chunks from CRYO_OPT_PIPE_MIN_BYTES on);
+ * only the n_blocks * 8 bytes of h_result come back (the transfer counters: h2d_bytes what was uploaded, d2h_bytes
+ * exactly 8 * n_blocks).  Returns CRYO_OK when the batch ran, whatever the blocks' verdicts. */
+int cryo_codec_check_blocks(cryo_codec *c, int method, const void *const *h_src, const uint32_t *h_src_size,
+                            size_t n_blocks, size_t block_size, cryo_check_result *h_result);
 
 /* ---- device-resident block pool ("optional device-resident compressed/decompressed pool so
  *      repeated scans skip PCIe"; the reference's cache is host-only: cache.c:17-50).
@@ -320,6 +368,9 @@ int cryo_multi_get_transfer_counters(const cryo_multi *m, cryo_codec_transfer_co
 /* cryo_codec_last_verify_failure of the last cryo_multi_compress_blocks call (block: the index within the whole call; the
  * lowest one when several handles failed) */
 int cryo_multi_last_verify_failure(const cryo_multi *m, uint64_t *block, uint32_t *first_mismatch);
+/* cryo_codec_check_blocks across the devices: block i -> handle i mod G */
+int cryo_multi_check_blocks(cryo_multi *m, int method, const void *const *h_src, const uint32_t *h_src_size,
+                            size_t n_blocks, size_t block_size, cryo_check_result *h_result);
 
 /* ---- batch helpers used by staging, tests and the benchmark ---- */
 

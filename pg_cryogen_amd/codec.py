@@ -29,6 +29,9 @@ OPT_ENCODE_SEGMENT_ZSTD_STRATEGY = 11  # highest zstd strategy of segment mode: 
 OPT_ENCODE_VERIFY = 12  # 0 (default) = none; 1 = every compress call decodes its output and compares it with the input
 OPT_ZSTD_CHECKSUM = 13  # 0 (default) = none; 1 = every zstd frame written carries a content checksum (XXH64)
 VERIFY_NONE = 0xFFFFFFFF  # first-mismatch offset of a block that verified (or whose stream the decoders reject)
+# cryo_check_reason (include/cryo_codec.h): the verdict of the stored-block check, with the offset it reports
+CHECK_OK, CHECK_STREAM, CHECK_HEADER, CHECK_ITEM, CHECK_NONZERO = 0, 1, 2, 3, 4
+CHECK_NONE = 0xFFFFFFFF  # offset of CHECK_OK and CHECK_STREAM
 LZ4_PATH_AUTO, LZ4_PATH_RING, LZ4_PATH_INDEXED, LZ4_PATH_FEW_BLOCKS = 0, 1, 2, 3
 
 DIST_WIDE, DIST_NARROW, DIST_INT4, DIST_RANDOM, DIST_ZEROS = range(5)
@@ -53,6 +56,7 @@ ABI_SYMBOLS = [
     "cryo_codec_compare_batch", "cryo_checksum64", "cryo_codec_timer_start",
     "cryo_codec_timer_stop", "cryo_codec_get_counters",
     "cryo_codec_verify_batch", "cryo_codec_last_verify_failure", "cryo_multi_last_verify_failure",
+    "cryo_codec_check_batch", "cryo_codec_check_blocks", "cryo_multi_check_blocks",
 ]
 
 
@@ -137,6 +141,9 @@ def lib():
     L.cryo_codec_verify_batch.argtypes = [vp, i32, vp, u64, u32, u64, vp, vp, vp, vp, vp]
     L.cryo_codec_last_verify_failure.argtypes = [vp, C.POINTER(u64), C.POINTER(u32)]
     L.cryo_multi_last_verify_failure.argtypes = [vp, C.POINTER(u64), C.POINTER(u32)]
+    L.cryo_codec_check_batch.argtypes = [vp, i32, vp, vp, vp, u32, u64, vp]
+    L.cryo_codec_check_blocks.argtypes = [vp, i32, vp, vp, sz, sz, vp]
+    L.cryo_multi_check_blocks.argtypes = [vp, i32, vp, vp, sz, sz, vp]
     _bound = True
     return L
 
@@ -295,6 +302,22 @@ class Codec:
         self._chk(self.L.cryo_codec_verify_batch(self.h, method, d_raw.ptr, raw_stride, block_size, n, d_comp.ptr, d_off.ptr,
                                                  d_sizes.ptr, d_status.ptr, d_first.ptr if d_first else None),
                   "verify_batch")
+
+    def check_batch(self, method, d_src, d_off, d_sizes, block_size, n, d_result):
+        """check the n stored blocks (d_src + d_off[i], d_sizes[i] bytes): d_result[i] = {reason, offset} (CHECK_*), 8 bytes per
+        block.  Asynchronous."""
+        self._chk(self.L.cryo_codec_check_batch(self.h, method, d_src.ptr, d_off.ptr, d_sizes.ptr, block_size, n, d_result.ptr),
+                  "check_batch")
+
+    def check_blocks(self, method, comps, block_size):
+        """check host compressed blocks; returns an (n, 2) uint32 array of {reason, offset}"""
+        n = len(comps)
+        arrs = [np.ascontiguousarray(np.asarray(c, dtype=np.uint8)) for c in comps]
+        src = (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.nbytes else None for a in arrs])
+        szs = (C.c_uint32 * max(n, 1))(*[a.nbytes for a in arrs])
+        out = np.zeros((n, 2), np.uint32)
+        self._chk(self.L.cryo_codec_check_blocks(self.h, method, src, szs, n, block_size, out.ctypes.data), "check_blocks")
+        return out
 
     def last_verify_failure(self):
         """(block, first mismatch) that made the last host-buffer compress call fail verification, or None"""

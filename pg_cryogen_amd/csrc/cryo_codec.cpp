@@ -818,31 +818,57 @@ int cryo_codec_decompress_batch(cryo_codec *c, int method, const void *d_src,
     return decompress_routed(c, method, d_src, d_src_off, d_src_size, d_dst, dst_stride, block_size, n_blocks, d_status, false, 0);
 }
 
-/* ---- write verification ----
- * Decode the streams of n blocks with the automatic routes into handle workspace (c->d_vfy), compare with the raw blocks
- * (verify.hip), fold the verdict into d_status, in chunks of K blocks that keep the decoded blocks, the stream tables and the
- * decoders' workspace within the call's budget (CRYO_OPT_WORKSPACE_MAX_BYTES, else what ws_budget allows).
+/* ---- the shared decode loop of write verification and the stored-block check ----
+ * Decode the streams of n blocks with the automatic routes into handle workspace (c->d_vfy), in chunks of K blocks that keep
+ * the decoded blocks, the stream tables, the pass's own per-chunk arrays and the decoders' workspace within the call's budget
+ * (CRYO_OPT_WORKSPACE_MAX_BYTES, else what ws_budget allows), and run the pass's kernels on each decoded chunk.
  * Streams come either from a table (d_comp_off: the caller's, who keeps the slack of cryo_dev_alloc) or from the slots of a
  * compress call (d_comp + i * comp_stride, an area of exactly n * comp_stride bytes as far as we know).  The decoders read
  * aligned 16-byte pieces, so up to 15 bytes beyond a stream's end, and before its start when it is not aligned: the last slot's
  * stream -- and the first's when the area is not 16-byte aligned -- may end at the area's bound, so those "edge" slots are
  * copied (slot bytes only: in bounds) into padded workspace and decoded from there.  Every other slot is followed by a whole
  * slot of at least 16 bytes (stride >= bound >= 16) and, in an aligned area, preceded by the area's own bytes. */
-static int verify_pass(cryo_codec *c, int method, const uint8_t *d_raw, uint64_t raw_stride, uint32_t B, uint64_t n,
-                       const uint8_t *d_comp, const uint64_t *d_comp_off, uint64_t comp_stride, const uint32_t *d_comp_size,
-                       int32_t *d_status, bool has_enc_status, uint32_t *d_first_user)
+namespace {
+constexpr uint64_t kNoEdge = ~0ull;
+struct DecodeChunk {
+    uint64_t lo = 0, K = 0;          /* blocks lo .. lo + cnt - 1 of the pass; K: blocks per chunk */
+    uint32_t cnt = 0;
+    uint64_t e0 = kNoEdge, e1 = kNoEdge, edge_stride = 0; /* the edge blocks of this chunk (kNoEdge: none) */
+    uint8_t *fixed = nullptr;        /* the pass's bytes for the whole call */
+    uint8_t *own = nullptr;          /* the pass's bytes for this chunk (K * own_per_block) */
+    uint8_t *dec = nullptr;          /* block lo + k decoded at dec + k * Bp */
+    uint64_t Bp = 0;
+    int32_t *dec_st = nullptr;       /* its decoder status at dec_st[k] (the edge blocks': entries cnt and cnt + 1) */
+    uint64_t *off = nullptr;         /* the chunk's stream table (K + 2 entries), filled by the pass's prep */
+    uint32_t *sz = nullptr;
+};
+struct DecodePass {
+    const uint8_t *d_comp = nullptr;
+    const uint64_t *d_comp_off = nullptr;
+    uint64_t comp_stride = 0;
+    const uint32_t *d_comp_size = nullptr;
+    uint64_t fixed = 0;          /* bytes of DecodeChunk::fixed */
+    uint64_t own_per_block = 0;  /* bytes per block of DecodeChunk::own */
+    /* before a chunk's decodes: fill its stream table (off, sz; the edge blocks' at entries cnt, cnt + 1); none: the decoders
+     * read d_comp_off + lo and d_comp_size + lo as they are (no edges then) */
+    std::function<int(const DecodeChunk &)> prep;
+    std::function<int(const DecodeChunk &)> run; /* the pass's kernels on the decoded chunk */
+};
+} // namespace
+
+static int decode_pass(cryo_codec *c, int method, uint32_t B, uint64_t n, const DecodePass &ps)
 {
-    constexpr uint64_t kNone = ~0ull;
     auto al = [](uint64_t x) { return (x + 255u) & ~(uint64_t)255u; };
-    const uint64_t Bp = ((uint64_t)B + 15u) & ~(uint64_t)15u; /* decoded block stride: 16-byte rows for the compare */
-    uint64_t e0 = kNone, e1 = kNone;
-    if (!d_comp_off) {
-        if ((uintptr_t)d_comp & 15u) e0 = 0;
+    const uint64_t Bp = ((uint64_t)B + 15u) & ~(uint64_t)15u; /* decoded block stride: 16-byte rows for the kernels */
+    uint64_t e0 = kNoEdge, e1 = kNoEdge;
+    if (!ps.d_comp_off) {
+        if ((uintptr_t)ps.d_comp & 15u) e0 = 0;
         if (n - 1 != e0) e1 = n - 1;
     }
-    const uint64_t E = d_comp_off ? 0 : al(comp_stride + 64u); /* one padded edge copy */
-    const uint64_t first_bytes = d_first_user ? 0 : al(n * 4u);
-    auto meta = [&](uint64_t K) { return al((K + 2) * 4u) + al((K + 2) * 8u) + al((K + 2) * 4u) + 2 * E; };
+    const uint64_t E = ps.d_comp_off ? 0 : al(ps.comp_stride + 64u); /* one padded edge copy */
+    auto meta = [&](uint64_t K) {
+        return al((K + 2) * 4u) + al((K + 2) * 8u) + al((K + 2) * 4u) + 2 * E + (ps.own_per_block ? al(K * ps.own_per_block) : 0);
+    };
     size_t budget = c->ws_max;
     if (!budget) {
         size_t fr = 0, tot = 0;
@@ -854,7 +880,7 @@ static int verify_pass(cryo_codec *c, int method, const uint8_t *d_raw, uint64_t
     uint64_t K = n < (1ull << 24) ? n : (1ull << 24);
     size_t zstd_max = 0;
     for (;;) {
-        const uint64_t fixed = first_bytes + meta(K) + K * Bp + 256u;
+        const uint64_t fixed = ps.fixed + meta(K) + K * Bp + 256u;
         size_t dec_ws = 0;
         if (method == CRYO_METHOD_LZ4) dec_ws = cryo::lz4_decompress_workspace(K, B, auto_opts);
         else {
@@ -865,44 +891,98 @@ static int verify_pass(cryo_codec *c, int method, const uint8_t *d_raw, uint64_t
         K = (K + 1) / 2;
     }
     if (method == CRYO_METHOD_ZSTD && K == 1 && zstd_max == 0) zstd_max = ~(size_t)0; /* one block: whatever it takes */
-    int rc = ensure(c, &c->d_vfy, &c->vfy_cap, first_bytes + meta(K) + K * Bp + 256u + 64u);
+    int rc = ensure(c, &c->d_vfy, &c->vfy_cap, ps.fixed + meta(K) + K * Bp + 256u + 64u);
     if (rc != CRYO_OK) return rc;
+    DecodeChunk ch;
     uint8_t *p = c->d_vfy;
-    uint32_t *first = d_first_user ? d_first_user : (uint32_t *)p;
-    p += first_bytes;
-    int32_t *dec_st = (int32_t *)p;   p += al((K + 2) * 4u);
-    uint64_t *off = (uint64_t *)p;    p += al((K + 2) * 8u);
-    uint32_t *sz = (uint32_t *)p;     p += al((K + 2) * 4u);
-    uint8_t *edge = p;                p += 2 * E;
-    uint8_t *dec = p;
-    c->vfy_first = d_first_user ? nullptr : first;
+    ch.K = K; ch.Bp = Bp; ch.edge_stride = E;
+    ch.fixed = p;                      p += ps.fixed;
+    ch.dec_st = (int32_t *)p;          p += al((K + 2) * 4u);
+    ch.off = (uint64_t *)p;            p += al((K + 2) * 8u);
+    ch.sz = (uint32_t *)p;             p += al((K + 2) * 4u);
+    uint8_t *edge = p;                 p += 2 * E;
+    ch.own = p;                        p += ps.own_per_block ? al(K * ps.own_per_block) : 0;
+    ch.dec = p;
     for (uint64_t lo = 0; lo < n; lo += K) {
         const uint32_t cnt = (uint32_t)(n - lo < K ? n - lo : K);
-        const uint64_t ce0 = e0 != kNone && e0 >= lo && e0 < lo + cnt ? e0 : kNone;
-        const uint64_t ce1 = e1 != kNone && e1 >= lo && e1 < lo + cnt ? e1 : kNone;
-        if (ce0 != kNone) HIP_TRY(c, hipMemcpyAsync(edge, d_comp + ce0 * comp_stride, comp_stride, hipMemcpyDeviceToDevice, c->stream));
-        if (ce1 != kNone) HIP_TRY(c, hipMemcpyAsync(edge + E, d_comp + ce1 * comp_stride, comp_stride, hipMemcpyDeviceToDevice, c->stream));
-        HIP_TRY(c, cryo::launch_verify_prep(c->stream, lo, cnt, d_comp_off, comp_stride, d_comp_size, has_enc_status ? d_status : nullptr,
-                                            ce0, ce1, E, off, sz, first));
-        const uint64_t b_lo = lo + (ce0 != kNone ? 1u : 0u), b_hi = lo + cnt - (ce1 != kNone ? 1u : 0u);
+        const uint64_t ce0 = e0 != kNoEdge && e0 >= lo && e0 < lo + cnt ? e0 : kNoEdge;
+        const uint64_t ce1 = e1 != kNoEdge && e1 >= lo && e1 < lo + cnt ? e1 : kNoEdge;
+        ch.lo = lo; ch.cnt = cnt; ch.e0 = ce0; ch.e1 = ce1;
+        if (ce0 != kNoEdge) HIP_TRY(c, hipMemcpyAsync(edge, ps.d_comp + ce0 * ps.comp_stride, ps.comp_stride, hipMemcpyDeviceToDevice, c->stream));
+        if (ce1 != kNoEdge) HIP_TRY(c, hipMemcpyAsync(edge + E, ps.d_comp + ce1 * ps.comp_stride, ps.comp_stride, hipMemcpyDeviceToDevice, c->stream));
+        if (ps.prep && (rc = ps.prep(ch)) != CRYO_OK) return rc;
+        const uint64_t b_lo = lo + (ce0 != kNoEdge ? 1u : 0u), b_hi = lo + cnt - (ce1 != kNoEdge ? 1u : 0u);
         if (b_hi > b_lo) {
             const uint64_t k0 = b_lo - lo;
-            rc = decompress_routed(c, method, d_comp, off + k0, sz + k0, dec + k0 * Bp, Bp, B, b_hi - b_lo, dec_st + k0, true, zstd_max);
+            const uint64_t *t_off = ps.prep ? ch.off + k0 : ps.d_comp_off + b_lo;
+            const uint32_t *t_sz = ps.prep ? ch.sz + k0 : ps.d_comp_size + b_lo;
+            rc = decompress_routed(c, method, ps.d_comp, t_off, t_sz, ch.dec + k0 * Bp, Bp, B, b_hi - b_lo, ch.dec_st + k0, true, zstd_max);
             if (rc != CRYO_OK) return rc;
         }
-        if (ce0 != kNone || ce1 != kNone) {
-            const uint64_t a = ce0 != kNone ? ce0 : ce1;
-            const uint32_t t = ce0 != kNone ? cnt : cnt + 1u;       /* table entry of the first edge decoded */
-            const uint64_t ne = (ce0 != kNone) + (ce1 != kNone);
+        if (ce0 != kNoEdge || ce1 != kNoEdge) {
+            const uint64_t a = ce0 != kNoEdge ? ce0 : ce1;
+            const uint32_t t = ce0 != kNoEdge ? cnt : cnt + 1u;       /* table entry of the first edge decoded */
+            const uint64_t ne = (ce0 != kNoEdge) + (ce1 != kNoEdge);
             const uint64_t stride = ne == 2 ? (ce1 - ce0) * Bp : Bp;
-            rc = decompress_routed(c, method, edge, off + t, sz + t, dec + (a - lo) * Bp, stride, B, ne, dec_st + t, true, zstd_max);
+            rc = decompress_routed(c, method, edge, ch.off + t, ch.sz + t, ch.dec + (a - lo) * Bp, stride, B, ne, ch.dec_st + t, true, zstd_max);
             if (rc != CRYO_OK) return rc;
         }
-        HIP_TRY(c, cryo::launch_verify_compare(c->stream, d_raw, raw_stride, dec, Bp, B, lo, cnt, sz, dec_st, ce0, ce1, first));
-        HIP_TRY(c, cryo::launch_verify_fold(c->stream, lo, cnt, sz, dec_st, ce0, ce1, has_enc_status, d_status, first));
+        if ((rc = ps.run(ch)) != CRYO_OK) return rc;
     }
     return CRYO_OK;
 }
+
+/* ---- write verification ----
+ * The shared decode loop over the compressed blocks, then the compare with the raw blocks (verify.hip) and the verdict folded
+ * into d_status, chunk by chunk.  The per-block first-mismatch words are the caller's (d_first_user) or held for the whole call
+ * in the pass's fixed bytes (c->vfy_first: a host-buffer call reports its failing block's). */
+static int verify_pass(cryo_codec *c, int method, const uint8_t *d_raw, uint64_t raw_stride, uint32_t B, uint64_t n,
+                       const uint8_t *d_comp, const uint64_t *d_comp_off, uint64_t comp_stride, const uint32_t *d_comp_size,
+                       int32_t *d_status, bool has_enc_status, uint32_t *d_first_user)
+{
+    DecodePass ps;
+    ps.d_comp = d_comp; ps.d_comp_off = d_comp_off; ps.comp_stride = comp_stride; ps.d_comp_size = d_comp_size;
+    ps.fixed = d_first_user ? 0 : ((n * 4u + 255u) & ~(uint64_t)255u);
+    auto first_of = [&](const DecodeChunk &ch) { return d_first_user ? d_first_user : (uint32_t *)ch.fixed; };
+    ps.prep = [&](const DecodeChunk &ch) -> int {
+        uint32_t *first = first_of(ch);
+        c->vfy_first = d_first_user ? nullptr : first;
+        HIP_TRY(c, cryo::launch_verify_prep(c->stream, ch.lo, ch.cnt, d_comp_off, comp_stride, d_comp_size, has_enc_status ? d_status : nullptr,
+                                            ch.e0, ch.e1, ch.edge_stride, ch.off, ch.sz, first));
+        return CRYO_OK;
+    };
+    ps.run = [&](const DecodeChunk &ch) -> int {
+        uint32_t *first = first_of(ch);
+        HIP_TRY(c, cryo::launch_verify_compare(c->stream, d_raw, raw_stride, ch.dec, ch.Bp, B, ch.lo, ch.cnt, ch.sz, ch.dec_st, ch.e0, ch.e1, first));
+        HIP_TRY(c, cryo::launch_verify_fold(c->stream, ch.lo, ch.cnt, ch.sz, ch.dec_st, ch.e0, ch.e1, has_enc_status, d_status, first));
+        return CRYO_OK;
+    };
+    return decode_pass(c, method, B, n, ps);
+}
+
+/* ---- the stored-block check ----
+ * The shared decode loop over the caller's stream table, then the layout rules of every decoded block (check.hip) into
+ * d_result, chunk by chunk.  Its decodes count nowhere: cryo_codec_counters are what they were before the call. */
+static int check_pass(cryo_codec *c, int method, const uint8_t *d_src, const uint64_t *d_src_off, const uint32_t *d_src_size,
+                      uint32_t B, uint64_t n, cryo_check_result *d_result)
+{
+    static_assert(sizeof(cryo_check_result) == sizeof(uint2), "cryo_check_result is the kernels' uint2 {reason, offset}");
+    const cryo_codec_counters keep = c->ctr;
+    DecodePass ps;
+    ps.d_comp = d_src; ps.d_comp_off = d_src_off; ps.d_comp_size = d_src_size;
+    ps.own_per_block = 8u + 8u + 4u; /* verdict, gap, first nonzero byte */
+    ps.run = [&](const DecodeChunk &ch) -> int {
+        uint2 *verdict = (uint2 *)ch.own, *gap = verdict + ch.K;
+        uint32_t *first = (uint32_t *)(gap + ch.K);
+        HIP_TRY(c, cryo::launch_check(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, verdict, gap, first, (uint2 *)(d_result + ch.lo)));
+        return CRYO_OK;
+    };
+    const int rc = decode_pass(c, method, B, n, ps);
+    c->ctr = keep;
+    return rc;
+}
+
+static bool check_block_size_ok(size_t block_size) { return block_size >= 16 && block_size % 8 == 0 && block_size <= 0x7E000000u; }
 
 /* a host-buffer compress call found block `at` (index into the last verified batch) failed: its first differing byte, the
  * error text; `block` is the index the caller knows it by */
@@ -938,6 +1018,18 @@ int cryo_codec_verify_batch(cryo_codec *c, int method, const void *d_raw, uint64
     return guarded([&] {
         return verify_pass(c, method, (const uint8_t *)d_raw, raw_stride, block_size, n_blocks, (const uint8_t *)d_comp, d_comp_off,
                            0, d_comp_size, d_status, false, d_first_mismatch);
+    });
+}
+
+int cryo_codec_check_batch(cryo_codec *c, int method, const void *d_src, const uint64_t *d_src_off, const uint32_t *d_src_size,
+                           uint32_t block_size, uint64_t n_blocks, cryo_check_result *d_result)
+{
+    DevGuard dev_(c);
+    if (!c || !method_ok(method) || !check_block_size_ok(block_size)) return CRYO_E_ARG;
+    if (n_blocks == 0) return CRYO_OK;
+    if (!d_src || !d_src_off || !d_src_size || !d_result) return CRYO_E_ARG;
+    return guarded([&] {
+        return check_pass(c, method, (const uint8_t *)d_src, d_src_off, d_src_size, block_size, n_blocks, d_result);
     });
 }
 
@@ -1105,9 +1197,13 @@ static int compress_blocks_piped(cryo_codec *c, int method, int param, const uin
 
 /* h_dst: one contiguous K-block buffer; or one destination per block in h_dst_each (the cache's slots, a multi-GPU share):
  * then a block that failed leaves its destination untouched -- the statuses of a chunk travel with its blocks */
+/* h_result (the stored-block check): the same staging and uploads, the check instead of the decode, and only the results come
+ * back (no decoded blocks, no statuses) */
 static int decompress_blocks_piped(cryo_codec *c, int method, const void *const *h_src, const uint32_t *h_src_size, size_t n,
-                                   uint8_t *h_dst, void *const *h_dst_each, size_t block_size, int32_t *h_status)
+                                   uint8_t *h_dst, void *const *h_dst_each, size_t block_size, int32_t *h_status,
+                                   cryo_check_result *h_result = nullptr)
 {
+    const bool check = h_result != nullptr;
     const size_t K = pipe_chunk_blocks(n, block_size, method), nch = (n + K - 1) / K;
     const bool per_chunk = pipe_kernel_per_chunk(K, method, false);
     /* device layout of the compressed side: [offsets u64 x n][sizes u32 x n][blocks, 16-byte aligned] */
@@ -1128,11 +1224,11 @@ static int decompress_blocks_piped(cryo_codec *c, int method, const void *const 
     if ((rc = ensure_pipe_streams(c)) != CRYO_OK) return rc;
     if ((rc = ensure_pinned(c, o_data + n * 4 + 64)) != CRYO_OK) return rc;
     if ((rc = ensure(c, &c->hb_src, &c->hb_src_cap, o_data + total + 64)) != CRYO_OK) return rc;
-    if ((rc = ensure(c, &c->hb_dst, &c->hb_dst_cap, n * block_size + 64)) != CRYO_OK) return rc;
+    if (!check && (rc = ensure(c, &c->hb_dst, &c->hb_dst_cap, n * block_size + 64)) != CRYO_OK) return rc;
     if ((rc = ensure(c, &c->hb_meta, &c->hb_meta_cap, n * 16 + 64)) != CRYO_OK) return rc;
     for (int b = 0; b < 2; b++) {
         if ((rc = ensure_pipe(c, b, max_chunk_in + 64)) != CRYO_OK) return rc;
-        if ((rc = ensure_pipe(c, 2 + b, K * block_size)) != CRYO_OK) return rc;
+        if (!check && (rc = ensure_pipe(c, 2 + b, K * block_size)) != CRYO_OK) return rc;
     }
     uint8_t *pin = (uint8_t *)c->pin;
     uint64_t *p_off = (uint64_t *)(pin + o_off);
@@ -1141,8 +1237,9 @@ static int decompress_blocks_piped(cryo_codec *c, int method, const void *const 
     for (size_t i = 0; i < n; i++) { p_off[i] = o_data + pos[i]; p_sz[i] = h_src_size[i]; }
     HIP_TRY(c, hipMemcpyAsync(c->hb_src, pin, o_data, hipMemcpyHostToDevice, c->stream));
     c->xfer_ctr.h2d_bytes += o_data + total;
-    c->xfer_ctr.d2h_bytes += n * block_size + n * sizeof(int32_t);
+    c->xfer_ctr.d2h_bytes += check ? n * sizeof(cryo_check_result) : n * block_size + n * sizeof(int32_t);
     int32_t *d_st = (int32_t *)c->hb_meta;
+    cryo_check_result *d_res = (cryo_check_result *)c->hb_meta;
     const uint64_t *d_off = (const uint64_t *)(c->hb_src + o_off);
     const uint32_t *d_sz = (const uint32_t *)(c->hb_src + o_sz);
     auto scatter = [&](size_t ch) -> int {
@@ -1173,6 +1270,11 @@ static int decompress_blocks_piped(cryo_codec *c, int method, const void *const 
             HIP_TRY(c, hipMemcpyAsync(c->hb_src + o_data + pos[lo], c->pipe_pin[b], pos[hi] - pos[lo], hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipEventRecord(c->ev_in[b], c->stream));
         if (!per_chunk) continue;
+        if (check) {
+            rc = check_pass(c, method, c->hb_src, d_off + lo, d_sz + lo, (uint32_t)block_size, cnt, d_res + lo);
+            if (rc != CRYO_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
+            continue;
+        }
         rc = cryo_codec_decompress_batch(c, method, c->hb_src, d_off + lo, d_sz + lo, c->hb_dst + lo * block_size, block_size,
                                          (uint32_t)block_size, cnt, d_st + lo);
         if (rc != CRYO_OK) { (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(c->xfer); return rc; }
@@ -1182,6 +1284,15 @@ static int decompress_blocks_piped(cryo_codec *c, int method, const void *const 
         HIP_TRY(c, hipMemcpyAsync(c->pipe_pin[2 + b], c->hb_dst + lo * block_size, cnt * block_size, hipMemcpyDeviceToHost, c->xfer));
         if (!h_dst) HIP_TRY(c, hipMemcpyAsync(p_st + lo, d_st + lo, cnt * 4, hipMemcpyDeviceToHost, c->xfer)); /* the scatter skips failed blocks */
         HIP_TRY(c, hipEventRecord(c->ev_out[b], c->xfer));
+    }
+    if (check) {
+        if (!per_chunk) {
+            rc = check_pass(c, method, c->hb_src, d_off, d_sz, (uint32_t)block_size, n, d_res);
+            if (rc != CRYO_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
+        }
+        HIP_TRY(c, hipMemcpyAsync(h_result, d_res, n * sizeof *d_res, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return CRYO_OK;
     }
     if (!per_chunk) {
         /* one launch over the whole call, then the D2H of chunk c+1 overlaps the host scatter of chunk c */
@@ -1294,16 +1405,20 @@ int cryo_codec_compress_blocks(cryo_codec *c, int method, int param, const void 
     });
 }
 
+/* h_result: the stored-block check of the staged streams instead of their decode; only the results come back */
 static int decompress_blocks_impl(cryo_codec *c, int method, const void *const *h_src, const uint32_t *h_src_size,
-                                  size_t n, void *h_dst, void *const *h_dst_each, size_t block_size, int32_t *h_status)
+                                  size_t n, void *h_dst, void *const *h_dst_each, size_t block_size, int32_t *h_status,
+                                  cryo_check_result *h_result = nullptr)
 {
     DevGuard dev_(c);
+    const bool check = h_result != nullptr;
     if (!c || !method_ok(method) || block_size == 0 || block_size > 0x7E000000u) return CRYO_E_ARG;
+    if (check && !check_block_size_ok(block_size)) return CRYO_E_ARG;
     if (n == 0) return CRYO_OK;
-    if (!h_src || !h_src_size || (!h_dst && !h_dst_each) || !h_status) return CRYO_E_ARG;
+    if (!h_src || !h_src_size || (!check && ((!h_dst && !h_dst_each) || !h_status))) return CRYO_E_ARG;
     ScopedLocalCpus numa_(n * block_size >= ((size_t)8 << 20) ? c : nullptr);
     if (pipe_worth_it(c, n, block_size)) {
-        const int rc = decompress_blocks_piped(c, method, h_src, h_src_size, n, (uint8_t *)h_dst, h_dst_each, block_size, h_status);
+        const int rc = decompress_blocks_piped(c, method, h_src, h_src_size, n, (uint8_t *)h_dst, h_dst_each, block_size, h_status, h_result);
         /* an error return must not leave copies in flight into the handle's pinned buffers or the caller's memory */
         if (rc != CRYO_OK) { (void)hipStreamSynchronize(c->stream); if (c->xfer) (void)hipStreamSynchronize(c->xfer); }
         pipe_trim(c);
@@ -1319,7 +1434,7 @@ static int decompress_blocks_impl(cryo_codec *c, int method, const void *const *
     int rc;
     if ((rc = ensure_pinned(c, o_data + total + 64)) != CRYO_OK) return rc;
     if ((rc = ensure(c, &c->hb_src, &c->hb_src_cap, o_data + total + 64)) != CRYO_OK) return rc;
-    if ((rc = ensure(c, &c->hb_dst, &c->hb_dst_cap, n * block_size + 64)) != CRYO_OK) return rc;
+    if (!check && (rc = ensure(c, &c->hb_dst, &c->hb_dst_cap, n * block_size + 64)) != CRYO_OK) return rc;
     if ((rc = ensure(c, &c->hb_meta, &c->hb_meta_cap, n * 16 + 64)) != CRYO_OK) return rc;
     uint8_t *pin = (uint8_t *)c->pin;
     uint64_t *p_off = (uint64_t *)(pin + o_off);
@@ -1334,6 +1449,16 @@ static int decompress_blocks_impl(cryo_codec *c, int method, const void *const *
     int32_t *d_st = (int32_t *)c->hb_meta;
     HIP_TRY(c, hipMemcpyAsync(c->hb_src, pin, o_data + total, hipMemcpyHostToDevice, c->stream));
     c->xfer_ctr.h2d_bytes += o_data + total;
+    if (check) {
+        c->xfer_ctr.d2h_bytes += n * sizeof(cryo_check_result);
+        cryo_check_result *d_res = (cryo_check_result *)c->hb_meta;
+        rc = check_pass(c, method, c->hb_src, (const uint64_t *)(c->hb_src + o_off), (const uint32_t *)(c->hb_src + o_sz),
+                        (uint32_t)block_size, n, d_res);
+        if (rc != CRYO_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
+        HIP_TRY(c, hipMemcpyAsync(h_result, d_res, n * sizeof *d_res, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return CRYO_OK;
+    }
     c->xfer_ctr.d2h_bytes += n * block_size + n * sizeof(int32_t);
     rc = cryo_codec_decompress_batch(c, method, c->hb_src, (const uint64_t *)(c->hb_src + o_off), (const uint32_t *)(c->hb_src + o_sz),
                                      c->hb_dst, block_size, (uint32_t)block_size, n, d_st);
@@ -1387,6 +1512,19 @@ int cryo_codec_decompress_blocks_to(cryo_codec *c, int method, const void *const
     return guarded([&] {
         const int rc = decompress_blocks_impl(c, method, h_src, h_src_size, n, nullptr, h_dst, block_size, h_status);
         if (c) ws_trim_after_call(c);
+        return rc;
+    });
+}
+
+int cryo_codec_check_blocks(cryo_codec *c, int method, const void *const *h_src, const uint32_t *h_src_size, size_t n,
+                            size_t block_size, cryo_check_result *h_result)
+{
+    if (!c || !method_ok(method) || !check_block_size_ok(block_size)) return CRYO_E_ARG;
+    if (n == 0) return CRYO_OK;
+    if (!h_src || !h_src_size || !h_result) return CRYO_E_ARG;
+    return guarded([&] {
+        const int rc = decompress_blocks_impl(c, method, h_src, h_src_size, n, nullptr, nullptr, block_size, nullptr, h_result);
+        ws_trim_after_call(c);
         return rc;
     });
 }
@@ -1784,6 +1922,26 @@ int cryo_multi_decompress_blocks_to(cryo_multi *m, int method, const void *const
     if (!h_src || !h_src_size || !h_dst || !h_status) return CRYO_E_ARG;
     if (m->h.size() == 1) return cryo_codec_decompress_blocks_to(m->h[0], method, h_src, h_src_size, n, h_dst, block_size, h_status);
     return multi_decompress(m, method, h_src, h_src_size, n, nullptr, h_dst, block_size, h_status);
+}
+
+int cryo_multi_check_blocks(cryo_multi *m, int method, const void *const *h_src, const uint32_t *h_src_size, size_t n,
+                            size_t block_size, cryo_check_result *h_result)
+{
+    if (!m || m->h.empty() || !method_ok(method) || !check_block_size_ok(block_size)) return CRYO_E_ARG;
+    if (n == 0) return CRYO_OK;
+    if (!h_src || !h_src_size || !h_result) return CRYO_E_ARG;
+    if (m->h.size() == 1) return cryo_codec_check_blocks(m->h[0], method, h_src, h_src_size, n, block_size, h_result);
+    return guarded([&] {
+        return multi_run(m, n, [&](size_t g, const std::vector<size_t> &idx) {
+            std::vector<const void *> src(idx.size());
+            std::vector<uint32_t> sz(idx.size());
+            std::vector<cryo_check_result> res(idx.size());
+            for (size_t k = 0; k < idx.size(); k++) { src[k] = h_src[idx[k]]; sz[k] = h_src_size[idx[k]]; }
+            const int rc = decompress_blocks_impl(m->h[g], method, src.data(), sz.data(), idx.size(), nullptr, nullptr, block_size, nullptr, res.data());
+            if (rc == CRYO_OK) for (size_t k = 0; k < idx.size(); k++) h_result[idx[k]] = res[k];
+            return rc;
+        });
+    });
 }
 
 int cryo_multi_decompress_blocks_keyed(cryo_multi *m, int method, const uint64_t *keys, const void *const *h_src,

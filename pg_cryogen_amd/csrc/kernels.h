@@ -192,6 +192,12 @@ hipError_t launch_verify_compare(hipStream_t s, const uint8_t *d_raw, uint64_t r
 hipError_t launch_verify_fold(hipStream_t s, uint64_t lo, uint32_t cnt, const uint32_t *d_size, const int32_t *d_dec_status,
                               uint64_t e0, uint64_t e1, bool has_enc_status, int32_t *d_status, uint32_t *d_first);
 
+/* the stored-block check (check.hip) on one decoded chunk of cnt blocks (block k at d_dec + k * dec_stride, 16-byte aligned
+ * rows; its decoder status in d_dec_status[k]): k_check_items, k_check_zero, k_check_fold.  d_verdict, d_gap, d_first: cnt
+ * entries of scratch; d_result[k] = {reason, offset} (cryo_check_result) */
+hipError_t launch_check(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
+                        const int32_t *d_dec_status, uint2 *d_verdict, uint2 *d_gap, uint32_t *d_first, uint2 *d_result);
+
 } // namespace cryo
 
 #define CRYO_WAVE 64

@@ -23,17 +23,40 @@ DECOMPRESS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p),
                             C.c_void_p, C.c_size_t, C.POINTER(C.c_int32))
 ERROR_HANDLER = C.CFUNCTYPE(None, C.c_int, C.c_char_p)
 VERIFY_FAILURE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32))
+CHECK_BLOCKS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_size_t,
+                              C.c_size_t, C.POINTER(C.c_uint32))
+CRYO_CHECK_CHAIN, CRYO_CHECK_METHOD = 16, 17   # host-only reasons of check.h (beside cryo_check_reason 0..4)
 
 
 class CryoCodecOps(C.Structure):
+    """host/compression.h's CryoCodecOps WITHOUT its last member, check_blocks: 8 bytes shorter than the C struct.  Enough
+    for every host call except cryo_check_relation, which reads check_blocks and would read it past the end of an object of
+    this layout.  A double that may reach cryo_check_relation must be built from CryoCodecOpsCheck."""
     _fields_ = [("bound", BOUND_FN), ("compress_blocks", COMPRESS_FN), ("decompress_blocks", DECOMPRESS_FN),
                 ("ctx", C.c_void_p), ("decompress_blocks_scatter", C.c_void_p),      # optional members: NULL in test doubles
                 ("decompress_blocks_keyed", C.c_void_p), ("pool_invalidate", C.c_void_p),
                 ("last_verify_failure", C.c_void_p)]
 
 
+class CryoCodecOpsCheck(CryoCodecOps):
+    """CryoCodecOps with its last optional member, check_blocks (CHECK_BLOCKS_FN or NULL), which cryo_check_relation reads:
+    a double that reaches cryo_check_relation is built from this layout"""
+    _fields_ = [("check_blocks", C.c_void_p)]
+
+
 class CryoRel(C.Structure):
     _fields_ = [("relid", C.c_uint), ("handle", C.c_void_p), ("ops", C.c_void_p)]
+
+
+class CryoCheckReport(C.Structure):
+    _fields_ = [("block", C.c_uint32), ("reason", C.c_uint32), ("offset", C.c_uint32), ("npages", C.c_uint32)]
+
+
+class CryoCheckTotals(C.Structure):
+    _fields_ = [("blocks", C.c_uint64), ("empty_pages", C.c_uint64), ("bad", C.c_uint64), ("codec_calls", C.c_uint64)]
+
+
+CHECK_REPORT_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(CryoCheckReport))
 
 
 class HeapTupleData(C.Structure):
@@ -128,10 +151,30 @@ def lib():
     L.cryo_cache_err.restype = C.c_char_p
     L.cryo_host_transfer_counters.argtypes = [C.POINTER(C.c_uint64)] * 4
     L.cryo_host_transfer_counters.restype = None
+    L.cryo_check_relation.argtypes = [C.POINTER(CryoRel), CHECK_REPORT_FN, vp, C.POINTER(CryoCheckTotals)]
     for n in ("cryo_cache_hits", "cryo_cache_misses", "cryo_cache_codec_calls"):
         getattr(L, n).restype = C.c_uint64
     _libs[prod] = L
     return L
+
+
+class CheckRelationError(RuntimeError):
+    def __init__(self, code):
+        self.code = code
+        super().__init__("cryo_check_relation failed: %d" % code)
+
+
+def check_relation(rel):
+    """cryo_check_relation (host/check.h): (reports, totals) -- reports a list of (block, reason, offset, npages) in ascending
+    block order, totals a dict of blocks, empty_pages, bad, codec_calls.  A nonzero status raises CheckRelationError."""
+    reports = []
+    cb = CHECK_REPORT_FN(lambda arg, r: reports.append((r.contents.block, r.contents.reason, r.contents.offset,
+                                                        r.contents.npages)))
+    t = CryoCheckTotals()
+    rc = lib().cryo_check_relation(C.byref(rel), cb, None, C.byref(t))
+    if rc != 0:
+        raise CheckRelationError(rc)
+    return reports, {f: getattr(t, f) for f, _ in CryoCheckTotals._fields_}
 
 
 def transfer_counters():

@@ -83,8 +83,13 @@ static int hip_last_verify_failure(void *ctx, uint64_t *block, uint32_t *first_m
     return cryo_multi_last_verify_failure((cryo_multi *)ctx, block, first_mismatch);
 }
 
+static int hip_check_blocks(void *ctx, int method, const void *const *src, const uint32_t *sz, size_t n, size_t bs, uint32_t *result)
+{
+    return cryo_multi_check_blocks((cryo_multi *)ctx, method, src, sz, n, bs, (cryo_check_result *)result);
+}
+
 static CryoCodecOps hip_ops = {hip_bound, hip_compress_blocks, hip_decompress_blocks, NULL, hip_decompress_blocks_scatter,
-                               hip_decompress_blocks_keyed, hip_pool_invalidate, hip_last_verify_failure};
+                               hip_decompress_blocks_keyed, hip_pool_invalidate, hip_last_verify_failure, hip_check_blocks};
 static const CryoCodecOps *bound_ops; /* CPU-only plumbing tests bind a double here (CRYO_HOST_TEST_HOOKS builds only) */
 
 #ifdef CRYO_HOST_TEST_HOOKS

@@ -87,6 +87,10 @@ typedef struct CryoCodecOps {
     /* optional (may be NULL): after compress_blocks returned CRYO_E_VERIFY, the failing block and its first differing byte
      * (0xFFFFFFFF: the decoders reject its stream); 1 when there is one (cryo_multi_last_verify_failure) */
     int (*last_verify_failure)(void *ctx, uint64_t *block, uint32_t *first_mismatch);
+    /* optional (may be NULL): the stored-block check of n streams (cryo_multi_check_blocks): result[2i], result[2i + 1] =
+     * block i's {reason, offset} (cryo_check_result); check.h, cryo_check_relation, needs it */
+    int (*check_blocks)(void *ctx, int method, const void *const *src, const uint32_t *src_size, size_t n, size_t block_size,
+                        uint32_t *result);
 } CryoCodecOps;
 #ifdef CRYO_HOST_TEST_HOOKS
 void cryo_host_set_codec_ops(const CryoCodecOps *ops); /* test builds only: bind a double; NULL restores the HIP binding */
