@@ -272,6 +272,33 @@ int cryo_codec_check_batch(cryo_codec *c, int method, const void *d_src, const u
                            const uint32_t *d_src_size, uint32_t block_size, uint64_t n_blocks,
                            cryo_check_result *d_result);
 
+/* ---- recompression: stored streams -> decoded in handle workspace -> encoded again, all on the device ----
+ * A cryo relation is append-only and every block keeps the codec it was written with; this is the codec side of rewriting
+ * one (pg_cryogen_amd/host/recompress.h): an LZ4 relation to checksummed zstd, zstd-1 to a deep level.  Stream i (src_method:
+ * the d_src_size[i] bytes at d_src + d_src_off[i], the slack rule of cryo_dev_alloc applies) is decoded and encoded with
+ * (dst_method, dst_param) into d_dst + i * dst_stride, dst_stride >= cryo_codec_bound(dst_method, block_size).
+ *   Bytes    d_out_size[i] bytes that are exactly what cryo_codec_compress_batch(dst_method, dst_param) writes for the decoded
+ *            block under the handle's current encode options (CRYO_OPT_ENCODE_SEGMENT_BYTES, _SEGMENT_ZSTD_STRATEGY,
+ *            _ZSTD_CHECKSUM, _ENCODE_VERIFY): the encode IS that call, so with the defaults liblz4 1.9.3's / libzstd 1.4.8's
+ *            own output.  No new stream format.  dst_method == src_method is allowed (a level change, adding checksums).
+ *   Decode   the automatic decode routes whatever the handle's decode-path options say, into handle workspace -- never into
+ *            caller memory --, zstd content checksums checked as on every read.  The call runs in chunks of K blocks that keep
+ *            the decoded blocks, the stream tables, the encoder's and the decoders' workspace (and, for the host-buffer call
+ *            below, K output slots and a packed area of K slots) within CRYO_OPT_WORKSPACE_MAX_BYTES; with verification on,
+ *            the verifier plans its own chunks within what is left (one block at least).  The device pool is neither read
+ *            nor filled.
+ *   Status   d_status[i] = CRYO_OK; CRYO_E_CORRUPT: the decoders reject stream i (its neighbours are unaffected);
+ *            CRYO_E_VERIFY: CRYO_OPT_ENCODE_VERIFY is on and the new stream failed it.  d_out_size[i] is 0 unless the status
+ *            is CRYO_OK.
+ *   Counters the internal decodes do not count in cryo_codec_counters (as in verify and check); the encode counts in
+ *            blocks_compressed / bytes_in as any compress does.
+ * Asynchronous on the handle's stream.  CRYO_E_ARG: an unknown method, block_size 0, a null pointer; CRYO_E_DSTSIZE: dst_stride
+ * below the bound; CRYO_E_UNSUPPORTED: a zstd level above 22; n_blocks == 0: CRYO_OK. */
+int cryo_codec_recode_batch(cryo_codec *c, int src_method, const void *d_src, const uint64_t *d_src_off,
+                            const uint32_t *d_src_size, uint32_t block_size, uint64_t n_blocks,
+                            int dst_method, int dst_param, void *d_dst, uint64_t dst_stride,
+                            uint32_t *d_out_size, int32_t *d_status);
+
 /* ---- single block, HOST buffers: what cryo_compress()/cryo_decompress()
  *      (compression.c:125-159) call.  Synchronous: H2D, kernel, D2H. ---- */
 int cryo_codec_compress_block(cryo_codec *c, int method, int param,
@@ -308,6 +335,23 @@ int cryo_codec_decompress_blocks_to(cryo_codec *c, int method,
  * exactly 8 * n_blocks).  Returns CRYO_OK when the batch ran, whatever the blocks' verdicts. */
 int cryo_codec_check_blocks(cryo_codec *c, int method, const void *const *h_src, const uint32_t *h_src_size,
                             size_t n_blocks, size_t block_size, cryo_check_result *h_result);
+
+/* cryo_codec_recode_batch on host buffers (stream i: h_src[i], h_src_size[i] bytes), synchronous.  Only compressed bytes
+ * cross PCIe, in both directions: the streams are staged and uploaded as by cryo_codec_check_blocks (h2d_bytes grows by the
+ * same amount for the same streams); on the device the new streams are packed (recode.hip) and only the packed bytes, a size
+ * and a status per block come back: d2h_bytes grows by exactly packed_total + 8 * n_blocks.
+ *   Packing  output stream i is the h_out_size[i] bytes at h_dst + h_out_off[i]; h_out_off[0] = 0, h_out_off[i + 1] =
+ *            h_out_off[i] + align16(h_out_size[i]); the pad bytes behind a stream are written as zero, and nothing beyond the
+ *            packed total is written: a caller may pass untouched virtual memory of the worst-case size.  A packed total above
+ *            dst_cap: CRYO_E_DSTSIZE, and h_dst holds nothing to rely on; dst_cap >= n_blocks * align16(bound) always suffices.
+ *   Status   h_status[i] as d_status[i] above; a block that failed has h_out_size[i] = 0 and takes no room.  Returns CRYO_OK
+ *            when the batch ran, whatever the per-block statuses (as cryo_codec_decompress_blocks).
+ * The host needs a chunk's sizes before it can size the copy of its packed bytes: two waits per internal chunk.  The upload is
+ * not pipelined: a call stages all its streams in the handle's pinned buffer, which grows to the call's compressed size
+ * (plus a quarter) and stays with the handle until cryo_codec_trim. */
+int cryo_codec_recode_blocks(cryo_codec *c, int src_method, const void *const *h_src, const uint32_t *h_src_size,
+                             size_t n_blocks, size_t block_size, int dst_method, int dst_param,
+                             void *h_dst, size_t dst_cap, uint64_t *h_out_off, uint32_t *h_out_size, int32_t *h_status);
 
 /* ---- device-resident block pool ("optional device-resident compressed/decompressed pool so
  *      repeated scans skip PCIe"; the reference's cache is host-only: cache.c:17-50).
@@ -371,6 +415,14 @@ int cryo_multi_last_verify_failure(const cryo_multi *m, uint64_t *block, uint32_
 /* cryo_codec_check_blocks across the devices: block i -> handle i mod G */
 int cryo_multi_check_blocks(cryo_multi *m, int method, const void *const *h_src, const uint32_t *h_src_size,
                             size_t n_blocks, size_t block_size, cryo_check_result *h_result);
+
+/* cryo_codec_recode_blocks across the devices: block i -> handle i mod G.  Handle g packs its share, in block order, into
+ * the g-th of G equal regions of h_dst (each dst_cap / G rounded down to a multiple of 16 bytes, the g-th starting at g times
+ * that); the offsets are absolute within h_dst.  Requires dst_cap >= G * ceil(n_blocks / G) * align16(bound), else
+ * CRYO_E_DSTSIZE.  One handle: exactly cryo_codec_recode_blocks. */
+int cryo_multi_recode_blocks(cryo_multi *m, int src_method, const void *const *h_src, const uint32_t *h_src_size,
+                             size_t n_blocks, size_t block_size, int dst_method, int dst_param,
+                             void *h_dst, size_t dst_cap, uint64_t *h_out_off, uint32_t *h_out_size, int32_t *h_status);
 
 /* ---- batch helpers used by staging, tests and the benchmark ---- */
 

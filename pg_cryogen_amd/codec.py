@@ -57,6 +57,7 @@ ABI_SYMBOLS = [
     "cryo_codec_timer_stop", "cryo_codec_get_counters",
     "cryo_codec_verify_batch", "cryo_codec_last_verify_failure", "cryo_multi_last_verify_failure",
     "cryo_codec_check_batch", "cryo_codec_check_blocks", "cryo_multi_check_blocks",
+    "cryo_codec_recode_batch", "cryo_codec_recode_blocks", "cryo_multi_recode_blocks",
 ]
 
 
@@ -144,6 +145,9 @@ def lib():
     L.cryo_codec_check_batch.argtypes = [vp, i32, vp, vp, vp, u32, u64, vp]
     L.cryo_codec_check_blocks.argtypes = [vp, i32, vp, vp, sz, sz, vp]
     L.cryo_multi_check_blocks.argtypes = [vp, i32, vp, vp, sz, sz, vp]
+    L.cryo_codec_recode_batch.argtypes = [vp, i32, vp, vp, vp, u32, u64, i32, i32, vp, u64, vp, vp]
+    L.cryo_codec_recode_blocks.argtypes = [vp, i32, vp, vp, sz, sz, i32, i32, vp, sz, vp, vp, vp]
+    L.cryo_multi_recode_blocks.argtypes = [vp, i32, vp, vp, sz, sz, i32, i32, vp, sz, vp, vp, vp]
     _bound = True
     return L
 
@@ -163,6 +167,22 @@ def bound(method, block_size):
 def checksum64(data):
     a = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data)
     return lib().cryo_checksum64(a.ctypes.data, a.nbytes)
+
+
+def recode_blocks_call(fn, handle, chk, src_method, comps, block_size, dst_method, dst_param, dst=None):
+    """cryo_codec_recode_blocks / cryo_multi_recode_blocks (fn) on a list of host streams"""
+    n = len(comps)
+    arrs = [np.ascontiguousarray(np.asarray(c, dtype=np.uint8)) for c in comps]
+    src = (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.nbytes else None for a in arrs])
+    szs = (C.c_uint32 * max(n, 1))(*[a.nbytes for a in arrs])
+    if dst is None:
+        dst = np.zeros(max(n, 1) * ((bound(dst_method, block_size) + 15) & ~15), np.uint8)
+    off, osz, st = np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.int32)
+    chk(fn(handle, src_method, src, szs, n, block_size, dst_method, dst_param, dst.ctypes.data, dst.nbytes,
+           off.ctypes.data, osz.ctypes.data, st.ctypes.data), "recode_blocks")
+    off, osz, st = off[:n], osz[:n], st[:n]
+    outs = [dst[int(off[i]):int(off[i]) + int(osz[i])] if st[i] == 0 else None for i in range(n)]
+    return outs, st, off, osz, dst
 
 
 class DeviceBuffer:
@@ -318,6 +338,21 @@ class Codec:
         out = np.zeros((n, 2), np.uint32)
         self._chk(self.L.cryo_codec_check_blocks(self.h, method, src, szs, n, block_size, out.ctypes.data), "check_blocks")
         return out
+
+    def recode_batch(self, src_method, d_src, d_off, d_sizes, block_size, n, dst_method, dst_param, d_dst, dst_stride,
+                     d_out_sizes, d_status):
+        """decode the n streams (d_src + d_off[i], d_sizes[i] bytes) into handle workspace and encode them again into
+        d_dst + i * dst_stride: d_out_sizes[i], d_status[i] (OK / E_CORRUPT / E_VERIFY).  Asynchronous."""
+        self._chk(self.L.cryo_codec_recode_batch(self.h, src_method, d_src.ptr, d_off.ptr, d_sizes.ptr, block_size, n,
+                                                 dst_method, dst_param, d_dst.ptr, dst_stride, d_out_sizes.ptr, d_status.ptr),
+                  "recode_batch")
+
+    def recode_blocks(self, src_method, comps, block_size, dst_method, dst_param, dst=None):
+        """recompress host streams; returns (streams, statuses, offsets, sizes, dst): streams[i] is a view of dst (None for a
+        block whose status is not OK), dst the packed buffer (a fresh one of the worst-case size unless the caller brings
+        one: its capacity is len(dst))"""
+        return recode_blocks_call(self.L.cryo_codec_recode_blocks, self.h, self._chk, src_method, comps, block_size,
+                                  dst_method, dst_param, dst)
 
     def last_verify_failure(self):
         """(block, first mismatch) that made the last host-buffer compress call fail verification, or None"""

@@ -167,6 +167,11 @@ struct cryo_codec {
     uint8_t *d_vfy = nullptr;
     size_t vfy_cap = 0;
     uint32_t *vfy_first = nullptr;
+    /* recompression (cryo_codec_recode_batch / _blocks): the decoded chunk, its output slots and packed area.  A buffer of its
+     * own: with CRYO_OPT_ENCODE_VERIFY on, the encode of a chunk verifies into d_vfy while the chunk's decoded blocks are
+     * still needed */
+    uint8_t *d_rec = nullptr;
+    size_t rec_cap = 0;
     bool vfy_failed = false;
     uint64_t vfy_block = 0;
     uint32_t vfy_off = 0;
@@ -317,7 +322,7 @@ void ws_trim_after_call(cryo_codec *c)
 {
     if (c->ws_keep < 0) return;
     const size_t keep = (size_t)c->ws_keep;
-    const size_t hb = c->hb_src_cap + c->hb_dst_cap + c->hb_meta_cap + c->vfy_cap;
+    const size_t hb = c->hb_src_cap + c->hb_dst_cap + c->hb_meta_cap + c->vfy_cap + c->rec_cap;
     const bool drop_ws = c->d_ws && c->ws_cap > keep;
     const bool drop_hb = hb != 0 && hb + (drop_ws ? 0 : c->ws_cap) > keep;
     if (!drop_ws && !drop_hb) return;
@@ -335,6 +340,7 @@ void ws_trim_after_call(cryo_codec *c)
         drop(c->hb_dst, c->hb_dst_cap);
         drop(c->hb_meta, c->hb_meta_cap);
         drop(c->d_vfy, c->vfy_cap);
+        drop(c->d_rec, c->rec_cap);
         c->vfy_first = nullptr;
     }
 }
@@ -456,6 +462,7 @@ void cryo_codec_close(cryo_codec *c)
     if (c->hb_dst) (void)hipFree(c->hb_dst);
     if (c->hb_meta) (void)hipFree(c->hb_meta);
     if (c->d_vfy) (void)hipFree(c->d_vfy);
+    if (c->d_rec) (void)hipFree(c->d_rec);
     if (c->pin) (void)hipHostFree(c->pin);
     for (int i = 0; i < 4; i++) if (c->pipe_pin[i]) (void)hipHostFree(c->pipe_pin[i]);
     if (c->xfer) { (void)hipStreamSynchronize(c->xfer); (void)hipStreamDestroy(c->xfer); }
@@ -503,6 +510,7 @@ int cryo_codec_trim(cryo_codec *c)
     drop(c->hb_dst, c->hb_dst_cap);
     drop(c->hb_meta, c->hb_meta_cap);
     drop(c->d_vfy, c->vfy_cap);
+    drop(c->d_rec, c->rec_cap);
     c->vfy_first = nullptr;
     if (c->pin) { (void)hipHostFree(c->pin); c->pin = nullptr; c->pin_cap = 0; }
     for (int i = 0; i < 4; i++)
@@ -670,6 +678,28 @@ static int verify_pass(cryo_codec *c, int method, const uint8_t *d_raw, uint64_t
                        const uint8_t *d_comp, const uint64_t *d_comp_off, uint64_t comp_stride, const uint32_t *d_comp_size,
                        int32_t *d_status, bool has_enc_status, uint32_t *d_first_user);
 
+/* which encoder a compress call takes, and the workspace (c->d_ws) it asks for: segment-parallel encode for blocks of more than
+ * S bytes (LZ4 up to 16 MiB; zstd with a strategy from `fast` up to the handle's CRYO_OPT_ENCODE_SEGMENT_ZSTD_STRATEGY);
+ * everything else the byte-identical encoders.  Recompression plans its chunks with the same two functions. */
+enum EncodePath { ENC_LZ4, ENC_ZSTD, ENC_LZ4_SEGMENTED, ENC_ZSTD_SEGMENTED };
+static EncodePath encode_path(const cryo_codec *c, int method, int param, uint32_t B)
+{
+    const uint32_t S = c->enc_seg;
+    if (S && B > S && method == CRYO_METHOD_LZ4 && B <= (16u << 20)) return ENC_LZ4_SEGMENTED;
+    if (S && B > S && method == CRYO_METHOD_ZSTD && cryo::zstd_segment_supported(param, B, c->enc_seg_zstd_strategy))
+        return ENC_ZSTD_SEGMENTED;
+    return method == CRYO_METHOD_LZ4 ? ENC_LZ4 : ENC_ZSTD;
+}
+static size_t encode_workspace(const cryo_codec *c, int method, int param, uint32_t B, uint64_t n)
+{
+    switch (encode_path(c, method, param, B)) {
+    case ENC_LZ4_SEGMENTED: return cryo::lz4_compress_segmented_workspace(n, B, c->enc_seg);
+    case ENC_ZSTD_SEGMENTED: return cryo::zstd_compress_segmented_workspace(n, param, B, c->enc_seg);
+    case ENC_ZSTD: return cryo::zstd_compress_workspace(n, param, B);
+    default: return 0;
+    }
+}
+
 int cryo_codec_compress_batch(cryo_codec *c, int method, int param, const void *d_src,
                               uint64_t src_stride, uint32_t block_size, uint64_t n_blocks,
                               void *d_dst, uint64_t dst_stride, uint32_t *d_out_size,
@@ -680,34 +710,35 @@ int cryo_codec_compress_batch(cryo_codec *c, int method, int param, const void *
     if (n_blocks == 0) return CRYO_OK;
     if (!d_src || !d_dst || !d_out_size || !d_status || src_stride < block_size) return CRYO_E_ARG;
     if (dst_stride < cryo_codec_bound(method, block_size)) return CRYO_E_DSTSIZE;
-    /* segment-parallel encode: blocks of more than S bytes (LZ4 up to 16 MiB; zstd with a strategy from `fast` up to the
-     * handle's CRYO_OPT_ENCODE_SEGMENT_ZSTD_STRATEGY); everything else takes the byte-identical encoders below */
     const uint32_t S = c->enc_seg;
-    if (S && block_size > S && method == CRYO_METHOD_LZ4 && block_size <= (16u << 20)) {
-        int rc = ensure_ws(c, cryo::lz4_compress_segmented_workspace(n_blocks, block_size, S));
+    const EncodePath path = encode_path(c, method, param, block_size);
+    /* levels whose strategy has a kernel; others: CRYO_E_UNSUPPORTED */
+    if (path == ENC_ZSTD && !cryo::zstd_compress_supported(param, block_size)) return CRYO_E_UNSUPPORTED;
+    if (path != ENC_LZ4) {
+        int rc = ensure_ws(c, encode_workspace(c, method, param, block_size, n_blocks));
         if (rc != CRYO_OK) return rc;
+    }
+    switch (path) {
+    case ENC_LZ4_SEGMENTED:
         HIP_TRY(c, cryo::launch_lz4_compress_segmented(c->stream, (const uint8_t *)d_src, src_stride, block_size, n_blocks,
                                                        (uint8_t *)d_dst, dst_stride, param, S, d_out_size, d_status, c->d_ws,
                                                        c->ws_cap));
-    } else if (S && block_size > S && method == CRYO_METHOD_ZSTD && cryo::zstd_segment_supported(param, block_size, c->enc_seg_zstd_strategy)) {
-        int rc = ensure_ws(c, cryo::zstd_compress_segmented_workspace(n_blocks, param, block_size, S));
-        if (rc != CRYO_OK) return rc;
+        break;
+    case ENC_ZSTD_SEGMENTED:
         HIP_TRY(c, cryo::launch_zstd_compress_segmented(c->stream, (const uint8_t *)d_src, src_stride, block_size, n_blocks,
                                                         (uint8_t *)d_dst, dst_stride, param, S, d_out_size, d_status, c->d_ws,
                                                         c->ws_cap, c->zstd_checksum ? 4u : 0u));
-    } else if (method == CRYO_METHOD_LZ4) {
+        break;
+    case ENC_LZ4:
         HIP_TRY(c, cryo::launch_lz4_compress(c->stream, (const uint8_t *)d_src, src_stride, block_size,
                                              n_blocks, (uint8_t *)d_dst, dst_stride, param,
                                              d_out_size, d_status));
-    } else {
-        /* levels whose strategy has a kernel (fast, dfast, greedy, lazy, lazy2: -5..10); others: CRYO_E_UNSUPPORTED */
-        if (!cryo::zstd_compress_supported(param, block_size)) return CRYO_E_UNSUPPORTED;
-        const size_t need = cryo::zstd_compress_workspace(n_blocks, param, block_size);
-        int rc = ensure_ws(c, need);
-        if (rc != CRYO_OK) return rc;
+        break;
+    case ENC_ZSTD:
         HIP_TRY(c, cryo::launch_zstd_compress(c->stream, (const uint8_t *)d_src, src_stride, block_size, n_blocks,
                                               (uint8_t *)d_dst, dst_stride, param, d_out_size, d_status, c->d_ws,
                                               c->ws_cap));
+        break;
     }
     /* content checksums (CRYO_OPT_ZSTD_CHECKSUM): the frames above plus the flag and XXH64 of the input, both zstd paths */
     if (method == CRYO_METHOD_ZSTD && c->zstd_checksum)
@@ -819,7 +850,8 @@ int cryo_codec_decompress_batch(cryo_codec *c, int method, const void *d_src,
 }
 
 /* ---- the shared decode loop of write verification and the stored-block check ----
- * Decode the streams of n blocks with the automatic routes into handle workspace (c->d_vfy), in chunks of K blocks that keep
+ * Decode the streams of n blocks with the automatic routes into handle workspace (c->d_vfy, or the pass's own buffer), in
+ * chunks of K blocks that keep
  * the decoded blocks, the stream tables, the pass's own per-chunk arrays and the decoders' workspace within the call's budget
  * (CRYO_OPT_WORKSPACE_MAX_BYTES, else what ws_budget allows), and run the pass's kernels on each decoded chunk.
  * Streams come either from a table (d_comp_off: the caller's, who keeps the slack of cryo_dev_alloc) or from the slots of a
@@ -853,11 +885,22 @@ struct DecodePass {
      * read d_comp_off + lo and d_comp_size + lo as they are (no edges then) */
     std::function<int(const DecodeChunk &)> prep;
     std::function<int(const DecodeChunk &)> run; /* the pass's kernels on the decoded chunk */
+    /* where the pass lives (a grow-only buffer of the handle and its capacity); none: c->d_vfy */
+    uint8_t **buf = nullptr;
+    size_t *cap = nullptr;
+    /* workspace (c->d_ws, shared with the decoders) the pass's own kernels want for a chunk of K blocks; it counts against the
+     * budget like the decoders' */
+    std::function<size_t(uint64_t K)> run_ws;
+    /* bytes per block that the pass's run allocates elsewhere for a chunk (a verification inside it: its decoded copy in
+     * c->d_vfy): planned for when K is chosen, not part of the pass's buffer */
+    uint64_t elsewhere_per_block = 0;
 };
 } // namespace
 
 static int decode_pass(cryo_codec *c, int method, uint32_t B, uint64_t n, const DecodePass &ps)
 {
+    uint8_t **buf = ps.buf ? ps.buf : &c->d_vfy;
+    size_t *cap = ps.cap ? ps.cap : &c->vfy_cap;
     auto al = [](uint64_t x) { return (x + 255u) & ~(uint64_t)255u; };
     const uint64_t Bp = ((uint64_t)B + 15u) & ~(uint64_t)15u; /* decoded block stride: 16-byte rows for the kernels */
     uint64_t e0 = kNoEdge, e1 = kNoEdge;
@@ -873,28 +916,32 @@ static int decode_pass(cryo_codec *c, int method, uint32_t B, uint64_t n, const 
     if (!budget) {
         size_t fr = 0, tot = 0;
         if (hipMemGetInfo(&fr, &tot) != hipSuccess) { (void)hipGetLastError(); fr = ~(size_t)0 / 2; }
-        budget = fr / 10u * 7u + c->ws_cap + c->vfy_cap;
+        budget = fr / 10u * 7u + c->ws_cap + *cap;
     }
     cryo::Lz4DecodeOpts auto_opts = c->lz4_opts;
     auto_opts.path = auto_opts.walkers = auto_opts.waves = 0;
     uint64_t K = n < (1ull << 24) ? n : (1ull << 24);
     size_t zstd_max = 0;
     for (;;) {
-        const uint64_t fixed = ps.fixed + meta(K) + K * Bp + 256u;
+        const uint64_t fixed = ps.fixed + meta(K) + K * Bp + 256u + K * ps.elsewhere_per_block;
         size_t dec_ws = 0;
         if (method == CRYO_METHOD_LZ4) dec_ws = cryo::lz4_decompress_workspace(K, B, auto_opts);
         else {
             zstd_max = budget > fixed ? budget - fixed : 0;
             dec_ws = cryo::zstd_decompress_workspace(K, B, 0, zstd_max);
         }
+        if (ps.run_ws) {
+            const size_t w = ps.run_ws(K);
+            if (w > dec_ws) dec_ws = w;
+        }
         if (fixed + dec_ws <= budget || K == 1) break;
         K = (K + 1) / 2;
     }
     if (method == CRYO_METHOD_ZSTD && K == 1 && zstd_max == 0) zstd_max = ~(size_t)0; /* one block: whatever it takes */
-    int rc = ensure(c, &c->d_vfy, &c->vfy_cap, ps.fixed + meta(K) + K * Bp + 256u + 64u);
+    int rc = ensure(c, buf, cap, ps.fixed + meta(K) + K * Bp + 256u + 64u);
     if (rc != CRYO_OK) return rc;
     DecodeChunk ch;
-    uint8_t *p = c->d_vfy;
+    uint8_t *p = *buf;
     ch.K = K; ch.Bp = Bp; ch.edge_stride = E;
     ch.fixed = p;                      p += ps.fixed;
     ch.dec_st = (int32_t *)p;          p += al((K + 2) * 4u);
@@ -984,6 +1031,99 @@ static int check_pass(cryo_codec *c, int method, const uint8_t *d_src, const uin
 
 static bool check_block_size_ok(size_t block_size) { return block_size >= 16 && block_size % 8 == 0 && block_size <= 0x7E000000u; }
 
+/* ---- recompression ----
+ * The shared decode loop over the caller's stream table; every decoded chunk is encoded by cryo_codec_compress_batch -- the
+ * path of every compress call, so the handle's encode options (segment mode, checksums, verification) apply as they are --
+ * and recode.hip folds the two statuses of each block and, for the host-buffer call, packs the chunk's streams.  The pass
+ * lives in c->d_rec, not in c->d_vfy: with verification on, the encode runs verify_pass, which decodes into c->d_vfy while this
+ * pass still holds the decoded chunk.  Per chunk of K blocks the buffer holds the decoded blocks, the stream tables, and (own)
+ * K output slots and a packed area of K slots for the host-buffer call, sizes, statuses and offsets; the encoder's workspace
+ * (run_ws) shares c->d_ws with the decoders'.  With verification on, K also leaves room for the verifier's decoded copy of
+ * the chunk, and while a chunk is encoded CRYO_OPT_WORKSPACE_MAX_BYTES is lowered by what this pass holds, so that the
+ * verifier plans its own chunks within the rest. */
+namespace {
+struct RecodeOut {
+    /* device-resident call: the caller's slots and arrays */
+    uint8_t *d_dst = nullptr;
+    uint64_t dst_stride = 0;
+    uint32_t *d_out_size = nullptr;
+    int32_t *d_status = nullptr;
+    /* host-buffer call: stream i at h_dst + h_off[i] - h_base (h_off[i] counts from h_base on), within dst_cap bytes */
+    uint8_t *h_dst = nullptr;
+    size_t dst_cap = 0;
+    uint64_t h_base = 0;
+    uint64_t *h_off = nullptr;
+    uint32_t *h_size = nullptr;
+    int32_t *h_status = nullptr;
+};
+} // namespace
+
+static int recode_pass(cryo_codec *c, int src_method, const uint8_t *d_src, const uint64_t *d_src_off, const uint32_t *d_src_size,
+                       uint32_t B, uint64_t n, int dst_method, int dst_param, RecodeOut &out)
+{
+    const bool host = out.h_dst != nullptr;
+    const uint64_t bound = cryo_codec_bound(dst_method, B);
+    const uint64_t dstride = host ? (bound + 15u) & ~(uint64_t)15u : out.dst_stride;
+    uint64_t h_run = 0; /* packed bytes of the chunks before this one */
+    DecodePass ps;
+    ps.d_comp = d_src; ps.d_comp_off = d_src_off; ps.d_comp_size = d_src_size;
+    ps.buf = &c->d_rec; ps.cap = &c->rec_cap;
+    ps.fixed = 256u;                                    /* the chunk's packed total (u64) */
+    ps.own_per_block = (host ? 2u * dstride : 0u) + 32u; /* slots, packed area; size u32, status i32, K + 1 offsets u64 */
+    ps.run_ws = [&](uint64_t K) { return encode_workspace(c, dst_method, dst_param, B, K); };
+    if (c->verify) ps.elsewhere_per_block = (((uint64_t)B + 15u) & ~(uint64_t)15u) + 64u; /* verify_pass: decoded block, tables */
+    ps.run = [&](const DecodeChunk &ch) -> int {
+        uint8_t *slots = host ? ch.own : out.d_dst + ch.lo * dstride;
+        uint8_t *packed = ch.own + ch.K * dstride;
+        uint8_t *m = ch.own + (host ? 2u * ch.K * dstride : 0u);
+        uint32_t *sz = host ? (uint32_t *)m : out.d_out_size + ch.lo;
+        int32_t *st = host ? (int32_t *)(m + ch.K * 4u) : out.d_status + ch.lo;
+        uint64_t *off = (uint64_t *)(m + ch.K * 8u);
+        uint64_t *total = (uint64_t *)ch.fixed;
+        /* the encode counts in cryo_codec_counters as any compress does; the decodes above counted no block */
+        int rc;
+        {
+            struct WsMaxScope { /* the option is what it was on every way out */
+                cryo_codec *c; size_t was;
+                ~WsMaxScope() { c->ws_max = was; }
+            } scope_{c, c->ws_max};
+            if (c->ws_max) c->ws_max = c->ws_max > c->rec_cap ? c->ws_max - c->rec_cap : 1;
+            rc = cryo_codec_compress_batch(c, dst_method, dst_param, ch.dec, ch.Bp, B, ch.cnt, slots, dstride, sz, st);
+        }
+        if (rc != CRYO_OK) return rc;
+        HIP_TRY(c, cryo::launch_recode_offsets(c->stream, ch.cnt, dstride, ch.dec_st, st, sz, 0, off, total));
+        if (!host) return CRYO_OK;
+        HIP_TRY(c, cryo::launch_recode_pack(c->stream, ch.cnt, slots, dstride, sz, off, total, packed, c->lz4_opts.cus));
+        /* the host sizes the copy of the packed bytes from the sizes: two waits per chunk */
+        HIP_TRY(c, hipMemcpyAsync(out.h_size + ch.lo, sz, ch.cnt * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(out.h_status + ch.lo, st, ch.cnt * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        uint64_t tot = 0;
+        for (uint32_t k = 0; k < ch.cnt; k++) {
+            const uint32_t s = out.h_size[ch.lo + k];
+            if ((out.h_status[ch.lo + k] != CRYO_OK) != (s == 0) || s > bound) return CRYO_E_HIP;
+            out.h_off[ch.lo + k] = out.h_base + h_run + tot;
+            tot += ((uint64_t)s + 15u) & ~(uint64_t)15u;
+        }
+        c->xfer_ctr.d2h_bytes += tot + 8u * (uint64_t)ch.cnt;
+        if (h_run + tot > out.dst_cap) return CRYO_E_DSTSIZE;
+        if (tot) {
+            HIP_TRY(c, hipMemcpyAsync(out.h_dst + h_run, packed, tot, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+        }
+        h_run += tot;
+        return CRYO_OK;
+    };
+    return decode_pass(c, src_method, B, n, ps);
+}
+
+static int recode_args(const cryo_codec *c, int src_method, int dst_method, int dst_param, size_t block_size)
+{
+    if (!c || !method_ok(src_method) || !method_ok(dst_method) || block_size == 0 || block_size > 0x7E000000u) return CRYO_E_ARG;
+    if (dst_method == CRYO_METHOD_ZSTD && !cryo::zstd_compress_supported(dst_param, (uint32_t)block_size)) return CRYO_E_UNSUPPORTED;
+    return CRYO_OK;
+}
+
 /* a host-buffer compress call found block `at` (index into the last verified batch) failed: its first differing byte, the
  * error text; `block` is the index the caller knows it by */
 static void set_verify_failure(cryo_codec *c, uint64_t block, uint32_t off)
@@ -1030,6 +1170,24 @@ int cryo_codec_check_batch(cryo_codec *c, int method, const void *d_src, const u
     if (!d_src || !d_src_off || !d_src_size || !d_result) return CRYO_E_ARG;
     return guarded([&] {
         return check_pass(c, method, (const uint8_t *)d_src, d_src_off, d_src_size, block_size, n_blocks, d_result);
+    });
+}
+
+int cryo_codec_recode_batch(cryo_codec *c, int src_method, const void *d_src, const uint64_t *d_src_off, const uint32_t *d_src_size,
+                            uint32_t block_size, uint64_t n_blocks, int dst_method, int dst_param, void *d_dst, uint64_t dst_stride,
+                            uint32_t *d_out_size, int32_t *d_status)
+{
+    DevGuard dev_(c);
+    const int ok = recode_args(c, src_method, dst_method, dst_param, block_size);
+    if (ok != CRYO_OK) return ok;
+    if (n_blocks == 0) return CRYO_OK;
+    if (!d_src || !d_src_off || !d_src_size || !d_dst || !d_out_size || !d_status) return CRYO_E_ARG;
+    if (dst_stride < cryo_codec_bound(dst_method, block_size)) return CRYO_E_DSTSIZE;
+    return guarded([&] {
+        RecodeOut out;
+        out.d_dst = (uint8_t *)d_dst; out.dst_stride = dst_stride; out.d_out_size = d_out_size; out.d_status = d_status;
+        return recode_pass(c, src_method, (const uint8_t *)d_src, d_src_off, d_src_size, block_size, n_blocks, dst_method,
+                           dst_param, out);
     });
 }
 
@@ -1405,6 +1563,41 @@ int cryo_codec_compress_blocks(cryo_codec *c, int method, int param, const void 
     });
 }
 
+/* the one-shot staging of n streams given by pointer: [offsets u64 x n][sizes u32 x n][streams, 16-byte aligned] built in the
+ * pinned buffer and sent to c->hb_src in one copy (counted in h2d_bytes); the device tables are at o_off and o_sz of c->hb_src.
+ * spread: the host copies go over the staging workers (recompression, whose large calls come through here too; a large
+ * decompress or check call takes the pipelined staging instead) */
+struct StagedStreams { size_t o_off = 0, o_sz = 0, o_data = 0, total = 0; };
+static int stage_streams(cryo_codec *c, const void *const *h_src, const uint32_t *h_src_size, size_t n, StagedStreams &sg,
+                         bool spread = false)
+{
+    sg.o_off = 0; sg.o_sz = n * 8; sg.o_data = (n * 12 + 63) & ~(size_t)63;
+    sg.total = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (h_src_size[i] != 0 && !h_src[i]) return CRYO_E_ARG;
+        sg.total += ((size_t)h_src_size[i] + 15) & ~(size_t)15;
+    }
+    int rc;
+    if ((rc = ensure_pinned(c, sg.o_data + sg.total + 64)) != CRYO_OK) return rc;
+    if ((rc = ensure(c, &c->hb_src, &c->hb_src_cap, sg.o_data + sg.total + 64)) != CRYO_OK) return rc;
+    uint8_t *pin = (uint8_t *)c->pin;
+    uint64_t *p_off = (uint64_t *)(pin + sg.o_off);
+    uint32_t *p_sz = (uint32_t *)(pin + sg.o_sz);
+    std::vector<CopyJob> jobs;
+    size_t pos = 0;
+    for (size_t i = 0; i < n; i++) {
+        p_off[i] = sg.o_data + pos;
+        p_sz[i] = h_src_size[i];
+        if (h_src_size[i] && spread) jobs.push_back({pin + sg.o_data + pos, h_src[i], h_src_size[i]});
+        else if (h_src_size[i]) memcpy(pin + sg.o_data + pos, h_src[i], h_src_size[i]);
+        pos += ((size_t)h_src_size[i] + 15) & ~(size_t)15;
+    }
+    parallel_copy(c, jobs);
+    HIP_TRY(c, hipMemcpyAsync(c->hb_src, pin, sg.o_data + sg.total, hipMemcpyHostToDevice, c->stream));
+    c->xfer_ctr.h2d_bytes += sg.o_data + sg.total;
+    return CRYO_OK;
+}
+
 /* h_result: the stored-block check of the staged streams instead of their decode; only the results come back */
 static int decompress_blocks_impl(cryo_codec *c, int method, const void *const *h_src, const uint32_t *h_src_size,
                                   size_t n, void *h_dst, void *const *h_dst_each, size_t block_size, int32_t *h_status,
@@ -1425,30 +1618,14 @@ static int decompress_blocks_impl(cryo_codec *c, int method, const void *const *
         return rc;
     }
     /* pinned staging: [offsets u64 x n][sizes u32 x n][compressed blocks, 16-byte aligned], sent in one copy */
-    const size_t o_off = 0, o_sz = n * 8, o_data = (n * 12 + 63) & ~(size_t)63;
-    size_t total = 0;
-    for (size_t i = 0; i < n; i++) {
-        if (h_src_size[i] != 0 && !h_src[i]) return CRYO_E_ARG;
-        total += ((size_t)h_src_size[i] + 15) & ~(size_t)15;
-    }
+    StagedStreams sg;
     int rc;
-    if ((rc = ensure_pinned(c, o_data + total + 64)) != CRYO_OK) return rc;
-    if ((rc = ensure(c, &c->hb_src, &c->hb_src_cap, o_data + total + 64)) != CRYO_OK) return rc;
+    /* every allocation of the call before the upload is queued and counted */
     if (!check && (rc = ensure(c, &c->hb_dst, &c->hb_dst_cap, n * block_size + 64)) != CRYO_OK) return rc;
     if ((rc = ensure(c, &c->hb_meta, &c->hb_meta_cap, n * 16 + 64)) != CRYO_OK) return rc;
-    uint8_t *pin = (uint8_t *)c->pin;
-    uint64_t *p_off = (uint64_t *)(pin + o_off);
-    uint32_t *p_sz = (uint32_t *)(pin + o_sz);
-    size_t pos = 0;
-    for (size_t i = 0; i < n; i++) {
-        p_off[i] = o_data + pos;
-        p_sz[i] = h_src_size[i];
-        if (h_src_size[i]) memcpy(pin + o_data + pos, h_src[i], h_src_size[i]);
-        pos += ((size_t)h_src_size[i] + 15) & ~(size_t)15;
-    }
+    if ((rc = stage_streams(c, h_src, h_src_size, n, sg)) != CRYO_OK) return rc;
+    const size_t o_off = sg.o_off, o_sz = sg.o_sz;
     int32_t *d_st = (int32_t *)c->hb_meta;
-    HIP_TRY(c, hipMemcpyAsync(c->hb_src, pin, o_data + total, hipMemcpyHostToDevice, c->stream));
-    c->xfer_ctr.h2d_bytes += o_data + total;
     if (check) {
         c->xfer_ctr.d2h_bytes += n * sizeof(cryo_check_result);
         cryo_check_result *d_res = (cryo_check_result *)c->hb_meta;
@@ -1525,6 +1702,44 @@ int cryo_codec_check_blocks(cryo_codec *c, int method, const void *const *h_src,
     return guarded([&] {
         const int rc = decompress_blocks_impl(c, method, h_src, h_src_size, n, nullptr, nullptr, block_size, nullptr, h_result);
         ws_trim_after_call(c);
+        return rc;
+    });
+}
+
+/* recompression of n streams given by pointer: staged and uploaded as the stored-block check's (stage_streams), recoded chunk
+ * by chunk on the device, and only the packed streams, the sizes and the statuses come back.  h_base: what the call's offsets
+ * count from (a multi-GPU share's region within the caller's h_dst) */
+static int recode_blocks_impl(cryo_codec *c, int src_method, const void *const *h_src, const uint32_t *h_src_size, size_t n,
+                              size_t block_size, int dst_method, int dst_param, void *h_dst, size_t dst_cap, uint64_t h_base,
+                              uint64_t *h_out_off, uint32_t *h_out_size, int32_t *h_status)
+{
+    DevGuard dev_(c);
+    const int ok = recode_args(c, src_method, dst_method, dst_param, block_size);
+    if (ok != CRYO_OK) return ok;
+    if (n == 0) return CRYO_OK;
+    if (!h_src || !h_src_size || !h_dst || !h_out_off || !h_out_size || !h_status) return CRYO_E_ARG;
+    ScopedLocalCpus numa_(n * block_size >= ((size_t)8 << 20) ? c : nullptr);
+    StagedStreams sg;
+    int rc;
+    if ((rc = stage_streams(c, h_src, h_src_size, n, sg, true)) != CRYO_OK) return rc;
+    const size_t o_off = sg.o_off, o_sz = sg.o_sz;
+    RecodeOut out;
+    out.h_dst = (uint8_t *)h_dst; out.dst_cap = dst_cap; out.h_base = h_base;
+    out.h_off = h_out_off; out.h_size = h_out_size; out.h_status = h_status;
+    rc = recode_pass(c, src_method, c->hb_src, (const uint64_t *)(c->hb_src + o_off), (const uint32_t *)(c->hb_src + o_sz),
+                     (uint32_t)block_size, n, dst_method, dst_param, out);
+    if (rc != CRYO_OK) (void)hipStreamSynchronize(c->stream); /* nothing in flight into the caller's memory after an error */
+    return rc;
+}
+
+int cryo_codec_recode_blocks(cryo_codec *c, int src_method, const void *const *h_src, const uint32_t *h_src_size, size_t n,
+                             size_t block_size, int dst_method, int dst_param, void *h_dst, size_t dst_cap, uint64_t *h_out_off,
+                             uint32_t *h_out_size, int32_t *h_status)
+{
+    return guarded([&] {
+        const int rc = recode_blocks_impl(c, src_method, h_src, h_src_size, n, block_size, dst_method, dst_param, h_dst, dst_cap, 0,
+                                          h_out_off, h_out_size, h_status);
+        if (c) ws_trim_after_call(c);
         return rc;
     });
 }
@@ -1940,6 +2155,45 @@ int cryo_multi_check_blocks(cryo_multi *m, int method, const void *const *h_src,
             const int rc = decompress_blocks_impl(m->h[g], method, src.data(), sz.data(), idx.size(), nullptr, nullptr, block_size, nullptr, res.data());
             if (rc == CRYO_OK) for (size_t k = 0; k < idx.size(); k++) h_result[idx[k]] = res[k];
             return rc;
+        });
+    });
+}
+
+/* block i -> handle i mod G; handle g packs its share, in block order, into the g-th of G equal 16-byte aligned regions of
+ * h_dst (dst_cap / G, rounded down to 16 bytes); the offsets are absolute within h_dst */
+int cryo_multi_recode_blocks(cryo_multi *m, int src_method, const void *const *h_src, const uint32_t *h_src_size, size_t n,
+                             size_t block_size, int dst_method, int dst_param, void *h_dst, size_t dst_cap, uint64_t *h_out_off,
+                             uint32_t *h_out_size, int32_t *h_status)
+{
+    if (!m || m->h.empty()) return CRYO_E_ARG;
+    const int ok = recode_args(m->h[0], src_method, dst_method, dst_param, block_size);
+    if (ok != CRYO_OK) return ok;
+    if (n == 0) return CRYO_OK;
+    if (!h_src || !h_src_size || !h_dst || !h_out_off || !h_out_size || !h_status) return CRYO_E_ARG;
+    const size_t G = m->h.size();
+    if (G == 1)
+        return cryo_codec_recode_blocks(m->h[0], src_method, h_src, h_src_size, n, block_size, dst_method, dst_param, h_dst, dst_cap,
+                                        h_out_off, h_out_size, h_status);
+    const size_t slot = (cryo_codec_bound(dst_method, block_size) + 15) & ~(size_t)15;
+    if (dst_cap / G / slot < (n + G - 1) / G) return CRYO_E_DSTSIZE;
+    const size_t region = (dst_cap / G) & ~(size_t)15;
+    return guarded([&] {
+        return multi_run(m, n, [&](size_t g, const std::vector<size_t> &idx) {
+            std::vector<const void *> src(idx.size());
+            std::vector<uint32_t> sz(idx.size()), osz(idx.size());
+            std::vector<uint64_t> off(idx.size());
+            std::vector<int32_t> st(idx.size());
+            for (size_t k = 0; k < idx.size(); k++) { src[k] = h_src[idx[k]]; sz[k] = h_src_size[idx[k]]; }
+            const int rc = recode_blocks_impl(m->h[g], src_method, src.data(), sz.data(), idx.size(), block_size, dst_method,
+                                              dst_param, (uint8_t *)h_dst + g * region, region, g * region, off.data(), osz.data(),
+                                              st.data());
+            if (rc != CRYO_OK) return rc;
+            for (size_t k = 0; k < idx.size(); k++) {
+                h_out_off[idx[k]] = off[k];
+                h_out_size[idx[k]] = osz[k];
+                h_status[idx[k]] = st[k];
+            }
+            return (int)CRYO_OK;
         });
     });
 }

@@ -198,6 +198,16 @@ hipError_t launch_verify_fold(hipStream_t s, uint64_t lo, uint32_t cnt, const ui
 hipError_t launch_check(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
                         const int32_t *d_dec_status, uint2 *d_verdict, uint2 *d_gap, uint32_t *d_first, uint2 *d_result);
 
+/* recompression (recode.hip) on one chunk of cnt encoded blocks in slots of slot_stride bytes (a multiple of 16, 16-byte
+ * aligned).  k_recode_offsets: d_status[k] (in: the encoder's) and d_size[k] become the block's final status and size (0 unless
+ * the decoder's status and the encoder's are both CRYO_OK); d_off[k] = base + the sum of align16(d_size[j]), j < k; d_off[cnt]
+ * = base + *d_total.  k_recode_pack: stream k to d_packed + d_off[k], pad bytes zero; d_packed holds base + *d_total bytes
+ * (at most base + cnt * slot_stride).  cus: compute units of the device (0: an MI355X's 256) */
+hipError_t launch_recode_offsets(hipStream_t s, uint32_t cnt, uint64_t slot_stride, const int32_t *d_dec_status, int32_t *d_status,
+                                 uint32_t *d_size, uint64_t base, uint64_t *d_off, uint64_t *d_total);
+hipError_t launch_recode_pack(hipStream_t s, uint32_t cnt, const uint8_t *d_slots, uint64_t slot_stride, const uint32_t *d_size,
+                              const uint64_t *d_off, const uint64_t *d_total, uint8_t *d_packed, int cus);
+
 } // namespace cryo
 
 #define CRYO_WAVE 64

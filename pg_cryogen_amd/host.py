@@ -25,6 +25,9 @@ ERROR_HANDLER = C.CFUNCTYPE(None, C.c_int, C.c_char_p)
 VERIFY_FAILURE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32))
 CHECK_BLOCKS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_size_t,
                               C.c_size_t, C.POINTER(C.c_uint32))
+RECODE_BLOCKS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_size_t,
+                               C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64),
+                               C.POINTER(C.c_uint32), C.POINTER(C.c_int32))
 CRYO_CHECK_CHAIN, CRYO_CHECK_METHOD = 16, 17   # host-only reasons of check.h (beside cryo_check_reason 0..4)
 
 
@@ -44,6 +47,12 @@ class CryoCodecOpsCheck(CryoCodecOps):
     _fields_ = [("check_blocks", C.c_void_p)]
 
 
+class CryoCodecOpsRecode(CryoCodecOpsCheck):
+    """CryoCodecOpsCheck with the last optional member, recode_blocks (RECODE_BLOCKS_FN or NULL), which only
+    cryo_recompress_relation reads: a double that reaches it is built from this layout"""
+    _fields_ = [("recode_blocks", C.c_void_p)]
+
+
 class CryoRel(C.Structure):
     _fields_ = [("relid", C.c_uint), ("handle", C.c_void_p), ("ops", C.c_void_p)]
 
@@ -57,6 +66,14 @@ class CryoCheckTotals(C.Structure):
 
 
 CHECK_REPORT_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(CryoCheckReport))
+
+
+class CryoRecompressTotals(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("blocks", "recoded", "verbatim", "skipped", "empty_pages", "bytes_in", "bytes_out",
+                                          "pages_in", "pages_out", "codec_calls")]
+
+
+RECOMPRESS_MOVED_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32)
 
 
 class HeapTupleData(C.Structure):
@@ -152,6 +169,8 @@ def lib():
     L.cryo_host_transfer_counters.argtypes = [C.POINTER(C.c_uint64)] * 4
     L.cryo_host_transfer_counters.restype = None
     L.cryo_check_relation.argtypes = [C.POINTER(CryoRel), CHECK_REPORT_FN, vp, C.POINTER(CryoCheckTotals)]
+    L.cryo_recompress_relation.argtypes = [C.POINTER(CryoRel), C.POINTER(CryoRel), i32, i32, RECOMPRESS_MOVED_FN, CHECK_REPORT_FN,
+                                           vp, C.POINTER(CryoRecompressTotals)]
     for n in ("cryo_cache_hits", "cryo_cache_misses", "cryo_cache_codec_calls"):
         getattr(L, n).restype = C.c_uint64
     _libs[prod] = L
@@ -175,6 +194,27 @@ def check_relation(rel):
     if rc != 0:
         raise CheckRelationError(rc)
     return reports, {f: getattr(t, f) for f, _ in CryoCheckTotals._fields_}
+
+
+class RecompressRelationError(RuntimeError):
+    def __init__(self, code):
+        self.code = code
+        super().__init__("cryo_recompress_relation failed: %d" % code)
+
+
+def recompress_relation(src, dst, method, param):
+    """cryo_recompress_relation (host/recompress.h): (moved, reports, totals) -- moved a list of (old_first, new_first,
+    old_npages, new_npages) in the order written, reports a list of (block, reason, offset, npages) in walk order, totals a
+    dict.  A nonzero status raises RecompressRelationError."""
+    moved, reports = [], []
+    mcb = RECOMPRESS_MOVED_FN(lambda arg, a, b, c, d: moved.append((a, b, c, d)))
+    rcb = CHECK_REPORT_FN(lambda arg, r: reports.append((r.contents.block, r.contents.reason, r.contents.offset,
+                                                         r.contents.npages)))
+    t = CryoRecompressTotals()
+    rc = lib().cryo_recompress_relation(C.byref(src), C.byref(dst), method, param, mcb, rcb, None, C.byref(t))
+    if rc != 0:
+        raise RecompressRelationError(rc)
+    return moved, reports, {f: getattr(t, f) for f, _ in CryoRecompressTotals._fields_}
 
 
 def transfer_counters():

@@ -88,8 +88,17 @@ static int hip_check_blocks(void *ctx, int method, const void *const *src, const
     return cryo_multi_check_blocks((cryo_multi *)ctx, method, src, sz, n, bs, (cryo_check_result *)result);
 }
 
+static int hip_recode_blocks(void *ctx, int src_method, const void *const *src, const uint32_t *sz, size_t n, size_t bs,
+                             int dst_method, int dst_param, void *dst, size_t dst_cap, uint64_t *out_off, uint32_t *out_size,
+                             int32_t *st)
+{
+    return cryo_multi_recode_blocks((cryo_multi *)ctx, src_method, src, sz, n, bs, dst_method, dst_param, dst, dst_cap, out_off,
+                                    out_size, st);
+}
+
 static CryoCodecOps hip_ops = {hip_bound, hip_compress_blocks, hip_decompress_blocks, NULL, hip_decompress_blocks_scatter,
-                               hip_decompress_blocks_keyed, hip_pool_invalidate, hip_last_verify_failure, hip_check_blocks};
+                               hip_decompress_blocks_keyed, hip_pool_invalidate, hip_last_verify_failure, hip_check_blocks,
+                               hip_recode_blocks};
 static const CryoCodecOps *bound_ops; /* CPU-only plumbing tests bind a double here (CRYO_HOST_TEST_HOOKS builds only) */
 
 #ifdef CRYO_HOST_TEST_HOOKS

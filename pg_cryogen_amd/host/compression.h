@@ -91,6 +91,12 @@ typedef struct CryoCodecOps {
      * block i's {reason, offset} (cryo_check_result); check.h, cryo_check_relation, needs it */
     int (*check_blocks)(void *ctx, int method, const void *const *src, const uint32_t *src_size, size_t n, size_t block_size,
                         uint32_t *result);
+    /* optional (may be NULL): recompression of n streams on the device (cryo_multi_recode_blocks): stream i is decoded and
+     * encoded with (dst_method, dst_param); the new stream is the out_size[i] bytes at dst + out_off[i] (packed at 16-byte
+     * steps, only compressed bytes cross PCIe), status[i] its cryo_status; recompress.h, cryo_recompress_relation, needs it */
+    int (*recode_blocks)(void *ctx, int src_method, const void *const *src, const uint32_t *src_size, size_t n, size_t block_size,
+                         int dst_method, int dst_param, void *dst, size_t dst_cap, uint64_t *out_off, uint32_t *out_size,
+                         int32_t *status);
 } CryoCodecOps;
 #ifdef CRYO_HOST_TEST_HOOKS
 void cryo_host_set_codec_ops(const CryoCodecOps *ops); /* test builds only: bind a double; NULL restores the HIP binding */
