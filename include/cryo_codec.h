@@ -299,6 +299,62 @@ int cryo_codec_recode_batch(cryo_codec *c, int src_method, const void *d_src, co
                             int dst_method, int dst_param, void *d_dst, uint64_t dst_stride,
                             uint32_t *d_out_size, int32_t *d_status);
 
+/* ---- fetching tuples by position: stored streams -> decoded in handle workspace -> only the tuples asked for come back ----
+ * Every other read route returns whole decoded blocks.  Two of the access method's read paths want a few tuples of a block (a
+ * bitmap heap scan: reference pg_cryogen.c:412-509; an index fetch: pg_cryogen.c:372-410); this is their codec side
+ * (pg_cryogen_amd/host/fetch.h walks a relation with it).
+ * A call names n_blocks stored streams as cryo_codec_check_batch does and, per block, a list of 1-based item positions
+ * (PostgreSQL's OffsetNumber) in CSR form: block i owns requests req_first[i] .. req_first[i + 1] - 1 of pos[]; req_first has
+ * n_blocks + 1 entries, req_first[0] = 0, req_first[n_blocks] = n_req.  A block may have no request.  Every request gets one
+ * cryo_fetch_result.  With the names of the check's rules above (lower, upper, n, off_i, len_i, MAXALIGN, a block of B bytes, B a
+ * multiple of 8 and at least 16, 64-bit arithmetic), for block i, the first failing class wins:
+ *   CRYO_FETCH_STREAM   every request of the block    the decoders reject the stream (malformed, other than B bytes, a zstd
+ *                                                     content checksum mismatch)
+ *   CRYO_FETCH_HEADER   every request of the block    the check's rule 1 fails
+ *   CRYO_FETCH_BADREQ   every request of the block    a position is 0, or the block's positions are not strictly ascending (a TID
+ *                                                     bitmap yields them sorted and distinct)
+ *   CRYO_FETCH_NOITEM   the request                   pos > n
+ *   CRYO_FETCH_ITEM     the request                   item pos - 1 has len == 0, off % 8 != 0, off < upper, or
+ *                                                     off + MAXALIGN(len) > B
+ *   CRYO_FETCH_OVERLAP  every request of the block    the MAXALIGNed lengths of the block's OK requests sum to more than
+ *                       that is still OK              B - upper (distinct items of a well-formed block are disjoint inside
+ *                                                     [upper, B), so only overlapping items get there)
+ *   CRYO_FETCH_OK       the request                   otherwise; len = len_i
+ * Values 1 .. 3 equal cryo_check_reason's; 4 (NONZERO) has no meaning here and is unused.  The fetch reads only the items it is
+ * asked for: it does NOT apply the check's chain rule (rule 2) or its zero rules (rule 3), and it does not look at tuple headers.
+ * Placement: requests are laid out in call order.  `off` of a request is the sum of MAXALIGN(len) over the OK requests before it
+ * (a failed request has len = 0, takes no room, and carries the offset at which the next tuple starts).  For an OK request the
+ * destination holds the tuple's len bytes at off, then zeros up to MAXALIGN(len) whatever the block holds in its pad; nothing at
+ * or beyond the call's total is written.  Because of the OVERLAP rule the total never exceeds the sum of B - upper_i, which is
+ * below n_blocks * B: a destination of n_blocks * block_size bytes always suffices, and a caller may pass untouched virtual
+ * memory of that size. */
+typedef enum {
+    CRYO_FETCH_OK = 0,
+    CRYO_FETCH_STREAM = 1,
+    CRYO_FETCH_HEADER = 2,
+    CRYO_FETCH_ITEM = 3,
+    CRYO_FETCH_NOITEM = 5,
+    CRYO_FETCH_BADREQ = 6,
+    CRYO_FETCH_OVERLAP = 7
+} cryo_fetch_status;
+typedef struct {
+    uint32_t status, len;
+    uint64_t off;
+} cryo_fetch_result; /* 16 bytes */
+/* Device buffers; asynchronous on the handle's stream.  Everything, the request table included, is device memory: d_req_first
+ * 8-byte, d_dst 8-byte, d_result 16-byte, d_total 8-byte aligned (CRYO_E_ARG otherwise).  *d_total receives the call's packed
+ * total; it is also where the running base lives between the call's internal chunks, so no host wait lies inside the call.
+ * Tuples that would end beyond dst_cap are not written, and *d_total > dst_cap tells the caller so (the records are complete
+ * either way).  Entries of d_req_first are cut to n_req, so a damaged table reads no request beyond d_pos[n_req - 1].
+ * Decode as in the check: the automatic routes whatever the handle's decode-path options say, into handle workspace, in chunks
+ * within CRYO_OPT_WORKSPACE_MAX_BYTES (the workspace also holds 8 bytes per request); the device pool is neither read nor
+ * filled, nothing counts in cryo_codec_counters.  CRYO_E_ARG as for cryo_codec_check_batch (the same block-size rule), a null
+ * request table with n_req > 0, a null d_dst with dst_cap > 0; n_blocks == 0: CRYO_OK, total 0. */
+int cryo_codec_fetch_batch(cryo_codec *c, int method, const void *d_src, const uint64_t *d_src_off,
+                           const uint32_t *d_src_size, uint32_t block_size, uint64_t n_blocks,
+                           const uint64_t *d_req_first, const uint16_t *d_pos, uint64_t n_req,
+                           void *d_dst, uint64_t dst_cap, cryo_fetch_result *d_result, uint64_t *d_total);
+
 /* ---- single block, HOST buffers: what cryo_compress()/cryo_decompress()
  *      (compression.c:125-159) call.  Synchronous: H2D, kernel, D2H. ---- */
 int cryo_codec_compress_block(cryo_codec *c, int method, int param,
@@ -352,6 +408,21 @@ int cryo_codec_check_blocks(cryo_codec *c, int method, const void *const *h_src,
 int cryo_codec_recode_blocks(cryo_codec *c, int src_method, const void *const *h_src, const uint32_t *h_src_size,
                              size_t n_blocks, size_t block_size, int dst_method, int dst_param,
                              void *h_dst, size_t dst_cap, uint64_t *h_out_off, uint32_t *h_out_size, int32_t *h_status);
+
+/* cryo_codec_fetch_batch on host buffers (stream i: h_src[i], h_src_size[i] bytes; n_req = h_req_first[n_blocks]), synchronous.
+ * Only compressed bytes and the request table travel towards the device, only records and tuples come back.
+ *   Upload   the streams are staged and uploaded as by cryo_codec_recode_blocks (one copy from pinned memory, not pipelined:
+ *            h2d_bytes grows by what cryo_codec_check_blocks uploads for the same streams in one copy), then the request table
+ *            in a second copy: h2d_bytes grows by another align16(8 * (n_blocks + 1)) + align16(2 * n_req).
+ *   Return   per internal chunk the chunk's records come back, then its packed bytes straight into h_dst (two waits per chunk;
+ *            the host derives a chunk's total from its last record): d2h_bytes grows by exactly *h_total + 16 * n_req.
+ *   Errors   a packed total above dst_cap: CRYO_E_DSTSIZE; the call stops at the chunk that does not fit, and *h_total, h_dst
+ *            and h_result hold nothing to rely on (dst_cap >= n_blocks * block_size always fits).  CRYO_E_ARG: as
+ *            cryo_codec_fetch_batch, and an h_req_first that does not start at 0 or that decreases.
+ * Returns CRYO_OK when the batch ran, whatever the records say. */
+int cryo_codec_fetch_blocks(cryo_codec *c, int method, const void *const *h_src, const uint32_t *h_src_size,
+                            size_t n_blocks, size_t block_size, const uint64_t *h_req_first, const uint16_t *h_pos,
+                            void *h_dst, size_t dst_cap, cryo_fetch_result *h_result, uint64_t *h_total);
 
 /* ---- device-resident block pool ("optional device-resident compressed/decompressed pool so
  *      repeated scans skip PCIe"; the reference's cache is host-only: cache.c:17-50).
@@ -423,6 +494,17 @@ int cryo_multi_check_blocks(cryo_multi *m, int method, const void *const *h_src,
 int cryo_multi_recode_blocks(cryo_multi *m, int src_method, const void *const *h_src, const uint32_t *h_src_size,
                              size_t n_blocks, size_t block_size, int dst_method, int dst_param,
                              void *h_dst, size_t dst_cap, uint64_t *h_out_off, uint32_t *h_out_size, int32_t *h_status);
+
+/* cryo_codec_fetch_blocks across the devices: block i -> handle i mod G.  Handle g packs the tuples of its share, in block
+ * order, into a region of its own: block_size * (blocks dealt to handle g) bytes, the regions laid out in handle order from
+ * h_dst on (a region that reaches beyond dst_cap is cut there), so dst_cap >= n_blocks * block_size always suffices.  The
+ * records come back in call order and their `off` counts from h_dst, but the tuples of different handles do NOT interleave in
+ * call order: with more than one handle `off` is not the running sum of the placement rule, within one handle's blocks it is
+ * (from the region's start).  *h_total is the end of the last byte used (0: none).  One handle: exactly
+ * cryo_codec_fetch_blocks. */
+int cryo_multi_fetch_blocks(cryo_multi *m, int method, const void *const *h_src, const uint32_t *h_src_size,
+                            size_t n_blocks, size_t block_size, const uint64_t *h_req_first, const uint16_t *h_pos,
+                            void *h_dst, size_t dst_cap, cryo_fetch_result *h_result, uint64_t *h_total);
 
 /* ---- batch helpers used by staging, tests and the benchmark ---- */
 

@@ -32,6 +32,10 @@ VERIFY_NONE = 0xFFFFFFFF  # first-mismatch offset of a block that verified (or w
 # cryo_check_reason (include/cryo_codec.h): the verdict of the stored-block check, with the offset it reports
 CHECK_OK, CHECK_STREAM, CHECK_HEADER, CHECK_ITEM, CHECK_NONZERO = 0, 1, 2, 3, 4
 CHECK_NONE = 0xFFFFFFFF  # offset of CHECK_OK and CHECK_STREAM
+# cryo_fetch_status (include/cryo_codec.h): the verdict on one requested tuple; 1 .. 3 equal CHECK_*'s, 4 is unused
+FETCH_OK, FETCH_STREAM, FETCH_HEADER, FETCH_ITEM, FETCH_NOITEM, FETCH_BADREQ, FETCH_OVERLAP = 0, 1, 2, 3, 5, 6, 7
+# cryo_fetch_result, 16 bytes per request
+FETCH_RESULT = np.dtype([("status", "<u4"), ("len", "<u4"), ("off", "<u8")])
 LZ4_PATH_AUTO, LZ4_PATH_RING, LZ4_PATH_INDEXED, LZ4_PATH_FEW_BLOCKS = 0, 1, 2, 3
 
 DIST_WIDE, DIST_NARROW, DIST_INT4, DIST_RANDOM, DIST_ZEROS = range(5)
@@ -58,6 +62,7 @@ ABI_SYMBOLS = [
     "cryo_codec_verify_batch", "cryo_codec_last_verify_failure", "cryo_multi_last_verify_failure",
     "cryo_codec_check_batch", "cryo_codec_check_blocks", "cryo_multi_check_blocks",
     "cryo_codec_recode_batch", "cryo_codec_recode_blocks", "cryo_multi_recode_blocks",
+    "cryo_codec_fetch_batch", "cryo_codec_fetch_blocks", "cryo_multi_fetch_blocks",
 ]
 
 
@@ -148,6 +153,9 @@ def lib():
     L.cryo_codec_recode_batch.argtypes = [vp, i32, vp, vp, vp, u32, u64, i32, i32, vp, u64, vp, vp]
     L.cryo_codec_recode_blocks.argtypes = [vp, i32, vp, vp, sz, sz, i32, i32, vp, sz, vp, vp, vp]
     L.cryo_multi_recode_blocks.argtypes = [vp, i32, vp, vp, sz, sz, i32, i32, vp, sz, vp, vp, vp]
+    L.cryo_codec_fetch_batch.argtypes = [vp, i32, vp, vp, vp, u32, u64, vp, vp, u64, vp, u64, vp, vp]
+    L.cryo_codec_fetch_blocks.argtypes = [vp, i32, vp, vp, sz, sz, vp, vp, vp, sz, vp, C.POINTER(u64)]
+    L.cryo_multi_fetch_blocks.argtypes = [vp, i32, vp, vp, sz, sz, vp, vp, vp, sz, vp, C.POINTER(u64)]
     _bound = True
     return L
 
@@ -183,6 +191,34 @@ def recode_blocks_call(fn, handle, chk, src_method, comps, block_size, dst_metho
     off, osz, st = off[:n], osz[:n], st[:n]
     outs = [dst[int(off[i]):int(off[i]) + int(osz[i])] if st[i] == 0 else None for i in range(n)]
     return outs, st, off, osz, dst
+
+
+def request_table(requests):
+    """the CSR request table of a fetch call from one list of 1-based item positions per block: (req_first u64[n + 1],
+    pos u16[n_req])"""
+    first = np.zeros(len(requests) + 1, np.uint64)
+    first[1:] = np.cumsum([len(r) for r in requests], dtype=np.uint64)
+    pos = np.array([p for r in requests for p in r], np.uint16)
+    return first, pos
+
+
+def fetch_blocks_call(fn, handle, chk, method, comps, block_size, requests, dst=None):
+    """cryo_codec_fetch_blocks / cryo_multi_fetch_blocks (fn) on a list of host streams and one list of positions per block;
+    returns (records: FETCH_RESULT array in call order, dst, total).  dst: the caller's buffer (its capacity is len(dst)), else a
+    fresh one of n * block_size bytes"""
+    n = len(comps)
+    arrs = [np.ascontiguousarray(np.asarray(c, dtype=np.uint8)) for c in comps]
+    src = (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.nbytes else None for a in arrs])
+    szs = (C.c_uint32 * max(n, 1))(*[a.nbytes for a in arrs])
+    first, pos = request_table(requests)
+    n_req = int(first[-1])
+    if dst is None:
+        dst = np.zeros(max(n, 1) * block_size, np.uint8)
+    res = np.zeros(max(n_req, 1), FETCH_RESULT)
+    total = C.c_uint64()
+    chk(fn(handle, method, src, szs, n, block_size, first.ctypes.data, pos.ctypes.data if n_req else None, dst.ctypes.data,
+           dst.nbytes, res.ctypes.data, C.byref(total)), "fetch_blocks")
+    return res[:n_req], dst, total.value
 
 
 class DeviceBuffer:
@@ -353,6 +389,21 @@ class Codec:
         one: its capacity is len(dst))"""
         return recode_blocks_call(self.L.cryo_codec_recode_blocks, self.h, self._chk, src_method, comps, block_size,
                                   dst_method, dst_param, dst)
+
+    def fetch_batch(self, method, d_src, d_off, d_sizes, block_size, n, d_req_first, d_pos, n_req, d_dst, dst_cap, d_result,
+                    d_total):
+        """gather the requested tuples of the n stored blocks (d_src + d_off[i], d_sizes[i] bytes): block i owns requests
+        d_req_first[i] .. d_req_first[i + 1] - 1 of d_pos (1-based item positions); d_result[r] = {status, len, off} (FETCH_*,
+        16 bytes per request), the tuples packed into d_dst, the packed total in d_total (u64).  Asynchronous."""
+        self._chk(self.L.cryo_codec_fetch_batch(self.h, method, d_src.ptr, d_off.ptr, d_sizes.ptr, block_size, n, d_req_first.ptr,
+                                                d_pos.ptr if d_pos else None, n_req, d_dst.ptr if d_dst else None, dst_cap,
+                                                d_result.ptr if d_result else None, d_total.ptr), "fetch_batch")
+
+    def fetch_blocks(self, method, comps, block_size, requests, dst=None):
+        """fetch tuples of host streams by position (requests[i]: the 1-based item positions wanted of block i, ascending);
+        returns (records, dst, total): records a FETCH_RESULT array in call order, tuple r the records[r]["len"] bytes at
+        dst[records[r]["off"]:] when its status is FETCH_OK"""
+        return fetch_blocks_call(self.L.cryo_codec_fetch_blocks, self.h, self._chk, method, comps, block_size, requests, dst)
 
     def last_verify_failure(self):
         """(block, first mismatch) that made the last host-buffer compress call fail verification, or None"""

@@ -1031,6 +1031,77 @@ static int check_pass(cryo_codec *c, int method, const uint8_t *d_src, const uin
 
 static bool check_block_size_ok(size_t block_size) { return block_size >= 16 && block_size % 8 == 0 && block_size <= 0x7E000000u; }
 
+/* ---- the tuple fetch ----
+ * The shared decode loop over the caller's stream table; on every decoded chunk fetch.hip writes the records of the chunk's
+ * requests, places the blocks behind the running total -- which stays in device memory from chunk to chunk -- and copies the
+ * tuples out.  The pass's fixed bytes hold the side table (8 bytes per request of the whole call) and, for the host-buffer call,
+ * the running total; per chunk (own) each block has its sum and base and, for the host-buffer call, a row of the chunk's staging
+ * area for packed bytes (a chunk's tuples take less than K * B bytes: the OVERLAP rule).  Its decodes count nowhere. */
+namespace {
+struct FetchIo {
+    const uint64_t *d_req_first = nullptr; /* device: n + 1 entries */
+    const uint16_t *d_pos = nullptr;
+    uint64_t n_req = 0;
+    cryo_fetch_result *d_result = nullptr;
+    /* device-resident call: the caller's buffer and total */
+    uint8_t *d_dst = nullptr;
+    uint64_t dst_cap = 0;
+    uint64_t *d_total = nullptr;
+    /* host-buffer call: the request table as the host knows it, and where records and bytes go */
+    const uint64_t *h_req_first = nullptr;
+    uint8_t *h_dst = nullptr;
+    cryo_fetch_result *h_result = nullptr;
+    uint64_t h_total = 0;
+};
+} // namespace
+
+static int fetch_pass(cryo_codec *c, int method, const uint8_t *d_src, const uint64_t *d_src_off, const uint32_t *d_src_size,
+                      uint32_t B, uint64_t n, FetchIo &io)
+{
+    static_assert(sizeof(cryo_fetch_result) == sizeof(uint4), "cryo_fetch_result is the kernels' 16-byte record");
+    const bool host = io.h_req_first != nullptr;
+    const cryo_codec_counters keep = c->ctr;
+    const uint64_t side_bytes = (io.n_req * 8u + 255u) & ~(uint64_t)255u;
+    const uint64_t row = ((uint64_t)B + 15u) & ~(uint64_t)15u; /* a block's share of the chunk's staging area */
+    DecodePass ps;
+    ps.d_comp = d_src; ps.d_comp_off = d_src_off; ps.d_comp_size = d_src_size;
+    ps.fixed = side_bytes + 256u;                 /* side table; the running total of the host-buffer call */
+    ps.own_per_block = 32u + (host ? row : 0u);   /* sum u64, K + 1 bases u64 (within 24 K bytes); staging row */
+    ps.run = [&](const DecodeChunk &ch) -> int {
+        uint2 *side = (uint2 *)ch.fixed;
+        uint64_t *running = host ? (uint64_t *)(ch.fixed + side_bytes) : io.d_total;
+        uint64_t *sum = (uint64_t *)ch.own, *base = sum + ch.K;
+        uint8_t *stage = ch.own + 32u * ch.K;
+        if (ch.lo == 0) HIP_TRY(c, hipMemsetAsync(running, 0, sizeof(uint64_t), c->stream));
+        HIP_TRY(c, cryo::launch_fetch(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.d_req_first + ch.lo, io.d_pos, io.n_req,
+                                      (uint4 *)io.d_result, side, sum, base, running, host ? stage : io.d_dst,
+                                      host ? ch.K * row : io.dst_cap, host, c->lz4_opts.cus));
+        if (!host) return CRYO_OK;
+        /* the chunk's records, then -- its total known from the last of them -- its bytes: two waits per chunk */
+        const uint64_t r0 = io.h_req_first[ch.lo], r1 = io.h_req_first[ch.lo + ch.cnt];
+        if (r1 == r0) return CRYO_OK; /* no request, no tuple */
+        HIP_TRY(c, hipMemcpyAsync(io.h_result + r0, io.d_result + r0, (r1 - r0) * sizeof(cryo_fetch_result), hipMemcpyDeviceToHost,
+                                  c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        c->xfer_ctr.d2h_bytes += (r1 - r0) * sizeof(cryo_fetch_result);
+        const cryo_fetch_result &last = io.h_result[r1 - 1];
+        const uint64_t end = last.off + (((uint64_t)last.len + 7u) & ~(uint64_t)7u);
+        if (end < io.h_total || end - io.h_total > ch.K * row) return CRYO_E_HIP; /* not a placement */
+        const uint64_t tot = end - io.h_total;
+        if (end > io.dst_cap) return CRYO_E_DSTSIZE;
+        if (tot) {
+            HIP_TRY(c, hipMemcpyAsync(io.h_dst + io.h_total, stage, tot, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            c->xfer_ctr.d2h_bytes += tot;
+        }
+        io.h_total = end;
+        return CRYO_OK;
+    };
+    const int rc = decode_pass(c, method, B, n, ps);
+    c->ctr = keep;
+    return rc;
+}
+
 /* ---- recompression ----
  * The shared decode loop over the caller's stream table; every decoded chunk is encoded by cryo_codec_compress_batch -- the
  * path of every compress call, so the handle's encode options (segment mode, checksums, verification) apply as they are --
@@ -1170,6 +1241,28 @@ int cryo_codec_check_batch(cryo_codec *c, int method, const void *d_src, const u
     if (!d_src || !d_src_off || !d_src_size || !d_result) return CRYO_E_ARG;
     return guarded([&] {
         return check_pass(c, method, (const uint8_t *)d_src, d_src_off, d_src_size, block_size, n_blocks, d_result);
+    });
+}
+
+int cryo_codec_fetch_batch(cryo_codec *c, int method, const void *d_src, const uint64_t *d_src_off, const uint32_t *d_src_size,
+                           uint32_t block_size, uint64_t n_blocks, const uint64_t *d_req_first, const uint16_t *d_pos, uint64_t n_req,
+                           void *d_dst, uint64_t dst_cap, cryo_fetch_result *d_result, uint64_t *d_total)
+{
+    DevGuard dev_(c);
+    if (!c || !method_ok(method) || !check_block_size_ok(block_size)) return CRYO_E_ARG;
+    if (!d_total || ((uintptr_t)d_total & 7u) != 0) return CRYO_E_ARG;
+    if (n_blocks == 0) {
+        HIP_TRY(c, hipMemsetAsync(d_total, 0, sizeof(uint64_t), c->stream));
+        return CRYO_OK;
+    }
+    if (!d_src || !d_src_off || !d_src_size || !d_req_first || ((uintptr_t)d_req_first & 7u) != 0) return CRYO_E_ARG;
+    if (n_req > 0 && (!d_pos || !d_result)) return CRYO_E_ARG;
+    if ((!d_dst && dst_cap > 0) || ((uintptr_t)d_dst & 7u) != 0 || ((uintptr_t)d_result & 15u) != 0) return CRYO_E_ARG;
+    return guarded([&] {
+        FetchIo io;
+        io.d_req_first = d_req_first; io.d_pos = d_pos; io.n_req = n_req; io.d_result = d_result;
+        io.d_dst = (uint8_t *)d_dst; io.dst_cap = dst_cap; io.d_total = d_total;
+        return fetch_pass(c, method, (const uint8_t *)d_src, d_src_off, d_src_size, block_size, n_blocks, io);
     });
 }
 
@@ -1744,6 +1837,69 @@ int cryo_codec_recode_blocks(cryo_codec *c, int src_method, const void *const *h
     });
 }
 
+/* the tuple fetch of n streams given by pointer: the streams staged and uploaded as recompression's (stage_streams), the request
+ * table from the same pinned buffer in a second copy, both into place before the first decode; records and tuples come back
+ * chunk by chunk (fetch_pass).  h_base: what the records' offsets count from (a multi-GPU share's region within the caller's
+ * h_dst); *h_total is relative to h_dst as given here */
+static int fetch_blocks_impl(cryo_codec *c, int method, const void *const *h_src, const uint32_t *h_src_size, size_t n,
+                             size_t block_size, const uint64_t *h_req_first, const uint16_t *h_pos, void *h_dst, size_t dst_cap,
+                             uint64_t h_base, cryo_fetch_result *h_result, uint64_t *h_total)
+{
+    DevGuard dev_(c);
+    if (!c || !method_ok(method) || !check_block_size_ok(block_size) || !h_total) return CRYO_E_ARG;
+    *h_total = 0;
+    if (n == 0) return CRYO_OK;
+    if (!h_src || !h_src_size || !h_req_first || h_req_first[0] != 0) return CRYO_E_ARG;
+    for (size_t i = 0; i < n; i++)
+        if (h_req_first[i + 1] < h_req_first[i]) return CRYO_E_ARG;
+    const uint64_t n_req = h_req_first[n];
+    if (n_req > 0 && (!h_pos || !h_result)) return CRYO_E_ARG;
+    if (!h_dst && dst_cap > 0) return CRYO_E_ARG;
+    ScopedLocalCpus numa_(n * block_size >= ((size_t)8 << 20) ? c : nullptr);
+    /* the request table: [first u64 x (n + 1)][pos u16 x n_req][records x n_req], each part 16-byte aligned */
+    const size_t t_first = 0, t_pos = ((n + 1) * 8 + 15) & ~(size_t)15, t_rec = t_pos + ((n_req * 2 + 15) & ~(size_t)15);
+    size_t streams = (n * 12 + 63) & ~(size_t)63; /* what stage_streams lays out in the pinned buffer */
+    for (size_t i = 0; i < n; i++) streams += ((size_t)h_src_size[i] + 15) & ~(size_t)15;
+    const size_t p_tbl = (streams + 64 + 15) & ~(size_t)15;
+    int rc;
+    /* every allocation of the call before the uploads are queued; the pinned buffer at its final size, so that the staging of
+     * the streams leaves it where it is */
+    if ((rc = ensure_pinned(c, p_tbl + t_rec)) != CRYO_OK) return rc;
+    if ((rc = ensure(c, &c->hb_meta, &c->hb_meta_cap, t_rec + n_req * sizeof(cryo_fetch_result) + 64)) != CRYO_OK) return rc;
+    StagedStreams sg;
+    if ((rc = stage_streams(c, h_src, h_src_size, n, sg, true)) != CRYO_OK) return rc;
+    uint8_t *pin = (uint8_t *)c->pin + p_tbl;
+    memset(pin, 0, t_rec);
+    memcpy(pin + t_first, h_req_first, (n + 1) * 8);
+    if (n_req) memcpy(pin + t_pos, h_pos, n_req * 2);
+    HIP_TRY(c, hipMemcpyAsync(c->hb_meta, pin, t_rec, hipMemcpyHostToDevice, c->stream));
+    c->xfer_ctr.h2d_bytes += t_rec;
+    FetchIo io;
+    io.d_req_first = (const uint64_t *)(c->hb_meta + t_first); io.d_pos = (const uint16_t *)(c->hb_meta + t_pos);
+    io.n_req = n_req; io.d_result = (cryo_fetch_result *)(c->hb_meta + t_rec);
+    io.h_req_first = h_req_first; io.h_dst = (uint8_t *)h_dst; io.dst_cap = dst_cap; io.h_result = h_result;
+    rc = fetch_pass(c, method, c->hb_src, (const uint64_t *)(c->hb_src + sg.o_off), (const uint32_t *)(c->hb_src + sg.o_sz),
+                    (uint32_t)block_size, n, io);
+    (void)hipStreamSynchronize(c->stream); /* nothing in flight from the pinned buffer or into the caller's memory */
+    if (rc != CRYO_OK) return rc;
+    if (h_base)
+        for (uint64_t r = 0; r < n_req; r++) h_result[r].off += h_base;
+    *h_total = io.h_total;
+    return CRYO_OK;
+}
+
+int cryo_codec_fetch_blocks(cryo_codec *c, int method, const void *const *h_src, const uint32_t *h_src_size, size_t n,
+                            size_t block_size, const uint64_t *h_req_first, const uint16_t *h_pos, void *h_dst, size_t dst_cap,
+                            cryo_fetch_result *h_result, uint64_t *h_total)
+{
+    return guarded([&] {
+        const int rc = fetch_blocks_impl(c, method, h_src, h_src_size, n, block_size, h_req_first, h_pos, h_dst, dst_cap, 0, h_result,
+                                         h_total);
+        if (c) ws_trim_after_call(c);
+        return rc;
+    });
+}
+
 } /* extern "C" */
 
 /* ---- device-resident block pool ---- */
@@ -2196,6 +2352,62 @@ int cryo_multi_recode_blocks(cryo_multi *m, int src_method, const void *const *h
             return (int)CRYO_OK;
         });
     });
+}
+
+/* block i -> handle i mod G; handle g packs its share, in block order, into a region of block_size * (its blocks) bytes, the
+ * regions in handle order; the records come back in call order with offsets that count from h_dst */
+int cryo_multi_fetch_blocks(cryo_multi *m, int method, const void *const *h_src, const uint32_t *h_src_size, size_t n,
+                            size_t block_size, const uint64_t *h_req_first, const uint16_t *h_pos, void *h_dst, size_t dst_cap,
+                            cryo_fetch_result *h_result, uint64_t *h_total)
+{
+    if (!m || m->h.empty() || !method_ok(method) || !check_block_size_ok(block_size) || !h_total) return CRYO_E_ARG;
+    const size_t G = m->h.size();
+    if (G == 1)
+        return cryo_codec_fetch_blocks(m->h[0], method, h_src, h_src_size, n, block_size, h_req_first, h_pos, h_dst, dst_cap, h_result,
+                                       h_total);
+    *h_total = 0;
+    if (n == 0) return CRYO_OK;
+    if (!h_src || !h_src_size || !h_req_first || h_req_first[0] != 0) return CRYO_E_ARG;
+    for (size_t i = 0; i < n; i++)
+        if (h_req_first[i + 1] < h_req_first[i]) return CRYO_E_ARG;
+    if (h_req_first[n] > 0 && (!h_pos || !h_result)) return CRYO_E_ARG;
+    if (!h_dst && dst_cap > 0) return CRYO_E_ARG;
+    std::vector<uint64_t> end(G, 0);
+    const int rc = guarded([&] {
+        return multi_run(m, n, [&](size_t g, const std::vector<size_t> &idx) {
+            /* handles before g hold blocks g' < g of every round of G: (n - g' + G - 1) / G each */
+            uint64_t start = 0;
+            for (size_t q = 0; q < g && q < n; q++) start += (uint64_t)((n - q + G - 1) / G) * block_size;
+            const uint64_t want = (uint64_t)idx.size() * block_size;
+            const uint64_t cap = dst_cap > start ? (dst_cap - start < want ? dst_cap - start : want) : 0;
+            std::vector<const void *> src(idx.size());
+            std::vector<uint32_t> sz(idx.size());
+            std::vector<uint64_t> first(idx.size() + 1, 0);
+            for (size_t k = 0; k < idx.size(); k++) {
+                src[k] = h_src[idx[k]];
+                sz[k] = h_src_size[idx[k]];
+                first[k + 1] = first[k] + (h_req_first[idx[k] + 1] - h_req_first[idx[k]]);
+            }
+            std::vector<uint16_t> pos(first.back() ? first.back() : 1);
+            std::vector<cryo_fetch_result> res(first.back() ? first.back() : 1);
+            for (size_t k = 0; k < idx.size(); k++)
+                if (first[k + 1] > first[k])
+                    memcpy(&pos[first[k]], h_pos + h_req_first[idx[k]], (first[k + 1] - first[k]) * sizeof(uint16_t));
+            uint64_t tot = 0;
+            const int r = fetch_blocks_impl(m->h[g], method, src.data(), sz.data(), idx.size(), block_size, first.data(), pos.data(),
+                                            cap ? (uint8_t *)h_dst + start : nullptr, cap, start, res.data(), &tot);
+            if (r != CRYO_OK) return r;
+            for (size_t k = 0; k < idx.size(); k++)
+                if (first[k + 1] > first[k])
+                    memcpy(h_result + h_req_first[idx[k]], &res[first[k]], (first[k + 1] - first[k]) * sizeof(cryo_fetch_result));
+            end[g] = tot ? start + tot : 0;
+            return (int)CRYO_OK;
+        });
+    });
+    if (rc != CRYO_OK) return rc;
+    for (size_t g = 0; g < G; g++)
+        if (end[g] > *h_total) *h_total = end[g];
+    return CRYO_OK;
 }
 
 int cryo_multi_decompress_blocks_keyed(cryo_multi *m, int method, const uint64_t *keys, const void *const *h_src,

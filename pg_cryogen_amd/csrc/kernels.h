@@ -208,6 +208,18 @@ hipError_t launch_recode_offsets(hipStream_t s, uint32_t cnt, uint64_t slot_stri
 hipError_t launch_recode_pack(hipStream_t s, uint32_t cnt, const uint8_t *d_slots, uint64_t slot_stride, const uint32_t *d_size,
                               const uint64_t *d_off, const uint64_t *d_total, uint8_t *d_packed, int cus);
 
+/* the tuple fetch (fetch.hip) on one decoded chunk of cnt blocks (block k at d_dec + k * dec_stride, 16-byte aligned rows; its
+ * decoder status in d_dec_status[k]): k_fetch_items, k_fetch_offsets, k_fetch_copy.  Block k owns requests d_req_first[k] ..
+ * d_req_first[k + 1] - 1 of d_pos / d_result / d_side (indices within the whole call, cut to n_req); d_result[r] = {status, len,
+ * off} (cryo_fetch_result, 16-byte aligned), d_side: 8 bytes per request of scratch; d_sum: cnt, d_base: cnt + 1 entries of
+ * scratch; *d_running: the packed total before the chunk in, after it out.  The chunk's tuples go to d_dst (8-byte aligned) at
+ * their offset within the call, or -- chunk_relative -- at that offset less the chunk's first; a tuple that would end beyond
+ * dst_cap is not written.  cus: compute units of the device (0: an MI355X's 256) */
+hipError_t launch_fetch(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
+                        const int32_t *d_dec_status, const uint64_t *d_req_first, const uint16_t *d_pos, uint64_t n_req,
+                        uint4 *d_result, uint2 *d_side, uint64_t *d_sum, uint64_t *d_base, uint64_t *d_running, uint8_t *d_dst,
+                        uint64_t dst_cap, bool chunk_relative, int cus);
+
 } // namespace cryo
 
 #define CRYO_WAVE 64

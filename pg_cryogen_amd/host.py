@@ -28,6 +28,9 @@ CHECK_BLOCKS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p
 RECODE_BLOCKS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_size_t,
                                C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64),
                                C.POINTER(C.c_uint32), C.POINTER(C.c_int32))
+FETCH_BLOCKS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_size_t,
+                              C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint16), C.c_void_p, C.c_size_t, C.c_void_p,
+                              C.POINTER(C.c_uint64))
 CRYO_CHECK_CHAIN, CRYO_CHECK_METHOD = 16, 17   # host-only reasons of check.h (beside cryo_check_reason 0..4)
 
 
@@ -53,6 +56,12 @@ class CryoCodecOpsRecode(CryoCodecOpsCheck):
     _fields_ = [("recode_blocks", C.c_void_p)]
 
 
+class CryoCodecFetchOps(C.Structure):
+    """host/compression.h's one-function table of the tuple fetch (FETCH_BLOCKS_FN), bound beside a CryoCodecOps double with
+    cryo_host_set_fetch_ops (test build)"""
+    _fields_ = [("fetch_blocks", FETCH_BLOCKS_FN)]
+
+
 class CryoRel(C.Structure):
     _fields_ = [("relid", C.c_uint), ("handle", C.c_void_p), ("ops", C.c_void_p)]
 
@@ -73,6 +82,25 @@ class CryoRecompressTotals(C.Structure):
                                           "pages_in", "pages_out", "codec_calls")]
 
 
+class CryoFetchPage(C.Structure):
+    _fields_ = [("block", C.c_uint32), ("ntuples", C.c_int32), ("offsets", C.POINTER(C.c_uint16))]
+
+
+class CryoFetchedTuple(C.Structure):
+    _fields_ = [("block", C.c_uint32), ("pos", C.c_uint16), ("created_xid", C.c_uint32), ("data", C.c_void_p),
+                ("len", C.c_uint32)]
+
+
+class CryoFetchReport(C.Structure):
+    _fields_ = [("block", C.c_uint32), ("reason", C.c_uint32), ("detail", C.c_uint32)]
+
+
+class CryoFetchTotals(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("pages", "not_block_starts", "blocks", "tuples", "bad", "codec_calls", "bytes_back")]
+
+
+FETCH_TUPLE_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(CryoFetchedTuple))
+FETCH_REPORT_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(CryoFetchReport))
 RECOMPRESS_MOVED_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32)
 
 
@@ -109,6 +137,9 @@ def lib():
     if hasattr(L, "cryo_host_set_codec_ops"):   # test build only
         L.cryo_host_set_codec_ops.argtypes = [C.POINTER(CryoCodecOps)]
         L.cryo_host_set_codec_ops.restype = None
+    if hasattr(L, "cryo_host_set_fetch_ops"):   # test build only
+        L.cryo_host_set_fetch_ops.argtypes = [C.POINTER(CryoCodecFetchOps)]
+        L.cryo_host_set_fetch_ops.restype = None
     L.cryo_host_codec_error.restype = C.c_char_p
     L.cryo_compat_set_error_handler.argtypes = [ERROR_HANDLER]
     L.cryo_compat_set_error_handler.restype = None
@@ -171,6 +202,8 @@ def lib():
     L.cryo_check_relation.argtypes = [C.POINTER(CryoRel), CHECK_REPORT_FN, vp, C.POINTER(CryoCheckTotals)]
     L.cryo_recompress_relation.argtypes = [C.POINTER(CryoRel), C.POINTER(CryoRel), i32, i32, RECOMPRESS_MOVED_FN, CHECK_REPORT_FN,
                                            vp, C.POINTER(CryoRecompressTotals)]
+    L.cryo_fetch_tuples.argtypes = [C.POINTER(CryoRel), C.POINTER(CryoFetchPage), sz, FETCH_TUPLE_FN, FETCH_REPORT_FN, vp,
+                                    C.POINTER(CryoFetchTotals)]
     for n in ("cryo_cache_hits", "cryo_cache_misses", "cryo_cache_codec_calls"):
         getattr(L, n).restype = C.c_uint64
     _libs[prod] = L
@@ -215,6 +248,39 @@ def recompress_relation(src, dst, method, param):
     if rc != 0:
         raise RecompressRelationError(rc)
     return moved, reports, {f: getattr(t, f) for f, _ in CryoRecompressTotals._fields_}
+
+
+class FetchTuplesError(RuntimeError):
+    def __init__(self, code, events, totals):
+        self.code, self.events, self.totals = code, events, totals
+        super().__init__("cryo_fetch_tuples failed: %d" % code)
+
+
+def fetch_tuples(rel, pages):
+    """cryo_fetch_tuples (host/fetch.h).  pages: a list of (block, positions) in ascending block order, positions a list of
+    1-based item positions or None for a lossy page.  Returns (events, totals): events in delivery order, ("tuple", block, pos,
+    created_xid, bytes of MAXALIGN(len), len) or ("report", block, reason, detail); totals a dict.  A nonzero status raises
+    FetchTuplesError (which carries what was delivered)."""
+    keep = [None if p is None else (C.c_uint16 * max(len(p), 1))(*p) for _, p in pages]
+    arr = (CryoFetchPage * max(len(pages), 1))()
+    for i, (b, p) in enumerate(pages):
+        arr[i].block = b
+        arr[i].ntuples = -1 if p is None else len(p)
+        arr[i].offsets = None if p is None else C.cast(keep[i], C.POINTER(C.c_uint16))
+    events = []
+
+    def on_tuple(arg, t):
+        t = t.contents
+        events.append(("tuple", t.block, t.pos, t.created_xid, C.string_at(t.data, (t.len + 7) & ~7), t.len))
+
+    tcb = FETCH_TUPLE_FN(on_tuple)
+    rcb = FETCH_REPORT_FN(lambda arg, r: events.append(("report", r.contents.block, r.contents.reason, r.contents.detail)))
+    t = CryoFetchTotals()
+    rc = lib().cryo_fetch_tuples(C.byref(rel), arr, len(pages), tcb, rcb, None, C.byref(t))
+    totals = {f: getattr(t, f) for f, _ in CryoFetchTotals._fields_}
+    if rc != 0:
+        raise FetchTuplesError(rc, events, totals)
+    return events, totals
 
 
 def transfer_counters():

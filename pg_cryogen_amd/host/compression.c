@@ -101,9 +101,22 @@ static CryoCodecOps hip_ops = {hip_bound, hip_compress_blocks, hip_decompress_bl
                                hip_recode_blocks};
 static const CryoCodecOps *bound_ops; /* CPU-only plumbing tests bind a double here (CRYO_HOST_TEST_HOOKS builds only) */
 
+static int hip_fetch_blocks(void *ctx, int method, const void *const *src, const uint32_t *sz, size_t n, size_t bs,
+                            const uint64_t *req_first, const uint16_t *pos, void *dst, size_t dst_cap, void *result, uint64_t *total)
+{
+    return cryo_multi_fetch_blocks((cryo_multi *)ctx, method, src, sz, n, bs, req_first, pos, dst, dst_cap,
+                                   (cryo_fetch_result *)result, total);
+}
+static const CryoCodecFetchOps hip_fetch_ops = {hip_fetch_blocks};
+static const CryoCodecFetchOps *bound_fetch_ops; /* the fetch table of a bound double (CRYO_HOST_TEST_HOOKS builds only) */
+
 #ifdef CRYO_HOST_TEST_HOOKS
 void cryo_host_set_codec_ops(const CryoCodecOps *ops) { bound_ops = ops; }
 #endif
+#ifdef CRYO_HOST_TEST_HOOKS
+void cryo_host_set_fetch_ops(const CryoCodecFetchOps *ops) { bound_fetch_ops = ops; }
+#endif
+const CryoCodecFetchOps *cryo_host_fetch_ops(void) { return bound_ops ? bound_fetch_ops : &hip_fetch_ops; }
 const char *cryo_host_codec_error(void) { return codec_err; }
 
 const CryoCodecOps *cryo_host_codec_ops(void)

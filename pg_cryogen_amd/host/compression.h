@@ -101,6 +101,19 @@ typedef struct CryoCodecOps {
 #ifdef CRYO_HOST_TEST_HOOKS
 void cryo_host_set_codec_ops(const CryoCodecOps *ops); /* test builds only: bind a double; NULL restores the HIP binding */
 #endif
+/* the tuple fetch (fetch.h, cryo_fetch_tuples) is bound through a table of its own: CryoCodecOps keeps its layout.  It is called
+ * with the ctx of the bound CryoCodecOps.  fetch_blocks is cryo_multi_fetch_blocks (include/cryo_codec.h): block i owns requests
+ * req_first[i] .. req_first[i + 1] - 1 of pos (1-based item positions), result is cryo_fetch_result[req_first[n]] (16 bytes per
+ * request: u32 status, u32 len, u64 off), the OK tuples lie packed in dst, *total is the end of the last byte used */
+typedef struct CryoCodecFetchOps {
+    int (*fetch_blocks)(void *ctx, int method, const void *const *src, const uint32_t *src_size, size_t n, size_t block_size,
+                        const uint64_t *req_first, const uint16_t *pos, void *dst, size_t dst_cap, void *result, uint64_t *total);
+} CryoCodecFetchOps;
+/* the fetch table that goes with cryo_host_codec_ops(): production's binds the GPU codec; NULL when a bound double has none */
+const CryoCodecFetchOps *cryo_host_fetch_ops(void);
+#ifdef CRYO_HOST_TEST_HOOKS
+void cryo_host_set_fetch_ops(const CryoCodecFetchOps *ops); /* test builds only: the fetch table of the bound double, or NULL */
+#endif
 const CryoCodecOps *cryo_host_codec_ops(void);         /* lazily opens the GPU codec */
 void cryo_host_codec_trim(void);                         /* idle backend: free the binding's device workspace and staging buffers */
 size_t cryo_host_codec_bound(int method, size_t n);      /* cryo_codec_bound (or the bound double's): never opens the GPU */
