@@ -170,6 +170,10 @@ int cryo_dev_memset(cryo_codec *c, void *d_dst, int value, size_t bytes);       
  * stateless one-shot APIs, compression.c:70-72,102-104).  All calls are
  * asynchronous on the handle's stream; per-block results land in the device
  * arrays d_out_size / d_status (cryo_status values).
+ *
+ * block_size: 1 .. 0x7E000000 (LZ4_MAX_INPUT_SIZE, 2 GiB - 32 MiB) for both methods.  Every entry point that takes a
+ * block size, these and the host-buffer and multi-GPU ones below, returns CRYO_E_ARG for a larger one, also for a call of
+ * no blocks; nothing is launched.
  */
 
 /*

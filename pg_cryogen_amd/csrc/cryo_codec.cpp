@@ -22,6 +22,10 @@
 #include <unordered_map>
 #include <vector>
 
+/* the largest block any entry point takes: LZ4_MAX_INPUT_SIZE (2 GiB - 32 MiB), for both methods */
+static constexpr size_t kMaxBlockSize = 0x7E000000u;
+static bool block_size_ok(size_t block_size) { return block_size != 0 && block_size <= kMaxBlockSize; }
+
 /* A few host threads kept by a handle (staging copies of the K-block calls) or by the multi-GPU dispatcher (one per
  * further device).  The caller of the C ABI is a PostgreSQL backend: workers are created with every signal blocked
  * (the backend's SIGUSR1/SIGTERM/SIGINT handlers must only ever run on its own thread), they are created once and
@@ -616,7 +620,7 @@ size_t cryo_codec_bound(int method, size_t n)
 {
     if (method == CRYO_METHOD_LZ4) {
         /* LZ4_compressBound: n + n/255 + 16, 0 above LZ4_MAX_INPUT_SIZE */
-        return n > 0x7E000000u ? 0 : n + n / 255 + 16;
+        return n > kMaxBlockSize ? 0 : n + n / 255 + 16;
     }
     if (method == CRYO_METHOD_ZSTD) {
         /* ZSTD_COMPRESSBOUND: n + n/256 + (n < 128 KiB ? (128 KiB - n) >> 11 : 0) */
@@ -706,7 +710,7 @@ int cryo_codec_compress_batch(cryo_codec *c, int method, int param, const void *
                               int32_t *d_status)
 {
     DevGuard dev_(c);
-    if (!c || !method_ok(method) || block_size == 0) return CRYO_E_ARG;
+    if (!c || !method_ok(method) || !block_size_ok(block_size)) return CRYO_E_ARG;
     if (n_blocks == 0) return CRYO_OK;
     if (!d_src || !d_dst || !d_out_size || !d_status || src_stride < block_size) return CRYO_E_ARG;
     if (dst_stride < cryo_codec_bound(method, block_size)) return CRYO_E_DSTSIZE;
@@ -842,7 +846,7 @@ int cryo_codec_decompress_batch(cryo_codec *c, int method, const void *d_src,
                                 int32_t *d_status)
 {
     DevGuard dev_(c);
-    if (!c || !method_ok(method) || block_size == 0) return CRYO_E_ARG;
+    if (!c || !method_ok(method) || !block_size_ok(block_size)) return CRYO_E_ARG;
     if (n_blocks == 0) return CRYO_OK;
     if (!d_src || !d_src_off || !d_src_size || !d_dst || !d_status || dst_stride < block_size)
         return CRYO_E_ARG;
@@ -1029,7 +1033,7 @@ static int check_pass(cryo_codec *c, int method, const uint8_t *d_src, const uin
     return rc;
 }
 
-static bool check_block_size_ok(size_t block_size) { return block_size >= 16 && block_size % 8 == 0 && block_size <= 0x7E000000u; }
+static bool check_block_size_ok(size_t block_size) { return block_size >= 16 && block_size % 8 == 0 && block_size <= kMaxBlockSize; }
 
 /* ---- the tuple fetch ----
  * The shared decode loop over the caller's stream table; on every decoded chunk fetch.hip writes the records of the chunk's
@@ -1190,7 +1194,7 @@ static int recode_pass(cryo_codec *c, int src_method, const uint8_t *d_src, cons
 
 static int recode_args(const cryo_codec *c, int src_method, int dst_method, int dst_param, size_t block_size)
 {
-    if (!c || !method_ok(src_method) || !method_ok(dst_method) || block_size == 0 || block_size > 0x7E000000u) return CRYO_E_ARG;
+    if (!c || !method_ok(src_method) || !method_ok(dst_method) || !block_size_ok(block_size)) return CRYO_E_ARG;
     if (dst_method == CRYO_METHOD_ZSTD && !cryo::zstd_compress_supported(dst_param, (uint32_t)block_size)) return CRYO_E_UNSUPPORTED;
     return CRYO_OK;
 }
@@ -1223,7 +1227,7 @@ int cryo_codec_verify_batch(cryo_codec *c, int method, const void *d_raw, uint64
                             int32_t *d_status, uint32_t *d_first_mismatch)
 {
     DevGuard dev_(c);
-    if (!c || !method_ok(method) || block_size == 0) return CRYO_E_ARG;
+    if (!c || !method_ok(method) || !block_size_ok(block_size)) return CRYO_E_ARG;
     if (n_blocks == 0) return CRYO_OK;
     if (!d_raw || !d_comp || !d_comp_off || !d_comp_size || !d_status || raw_stride < block_size) return CRYO_E_ARG;
     return guarded([&] {
@@ -1299,7 +1303,7 @@ int cryo_codec_compress_block(cryo_codec *c, int method, int param, const void *
 {
     DevGuard dev_(c);
     if (!c || !h_src || !h_dst || !out_size || !method_ok(method)) return CRYO_E_ARG;
-    if (block_size == 0 || block_size > 0x7E000000u) return CRYO_E_ARG;
+    if (!block_size_ok(block_size)) return CRYO_E_ARG;
     const size_t bound = cryo_codec_bound(method, block_size);
     if (dst_cap < bound) return CRYO_E_DSTSIZE;
     int rc;
@@ -1329,7 +1333,7 @@ int cryo_codec_decompress_block(cryo_codec *c, int method, const void *h_src, si
 {
     DevGuard dev_(c);
     if (!c || !h_src || !h_dst || !method_ok(method)) return CRYO_E_ARG;
-    if (block_size == 0 || block_size > 0x7E000000u) return CRYO_E_ARG;
+    if (!block_size_ok(block_size)) return CRYO_E_ARG;
     if (src_size == 0 || src_size > 0xFFFFFFFFu) return CRYO_E_CORRUPT;
     int rc;
     if ((rc = ensure(c, &c->d_in, &c->in_cap, src_size)) != CRYO_OK) return rc;
@@ -1601,7 +1605,7 @@ static int compress_blocks_body(cryo_codec *c, int method, int param, const void
                                 size_t n, void *h_dst, size_t dst_stride, uint32_t *h_out_size)
 {
     DevGuard dev_(c);
-    if (!c || !method_ok(method) || block_size == 0 || block_size > 0x7E000000u) return CRYO_E_ARG;
+    if (!c || !method_ok(method) || !block_size_ok(block_size)) return CRYO_E_ARG;
     if (n == 0) return CRYO_OK;
     if (!h_src || !h_dst || !h_out_size) return CRYO_E_ARG;
     const size_t bound = cryo_codec_bound(method, block_size);
@@ -1698,7 +1702,7 @@ static int decompress_blocks_impl(cryo_codec *c, int method, const void *const *
 {
     DevGuard dev_(c);
     const bool check = h_result != nullptr;
-    if (!c || !method_ok(method) || block_size == 0 || block_size > 0x7E000000u) return CRYO_E_ARG;
+    if (!c || !method_ok(method) || !block_size_ok(block_size)) return CRYO_E_ARG;
     if (check && !check_block_size_ok(block_size)) return CRYO_E_ARG;
     if (n == 0) return CRYO_OK;
     if (!h_src || !h_src_size || (!check && ((!h_dst && !h_dst_each) || !h_status))) return CRYO_E_ARG;
@@ -1963,7 +1967,7 @@ static int decompress_blocks_keyed_impl(cryo_codec *c, int method, const uint64_
                                         const uint32_t *h_src_size, size_t n, void *const *h_dst, size_t block_size, int32_t *h_status)
 {
     DevGuard dev_(c);
-    if (!c || !method_ok(method) || block_size == 0 || block_size > 0x7E000000u) return CRYO_E_ARG;
+    if (!c || !method_ok(method) || !block_size_ok(block_size)) return CRYO_E_ARG;
     if (n == 0) return CRYO_OK;
     if (!keys || !h_src || !h_src_size || !h_dst || !h_status) return CRYO_E_ARG;
     if (!pool_ready(c, block_size)) return decompress_blocks_impl(c, method, h_src, h_src_size, n, nullptr, h_dst, block_size, h_status);
@@ -2229,7 +2233,7 @@ extern "C" {
 int cryo_multi_compress_blocks(cryo_multi *m, int method, int param, const void *h_src, size_t block_size, size_t n,
                                void *h_dst, size_t dst_stride, uint32_t *h_out_size)
 {
-    if (!m || m->h.empty() || !method_ok(method) || block_size == 0 || block_size > 0x7E000000u) return CRYO_E_ARG;
+    if (!m || m->h.empty() || !method_ok(method) || !block_size_ok(block_size)) return CRYO_E_ARG;
     if (n == 0) return CRYO_OK;
     if (!h_src || !h_dst || !h_out_size) return CRYO_E_ARG;
     if (dst_stride < cryo_codec_bound(method, block_size)) return CRYO_E_DSTSIZE;
@@ -2278,7 +2282,7 @@ static int multi_decompress(cryo_multi *m, int method, const void *const *h_src,
 int cryo_multi_decompress_blocks(cryo_multi *m, int method, const void *const *h_src, const uint32_t *h_src_size, size_t n,
                                  void *h_dst, size_t block_size, int32_t *h_status)
 {
-    if (!m || m->h.empty() || !method_ok(method) || block_size == 0 || block_size > 0x7E000000u) return CRYO_E_ARG;
+    if (!m || m->h.empty() || !method_ok(method) || !block_size_ok(block_size)) return CRYO_E_ARG;
     if (n == 0) return CRYO_OK;
     if (!h_src || !h_src_size || !h_dst || !h_status) return CRYO_E_ARG;
     if (m->h.size() == 1) return cryo_codec_decompress_blocks(m->h[0], method, h_src, h_src_size, n, h_dst, block_size, h_status);
@@ -2288,7 +2292,7 @@ int cryo_multi_decompress_blocks(cryo_multi *m, int method, const void *const *h
 int cryo_multi_decompress_blocks_to(cryo_multi *m, int method, const void *const *h_src, const uint32_t *h_src_size, size_t n,
                                     void *const *h_dst, size_t block_size, int32_t *h_status)
 {
-    if (!m || m->h.empty() || !method_ok(method) || block_size == 0 || block_size > 0x7E000000u) return CRYO_E_ARG;
+    if (!m || m->h.empty() || !method_ok(method) || !block_size_ok(block_size)) return CRYO_E_ARG;
     if (n == 0) return CRYO_OK;
     if (!h_src || !h_src_size || !h_dst || !h_status) return CRYO_E_ARG;
     if (m->h.size() == 1) return cryo_codec_decompress_blocks_to(m->h[0], method, h_src, h_src_size, n, h_dst, block_size, h_status);
@@ -2413,7 +2417,7 @@ int cryo_multi_fetch_blocks(cryo_multi *m, int method, const void *const *h_src,
 int cryo_multi_decompress_blocks_keyed(cryo_multi *m, int method, const uint64_t *keys, const void *const *h_src,
                                        const uint32_t *h_src_size, size_t n, void *const *h_dst, size_t block_size, int32_t *h_status)
 {
-    if (!m || m->h.empty() || !method_ok(method) || block_size == 0 || block_size > 0x7E000000u) return CRYO_E_ARG;
+    if (!m || m->h.empty() || !method_ok(method) || !block_size_ok(block_size)) return CRYO_E_ARG;
     if (n == 0) return CRYO_OK;
     if (!keys || !h_src || !h_src_size || !h_dst || !h_status) return CRYO_E_ARG;
     if (m->h.size() == 1) return cryo_codec_decompress_blocks_keyed(m->h[0], method, keys, h_src, h_src_size, n, h_dst, block_size, h_status);
@@ -2508,7 +2512,7 @@ int cryo_codec_synth_batch(cryo_codec *c, uint64_t seed, uint64_t first_block, u
                            uint64_t n_blocks, uint32_t block_size, int dist, void *d_dst, uint64_t dst_stride)
 {
     DevGuard dev_(c);
-    if (!c || block_size < 64 || dist < 0 || dist > 4) return CRYO_E_ARG;
+    if (!c || block_size < 64 || block_size > kMaxBlockSize || dist < 0 || dist > 4) return CRYO_E_ARG;
     if (n_blocks == 0) return CRYO_OK;
     if (!d_dst || dst_stride < block_size) return CRYO_E_ARG;
     HIP_TRY(c, cryo::launch_synth(c->stream, seed, first_block, block_step ? block_step : 1, n_blocks, block_size, dist,
@@ -2536,7 +2540,7 @@ int cryo_codec_compare_batch(cryo_codec *c, const void *d_a, uint64_t a_stride, 
                              uint64_t *d_mismatch)
 {
     DevGuard dev_(c);
-    if (!c) return CRYO_E_ARG;
+    if (!c || block_size > kMaxBlockSize) return CRYO_E_ARG;
     if (n_blocks == 0) return CRYO_OK;
     if (!d_a || !d_b || !d_mismatch) return CRYO_E_ARG;
     HIP_TRY(c, cryo::launch_compare(c->stream, (const uint8_t *)d_a, a_stride, (const uint8_t *)d_b,
