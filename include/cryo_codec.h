@@ -136,7 +136,13 @@ typedef enum {
      * is hashed by one quad of lanes: about 2 ms for a lone 1 MiB frame.  cryo_codec_bound is unchanged: the frame and its
      * checksum stay within ZSTD_compressBound.  LZ4 blocks have no checksum field: no effect on them.  Other values:
      * CRYO_E_ARG. */
-    CRYO_OPT_ZSTD_CHECKSUM = 13
+    CRYO_OPT_ZSTD_CHECKSUM = 13,
+    /* form of the sequence-index pass where the plan is ONE walker per block (full batches, CRYO_OPT_LZ4_INDEX_WALKERS = 1):
+     * 0 (default) = automatic (the pair for batches that are resident at once, up to 256 blocks per compute unit; the single
+     * wave for larger ones), 1 = one wave walks 64 blocks and feeds their LDS rings itself (k_lz4_index), 2 = a pair of
+     * waves per 64 blocks, one walking and one feeding the same rings (k_lz4_idx_pair).  Both write the same rows; batches
+     * indexed with several walkers per block are not affected.  Other values: CRYO_E_ARG. */
+    CRYO_OPT_LZ4_INDEX_FORM = 14
 } cryo_option;
 int cryo_codec_set_option(cryo_codec *c, int option, int64_t value);
 /* a long-lived backend between bursts: waits for the handle's queued work, then frees its device workspace, the device and
@@ -516,6 +522,15 @@ int cryo_multi_fetch_blocks(cryo_multi *m, int method, const void *const *h_src,
  * first_block + k*block_step (block_step = N, first_block = rank gives rank's round-robin share) */
 int cryo_codec_synth_batch(cryo_codec *c, uint64_t seed, uint64_t first_block, uint64_t block_step,
                            uint64_t n_blocks, uint32_t block_size, int dist, void *d_dst, uint64_t dst_stride);
+/* The LZ4 sequence index read back (test support: a wrong row only costs decode speed, so no decode result shows it).
+ * cryo_codec_lz4_index_cap: 16-bit entries per row of the one-walker index of a block size (0: block_size is 0).
+ * cryo_codec_lz4_index_rows: builds the one-walker-per-block index of the batch (streams as for
+ * cryo_codec_decompress_batch) with the form asked for (1 or 2 of CRYO_OPT_LZ4_INDEX_FORM; 0 = what automatic takes)
+ * in handle workspace and copies it into the caller's device buffers: d_entries[i * cap + j] = low 16 bits of the offset
+ * of token j of block i for j < d_counts[i]; entries behind the count are unspecified.  Asynchronous on the handle's stream. */
+uint32_t cryo_codec_lz4_index_cap(uint32_t block_size);
+int cryo_codec_lz4_index_rows(cryo_codec *c, const void *d_src, const uint64_t *d_src_off, const uint32_t *d_src_size,
+                              uint32_t block_size, uint64_t n_blocks, int form, uint16_t *d_entries, uint32_t *d_counts);
 /* per-block 64-bit checksum (same function as cryo_checksum64() below) */
 int cryo_codec_checksum_batch(cryo_codec *c, const void *d_src, uint64_t src_stride,
                               const uint32_t *d_sizes /* or NULL: fixed_size */, uint32_t fixed_size,

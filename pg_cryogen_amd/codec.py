@@ -28,6 +28,8 @@ OPT_ENCODE_SEGMENT_BYTES = 10  # 0 = byte-identical encoders; 4 KiB .. 128 KiB (
 OPT_ENCODE_SEGMENT_ZSTD_STRATEGY = 11  # highest zstd strategy of segment mode: 1 fast (default) .. 6 btlazy2
 OPT_ENCODE_VERIFY = 12  # 0 (default) = none; 1 = every compress call decodes its output and compares it with the input
 OPT_ZSTD_CHECKSUM = 13  # 0 (default) = none; 1 = every zstd frame written carries a content checksum (XXH64)
+OPT_LZ4_INDEX_FORM = 14  # one-walker index pass: 0 automatic, 1 one wave walks and feeds, 2 a walker wave and a feeder wave
+LZ4_INDEX_AUTO, LZ4_INDEX_SINGLE, LZ4_INDEX_PAIR = 0, 1, 2
 VERIFY_NONE = 0xFFFFFFFF  # first-mismatch offset of a block that verified (or whose stream the decoders reject)
 # cryo_check_reason (include/cryo_codec.h): the verdict of the stored-block check, with the offset it reports
 CHECK_OK, CHECK_STREAM, CHECK_HEADER, CHECK_ITEM, CHECK_NONZERO = 0, 1, 2, 3, 4
@@ -63,6 +65,7 @@ ABI_SYMBOLS = [
     "cryo_codec_check_batch", "cryo_codec_check_blocks", "cryo_multi_check_blocks",
     "cryo_codec_recode_batch", "cryo_codec_recode_blocks", "cryo_multi_recode_blocks",
     "cryo_codec_fetch_batch", "cryo_codec_fetch_blocks", "cryo_multi_fetch_blocks",
+    "cryo_codec_lz4_index_cap", "cryo_codec_lz4_index_rows",
 ]
 
 
@@ -156,6 +159,9 @@ def lib():
     L.cryo_codec_fetch_batch.argtypes = [vp, i32, vp, vp, vp, u32, u64, vp, vp, u64, vp, u64, vp, vp]
     L.cryo_codec_fetch_blocks.argtypes = [vp, i32, vp, vp, sz, sz, vp, vp, vp, sz, vp, C.POINTER(u64)]
     L.cryo_multi_fetch_blocks.argtypes = [vp, i32, vp, vp, sz, sz, vp, vp, vp, sz, vp, C.POINTER(u64)]
+    L.cryo_codec_lz4_index_cap.argtypes = [u32]
+    L.cryo_codec_lz4_index_cap.restype = u32
+    L.cryo_codec_lz4_index_rows.argtypes = [vp, vp, vp, vp, u32, u64, i32, vp, vp]
     _bound = True
     return L
 
@@ -351,6 +357,17 @@ class Codec:
         self._chk(self.L.cryo_codec_decompress_batch(self.h, method, d_src.ptr, d_off.ptr, d_sizes.ptr, d_dst.ptr,
                                                      dst_stride, block_size, n, d_status.ptr),
                   "decompress_batch")
+
+    def lz4_index_cap(self, block_size):
+        """16-bit entries per row of the one-walker LZ4 sequence index of a block size"""
+        return int(self.L.cryo_codec_lz4_index_cap(block_size))
+
+    def lz4_index_rows(self, d_src, d_off, d_sizes, block_size, n, form, d_entries, d_counts):
+        """build the one-walker LZ4 sequence index of the batch with `form` (LZ4_INDEX_*) into d_entries (n x lz4_index_cap
+        uint16) and d_counts (n uint32).  Asynchronous."""
+        self._chk(self.L.cryo_codec_lz4_index_rows(self.h, d_src.ptr, d_off.ptr, d_sizes.ptr, block_size, n, form,
+                                                   d_entries.ptr, d_counts.ptr),
+                  "lz4_index_rows")
 
     def verify_batch(self, method, d_raw, raw_stride, block_size, n, d_comp, d_off, d_sizes, d_status, d_first=None):
         """decode the n streams (d_comp + d_off[i], d_sizes[i] bytes) and compare them with the raw blocks: d_status[i] = OK /

@@ -424,6 +424,7 @@ int cryo_codec_open(int device, cryo_codec **out)
     if (const char *e = cryo_tuning_env("CRYO_PIPE_MIN_MB")) c->pipe_min_bytes = (size_t)atoll(e) << 20; /* 0 = always, huge = never */
     if (const char *e = cryo_tuning_env("CRYO_LZ4_DECODE_PATH")) c->lz4_opts.path = atoi(e);             /* tuning aids: the options' */
     if (const char *e = cryo_tuning_env("CRYO_LZ4_INDEX_WALKERS")) c->lz4_opts.walkers = atoi(e);        /* initial values          */
+    if (const char *e = cryo_tuning_env("CRYO_LZ4_INDEX_FORM")) c->lz4_opts.index_form = atoi(e);
     if (const char *e = cryo_tuning_env("CRYO_ZSTD_DECODE_PATH")) c->zstd_path = atoi(e);
     DevGuard dev_(c); /* the caller's current device is restored on return */
     hipError_t e = hipSuccess;
@@ -538,6 +539,10 @@ int cryo_codec_set_option(cryo_codec *c, int option, int64_t value)
         if (value < 0 || value > 2) return CRYO_E_ARG;
         c->lz4_opts.waves = (int)value;
         return CRYO_OK;
+    case CRYO_OPT_LZ4_INDEX_FORM:
+        if (value < 0 || value > 2) return CRYO_E_ARG;
+        c->lz4_opts.index_form = (int)value;
+        return CRYO_OK;
     case CRYO_OPT_PIPE_MIN_BYTES:
         if (value < 0) return CRYO_E_ARG;
         c->pipe_min_bytes = (size_t)value;
@@ -593,6 +598,7 @@ int cryo_codec_get_option(const cryo_codec *c, int option, int64_t *value)
     case CRYO_OPT_LZ4_DECODE_PATH: *value = c->lz4_opts.path; return CRYO_OK;
     case CRYO_OPT_LZ4_INDEX_WALKERS: *value = c->lz4_opts.walkers; return CRYO_OK;
     case CRYO_OPT_LZ4_DECODE_WAVES: *value = c->lz4_opts.waves; return CRYO_OK;
+    case CRYO_OPT_LZ4_INDEX_FORM: *value = c->lz4_opts.index_form; return CRYO_OK;
     case CRYO_OPT_PIPE_MIN_BYTES: *value = (int64_t)c->pipe_min_bytes; return CRYO_OK;
     case CRYO_OPT_POOL_BYTES: *value = (int64_t)c->pool_bytes; return CRYO_OK;
     case CRYO_OPT_ZSTD_DECODE_PATH: *value = c->zstd_path; return CRYO_OK;
@@ -783,7 +789,7 @@ static int decompress_routed(cryo_codec *c, int method, const void *d_src, const
 {
     if (method == CRYO_METHOD_LZ4) {
         cryo::Lz4DecodeOpts opts = c->lz4_opts;
-        if (verification) opts.path = opts.walkers = opts.waves = 0;
+        if (verification) opts.path = opts.walkers = opts.waves = opts.index_form = 0;
         const size_t need = cryo::lz4_decompress_workspace(n_blocks, block_size, opts);
         if (need != 0) {
             int rc = ensure_ws(c, need);
@@ -923,7 +929,7 @@ static int decode_pass(cryo_codec *c, int method, uint32_t B, uint64_t n, const 
         budget = fr / 10u * 7u + c->ws_cap + *cap;
     }
     cryo::Lz4DecodeOpts auto_opts = c->lz4_opts;
-    auto_opts.path = auto_opts.walkers = auto_opts.waves = 0;
+    auto_opts.path = auto_opts.walkers = auto_opts.waves = auto_opts.index_form = 0;
     uint64_t K = n < (1ull << 24) ? n : (1ull << 24);
     size_t zstd_max = 0;
     for (;;) {
@@ -2517,6 +2523,30 @@ int cryo_codec_synth_batch(cryo_codec *c, uint64_t seed, uint64_t first_block, u
     if (!d_dst || dst_stride < block_size) return CRYO_E_ARG;
     HIP_TRY(c, cryo::launch_synth(c->stream, seed, first_block, block_step ? block_step : 1, n_blocks, block_size, dist,
                                   (uint8_t *)d_dst, dst_stride));
+    c->ctr.launches++;
+    return CRYO_OK;
+}
+
+uint32_t cryo_codec_lz4_index_cap(uint32_t block_size)
+{
+    if (block_size == 0 || block_size > kMaxBlockSize) return 0;
+    return cryo::lz4_index_layout(1, block_size, 1).cap;
+}
+
+int cryo_codec_lz4_index_rows(cryo_codec *c, const void *d_src, const uint64_t *d_src_off, const uint32_t *d_src_size,
+                              uint32_t block_size, uint64_t n_blocks, int form, uint16_t *d_entries, uint32_t *d_counts)
+{
+    DevGuard dev_(c);
+    if (!c || block_size == 0 || block_size > kMaxBlockSize || form < 0 || form > 2) return CRYO_E_ARG;
+    if (n_blocks == 0) return CRYO_OK;
+    if (!d_src || !d_src_off || !d_src_size || !d_entries || !d_counts) return CRYO_E_ARG;
+    const cryo::Lz4IndexLayout L = cryo::lz4_index_layout(n_blocks, block_size, 1);
+    int rc = ensure_ws(c, L.bytes);
+    if (rc != CRYO_OK) return rc;
+    HIP_TRY(c, cryo::launch_lz4_index_form(c->stream, (const uint8_t *)d_src, d_src_off, d_src_size, n_blocks, block_size, c->d_ws, L, form,
+                                           c->lz4_opts.cus));
+    HIP_TRY(c, hipMemcpyAsync(d_entries, c->d_ws, (size_t)n_blocks * L.cap * sizeof(uint16_t), hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, cryo::launch_lz4_index_counts(c->stream, c->d_ws, L, n_blocks, d_counts));
     c->ctr.launches++;
     return CRYO_OK;
 }

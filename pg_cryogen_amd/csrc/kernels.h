@@ -50,6 +50,7 @@ struct Lz4DecodeOpts {
     int path = 0;    /* 1: in-wave parse kernel, 2: sequence index + indexed decoder, 3: few blocks, every output byte in parallel (lz4_lat.hip) */
     int walkers = 0; /* walkers per block of the index pass (power of two, 1..64) */
     int waves = 0;   /* waves per block of the indexed decoder: 1 = k_lz4_dec_seq, 2 = k_lz4_dec_dual, 0 = by the batch size */
+    int index_form = 0; /* index pass of a one-walker plan: 1 = k_lz4_index, 2 = k_lz4_idx_pair (lz4_index_pair.hip), 0 = automatic */
     /* a low-priority side stream with its events (created by the handle, may be null): the last, partial round of a batch
      * that fills the chip once or a few times is decoded there with two waves per block (lz4_dec2.hip, launch_dec_seq) */
     hipStream_t side = nullptr;
@@ -75,6 +76,21 @@ struct Lz4IndexLayout {
 Lz4IndexLayout lz4_index_layout(uint64_t n_blocks, uint32_t block_size, uint32_t walkers);
 hipError_t launch_lz4_index(hipStream_t s, const uint8_t *d_src, const uint64_t *d_src_off, const uint32_t *d_src_size,
                             uint64_t n_blocks, uint32_t block_size, void *d_workspace, const Lz4IndexLayout &L);
+/* lz4_index_pair.hip: the same rows and descriptors for L.logS == 0, by pairs of waves (a walker and a feeder on the same rings) */
+hipError_t launch_lz4_index_pair(hipStream_t s, const uint8_t *d_src, const uint64_t *d_src_off, const uint32_t *d_src_size,
+                                 uint64_t n_blocks, uint32_t block_size, void *d_workspace, const Lz4IndexLayout &L);
+/* which of the two a one-walker plan takes: `form` as CRYO_OPT_LZ4_INDEX_FORM.  Automatic is the pair for batches that are
+ * resident at once (one wave of 64 walkers per SIMD: 256 blocks per compute unit); a batch of several rounds loses with it
+ * (131 072 x 128 KiB: 15.6 -> 16.3 ms, profiles/lz4_index_pair.txt) and keeps k_lz4_index */
+inline bool lz4_index_use_pair(const Lz4IndexLayout &L, int form, uint64_t n_blocks, int cus)
+{
+    if (L.logS != 0u || form == 1) return false;
+    return form == 2 || n_blocks <= (uint64_t)(cus > 0 ? cus : 256) * 256u;
+}
+hipError_t launch_lz4_index_form(hipStream_t s, const uint8_t *d_src, const uint64_t *d_src_off, const uint32_t *d_src_size,
+                                 uint64_t n_blocks, uint32_t block_size, void *d_workspace, const Lz4IndexLayout &L, int form, int cus);
+/* test support (cryo_codec_lz4_index_rows): the counts of a one-walker index, out of its descriptors */
+hipError_t launch_lz4_index_counts(hipStream_t s, const void *d_workspace, const Lz4IndexLayout &L, uint64_t n_blocks, uint32_t *d_counts);
 /* few blocks per call: a workgroup of up to 1 024 walkers per block, direct loads (lz4_index.hip, k_lz4_index_few) */
 Lz4IndexLayout lz4_index_layout_few(uint64_t n_blocks, uint32_t block_size);
 const uint32_t *lz4_index_few_failed(const void *d_workspace, const Lz4IndexLayout &L, uint64_t n_blocks); /* one word per block: 1 = no index */

@@ -796,7 +796,10 @@ hipError_t launch_lz4_decompress_indexed(hipStream_t s, const uint8_t *d_src, co
     if (grid > 0x7fffffffull || !d_workspace) return hipErrorInvalidValue;
     const Lz4IndexLayout Lx = lz4_index_layout(n_blocks, block_size, walkers);
     if (workspace_bytes < Lx.bytes) return hipErrorInvalidValue;
-    if (hipError_t e = launch_lz4_index(s, d_src, d_src_off, d_src_size, n_blocks, block_size, d_workspace, Lx); e != hipSuccess) return e;
+    if (hipError_t e = launch_lz4_index_form(s, d_src, d_src_off, d_src_size, n_blocks, block_size, d_workspace, Lx, opts ? opts->index_form : 0,
+                                             opts ? opts->cus : 0);
+        e != hipSuccess)
+        return e;
     const dim3 g((uint32_t)grid), b(64 * kDecWpb);
 #ifdef CRYO_DEBUG
     /* phase timing and ablation of the decoder (profiles/scripts): a debug build only -- an ablated run decodes wrong bytes */
