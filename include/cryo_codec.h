@@ -365,6 +365,99 @@ int cryo_codec_fetch_batch(cryo_codec *c, int method, const void *d_src, const u
                            const uint64_t *d_req_first, const uint16_t *d_pos, uint64_t n_req,
                            void *d_dst, uint64_t dst_cap, cryo_fetch_result *d_result, uint64_t *d_total);
 
+/* ---- filtering a scan: stored streams -> decoded in handle workspace -> a column test per tuple -> only the matches come back ----
+ * The read route a sequential scan with a range predicate takes (WHERE ts >= a AND ts < b, WHERE id = x): the reference accepts
+ * scan keys in cryo_beginscan and ignores them (pg_cryogen.c:185-211), so every decoded byte crosses PCIe and the executor throws
+ * most of them away.  Here the test runs where the decoded block lies (pg_cryogen_amd/host/filter.h walks a relation with it).
+ * A call names n_blocks stored streams as cryo_codec_check_batch does and one descriptor: the relation's columns as far as the
+ * keys need them (pg_attribute.attlen, and attalign as 1 / 2 / 4 / 8 bytes) and up to four scan keys, which are ANDed.
+ *
+ * Descriptor.  CRYO_E_ARG when: natts is 0 or above 1600 (MaxHeapAttributeNumber), or nkeys above 4 (nkeys == 0 is allowed:
+ * every well-formed tuple matches); a key's att outside 1 .. natts; an attlen of 0, below -1 (cstring is not supported) or above
+ * 32767; an attalign other than 1, 2, 4, 8; a varlena column (attlen == -1) with attalign < 4; a comparison key (CRYO_OP_LT ..
+ * CRYO_OP_NE) with an unknown type, on a column whose attlen is not the type's size or whose attalign is below its attlen, or with
+ * a value outside the type's range; an unknown op; a reserved field that is not zero; an unknown bit in flags.  For
+ * CRYO_OP_ISNULL and CRYO_OP_NOTNULL, type and value are ignored.  Key values are signed and compared as such; tuples are
+ * little-endian.
+ *
+ * Per block (names as in the check's rules above: lower, upper, n, off_i, len_i, MAXALIGN, B), the first failing rule wins:
+ *   CRYO_FETCH_STREAM (1), CRYO_FETCH_HEADER (2)   exactly the fetch's; no item is examined, the block has no record
+ *   otherwise every item 1 .. n is examined:
+ *     CRYO_FETCH_ITEM (3)    the item fails the fetch's ITEM rule (len == 0, off % 8 != 0, off < upper, off + MAXALIGN(len) > B)
+ *     CRYO_FILTER_TUPLE (8)  the tuple fails a tuple rule below
+ *     the items that pass both and pass every key are the block's matches; the rest is silently no match
+ *   CRYO_FETCH_OVERLAP (7)   the MAXALIGNed lengths of the matches sum to more than B - upper: the block delivers no tuple and no
+ *                            match record (n_match = 0); its bad items keep their records
+ *
+ * Per tuple of len bytes at t (PostgreSQL's access/htup_details.h: HeapTupleHeaderData, HEAP_NATTS_MASK, HEAP_HASNULL, att_isnull;
+ * access/tupmacs.h: att_align_nominal, att_align_pointer, att_addlength_pointer; postgres.h / varatt.h: VARATT_IS_1B, VARATT_IS_1B_E,
+ * VARSIZE_1B, VARSIZE_4B, VARTAG_SIZE(VARTAG_ONDISK); the walk is heap_deform_tuple's, common/heaptuple.c -- restated for a
+ * little-endian machine):
+ *   t_infomask2 = u16 at t + 18, tnatts = t_infomask2 & 0x07FF;  t_infomask = u16 at t + 20, HASNULL = t_infomask & 1;
+ *   t_hoff = the byte at t + 22;  the null bitmap starts at t + 23, bit i - 1 (byte (i - 1) / 8, bit (i - 1) % 8) SET means column
+ *   i is NOT null.
+ *   TUPLE rule, checked before anything else of the tuple is read: len >= 23, hoff % 8 == 0,
+ *   hoff >= MAXALIGN(23 + (HASNULL ? (tnatts + 7) / 8 : 0)), hoff <= len.
+ *   A column i > tnatts is NULL (missing-attribute defaults are not known here: the binder must not push down a key on a column
+ *   with atthasmissing).  With HASNULL, a column whose bitmap bit is clear is NULL.  A NULL column takes no room.
+ *   The walk keeps an offset o from t + hoff, starting at 0, over the columns i = 1 .. the highest key column -- that far for
+ *   every tuple, whatever the keys on the way said, and not a column further:
+ *     fixed width   o = align(o, attalign); the column is the attlen bytes at o
+ *     varlena       if the byte at o is 0: o = align(o, attalign).  With b the byte at o:
+ *                   b == 0x01         an external pointer: the byte at o + 1 is its tag; tag 18 (on-disk TOAST): 18 bytes; any
+ *                                     other tag: TUPLE
+ *                   b & 1             a 1-byte header: b >> 1 bytes, header included
+ *                   otherwise         a 4-byte header: (u32 at o) >> 2 bytes, header included; below 4: TUPLE
+ *     then o += the column's size
+ *   Every byte a column covers, its header (and an external pointer's tag) included, must lie below len: TUPLE otherwise.
+ *   Nothing outside [t, t + len) is ever loaded, whatever the tuple says.
+ *   Keys: a comparison on a NULL column is false; ISNULL and NOTNULL are what they say; the column's value is the signed
+ *   little-endian integer of the key's type at o.
+ *
+ * Results.  One cryo_filter_block per block, in call order.  One cryo_filter_rec per match {pos, 0, len} and one per bad item
+ * {pos, CRYO_FETCH_ITEM or CRYO_FILTER_TUPLE, 0} -- a damaged tuple is never silently absent from a scan --, in position order
+ * within the block; the block's records are records rec_first .. rec_first + n_match + n_bad - 1 of the call.  Its tuples lie
+ * packed from byte `off` of the destination on: each its len bytes, then zeros up to MAXALIGN(len) whatever the block holds in its
+ * pad (as the fetch writes them); a tuple's offset is `off` plus the MAXALIGNed lengths of the block's matches before it.  Blocks
+ * are placed in call order: rec_first and off of a block are the sums over the blocks before it (a STREAM, HEADER or OVERLAP block
+ * carries the values at which the next block starts).  n_items = n (0 under STREAM and HEADER).  total[0] = the packed bytes,
+ * total[1] = the records of the whole call, counted in full even where the caps cut the writing off; nothing at or beyond
+ * either total, and nothing beyond dst_cap bytes or rec_cap records, is written: a tuple that would end beyond dst_cap and a
+ * record at or beyond rec_cap are left out.  Because of the OVERLAP rule dst_cap >= n_blocks * B and rec_cap >= n_blocks * 290
+ * always suffice.
+ * CRYO_FILTER_COUNT_ONLY: the per-block table only -- status, n_items, n_match, n_bad; rec_first, off and both totals are 0; no
+ * record, no tuple is written; OVERLAP is not applied, because nothing is placed. */
+typedef struct { int16_t attlen; uint8_t attalign; uint8_t rsv; } cryo_att; /* pg_attribute.attlen; attalign as 1/2/4/8; 4 bytes */
+typedef enum { CRYO_KEY_INT2 = 1, CRYO_KEY_INT4 = 2, CRYO_KEY_INT8 = 3 } cryo_key_type; /* signed, little-endian */
+typedef enum {
+    CRYO_OP_LT = 1, CRYO_OP_LE, CRYO_OP_EQ, CRYO_OP_GE, CRYO_OP_GT, CRYO_OP_NE, CRYO_OP_ISNULL, CRYO_OP_NOTNULL
+} cryo_key_op;
+typedef struct { uint16_t att; uint8_t type, op; uint32_t rsv; int64_t value; } cryo_scan_key; /* att 1-based; 16 bytes */
+typedef struct {
+    uint32_t natts, nkeys, flags, rsv;
+    const cryo_att *atts;      /* natts entries */
+    const cryo_scan_key *keys; /* nkeys entries (may be null when nkeys == 0) */
+} cryo_filter;
+#define CRYO_FILTER_COUNT_ONLY 1u /* per-block table only: no records, no tuples */
+#define CRYO_FILTER_TUPLE 8u      /* a record's status beside CRYO_FETCH_ITEM: the tuple breaks a tuple rule */
+#define CRYO_FILTER_MAX_ATTS 1600u
+#define CRYO_FILTER_MAX_KEYS 4u
+typedef struct { uint32_t status, n_items, n_match, n_bad; uint64_t rec_first, off; } cryo_filter_block; /* 32 bytes, one per block */
+typedef struct { uint16_t pos, status; uint32_t len; } cryo_filter_rec;                                   /* 8 bytes */
+/* Device buffers.  The struct *f itself is host memory; f->atts and f->keys are DEVICE arrays (4-byte / 8-byte aligned).  The
+ * host validates the descriptor before anything is queued: it reads the two arrays back on the handle's stream (one wait for
+ * what the stream held before the call, at most 6400 + 64 bytes); from there on the call is asynchronous.  d_dst 8-byte, d_rec
+ * 8-byte, d_blocks 16-byte, d_total 8-byte aligned (CRYO_E_ARG otherwise); d_total has two entries and is also where the two
+ * running totals live between the call's internal chunks.  Decode as in the fetch: the automatic routes, handle workspace,
+ * chunks within CRYO_OPT_WORKSPACE_MAX_BYTES (the workspace also holds 16 bytes per possible item of a chunk); the device pool
+ * is neither read nor filled, nothing counts in cryo_codec_counters.  CRYO_E_ARG as for cryo_codec_fetch_batch (the same
+ * block-size rule), a bad descriptor, a null d_blocks, and -- without CRYO_FILTER_COUNT_ONLY -- a null d_dst with dst_cap > 0 or a
+ * null d_rec with rec_cap > 0; n_blocks == 0: CRYO_OK, totals 0. */
+int cryo_codec_filter_batch(cryo_codec *c, int method, const void *d_src, const uint64_t *d_src_off,
+                            const uint32_t *d_src_size, uint32_t block_size, uint64_t n_blocks, const cryo_filter *f,
+                            void *d_dst, uint64_t dst_cap, cryo_filter_rec *d_rec, uint64_t rec_cap,
+                            cryo_filter_block *d_blocks, uint64_t *d_total);
+
 /* ---- single block, HOST buffers: what cryo_compress()/cryo_decompress()
  *      (compression.c:125-159) call.  Synchronous: H2D, kernel, D2H. ---- */
 int cryo_codec_compress_block(cryo_codec *c, int method, int param,
@@ -433,6 +526,24 @@ int cryo_codec_recode_blocks(cryo_codec *c, int src_method, const void *const *h
 int cryo_codec_fetch_blocks(cryo_codec *c, int method, const void *const *h_src, const uint32_t *h_src_size,
                             size_t n_blocks, size_t block_size, const uint64_t *h_req_first, const uint16_t *h_pos,
                             void *h_dst, size_t dst_cap, cryo_fetch_result *h_result, uint64_t *h_total);
+
+/* cryo_codec_filter_batch on host buffers (stream i: h_src[i], h_src_size[i] bytes; f->atts and f->keys are HOST arrays),
+ * synchronous.  Only compressed bytes and the descriptor travel towards the device, only the block table, records and matching
+ * tuples come back.
+ *   Upload   the streams staged and uploaded as by cryo_codec_fetch_blocks, then the descriptor in a second copy: h2d_bytes grows
+ *            by another align16(4 * natts) + 16 * nkeys.
+ *   Return   per internal chunk the chunk's rows of the block table come back first, then exactly the chunk's records, then
+ *            exactly its packed bytes straight into h_dst (the host takes the record count from the table and the byte count from
+ *            the table and the last block's records: up to three waits per chunk): d2h_bytes grows by exactly
+ *            32 * n_blocks + 8 * h_total[1] + h_total[0]; with CRYO_FILTER_COUNT_ONLY by 32 * n_blocks.
+ *   Errors   packed bytes above dst_cap or records above rec_cap: CRYO_E_DSTSIZE; the call stops at the chunk that does not fit
+ *            and the outputs hold nothing to rely on (dst_cap >= n_blocks * block_size and rec_cap >= n_blocks * 290 always
+ *            fit).  CRYO_E_ARG as cryo_codec_filter_batch; a bad descriptor is refused before a device is touched.
+ * h_total has two entries.  Returns CRYO_OK when the batch ran, whatever the table says. */
+int cryo_codec_filter_blocks(cryo_codec *c, int method, const void *const *h_src, const uint32_t *h_src_size,
+                             size_t n_blocks, size_t block_size, const cryo_filter *f,
+                             void *h_dst, size_t dst_cap, cryo_filter_rec *h_rec, size_t rec_cap,
+                             cryo_filter_block *h_blocks, uint64_t *h_total);
 
 /* ---- device-resident block pool ("optional device-resident compressed/decompressed pool so
  *      repeated scans skip PCIe"; the reference's cache is host-only: cache.c:17-50).
@@ -515,6 +626,18 @@ int cryo_multi_recode_blocks(cryo_multi *m, int src_method, const void *const *h
 int cryo_multi_fetch_blocks(cryo_multi *m, int method, const void *const *h_src, const uint32_t *h_src_size,
                             size_t n_blocks, size_t block_size, const uint64_t *h_req_first, const uint16_t *h_pos,
                             void *h_dst, size_t dst_cap, cryo_fetch_result *h_result, uint64_t *h_total);
+
+/* cryo_codec_filter_blocks across the devices: block i -> handle i mod G.  Handle g, whose share is the blocks g, g + G, ..., has
+ * one tuple region of block_size * share bytes and one record region of 290 * share records, the regions laid out in handle order
+ * from h_dst and h_rec on (a region that reaches beyond its cap is cut there, so dst_cap >= n_blocks * block_size and rec_cap >=
+ * n_blocks * 290 always suffice).  The block table comes back in call order and finds everything: `off` counts from h_dst and
+ * rec_first from h_rec, but with more than one handle they are running sums only within one handle's blocks (from its regions'
+ * starts).  h_total[0] / h_total[1]: the end of the last byte / record used (0: none); with CRYO_FILTER_COUNT_ONLY both are 0.
+ * One handle: exactly cryo_codec_filter_blocks. */
+int cryo_multi_filter_blocks(cryo_multi *m, int method, const void *const *h_src, const uint32_t *h_src_size,
+                             size_t n_blocks, size_t block_size, const cryo_filter *f,
+                             void *h_dst, size_t dst_cap, cryo_filter_rec *h_rec, size_t rec_cap,
+                             cryo_filter_block *h_blocks, uint64_t *h_total);
 
 /* ---- batch helpers used by staging, tests and the benchmark ---- */
 

@@ -38,6 +38,17 @@ CHECK_NONE = 0xFFFFFFFF  # offset of CHECK_OK and CHECK_STREAM
 FETCH_OK, FETCH_STREAM, FETCH_HEADER, FETCH_ITEM, FETCH_NOITEM, FETCH_BADREQ, FETCH_OVERLAP = 0, 1, 2, 3, 5, 6, 7
 # cryo_fetch_result, 16 bytes per request
 FETCH_RESULT = np.dtype([("status", "<u4"), ("len", "<u4"), ("off", "<u8")])
+# the scan filter (include/cryo_codec.h): a record's statuses are 0, FETCH_ITEM and FILTER_TUPLE, a block's 0, FETCH_STREAM,
+# FETCH_HEADER and FETCH_OVERLAP
+FILTER_TUPLE = 8
+FILTER_COUNT_ONLY = 1
+KEY_INT2, KEY_INT4, KEY_INT8 = 1, 2, 3
+OP_LT, OP_LE, OP_EQ, OP_GE, OP_GT, OP_NE, OP_ISNULL, OP_NOTNULL = range(1, 9)
+FILTER_ATT = np.dtype([("attlen", "<i2"), ("attalign", "u1"), ("rsv", "u1")])                                  # cryo_att
+FILTER_KEY = np.dtype([("att", "<u2"), ("type", "u1"), ("op", "u1"), ("rsv", "<u4"), ("value", "<i8")])        # cryo_scan_key
+FILTER_BLOCK = np.dtype([("status", "<u4"), ("n_items", "<u4"), ("n_match", "<u4"), ("n_bad", "<u4"),
+                         ("rec_first", "<u8"), ("off", "<u8")])                                                # cryo_filter_block
+FILTER_REC = np.dtype([("pos", "<u2"), ("status", "<u2"), ("len", "<u4")])                                     # cryo_filter_rec
 LZ4_PATH_AUTO, LZ4_PATH_RING, LZ4_PATH_INDEXED, LZ4_PATH_FEW_BLOCKS = 0, 1, 2, 3
 
 DIST_WIDE, DIST_NARROW, DIST_INT4, DIST_RANDOM, DIST_ZEROS = range(5)
@@ -65,6 +76,7 @@ ABI_SYMBOLS = [
     "cryo_codec_check_batch", "cryo_codec_check_blocks", "cryo_multi_check_blocks",
     "cryo_codec_recode_batch", "cryo_codec_recode_blocks", "cryo_multi_recode_blocks",
     "cryo_codec_fetch_batch", "cryo_codec_fetch_blocks", "cryo_multi_fetch_blocks",
+    "cryo_codec_filter_batch", "cryo_codec_filter_blocks", "cryo_multi_filter_blocks",
     "cryo_codec_lz4_index_cap", "cryo_codec_lz4_index_rows",
 ]
 
@@ -73,6 +85,12 @@ class CryoError(RuntimeError):
     def __init__(self, code, what="", detail=""):
         self.code = code
         super().__init__("%s failed: %s (%d) %s" % (what, _ERR_NAMES.get(code, "?"), code, detail))
+
+
+class CryoFilter(C.Structure):
+    """cryo_filter: atts / keys point to device arrays for filter_batch, to host arrays for filter_blocks"""
+    _fields_ = [("natts", C.c_uint32), ("nkeys", C.c_uint32), ("flags", C.c_uint32), ("rsv", C.c_uint32),
+                ("atts", C.c_void_p), ("keys", C.c_void_p)]
 
 
 class TransferCounters(C.Structure):
@@ -159,6 +177,10 @@ def lib():
     L.cryo_codec_fetch_batch.argtypes = [vp, i32, vp, vp, vp, u32, u64, vp, vp, u64, vp, u64, vp, vp]
     L.cryo_codec_fetch_blocks.argtypes = [vp, i32, vp, vp, sz, sz, vp, vp, vp, sz, vp, C.POINTER(u64)]
     L.cryo_multi_fetch_blocks.argtypes = [vp, i32, vp, vp, sz, sz, vp, vp, vp, sz, vp, C.POINTER(u64)]
+    fp = C.POINTER(CryoFilter)
+    L.cryo_codec_filter_batch.argtypes = [vp, i32, vp, vp, vp, u32, u64, fp, vp, u64, vp, u64, vp, vp]
+    L.cryo_codec_filter_blocks.argtypes = [vp, i32, vp, vp, sz, sz, fp, vp, sz, vp, sz, vp, vp]
+    L.cryo_multi_filter_blocks.argtypes = [vp, i32, vp, vp, sz, sz, fp, vp, sz, vp, sz, vp, vp]
     L.cryo_codec_lz4_index_cap.argtypes = [u32]
     L.cryo_codec_lz4_index_cap.restype = u32
     L.cryo_codec_lz4_index_rows.argtypes = [vp, vp, vp, vp, u32, u64, i32, vp, vp]
@@ -225,6 +247,39 @@ def fetch_blocks_call(fn, handle, chk, method, comps, block_size, requests, dst=
     chk(fn(handle, method, src, szs, n, block_size, first.ctypes.data, pos.ctypes.data if n_req else None, dst.ctypes.data,
            dst.nbytes, res.ctypes.data, C.byref(total)), "fetch_blocks")
     return res[:n_req], dst, total.value
+
+
+def filter_desc(atts, keys=(), flags=0):
+    """the descriptor of a filter call as host arrays: atts a list of (attlen, attalign), keys a list of (att, type, op, value)
+    (att 1-based; type KEY_*, op OP_*).  Returns (CryoFilter, atts array, keys array); the struct points into the two arrays,
+    which the caller keeps alive"""
+    a = np.zeros(max(len(atts), 1), FILTER_ATT)
+    for i, (attlen, attalign) in enumerate(atts):
+        a[i] = (attlen, attalign, 0)
+    k = np.zeros(max(len(keys), 1), FILTER_KEY)
+    for i, (att, typ, op, value) in enumerate(keys):
+        k[i] = (att, typ, op, 0, value)
+    f = CryoFilter(len(atts), len(keys), flags, 0, a.ctypes.data, k.ctypes.data if len(keys) else None)
+    return f, a, k
+
+
+def filter_blocks_call(fn, handle, chk, method, comps, block_size, desc, dst=None, rec=None):
+    """cryo_codec_filter_blocks / cryo_multi_filter_blocks (fn) on a list of host streams with the descriptor filter_desc made;
+    returns (table: FILTER_BLOCK array in call order, records: the FILTER_REC buffer, dst, (total bytes, total records)).
+    dst / rec: the caller's buffers (their capacities are their lengths), else fresh ones of the worst-case size"""
+    n = len(comps)
+    arrs = [np.ascontiguousarray(np.asarray(c, dtype=np.uint8)) for c in comps]
+    src = (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.nbytes else None for a in arrs])
+    szs = (C.c_uint32 * max(n, 1))(*[a.nbytes for a in arrs])
+    if dst is None:
+        dst = np.zeros(max(n, 1) * block_size, np.uint8)
+    if rec is None:
+        rec = np.zeros(max(n, 1) * 290, FILTER_REC)
+    table = np.zeros(max(n, 1), FILTER_BLOCK)
+    total = (C.c_uint64 * 2)()
+    chk(fn(handle, method, src, szs, n, block_size, C.byref(desc[0]), dst.ctypes.data if dst.size else None, dst.nbytes,
+           rec.ctypes.data if rec.size else None, rec.size, table.ctypes.data, total), "filter_blocks")
+    return table[:n], rec, dst, (total[0], total[1])
 
 
 class DeviceBuffer:
@@ -421,6 +476,22 @@ class Codec:
         returns (records, dst, total): records a FETCH_RESULT array in call order, tuple r the records[r]["len"] bytes at
         dst[records[r]["off"]:] when its status is FETCH_OK"""
         return fetch_blocks_call(self.L.cryo_codec_fetch_blocks, self.h, self._chk, method, comps, block_size, requests, dst)
+
+    def filter_batch(self, method, d_src, d_off, d_sizes, block_size, n, natts, d_atts, nkeys, d_keys, flags, d_dst, dst_cap,
+                     d_rec, rec_cap, d_blocks, d_total):
+        """test the keys (d_keys: FILTER_KEY, d_atts: FILTER_ATT, device arrays) on every tuple of the n stored blocks: one
+        FILTER_BLOCK row per block in d_blocks, one FILTER_REC per match and per bad item in d_rec, the matches packed into
+        d_dst, the two totals {bytes, records} in d_total (2 x u64).  Asynchronous once the descriptor is read back."""
+        f = CryoFilter(natts, nkeys, flags, 0, d_atts.ptr if d_atts else None, d_keys.ptr if d_keys else None)
+        self._chk(self.L.cryo_codec_filter_batch(self.h, method, d_src.ptr, d_off.ptr, d_sizes.ptr, block_size, n, C.byref(f),
+                                                 d_dst.ptr if d_dst else None, dst_cap, d_rec.ptr if d_rec else None, rec_cap,
+                                                 d_blocks.ptr if d_blocks else None, d_total.ptr if d_total else None),
+                  "filter_batch")
+
+    def filter_blocks(self, method, comps, block_size, desc, dst=None, rec=None):
+        """filter host streams (desc: what filter_desc returns); returns (table, records, dst, (bytes, records)): block i's
+        records are records[table[i]["rec_first"]:][:n_match + n_bad], its tuples lie MAXALIGN-packed from dst[table[i]["off"]:]"""
+        return filter_blocks_call(self.L.cryo_codec_filter_blocks, self.h, self._chk, method, comps, block_size, desc, dst, rec)
 
     def last_verify_failure(self):
         """(block, first mismatch) that made the last host-buffer compress call fail verification, or None"""

@@ -1112,6 +1112,126 @@ static int fetch_pass(cryo_codec *c, int method, const uint8_t *d_src, const uin
     return rc;
 }
 
+/* ---- the scan filter ----
+ * The shared decode loop over the caller's stream table; on every decoded chunk filter.hip tests the keys on every tuple, places
+ * the blocks behind the two running totals (bytes, records) -- which stay in device memory from chunk to chunk -- and copies the
+ * matches and the records out.  Per chunk (own) each block has 16 bytes per possible item of side table, its two sums and bases
+ * and, for the host-buffer call, a row of the chunk's staging areas for packed bytes and for records; the pass's fixed bytes hold
+ * the host-buffer call's running totals.  Its decodes count nowhere. */
+namespace {
+struct FilterIo {
+    const void *d_atts = nullptr, *d_keys = nullptr; /* device */
+    uint32_t nkeys = 0, max_att = 0;
+    bool count_only = false;
+    cryo_filter_block *d_blocks = nullptr;           /* device: n rows */
+    uint64_t dst_cap = 0, rec_cap = 0;
+    /* device-resident call: the caller's buffers and totals */
+    uint8_t *d_dst = nullptr;
+    cryo_filter_rec *d_rec = nullptr;
+    uint64_t *d_total = nullptr;
+    /* host-buffer call: where table, records and bytes go, and how far they got */
+    bool host = false;
+    cryo_filter_block *h_blocks = nullptr;
+    cryo_filter_rec *h_rec = nullptr;
+    uint8_t *h_dst = nullptr;
+    uint64_t h_bytes = 0, h_recs = 0;
+};
+} // namespace
+
+/* the descriptor's rules (include/cryo_codec.h); atts and keys are host memory here.  *max_att: the highest key column */
+static bool filter_desc_ok(const cryo_filter *f, const cryo_att *atts, const cryo_scan_key *keys, uint32_t *max_att)
+{
+    *max_att = 0;
+    if (!f || f->natts == 0 || f->natts > CRYO_FILTER_MAX_ATTS || f->nkeys > CRYO_FILTER_MAX_KEYS || f->rsv != 0 ||
+        (f->flags & ~CRYO_FILTER_COUNT_ONLY) != 0 || !atts || (f->nkeys > 0 && !keys))
+        return false;
+    for (uint32_t i = 0; i < f->natts; i++) {
+        const cryo_att &a = atts[i];
+        if (a.rsv != 0 || a.attlen == 0 || a.attlen < -1) return false; /* an int16 is never above 32767 */
+        if (a.attalign != 1 && a.attalign != 2 && a.attalign != 4 && a.attalign != 8) return false;
+        if (a.attlen == -1 && a.attalign < 4) return false;
+    }
+    for (uint32_t k = 0; k < f->nkeys; k++) {
+        const cryo_scan_key &q = keys[k];
+        if (q.rsv != 0 || q.att == 0 || q.att > f->natts || q.op < CRYO_OP_LT || q.op > CRYO_OP_NOTNULL) return false;
+        if (q.att > *max_att) *max_att = q.att;
+        if (q.op == CRYO_OP_ISNULL || q.op == CRYO_OP_NOTNULL) continue;
+        if (q.type < CRYO_KEY_INT2 || q.type > CRYO_KEY_INT8) return false;
+        const int size = q.type == CRYO_KEY_INT2 ? 2 : q.type == CRYO_KEY_INT4 ? 4 : 8;
+        const cryo_att &a = atts[q.att - 1];
+        if (a.attlen != size || a.attalign < size) return false;
+        if (size == 2 && (q.value < INT16_MIN || q.value > INT16_MAX)) return false;
+        if (size == 4 && (q.value < INT32_MIN || q.value > INT32_MAX)) return false;
+    }
+    return true;
+}
+
+static int filter_pass(cryo_codec *c, int method, const uint8_t *d_src, const uint64_t *d_src_off, const uint32_t *d_src_size,
+                       uint32_t B, uint64_t n, FilterIo &io)
+{
+    static_assert(sizeof(cryo_filter_block) == 2 * sizeof(uint4) && sizeof(cryo_filter_rec) == sizeof(uint2) &&
+                      sizeof(cryo_att) == 4 && sizeof(cryo_scan_key) == 16,
+                  "the filter's records are the kernels'");
+    const bool host = io.host, stage = host && !io.count_only;
+    const cryo_codec_counters keep = c->ctr;
+    const uint64_t S = cryo::filter_side_stride(B);
+    const uint64_t row = ((uint64_t)B + 15u) & ~(uint64_t)15u; /* a block's share of the chunk's staging area for bytes */
+    DecodePass ps;
+    ps.d_comp = d_src; ps.d_comp_off = d_src_off; ps.d_comp_size = d_src_size;
+    ps.fixed = 256u;                                                /* the running totals of the host-buffer call */
+    ps.own_per_block = 16u * S + 48u + (stage ? row + 8u * S : 0u); /* side; 2 sums, 2 x (K + 1) bases (u64); staging rows */
+    ps.run = [&](const DecodeChunk &ch) -> int {
+        uint64_t *running = host ? (uint64_t *)ch.fixed : io.d_total;
+        uint4 *side = (uint4 *)ch.own;
+        uint64_t *sum = (uint64_t *)(ch.own + 16u * S * ch.K), *base = sum + 2u * ch.K;
+        uint8_t *st_dst = ch.own + (16u * S + 48u) * ch.K;
+        cryo_filter_rec *st_rec = (cryo_filter_rec *)(st_dst + row * ch.K);
+        if (ch.lo == 0) HIP_TRY(c, hipMemsetAsync(running, 0, 2 * sizeof(uint64_t), c->stream));
+        HIP_TRY(c, cryo::launch_filter(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.d_atts, io.d_keys, io.nkeys, io.max_att,
+                                       io.count_only, (uint4 *)(io.d_blocks + ch.lo), side, sum, base, running,
+                                       stage ? st_dst : io.d_dst, stage ? ch.K * row : io.dst_cap,
+                                       stage ? (uint2 *)st_rec : (uint2 *)io.d_rec, stage ? ch.K * S : io.rec_cap, host,
+                                       c->lz4_opts.cus));
+        if (!host) return CRYO_OK;
+        /* the chunk's rows of the table; then -- their number known from the rows -- its records; then -- their total known from
+         * the last row and the last block's records -- its bytes */
+        cryo_filter_block *rows = io.h_blocks + ch.lo;
+        HIP_TRY(c, hipMemcpyAsync(rows, io.d_blocks + ch.lo, ch.cnt * sizeof(cryo_filter_block), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        c->xfer_ctr.d2h_bytes += ch.cnt * sizeof(cryo_filter_block);
+        if (io.count_only) return CRYO_OK;
+        const cryo_filter_block &last = rows[ch.cnt - 1];
+        const uint64_t last_recs = (uint64_t)last.n_match + last.n_bad;
+        if (rows[0].rec_first != io.h_recs || rows[0].off != io.h_bytes || last.rec_first < io.h_recs || last.off < io.h_bytes ||
+            last_recs > S || last.rec_first + last_recs - io.h_recs > ch.K * S)
+            return CRYO_E_HIP; /* not a placement */
+        const uint64_t rec_end = last.rec_first + last_recs, nrec = rec_end - io.h_recs;
+        if (rec_end > io.rec_cap) return CRYO_E_DSTSIZE;
+        if (nrec) {
+            HIP_TRY(c, hipMemcpyAsync(io.h_rec + io.h_recs, st_rec, nrec * sizeof(cryo_filter_rec), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            c->xfer_ctr.d2h_bytes += nrec * sizeof(cryo_filter_rec);
+        }
+        uint64_t end = last.off;
+        for (uint64_t r = last.rec_first; r < rec_end; r++)
+            if (io.h_rec[r].status == 0) end += ((uint64_t)io.h_rec[r].len + 7u) & ~(uint64_t)7u;
+        if (end - io.h_bytes > ch.K * row) return CRYO_E_HIP; /* not a placement */
+        const uint64_t tot = end - io.h_bytes;
+        if (end > io.dst_cap) return CRYO_E_DSTSIZE;
+        if (tot) {
+            HIP_TRY(c, hipMemcpyAsync(io.h_dst + io.h_bytes, st_dst, tot, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            c->xfer_ctr.d2h_bytes += tot;
+        }
+        io.h_bytes = end;
+        io.h_recs = rec_end;
+        return CRYO_OK;
+    };
+    const int rc = decode_pass(c, method, B, n, ps);
+    c->ctr = keep;
+    return rc;
+}
+
 /* ---- recompression ----
  * The shared decode loop over the caller's stream table; every decoded chunk is encoded by cryo_codec_compress_batch -- the
  * path of every compress call, so the handle's encode options (segment mode, checksums, verification) apply as they are --
@@ -1273,6 +1393,41 @@ int cryo_codec_fetch_batch(cryo_codec *c, int method, const void *d_src, const u
         io.d_req_first = d_req_first; io.d_pos = d_pos; io.n_req = n_req; io.d_result = d_result;
         io.d_dst = (uint8_t *)d_dst; io.dst_cap = dst_cap; io.d_total = d_total;
         return fetch_pass(c, method, (const uint8_t *)d_src, d_src_off, d_src_size, block_size, n_blocks, io);
+    });
+}
+
+int cryo_codec_filter_batch(cryo_codec *c, int method, const void *d_src, const uint64_t *d_src_off, const uint32_t *d_src_size,
+                            uint32_t block_size, uint64_t n_blocks, const cryo_filter *f, void *d_dst, uint64_t dst_cap,
+                            cryo_filter_rec *d_rec, uint64_t rec_cap, cryo_filter_block *d_blocks, uint64_t *d_total)
+{
+    DevGuard dev_(c);
+    if (!c || !method_ok(method) || !check_block_size_ok(block_size)) return CRYO_E_ARG;
+    if (!d_total || ((uintptr_t)d_total & 7u) != 0) return CRYO_E_ARG;
+    if (!f || f->natts == 0 || f->natts > CRYO_FILTER_MAX_ATTS || f->nkeys > CRYO_FILTER_MAX_KEYS || !f->atts ||
+        (f->nkeys > 0 && !f->keys) || ((uintptr_t)f->atts & 3u) != 0 || ((uintptr_t)f->keys & 7u) != 0)
+        return CRYO_E_ARG;
+    const bool count_only = (f->flags & CRYO_FILTER_COUNT_ONLY) != 0;
+    if (n_blocks > 0) {
+        if (!d_src || !d_src_off || !d_src_size || !d_blocks || ((uintptr_t)d_blocks & 15u) != 0) return CRYO_E_ARG;
+        if (!count_only && ((!d_dst && dst_cap > 0) || (!d_rec && rec_cap > 0))) return CRYO_E_ARG;
+        if ((((uintptr_t)d_dst | (uintptr_t)d_rec) & 7u) != 0) return CRYO_E_ARG;
+    }
+    return guarded([&] {
+        /* the descriptor lives in device memory: read back and checked before anything is queued */
+        std::vector<cryo_att> atts(f->natts);
+        std::vector<cryo_scan_key> keys(f->nkeys ? f->nkeys : 1);
+        HIP_TRY(c, hipMemcpyAsync(atts.data(), f->atts, f->natts * sizeof(cryo_att), hipMemcpyDeviceToHost, c->stream));
+        if (f->nkeys)
+            HIP_TRY(c, hipMemcpyAsync(keys.data(), f->keys, f->nkeys * sizeof(cryo_scan_key), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        FilterIo io;
+        if (!filter_desc_ok(f, atts.data(), keys.data(), &io.max_att)) return (int)CRYO_E_ARG;
+        HIP_TRY(c, hipMemsetAsync(d_total, 0, 2 * sizeof(uint64_t), c->stream));
+        if (n_blocks == 0) return (int)CRYO_OK;
+        io.d_atts = f->atts; io.d_keys = f->keys; io.nkeys = f->nkeys; io.count_only = count_only;
+        io.d_blocks = d_blocks; io.dst_cap = count_only ? 0 : dst_cap; io.rec_cap = count_only ? 0 : rec_cap;
+        io.d_dst = (uint8_t *)d_dst; io.d_rec = d_rec; io.d_total = d_total;
+        return filter_pass(c, method, (const uint8_t *)d_src, d_src_off, d_src_size, block_size, n_blocks, io);
     });
 }
 
@@ -1910,6 +2065,77 @@ int cryo_codec_fetch_blocks(cryo_codec *c, int method, const void *const *h_src,
     });
 }
 
+/* what every host-buffer filter call checks before a device is touched */
+static int filter_blocks_args(int method, size_t block_size, const cryo_filter *f, uint64_t *h_total, uint32_t *max_att)
+{
+    if (!method_ok(method) || !check_block_size_ok(block_size) || !h_total) return CRYO_E_ARG;
+    if (!f || !filter_desc_ok(f, f->atts, f->keys, max_att)) return CRYO_E_ARG;
+    return CRYO_OK;
+}
+
+/* the scan filter of n streams given by pointer: the streams staged and uploaded as the fetch's (stage_streams), the descriptor
+ * from the same pinned buffer in a second copy, both into place before the first decode; table, records and tuples come back
+ * chunk by chunk (filter_pass).  b_base / r_base: what the table's `off` / rec_first count from (a multi-GPU share's regions
+ * within the caller's buffers); h_total is relative to h_dst / h_rec as given here */
+static int filter_blocks_impl(cryo_codec *c, int method, const void *const *h_src, const uint32_t *h_src_size, size_t n,
+                              size_t block_size, const cryo_filter *f, void *h_dst, size_t dst_cap, uint64_t b_base,
+                              cryo_filter_rec *h_rec, size_t rec_cap, uint64_t r_base, cryo_filter_block *h_blocks, uint64_t *h_total)
+{
+    uint32_t max_att = 0;
+    int rc = filter_blocks_args(method, block_size, f, h_total, &max_att);
+    if (rc != CRYO_OK || !c) return CRYO_E_ARG;
+    DevGuard dev_(c);
+    h_total[0] = h_total[1] = 0;
+    if (n == 0) return CRYO_OK;
+    const bool count_only = (f->flags & CRYO_FILTER_COUNT_ONLY) != 0;
+    if (!h_src || !h_src_size || !h_blocks) return CRYO_E_ARG;
+    if (!count_only && ((!h_dst && dst_cap > 0) || (!h_rec && rec_cap > 0))) return CRYO_E_ARG;
+    ScopedLocalCpus numa_(n * block_size >= ((size_t)8 << 20) ? c : nullptr);
+    /* the descriptor and the table: [atts 4 x natts][keys 16 x nkeys][rows 32 x n], each part 16-byte aligned */
+    const size_t t_atts = 0, t_keys = ((size_t)f->natts * 4 + 15) & ~(size_t)15, t_rows = t_keys + (size_t)f->nkeys * 16;
+    size_t streams = (n * 12 + 63) & ~(size_t)63; /* what stage_streams lays out in the pinned buffer */
+    for (size_t i = 0; i < n; i++) streams += ((size_t)h_src_size[i] + 15) & ~(size_t)15;
+    const size_t p_tbl = (streams + 64 + 15) & ~(size_t)15;
+    /* every allocation of the call before the uploads are queued; the pinned buffer at its final size, so that the staging of
+     * the streams leaves it where it is */
+    if ((rc = ensure_pinned(c, p_tbl + t_rows)) != CRYO_OK) return rc;
+    if ((rc = ensure(c, &c->hb_meta, &c->hb_meta_cap, t_rows + n * sizeof(cryo_filter_block) + 64)) != CRYO_OK) return rc;
+    StagedStreams sg;
+    if ((rc = stage_streams(c, h_src, h_src_size, n, sg, true)) != CRYO_OK) return rc;
+    uint8_t *pin = (uint8_t *)c->pin + p_tbl;
+    memset(pin, 0, t_rows);
+    memcpy(pin + t_atts, f->atts, (size_t)f->natts * 4);
+    if (f->nkeys) memcpy(pin + t_keys, f->keys, (size_t)f->nkeys * 16);
+    HIP_TRY(c, hipMemcpyAsync(c->hb_meta, pin, t_rows, hipMemcpyHostToDevice, c->stream));
+    c->xfer_ctr.h2d_bytes += t_rows;
+    FilterIo io;
+    io.d_atts = c->hb_meta + t_atts; io.d_keys = c->hb_meta + t_keys; io.nkeys = f->nkeys; io.max_att = max_att;
+    io.count_only = count_only; io.d_blocks = (cryo_filter_block *)(c->hb_meta + t_rows);
+    io.dst_cap = count_only ? 0 : dst_cap; io.rec_cap = count_only ? 0 : rec_cap;
+    io.host = true; io.h_blocks = h_blocks; io.h_rec = h_rec; io.h_dst = (uint8_t *)h_dst;
+    rc = filter_pass(c, method, c->hb_src, (const uint64_t *)(c->hb_src + sg.o_off), (const uint32_t *)(c->hb_src + sg.o_sz),
+                     (uint32_t)block_size, n, io);
+    (void)hipStreamSynchronize(c->stream); /* nothing in flight from the pinned buffer or into the caller's memory */
+    if (rc != CRYO_OK) return rc;
+    if (!count_only && (b_base || r_base))
+        for (size_t i = 0; i < n; i++) { h_blocks[i].off += b_base; h_blocks[i].rec_first += r_base; }
+    h_total[0] = io.h_bytes;
+    h_total[1] = io.h_recs;
+    return CRYO_OK;
+}
+
+int cryo_codec_filter_blocks(cryo_codec *c, int method, const void *const *h_src, const uint32_t *h_src_size, size_t n,
+                             size_t block_size, const cryo_filter *f, void *h_dst, size_t dst_cap, cryo_filter_rec *h_rec,
+                             size_t rec_cap, cryo_filter_block *h_blocks, uint64_t *h_total)
+{
+    return guarded([&] {
+        const int rc = filter_blocks_impl(c, method, h_src, h_src_size, n, block_size, f, h_dst, dst_cap, 0, h_rec, rec_cap, 0,
+                                          h_blocks, h_total);
+        if (c) ws_trim_after_call(c);
+        return rc;
+    });
+}
+
 } /* extern "C" */
 
 /* ---- device-resident block pool ---- */
@@ -2417,6 +2643,57 @@ int cryo_multi_fetch_blocks(cryo_multi *m, int method, const void *const *h_src,
     if (rc != CRYO_OK) return rc;
     for (size_t g = 0; g < G; g++)
         if (end[g] > *h_total) *h_total = end[g];
+    return CRYO_OK;
+}
+
+/* block i -> handle i mod G; handle g packs its share, in block order, into a tuple region of block_size * (its blocks) bytes and
+ * a record region of 290 * (its blocks) records, the regions in handle order; the table comes back in call order with `off` and
+ * rec_first counting from h_dst and h_rec */
+int cryo_multi_filter_blocks(cryo_multi *m, int method, const void *const *h_src, const uint32_t *h_src_size, size_t n,
+                             size_t block_size, const cryo_filter *f, void *h_dst, size_t dst_cap, cryo_filter_rec *h_rec,
+                             size_t rec_cap, cryo_filter_block *h_blocks, uint64_t *h_total)
+{
+    uint32_t max_att = 0;
+    if (!m || m->h.empty() || filter_blocks_args(method, block_size, f, h_total, &max_att) != CRYO_OK) return CRYO_E_ARG;
+    const size_t G = m->h.size();
+    if (G == 1)
+        return cryo_codec_filter_blocks(m->h[0], method, h_src, h_src_size, n, block_size, f, h_dst, dst_cap, h_rec, rec_cap,
+                                        h_blocks, h_total);
+    h_total[0] = h_total[1] = 0;
+    if (n == 0) return CRYO_OK;
+    const bool count_only = (f->flags & CRYO_FILTER_COUNT_ONLY) != 0;
+    if (!h_src || !h_src_size || !h_blocks) return CRYO_E_ARG;
+    if (!count_only && ((!h_dst && dst_cap > 0) || (!h_rec && rec_cap > 0))) return CRYO_E_ARG;
+    std::vector<uint64_t> end_b(G, 0), end_r(G, 0);
+    const int rc = guarded([&] {
+        return multi_run(m, n, [&](size_t g, const std::vector<size_t> &idx) {
+            /* handles before g hold blocks g' < g of every round of G: (n - g' + G - 1) / G each */
+            uint64_t before = 0;
+            for (size_t q = 0; q < g && q < n; q++) before += (uint64_t)((n - q + G - 1) / G);
+            const uint64_t b0 = before * block_size, r0 = before * 290u;
+            const uint64_t want_b = (uint64_t)idx.size() * block_size, want_r = (uint64_t)idx.size() * 290u;
+            const uint64_t cap_b = dst_cap > b0 ? (dst_cap - b0 < want_b ? dst_cap - b0 : want_b) : 0;
+            const uint64_t cap_r = rec_cap > r0 ? (rec_cap - r0 < want_r ? rec_cap - r0 : want_r) : 0;
+            std::vector<const void *> src(idx.size());
+            std::vector<uint32_t> sz(idx.size());
+            std::vector<cryo_filter_block> rows(idx.size());
+            for (size_t k = 0; k < idx.size(); k++) { src[k] = h_src[idx[k]]; sz[k] = h_src_size[idx[k]]; }
+            uint64_t tot[2] = {0, 0};
+            const int r = filter_blocks_impl(m->h[g], method, src.data(), sz.data(), idx.size(), block_size, f,
+                                             cap_b ? (uint8_t *)h_dst + b0 : nullptr, cap_b, b0, cap_r ? h_rec + r0 : nullptr, cap_r,
+                                             r0, rows.data(), tot);
+            if (r != CRYO_OK) return r;
+            for (size_t k = 0; k < idx.size(); k++) h_blocks[idx[k]] = rows[k];
+            end_b[g] = tot[0] ? b0 + tot[0] : 0;
+            end_r[g] = tot[1] ? r0 + tot[1] : 0;
+            return (int)CRYO_OK;
+        });
+    });
+    if (rc != CRYO_OK) return rc;
+    for (size_t g = 0; g < G; g++) {
+        if (end_b[g] > h_total[0]) h_total[0] = end_b[g];
+        if (end_r[g] > h_total[1]) h_total[1] = end_r[g];
+    }
     return CRYO_OK;
 }
 

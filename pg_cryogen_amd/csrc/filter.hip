@@ -1,0 +1,371 @@
+/*
+ * filter.hip -- the device side of the scan filter (cryo_codec_filter_batch / _blocks, include/cryo_codec.h: the rules).
+ *
+ * The host (cryo_codec.cpp, filter_pass) decodes a chunk of stored streams into handle workspace with the shared decode loop
+ * (decode_pass); these kernels look into every heap tuple of the decoded chunk, test up to four scan keys on it and pack the
+ * tuples that pass, so that only matches leave the device:
+ *   k_filter_match    one wave per block, four blocks per workgroup, as k_fetch_items.  A block the decoders rejected gets STREAM
+ *                     without a load, a bad header HEADER.  Otherwise a lane takes one item per turn (290 items: five turns):
+ *                     the fetch's ITEM rule, the TUPLE rule on the tuple's header, then the walk over the columns 1 .. the
+ *                     highest key column.  That loop is the same trip for all 64 lanes -- the column descriptor and the keys
+ *                     are read at addresses that depend on the loop counter only, so they are uniform loads; what differs per
+ *                     lane is the offset, the null bit and the varlena branch.  Keys are evaluated as the walk passes their
+ *                     column.  A key's value is loaded at its proven alignment (tuples start at multiples of 8, hoff is one,
+ *                     attalign >= attlen is the argument rule); everything else of a tuple is read bytewise or, the three header
+ *                     fields, at their fixed even offsets.  No load leaves [t, t + len): every read is preceded by its bound.
+ *                     OVERLAP is a verdict on the block that is known only after the last turn, so -- as in the fetch -- a first
+ *                     sweep sums and a second one writes (items and tuples come from L2 then): per record {offset inside the
+ *                     block's output, the tuple's place in the decoded block, len, pos | status << 16} into a side table in
+ *                     position order, the first half of the block's row of the table, and the block's two sums.
+ *   k_filter_offsets  one workgroup per chunk: the scan of k_fetch_offsets over two arrays at once (bytes, records), from the two
+ *                     running totals the chunk before left in device memory; it also writes {rec_first, off} of every row.
+ *   k_filter_copy     walks the PACKED side as k_fetch_copy does (2 KiB pieces, a binary search for the block, one for the
+ *                     record in the block's side table; bad items share their offset with the next tuple, so "the last entry at
+ *                     or below the byte" is the match that owns it), then the same grid strides over the blocks and writes the
+ *                     8-byte records to their final places.
+ * The fetch's kernels are not reused: k_fetch_offsets scans one array and its copy finds requests through the caller's CSR table,
+ * which a filter does not have.  Every device write is a vector store in plain C++.  No LDS beyond the scan's eight words, no
+ * scratch.
+ */
+#include "kernels.h"
+
+namespace cryo {
+
+constexpr uint32_t kFilterStream = 1, kFilterHeader = 2, kFilterItem = 3, kFilterOverlap = 7, kFilterTuple = 8; /* statuses */
+constexpr uint32_t kFilterNoMatch = 0xFFFFu;  /* inside k_filter_match only: a good tuple that fails a key */
+constexpr uint32_t kFilterPiece = 256u * 8u;  /* packed bytes one workgroup copies per turn */
+constexpr uint32_t kOpLt = 1, kOpLe = 2, kOpEq = 3, kOpGe = 4, kOpGt = 5, kOpNe = 6, kOpIsNull = 7, kOpNotNull = 8;
+
+struct FilterAtt { int16_t attlen; uint8_t attalign, rsv; };                           /* cryo_att */
+struct FilterKey { uint16_t att; uint8_t type, op; uint32_t rsv; int64_t value; };    /* cryo_scan_key */
+static_assert(sizeof(FilterAtt) == 4 && sizeof(FilterKey) == 16, "the descriptor's layout is the header's");
+
+__device__ inline bool filter_compare(uint32_t op, int64_t v, int64_t k)
+{
+    switch (op) {
+    case kOpLt: return v < k;
+    case kOpLe: return v <= k;
+    case kOpEq: return v == k;
+    case kOpGe: return v >= k;
+    case kOpGt: return v > k;
+    case kOpNe: return v != k;
+    default: return false; /* the host lets no other op through */
+    }
+}
+
+/* The verdict on one tuple of len bytes at t (8-byte aligned): 0 a match, kFilterNoMatch, or kFilterTuple.  `live` is false in
+ * lanes without a tuple: they make the same trips and load nothing.  Invariant of the walk: hoff + o <= len. */
+__device__ inline uint32_t filter_tuple(const uint8_t *__restrict__ t, uint32_t len, bool live, const FilterAtt *__restrict__ atts,
+                                        const FilterKey *__restrict__ keys, uint32_t nkeys, uint32_t max_att)
+{
+    uint32_t tnatts = 0, hoff = 0;
+    bool hasnull = false, bad = false, pass = true;
+    if (live) {
+        if (len < 23u) bad = true;
+        else {
+            tnatts = *reinterpret_cast<const uint16_t *>(t + 18) & 0x07FFu;
+            hasnull = (*reinterpret_cast<const uint16_t *>(t + 20) & 1u) != 0;
+            hoff = t[22];
+            const uint32_t need = (23u + (hasnull ? (tnatts + 7u) >> 3 : 0u) + 7u) & ~7u;
+            if ((hoff & 7u) != 0 || hoff < need || hoff > len) bad = true;
+        }
+    }
+    uint32_t pos = hoff; /* hoff + o; alignment counts from hoff, a multiple of 8, so aligning pos aligns o */
+    for (uint32_t col = 1; col <= max_att; col++) {
+        const FilterAtt a = atts[col - 1u]; /* uniform */
+        const uint32_t al = a.attalign - 1u;
+        const bool on = live && !bad;
+        bool isnull = true;
+        if (on && col <= tnatts) /* the bitmap's byte lies below hoff: the TUPLE rule */
+            isnull = hasnull && ((t[23u + ((col - 1u) >> 3)] >> ((col - 1u) & 7u)) & 1u) == 0;
+        const bool here = on && !isnull;
+        uint32_t size = 0;
+        if (a.attlen > 0) {
+            if (here) {
+                size = (uint32_t)a.attlen;
+                pos = (pos + al) & ~al;
+                if (pos > len || size > len - pos) bad = true;
+            }
+        } else if (here) {
+            if (pos >= len) bad = true;
+            else {
+                if (t[pos] == 0) pos = (pos + al) & ~al; /* a pad byte: the header is aligned (att_align_pointer) */
+                if (pos >= len) bad = true;
+                else {
+                    const uint32_t b = t[pos];
+                    if (b == 1u) { /* external: 18 bytes when on-disk TOAST */
+                        if (len - pos < 2u || t[pos + 1u] != 18u) bad = true;
+                        else size = 18u;
+                    } else if (b & 1u) size = b >> 1;
+                    else if (len - pos < 4u) bad = true;
+                    else {
+                        size = (b | (uint32_t)t[pos + 1u] << 8 | (uint32_t)t[pos + 2u] << 16 | (uint32_t)t[pos + 3u] << 24) >> 2;
+                        if (size < 4u) bad = true;
+                    }
+                    if (!bad && size > len - pos) bad = true;
+                }
+            }
+        }
+        const bool val = here && !bad;
+        for (uint32_t k = 0; k < nkeys; k++) {
+            const FilterKey key = keys[k]; /* uniform */
+            if (key.att != col) continue;
+            if (key.op == kOpIsNull) pass = pass && isnull;
+            else if (key.op == kOpNotNull) pass = pass && !isnull;
+            else {
+                int64_t v = 0;
+                if (val) { /* attlen is the key type's size and pos a multiple of it: the argument rule */
+                    if (a.attlen == 2) v = *reinterpret_cast<const int16_t *>(t + pos);
+                    else if (a.attlen == 4) v = *reinterpret_cast<const int32_t *>(t + pos);
+                    else v = *reinterpret_cast<const int64_t *>(t + pos);
+                }
+                pass = pass && val && filter_compare(key.op, v, key.value);
+            }
+        }
+        if (val) pos += size;
+    }
+    return bad ? kFilterTuple : pass ? 0u : kFilterNoMatch;
+}
+
+/* One sweep over a block's items.  WRITE = false: the sums {MAXALIGNed bytes of the matches, matches, bad items}.  WRITE = true:
+ * the side table's entries in position order; `overlap` drops the matches. */
+template <bool WRITE>
+__device__ inline void filter_sweep(const uint8_t *__restrict__ p, uint32_t B, uint32_t n, uint32_t upper, uint32_t lane,
+                                    const FilterAtt *__restrict__ atts, const FilterKey *__restrict__ keys, uint32_t nkeys,
+                                    uint32_t max_att, bool overlap, uint4 *__restrict__ side, uint64_t &bytes, uint32_t &n_match,
+                                    uint32_t &n_bad)
+{
+    uint64_t run = 0;
+    uint32_t recs = 0, matches = 0, bads = 0;
+    for (uint32_t t0 = 0; t0 < n; t0 += 64u) {
+        const uint32_t i = t0 + lane;
+        const bool valid = i < n;
+        uint32_t status = kFilterNoMatch, len = 0, src = 0;
+        if (valid) {
+            const uint2 it = *reinterpret_cast<const uint2 *>(p + 8u + 8u * i);
+            const uint64_t off = it.x, ln = it.y;
+            if (ln == 0 || (off & 7u) != 0 || off < upper || off + ((ln + 7u) & ~(uint64_t)7u) > B) status = kFilterItem;
+            else { len = it.y; src = it.x; }
+        }
+        const bool live = valid && status != kFilterItem;
+        const uint32_t verdict = filter_tuple(p + src, len, live, atts, keys, nkeys, max_att);
+        if (live) status = verdict;
+        const bool match = status == 0u, bad = status == kFilterItem || status == kFilterTuple;
+        const unsigned long long mm = __ballot(match), mb = __ballot(bad);
+        if (WRITE) {
+            const bool rec = bad || (match && !overlap);
+            const unsigned long long mr = overlap ? mb : (mm | mb);
+            const uint32_t a = match && !overlap ? (len + 7u) & ~7u : 0u;
+            uint32_t inc = a; /* a block's matches sum to at most B - upper here: 32 bits */
+#pragma unroll
+            for (uint32_t d = 1; d < 64u; d <<= 1) {
+                const uint32_t v = __shfl_up(inc, d);
+                if (lane >= d) inc += v;
+            }
+            if (rec) {
+                const uint32_t j = recs + (uint32_t)__popcll(mr & ((1ull << lane) - 1ull));
+                side[j] = make_uint4((uint32_t)run + inc - a, match ? src : 0u, match ? len : 0u, (i + 1u) | (match ? 0u : status << 16));
+            }
+            run += __shfl(inc, 63);
+            recs += (uint32_t)__popcll(mr);
+        } else {
+            uint64_t a = match ? ((uint64_t)len + 7u) & ~(uint64_t)7u : 0u;
+#pragma unroll
+            for (uint32_t d = 32; d >= 1u; d >>= 1) a += __shfl_xor((unsigned long long)a, d);
+            run += a;
+        }
+        matches += (uint32_t)__popcll(mm);
+        bads += (uint32_t)__popcll(mb);
+    }
+    bytes = run;
+    n_match = matches;
+    n_bad = bads;
+}
+
+__global__ void __launch_bounds__(256)
+k_filter_match(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, uint32_t cnt,
+               const int32_t *__restrict__ dec_status, const FilterAtt *__restrict__ atts, const FilterKey *__restrict__ keys,
+               uint32_t nkeys, uint32_t max_att, uint32_t count_only, uint32_t side_stride, uint4 *__restrict__ blocks,
+               uint4 *__restrict__ side, uint64_t *__restrict__ sum)
+{
+    /* the wave's number through readfirstlane: the compiler then knows the block, its header and the trip counts to be the same
+     * in all 64 lanes, and keeps them and the descriptor reads in scalar registers */
+    const uint32_t k = blockIdx.x * 4u + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t lane = threadIdx.x & 63u;
+    if (k >= cnt) return;
+    uint32_t status = 0, n_items = 0, n_match = 0, n_bad = 0;
+    uint64_t bytes = 0;
+    if (dec_status[k] != 0) status = kFilterStream; /* the decoders rejected the stream: nothing decoded to look at */
+    else {
+        const uint8_t *p = dec + (uint64_t)k * dec_stride;
+        const uint2 hdr = *reinterpret_cast<const uint2 *>(p);
+        const uint32_t lower = hdr.x, upper = hdr.y;
+        const uint32_t n = (lower - 8u) >> 3;
+        if (lower < 8u || (lower & 7u) != 0u || n > kFilterMaxItems || lower > upper || upper > B || (n == 0u && upper != B))
+            status = kFilterHeader;
+        else {
+            n_items = n; /* lower <= B: n <= side_stride */
+            filter_sweep<false>(p, B, n, upper, lane, atts, keys, nkeys, max_att, false, nullptr, bytes, n_match, n_bad);
+            if (!count_only) {
+                const bool overlap = bytes > (uint64_t)(B - upper);
+                uint64_t b2;
+                uint32_t m2, x2;
+                filter_sweep<true>(p, B, n, upper, lane, atts, keys, nkeys, max_att, overlap, side + (uint64_t)k * side_stride, b2,
+                                   m2, x2);
+                if (overlap) { status = kFilterOverlap; n_match = 0; bytes = 0; }
+            }
+        }
+    }
+    if (lane == 0) {
+        blocks[2u * k] = make_uint4(status, n_items, n_match, n_bad);
+        if (count_only) blocks[2u * k + 1u] = make_uint4(0u, 0u, 0u, 0u);
+        else {
+            sum[k] = bytes;
+            sum[cnt + k] = (uint64_t)n_match + n_bad;
+        }
+    }
+}
+
+/* base[k], base[cnt + 1 + k]: the bytes / records before block k of the chunk, counted from the call's start; entries cnt of both:
+ * the chunk's ends */
+__global__ void __launch_bounds__(256)
+k_filter_offsets(uint32_t cnt, const uint64_t *__restrict__ sum, uint64_t *__restrict__ base, uint64_t *__restrict__ running,
+                 uint4 *__restrict__ blocks)
+{
+    __shared__ uint64_t wave_sum[8];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint64_t run_b = running[0], run_r = running[1]; /* the same in every thread; written again only after the barriers below */
+    for (uint32_t t = 0; t < cnt; t += 256u) {
+        const uint32_t k = t + threadIdx.x;
+        const uint64_t ab = k < cnt ? sum[k] : 0u, ar = k < cnt ? sum[cnt + k] : 0u;
+        uint64_t ib = ab, ir = ar;
+#pragma unroll
+        for (uint32_t d = 1; d < 64u; d <<= 1) {
+            const uint64_t ub = __shfl_up((unsigned long long)ib, d), ur = __shfl_up((unsigned long long)ir, d);
+            if (lane >= d) { ib += ub; ir += ur; }
+        }
+        if (lane == 63u) { wave_sum[wave] = ib; wave_sum[4u + wave] = ir; }
+        __syncthreads();
+        uint64_t before_b = 0, tile_b = 0, before_r = 0, tile_r = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < 4u; w++) {
+            const uint64_t sb = wave_sum[w], sr = wave_sum[4u + w];
+            if (w < wave) { before_b += sb; before_r += sr; }
+            tile_b += sb;
+            tile_r += sr;
+        }
+        if (k < cnt) {
+            const uint64_t off = run_b + before_b + ib - ab, first = run_r + before_r + ir - ar;
+            base[k] = off;
+            base[cnt + 1u + k] = first;
+            blocks[2u * k + 1u] = make_uint4((uint32_t)first, (uint32_t)(first >> 32), (uint32_t)off, (uint32_t)(off >> 32));
+        }
+        run_b += tile_b;
+        run_r += tile_r;
+        __syncthreads(); /* wave_sum is written again in the next turn */
+    }
+    if (threadIdx.x == 0) {
+        base[cnt] = run_b;
+        base[2u * cnt + 1u] = run_r;
+        running[0] = run_b;
+        running[1] = run_r;
+    }
+}
+
+/* the last k in [lo, hi] with v[k] <= x; v[lo] <= x is the caller's */
+__device__ inline uint32_t filter_find_block(const uint64_t *__restrict__ v, uint32_t lo, uint32_t hi, uint64_t x)
+{
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
+        if (v[mid] <= x) lo = mid;
+        else hi = mid - 1u;
+    }
+    return lo;
+}
+/* the last j in [lo, hi] with side[j].x <= x; side[lo].x <= x is the caller's */
+__device__ inline uint32_t filter_find_rec(const uint4 *__restrict__ side, uint32_t lo, uint32_t hi, uint32_t x)
+{
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
+        if (side[mid].x <= x) lo = mid;
+        else hi = mid - 1u;
+    }
+    return lo;
+}
+
+__global__ void __launch_bounds__(256)
+k_filter_copy(uint32_t cnt, const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t side_stride,
+              const uint64_t *__restrict__ base, const uint4 *__restrict__ side, uint8_t *__restrict__ dst, uint64_t dst_cap,
+              uint2 *__restrict__ rec, uint64_t rec_cap, uint32_t chunk_relative)
+{
+    const uint64_t *base_r = base + cnt + 1u;
+    const uint64_t begin = base[0], end = base[cnt];
+    const uint64_t bias = chunk_relative ? begin : 0u, bias_r = chunk_relative ? base_r[0] : 0u;
+    for (uint64_t p0 = begin + (uint64_t)blockIdx.x * kFilterPiece; p0 < end; p0 += (uint64_t)gridDim.x * kFilterPiece) {
+        const uint64_t x = p0 + threadIdx.x * 8u;
+        if (x >= end) continue;
+        /* base[cnt] = end > p0: the block of the piece's first byte lies in [0, cnt - 1]; a block without room is never found
+         * (its successor starts at the same base) */
+        const uint32_t k0 = filter_find_block(base, 0u, cnt - 1u, p0);
+        const uint32_t k = base[k0 + 1u] > x ? k0 : filter_find_block(base, k0 + 1u, cnt - 1u, x);
+        const uint32_t xr = (uint32_t)(x - base[k]); /* below the block's sum, which is below the block size */
+        const uint32_t nrec = (uint32_t)(base_r[k + 1u] - base_r[k]);
+        if (nrec == 0u || nrec > side_stride) continue; /* a block with room has records */
+        const uint4 *sk = side + (uint64_t)k * side_stride;
+        const uint4 e = sk[filter_find_rec(sk, 0u, nrec - 1u, xr)];
+        const uint32_t at = xr - e.x, len = e.z;
+        if ((e.w >> 16) != 0u || at >= len) continue; /* cannot happen for a byte below the block's sum */
+        const uint64_t tuple_end = base[k] + e.x + (((uint64_t)len + 7u) & ~(uint64_t)7u) - bias;
+        if (tuple_end > dst_cap) continue;
+        uint2 v = *reinterpret_cast<const uint2 *>(dec + (uint64_t)k * dec_stride + e.y + at);
+        const uint32_t keep = len - at; /* bytes of the tuple from here on */
+        if (keep < 8u) {                 /* the tuple's last word: its pad is zero whatever the block holds there */
+            if (keep <= 4u) { v.y = 0u; if (keep < 4u) v.x &= (1u << (8u * keep)) - 1u; }
+            else v.y &= (1u << (8u * (keep - 4u))) - 1u;
+        }
+        *reinterpret_cast<uint2 *>(dst + (x - bias)) = v;
+    }
+    /* the records, from the side table to their places within the call */
+    for (uint32_t k = blockIdx.x; k < cnt; k += gridDim.x) {
+        const uint64_t first = base_r[k] - bias_r;
+        uint32_t nrec = (uint32_t)(base_r[k + 1u] - base_r[k]);
+        if (nrec > side_stride) nrec = side_stride;
+        const uint4 *sk = side + (uint64_t)k * side_stride;
+        for (uint32_t j = threadIdx.x; j < nrec; j += 256u) {
+            if (first + j >= rec_cap) break;
+            const uint4 e = sk[j];
+            rec[first + j] = make_uint2(e.w, e.z); /* {u16 pos, u16 status}, len */
+        }
+    }
+}
+
+hipError_t launch_filter(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
+                         const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, uint32_t max_att,
+                         bool count_only, uint4 *d_blocks, uint4 *d_side, uint64_t *d_sum, uint64_t *d_base, uint64_t *d_running,
+                         uint8_t *d_dst, uint64_t dst_cap, uint2 *d_rec, uint64_t rec_cap, bool chunk_relative, int cus)
+{
+    if (cnt == 0) return hipSuccess;
+    if ((dec_stride & 15u) != 0 || (((uintptr_t)d_dec | (uintptr_t)d_blocks | (uintptr_t)d_side) & 15u) != 0 ||
+        (((uintptr_t)d_dst | (uintptr_t)d_rec | (uintptr_t)d_keys) & 7u) != 0 || ((uintptr_t)d_atts & 3u) != 0 || block_size < 16u ||
+        nkeys > 4u)
+        return hipErrorInvalidValue;
+    const uint32_t stride = filter_side_stride(block_size);
+    hipLaunchKernelGGL(k_filter_match, dim3((cnt + 3u) / 4u), dim3(256), 0, s, d_dec, dec_stride, block_size, cnt, d_dec_status,
+                       (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys, max_att, count_only ? 1u : 0u, stride, d_blocks,
+                       d_side, d_sum);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || count_only) return e;
+    hipLaunchKernelGGL(k_filter_offsets, dim3(1), dim3(256), 0, s, cnt, d_sum, d_base, d_running, d_blocks);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    /* four workgroups per compute unit, but never more than the chunk's worst case has pieces (or blocks, for the records) */
+    const uint64_t worst = ((uint64_t)cnt * block_size + kFilterPiece - 1u) / kFilterPiece;
+    uint64_t grid = (uint64_t)(cus > 0 ? cus : 256) * 4u;
+    if (grid > worst) grid = worst;
+    if (grid < 1u) grid = 1u;
+    hipLaunchKernelGGL(k_filter_copy, dim3((uint32_t)grid), dim3(256), 0, s, cnt, d_dec, dec_stride, stride, d_base, d_side, d_dst,
+                       dst_cap, d_rec, rec_cap, chunk_relative ? 1u : 0u);
+    return hipGetLastError();
+}
+
+} // namespace cryo

@@ -236,6 +236,26 @@ hipError_t launch_fetch(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride
                         uint4 *d_result, uint2 *d_side, uint64_t *d_sum, uint64_t *d_base, uint64_t *d_running, uint8_t *d_dst,
                         uint64_t dst_cap, bool chunk_relative, int cus);
 
+/* the scan filter (filter.hip) on one decoded chunk of cnt blocks (laid out as for launch_fetch): k_filter_match,
+ * k_filter_offsets, k_filter_copy.  The descriptor is validated by the caller (cryo_codec.cpp, filter_desc_ok): d_atts natts
+ * entries of {i16 attlen, u8 attalign, u8 0}, d_keys nkeys <= 4 entries of cryo_scan_key (device memory), max_att the highest
+ * key column (0: no key).  d_blocks: the chunk's rows of the block table (cryo_filter_block, 16-byte aligned).  Scratch: d_side
+ * 16 bytes per possible item (cnt * filter_side_stride(block_size) entries), d_sum 2 * cnt and d_base 2 * (cnt + 1) entries.
+ * d_running: the two totals {bytes, records} before the chunk in, after it out.  The chunk's tuples go to d_dst (8-byte aligned)
+ * and its records to d_rec at their places within the call, or -- chunk_relative -- at those less the chunk's first; a tuple that
+ * would end beyond dst_cap and a record at or beyond rec_cap are not written.  count_only: k_filter_match alone; rec_first and
+ * off of the table are 0 and nothing else is written. */
+constexpr uint32_t kFilterMaxItems = 290u; /* MaxHeapTuplesPerPage - 1 (host/storage.c) */
+inline uint32_t filter_side_stride(uint32_t block_size)
+{
+    const uint32_t fit = (block_size - 8u) / 8u; /* lower <= B: no more item ids than this */
+    return fit < kFilterMaxItems ? fit : kFilterMaxItems;
+}
+hipError_t launch_filter(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
+                         const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, uint32_t max_att,
+                         bool count_only, uint4 *d_blocks, uint4 *d_side, uint64_t *d_sum, uint64_t *d_base, uint64_t *d_running,
+                         uint8_t *d_dst, uint64_t dst_cap, uint2 *d_rec, uint64_t rec_cap, bool chunk_relative, int cus);
+
 } // namespace cryo
 
 #define CRYO_WAVE 64

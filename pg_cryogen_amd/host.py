@@ -31,6 +31,9 @@ RECODE_BLOCKS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_
 FETCH_BLOCKS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_size_t,
                               C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint16), C.c_void_p, C.c_size_t, C.c_void_p,
                               C.POINTER(C.c_uint64))
+FILTER_BLOCKS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_size_t,
+                               C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                               C.POINTER(C.c_uint64))
 CRYO_CHECK_CHAIN, CRYO_CHECK_METHOD = 16, 17   # host-only reasons of check.h (beside cryo_check_reason 0..4)
 
 
@@ -60,6 +63,12 @@ class CryoCodecFetchOps(C.Structure):
     """host/compression.h's one-function table of the tuple fetch (FETCH_BLOCKS_FN), bound beside a CryoCodecOps double with
     cryo_host_set_fetch_ops (test build)"""
     _fields_ = [("fetch_blocks", FETCH_BLOCKS_FN)]
+
+
+class CryoCodecFilterOps(C.Structure):
+    """host/compression.h's one-function table of the scan filter (FILTER_BLOCKS_FN), bound beside a CryoCodecOps double with
+    cryo_host_set_filter_ops (test build)"""
+    _fields_ = [("filter_blocks", FILTER_BLOCKS_FN)]
 
 
 class CryoRel(C.Structure):
@@ -97,6 +106,11 @@ class CryoFetchReport(C.Structure):
 
 class CryoFetchTotals(C.Structure):
     _fields_ = [(f, C.c_uint64) for f in ("pages", "not_block_starts", "blocks", "tuples", "bad", "codec_calls", "bytes_back")]
+
+
+class CryoFilterTotals(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("blocks", "empty_pages", "items", "matches", "bad", "reports", "codec_calls",
+                                          "bytes_back")]
 
 
 FETCH_TUPLE_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(CryoFetchedTuple))
@@ -140,6 +154,11 @@ def lib():
     if hasattr(L, "cryo_host_set_fetch_ops"):   # test build only
         L.cryo_host_set_fetch_ops.argtypes = [C.POINTER(CryoCodecFetchOps)]
         L.cryo_host_set_fetch_ops.restype = None
+    if hasattr(L, "cryo_host_set_filter_ops"):  # test build only
+        L.cryo_host_set_filter_ops.argtypes = [C.POINTER(CryoCodecFilterOps)]
+        L.cryo_host_set_filter_ops.restype = None
+        L.cryo_filter_set_window.argtypes = [i32, sz]
+        L.cryo_filter_set_window.restype = None
     L.cryo_host_codec_error.restype = C.c_char_p
     L.cryo_compat_set_error_handler.argtypes = [ERROR_HANDLER]
     L.cryo_compat_set_error_handler.restype = None
@@ -204,6 +223,8 @@ def lib():
                                            vp, C.POINTER(CryoRecompressTotals)]
     L.cryo_fetch_tuples.argtypes = [C.POINTER(CryoRel), C.POINTER(CryoFetchPage), sz, FETCH_TUPLE_FN, FETCH_REPORT_FN, vp,
                                     C.POINTER(CryoFetchTotals)]
+    # CryoFilteredTuple and CryoFilterReport have the layouts of the fetch's CryoFetchedTuple and CryoFetchReport
+    L.cryo_filter_scan.argtypes = [C.POINTER(CryoRel), vp, FETCH_TUPLE_FN, FETCH_REPORT_FN, vp, C.POINTER(CryoFilterTotals)]
     for n in ("cryo_cache_hits", "cryo_cache_misses", "cryo_cache_codec_calls"):
         getattr(L, n).restype = C.c_uint64
     _libs[prod] = L
@@ -280,6 +301,35 @@ def fetch_tuples(rel, pages):
     totals = {f: getattr(t, f) for f, _ in CryoFetchTotals._fields_}
     if rc != 0:
         raise FetchTuplesError(rc, events, totals)
+    return events, totals
+
+
+class FilterScanError(RuntimeError):
+    def __init__(self, code, events, totals):
+        self.code, self.events, self.totals = code, events, totals
+        super().__init__("cryo_filter_scan failed: %d" % code)
+
+
+def filter_scan(rel, atts, keys=(), flags=0):
+    """cryo_filter_scan (host/filter.h) with the descriptor codec.filter_desc makes of atts [(attlen, attalign)], keys [(att,
+    type, op, value)] and flags.  Returns (events, totals): events in delivery order, ("tuple", block, pos, created_xid, bytes of
+    MAXALIGN(len), len) or ("report", block, reason, detail); totals a dict.  A nonzero status raises FilterScanError (which
+    carries what was delivered)."""
+    from . import codec
+    desc = codec.filter_desc(atts, keys, flags)
+    events = []
+
+    def on_tuple(arg, t):
+        t = t.contents
+        events.append(("tuple", t.block, t.pos, t.created_xid, C.string_at(t.data, (t.len + 7) & ~7), t.len))
+
+    tcb = FETCH_TUPLE_FN(on_tuple)
+    rcb = FETCH_REPORT_FN(lambda arg, r: events.append(("report", r.contents.block, r.contents.reason, r.contents.detail)))
+    t = CryoFilterTotals()
+    rc = lib().cryo_filter_scan(C.byref(rel), C.byref(desc[0]), tcb, rcb, None, C.byref(t))
+    totals = {f: getattr(t, f) for f, _ in CryoFilterTotals._fields_}
+    if rc != 0:
+        raise FilterScanError(rc, events, totals)
     return events, totals
 
 

@@ -117,6 +117,18 @@ void cryo_host_set_codec_ops(const CryoCodecOps *ops) { bound_ops = ops; }
 void cryo_host_set_fetch_ops(const CryoCodecFetchOps *ops) { bound_fetch_ops = ops; }
 #endif
 const CryoCodecFetchOps *cryo_host_fetch_ops(void) { return bound_ops ? bound_fetch_ops : &hip_fetch_ops; }
+static int hip_filter_blocks(void *ctx, int method, const void *const *src, const uint32_t *sz, size_t n, size_t bs,
+                             const void *filter, void *dst, size_t dst_cap, void *rec, size_t rec_cap, void *blocks, uint64_t *total)
+{
+    return cryo_multi_filter_blocks((cryo_multi *)ctx, method, src, sz, n, bs, (const cryo_filter *)filter, dst, dst_cap,
+                                    (cryo_filter_rec *)rec, rec_cap, (cryo_filter_block *)blocks, total);
+}
+static const CryoCodecFilterOps hip_filter_ops = {hip_filter_blocks};
+static const CryoCodecFilterOps *bound_filter_ops; /* the filter table of a bound double (CRYO_HOST_TEST_HOOKS builds only) */
+#ifdef CRYO_HOST_TEST_HOOKS
+void cryo_host_set_filter_ops(const CryoCodecFilterOps *ops) { bound_filter_ops = ops; }
+#endif
+const CryoCodecFilterOps *cryo_host_filter_ops(void) { return bound_ops ? bound_filter_ops : &hip_filter_ops; }
 const char *cryo_host_codec_error(void) { return codec_err; }
 
 const CryoCodecOps *cryo_host_codec_ops(void)

@@ -114,6 +114,19 @@ const CryoCodecFetchOps *cryo_host_fetch_ops(void);
 #ifdef CRYO_HOST_TEST_HOOKS
 void cryo_host_set_fetch_ops(const CryoCodecFetchOps *ops); /* test builds only: the fetch table of the bound double, or NULL */
 #endif
+/* the scan filter (filter.h, cryo_filter_scan) is bound through a table of its own as well.  filter_blocks is
+ * cryo_multi_filter_blocks (include/cryo_codec.h): filter is a const cryo_filter * with host arrays, blocks gets one
+ * cryo_filter_block (32 bytes) per stream, rec one cryo_filter_rec (8 bytes) per match and per bad item, the matches lie packed
+ * in dst, total[0] / total[1] are the ends of the last byte / record used */
+typedef struct CryoCodecFilterOps {
+    int (*filter_blocks)(void *ctx, int method, const void *const *src, const uint32_t *src_size, size_t n, size_t block_size,
+                         const void *filter, void *dst, size_t dst_cap, void *rec, size_t rec_cap, void *blocks, uint64_t *total);
+} CryoCodecFilterOps;
+/* the filter table that goes with cryo_host_codec_ops(): production's binds the GPU codec; NULL when a bound double has none */
+const CryoCodecFilterOps *cryo_host_filter_ops(void);
+#ifdef CRYO_HOST_TEST_HOOKS
+void cryo_host_set_filter_ops(const CryoCodecFilterOps *ops); /* test builds only: the filter table of the bound double, or NULL */
+#endif
 const CryoCodecOps *cryo_host_codec_ops(void);         /* lazily opens the GPU codec */
 void cryo_host_codec_trim(void);                         /* idle backend: free the binding's device workspace and staging buffers */
 size_t cryo_host_codec_bound(int method, size_t n);      /* cryo_codec_bound (or the bound double's): never opens the GPU */
