@@ -458,6 +458,62 @@ int cryo_codec_filter_batch(cryo_codec *c, int method, const void *d_src, const 
                             void *d_dst, uint64_t dst_cap, cryo_filter_rec *d_rec, uint64_t rec_cap,
                             cryo_filter_block *d_blocks, uint64_t *d_total);
 
+/* ---- aggregating a scan: stored streams -> decoded in handle workspace -> keys tested, integer columns reduced per block -> a
+ *      row and a few cells per block come back ----
+ * The query an append-only analytics store answers most: SELECT sum(x), min(ts), max(ts), count(x) FROM t WHERE ts >= a AND
+ * ts < b.  The filter above ships every matching tuple back and the host deforms it a second time to add up one column; here the
+ * column is reduced where the decoded block lies, and 16 + 40 * ncols bytes per block leave the device
+ * (pg_cryogen_amd/host/aggregate.h walks a relation with it).  The unit is the block because visibility is a per-block decision in
+ * this access method: a cryo block is written by one transaction (created_xid in the first page header), so the caller tests each
+ * block's xid once and adds up the partial aggregates of the visible blocks -- exact under any snapshot.
+ * A call names n_blocks stored streams as cryo_codec_check_batch does, the filter's descriptor *f (columns and up to four ANDed
+ * keys, unchanged) and an aggregate descriptor *agg: ncols columns, each {att, type}, whose values are reduced over the block's
+ * matches.
+ *
+ * Descriptor.  CRYO_E_ARG when: *f breaks one of the filter's descriptor rules above; f->flags != 0 (CRYO_FILTER_COUNT_ONLY has
+ * no meaning here); ncols is 0 or above 4 (a bare count is CRYO_FILTER_COUNT_ONLY's job); a column's att outside 1 .. f->natts; a
+ * column's type not a cryo_key_type; the column's attlen not the type's size, or its attalign below its attlen (the comparison
+ * key's rules); a reserved field (agg->rsv, a column's rsv or rsv2) that is not zero.  The same column may be named twice, and it
+ * may also carry a key.
+ *
+ * Per block (names as in the check's and the filter's rules above):
+ *   CRYO_FETCH_STREAM (1), CRYO_FETCH_HEADER (2)   exactly the filter's; n_items = n_match = n_bad = 0 and every cell of the block
+ *                                                  is all zero
+ *   otherwise (status 0, n_items = n) every item 1 .. n is examined with the filter's ITEM rule and TUPLE rule.  The walk over the
+ *   tuple is the filter's with ONE difference: it goes over the columns 1 .. max(highest key column, highest aggregate column) --
+ *   that far for every tuple, whatever the keys on the way said, and not a column further.  So a tuple whose bytes end before an
+ *   aggregate column that lies beyond the last key column is CRYO_FILTER_TUPLE here, where the same keys alone would pass it in the
+ *   filter.
+ *     n_match   the items that pass both rules and every key
+ *     n_bad     the items that fail the ITEM rule or the TUPLE rule (the walk included): counted, not listed, as under
+ *               CRYO_FILTER_COUNT_ONLY -- a caller who sees n_bad > 0 reads that block through the filter
+ *   OVERLAP is not applied, because nothing is placed.
+ *
+ * Per cell (block i, column j: cell i * ncols + j), over the block's matches:
+ *   n               the matches whose column j is not NULL (a column beyond the tuple's natts is NULL, as is one whose bitmap bit
+ *                   is clear)
+ *   min, max        over those values, each the signed little-endian integer of the column's type at its place in the tuple
+ *   sum_hi:sum_lo   their exact sum as a 128-bit two's-complement number (sum_lo the low 64 bits, unsigned; sum_hi the high 64
+ *                   bits, signed).  A block has at most 290 items, so it never overflows.
+ *   n == 0          min = max = 0 and the sum is 0
+ * count(col) is n, count(*) is n_match, avg is the caller's division; the partials of blocks combine by adding n and the 128-bit
+ * sums (with carry) and taking min / max over the cells with n > 0. */
+typedef struct { uint16_t att; uint8_t type, rsv; uint32_t rsv2; } cryo_agg_col;   /* att 1-based; type: cryo_key_type; 8 bytes */
+typedef struct { uint32_t ncols, rsv; const cryo_agg_col *cols; } cryo_agg;
+#define CRYO_AGG_MAX_COLS 4u
+typedef struct { uint32_t status, n_items, n_match, n_bad; } cryo_agg_block;      /* 16 bytes, one per block */
+typedef struct { uint64_t n; int64_t min, max; uint64_t sum_lo; int64_t sum_hi; } cryo_agg_cell; /* 40 bytes */
+/* Device buffers.  The structs *f and *agg are host memory; f->atts, f->keys and agg->cols are DEVICE arrays (4-byte / 8-byte /
+ * 8-byte aligned).  The host validates the descriptors before anything is queued: it reads the three arrays back on the handle's
+ * stream (one wait for what the stream held before the call); from there on the call is asynchronous, with no host wait between
+ * its internal chunks.  d_blocks (n_blocks rows) 16-byte, d_cells (n_blocks * ncols cells) 8-byte aligned (CRYO_E_ARG otherwise).
+ * Decode as in the filter: the automatic routes, handle workspace, chunks within CRYO_OPT_WORKSPACE_MAX_BYTES (the aggregate
+ * itself needs no workspace); the device pool is neither read nor filled, nothing counts in cryo_codec_counters.  CRYO_E_ARG as
+ * for cryo_codec_filter_batch (the same block-size rule), a bad descriptor, a null d_blocks or d_cells; n_blocks == 0: CRYO_OK. */
+int cryo_codec_agg_batch(cryo_codec *c, int method, const void *d_src, const uint64_t *d_src_off,
+                         const uint32_t *d_src_size, uint32_t block_size, uint64_t n_blocks, const cryo_filter *f,
+                         const cryo_agg *agg, cryo_agg_block *d_blocks, cryo_agg_cell *d_cells);
+
 /* ---- single block, HOST buffers: what cryo_compress()/cryo_decompress()
  *      (compression.c:125-159) call.  Synchronous: H2D, kernel, D2H. ---- */
 int cryo_codec_compress_block(cryo_codec *c, int method, int param,
@@ -544,6 +600,18 @@ int cryo_codec_filter_blocks(cryo_codec *c, int method, const void *const *h_src
                              size_t n_blocks, size_t block_size, const cryo_filter *f,
                              void *h_dst, size_t dst_cap, cryo_filter_rec *h_rec, size_t rec_cap,
                              cryo_filter_block *h_blocks, uint64_t *h_total);
+
+/* cryo_codec_agg_batch on host buffers (stream i: h_src[i], h_src_size[i] bytes; f->atts, f->keys and agg->cols are HOST arrays),
+ * synchronous.  Only compressed bytes and the descriptors travel towards the device, only rows and cells come back.
+ *   Upload   the streams staged and uploaded as by cryo_codec_filter_blocks, then the descriptors in a second copy: h2d_bytes
+ *            grows by another align16(4 * natts) + 16 * nkeys + align16(8 * ncols).
+ *   Return   rows and cells of the whole call in two copies after the last chunk, one wait: d2h_bytes grows by exactly
+ *            16 * n_blocks + 40 * n_blocks * ncols.
+ * CRYO_E_ARG as cryo_codec_agg_batch; a bad descriptor is refused before a device is touched.  Returns CRYO_OK when the batch
+ * ran, whatever the rows say. */
+int cryo_codec_agg_blocks(cryo_codec *c, int method, const void *const *h_src, const uint32_t *h_src_size,
+                          size_t n_blocks, size_t block_size, const cryo_filter *f, const cryo_agg *agg,
+                          cryo_agg_block *h_blocks, cryo_agg_cell *h_cells);
 
 /* ---- device-resident block pool ("optional device-resident compressed/decompressed pool so
  *      repeated scans skip PCIe"; the reference's cache is host-only: cache.c:17-50).
@@ -638,6 +706,13 @@ int cryo_multi_filter_blocks(cryo_multi *m, int method, const void *const *h_src
                              size_t n_blocks, size_t block_size, const cryo_filter *f,
                              void *h_dst, size_t dst_cap, cryo_filter_rec *h_rec, size_t rec_cap,
                              cryo_filter_block *h_blocks, uint64_t *h_total);
+
+/* cryo_codec_agg_blocks across the devices: block i -> handle i mod G.  Rows and cells have a fixed size per block and land in
+ * call order (block i's row at h_blocks[i], its cells from h_cells[i * ncols] on), so no per-handle regions are needed.  One
+ * handle: exactly cryo_codec_agg_blocks. */
+int cryo_multi_agg_blocks(cryo_multi *m, int method, const void *const *h_src, const uint32_t *h_src_size,
+                          size_t n_blocks, size_t block_size, const cryo_filter *f, const cryo_agg *agg,
+                          cryo_agg_block *h_blocks, cryo_agg_cell *h_cells);
 
 /* ---- batch helpers used by staging, tests and the benchmark ---- */
 

@@ -49,6 +49,11 @@ FILTER_KEY = np.dtype([("att", "<u2"), ("type", "u1"), ("op", "u1"), ("rsv", "<u
 FILTER_BLOCK = np.dtype([("status", "<u4"), ("n_items", "<u4"), ("n_match", "<u4"), ("n_bad", "<u4"),
                          ("rec_first", "<u8"), ("off", "<u8")])                                                # cryo_filter_block
 FILTER_REC = np.dtype([("pos", "<u2"), ("status", "<u2"), ("len", "<u4")])                                     # cryo_filter_rec
+# the scan aggregate (include/cryo_codec.h): a block's statuses are 0, FETCH_STREAM and FETCH_HEADER
+AGG_MAX_COLS = 4
+AGG_COL = np.dtype([("att", "<u2"), ("type", "u1"), ("rsv", "u1"), ("rsv2", "<u4")])                            # cryo_agg_col
+AGG_BLOCK = np.dtype([("status", "<u4"), ("n_items", "<u4"), ("n_match", "<u4"), ("n_bad", "<u4")])             # cryo_agg_block
+AGG_CELL = np.dtype([("n", "<u8"), ("min", "<i8"), ("max", "<i8"), ("sum_lo", "<u8"), ("sum_hi", "<i8")])       # cryo_agg_cell
 LZ4_PATH_AUTO, LZ4_PATH_RING, LZ4_PATH_INDEXED, LZ4_PATH_FEW_BLOCKS = 0, 1, 2, 3
 
 DIST_WIDE, DIST_NARROW, DIST_INT4, DIST_RANDOM, DIST_ZEROS = range(5)
@@ -77,6 +82,7 @@ ABI_SYMBOLS = [
     "cryo_codec_recode_batch", "cryo_codec_recode_blocks", "cryo_multi_recode_blocks",
     "cryo_codec_fetch_batch", "cryo_codec_fetch_blocks", "cryo_multi_fetch_blocks",
     "cryo_codec_filter_batch", "cryo_codec_filter_blocks", "cryo_multi_filter_blocks",
+    "cryo_codec_agg_batch", "cryo_codec_agg_blocks", "cryo_multi_agg_blocks",
     "cryo_codec_lz4_index_cap", "cryo_codec_lz4_index_rows",
 ]
 
@@ -91,6 +97,11 @@ class CryoFilter(C.Structure):
     """cryo_filter: atts / keys point to device arrays for filter_batch, to host arrays for filter_blocks"""
     _fields_ = [("natts", C.c_uint32), ("nkeys", C.c_uint32), ("flags", C.c_uint32), ("rsv", C.c_uint32),
                 ("atts", C.c_void_p), ("keys", C.c_void_p)]
+
+
+class CryoAgg(C.Structure):
+    """cryo_agg: cols points to a device array for agg_batch, to a host array for agg_blocks"""
+    _fields_ = [("ncols", C.c_uint32), ("rsv", C.c_uint32), ("cols", C.c_void_p)]
 
 
 class TransferCounters(C.Structure):
@@ -181,6 +192,10 @@ def lib():
     L.cryo_codec_filter_batch.argtypes = [vp, i32, vp, vp, vp, u32, u64, fp, vp, u64, vp, u64, vp, vp]
     L.cryo_codec_filter_blocks.argtypes = [vp, i32, vp, vp, sz, sz, fp, vp, sz, vp, sz, vp, vp]
     L.cryo_multi_filter_blocks.argtypes = [vp, i32, vp, vp, sz, sz, fp, vp, sz, vp, sz, vp, vp]
+    ap = C.POINTER(CryoAgg)
+    L.cryo_codec_agg_batch.argtypes = [vp, i32, vp, vp, vp, u32, u64, fp, ap, vp, vp]
+    L.cryo_codec_agg_blocks.argtypes = [vp, i32, vp, vp, sz, sz, fp, ap, vp, vp]
+    L.cryo_multi_agg_blocks.argtypes = [vp, i32, vp, vp, sz, sz, fp, ap, vp, vp]
     L.cryo_codec_lz4_index_cap.argtypes = [u32]
     L.cryo_codec_lz4_index_cap.restype = u32
     L.cryo_codec_lz4_index_rows.argtypes = [vp, vp, vp, vp, u32, u64, i32, vp, vp]
@@ -280,6 +295,34 @@ def filter_blocks_call(fn, handle, chk, method, comps, block_size, desc, dst=Non
     chk(fn(handle, method, src, szs, n, block_size, C.byref(desc[0]), dst.ctypes.data if dst.size else None, dst.nbytes,
            rec.ctypes.data if rec.size else None, rec.size, table.ctypes.data, total), "filter_blocks")
     return table[:n], rec, dst, (total[0], total[1])
+
+
+def agg_desc(cols):
+    """the aggregate descriptor of an agg call as a host array: cols a list of (att, type) (att 1-based; type KEY_*).  Returns
+    (CryoAgg, cols array); the struct points into the array, which the caller keeps alive"""
+    a = np.zeros(max(len(cols), 1), AGG_COL)
+    for j, (att, typ) in enumerate(cols):
+        a[j] = (att, typ, 0, 0)
+    return CryoAgg(len(cols), 0, a.ctypes.data), a
+
+
+def agg_blocks_call(fn, handle, chk, method, comps, block_size, desc, adesc):
+    """cryo_codec_agg_blocks / cryo_multi_agg_blocks (fn) on a list of host streams with the descriptors filter_desc and agg_desc
+    made; returns (rows: AGG_BLOCK array in call order, cells: AGG_CELL array of shape (n, ncols))"""
+    n, ncols = len(comps), adesc[0].ncols
+    arrs = [np.ascontiguousarray(np.asarray(c, dtype=np.uint8)) for c in comps]
+    src = (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.nbytes else None for a in arrs])
+    szs = (C.c_uint32 * max(n, 1))(*[a.nbytes for a in arrs])
+    rows = np.zeros(max(n, 1), AGG_BLOCK)
+    cells = np.zeros((max(n, 1), max(ncols, 1)), AGG_CELL)
+    chk(fn(handle, method, src, szs, n, block_size, C.byref(desc[0]), C.byref(adesc[0]), rows.ctypes.data, cells.ctypes.data),
+        "agg_blocks")
+    return rows[:n], cells[:n]
+
+
+def cell_sum(cell):
+    """the exact sum of an AGG_CELL as a Python integer"""
+    return (int(cell["sum_hi"]) << 64) + int(cell["sum_lo"])
 
 
 class DeviceBuffer:
@@ -492,6 +535,22 @@ class Codec:
         """filter host streams (desc: what filter_desc returns); returns (table, records, dst, (bytes, records)): block i's
         records are records[table[i]["rec_first"]:][:n_match + n_bad], its tuples lie MAXALIGN-packed from dst[table[i]["off"]:]"""
         return filter_blocks_call(self.L.cryo_codec_filter_blocks, self.h, self._chk, method, comps, block_size, desc, dst, rec)
+
+    def agg_batch(self, method, d_src, d_off, d_sizes, block_size, n, natts, d_atts, nkeys, d_keys, ncols, d_cols, d_blocks,
+                  d_cells):
+        """test the keys on every tuple of the n stored blocks and reduce the ncols columns d_cols names (AGG_COL; d_keys:
+        FILTER_KEY, d_atts: FILTER_ATT, device arrays) over each block's matches: one AGG_BLOCK row per block in d_blocks, ncols
+        AGG_CELL cells per block in d_cells.  Asynchronous once the descriptors are read back."""
+        f = CryoFilter(natts, nkeys, 0, 0, d_atts.ptr if d_atts else None, d_keys.ptr if d_keys else None)
+        a = CryoAgg(ncols, 0, d_cols.ptr if d_cols else None)
+        self._chk(self.L.cryo_codec_agg_batch(self.h, method, d_src.ptr, d_off.ptr, d_sizes.ptr, block_size, n, C.byref(f),
+                                              C.byref(a), d_blocks.ptr if d_blocks else None, d_cells.ptr if d_cells else None),
+                  "agg_batch")
+
+    def agg_blocks(self, method, comps, block_size, desc, adesc):
+        """aggregate host streams (desc: what filter_desc returns, adesc: what agg_desc returns); returns (rows, cells): rows an
+        AGG_BLOCK array in call order, cells an AGG_CELL array of shape (n, ncols); cell_sum gives a cell's 128-bit sum"""
+        return agg_blocks_call(self.L.cryo_codec_agg_blocks, self.h, self._chk, method, comps, block_size, desc, adesc)
 
     def last_verify_failure(self):
         """(block, first mismatch) that made the last host-buffer compress call fail verification, or None"""

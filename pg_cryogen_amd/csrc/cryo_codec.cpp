@@ -1232,6 +1232,56 @@ static int filter_pass(cryo_codec *c, int method, const uint8_t *d_src, const ui
     return rc;
 }
 
+/* ---- the scan aggregate ----
+ * The shared decode loop over the caller's stream table; on every decoded chunk agg.hip tests the keys on every tuple and reduces
+ * the aggregate columns of the matches, one row and ncols cells per block, written straight to the call's output at the chunk's
+ * first block.  The pass asks for no bytes of its own, keeps no totals and waits for nothing.  Its decodes count nowhere. */
+namespace {
+struct AggIo {
+    const void *d_atts = nullptr, *d_keys = nullptr, *d_cols = nullptr; /* device */
+    uint32_t nkeys = 0, ncols = 0, max_att = 0;
+    cryo_agg_block *d_blocks = nullptr; /* device: n rows */
+    cryo_agg_cell *d_cells = nullptr;   /* device: n * ncols cells */
+};
+} // namespace
+
+/* the aggregate's descriptor rules (include/cryo_codec.h); every array is host memory here.  *max_att: the highest key or
+ * aggregate column */
+static bool agg_desc_ok(const cryo_filter *f, const cryo_att *atts, const cryo_scan_key *keys, const cryo_agg *agg,
+                        const cryo_agg_col *cols, uint32_t *max_att)
+{
+    if (!filter_desc_ok(f, atts, keys, max_att)) return false;
+    if (f->flags != 0 || !agg || agg->ncols == 0 || agg->ncols > CRYO_AGG_MAX_COLS || agg->rsv != 0 || !cols) return false;
+    for (uint32_t j = 0; j < agg->ncols; j++) {
+        const cryo_agg_col &q = cols[j];
+        if (q.rsv != 0 || q.rsv2 != 0 || q.att == 0 || q.att > f->natts) return false;
+        if (q.type < CRYO_KEY_INT2 || q.type > CRYO_KEY_INT8) return false;
+        const int size = q.type == CRYO_KEY_INT2 ? 2 : q.type == CRYO_KEY_INT4 ? 4 : 8;
+        const cryo_att &a = atts[q.att - 1];
+        if (a.attlen != size || a.attalign < size) return false;
+        if (q.att > *max_att) *max_att = q.att;
+    }
+    return true;
+}
+
+static int agg_pass(cryo_codec *c, int method, const uint8_t *d_src, const uint64_t *d_src_off, const uint32_t *d_src_size,
+                    uint32_t B, uint64_t n, const AggIo &io)
+{
+    static_assert(sizeof(cryo_agg_block) == sizeof(uint4) && sizeof(cryo_agg_cell) == 40 && sizeof(cryo_agg_col) == 8,
+                  "the aggregate's records are the kernel's");
+    const cryo_codec_counters keep = c->ctr;
+    DecodePass ps;
+    ps.d_comp = d_src; ps.d_comp_off = d_src_off; ps.d_comp_size = d_src_size;
+    ps.run = [&](const DecodeChunk &ch) -> int {
+        HIP_TRY(c, cryo::launch_agg(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.d_atts, io.d_keys, io.nkeys, io.d_cols,
+                                    io.ncols, io.max_att, (uint4 *)(io.d_blocks + ch.lo), io.d_cells + ch.lo * io.ncols));
+        return CRYO_OK;
+    };
+    const int rc = decode_pass(c, method, B, n, ps);
+    c->ctr = keep;
+    return rc;
+}
+
 /* ---- recompression ----
  * The shared decode loop over the caller's stream table; every decoded chunk is encoded by cryo_codec_compress_batch -- the
  * path of every compress call, so the handle's encode options (segment mode, checksums, verification) apply as they are --
@@ -1428,6 +1478,39 @@ int cryo_codec_filter_batch(cryo_codec *c, int method, const void *d_src, const 
         io.d_blocks = d_blocks; io.dst_cap = count_only ? 0 : dst_cap; io.rec_cap = count_only ? 0 : rec_cap;
         io.d_dst = (uint8_t *)d_dst; io.d_rec = d_rec; io.d_total = d_total;
         return filter_pass(c, method, (const uint8_t *)d_src, d_src_off, d_src_size, block_size, n_blocks, io);
+    });
+}
+
+int cryo_codec_agg_batch(cryo_codec *c, int method, const void *d_src, const uint64_t *d_src_off, const uint32_t *d_src_size,
+                         uint32_t block_size, uint64_t n_blocks, const cryo_filter *f, const cryo_agg *agg,
+                         cryo_agg_block *d_blocks, cryo_agg_cell *d_cells)
+{
+    DevGuard dev_(c);
+    if (!c || !method_ok(method) || !check_block_size_ok(block_size)) return CRYO_E_ARG;
+    if (!f || f->natts == 0 || f->natts > CRYO_FILTER_MAX_ATTS || f->nkeys > CRYO_FILTER_MAX_KEYS || !f->atts ||
+        (f->nkeys > 0 && !f->keys) || ((uintptr_t)f->atts & 3u) != 0 || ((uintptr_t)f->keys & 7u) != 0)
+        return CRYO_E_ARG;
+    if (!agg || agg->ncols == 0 || agg->ncols > CRYO_AGG_MAX_COLS || !agg->cols || ((uintptr_t)agg->cols & 7u) != 0)
+        return CRYO_E_ARG;
+    if (n_blocks > 0 && (!d_src || !d_src_off || !d_src_size || !d_blocks || !d_cells || ((uintptr_t)d_blocks & 15u) != 0 ||
+                         ((uintptr_t)d_cells & 7u) != 0))
+        return CRYO_E_ARG;
+    return guarded([&] {
+        /* the descriptors live in device memory: read back and checked before anything is queued */
+        std::vector<cryo_att> atts(f->natts);
+        std::vector<cryo_scan_key> keys(f->nkeys ? f->nkeys : 1);
+        std::vector<cryo_agg_col> cols(agg->ncols);
+        HIP_TRY(c, hipMemcpyAsync(atts.data(), f->atts, f->natts * sizeof(cryo_att), hipMemcpyDeviceToHost, c->stream));
+        if (f->nkeys)
+            HIP_TRY(c, hipMemcpyAsync(keys.data(), f->keys, f->nkeys * sizeof(cryo_scan_key), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(cols.data(), agg->cols, agg->ncols * sizeof(cryo_agg_col), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        AggIo io;
+        if (!agg_desc_ok(f, atts.data(), keys.data(), agg, cols.data(), &io.max_att)) return (int)CRYO_E_ARG;
+        if (n_blocks == 0) return (int)CRYO_OK;
+        io.d_atts = f->atts; io.d_keys = f->keys; io.d_cols = agg->cols; io.nkeys = f->nkeys; io.ncols = agg->ncols;
+        io.d_blocks = d_blocks; io.d_cells = d_cells;
+        return agg_pass(c, method, (const uint8_t *)d_src, d_src_off, d_src_size, block_size, n_blocks, io);
     });
 }
 
@@ -2136,6 +2219,79 @@ int cryo_codec_filter_blocks(cryo_codec *c, int method, const void *const *h_src
     });
 }
 
+/* what every host-buffer aggregate call checks before a device is touched */
+static int agg_blocks_args(int method, size_t block_size, const cryo_filter *f, const cryo_agg *agg, uint32_t *max_att)
+{
+    if (!method_ok(method) || !check_block_size_ok(block_size)) return CRYO_E_ARG;
+    if (!f || !agg || !agg_desc_ok(f, f->atts, f->keys, agg, agg->cols, max_att)) return CRYO_E_ARG;
+    return CRYO_OK;
+}
+
+/* the scan aggregate of n streams given by pointer: the streams staged and uploaded as the filter's (stage_streams), the
+ * descriptors from the same pinned buffer in a second copy, both into place before the first decode; rows and cells of the whole
+ * call come back after the last chunk (agg_pass waits for nothing) */
+static int agg_blocks_impl(cryo_codec *c, int method, const void *const *h_src, const uint32_t *h_src_size, size_t n,
+                           size_t block_size, const cryo_filter *f, const cryo_agg *agg, cryo_agg_block *h_blocks,
+                           cryo_agg_cell *h_cells)
+{
+    uint32_t max_att = 0;
+    int rc = agg_blocks_args(method, block_size, f, agg, &max_att);
+    if (rc != CRYO_OK || !c) return CRYO_E_ARG;
+    DevGuard dev_(c);
+    if (n == 0) return CRYO_OK;
+    if (!h_src || !h_src_size || !h_blocks || !h_cells) return CRYO_E_ARG;
+    ScopedLocalCpus numa_(n * block_size >= ((size_t)8 << 20) ? c : nullptr);
+    /* the descriptors and the results: [atts 4 x natts][keys 16 x nkeys][cols 8 x ncols][rows 16 x n][cells 40 x n x ncols], each
+     * part 16-byte aligned */
+    const size_t t_atts = 0, t_keys = ((size_t)f->natts * 4 + 15) & ~(size_t)15, t_cols = t_keys + (size_t)f->nkeys * 16;
+    const size_t t_rows = t_cols + (((size_t)agg->ncols * 8 + 15) & ~(size_t)15);
+    const size_t rows_bytes = n * sizeof(cryo_agg_block), cells_bytes = n * agg->ncols * sizeof(cryo_agg_cell);
+    size_t streams = (n * 12 + 63) & ~(size_t)63; /* what stage_streams lays out in the pinned buffer */
+    for (size_t i = 0; i < n; i++) streams += ((size_t)h_src_size[i] + 15) & ~(size_t)15;
+    const size_t p_tbl = (streams + 64 + 15) & ~(size_t)15;
+    /* every allocation of the call before the uploads are queued; the pinned buffer at its final size, so that the staging of
+     * the streams leaves it where it is */
+    if ((rc = ensure_pinned(c, p_tbl + t_rows)) != CRYO_OK) return rc;
+    if ((rc = ensure(c, &c->hb_meta, &c->hb_meta_cap, t_rows + rows_bytes + cells_bytes + 64)) != CRYO_OK) return rc;
+    StagedStreams sg;
+    if ((rc = stage_streams(c, h_src, h_src_size, n, sg, true)) != CRYO_OK) return rc;
+    uint8_t *pin = (uint8_t *)c->pin + p_tbl;
+    memset(pin, 0, t_rows);
+    memcpy(pin + t_atts, f->atts, (size_t)f->natts * 4);
+    if (f->nkeys) memcpy(pin + t_keys, f->keys, (size_t)f->nkeys * 16);
+    memcpy(pin + t_cols, agg->cols, (size_t)agg->ncols * 8);
+    HIP_TRY(c, hipMemcpyAsync(c->hb_meta, pin, t_rows, hipMemcpyHostToDevice, c->stream));
+    c->xfer_ctr.h2d_bytes += t_rows;
+    AggIo io;
+    io.d_atts = c->hb_meta + t_atts; io.d_keys = c->hb_meta + t_keys; io.d_cols = c->hb_meta + t_cols;
+    io.nkeys = f->nkeys; io.ncols = agg->ncols; io.max_att = max_att;
+    io.d_blocks = (cryo_agg_block *)(c->hb_meta + t_rows);
+    io.d_cells = (cryo_agg_cell *)(c->hb_meta + t_rows + rows_bytes);
+    rc = agg_pass(c, method, c->hb_src, (const uint64_t *)(c->hb_src + sg.o_off), (const uint32_t *)(c->hb_src + sg.o_sz),
+                  (uint32_t)block_size, n, io);
+    if (rc == CRYO_OK) {
+        hipError_t e = hipMemcpyAsync(h_blocks, io.d_blocks, rows_bytes, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(h_cells, io.d_cells, cells_bytes, hipMemcpyDeviceToHost, c->stream);
+        if (e != hipSuccess) rc = fail(c, e, "hipMemcpyAsync of rows and cells");
+        else c->xfer_ctr.d2h_bytes += rows_bytes + cells_bytes;
+    }
+    /* the call's one wait: nothing in flight from the pinned buffer or into the caller's memory afterwards */
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (rc == CRYO_OK && es != hipSuccess) rc = fail(c, es, "hipStreamSynchronize");
+    return rc;
+}
+
+int cryo_codec_agg_blocks(cryo_codec *c, int method, const void *const *h_src, const uint32_t *h_src_size, size_t n,
+                          size_t block_size, const cryo_filter *f, const cryo_agg *agg, cryo_agg_block *h_blocks,
+                          cryo_agg_cell *h_cells)
+{
+    return guarded([&] {
+        const int rc = agg_blocks_impl(c, method, h_src, h_src_size, n, block_size, f, agg, h_blocks, h_cells);
+        if (c) ws_trim_after_call(c);
+        return rc;
+    });
+}
+
 } /* extern "C" */
 
 /* ---- device-resident block pool ---- */
@@ -2695,6 +2851,37 @@ int cryo_multi_filter_blocks(cryo_multi *m, int method, const void *const *h_src
         if (end_r[g] > h_total[1]) h_total[1] = end_r[g];
     }
     return CRYO_OK;
+}
+
+/* block i -> handle i mod G; rows and cells are fixed-size per block and land in call order */
+int cryo_multi_agg_blocks(cryo_multi *m, int method, const void *const *h_src, const uint32_t *h_src_size, size_t n,
+                          size_t block_size, const cryo_filter *f, const cryo_agg *agg, cryo_agg_block *h_blocks,
+                          cryo_agg_cell *h_cells)
+{
+    uint32_t max_att = 0;
+    if (!m || m->h.empty() || agg_blocks_args(method, block_size, f, agg, &max_att) != CRYO_OK) return CRYO_E_ARG;
+    const size_t G = m->h.size();
+    if (G == 1) return cryo_codec_agg_blocks(m->h[0], method, h_src, h_src_size, n, block_size, f, agg, h_blocks, h_cells);
+    if (n == 0) return CRYO_OK;
+    if (!h_src || !h_src_size || !h_blocks || !h_cells) return CRYO_E_ARG;
+    const size_t nc = agg->ncols;
+    return guarded([&] {
+        return multi_run(m, n, [&](size_t g, const std::vector<size_t> &idx) {
+            std::vector<const void *> src(idx.size());
+            std::vector<uint32_t> sz(idx.size());
+            std::vector<cryo_agg_block> rows(idx.size());
+            std::vector<cryo_agg_cell> cells(idx.size() * nc);
+            for (size_t k = 0; k < idx.size(); k++) { src[k] = h_src[idx[k]]; sz[k] = h_src_size[idx[k]]; }
+            const int r = agg_blocks_impl(m->h[g], method, src.data(), sz.data(), idx.size(), block_size, f, agg, rows.data(),
+                                          cells.data());
+            if (r != CRYO_OK) return r;
+            for (size_t k = 0; k < idx.size(); k++) {
+                h_blocks[idx[k]] = rows[k];
+                memcpy(h_cells + idx[k] * nc, &cells[k * nc], nc * sizeof(cryo_agg_cell));
+            }
+            return (int)CRYO_OK;
+        });
+    });
 }
 
 int cryo_multi_decompress_blocks_keyed(cryo_multi *m, int method, const uint64_t *keys, const void *const *h_src,

@@ -10,7 +10,7 @@
  *                     highest key column.  That loop is the same trip for all 64 lanes -- the column descriptor and the keys
  *                     are read at addresses that depend on the loop counter only, so they are uniform loads; what differs per
  *                     lane is the offset, the null bit and the varlena branch.  Keys are evaluated as the walk passes their
- *                     column.  A key's value is loaded at its proven alignment (tuples start at multiples of 8, hoff is one,
+ *                     column (the walk itself is filter_walk.h's, shared with agg.hip).  A key's value is loaded at its proven alignment (tuples start at multiples of 8, hoff is one,
  *                     attalign >= attlen is the argument rule); everything else of a tuple is read bytewise or, the three header
  *                     fields, at their fixed even offsets.  No load leaves [t, t + len): every read is preceded by its bound.
  *                     OVERLAP is a verdict on the block that is known only after the last turn, so -- as in the fetch -- a first
@@ -28,103 +28,17 @@
  * scratch.
  */
 #include "kernels.h"
+#include "filter_walk.h"
 
 namespace cryo {
 
-constexpr uint32_t kFilterStream = 1, kFilterHeader = 2, kFilterItem = 3, kFilterOverlap = 7, kFilterTuple = 8; /* statuses */
-constexpr uint32_t kFilterNoMatch = 0xFFFFu;  /* inside k_filter_match only: a good tuple that fails a key */
 constexpr uint32_t kFilterPiece = 256u * 8u;  /* packed bytes one workgroup copies per turn */
-constexpr uint32_t kOpLt = 1, kOpLe = 2, kOpEq = 3, kOpGe = 4, kOpGt = 5, kOpNe = 6, kOpIsNull = 7, kOpNotNull = 8;
 
-struct FilterAtt { int16_t attlen; uint8_t attalign, rsv; };                           /* cryo_att */
-struct FilterKey { uint16_t att; uint8_t type, op; uint32_t rsv; int64_t value; };    /* cryo_scan_key */
-static_assert(sizeof(FilterAtt) == 4 && sizeof(FilterKey) == 16, "the descriptor's layout is the header's");
-
-__device__ inline bool filter_compare(uint32_t op, int64_t v, int64_t k)
-{
-    switch (op) {
-    case kOpLt: return v < k;
-    case kOpLe: return v <= k;
-    case kOpEq: return v == k;
-    case kOpGe: return v >= k;
-    case kOpGt: return v > k;
-    case kOpNe: return v != k;
-    default: return false; /* the host lets no other op through */
-    }
-}
-
-/* The verdict on one tuple of len bytes at t (8-byte aligned): 0 a match, kFilterNoMatch, or kFilterTuple.  `live` is false in
- * lanes without a tuple: they make the same trips and load nothing.  Invariant of the walk: hoff + o <= len. */
+/* the walk of filter_walk.h without capture: 0 a match, kFilterNoMatch, or kFilterTuple */
 __device__ inline uint32_t filter_tuple(const uint8_t *__restrict__ t, uint32_t len, bool live, const FilterAtt *__restrict__ atts,
                                         const FilterKey *__restrict__ keys, uint32_t nkeys, uint32_t max_att)
 {
-    uint32_t tnatts = 0, hoff = 0;
-    bool hasnull = false, bad = false, pass = true;
-    if (live) {
-        if (len < 23u) bad = true;
-        else {
-            tnatts = *reinterpret_cast<const uint16_t *>(t + 18) & 0x07FFu;
-            hasnull = (*reinterpret_cast<const uint16_t *>(t + 20) & 1u) != 0;
-            hoff = t[22];
-            const uint32_t need = (23u + (hasnull ? (tnatts + 7u) >> 3 : 0u) + 7u) & ~7u;
-            if ((hoff & 7u) != 0 || hoff < need || hoff > len) bad = true;
-        }
-    }
-    uint32_t pos = hoff; /* hoff + o; alignment counts from hoff, a multiple of 8, so aligning pos aligns o */
-    for (uint32_t col = 1; col <= max_att; col++) {
-        const FilterAtt a = atts[col - 1u]; /* uniform */
-        const uint32_t al = a.attalign - 1u;
-        const bool on = live && !bad;
-        bool isnull = true;
-        if (on && col <= tnatts) /* the bitmap's byte lies below hoff: the TUPLE rule */
-            isnull = hasnull && ((t[23u + ((col - 1u) >> 3)] >> ((col - 1u) & 7u)) & 1u) == 0;
-        const bool here = on && !isnull;
-        uint32_t size = 0;
-        if (a.attlen > 0) {
-            if (here) {
-                size = (uint32_t)a.attlen;
-                pos = (pos + al) & ~al;
-                if (pos > len || size > len - pos) bad = true;
-            }
-        } else if (here) {
-            if (pos >= len) bad = true;
-            else {
-                if (t[pos] == 0) pos = (pos + al) & ~al; /* a pad byte: the header is aligned (att_align_pointer) */
-                if (pos >= len) bad = true;
-                else {
-                    const uint32_t b = t[pos];
-                    if (b == 1u) { /* external: 18 bytes when on-disk TOAST */
-                        if (len - pos < 2u || t[pos + 1u] != 18u) bad = true;
-                        else size = 18u;
-                    } else if (b & 1u) size = b >> 1;
-                    else if (len - pos < 4u) bad = true;
-                    else {
-                        size = (b | (uint32_t)t[pos + 1u] << 8 | (uint32_t)t[pos + 2u] << 16 | (uint32_t)t[pos + 3u] << 24) >> 2;
-                        if (size < 4u) bad = true;
-                    }
-                    if (!bad && size > len - pos) bad = true;
-                }
-            }
-        }
-        const bool val = here && !bad;
-        for (uint32_t k = 0; k < nkeys; k++) {
-            const FilterKey key = keys[k]; /* uniform */
-            if (key.att != col) continue;
-            if (key.op == kOpIsNull) pass = pass && isnull;
-            else if (key.op == kOpNotNull) pass = pass && !isnull;
-            else {
-                int64_t v = 0;
-                if (val) { /* attlen is the key type's size and pos a multiple of it: the argument rule */
-                    if (a.attlen == 2) v = *reinterpret_cast<const int16_t *>(t + pos);
-                    else if (a.attlen == 4) v = *reinterpret_cast<const int32_t *>(t + pos);
-                    else v = *reinterpret_cast<const int64_t *>(t + pos);
-                }
-                pass = pass && val && filter_compare(key.op, v, key.value);
-            }
-        }
-        if (val) pos += size;
-    }
-    return bad ? kFilterTuple : pass ? 0u : kFilterNoMatch;
+    return walk_tuple<false>(t, len, live, atts, keys, nkeys, max_att, nullptr, 0u, nullptr);
 }
 
 /* One sweep over a block's items.  WRITE = false: the sums {MAXALIGNed bytes of the matches, matches, bad items}.  WRITE = true:

@@ -1,0 +1,131 @@
+/*
+ * filter_walk.h -- the walk over one heap tuple that the scan filter (filter.hip) and the scan aggregate (agg.hip) share: the
+ * TUPLE rule, the column walk and the key tests of include/cryo_codec.h ("filtering a scan"), and -- for the aggregate -- the
+ * capture of up to four column values as the walk passes them ("aggregating a scan").  One statement of the walk: the filter
+ * instantiates it without capture, and the capture costs it nothing (the same registers, no scratch).
+ */
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace cryo {
+
+constexpr uint32_t kFilterStream = 1, kFilterHeader = 2, kFilterItem = 3, kFilterOverlap = 7, kFilterTuple = 8; /* statuses */
+constexpr uint32_t kFilterNoMatch = 0xFFFFu;  /* inside the kernels only: a good tuple that fails a key */
+constexpr uint32_t kOpLt = 1, kOpLe = 2, kOpEq = 3, kOpGe = 4, kOpGt = 5, kOpNe = 6, kOpIsNull = 7, kOpNotNull = 8;
+constexpr uint32_t kAggMaxCols = 4u;
+
+struct FilterAtt { int16_t attlen; uint8_t attalign, rsv; };                           /* cryo_att */
+struct FilterKey { uint16_t att; uint8_t type, op; uint32_t rsv; int64_t value; };    /* cryo_scan_key */
+struct AggCol { uint16_t att; uint8_t type, rsv; uint32_t rsv2; };                     /* cryo_agg_col */
+static_assert(sizeof(FilterAtt) == 4 && sizeof(FilterKey) == 16 && sizeof(AggCol) == 8, "the descriptor's layout is the header's");
+
+/* what the walk captured of a tuple: v[j] the value of aggregate column j, valid when bit j of `has` is set (the column is not
+ * NULL).  Only a tuple whose verdict is 0 has a capture worth reading. */
+struct WalkCapture { int64_t v[kAggMaxCols]; uint32_t has; };
+
+__device__ inline bool filter_compare(uint32_t op, int64_t v, int64_t k)
+{
+    switch (op) {
+    case kOpLt: return v < k;
+    case kOpLe: return v <= k;
+    case kOpEq: return v == k;
+    case kOpGe: return v >= k;
+    case kOpGt: return v > k;
+    case kOpNe: return v != k;
+    default: return false; /* the host lets no other op through */
+    }
+}
+
+/* the signed integer of attlen 2, 4 or 8 bytes at p, which is aligned to attlen */
+__device__ inline int64_t walk_value(const uint8_t *__restrict__ p, int32_t attlen)
+{
+    if (attlen == 2) return *reinterpret_cast<const int16_t *>(p);
+    if (attlen == 4) return *reinterpret_cast<const int32_t *>(p);
+    return *reinterpret_cast<const int64_t *>(p);
+}
+
+/* The verdict on one tuple of len bytes at t (8-byte aligned): 0 a match, kFilterNoMatch, or kFilterTuple.  `live` is false in
+ * lanes without a tuple: they make the same trips and load nothing.  Invariant of the walk: hoff + o <= len.  CAPTURE: the walk
+ * also notes the value of each of the ncols columns cols[] names (their att <= max_att, attlen the type's size and attalign at
+ * least that: the aggregate's argument rule) in *cap; cols is read at addresses that depend on the loop counters only. */
+template <bool CAPTURE>
+__device__ inline uint32_t walk_tuple(const uint8_t *__restrict__ t, uint32_t len, bool live, const FilterAtt *__restrict__ atts,
+                                      const FilterKey *__restrict__ keys, uint32_t nkeys, uint32_t max_att,
+                                      const AggCol *__restrict__ cols, uint32_t ncols, WalkCapture *cap)
+{
+    uint32_t tnatts = 0, hoff = 0;
+    bool hasnull = false, bad = false, pass = true;
+    if (live) {
+        if (len < 23u) bad = true;
+        else {
+            tnatts = *reinterpret_cast<const uint16_t *>(t + 18) & 0x07FFu;
+            hasnull = (*reinterpret_cast<const uint16_t *>(t + 20) & 1u) != 0;
+            hoff = t[22];
+            const uint32_t need = (23u + (hasnull ? (tnatts + 7u) >> 3 : 0u) + 7u) & ~7u;
+            if ((hoff & 7u) != 0 || hoff < need || hoff > len) bad = true;
+        }
+    }
+    uint32_t pos = hoff; /* hoff + o; alignment counts from hoff, a multiple of 8, so aligning pos aligns o */
+    for (uint32_t col = 1; col <= max_att; col++) {
+        const FilterAtt a = atts[col - 1u]; /* uniform */
+        const uint32_t al = a.attalign - 1u;
+        const bool on = live && !bad;
+        bool isnull = true;
+        if (on && col <= tnatts) /* the bitmap's byte lies below hoff: the TUPLE rule */
+            isnull = hasnull && ((t[23u + ((col - 1u) >> 3)] >> ((col - 1u) & 7u)) & 1u) == 0;
+        const bool here = on && !isnull;
+        uint32_t size = 0;
+        if (a.attlen > 0) {
+            if (here) {
+                size = (uint32_t)a.attlen;
+                pos = (pos + al) & ~al;
+                if (pos > len || size > len - pos) bad = true;
+            }
+        } else if (here) {
+            if (pos >= len) bad = true;
+            else {
+                if (t[pos] == 0) pos = (pos + al) & ~al; /* a pad byte: the header is aligned (att_align_pointer) */
+                if (pos >= len) bad = true;
+                else {
+                    const uint32_t b = t[pos];
+                    if (b == 1u) { /* external: 18 bytes when on-disk TOAST */
+                        if (len - pos < 2u || t[pos + 1u] != 18u) bad = true;
+                        else size = 18u;
+                    } else if (b & 1u) size = b >> 1;
+                    else if (len - pos < 4u) bad = true;
+                    else {
+                        size = (b | (uint32_t)t[pos + 1u] << 8 | (uint32_t)t[pos + 2u] << 16 | (uint32_t)t[pos + 3u] << 24) >> 2;
+                        if (size < 4u) bad = true;
+                    }
+                    if (!bad && size > len - pos) bad = true;
+                }
+            }
+        }
+        const bool val = here && !bad;
+        for (uint32_t k = 0; k < nkeys; k++) {
+            const FilterKey key = keys[k]; /* uniform */
+            if (key.att != col) continue;
+            if (key.op == kOpIsNull) pass = pass && isnull;
+            else if (key.op == kOpNotNull) pass = pass && !isnull;
+            else {
+                /* attlen is the key type's size and pos a multiple of it: the argument rule */
+                const int64_t v = val ? walk_value(t + pos, a.attlen) : 0;
+                pass = pass && val && filter_compare(key.op, v, key.value);
+            }
+        }
+        if (CAPTURE) {
+#pragma unroll
+            for (uint32_t j = 0; j < kAggMaxCols; j++) { /* unrolled: v[j] stays in registers */
+                if (j >= ncols || cols[j].att != col) continue; /* uniform */
+                /* as for a key: the column's [pos, pos + attlen) lies below len, aligned by the aggregate's argument rule */
+                cap->v[j] = val ? walk_value(t + pos, a.attlen) : 0;
+                if (val) cap->has |= 1u << j;
+            }
+        }
+        if (val) pos += size;
+    }
+    return bad ? kFilterTuple : pass ? 0u : kFilterNoMatch;
+}
+
+} // namespace cryo

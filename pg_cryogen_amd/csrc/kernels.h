@@ -256,6 +256,16 @@ hipError_t launch_filter(hipStream_t s, const uint8_t *d_dec, uint64_t dec_strid
                          bool count_only, uint4 *d_blocks, uint4 *d_side, uint64_t *d_sum, uint64_t *d_base, uint64_t *d_running,
                          uint8_t *d_dst, uint64_t dst_cap, uint2 *d_rec, uint64_t rec_cap, bool chunk_relative, int cus);
 
+/* the scan aggregate (agg.hip) on one decoded chunk of cnt blocks (laid out as for launch_filter): k_agg_block alone.  The
+ * descriptors are validated by the caller (cryo_codec.cpp, agg_desc_ok): d_atts and d_keys as for launch_filter, d_cols ncols
+ * (1 .. 4) entries of cryo_agg_col (device memory, 8-byte aligned), max_att the highest key or aggregate column.  d_blocks: the
+ * chunk's rows (cryo_agg_block, 16-byte aligned); d_cells: its cnt * ncols cells (cryo_agg_cell, 8-byte aligned), block k's at
+ * k * ncols.  Workspace rule: none -- the kernel keeps everything in registers and writes only the rows and the cells, so a pass
+ * over it asks the shared decode loop for no bytes of its own. */
+hipError_t launch_agg(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
+                      const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_cols,
+                      uint32_t ncols, uint32_t max_att, uint4 *d_blocks, void *d_cells);
+
 } // namespace cryo
 
 #define CRYO_WAVE 64

@@ -34,6 +34,8 @@ FETCH_BLOCKS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p
 FILTER_BLOCKS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_size_t,
                                C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
                                C.POINTER(C.c_uint64))
+AGG_BLOCKS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_size_t,
+                            C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
 CRYO_CHECK_CHAIN, CRYO_CHECK_METHOD = 16, 17   # host-only reasons of check.h (beside cryo_check_reason 0..4)
 
 
@@ -69,6 +71,12 @@ class CryoCodecFilterOps(C.Structure):
     """host/compression.h's one-function table of the scan filter (FILTER_BLOCKS_FN), bound beside a CryoCodecOps double with
     cryo_host_set_filter_ops (test build)"""
     _fields_ = [("filter_blocks", FILTER_BLOCKS_FN)]
+
+
+class CryoCodecAggOps(C.Structure):
+    """host/compression.h's one-function table of the scan aggregate (AGG_BLOCKS_FN), bound beside a CryoCodecOps double with
+    cryo_host_set_agg_ops (test build)"""
+    _fields_ = [("agg_blocks", AGG_BLOCKS_FN)]
 
 
 class CryoRel(C.Structure):
@@ -113,6 +121,22 @@ class CryoFilterTotals(C.Structure):
                                           "bytes_back")]
 
 
+class CryoAggCell(C.Structure):
+    """cryo_agg_cell (include/cryo_codec.h)"""
+    _fields_ = [("n", C.c_uint64), ("min", C.c_int64), ("max", C.c_int64), ("sum_lo", C.c_uint64), ("sum_hi", C.c_int64)]
+
+
+class CryoAggBlock(C.Structure):
+    _fields_ = [("block", C.c_uint32), ("created_xid", C.c_uint32), ("n_items", C.c_uint32), ("n_match", C.c_uint32),
+                ("n_bad", C.c_uint32), ("cells", C.POINTER(CryoAggCell))]
+
+
+class CryoAggTotals(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("blocks", "empty_pages", "items", "matches", "bad", "reports", "codec_calls",
+                                          "bytes_back")] + [("cells", CryoAggCell * 4)]
+
+
+AGG_BLOCK_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(CryoAggBlock))
 FETCH_TUPLE_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(CryoFetchedTuple))
 FETCH_REPORT_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(CryoFetchReport))
 RECOMPRESS_MOVED_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32)
@@ -159,6 +183,11 @@ def lib():
         L.cryo_host_set_filter_ops.restype = None
         L.cryo_filter_set_window.argtypes = [i32, sz]
         L.cryo_filter_set_window.restype = None
+    if hasattr(L, "cryo_host_set_agg_ops"):     # test build only
+        L.cryo_host_set_agg_ops.argtypes = [C.POINTER(CryoCodecAggOps)]
+        L.cryo_host_set_agg_ops.restype = None
+        L.cryo_aggregate_set_window.argtypes = [i32, sz]
+        L.cryo_aggregate_set_window.restype = None
     L.cryo_host_codec_error.restype = C.c_char_p
     L.cryo_compat_set_error_handler.argtypes = [ERROR_HANDLER]
     L.cryo_compat_set_error_handler.restype = None
@@ -225,6 +254,8 @@ def lib():
                                     C.POINTER(CryoFetchTotals)]
     # CryoFilteredTuple and CryoFilterReport have the layouts of the fetch's CryoFetchedTuple and CryoFetchReport
     L.cryo_filter_scan.argtypes = [C.POINTER(CryoRel), vp, FETCH_TUPLE_FN, FETCH_REPORT_FN, vp, C.POINTER(CryoFilterTotals)]
+    # CryoAggReport has the layout of the fetch's CryoFetchReport
+    L.cryo_aggregate_scan.argtypes = [C.POINTER(CryoRel), vp, vp, AGG_BLOCK_FN, FETCH_REPORT_FN, vp, C.POINTER(CryoAggTotals)]
     for n in ("cryo_cache_hits", "cryo_cache_misses", "cryo_cache_codec_calls"):
         getattr(L, n).restype = C.c_uint64
     _libs[prod] = L
@@ -330,6 +361,43 @@ def filter_scan(rel, atts, keys=(), flags=0):
     totals = {f: getattr(t, f) for f, _ in CryoFilterTotals._fields_}
     if rc != 0:
         raise FilterScanError(rc, events, totals)
+    return events, totals
+
+
+class AggregateScanError(RuntimeError):
+    def __init__(self, code, events, totals):
+        self.code, self.events, self.totals = code, events, totals
+        super().__init__("cryo_aggregate_scan failed: %d" % code)
+
+
+def _cell(c):
+    """(n, min, max, sum) of a CryoAggCell, the sum as a Python integer"""
+    return (c.n, c.min, c.max, (c.sum_hi << 64) + c.sum_lo)
+
+
+def aggregate_scan(rel, atts, keys, cols):
+    """cryo_aggregate_scan (host/aggregate.h) with the descriptors codec.filter_desc and codec.agg_desc make of atts [(attlen,
+    attalign)], keys [(att, type, op, value)] and cols [(att, type)].  Returns (events, totals): events in delivery order,
+    ("block", block, created_xid, n_items, n_match, n_bad, [(n, min, max, sum) per column]) or ("report", block, reason, detail);
+    totals a dict whose "cells" are the combined [(n, min, max, sum) per column].  A nonzero status raises AggregateScanError
+    (which carries what was delivered)."""
+    from . import codec
+    desc, adesc = codec.filter_desc(atts, keys), codec.agg_desc(cols)
+    ncols = len(cols)
+    events = []
+
+    def on_block(arg, b):
+        b = b.contents
+        events.append(("block", b.block, b.created_xid, b.n_items, b.n_match, b.n_bad, [_cell(b.cells[j]) for j in range(ncols)]))
+
+    bcb = AGG_BLOCK_FN(on_block)
+    rcb = FETCH_REPORT_FN(lambda arg, r: events.append(("report", r.contents.block, r.contents.reason, r.contents.detail)))
+    t = CryoAggTotals()
+    rc = lib().cryo_aggregate_scan(C.byref(rel), C.byref(desc[0]), C.byref(adesc[0]), bcb, rcb, None, C.byref(t))
+    totals = {f: getattr(t, f) for f, _ in CryoAggTotals._fields_ if f != "cells"}
+    totals["cells"] = [_cell(t.cells[j]) for j in range(min(ncols, 4))]
+    if rc != 0:
+        raise AggregateScanError(rc, events, totals)
     return events, totals
 
 

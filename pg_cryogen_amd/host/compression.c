@@ -129,6 +129,18 @@ static const CryoCodecFilterOps *bound_filter_ops; /* the filter table of a boun
 void cryo_host_set_filter_ops(const CryoCodecFilterOps *ops) { bound_filter_ops = ops; }
 #endif
 const CryoCodecFilterOps *cryo_host_filter_ops(void) { return bound_ops ? bound_filter_ops : &hip_filter_ops; }
+static int hip_agg_blocks(void *ctx, int method, const void *const *src, const uint32_t *sz, size_t n, size_t bs,
+                          const void *filter, const void *agg, void *blocks, void *cells)
+{
+    return cryo_multi_agg_blocks((cryo_multi *)ctx, method, src, sz, n, bs, (const cryo_filter *)filter, (const cryo_agg *)agg,
+                                 (cryo_agg_block *)blocks, (cryo_agg_cell *)cells);
+}
+static const CryoCodecAggOps hip_agg_ops = {hip_agg_blocks};
+static const CryoCodecAggOps *bound_agg_ops; /* the aggregate table of a bound double (CRYO_HOST_TEST_HOOKS builds only) */
+#ifdef CRYO_HOST_TEST_HOOKS
+void cryo_host_set_agg_ops(const CryoCodecAggOps *ops) { bound_agg_ops = ops; }
+#endif
+const CryoCodecAggOps *cryo_host_agg_ops(void) { return bound_ops ? bound_agg_ops : &hip_agg_ops; }
 const char *cryo_host_codec_error(void) { return codec_err; }
 
 const CryoCodecOps *cryo_host_codec_ops(void)

@@ -127,6 +127,19 @@ const CryoCodecFilterOps *cryo_host_filter_ops(void);
 #ifdef CRYO_HOST_TEST_HOOKS
 void cryo_host_set_filter_ops(const CryoCodecFilterOps *ops); /* test builds only: the filter table of the bound double, or NULL */
 #endif
+/* the scan aggregate (aggregate.h, cryo_aggregate_scan) is bound through a table of its own as well.  agg_blocks is
+ * cryo_multi_agg_blocks (include/cryo_codec.h): filter is a const cryo_filter * and agg a const cryo_agg *, both with host
+ * arrays; blocks gets one cryo_agg_block (16 bytes) per stream, cells agg->ncols cryo_agg_cell (40 bytes each) per stream, in
+ * call order */
+typedef struct CryoCodecAggOps {
+    int (*agg_blocks)(void *ctx, int method, const void *const *src, const uint32_t *src_size, size_t n, size_t block_size,
+                      const void *filter, const void *agg, void *blocks, void *cells);
+} CryoCodecAggOps;
+/* the aggregate table that goes with cryo_host_codec_ops(): production's binds the GPU codec; NULL when a bound double has none */
+const CryoCodecAggOps *cryo_host_agg_ops(void);
+#ifdef CRYO_HOST_TEST_HOOKS
+void cryo_host_set_agg_ops(const CryoCodecAggOps *ops); /* test builds only: the aggregate table of the bound double, or NULL */
+#endif
 const CryoCodecOps *cryo_host_codec_ops(void);         /* lazily opens the GPU codec */
 void cryo_host_codec_trim(void);                         /* idle backend: free the binding's device workspace and staging buffers */
 size_t cryo_host_codec_bound(int method, size_t n);      /* cryo_codec_bound (or the bound double's): never opens the GPU */

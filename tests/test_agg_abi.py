@@ -1,0 +1,89 @@
+"""CPU tests of the scan aggregate's surface: what include/cryo_codec.h declares, what the libraries export, the layouts of the
+structures on both sides of the ABI, and the argument errors that need no device."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+
+import agg_cases as ac
+import agg_ref as ar
+from pg_cryogen_amd import codec, host
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMES = ("cryo_codec_agg_batch", "cryo_codec_agg_blocks", "cryo_multi_agg_blocks")
+
+
+def test_header_declares_and_libraries_export():
+    from pg_cryogen_amd import _loader
+    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "cryo_codec.h")).read(), flags=re.S)
+    L = codec.lib()
+    for n in NAMES:
+        assert re.search(r"\bint\s+%s\s*\(" % n, txt), n
+        assert n in codec.ABI_SYMBOLS and hasattr(L, n), n
+    _loader.load()
+    for path in (host.HOST_LIB_PATH, host.HOST_TEST_LIB_PATH):
+        lib = C.CDLL(path)
+        assert hasattr(lib, "cryo_aggregate_scan") and hasattr(lib, "cryo_host_agg_ops"), path
+    assert hasattr(C.CDLL(host.HOST_TEST_LIB_PATH), "cryo_host_set_agg_ops")
+    assert hasattr(C.CDLL(host.HOST_TEST_LIB_PATH), "cryo_aggregate_set_window")
+    assert not hasattr(C.CDLL(host.HOST_LIB_PATH), "cryo_host_set_agg_ops")         # the hooks are the test build's only
+    assert not hasattr(C.CDLL(host.HOST_LIB_PATH), "cryo_aggregate_set_window")
+
+
+def test_struct_sizes_and_values():
+    txt = open(os.path.join(ROOT, "include", "cryo_codec.h")).read()
+    assert re.search(r"typedef struct \{ uint16_t att; uint8_t type, rsv; uint32_t rsv2; \} cryo_agg_col;", txt)
+    assert re.search(r"typedef struct \{ uint32_t ncols, rsv; const cryo_agg_col \*cols; \} cryo_agg;", txt)
+    assert re.search(r"typedef struct \{ uint32_t status, n_items, n_match, n_bad; \} cryo_agg_block;", txt)
+    assert re.search(r"typedef struct \{ uint64_t n; int64_t min, max; uint64_t sum_lo; int64_t sum_hi; \} cryo_agg_cell;", txt)
+    assert re.search(r"#define CRYO_AGG_MAX_COLS 4u", re.sub(r"/\*.*?\*/", "", txt, flags=re.S))
+    assert (codec.AGG_COL.itemsize, C.sizeof(codec.CryoAgg), codec.AGG_BLOCK.itemsize, codec.AGG_CELL.itemsize) == (8, 16, 16, 40)
+    assert (ar.ROW, ar.CELL) == (codec.AGG_BLOCK, codec.AGG_CELL) and codec.AGG_MAX_COLS == ar.MAX_COLS == 4
+    assert C.sizeof(host.CryoAggCell) == 40 and C.sizeof(host.CryoAggBlock) == 32 and C.sizeof(host.CryoCodecAggOps) == 8
+    assert C.sizeof(host.CryoAggTotals) == 8 * 8 + 4 * 40
+    # the other tables keep their layouts: the aggregate is bound through a table of its own
+    assert C.sizeof(host.CryoCodecOpsRecode) == C.sizeof(host.CryoCodecOps) + 16
+    assert C.sizeof(host.CryoCodecFilterOps) == 8 and C.sizeof(host.CryoCodecFetchOps) == 8
+    # the section that states the rules comes after the filter's
+    assert txt.index("filtering a scan") < txt.index("aggregating a scan") < txt.index("int cryo_codec_agg_batch")
+
+
+def test_descriptor_helpers():
+    g, a = codec.agg_desc(ac.COLS4)
+    assert g.ncols == 4 and g.rsv == 0 and g.cols == a.ctypes.data
+    assert [(int(c["att"]), int(c["type"])) for c in a] == ac.COLS4 and not a["rsv"].any() and not a["rsv2"].any()
+    cell = np.zeros(1, codec.AGG_CELL)[0]
+    cell["sum_lo"], cell["sum_hi"] = (1 << 64) - 56, -1
+    assert codec.cell_sum(cell) == -56 == ar.total_of(cell)
+    cell["sum_lo"], cell["sum_hi"] = (1 << 64) - 290, 144
+    assert codec.cell_sum(cell) == 290 * ((1 << 63) - 1)
+
+
+def test_argument_errors_need_no_device():
+    """a null handle and every bad descriptor: CRYO_E_ARG from the host-buffer calls before a device is touched"""
+    L = codec.lib()
+    rows, cells = np.zeros(1, codec.AGG_BLOCK), np.zeros(4, codec.AGG_CELL)
+    f, g = codec.filter_desc(ac.ATTS, []), codec.agg_desc([(4, codec.KEY_INT4)])
+    assert L.cryo_codec_agg_batch(None, 0, None, None, None, 4096, 0, C.byref(f[0]), C.byref(g[0]), None, None) == codec.E_ARG
+    for fn in (L.cryo_codec_agg_blocks, L.cryo_multi_agg_blocks):
+        assert fn(None, 0, None, None, 0, 4096, C.byref(f[0]), C.byref(g[0]), rows.ctypes.data, cells.ctypes.data) == codec.E_ARG
+        assert fn(None, 0, None, None, 0, 4096, None, C.byref(g[0]), rows.ctypes.data, cells.ctypes.data) == codec.E_ARG
+        assert fn(None, 0, None, None, 0, 4096, C.byref(f[0]), None, rows.ctypes.data, cells.ctypes.data) == codec.E_ARG
+
+
+def test_agg_source_is_in_the_build():
+    csrc = os.path.join(ROOT, "pg_cryogen_amd", "csrc")
+    txt = open(os.path.join(csrc, "agg.hip")).read()
+    assert re.search(r"__global__[^;{]*\bk_agg_block\s*\(", txt)
+    assert "asm" not in re.sub(r"/\*.*?\*/", "", txt, flags=re.S)                     # plain C++ only
+    assert re.search(r"^SRCS\s*:=.*\bagg\.hip\b", open(os.path.join(csrc, "Makefile")).read(), flags=re.M)
+    assert "launch_agg" in open(os.path.join(csrc, "kernels.h")).read()
+    # the walk exists once: both kernels' sources take it from the shared header
+    walk = open(os.path.join(csrc, "filter_walk.h")).read()
+    assert len(re.findall(r"\bwalk_tuple\s*\(const uint8_t", walk)) == 1
+    for name in ("agg.hip", "filter.hip"):
+        src = open(os.path.join(csrc, name)).read()
+        assert '#include "filter_walk.h"' in src and "walk_tuple<" in src and "t[22]" not in src, name   # no second header parse
+    hmk = open(os.path.join(ROOT, "pg_cryogen_amd", "host", "Makefile")).read()
+    assert re.search(r"^SRCS\s*:=.*\baggregate\.c\b", hmk, flags=re.M)
