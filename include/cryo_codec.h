@@ -514,6 +514,69 @@ int cryo_codec_agg_batch(cryo_codec *c, int method, const void *d_src, const uin
                          const uint32_t *d_src_size, uint32_t block_size, uint64_t n_blocks, const cryo_filter *f,
                          const cryo_agg *agg, cryo_agg_block *d_blocks, cryo_agg_cell *d_cells);
 
+/* ---- grouping a scan: stored streams -> decoded in handle workspace -> keys tested, matches partitioned by one or two integer
+ *      columns per block, integer columns reduced per group -> a row per block, a record and a few cells per group come back ----
+ * The query that follows the aggregate above: SELECT app_id, country, count(*), sum(revenue) FROM t WHERE ts >= a AND ts < b
+ * GROUP BY app_id, country.  Through the filter every matching tuple crosses PCIe and the host deforms it a second time; here each
+ * block's matches are grouped where the decoded block lies, and 32 bytes per block and 24 + 40 * ncols bytes per group and block
+ * leave the device (pg_cryogen_amd/host/group.h walks a relation with it).  The unit is the block for the aggregate's reason:
+ * one created_xid per block, so the caller tests each block's xid once and merges the groups of the visible blocks -- exact
+ * under any snapshot.  Merging the groups of different blocks is the caller's (a hash table on the key and the null bits).
+ * A call names n_blocks stored streams as cryo_codec_check_batch does, the filter's descriptor *f (unchanged), a group
+ * descriptor *grp: nby columns, each {att, type}, and an aggregate descriptor *agg (may be NULL): ncols columns.
+ *
+ * Descriptors.  CRYO_E_ARG when: *f breaks one of the filter's descriptor rules above; f->flags != 0; nby is 0 or above 2; a
+ * group column breaks a rule of an aggregate column above (att outside 1 .. f->natts; a type that is not a cryo_key_type; the
+ * column's attlen not the type's size, or its attalign below its attlen; rsv or rsv2 not zero); grp->rsv not zero; ncols above 4;
+ * with ncols > 0, anything cryo_codec_agg_batch refuses in *agg.  ncols == 0 is allowed here -- agg NULL, or agg->ncols 0 with
+ * agg->rsv 0 (agg->cols is not looked at) --: SELECT g, count(*) ... GROUP BY g needs no cell.  A column may be a group column,
+ * an aggregate column and a key column at once, and may be named twice.
+ *
+ * Per block (names as in the check's, the filter's and the aggregate's rules above):
+ *   CRYO_FETCH_STREAM (1), CRYO_FETCH_HEADER (2)   exactly the filter's; n_items = n_match = n_bad = n_groups = 0: the block has no
+ *                                                  group
+ *   otherwise (status 0, n_items = n) every item 1 .. n is examined with the filter's ITEM rule and TUPLE rule and the walk over
+ *   the columns 1 .. max(highest key column, highest group column, highest aggregate column) -- that far for every tuple and not a
+ *   column further: the aggregate's documented difference from the filter, the group columns included.  n_match and n_bad are the
+ *   aggregate's; a damaged item is in no group (a caller who sees n_bad > 0 reads that block through the filter).  OVERLAP is not
+ *   applied, because nothing is placed.
+ *
+ * Groups of a block.  The block's matches are partitioned by the tuple (null_1, value_1[, null_2, value_2]) of the group columns:
+ * value_j the signed little-endian integer of the column's type, sign-extended to 64 bits; null_j set when the column is NULL -- its
+ * bitmap bit is clear, or the column lies beyond the tuple's natts.  NULL is a value of its own, so NULLs form groups: (NULL, 5),
+ * (5, NULL) and (NULL, NULL) are three groups.  A block's groups are ordered ascending by column 1, then by column 2; values compare
+ * as signed 64-bit integers and NULL sorts after every value (PostgreSQL's ASC NULLS LAST).  The order is part of the contract:
+ * the output of a call is defined byte for byte.
+ *
+ * Results.  One cryo_group_block per block, in call order: n_groups the block's groups, first_group the sum of n_groups over the
+ * call's blocks before it (a block without groups carries the value at which the next block starts); rsv is 0.  One
+ * cryo_group_rec per group: the block's are records first_group .. first_group + n_groups - 1 of the call, in the order above.
+ * key[j] is value_j, or 0 when column j is NULL or j >= nby; bit j of nulls is set when group column j is NULL (no other bit is);
+ * n_rows is the number of the group's matches -- count(*) --, so a block's n_rows sum to its n_match.  Per group and aggregate
+ * column j one cryo_agg_cell, cell (first_group + g) * ncols + j for the block's group g: exactly the aggregate's cell (n of
+ * non-NULL values, min, max, the exact 128-bit sum; all zero when n == 0), over the group's matches instead of the block's.
+ * *total is the call's number of groups, counted in full even where group_cap cuts the writing off: no record at or beyond
+ * group_cap and no cell at or beyond group_cap * ncols is written.  A block has at most 290 groups, so group_cap >= 290 *
+ * n_blocks always suffices. */
+typedef struct { uint32_t nby, rsv; const cryo_agg_col *by; } cryo_group;
+#define CRYO_GROUP_MAX_BY 2u
+typedef struct { uint32_t status, n_items, n_match, n_bad; uint32_t n_groups, rsv; uint64_t first_group; } cryo_group_block; /* 32 bytes, one per block */
+typedef struct { int64_t key[2]; uint32_t n_rows, nulls; } cryo_group_rec;                                    /* 24 bytes, one per group */
+/* Device buffers.  The structs *f, *grp and *agg are host memory; f->atts, f->keys, grp->by and agg->cols are DEVICE arrays (4-byte
+ * / 8-byte / 8-byte / 8-byte aligned).  The host validates the descriptors before anything is queued: it reads the arrays back on
+ * the handle's stream (one wait for what the stream held before the call); from there on the call is asynchronous, with no host
+ * wait between its internal chunks.  d_blocks (n_blocks rows) 16-byte, d_groups (group_cap records) 8-byte, d_cells (group_cap *
+ * ncols cells; may be NULL only when ncols == 0) 8-byte, d_total (one u64, also where the running total lives between the call's
+ * internal chunks) 8-byte aligned: CRYO_E_ARG otherwise.  Decode as in the filter: the automatic routes, handle workspace, chunks
+ * within CRYO_OPT_WORKSPACE_MAX_BYTES (the workspace also holds a side area of 24 + 40 * ncols bytes per possible group of a chunk:
+ * up to 290 per block); the device pool is neither read nor filled, nothing counts in cryo_codec_counters.  CRYO_E_ARG as for
+ * cryo_codec_filter_batch (the same block-size rule), a bad descriptor, a null d_total, a null d_blocks, and a null d_groups or
+ * (with ncols > 0) a null d_cells with group_cap > 0; n_blocks == 0: CRYO_OK, *d_total = 0, nothing else is written. */
+int cryo_codec_group_batch(cryo_codec *c, int method, const void *d_src, const uint64_t *d_src_off,
+                           const uint32_t *d_src_size, uint32_t block_size, uint64_t n_blocks, const cryo_filter *f,
+                           const cryo_group *grp, const cryo_agg *agg, cryo_group_block *d_blocks, cryo_group_rec *d_groups,
+                           uint64_t group_cap, cryo_agg_cell *d_cells, uint64_t *d_total);
+
 /* ---- single block, HOST buffers: what cryo_compress()/cryo_decompress()
  *      (compression.c:125-159) call.  Synchronous: H2D, kernel, D2H. ---- */
 int cryo_codec_compress_block(cryo_codec *c, int method, int param,
@@ -612,6 +675,22 @@ int cryo_codec_filter_blocks(cryo_codec *c, int method, const void *const *h_src
 int cryo_codec_agg_blocks(cryo_codec *c, int method, const void *const *h_src, const uint32_t *h_src_size,
                           size_t n_blocks, size_t block_size, const cryo_filter *f, const cryo_agg *agg,
                           cryo_agg_block *h_blocks, cryo_agg_cell *h_cells);
+
+/* cryo_codec_group_batch on host buffers (stream i: h_src[i], h_src_size[i] bytes; f->atts, f->keys, grp->by and agg->cols are
+ * HOST arrays), synchronous.  Only compressed bytes and the descriptors travel towards the device, only rows, records and cells
+ * come back.
+ *   Upload   the streams staged and uploaded as by cryo_codec_agg_blocks, then the descriptors in a second copy: h2d_bytes grows
+ *            by another align16(4 * natts) + 16 * nkeys + 48 (the six column slots of the kernel).
+ *   Return   after the last chunk the rows of the whole call, then -- their number known from the last row -- exactly the call's
+ *            records and cells (two waits): d2h_bytes grows by exactly 32 * n_blocks + (24 + 40 * ncols) * *h_total.
+ *   Errors   more groups than group_cap: CRYO_E_DSTSIZE, and the outputs hold nothing to rely on (group_cap >= 290 * n_blocks
+ *            always fits).  CRYO_E_ARG as cryo_codec_group_batch (h_cells may be NULL only when ncols == 0); a bad descriptor is
+ *            refused before a device is touched.  n_blocks == 0: CRYO_OK, *h_total = 0.
+ * Returns CRYO_OK when the batch ran, whatever the rows say. */
+int cryo_codec_group_blocks(cryo_codec *c, int method, const void *const *h_src, const uint32_t *h_src_size,
+                            size_t n_blocks, size_t block_size, const cryo_filter *f, const cryo_group *grp,
+                            const cryo_agg *agg, cryo_group_block *h_blocks, cryo_group_rec *h_groups, size_t group_cap,
+                            cryo_agg_cell *h_cells, uint64_t *h_total);
 
 /* ---- device-resident block pool ("optional device-resident compressed/decompressed pool so
  *      repeated scans skip PCIe"; the reference's cache is host-only: cache.c:17-50).
@@ -713,6 +792,14 @@ int cryo_multi_filter_blocks(cryo_multi *m, int method, const void *const *h_src
 int cryo_multi_agg_blocks(cryo_multi *m, int method, const void *const *h_src, const uint32_t *h_src_size,
                           size_t n_blocks, size_t block_size, const cryo_filter *f, const cryo_agg *agg,
                           cryo_agg_block *h_blocks, cryo_agg_cell *h_cells);
+
+/* cryo_codec_group_blocks across the devices: block i -> handle i mod G.  The host lays each handle's records and cells back into
+ * call order and rebases first_group, so rows, records, cells and *h_total are byte for byte the single-handle call's and no
+ * per-handle regions are needed; more groups than group_cap: CRYO_E_DSTSIZE.  One handle: exactly cryo_codec_group_blocks. */
+int cryo_multi_group_blocks(cryo_multi *m, int method, const void *const *h_src, const uint32_t *h_src_size,
+                            size_t n_blocks, size_t block_size, const cryo_filter *f, const cryo_group *grp,
+                            const cryo_agg *agg, cryo_group_block *h_blocks, cryo_group_rec *h_groups, size_t group_cap,
+                            cryo_agg_cell *h_cells, uint64_t *h_total);
 
 /* ---- batch helpers used by staging, tests and the benchmark ---- */
 

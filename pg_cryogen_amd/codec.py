@@ -54,6 +54,11 @@ AGG_MAX_COLS = 4
 AGG_COL = np.dtype([("att", "<u2"), ("type", "u1"), ("rsv", "u1"), ("rsv2", "<u4")])                            # cryo_agg_col
 AGG_BLOCK = np.dtype([("status", "<u4"), ("n_items", "<u4"), ("n_match", "<u4"), ("n_bad", "<u4")])             # cryo_agg_block
 AGG_CELL = np.dtype([("n", "<u8"), ("min", "<i8"), ("max", "<i8"), ("sum_lo", "<u8"), ("sum_hi", "<i8")])       # cryo_agg_cell
+# the grouped scan (include/cryo_codec.h): a block's statuses are the aggregate's; cells are AGG_CELL, one per group and column
+GROUP_MAX_BY = 2
+GROUP_BLOCK = np.dtype([("status", "<u4"), ("n_items", "<u4"), ("n_match", "<u4"), ("n_bad", "<u4"),
+                        ("n_groups", "<u4"), ("rsv", "<u4"), ("first_group", "<u8")])                             # cryo_group_block
+GROUP_REC = np.dtype([("key", "<i8", (2,)), ("n_rows", "<u4"), ("nulls", "<u4")])                                # cryo_group_rec
 LZ4_PATH_AUTO, LZ4_PATH_RING, LZ4_PATH_INDEXED, LZ4_PATH_FEW_BLOCKS = 0, 1, 2, 3
 
 DIST_WIDE, DIST_NARROW, DIST_INT4, DIST_RANDOM, DIST_ZEROS = range(5)
@@ -83,6 +88,7 @@ ABI_SYMBOLS = [
     "cryo_codec_fetch_batch", "cryo_codec_fetch_blocks", "cryo_multi_fetch_blocks",
     "cryo_codec_filter_batch", "cryo_codec_filter_blocks", "cryo_multi_filter_blocks",
     "cryo_codec_agg_batch", "cryo_codec_agg_blocks", "cryo_multi_agg_blocks",
+    "cryo_codec_group_batch", "cryo_codec_group_blocks", "cryo_multi_group_blocks",
     "cryo_codec_lz4_index_cap", "cryo_codec_lz4_index_rows",
 ]
 
@@ -102,6 +108,11 @@ class CryoFilter(C.Structure):
 class CryoAgg(C.Structure):
     """cryo_agg: cols points to a device array for agg_batch, to a host array for agg_blocks"""
     _fields_ = [("ncols", C.c_uint32), ("rsv", C.c_uint32), ("cols", C.c_void_p)]
+
+
+class CryoGroup(C.Structure):
+    """cryo_group: by points to a device array for group_batch, to a host array for group_blocks"""
+    _fields_ = [("nby", C.c_uint32), ("rsv", C.c_uint32), ("by", C.c_void_p)]
 
 
 class TransferCounters(C.Structure):
@@ -196,6 +207,10 @@ def lib():
     L.cryo_codec_agg_batch.argtypes = [vp, i32, vp, vp, vp, u32, u64, fp, ap, vp, vp]
     L.cryo_codec_agg_blocks.argtypes = [vp, i32, vp, vp, sz, sz, fp, ap, vp, vp]
     L.cryo_multi_agg_blocks.argtypes = [vp, i32, vp, vp, sz, sz, fp, ap, vp, vp]
+    gp = C.POINTER(CryoGroup)
+    L.cryo_codec_group_batch.argtypes = [vp, i32, vp, vp, vp, u32, u64, fp, gp, ap, vp, vp, u64, vp, vp]
+    L.cryo_codec_group_blocks.argtypes = [vp, i32, vp, vp, sz, sz, fp, gp, ap, vp, vp, sz, vp, C.POINTER(u64)]
+    L.cryo_multi_group_blocks.argtypes = [vp, i32, vp, vp, sz, sz, fp, gp, ap, vp, vp, sz, vp, C.POINTER(u64)]
     L.cryo_codec_lz4_index_cap.argtypes = [u32]
     L.cryo_codec_lz4_index_cap.restype = u32
     L.cryo_codec_lz4_index_rows.argtypes = [vp, vp, vp, vp, u32, u64, i32, vp, vp]
@@ -318,6 +333,34 @@ def agg_blocks_call(fn, handle, chk, method, comps, block_size, desc, adesc):
     chk(fn(handle, method, src, szs, n, block_size, C.byref(desc[0]), C.byref(adesc[0]), rows.ctypes.data, cells.ctypes.data),
         "agg_blocks")
     return rows[:n], cells[:n]
+
+
+def group_desc(by):
+    """the group descriptor of a group call as a host array: by a list of (att, type) (att 1-based; type KEY_*).  Returns
+    (CryoGroup, by array); the struct points into the array, which the caller keeps alive"""
+    a = np.zeros(max(len(by), 1), AGG_COL)
+    for j, (att, typ) in enumerate(by):
+        a[j] = (att, typ, 0, 0)
+    return CryoGroup(len(by), 0, a.ctypes.data), a
+
+
+def group_blocks_call(fn, handle, chk, method, comps, block_size, desc, gdesc, adesc=None, group_cap=None):
+    """cryo_codec_group_blocks / cryo_multi_group_blocks (fn) on a list of host streams with the descriptors filter_desc,
+    group_desc and agg_desc made (adesc None: no aggregate column, a null agg and null cells); returns (rows: GROUP_BLOCK array
+    in call order, records: GROUP_REC array of the call's groups, cells: AGG_CELL array of shape (groups, ncols), total).
+    group_cap: the room in records (default: the worst case, 290 per block)"""
+    n, ncols = len(comps), adesc[0].ncols if adesc else 0
+    arrs = [np.ascontiguousarray(np.asarray(c, dtype=np.uint8)) for c in comps]
+    src = (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.nbytes else None for a in arrs])
+    szs = (C.c_uint32 * max(n, 1))(*[a.nbytes for a in arrs])
+    cap = 290 * n if group_cap is None else group_cap
+    rows = np.zeros(max(n, 1), GROUP_BLOCK)
+    recs = np.zeros(max(cap, 1), GROUP_REC)
+    cells = np.zeros((max(cap, 1), max(ncols, 1)), AGG_CELL)
+    total = C.c_uint64()
+    chk(fn(handle, method, src, szs, n, block_size, C.byref(desc[0]), C.byref(gdesc[0]), C.byref(adesc[0]) if adesc else None,
+           rows.ctypes.data, recs.ctypes.data, cap, cells.ctypes.data if ncols else None, C.byref(total)), "group_blocks")
+    return rows[:n], recs[:total.value], cells[:total.value, :ncols], total.value
 
 
 def cell_sum(cell):
@@ -551,6 +594,28 @@ class Codec:
         """aggregate host streams (desc: what filter_desc returns, adesc: what agg_desc returns); returns (rows, cells): rows an
         AGG_BLOCK array in call order, cells an AGG_CELL array of shape (n, ncols); cell_sum gives a cell's 128-bit sum"""
         return agg_blocks_call(self.L.cryo_codec_agg_blocks, self.h, self._chk, method, comps, block_size, desc, adesc)
+
+    def group_batch(self, method, d_src, d_off, d_sizes, block_size, n, natts, d_atts, nkeys, d_keys, nby, d_by, ncols, d_cols,
+                    d_blocks, d_groups, group_cap, d_cells, d_total):
+        """test the keys on every tuple of the n stored blocks, partition each block's matches by the nby columns d_by names and
+        reduce the ncols columns d_cols names per group (both AGG_COL; d_keys: FILTER_KEY, d_atts: FILTER_ATT, device arrays):
+        one GROUP_BLOCK row per block in d_blocks, one GROUP_REC per group in d_groups and ncols AGG_CELL per group in d_cells (at
+        most group_cap groups are written), the call's number of groups in d_total (u64).  ncols 0: d_cols and d_cells may be
+        None.  Asynchronous once the descriptors are read back."""
+        f = CryoFilter(natts, nkeys, 0, 0, d_atts.ptr if d_atts else None, d_keys.ptr if d_keys else None)
+        g = CryoGroup(nby, 0, d_by.ptr if d_by else None)
+        a = CryoAgg(ncols, 0, d_cols.ptr if d_cols else None)
+        self._chk(self.L.cryo_codec_group_batch(self.h, method, d_src.ptr, d_off.ptr, d_sizes.ptr, block_size, n, C.byref(f),
+                                                C.byref(g), C.byref(a), d_blocks.ptr if d_blocks else None,
+                                                d_groups.ptr if d_groups else None, group_cap, d_cells.ptr if d_cells else None,
+                                                d_total.ptr if d_total else None), "group_batch")
+
+    def group_blocks(self, method, comps, block_size, desc, gdesc, adesc=None, group_cap=None):
+        """group host streams (desc: what filter_desc returns, gdesc: group_desc, adesc: agg_desc or None); returns (rows,
+        records, cells, total): block i's groups are records[rows[i]["first_group"]:][:rows[i]["n_groups"]], cells has one row
+        per group and one column per aggregate column; cell_sum gives a cell's 128-bit sum"""
+        return group_blocks_call(self.L.cryo_codec_group_blocks, self.h, self._chk, method, comps, block_size, desc, gdesc, adesc,
+                                 group_cap)
 
     def last_verify_failure(self):
         """(block, first mismatch) that made the last host-buffer compress call fail verification, or None"""

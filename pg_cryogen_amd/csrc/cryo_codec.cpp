@@ -1247,20 +1247,25 @@ struct AggIo {
 
 /* the aggregate's descriptor rules (include/cryo_codec.h); every array is host memory here.  *max_att: the highest key or
  * aggregate column */
+/* the rule of one aggregate (or group) column; raises *max_att to it */
+static bool agg_col_ok(const cryo_filter *f, const cryo_att *atts, const cryo_agg_col &q, uint32_t *max_att)
+{
+    if (q.rsv != 0 || q.rsv2 != 0 || q.att == 0 || q.att > f->natts) return false;
+    if (q.type < CRYO_KEY_INT2 || q.type > CRYO_KEY_INT8) return false;
+    const int size = q.type == CRYO_KEY_INT2 ? 2 : q.type == CRYO_KEY_INT4 ? 4 : 8;
+    const cryo_att &a = atts[q.att - 1];
+    if (a.attlen != size || a.attalign < size) return false;
+    if (q.att > *max_att) *max_att = q.att;
+    return true;
+}
+
 static bool agg_desc_ok(const cryo_filter *f, const cryo_att *atts, const cryo_scan_key *keys, const cryo_agg *agg,
                         const cryo_agg_col *cols, uint32_t *max_att)
 {
     if (!filter_desc_ok(f, atts, keys, max_att)) return false;
     if (f->flags != 0 || !agg || agg->ncols == 0 || agg->ncols > CRYO_AGG_MAX_COLS || agg->rsv != 0 || !cols) return false;
-    for (uint32_t j = 0; j < agg->ncols; j++) {
-        const cryo_agg_col &q = cols[j];
-        if (q.rsv != 0 || q.rsv2 != 0 || q.att == 0 || q.att > f->natts) return false;
-        if (q.type < CRYO_KEY_INT2 || q.type > CRYO_KEY_INT8) return false;
-        const int size = q.type == CRYO_KEY_INT2 ? 2 : q.type == CRYO_KEY_INT4 ? 4 : 8;
-        const cryo_att &a = atts[q.att - 1];
-        if (a.attlen != size || a.attalign < size) return false;
-        if (q.att > *max_att) *max_att = q.att;
-    }
+    for (uint32_t j = 0; j < agg->ncols; j++)
+        if (!agg_col_ok(f, atts, cols[j], max_att)) return false;
     return true;
 }
 
@@ -1275,6 +1280,77 @@ static int agg_pass(cryo_codec *c, int method, const uint8_t *d_src, const uint6
     ps.run = [&](const DecodeChunk &ch) -> int {
         HIP_TRY(c, cryo::launch_agg(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.d_atts, io.d_keys, io.nkeys, io.d_cols,
                                     io.ncols, io.max_att, (uint4 *)(io.d_blocks + ch.lo), io.d_cells + ch.lo * io.ncols));
+        return CRYO_OK;
+    };
+    const int rc = decode_pass(c, method, B, n, ps);
+    c->ctr = keep;
+    return rc;
+}
+
+/* ---- the grouped scan ----
+ * The shared decode loop over the caller's stream table; on every decoded chunk group.hip tests the keys on every tuple, groups
+ * each block's matches in LDS and writes the groups to a side area, places the blocks behind the running total -- which stays in
+ * device memory (*d_total) from chunk to chunk -- and copies records and cells to their places in the call's output.  Per chunk
+ * (own) each block has 24 + 40 * ncols bytes per possible group of side area; the pass's fixed bytes hold the kernel's six column
+ * slots when the caller's descriptors come as two arrays.  The pass waits for nothing.  Its decodes count nowhere. */
+namespace {
+struct GroupIo {
+    const void *d_atts = nullptr, *d_keys = nullptr; /* device */
+    const void *d_by = nullptr, *d_cols = nullptr;   /* device: the caller's two arrays, or */
+    const void *d_slots = nullptr;                   /* device: the six slots laid out already */
+    uint32_t nkeys = 0, nby = 0, ncols = 0, max_att = 0;
+    cryo_group_block *d_blocks = nullptr; /* device: n rows */
+    cryo_group_rec *d_groups = nullptr;   /* device: group_cap records */
+    cryo_agg_cell *d_cells = nullptr;     /* device: group_cap * ncols cells */
+    uint64_t group_cap = 0;
+    uint64_t *d_total = nullptr;          /* device: the running total */
+};
+} // namespace
+
+/* the grouping's descriptor rules (include/cryo_codec.h); every array is host memory here.  *max_att: the highest key, group or
+ * aggregate column; *ncols: the aggregate columns (0 with a null agg) */
+static bool group_desc_ok(const cryo_filter *f, const cryo_att *atts, const cryo_scan_key *keys, const cryo_group *grp,
+                          const cryo_agg_col *by, const cryo_agg *agg, const cryo_agg_col *cols, uint32_t *max_att, uint32_t *ncols)
+{
+    *ncols = 0;
+    if (!filter_desc_ok(f, atts, keys, max_att)) return false;
+    if (f->flags != 0 || !grp || grp->nby == 0 || grp->nby > CRYO_GROUP_MAX_BY || grp->rsv != 0 || !by) return false;
+    for (uint32_t j = 0; j < grp->nby; j++)
+        if (!agg_col_ok(f, atts, by[j], max_att)) return false;
+    if (!agg) return true;
+    if (agg->ncols > CRYO_AGG_MAX_COLS || agg->rsv != 0 || (agg->ncols > 0 && !cols)) return false;
+    for (uint32_t j = 0; j < agg->ncols; j++)
+        if (!agg_col_ok(f, atts, cols[j], max_att)) return false;
+    *ncols = agg->ncols;
+    return true;
+}
+
+static int group_pass(cryo_codec *c, int method, const uint8_t *d_src, const uint64_t *d_src_off, const uint32_t *d_src_size,
+                      uint32_t B, uint64_t n, const GroupIo &io)
+{
+    static_assert(sizeof(cryo_group_block) == 2 * sizeof(uint4) && sizeof(cryo_group_rec) == 24 && sizeof(cryo_group) == 16,
+                  "the grouping's records are the kernels'");
+    const cryo_codec_counters keep = c->ctr;
+    const uint64_t S = cryo::filter_side_stride(B);
+    DecodePass ps;
+    ps.d_comp = d_src; ps.d_comp_off = d_src_off; ps.d_comp_size = d_src_size;
+    ps.fixed = 256u;                                                 /* the six column slots */
+    ps.own_per_block = S * (sizeof(cryo_group_rec) + io.ncols * sizeof(cryo_agg_cell)); /* the side area */
+    ps.run = [&](const DecodeChunk &ch) -> int {
+        const void *slots = io.d_slots ? io.d_slots : ch.fixed;
+        if (ch.lo == 0) {
+            HIP_TRY(c, hipMemsetAsync(io.d_total, 0, sizeof(uint64_t), c->stream));
+            if (!io.d_slots) {
+                HIP_TRY(c, hipMemsetAsync(ch.fixed, 0, 48, c->stream));
+                HIP_TRY(c, hipMemcpyAsync(ch.fixed, io.d_by, io.nby * sizeof(cryo_agg_col), hipMemcpyDeviceToDevice, c->stream));
+                if (io.ncols)
+                    HIP_TRY(c, hipMemcpyAsync(ch.fixed + 16, io.d_cols, io.ncols * sizeof(cryo_agg_col), hipMemcpyDeviceToDevice, c->stream));
+            }
+        }
+        uint8_t *side_rec = ch.own, *side_cell = ch.own + ch.K * S * sizeof(cryo_group_rec);
+        HIP_TRY(c, cryo::launch_group(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.d_atts, io.d_keys, io.nkeys, slots, io.nby,
+                                      io.ncols, io.max_att, (uint4 *)(io.d_blocks + ch.lo), side_rec, side_cell, io.d_total,
+                                      io.d_groups, io.d_cells, io.group_cap, c->lz4_opts.cus));
         return CRYO_OK;
     };
     const int rc = decode_pass(c, method, B, n, ps);
@@ -1511,6 +1587,45 @@ int cryo_codec_agg_batch(cryo_codec *c, int method, const void *d_src, const uin
         io.d_atts = f->atts; io.d_keys = f->keys; io.d_cols = agg->cols; io.nkeys = f->nkeys; io.ncols = agg->ncols;
         io.d_blocks = d_blocks; io.d_cells = d_cells;
         return agg_pass(c, method, (const uint8_t *)d_src, d_src_off, d_src_size, block_size, n_blocks, io);
+    });
+}
+
+int cryo_codec_group_batch(cryo_codec *c, int method, const void *d_src, const uint64_t *d_src_off, const uint32_t *d_src_size,
+                           uint32_t block_size, uint64_t n_blocks, const cryo_filter *f, const cryo_group *grp, const cryo_agg *agg,
+                           cryo_group_block *d_blocks, cryo_group_rec *d_groups, uint64_t group_cap, cryo_agg_cell *d_cells,
+                           uint64_t *d_total)
+{
+    DevGuard dev_(c);
+    if (!c || !method_ok(method) || !check_block_size_ok(block_size)) return CRYO_E_ARG;
+    if (!d_total || ((uintptr_t)d_total & 7u) != 0) return CRYO_E_ARG;
+    if (!f || f->natts == 0 || f->natts > CRYO_FILTER_MAX_ATTS || f->nkeys > CRYO_FILTER_MAX_KEYS || !f->atts ||
+        (f->nkeys > 0 && !f->keys) || ((uintptr_t)f->atts & 3u) != 0 || ((uintptr_t)f->keys & 7u) != 0)
+        return CRYO_E_ARG;
+    if (!grp || grp->nby == 0 || grp->nby > CRYO_GROUP_MAX_BY || !grp->by || ((uintptr_t)grp->by & 7u) != 0) return CRYO_E_ARG;
+    const uint32_t ncols = agg ? agg->ncols : 0u;
+    if (ncols > CRYO_AGG_MAX_COLS || (ncols > 0 && (!agg->cols || ((uintptr_t)agg->cols & 7u) != 0))) return CRYO_E_ARG;
+    if ((((uintptr_t)d_groups | (uintptr_t)d_cells) & 7u) != 0 || ((uintptr_t)d_blocks & 15u) != 0) return CRYO_E_ARG;
+    if (n_blocks > 0 && (!d_src || !d_src_off || !d_src_size || !d_blocks || (group_cap > 0 && (!d_groups || (ncols > 0 && !d_cells)))))
+        return CRYO_E_ARG;
+    return guarded([&] {
+        /* the descriptors live in device memory: read back and checked before anything is queued */
+        std::vector<cryo_att> atts(f->natts);
+        std::vector<cryo_scan_key> keys(f->nkeys ? f->nkeys : 1);
+        std::vector<cryo_agg_col> by(grp->nby), cols(ncols ? ncols : 1);
+        HIP_TRY(c, hipMemcpyAsync(atts.data(), f->atts, f->natts * sizeof(cryo_att), hipMemcpyDeviceToHost, c->stream));
+        if (f->nkeys)
+            HIP_TRY(c, hipMemcpyAsync(keys.data(), f->keys, f->nkeys * sizeof(cryo_scan_key), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(by.data(), grp->by, grp->nby * sizeof(cryo_agg_col), hipMemcpyDeviceToHost, c->stream));
+        if (ncols) HIP_TRY(c, hipMemcpyAsync(cols.data(), agg->cols, ncols * sizeof(cryo_agg_col), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        GroupIo io;
+        if (!group_desc_ok(f, atts.data(), keys.data(), grp, by.data(), agg, cols.data(), &io.max_att, &io.ncols)) return (int)CRYO_E_ARG;
+        HIP_TRY(c, hipMemsetAsync(d_total, 0, sizeof(uint64_t), c->stream));
+        if (n_blocks == 0) return (int)CRYO_OK;
+        io.d_atts = f->atts; io.d_keys = f->keys; io.d_by = grp->by; io.d_cols = ncols ? agg->cols : nullptr;
+        io.nkeys = f->nkeys; io.nby = grp->nby;
+        io.d_blocks = d_blocks; io.d_groups = d_groups; io.d_cells = d_cells; io.group_cap = group_cap; io.d_total = d_total;
+        return group_pass(c, method, (const uint8_t *)d_src, d_src_off, d_src_size, block_size, n_blocks, io);
     });
 }
 
@@ -2292,6 +2407,106 @@ int cryo_codec_agg_blocks(cryo_codec *c, int method, const void *const *h_src, c
     });
 }
 
+/* what every host-buffer group call checks before a device is touched */
+static int group_blocks_args(int method, size_t block_size, const cryo_filter *f, const cryo_group *grp, const cryo_agg *agg,
+                             uint64_t *h_total, uint32_t *max_att, uint32_t *ncols)
+{
+    if (!method_ok(method) || !check_block_size_ok(block_size) || !h_total) return CRYO_E_ARG;
+    if (!f || !grp || !group_desc_ok(f, f->atts, f->keys, grp, grp->by, agg, agg ? agg->cols : nullptr, max_att, ncols))
+        return CRYO_E_ARG;
+    return CRYO_OK;
+}
+
+/* the grouped scan of n streams given by pointer: the streams staged and uploaded as the aggregate's (stage_streams), the
+ * descriptors -- the two column arrays as the kernel's six slots -- from the same pinned buffer in a second copy, both into place
+ * before the first decode; the rows of the whole call come back after the last chunk (group_pass waits for nothing), then -- their
+ * number known from the last row -- its records and cells */
+static int group_blocks_impl(cryo_codec *c, int method, const void *const *h_src, const uint32_t *h_src_size, size_t n,
+                             size_t block_size, const cryo_filter *f, const cryo_group *grp, const cryo_agg *agg,
+                             cryo_group_block *h_blocks, cryo_group_rec *h_groups, size_t group_cap, cryo_agg_cell *h_cells,
+                             uint64_t *h_total)
+{
+    uint32_t max_att = 0, ncols = 0;
+    int rc = group_blocks_args(method, block_size, f, grp, agg, h_total, &max_att, &ncols);
+    if (rc != CRYO_OK || !c) return CRYO_E_ARG;
+    DevGuard dev_(c);
+    *h_total = 0;
+    if (n == 0) return CRYO_OK;
+    if (!h_src || !h_src_size || !h_blocks || (group_cap > 0 && (!h_groups || (ncols > 0 && !h_cells)))) return CRYO_E_ARG;
+    ScopedLocalCpus numa_(n * block_size >= ((size_t)8 << 20) ? c : nullptr);
+    /* the descriptors and the results: [atts 4 x natts][keys 16 x nkeys][slots 8 x 6][total 16][rows 32 x n][records 24 x cap]
+     * [cells 40 x cap x ncols], each part 8-byte aligned, the rows 16; cap: what the caller has room for, at most the worst case */
+    const size_t worst = n * (size_t)cryo::filter_side_stride((uint32_t)block_size);
+    const size_t cap = group_cap < worst ? group_cap : worst;
+    const size_t t_atts = 0, t_keys = ((size_t)f->natts * 4 + 15) & ~(size_t)15, t_slots = t_keys + (size_t)f->nkeys * 16;
+    const size_t t_total = t_slots + 48, t_rows = t_total + 16;
+    const size_t rows_bytes = n * sizeof(cryo_group_block), t_recs = t_rows + rows_bytes, t_cells = t_recs + cap * sizeof(cryo_group_rec);
+    size_t streams = (n * 12 + 63) & ~(size_t)63; /* what stage_streams lays out in the pinned buffer */
+    for (size_t i = 0; i < n; i++) streams += ((size_t)h_src_size[i] + 15) & ~(size_t)15;
+    const size_t p_tbl = (streams + 64 + 15) & ~(size_t)15;
+    /* every allocation of the call before the uploads are queued; the pinned buffer at its final size, so that the staging of
+     * the streams leaves it where it is */
+    if ((rc = ensure_pinned(c, p_tbl + t_total)) != CRYO_OK) return rc;
+    if ((rc = ensure(c, &c->hb_meta, &c->hb_meta_cap, t_cells + cap * ncols * sizeof(cryo_agg_cell) + 64)) != CRYO_OK) return rc;
+    StagedStreams sg;
+    if ((rc = stage_streams(c, h_src, h_src_size, n, sg, true)) != CRYO_OK) return rc;
+    uint8_t *pin = (uint8_t *)c->pin + p_tbl;
+    memset(pin, 0, t_total);
+    memcpy(pin + t_atts, f->atts, (size_t)f->natts * 4);
+    if (f->nkeys) memcpy(pin + t_keys, f->keys, (size_t)f->nkeys * 16);
+    memcpy(pin + t_slots, grp->by, (size_t)grp->nby * 8);
+    if (ncols) memcpy(pin + t_slots + 16, agg->cols, (size_t)ncols * 8);
+    HIP_TRY(c, hipMemcpyAsync(c->hb_meta, pin, t_total, hipMemcpyHostToDevice, c->stream));
+    c->xfer_ctr.h2d_bytes += t_total;
+    GroupIo io;
+    io.d_atts = c->hb_meta + t_atts; io.d_keys = c->hb_meta + t_keys; io.d_slots = c->hb_meta + t_slots;
+    io.nkeys = f->nkeys; io.nby = grp->nby; io.ncols = ncols; io.max_att = max_att;
+    io.d_total = (uint64_t *)(c->hb_meta + t_total);
+    io.d_blocks = (cryo_group_block *)(c->hb_meta + t_rows);
+    io.d_groups = (cryo_group_rec *)(c->hb_meta + t_recs);
+    io.d_cells = (cryo_agg_cell *)(c->hb_meta + t_cells);
+    io.group_cap = cap;
+    rc = group_pass(c, method, c->hb_src, (const uint64_t *)(c->hb_src + sg.o_off), (const uint32_t *)(c->hb_src + sg.o_sz),
+                    (uint32_t)block_size, n, io);
+    if (rc == CRYO_OK) {
+        const hipError_t e = hipMemcpyAsync(h_blocks, io.d_blocks, rows_bytes, hipMemcpyDeviceToHost, c->stream);
+        if (e != hipSuccess) rc = fail(c, e, "hipMemcpyAsync of rows");
+        else c->xfer_ctr.d2h_bytes += rows_bytes;
+    }
+    /* nothing in flight from the pinned buffer or into the caller's memory afterwards */
+    hipError_t es = hipStreamSynchronize(c->stream);
+    if (rc == CRYO_OK && es != hipSuccess) rc = fail(c, es, "hipStreamSynchronize");
+    if (rc != CRYO_OK) return rc;
+    const cryo_group_block &last = h_blocks[n - 1];
+    if (last.first_group > worst || last.n_groups > worst - last.first_group) return CRYO_E_HIP; /* not a placement */
+    const uint64_t total = last.first_group + last.n_groups;
+    *h_total = total;
+    if (total > group_cap) return CRYO_E_DSTSIZE;
+    if (total) {
+        hipError_t e = hipMemcpyAsync(h_groups, io.d_groups, total * sizeof(cryo_group_rec), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && ncols)
+            e = hipMemcpyAsync(h_cells, io.d_cells, total * ncols * sizeof(cryo_agg_cell), hipMemcpyDeviceToHost, c->stream);
+        if (e != hipSuccess) rc = fail(c, e, "hipMemcpyAsync of records and cells");
+        else c->xfer_ctr.d2h_bytes += total * (sizeof(cryo_group_rec) + ncols * sizeof(cryo_agg_cell));
+        es = hipStreamSynchronize(c->stream);
+        if (rc == CRYO_OK && es != hipSuccess) rc = fail(c, es, "hipStreamSynchronize");
+    }
+    return rc;
+}
+
+int cryo_codec_group_blocks(cryo_codec *c, int method, const void *const *h_src, const uint32_t *h_src_size, size_t n,
+                            size_t block_size, const cryo_filter *f, const cryo_group *grp, const cryo_agg *agg,
+                            cryo_group_block *h_blocks, cryo_group_rec *h_groups, size_t group_cap, cryo_agg_cell *h_cells,
+                            uint64_t *h_total)
+{
+    return guarded([&] {
+        const int rc = group_blocks_impl(c, method, h_src, h_src_size, n, block_size, f, grp, agg, h_blocks, h_groups, group_cap,
+                                         h_cells, h_total);
+        if (c) ws_trim_after_call(c);
+        return rc;
+    });
+}
+
 } /* extern "C" */
 
 /* ---- device-resident block pool ---- */
@@ -2882,6 +3097,62 @@ int cryo_multi_agg_blocks(cryo_multi *m, int method, const void *const *h_src, c
             return (int)CRYO_OK;
         });
     });
+}
+
+/* block i -> handle i mod G; every handle groups its share into buffers of its own, then the host lays records and cells back
+ * into call order and rebases first_group: the single-handle call's output, byte for byte */
+int cryo_multi_group_blocks(cryo_multi *m, int method, const void *const *h_src, const uint32_t *h_src_size, size_t n,
+                            size_t block_size, const cryo_filter *f, const cryo_group *grp, const cryo_agg *agg,
+                            cryo_group_block *h_blocks, cryo_group_rec *h_groups, size_t group_cap, cryo_agg_cell *h_cells,
+                            uint64_t *h_total)
+{
+    uint32_t max_att = 0, nc = 0;
+    if (!m || m->h.empty() || group_blocks_args(method, block_size, f, grp, agg, h_total, &max_att, &nc) != CRYO_OK) return CRYO_E_ARG;
+    const size_t G = m->h.size();
+    if (G == 1)
+        return cryo_codec_group_blocks(m->h[0], method, h_src, h_src_size, n, block_size, f, grp, agg, h_blocks, h_groups, group_cap,
+                                       h_cells, h_total);
+    *h_total = 0;
+    if (n == 0) return CRYO_OK;
+    if (!h_src || !h_src_size || !h_blocks || (group_cap > 0 && (!h_groups || (nc > 0 && !h_cells)))) return CRYO_E_ARG;
+    const size_t S = cryo::filter_side_stride((uint32_t)block_size);
+    std::vector<std::vector<cryo_group_block>> rows(G);
+    std::vector<std::vector<cryo_group_rec>> recs(G);
+    std::vector<std::vector<cryo_agg_cell>> cells(G);
+    std::vector<uint64_t> tot(G, 0);
+    const int rc = guarded([&] {
+        return multi_run(m, n, [&](size_t g, const std::vector<size_t> &idx) {
+            std::vector<const void *> src(idx.size());
+            std::vector<uint32_t> sz(idx.size());
+            for (size_t k = 0; k < idx.size(); k++) { src[k] = h_src[idx[k]]; sz[k] = h_src_size[idx[k]]; }
+            /* a share's room: its worst case, or the whole call's room when that is less -- a share that needs more than the
+             * call has room for fails the call as the single handle would */
+            const size_t cap = idx.size() * S < group_cap ? idx.size() * S : group_cap;
+            rows[g].resize(idx.size());
+            recs[g].resize(cap ? cap : 1);
+            cells[g].resize(cap * nc ? cap * nc : 1);
+            return group_blocks_impl(m->h[g], method, src.data(), sz.data(), idx.size(), block_size, f, grp, agg, rows[g].data(),
+                                     recs[g].data(), cap, cells[g].data(), &tot[g]);
+        });
+    });
+    uint64_t total = 0;
+    for (size_t g = 0; g < G; g++) total += tot[g];
+    if (rc != CRYO_OK) return rc;
+    *h_total = total;
+    if (total > group_cap) return CRYO_E_DSTSIZE;
+    uint64_t at = 0;
+    for (size_t i = 0; i < n; i++) {
+        const size_t g = i % G, k = i / G;
+        cryo_group_block row = rows[g][k];
+        if (row.n_groups) {
+            memcpy(h_groups + at, &recs[g][row.first_group], row.n_groups * sizeof(cryo_group_rec));
+            if (nc) memcpy(h_cells + at * nc, &cells[g][row.first_group * nc], row.n_groups * nc * sizeof(cryo_agg_cell));
+        }
+        row.first_group = at;
+        at += row.n_groups;
+        h_blocks[i] = row;
+    }
+    return CRYO_OK;
 }
 
 int cryo_multi_decompress_blocks_keyed(cryo_multi *m, int method, const uint64_t *keys, const void *const *h_src,

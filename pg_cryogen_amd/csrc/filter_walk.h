@@ -1,8 +1,10 @@
 /*
- * filter_walk.h -- the walk over one heap tuple that the scan filter (filter.hip) and the scan aggregate (agg.hip) share: the
- * TUPLE rule, the column walk and the key tests of include/cryo_codec.h ("filtering a scan"), and -- for the aggregate -- the
- * capture of up to four column values as the walk passes them ("aggregating a scan").  One statement of the walk: the filter
- * instantiates it without capture, and the capture costs it nothing (the same registers, no scratch).
+ * filter_walk.h -- the walk over one heap tuple that the scan filter (filter.hip), the scan aggregate (agg.hip) and the grouped
+ * scan (group.hip) share: the TUPLE rule, the column walk and the key tests of include/cryo_codec.h ("filtering a scan"), and --
+ * for the aggregate and the grouping -- the capture of column values as the walk passes them ("aggregating a scan", "grouping a
+ * scan").  One statement of the walk: the filter instantiates it without capture, and the capture costs it nothing (the same
+ * registers, no scratch).  The number of capture slots is a template parameter: four for the aggregate, six for the grouping (two
+ * group columns and four aggregate columns).
  */
 #pragma once
 #include <hip/hip_runtime.h>
@@ -20,9 +22,11 @@ struct FilterKey { uint16_t att; uint8_t type, op; uint32_t rsv; int64_t value; 
 struct AggCol { uint16_t att; uint8_t type, rsv; uint32_t rsv2; };                     /* cryo_agg_col */
 static_assert(sizeof(FilterAtt) == 4 && sizeof(FilterKey) == 16 && sizeof(AggCol) == 8, "the descriptor's layout is the header's");
 
-/* what the walk captured of a tuple: v[j] the value of aggregate column j, valid when bit j of `has` is set (the column is not
- * NULL).  Only a tuple whose verdict is 0 has a capture worth reading. */
-struct WalkCapture { int64_t v[kAggMaxCols]; uint32_t has; };
+/* what the walk captured of a tuple: v[j] the value of captured column j, valid when bit j of `has` is set (the column is not
+ * NULL).  Only a tuple whose verdict is 0 has a capture worth reading.  SLOTS: how many columns a kernel captures at most. */
+template <uint32_t SLOTS> struct WalkCaptureN { int64_t v[SLOTS]; uint32_t has; };
+using WalkCapture = WalkCaptureN<kAggMaxCols>; /* the aggregate's */
+template <class T> struct WalkPlain { using type = T; }; /* keeps SLOTS out of deduction: the filter passes a null capture */
 
 __device__ inline bool filter_compare(uint32_t op, int64_t v, int64_t k)
 {
@@ -47,12 +51,14 @@ __device__ inline int64_t walk_value(const uint8_t *__restrict__ p, int32_t attl
 
 /* The verdict on one tuple of len bytes at t (8-byte aligned): 0 a match, kFilterNoMatch, or kFilterTuple.  `live` is false in
  * lanes without a tuple: they make the same trips and load nothing.  Invariant of the walk: hoff + o <= len.  CAPTURE: the walk
- * also notes the value of each of the ncols columns cols[] names (their att <= max_att, attlen the type's size and attalign at
- * least that: the aggregate's argument rule) in *cap; cols is read at addresses that depend on the loop counters only. */
-template <bool CAPTURE>
+ * also notes the value of each of the ncols <= SLOTS columns cols[] names (their att <= max_att, attlen the type's size and
+ * attalign at least that: the aggregate's argument rule; an att of 0 names no column) in *cap; cols is read at addresses that
+ * depend on the loop counters only. */
+template <bool CAPTURE, uint32_t SLOTS = kAggMaxCols>
 __device__ inline uint32_t walk_tuple(const uint8_t *__restrict__ t, uint32_t len, bool live, const FilterAtt *__restrict__ atts,
                                       const FilterKey *__restrict__ keys, uint32_t nkeys, uint32_t max_att,
-                                      const AggCol *__restrict__ cols, uint32_t ncols, WalkCapture *cap)
+                                      const AggCol *__restrict__ cols, uint32_t ncols,
+                                      typename WalkPlain<WalkCaptureN<SLOTS>>::type *cap)
 {
     uint32_t tnatts = 0, hoff = 0;
     bool hasnull = false, bad = false, pass = true;
@@ -116,7 +122,7 @@ __device__ inline uint32_t walk_tuple(const uint8_t *__restrict__ t, uint32_t le
         }
         if (CAPTURE) {
 #pragma unroll
-            for (uint32_t j = 0; j < kAggMaxCols; j++) { /* unrolled: v[j] stays in registers */
+            for (uint32_t j = 0; j < SLOTS; j++) { /* unrolled: v[j] stays in registers */
                 if (j >= ncols || cols[j].att != col) continue; /* uniform */
                 /* as for a key: the column's [pos, pos + attlen) lies below len, aligned by the aggregate's argument rule */
                 cap->v[j] = val ? walk_value(t + pos, a.attlen) : 0;

@@ -266,6 +266,19 @@ hipError_t launch_agg(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, 
                       const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_cols,
                       uint32_t ncols, uint32_t max_att, uint4 *d_blocks, void *d_cells);
 
+/* the grouped scan (group.hip) on one decoded chunk of cnt blocks (laid out as for launch_filter): k_group_block,
+ * k_group_offsets, k_group_copy.  The descriptors are validated by the caller (cryo_codec.cpp, group_desc_ok): d_atts and d_keys as
+ * for launch_filter; d_slots six entries of cryo_agg_col (device memory, 8-byte aligned): the nby (1 .. 2) group columns in
+ * entries 0 .. 1, the ncols (0 .. 4) aggregate columns in entries 2 .. 5, every unused entry all zero; max_att the highest key,
+ * group or aggregate column.  d_blocks: the chunk's rows (cryo_group_block, 16-byte aligned).  Scratch: d_side_rec 24 bytes and
+ * d_side_cell 40 * ncols bytes per possible group (cnt * filter_side_stride(block_size) groups; both 8-byte aligned).
+ * *d_running: the groups before the chunk in, after it out.  The chunk's records go to d_rec and its cells to d_cells (8-byte
+ * aligned) at first_group within the call; nothing at or beyond group_cap groups is written.  cus as for launch_fetch. */
+hipError_t launch_group(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
+                        const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,
+                        uint32_t nby, uint32_t ncols, uint32_t max_att, uint4 *d_blocks, void *d_side_rec, void *d_side_cell,
+                        uint64_t *d_running, void *d_rec, void *d_cells, uint64_t group_cap, int cus);
+
 } // namespace cryo
 
 #define CRYO_WAVE 64

@@ -36,6 +36,9 @@ FILTER_BLOCKS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_
                                C.POINTER(C.c_uint64))
 AGG_BLOCKS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_size_t,
                             C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+GROUP_BLOCKS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_size_t,
+                              C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                              C.POINTER(C.c_uint64))
 CRYO_CHECK_CHAIN, CRYO_CHECK_METHOD = 16, 17   # host-only reasons of check.h (beside cryo_check_reason 0..4)
 
 
@@ -77,6 +80,12 @@ class CryoCodecAggOps(C.Structure):
     """host/compression.h's one-function table of the scan aggregate (AGG_BLOCKS_FN), bound beside a CryoCodecOps double with
     cryo_host_set_agg_ops (test build)"""
     _fields_ = [("agg_blocks", AGG_BLOCKS_FN)]
+
+
+class CryoCodecGroupOps(C.Structure):
+    """host/compression.h's one-function table of the grouped scan (GROUP_BLOCKS_FN), bound beside a CryoCodecOps double with
+    cryo_host_set_group_ops (test build)"""
+    _fields_ = [("group_blocks", GROUP_BLOCKS_FN)]
 
 
 class CryoRel(C.Structure):
@@ -136,7 +145,23 @@ class CryoAggTotals(C.Structure):
                                           "bytes_back")] + [("cells", CryoAggCell * 4)]
 
 
+class CryoGroupRec(C.Structure):
+    """cryo_group_rec (include/cryo_codec.h)"""
+    _fields_ = [("key", C.c_int64 * 2), ("n_rows", C.c_uint32), ("nulls", C.c_uint32)]
+
+
+class CryoGroupBlock(C.Structure):
+    _fields_ = [("block", C.c_uint32), ("created_xid", C.c_uint32), ("n_items", C.c_uint32), ("n_match", C.c_uint32),
+                ("n_bad", C.c_uint32), ("n_groups", C.c_uint32), ("recs", C.POINTER(CryoGroupRec)), ("cells", C.POINTER(CryoAggCell))]
+
+
+class CryoGroupTotals(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("blocks", "empty_pages", "items", "matches", "bad", "reports", "codec_calls",
+                                          "bytes_back", "groups")]
+
+
 AGG_BLOCK_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(CryoAggBlock))
+GROUP_BLOCK_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(CryoGroupBlock))
 FETCH_TUPLE_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(CryoFetchedTuple))
 FETCH_REPORT_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(CryoFetchReport))
 RECOMPRESS_MOVED_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32)
@@ -188,6 +213,11 @@ def lib():
         L.cryo_host_set_agg_ops.restype = None
         L.cryo_aggregate_set_window.argtypes = [i32, sz]
         L.cryo_aggregate_set_window.restype = None
+    if hasattr(L, "cryo_host_set_group_ops"):   # test build only
+        L.cryo_host_set_group_ops.argtypes = [C.POINTER(CryoCodecGroupOps)]
+        L.cryo_host_set_group_ops.restype = None
+        L.cryo_group_set_window.argtypes = [i32, sz]
+        L.cryo_group_set_window.restype = None
     L.cryo_host_codec_error.restype = C.c_char_p
     L.cryo_compat_set_error_handler.argtypes = [ERROR_HANDLER]
     L.cryo_compat_set_error_handler.restype = None
@@ -256,6 +286,8 @@ def lib():
     L.cryo_filter_scan.argtypes = [C.POINTER(CryoRel), vp, FETCH_TUPLE_FN, FETCH_REPORT_FN, vp, C.POINTER(CryoFilterTotals)]
     # CryoAggReport has the layout of the fetch's CryoFetchReport
     L.cryo_aggregate_scan.argtypes = [C.POINTER(CryoRel), vp, vp, AGG_BLOCK_FN, FETCH_REPORT_FN, vp, C.POINTER(CryoAggTotals)]
+    # CryoGroupReport has the layout of the fetch's CryoFetchReport
+    L.cryo_group_scan.argtypes = [C.POINTER(CryoRel), vp, vp, vp, GROUP_BLOCK_FN, FETCH_REPORT_FN, vp, C.POINTER(CryoGroupTotals)]
     for n in ("cryo_cache_hits", "cryo_cache_misses", "cryo_cache_codec_calls"):
         getattr(L, n).restype = C.c_uint64
     _libs[prod] = L
@@ -398,6 +430,44 @@ def aggregate_scan(rel, atts, keys, cols):
     totals["cells"] = [_cell(t.cells[j]) for j in range(min(ncols, 4))]
     if rc != 0:
         raise AggregateScanError(rc, events, totals)
+    return events, totals
+
+
+class GroupScanError(RuntimeError):
+    def __init__(self, code, events, totals):
+        self.code, self.events, self.totals = code, events, totals
+        super().__init__("cryo_group_scan failed: %d" % code)
+
+
+def group_scan(rel, atts, keys, by, cols=None):
+    """cryo_group_scan (host/group.h) with the descriptors codec.filter_desc, codec.group_desc and codec.agg_desc make of atts
+    [(attlen, attalign)], keys [(att, type, op, value)], by and cols [(att, type)] (cols None: a null aggregate descriptor).
+    Returns (events, totals): events in delivery order, ("block", block, created_xid, n_items, n_match, n_bad, [(key tuple with
+    None for NULL, n_rows, [(n, min, max, sum) per column]) per group]) or ("report", block, reason, detail); totals a dict.  A
+    nonzero status raises GroupScanError (which carries what was delivered)."""
+    from . import codec
+    desc, gdesc = codec.filter_desc(atts, keys), codec.group_desc(by)
+    adesc = None if cols is None else codec.agg_desc(cols)
+    nby, ncols = len(by), len(cols or ())
+    events = []
+
+    def on_block(arg, b):
+        b = b.contents
+        groups = []
+        for g in range(b.n_groups):
+            r = b.recs[g]
+            key = tuple(None if (r.nulls >> j) & 1 else r.key[j] for j in range(min(nby, 2)))
+            groups.append((key, r.n_rows, [_cell(b.cells[g * ncols + j]) for j in range(ncols)]))
+        events.append(("block", b.block, b.created_xid, b.n_items, b.n_match, b.n_bad, groups))
+
+    bcb = GROUP_BLOCK_FN(on_block)
+    rcb = FETCH_REPORT_FN(lambda arg, r: events.append(("report", r.contents.block, r.contents.reason, r.contents.detail)))
+    t = CryoGroupTotals()
+    rc = lib().cryo_group_scan(C.byref(rel), C.byref(desc[0]), C.byref(gdesc[0]), C.byref(adesc[0]) if adesc else None, bcb, rcb,
+                               None, C.byref(t))
+    totals = {f: getattr(t, f) for f, _ in CryoGroupTotals._fields_}
+    if rc != 0:
+        raise GroupScanError(rc, events, totals)
     return events, totals
 
 

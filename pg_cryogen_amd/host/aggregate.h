@@ -14,7 +14,7 @@
  * blocks its snapshot sees.  The totals' combined cells are the answer for a relation whose blocks are all visible.
  *
  * Where it does not pay: one block per call (a device round trip per block), and aggregates this codec does not reduce (float and
- * numeric columns, expressions, GROUP BY) -- those go through filter.h.
+ * numeric columns, expressions) -- those go through filter.h.  GROUP BY on one or two integer columns is group.h's.
  */
 #ifndef CRYO_AGGREGATE_H
 #define CRYO_AGGREGATE_H

@@ -141,6 +141,20 @@ static const CryoCodecAggOps *bound_agg_ops; /* the aggregate table of a bound d
 void cryo_host_set_agg_ops(const CryoCodecAggOps *ops) { bound_agg_ops = ops; }
 #endif
 const CryoCodecAggOps *cryo_host_agg_ops(void) { return bound_ops ? bound_agg_ops : &hip_agg_ops; }
+static int hip_group_blocks(void *ctx, int method, const void *const *src, const uint32_t *sz, size_t n, size_t bs,
+                            const void *filter, const void *group, const void *agg, void *blocks, void *groups, size_t group_cap,
+                            void *cells, uint64_t *total)
+{
+    return cryo_multi_group_blocks((cryo_multi *)ctx, method, src, sz, n, bs, (const cryo_filter *)filter, (const cryo_group *)group,
+                                   (const cryo_agg *)agg, (cryo_group_block *)blocks, (cryo_group_rec *)groups, group_cap,
+                                   (cryo_agg_cell *)cells, total);
+}
+static const CryoCodecGroupOps hip_group_ops = {hip_group_blocks};
+static const CryoCodecGroupOps *bound_group_ops; /* the group table of a bound double (CRYO_HOST_TEST_HOOKS builds only) */
+#ifdef CRYO_HOST_TEST_HOOKS
+void cryo_host_set_group_ops(const CryoCodecGroupOps *ops) { bound_group_ops = ops; }
+#endif
+const CryoCodecGroupOps *cryo_host_group_ops(void) { return bound_ops ? bound_group_ops : &hip_group_ops; }
 const char *cryo_host_codec_error(void) { return codec_err; }
 
 const CryoCodecOps *cryo_host_codec_ops(void)

@@ -140,6 +140,20 @@ const CryoCodecAggOps *cryo_host_agg_ops(void);
 #ifdef CRYO_HOST_TEST_HOOKS
 void cryo_host_set_agg_ops(const CryoCodecAggOps *ops); /* test builds only: the aggregate table of the bound double, or NULL */
 #endif
+/* the grouped scan (group.h, cryo_group_scan) is bound through a table of its own as well.  group_blocks is
+ * cryo_multi_group_blocks (include/cryo_codec.h): filter is a const cryo_filter *, group a const cryo_group * and agg a const
+ * cryo_agg * (or NULL), all with host arrays; blocks gets one cryo_group_block (32 bytes) per stream in call order, groups up to
+ * group_cap cryo_group_rec (24 bytes), cells agg->ncols cryo_agg_cell (40 bytes each) per group, *total the call's groups */
+typedef struct CryoCodecGroupOps {
+    int (*group_blocks)(void *ctx, int method, const void *const *src, const uint32_t *src_size, size_t n, size_t block_size,
+                        const void *filter, const void *group, const void *agg, void *blocks, void *groups, size_t group_cap,
+                        void *cells, uint64_t *total);
+} CryoCodecGroupOps;
+/* the group table that goes with cryo_host_codec_ops(): production's binds the GPU codec; NULL when a bound double has none */
+const CryoCodecGroupOps *cryo_host_group_ops(void);
+#ifdef CRYO_HOST_TEST_HOOKS
+void cryo_host_set_group_ops(const CryoCodecGroupOps *ops); /* test builds only: the group table of the bound double, or NULL */
+#endif
 const CryoCodecOps *cryo_host_codec_ops(void);         /* lazily opens the GPU codec */
 void cryo_host_codec_trim(void);                         /* idle backend: free the binding's device workspace and staging buffers */
 size_t cryo_host_codec_bound(int method, size_t n);      /* cryo_codec_bound (or the bound double's): never opens the GPU */
