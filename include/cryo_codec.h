@@ -379,13 +379,22 @@ int cryo_codec_fetch_batch(cryo_codec *c, int method, const void *d_src, const u
  * a value outside the type's range; an unknown op; a reserved field that is not zero; an unknown bit in flags.  For
  * CRYO_OP_ISNULL and CRYO_OP_NOTNULL, type and value are ignored.  Key values are signed and compared as such; tuples are
  * little-endian.
+ * Byte-string keys.  A comparison key (CRYO_OP_LT .. CRYO_OP_NE) of type CRYO_KEY_BYTES (16; 4 .. 15 stay free for fixed-width
+ * types, and they, 0 and anything above 16 are unknown) compares a text / varchar / bytea column with a constant: rsv is the
+ * constant's length n, 0 .. CRYO_KEY_BYTES_MAX, and value the address of its n bytes -- a device address for cryo_codec_*_batch,
+ * a host address for cryo_codec_*_blocks and cryo_multi_*_blocks; any alignment; not looked at when n == 0.  CRYO_E_ARG when the
+ * key's column is not a varlena (attlen != -1), n > CRYO_KEY_BYTES_MAX, or n > 0 with a null address.  For every other type and
+ * for the null tests rsv != 0 stays refused.  The caller's arrays are never written: the library makes its own device copy of
+ * the keys and of the constants, in which the kernels find each constant 8-byte aligned and zero-padded to a multiple of 8.
+ * Such a key is no aggregate and no group column (CRYO_E_ARG there, as any unknown type).
  *
  * Per block (names as in the check's rules above: lower, upper, n, off_i, len_i, MAXALIGN, B), the first failing rule wins:
  *   CRYO_FETCH_STREAM (1), CRYO_FETCH_HEADER (2)   exactly the fetch's; no item is examined, the block has no record
  *   otherwise every item 1 .. n is examined:
  *     CRYO_FETCH_ITEM (3)    the item fails the fetch's ITEM rule (len == 0, off % 8 != 0, off < upper, off + MAXALIGN(len) > B)
  *     CRYO_FILTER_TUPLE (8)  the tuple fails a tuple rule below
- *     the items that pass both and pass every key are the block's matches; the rest is silently no match
+ *     CRYO_FILTER_UNDECIDED (9)  no key is false on the tuple, and a byte-string key met a value whose bytes are not in it
+ *     the items that pass these and pass every key are the block's matches; the rest is silently no match
  *   CRYO_FETCH_OVERLAP (7)   the MAXALIGNed lengths of the matches sum to more than B - upper: the block delivers no tuple and no
  *                            match record (n_match = 0); its bad items keep their records
  *
@@ -413,9 +422,23 @@ int cryo_codec_fetch_batch(cryo_codec *c, int method, const void *d_src, const u
  *   Nothing outside [t, t + len) is ever loaded, whatever the tuple says.
  *   Keys: a comparison on a NULL column is false; ISNULL and NOTNULL are what they say; the column's value is the signed
  *   little-endian integer of the key's type at o.
+ *   Byte-string keys: the stepping above is unchanged.  The value of a non-NULL varlena column at o is
+ *     1-byte header b (b & 1, b != 1)      the payload: the (b >> 1) - 1 bytes from o + 1
+ *     4-byte header w, (w & 3) == 0        the payload: the (w >> 2) - 4 bytes from o + 4
+ *     4-byte header w, (w & 3) == 2 (compressed in line), or an external pointer (0x01, tag 18)
+ *                                          not in the tuple: the key is UNDECIDED on this tuple
+ *   With plen the payload's length and n the constant's: c = memcmp(payload, constant, min(plen, n)) on UNSIGNED bytes, and when
+ *   that is 0, c = sign(plen - n); the six ops are the obvious tests on c (= is c == 0, < is c < 0, ...).  Only the payload's
+ *   plen bytes are read, never the pad behind them.
+ *   The verdict on a tuple, the first rule that applies: CRYO_FILTER_TUPLE if the walk fails anywhere up to the highest column
+ *   it visits (it still goes that far whatever the keys said); no match if some key is decidedly false (false AND unknown is
+ *   false); CRYO_FILTER_UNDECIDED if a byte-string key met an undecided value; otherwise a match.
  *
  * Results.  One cryo_filter_block per block, in call order.  One cryo_filter_rec per match {pos, 0, len} and one per bad item
- * {pos, CRYO_FETCH_ITEM or CRYO_FILTER_TUPLE, 0} -- a damaged tuple is never silently absent from a scan --, in position order
+ * {pos, CRYO_FETCH_ITEM, CRYO_FILTER_TUPLE or CRYO_FILTER_UNDECIDED, 0} -- a damaged tuple is never silently absent from a scan,
+ * and an undecided one is a bad item everywhere: it counts in n_bad (under CRYO_FILTER_COUNT_ONLY, in the aggregate and in the
+ * grouped scan too), is in no cell and no group, and has a record and no tuple bytes here, so that the caller fetches or
+ * rechecks the positions the records name --, in position order
  * within the block; the block's records are records rec_first .. rec_first + n_match + n_bad - 1 of the call.  Its tuples lie
  * packed from byte `off` of the destination on: each its len bytes, then zeros up to MAXALIGN(len) whatever the block holds in its
  * pad (as the fetch writes them); a tuple's offset is `off` plus the MAXALIGNed lengths of the block's matches before it.  Blocks
@@ -428,7 +451,10 @@ int cryo_codec_fetch_batch(cryo_codec *c, int method, const void *d_src, const u
  * CRYO_FILTER_COUNT_ONLY: the per-block table only -- status, n_items, n_match, n_bad; rec_first, off and both totals are 0; no
  * record, no tuple is written; OVERLAP is not applied, because nothing is placed. */
 typedef struct { int16_t attlen; uint8_t attalign; uint8_t rsv; } cryo_att; /* pg_attribute.attlen; attalign as 1/2/4/8; 4 bytes */
-typedef enum { CRYO_KEY_INT2 = 1, CRYO_KEY_INT4 = 2, CRYO_KEY_INT8 = 3 } cryo_key_type; /* signed, little-endian */
+typedef enum {
+    CRYO_KEY_INT2 = 1, CRYO_KEY_INT4 = 2, CRYO_KEY_INT8 = 3, /* signed, little-endian */
+    CRYO_KEY_BYTES = 16                                      /* a byte string: rsv its length, value its address */
+} cryo_key_type;
 typedef enum {
     CRYO_OP_LT = 1, CRYO_OP_LE, CRYO_OP_EQ, CRYO_OP_GE, CRYO_OP_GT, CRYO_OP_NE, CRYO_OP_ISNULL, CRYO_OP_NOTNULL
 } cryo_key_op;
@@ -440,13 +466,18 @@ typedef struct {
 } cryo_filter;
 #define CRYO_FILTER_COUNT_ONLY 1u /* per-block table only: no records, no tuples */
 #define CRYO_FILTER_TUPLE 8u      /* a record's status beside CRYO_FETCH_ITEM: the tuple breaks a tuple rule */
+#define CRYO_FILTER_UNDECIDED 9u  /* a record's status: a byte-string key met a compressed or external value */
+#define CRYO_KEY_BYTES_MAX 256u   /* the longest constant of a CRYO_KEY_BYTES key */
 #define CRYO_FILTER_MAX_ATTS 1600u
 #define CRYO_FILTER_MAX_KEYS 4u
 typedef struct { uint32_t status, n_items, n_match, n_bad; uint64_t rec_first, off; } cryo_filter_block; /* 32 bytes, one per block */
 typedef struct { uint16_t pos, status; uint32_t len; } cryo_filter_rec;                                   /* 8 bytes */
 /* Device buffers.  The struct *f itself is host memory; f->atts and f->keys are DEVICE arrays (4-byte / 8-byte aligned).  The
  * host validates the descriptor before anything is queued: it reads the two arrays back on the handle's stream (one wait for
- * what the stream held before the call, at most 6400 + 64 bytes); from there on the call is asynchronous.  d_dst 8-byte, d_rec
+ * what the stream held before the call, at most 6400 + 64 bytes); from there on the call is asynchronous.  With a byte-string
+ * key the constants are read back too (at most 1 024 more bytes) and the library's copy of keys and constants goes into
+ * handle-owned device memory: two more waits before the call turns asynchronous; the copy serves all of the call's internal
+ * chunks.  d_dst 8-byte, d_rec
  * 8-byte, d_blocks 16-byte, d_total 8-byte aligned (CRYO_E_ARG otherwise); d_total has two entries and is also where the two
  * running totals live between the call's internal chunks.  Decode as in the fetch: the automatic routes, handle workspace,
  * chunks within CRYO_OPT_WORKSPACE_MAX_BYTES (the workspace also holds 16 bytes per possible item of a chunk); the device pool
@@ -485,7 +516,7 @@ int cryo_codec_filter_batch(cryo_codec *c, int method, const void *d_src, const 
  *   aggregate column that lies beyond the last key column is CRYO_FILTER_TUPLE here, where the same keys alone would pass it in the
  *   filter.
  *     n_match   the items that pass both rules and every key
- *     n_bad     the items that fail the ITEM rule or the TUPLE rule (the walk included): counted, not listed, as under
+ *     n_bad     the items that fail the ITEM rule or the TUPLE rule (the walk included) or are undecided: counted, not listed, as under
  *               CRYO_FILTER_COUNT_ONLY -- a caller who sees n_bad > 0 reads that block through the filter
  *   OVERLAP is not applied, because nothing is placed.
  *
@@ -538,7 +569,7 @@ int cryo_codec_agg_batch(cryo_codec *c, int method, const void *d_src, const uin
  *   otherwise (status 0, n_items = n) every item 1 .. n is examined with the filter's ITEM rule and TUPLE rule and the walk over
  *   the columns 1 .. max(highest key column, highest group column, highest aggregate column) -- that far for every tuple and not a
  *   column further: the aggregate's documented difference from the filter, the group columns included.  n_match and n_bad are the
- *   aggregate's; a damaged item is in no group (a caller who sees n_bad > 0 reads that block through the filter).  OVERLAP is not
+ *   aggregate's (n_bad: the items that fail the ITEM or the TUPLE rule or are undecided); a damaged or undecided item is in no group (a caller who sees n_bad > 0 reads that block through the filter).  OVERLAP is not
  *   applied, because nothing is placed.
  *
  * Groups of a block.  The block's matches are partitioned by the tuple (null_1, value_1[, null_2, value_2]) of the group columns:

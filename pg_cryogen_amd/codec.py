@@ -41,8 +41,11 @@ FETCH_RESULT = np.dtype([("status", "<u4"), ("len", "<u4"), ("off", "<u8")])
 # the scan filter (include/cryo_codec.h): a record's statuses are 0, FETCH_ITEM and FILTER_TUPLE, a block's 0, FETCH_STREAM,
 # FETCH_HEADER and FETCH_OVERLAP
 FILTER_TUPLE = 8
+FILTER_UNDECIDED = 9        # a record's status: a byte-string key met a compressed or external value
 FILTER_COUNT_ONLY = 1
 KEY_INT2, KEY_INT4, KEY_INT8 = 1, 2, 3
+KEY_BYTES = 16              # a byte string: the key's value is bytes, compared unsigned, then by length
+KEY_BYTES_MAX = 256
 OP_LT, OP_LE, OP_EQ, OP_GE, OP_GT, OP_NE, OP_ISNULL, OP_NOTNULL = range(1, 9)
 FILTER_ATT = np.dtype([("attlen", "<i2"), ("attalign", "u1"), ("rsv", "u1")])                                  # cryo_att
 FILTER_KEY = np.dtype([("att", "<u2"), ("type", "u1"), ("op", "u1"), ("rsv", "<u4"), ("value", "<i8")])        # cryo_scan_key
@@ -281,16 +284,63 @@ def fetch_blocks_call(fn, handle, chk, method, comps, block_size, requests, dst=
 
 def filter_desc(atts, keys=(), flags=0):
     """the descriptor of a filter call as host arrays: atts a list of (attlen, attalign), keys a list of (att, type, op, value)
-    (att 1-based; type KEY_*, op OP_*).  Returns (CryoFilter, atts array, keys array); the struct points into the two arrays,
-    which the caller keeps alive"""
+    (att 1-based; type KEY_*, op OP_*; the value of a KEY_BYTES comparison is a bytes object).  Returns (CryoFilter, atts array,
+    keys array); the struct points into the two arrays, which the caller keeps alive.  The constants of KEY_BYTES keys live in
+    one uint8 array the struct holds (f.consts), so they live as long as it does"""
     a = np.zeros(max(len(atts), 1), FILTER_ATT)
     for i, (attlen, attalign) in enumerate(atts):
         a[i] = (attlen, attalign, 0)
-    k = np.zeros(max(len(keys), 1), FILTER_KEY)
-    for i, (att, typ, op, value) in enumerate(keys):
-        k[i] = (att, typ, op, 0, value)
+    k, consts = _filter_keys(keys)
+    _rebase_keys(k, keys, consts.ctypes.data)
     f = CryoFilter(len(atts), len(keys), flags, 0, a.ctypes.data, k.ctypes.data if len(keys) else None)
+    f.consts = consts
     return f, a, k
+
+
+def _is_bytes_key(key):
+    """a key whose value is a byte string (None: no bytes and a null address)"""
+    return key[1] == KEY_BYTES and isinstance(key[3], (bytes, bytearray, memoryview, type(None)))
+
+
+def _filter_keys(keys):
+    """(keys array with rsv = the length and value = the offset of each KEY_BYTES constant, the constants packed back to back)"""
+    k = np.zeros(max(len(keys), 1), FILTER_KEY)
+    parts, at = [], 0
+    for i, key in enumerate(keys):
+        att, typ, op, value = key
+        if _is_bytes_key(key):
+            value = bytes(value or b"")
+            k[i] = (att, typ, op, len(value), at)
+            parts.append(value)
+            at += len(value)
+        else:
+            k[i] = (att, typ, op, 0, value)
+    consts = np.frombuffer(b"".join(parts) + b"\0", np.uint8).copy()        # never empty: it has an address
+    return k, consts
+
+
+def _rebase_keys(k, keys, base):
+    """offsets into the packed constants -> addresses from `base` on; an empty constant keeps a null address"""
+    for i, key in enumerate(keys):
+        if _is_bytes_key(key):
+            k[i]["value"] = base + int(k[i]["value"]) if key[3] else 0
+
+
+def filter_desc_device(atts, keys=()):
+    """the device form of a descriptor with KEY_BYTES keys: returns (atts array, keys array, consts array, rebase).  The caller
+    uploads consts to device memory at some address d and calls rebase(d), which sets every KEY_BYTES key's value to the
+    device address of its constant (constants lie back to back in consts, at any alignment); then it uploads the keys"""
+    a = np.zeros(max(len(atts), 1), FILTER_ATT)
+    for i, (attlen, attalign) in enumerate(atts):
+        a[i] = (attlen, attalign, 0)
+    k, consts = _filter_keys(keys)
+    offs = k["value"].copy()
+
+    def rebase(d_consts):
+        k["value"] = offs
+        _rebase_keys(k, keys, int(d_consts))
+        return k
+    return a, k, consts, rebase
 
 
 def filter_blocks_call(fn, handle, chk, method, comps, block_size, desc, dst=None, rec=None):

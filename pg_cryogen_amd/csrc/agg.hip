@@ -10,7 +10,8 @@
  *                 ITEM rule, then the walk of filter_walk.h over the columns 1 .. max(highest key column, highest aggregate
  *                 column), which tests the keys and notes the aggregate columns' values as it passes them.  Descriptor, keys and
  *                 aggregate columns are read at addresses that depend on loop counters only (uniform loads); no load leaves
- *                 [t, t + len).  There is no OVERLAP verdict and nothing to place, so one sweep suffices.  A lane keeps, per
+ *                 [t, t + len).  A descriptor with a byte-string key runs k_agg_block<true>, whose walk compares those too and
+ *                 counts an undecided tuple in n_bad; every other descriptor runs k_agg_block<false>.  There is no OVERLAP verdict and nothing to place, so one sweep suffices.  A lane keeps, per
  *                 aggregate column, the count of non-NULL matches, their min and max, and their sum in two 64-bit halves: the low
  *                 32 bits of every value summed unsigned, the high 32 bits summed signed -- at most 290 values, so neither half
  *                 overflows.  After the sweep a butterfly (__shfl_xor) reduces the five words per column across the wave; lane 0
@@ -25,6 +26,7 @@ namespace cryo {
 struct AggCell { uint64_t n; int64_t min, max; uint64_t sum_lo; int64_t sum_hi; }; /* cryo_agg_cell */
 static_assert(sizeof(AggCell) == 40, "the cell's layout is the header's");
 
+template <bool BYTES>
 __global__ void __launch_bounds__(256)
 k_agg_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, uint32_t cnt, const int32_t *__restrict__ dec_status,
             const FilterAtt *__restrict__ atts, const FilterKey *__restrict__ keys, uint32_t nkeys,
@@ -67,9 +69,10 @@ k_agg_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, ui
                 cap.has = 0;
 #pragma unroll
                 for (uint32_t j = 0; j < kAggMaxCols; j++) cap.v[j] = 0;
-                const uint32_t walked = walk_tuple<true>(p + src, len, live, atts, keys, nkeys, max_att, cols, ncols, &cap);
+                const uint32_t walked = walk_tuple<true>(p + src, len, live, atts, keys, nkeys, max_att, cols, ncols, &cap, WalkKeys<BYTES>());
                 if (live) verdict = walked;
-                const bool match = verdict == 0u, bad = verdict == kFilterItem || verdict == kFilterTuple;
+                const bool match = verdict == 0u,
+                           bad = verdict == kFilterItem || verdict == kFilterTuple || (BYTES && verdict == kFilterUndecided);
                 n_match += (uint32_t)__popcll(__ballot(match));
                 n_bad += (uint32_t)__popcll(__ballot(bad));
 #pragma unroll
@@ -119,16 +122,16 @@ k_agg_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, ui
 
 hipError_t launch_agg(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
                       const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_cols,
-                      uint32_t ncols, uint32_t max_att, uint4 *d_blocks, void *d_cells)
+                      uint32_t ncols, uint32_t max_att, bool bytes_keys, uint4 *d_blocks, void *d_cells)
 {
     if (cnt == 0) return hipSuccess;
     if ((dec_stride & 15u) != 0 || (((uintptr_t)d_dec | (uintptr_t)d_blocks) & 15u) != 0 ||
         (((uintptr_t)d_cells | (uintptr_t)d_keys | (uintptr_t)d_cols) & 7u) != 0 || ((uintptr_t)d_atts & 3u) != 0 || block_size < 16u ||
         nkeys > 4u || ncols == 0u || ncols > kAggMaxCols)
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_agg_block, dim3((cnt + 3u) / 4u), dim3(256), 0, s, d_dec, dec_stride, block_size, cnt, d_dec_status,
-                       (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys, (const AggCol *)d_cols, ncols, max_att, d_blocks,
-                       (AggCell *)d_cells);
+    hipLaunchKernelGGL(bytes_keys ? k_agg_block<true> : k_agg_block<false>, dim3((cnt + 3u) / 4u), dim3(256), 0, s, d_dec, dec_stride,
+                       block_size, cnt, d_dec_status, (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys,
+                       (const AggCol *)d_cols, ncols, max_att, d_blocks, (AggCell *)d_cells);
     return hipGetLastError();
 }
 

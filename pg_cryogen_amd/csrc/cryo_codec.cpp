@@ -127,6 +127,7 @@ struct cryo_codec {
     size_t ws_cap = 0;
     /* host-buffer batch API: grow-only device buffers and one pinned staging buffer */
     uint8_t *hb_src = nullptr, *hb_dst = nullptr, *hb_meta = nullptr;
+    uint8_t *d_keytab = nullptr; /* the device-resident scan calls' copy of keys and byte-string constants (kKeyTableBytes) */
     size_t hb_src_cap = 0, hb_dst_cap = 0, hb_meta_cap = 0;
     void *pin = nullptr;
     size_t pin_cap = 0;
@@ -466,6 +467,7 @@ void cryo_codec_close(cryo_codec *c)
     if (c->hb_src) (void)hipFree(c->hb_src);
     if (c->hb_dst) (void)hipFree(c->hb_dst);
     if (c->hb_meta) (void)hipFree(c->hb_meta);
+    if (c->d_keytab) (void)hipFree(c->d_keytab);
     if (c->d_vfy) (void)hipFree(c->d_vfy);
     if (c->d_rec) (void)hipFree(c->d_rec);
     if (c->pin) (void)hipHostFree(c->pin);
@@ -516,6 +518,7 @@ int cryo_codec_trim(cryo_codec *c)
     drop(c->hb_meta, c->hb_meta_cap);
     drop(c->d_vfy, c->vfy_cap);
     drop(c->d_rec, c->rec_cap);
+    if (c->d_keytab) { (void)hipFree(c->d_keytab); c->d_keytab = nullptr; }
     c->vfy_first = nullptr;
     if (c->pin) { (void)hipHostFree(c->pin); c->pin = nullptr; c->pin_cap = 0; }
     for (int i = 0; i < 4; i++)
@@ -1122,7 +1125,7 @@ namespace {
 struct FilterIo {
     const void *d_atts = nullptr, *d_keys = nullptr; /* device */
     uint32_t nkeys = 0, max_att = 0;
-    bool count_only = false;
+    bool count_only = false, bytes_keys = false; /* bytes_keys: d_keys is a key table with a byte-string key */
     cryo_filter_block *d_blocks = nullptr;           /* device: n rows */
     uint64_t dst_cap = 0, rec_cap = 0;
     /* device-resident call: the caller's buffers and totals */
@@ -1153,9 +1156,16 @@ static bool filter_desc_ok(const cryo_filter *f, const cryo_att *atts, const cry
     }
     for (uint32_t k = 0; k < f->nkeys; k++) {
         const cryo_scan_key &q = keys[k];
-        if (q.rsv != 0 || q.att == 0 || q.att > f->natts || q.op < CRYO_OP_LT || q.op > CRYO_OP_NOTNULL) return false;
+        const bool cmp = q.op >= CRYO_OP_LT && q.op <= CRYO_OP_NE;
+        if ((q.rsv != 0 && !(cmp && q.type == CRYO_KEY_BYTES)) || q.att == 0 || q.att > f->natts || q.op < CRYO_OP_LT ||
+            q.op > CRYO_OP_NOTNULL)
+            return false;
         if (q.att > *max_att) *max_att = q.att;
         if (q.op == CRYO_OP_ISNULL || q.op == CRYO_OP_NOTNULL) continue;
+        if (q.type == CRYO_KEY_BYTES) { /* rsv: the constant's length; value: its address, not looked at here beyond null */
+            if (atts[q.att - 1].attlen != -1 || q.rsv > CRYO_KEY_BYTES_MAX || (q.rsv > 0 && q.value == 0)) return false;
+            continue;
+        }
         if (q.type < CRYO_KEY_INT2 || q.type > CRYO_KEY_INT8) return false;
         const int size = q.type == CRYO_KEY_INT2 ? 2 : q.type == CRYO_KEY_INT4 ? 4 : 8;
         const cryo_att &a = atts[q.att - 1];
@@ -1163,6 +1173,80 @@ static bool filter_desc_ok(const cryo_filter *f, const cryo_att *atts, const cry
         if (size == 2 && (q.value < INT16_MIN || q.value > INT16_MAX)) return false;
         if (size == 4 && (q.value < INT32_MIN || q.value > INT32_MAX)) return false;
     }
+    return true;
+}
+
+/* ---- byte-string keys: the library's own copy ----
+ * A descriptor with a CRYO_KEY_BYTES key reaches the kernels as a key table: [keys 16 x nkeys][the constants in key order, each
+ * zero-padded to a multiple of 8], the whole a multiple of 16 bytes, with the value of every such key rewritten to the device
+ * address of its constant in the table -- 8-byte aligned there, whatever the caller's address was.  The caller's arrays are only
+ * read.  A descriptor without such a key has no table: its keys go to the device as they are. */
+static constexpr size_t kKeyTableBytes = CRYO_FILTER_MAX_KEYS * (sizeof(cryo_scan_key) + CRYO_KEY_BYTES_MAX);
+
+static bool key_is_bytes(const cryo_scan_key &q) { return q.type == CRYO_KEY_BYTES && q.op >= CRYO_OP_LT && q.op <= CRYO_OP_NE; }
+
+/* the bytes the constants take behind the keys of a (valid) descriptor, a multiple of 16; 0: no byte-string key */
+static size_t key_consts_bytes(const cryo_scan_key *keys, uint32_t nkeys, bool *any)
+{
+    size_t b = 0;
+    *any = false;
+    for (uint32_t k = 0; k < nkeys; k++)
+        if (key_is_bytes(keys[k])) { *any = true; b += ((size_t)keys[k].rsv + 7) & ~(size_t)7; }
+    return (b + 15) & ~(size_t)15;
+}
+
+/* the key table of a (valid) descriptor at tab (zeroed, nkeys * 16 + key_consts_bytes bytes), which will lie at device address
+ * d_tab; consts[k]: where the host finds the constant of key k */
+static void key_table_fill(uint8_t *tab, uint64_t d_tab, const cryo_scan_key *keys, uint32_t nkeys, const void *const *consts)
+{
+    size_t at = (size_t)nkeys * sizeof(cryo_scan_key);
+    for (uint32_t k = 0; k < nkeys; k++) {
+        cryo_scan_key q = keys[k];
+        if (key_is_bytes(q)) {
+            if (q.rsv) memcpy(tab + at, consts[k], q.rsv);
+            q.value = (int64_t)(d_tab + at);
+            at += ((size_t)q.rsv + 7) & ~(size_t)7;
+        }
+        memcpy(tab + (size_t)k * sizeof(cryo_scan_key), &q, sizeof q);
+    }
+}
+
+/* the device-resident calls: keys (host copy, validated) name constants in DEVICE memory.  Reads them back (at most 1 024 bytes),
+ * builds the table in handle-owned device memory and gives its address; one more wait on the stream.  Without a byte-string key:
+ * *d_keys stays the caller's array and nothing is queued. */
+static int key_table_device(cryo_codec *c, const cryo_scan_key *keys, uint32_t nkeys, const void **d_keys, bool *bytes_keys)
+{
+    const size_t cb = key_consts_bytes(keys, nkeys, bytes_keys);
+    if (!*bytes_keys) return CRYO_OK;
+    std::vector<uint8_t> consts(CRYO_FILTER_MAX_KEYS * CRYO_KEY_BYTES_MAX), tab((size_t)nkeys * sizeof(cryo_scan_key) + cb, 0);
+    const void *where[CRYO_FILTER_MAX_KEYS] = {nullptr, nullptr, nullptr, nullptr};
+    for (uint32_t k = 0; k < nkeys; k++) {
+        if (!key_is_bytes(keys[k]) || keys[k].rsv == 0) continue;
+        where[k] = consts.data() + (size_t)k * CRYO_KEY_BYTES_MAX;
+        HIP_TRY(c, hipMemcpyAsync((void *)where[k], (const void *)(uintptr_t)keys[k].value, keys[k].rsv, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (!c->d_keytab) HIP_TRY(c, hipMalloc(&c->d_keytab, kKeyTableBytes));
+    key_table_fill(tab.data(), (uint64_t)(uintptr_t)c->d_keytab, keys, nkeys, where);
+    HIP_TRY(c, hipMemcpyAsync(c->d_keytab, tab.data(), tab.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream)); /* tab is the call's own: gone when it returns */
+    *d_keys = c->d_keytab;
+    return CRYO_OK;
+}
+
+/* the host-buffer calls: the table into the pinned copy of the descriptor at pin_keys, which the upload puts at d_keys.  Returns
+ * whether the descriptor has a byte-string key */
+static bool key_table_host(uint8_t *pin_keys, const uint8_t *d_keys, const cryo_filter *f)
+{
+    bool any = false;
+    (void)key_consts_bytes(f->keys, f->nkeys, &any);
+    if (!any) {
+        if (f->nkeys) memcpy(pin_keys, f->keys, (size_t)f->nkeys * sizeof(cryo_scan_key));
+        return false;
+    }
+    const void *where[CRYO_FILTER_MAX_KEYS] = {nullptr, nullptr, nullptr, nullptr};
+    for (uint32_t k = 0; k < f->nkeys; k++) where[k] = (const void *)(uintptr_t)f->keys[k].value;
+    key_table_fill(pin_keys, (uint64_t)(uintptr_t)d_keys, f->keys, f->nkeys, where);
     return true;
 }
 
@@ -1188,7 +1272,7 @@ static int filter_pass(cryo_codec *c, int method, const uint8_t *d_src, const ui
         cryo_filter_rec *st_rec = (cryo_filter_rec *)(st_dst + row * ch.K);
         if (ch.lo == 0) HIP_TRY(c, hipMemsetAsync(running, 0, 2 * sizeof(uint64_t), c->stream));
         HIP_TRY(c, cryo::launch_filter(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.d_atts, io.d_keys, io.nkeys, io.max_att,
-                                       io.count_only, (uint4 *)(io.d_blocks + ch.lo), side, sum, base, running,
+                                       io.bytes_keys, io.count_only, (uint4 *)(io.d_blocks + ch.lo), side, sum, base, running,
                                        stage ? st_dst : io.d_dst, stage ? ch.K * row : io.dst_cap,
                                        stage ? (uint2 *)st_rec : (uint2 *)io.d_rec, stage ? ch.K * S : io.rec_cap, host,
                                        c->lz4_opts.cus));
@@ -1240,6 +1324,7 @@ namespace {
 struct AggIo {
     const void *d_atts = nullptr, *d_keys = nullptr, *d_cols = nullptr; /* device */
     uint32_t nkeys = 0, ncols = 0, max_att = 0;
+    bool bytes_keys = false;            /* d_keys is a key table with a byte-string key */
     cryo_agg_block *d_blocks = nullptr; /* device: n rows */
     cryo_agg_cell *d_cells = nullptr;   /* device: n * ncols cells */
 };
@@ -1279,7 +1364,8 @@ static int agg_pass(cryo_codec *c, int method, const uint8_t *d_src, const uint6
     ps.d_comp = d_src; ps.d_comp_off = d_src_off; ps.d_comp_size = d_src_size;
     ps.run = [&](const DecodeChunk &ch) -> int {
         HIP_TRY(c, cryo::launch_agg(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.d_atts, io.d_keys, io.nkeys, io.d_cols,
-                                    io.ncols, io.max_att, (uint4 *)(io.d_blocks + ch.lo), io.d_cells + ch.lo * io.ncols));
+                                    io.ncols, io.max_att, io.bytes_keys, (uint4 *)(io.d_blocks + ch.lo),
+                                    io.d_cells + ch.lo * io.ncols));
         return CRYO_OK;
     };
     const int rc = decode_pass(c, method, B, n, ps);
@@ -1299,6 +1385,7 @@ struct GroupIo {
     const void *d_by = nullptr, *d_cols = nullptr;   /* device: the caller's two arrays, or */
     const void *d_slots = nullptr;                   /* device: the six slots laid out already */
     uint32_t nkeys = 0, nby = 0, ncols = 0, max_att = 0;
+    bool bytes_keys = false;              /* d_keys is a key table with a byte-string key */
     cryo_group_block *d_blocks = nullptr; /* device: n rows */
     cryo_group_rec *d_groups = nullptr;   /* device: group_cap records */
     cryo_agg_cell *d_cells = nullptr;     /* device: group_cap * ncols cells */
@@ -1349,7 +1436,7 @@ static int group_pass(cryo_codec *c, int method, const uint8_t *d_src, const uin
         }
         uint8_t *side_rec = ch.own, *side_cell = ch.own + ch.K * S * sizeof(cryo_group_rec);
         HIP_TRY(c, cryo::launch_group(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.d_atts, io.d_keys, io.nkeys, slots, io.nby,
-                                      io.ncols, io.max_att, (uint4 *)(io.d_blocks + ch.lo), side_rec, side_cell, io.d_total,
+                                      io.ncols, io.max_att, io.bytes_keys, (uint4 *)(io.d_blocks + ch.lo), side_rec, side_cell, io.d_total,
                                       io.d_groups, io.d_cells, io.group_cap, c->lz4_opts.cus));
         return CRYO_OK;
     };
@@ -1551,6 +1638,8 @@ int cryo_codec_filter_batch(cryo_codec *c, int method, const void *d_src, const 
         HIP_TRY(c, hipMemsetAsync(d_total, 0, 2 * sizeof(uint64_t), c->stream));
         if (n_blocks == 0) return (int)CRYO_OK;
         io.d_atts = f->atts; io.d_keys = f->keys; io.nkeys = f->nkeys; io.count_only = count_only;
+        const int krc = key_table_device(c, keys.data(), f->nkeys, &io.d_keys, &io.bytes_keys);
+        if (krc != CRYO_OK) return krc;
         io.d_blocks = d_blocks; io.dst_cap = count_only ? 0 : dst_cap; io.rec_cap = count_only ? 0 : rec_cap;
         io.d_dst = (uint8_t *)d_dst; io.d_rec = d_rec; io.d_total = d_total;
         return filter_pass(c, method, (const uint8_t *)d_src, d_src_off, d_src_size, block_size, n_blocks, io);
@@ -1585,6 +1674,8 @@ int cryo_codec_agg_batch(cryo_codec *c, int method, const void *d_src, const uin
         if (!agg_desc_ok(f, atts.data(), keys.data(), agg, cols.data(), &io.max_att)) return (int)CRYO_E_ARG;
         if (n_blocks == 0) return (int)CRYO_OK;
         io.d_atts = f->atts; io.d_keys = f->keys; io.d_cols = agg->cols; io.nkeys = f->nkeys; io.ncols = agg->ncols;
+        const int krc = key_table_device(c, keys.data(), f->nkeys, &io.d_keys, &io.bytes_keys);
+        if (krc != CRYO_OK) return krc;
         io.d_blocks = d_blocks; io.d_cells = d_cells;
         return agg_pass(c, method, (const uint8_t *)d_src, d_src_off, d_src_size, block_size, n_blocks, io);
     });
@@ -1624,6 +1715,8 @@ int cryo_codec_group_batch(cryo_codec *c, int method, const void *d_src, const u
         if (n_blocks == 0) return (int)CRYO_OK;
         io.d_atts = f->atts; io.d_keys = f->keys; io.d_by = grp->by; io.d_cols = ncols ? agg->cols : nullptr;
         io.nkeys = f->nkeys; io.nby = grp->nby;
+        const int krc = key_table_device(c, keys.data(), f->nkeys, &io.d_keys, &io.bytes_keys);
+        if (krc != CRYO_OK) return krc;
         io.d_blocks = d_blocks; io.d_groups = d_groups; io.d_cells = d_cells; io.group_cap = group_cap; io.d_total = d_total;
         return group_pass(c, method, (const uint8_t *)d_src, d_src_off, d_src_size, block_size, n_blocks, io);
     });
@@ -2289,8 +2382,11 @@ static int filter_blocks_impl(cryo_codec *c, int method, const void *const *h_sr
     if (!h_src || !h_src_size || !h_blocks) return CRYO_E_ARG;
     if (!count_only && ((!h_dst && dst_cap > 0) || (!h_rec && rec_cap > 0))) return CRYO_E_ARG;
     ScopedLocalCpus numa_(n * block_size >= ((size_t)8 << 20) ? c : nullptr);
-    /* the descriptor and the table: [atts 4 x natts][keys 16 x nkeys][rows 32 x n], each part 16-byte aligned */
-    const size_t t_atts = 0, t_keys = ((size_t)f->natts * 4 + 15) & ~(size_t)15, t_rows = t_keys + (size_t)f->nkeys * 16;
+    /* the descriptor and the table: [atts 4 x natts][keys 16 x nkeys][byte-string constants][rows 32 x n], each part 16-byte
+     * aligned */
+    bool bytes_keys = false;
+    const size_t t_atts = 0, t_keys = ((size_t)f->natts * 4 + 15) & ~(size_t)15;
+    const size_t t_rows = t_keys + (size_t)f->nkeys * 16 + key_consts_bytes(f->keys, f->nkeys, &bytes_keys);
     size_t streams = (n * 12 + 63) & ~(size_t)63; /* what stage_streams lays out in the pinned buffer */
     for (size_t i = 0; i < n; i++) streams += ((size_t)h_src_size[i] + 15) & ~(size_t)15;
     const size_t p_tbl = (streams + 64 + 15) & ~(size_t)15;
@@ -2303,10 +2399,11 @@ static int filter_blocks_impl(cryo_codec *c, int method, const void *const *h_sr
     uint8_t *pin = (uint8_t *)c->pin + p_tbl;
     memset(pin, 0, t_rows);
     memcpy(pin + t_atts, f->atts, (size_t)f->natts * 4);
-    if (f->nkeys) memcpy(pin + t_keys, f->keys, (size_t)f->nkeys * 16);
+    (void)key_table_host(pin + t_keys, c->hb_meta + t_keys, f);
     HIP_TRY(c, hipMemcpyAsync(c->hb_meta, pin, t_rows, hipMemcpyHostToDevice, c->stream));
     c->xfer_ctr.h2d_bytes += t_rows;
     FilterIo io;
+    io.bytes_keys = bytes_keys;
     io.d_atts = c->hb_meta + t_atts; io.d_keys = c->hb_meta + t_keys; io.nkeys = f->nkeys; io.max_att = max_att;
     io.count_only = count_only; io.d_blocks = (cryo_filter_block *)(c->hb_meta + t_rows);
     io.dst_cap = count_only ? 0 : dst_cap; io.rec_cap = count_only ? 0 : rec_cap;
@@ -2356,9 +2453,11 @@ static int agg_blocks_impl(cryo_codec *c, int method, const void *const *h_src, 
     if (n == 0) return CRYO_OK;
     if (!h_src || !h_src_size || !h_blocks || !h_cells) return CRYO_E_ARG;
     ScopedLocalCpus numa_(n * block_size >= ((size_t)8 << 20) ? c : nullptr);
-    /* the descriptors and the results: [atts 4 x natts][keys 16 x nkeys][cols 8 x ncols][rows 16 x n][cells 40 x n x ncols], each
-     * part 16-byte aligned */
-    const size_t t_atts = 0, t_keys = ((size_t)f->natts * 4 + 15) & ~(size_t)15, t_cols = t_keys + (size_t)f->nkeys * 16;
+    /* the descriptors and the results: [atts 4 x natts][keys 16 x nkeys][byte-string constants][cols 8 x ncols][rows 16 x n]
+     * [cells 40 x n x ncols], each part 16-byte aligned */
+    bool bytes_keys = false;
+    const size_t t_atts = 0, t_keys = ((size_t)f->natts * 4 + 15) & ~(size_t)15;
+    const size_t t_cols = t_keys + (size_t)f->nkeys * 16 + key_consts_bytes(f->keys, f->nkeys, &bytes_keys);
     const size_t t_rows = t_cols + (((size_t)agg->ncols * 8 + 15) & ~(size_t)15);
     const size_t rows_bytes = n * sizeof(cryo_agg_block), cells_bytes = n * agg->ncols * sizeof(cryo_agg_cell);
     size_t streams = (n * 12 + 63) & ~(size_t)63; /* what stage_streams lays out in the pinned buffer */
@@ -2373,13 +2472,13 @@ static int agg_blocks_impl(cryo_codec *c, int method, const void *const *h_src, 
     uint8_t *pin = (uint8_t *)c->pin + p_tbl;
     memset(pin, 0, t_rows);
     memcpy(pin + t_atts, f->atts, (size_t)f->natts * 4);
-    if (f->nkeys) memcpy(pin + t_keys, f->keys, (size_t)f->nkeys * 16);
+    (void)key_table_host(pin + t_keys, c->hb_meta + t_keys, f);
     memcpy(pin + t_cols, agg->cols, (size_t)agg->ncols * 8);
     HIP_TRY(c, hipMemcpyAsync(c->hb_meta, pin, t_rows, hipMemcpyHostToDevice, c->stream));
     c->xfer_ctr.h2d_bytes += t_rows;
     AggIo io;
     io.d_atts = c->hb_meta + t_atts; io.d_keys = c->hb_meta + t_keys; io.d_cols = c->hb_meta + t_cols;
-    io.nkeys = f->nkeys; io.ncols = agg->ncols; io.max_att = max_att;
+    io.nkeys = f->nkeys; io.ncols = agg->ncols; io.max_att = max_att; io.bytes_keys = bytes_keys;
     io.d_blocks = (cryo_agg_block *)(c->hb_meta + t_rows);
     io.d_cells = (cryo_agg_cell *)(c->hb_meta + t_rows + rows_bytes);
     rc = agg_pass(c, method, c->hb_src, (const uint64_t *)(c->hb_src + sg.o_off), (const uint32_t *)(c->hb_src + sg.o_sz),
@@ -2434,11 +2533,14 @@ static int group_blocks_impl(cryo_codec *c, int method, const void *const *h_src
     if (n == 0) return CRYO_OK;
     if (!h_src || !h_src_size || !h_blocks || (group_cap > 0 && (!h_groups || (ncols > 0 && !h_cells)))) return CRYO_E_ARG;
     ScopedLocalCpus numa_(n * block_size >= ((size_t)8 << 20) ? c : nullptr);
-    /* the descriptors and the results: [atts 4 x natts][keys 16 x nkeys][slots 8 x 6][total 16][rows 32 x n][records 24 x cap]
-     * [cells 40 x cap x ncols], each part 8-byte aligned, the rows 16; cap: what the caller has room for, at most the worst case */
+    /* the descriptors and the results: [atts 4 x natts][keys 16 x nkeys][byte-string constants][slots 8 x 6][total 16][rows 32 x n]
+     * [records 24 x cap][cells 40 x cap x ncols], each part 8-byte aligned, the rows 16; cap: what the caller has room for, at most
+     * the worst case */
+    bool bytes_keys = false;
     const size_t worst = n * (size_t)cryo::filter_side_stride((uint32_t)block_size);
     const size_t cap = group_cap < worst ? group_cap : worst;
-    const size_t t_atts = 0, t_keys = ((size_t)f->natts * 4 + 15) & ~(size_t)15, t_slots = t_keys + (size_t)f->nkeys * 16;
+    const size_t t_atts = 0, t_keys = ((size_t)f->natts * 4 + 15) & ~(size_t)15;
+    const size_t t_slots = t_keys + (size_t)f->nkeys * 16 + key_consts_bytes(f->keys, f->nkeys, &bytes_keys);
     const size_t t_total = t_slots + 48, t_rows = t_total + 16;
     const size_t rows_bytes = n * sizeof(cryo_group_block), t_recs = t_rows + rows_bytes, t_cells = t_recs + cap * sizeof(cryo_group_rec);
     size_t streams = (n * 12 + 63) & ~(size_t)63; /* what stage_streams lays out in the pinned buffer */
@@ -2453,14 +2555,14 @@ static int group_blocks_impl(cryo_codec *c, int method, const void *const *h_src
     uint8_t *pin = (uint8_t *)c->pin + p_tbl;
     memset(pin, 0, t_total);
     memcpy(pin + t_atts, f->atts, (size_t)f->natts * 4);
-    if (f->nkeys) memcpy(pin + t_keys, f->keys, (size_t)f->nkeys * 16);
+    (void)key_table_host(pin + t_keys, c->hb_meta + t_keys, f);
     memcpy(pin + t_slots, grp->by, (size_t)grp->nby * 8);
     if (ncols) memcpy(pin + t_slots + 16, agg->cols, (size_t)ncols * 8);
     HIP_TRY(c, hipMemcpyAsync(c->hb_meta, pin, t_total, hipMemcpyHostToDevice, c->stream));
     c->xfer_ctr.h2d_bytes += t_total;
     GroupIo io;
     io.d_atts = c->hb_meta + t_atts; io.d_keys = c->hb_meta + t_keys; io.d_slots = c->hb_meta + t_slots;
-    io.nkeys = f->nkeys; io.nby = grp->nby; io.ncols = ncols; io.max_att = max_att;
+    io.nkeys = f->nkeys; io.nby = grp->nby; io.ncols = ncols; io.max_att = max_att; io.bytes_keys = bytes_keys;
     io.d_total = (uint64_t *)(c->hb_meta + t_total);
     io.d_blocks = (cryo_group_block *)(c->hb_meta + t_rows);
     io.d_groups = (cryo_group_rec *)(c->hb_meta + t_recs);

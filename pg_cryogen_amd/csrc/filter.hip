@@ -9,7 +9,9 @@
  *                     the fetch's ITEM rule, the TUPLE rule on the tuple's header, then the walk over the columns 1 .. the
  *                     highest key column.  That loop is the same trip for all 64 lanes -- the column descriptor and the keys
  *                     are read at addresses that depend on the loop counter only, so they are uniform loads; what differs per
- *                     lane is the offset, the null bit and the varlena branch.  Keys are evaluated as the walk passes their
+ *                     lane is the offset, the null bit and the varlena branch.  A byte-string key (CRYO_KEY_BYTES) reads its
+ *                     constant the same way, a word per trip, and the payload bytewise; a descriptor with one runs
+ *                     k_filter_match<true>, every other k_filter_match<false>.  Keys are evaluated as the walk passes their
  *                     column (the walk itself is filter_walk.h's, shared with agg.hip).  A key's value is loaded at its proven alignment (tuples start at multiples of 8, hoff is one,
  *                     attalign >= attlen is the argument rule); everything else of a tuple is read bytewise or, the three header
  *                     fields, at their fixed even offsets.  No load leaves [t, t + len): every read is preceded by its bound.
@@ -34,16 +36,18 @@ namespace cryo {
 
 constexpr uint32_t kFilterPiece = 256u * 8u;  /* packed bytes one workgroup copies per turn */
 
-/* the walk of filter_walk.h without capture: 0 a match, kFilterNoMatch, or kFilterTuple */
+/* the walk of filter_walk.h without capture: 0 a match, kFilterNoMatch, kFilterTuple or -- BYTES -- kFilterUndecided */
+template <bool BYTES>
 __device__ inline uint32_t filter_tuple(const uint8_t *__restrict__ t, uint32_t len, bool live, const FilterAtt *__restrict__ atts,
                                         const FilterKey *__restrict__ keys, uint32_t nkeys, uint32_t max_att)
 {
-    return walk_tuple<false>(t, len, live, atts, keys, nkeys, max_att, nullptr, 0u, nullptr);
+    return walk_tuple<false>(t, len, live, atts, keys, nkeys, max_att, nullptr, 0u, nullptr, WalkKeys<BYTES>());
 }
 
 /* One sweep over a block's items.  WRITE = false: the sums {MAXALIGNed bytes of the matches, matches, bad items}.  WRITE = true:
- * the side table's entries in position order; `overlap` drops the matches. */
-template <bool WRITE>
+ * the side table's entries in position order; `overlap` drops the matches.  An undecided tuple is a bad item: counted, and listed
+ * with its status and no bytes. */
+template <bool WRITE, bool BYTES>
 __device__ inline void filter_sweep(const uint8_t *__restrict__ p, uint32_t B, uint32_t n, uint32_t upper, uint32_t lane,
                                     const FilterAtt *__restrict__ atts, const FilterKey *__restrict__ keys, uint32_t nkeys,
                                     uint32_t max_att, bool overlap, uint4 *__restrict__ side, uint64_t &bytes, uint32_t &n_match,
@@ -62,9 +66,9 @@ __device__ inline void filter_sweep(const uint8_t *__restrict__ p, uint32_t B, u
             else { len = it.y; src = it.x; }
         }
         const bool live = valid && status != kFilterItem;
-        const uint32_t verdict = filter_tuple(p + src, len, live, atts, keys, nkeys, max_att);
+        const uint32_t verdict = filter_tuple<BYTES>(p + src, len, live, atts, keys, nkeys, max_att);
         if (live) status = verdict;
-        const bool match = status == 0u, bad = status == kFilterItem || status == kFilterTuple;
+        const bool match = status == 0u, bad = status == kFilterItem || status == kFilterTuple || (BYTES && status == kFilterUndecided);
         const unsigned long long mm = __ballot(match), mb = __ballot(bad);
         if (WRITE) {
             const bool rec = bad || (match && !overlap);
@@ -96,6 +100,7 @@ __device__ inline void filter_sweep(const uint8_t *__restrict__ p, uint32_t B, u
     n_bad = bads;
 }
 
+template <bool BYTES>
 __global__ void __launch_bounds__(256)
 k_filter_match(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, uint32_t cnt,
                const int32_t *__restrict__ dec_status, const FilterAtt *__restrict__ atts, const FilterKey *__restrict__ keys,
@@ -119,12 +124,12 @@ k_filter_match(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B,
             status = kFilterHeader;
         else {
             n_items = n; /* lower <= B: n <= side_stride */
-            filter_sweep<false>(p, B, n, upper, lane, atts, keys, nkeys, max_att, false, nullptr, bytes, n_match, n_bad);
+            filter_sweep<false, BYTES>(p, B, n, upper, lane, atts, keys, nkeys, max_att, false, nullptr, bytes, n_match, n_bad);
             if (!count_only) {
                 const bool overlap = bytes > (uint64_t)(B - upper);
                 uint64_t b2;
                 uint32_t m2, x2;
-                filter_sweep<true>(p, B, n, upper, lane, atts, keys, nkeys, max_att, overlap, side + (uint64_t)k * side_stride, b2,
+                filter_sweep<true, BYTES>(p, B, n, upper, lane, atts, keys, nkeys, max_att, overlap, side + (uint64_t)k * side_stride, b2,
                                    m2, x2);
                 if (overlap) { status = kFilterOverlap; n_match = 0; bytes = 0; }
             }
@@ -255,7 +260,7 @@ k_filter_copy(uint32_t cnt, const uint8_t *__restrict__ dec, uint64_t dec_stride
 
 hipError_t launch_filter(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
                          const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, uint32_t max_att,
-                         bool count_only, uint4 *d_blocks, uint4 *d_side, uint64_t *d_sum, uint64_t *d_base, uint64_t *d_running,
+                         bool bytes_keys, bool count_only, uint4 *d_blocks, uint4 *d_side, uint64_t *d_sum, uint64_t *d_base, uint64_t *d_running,
                          uint8_t *d_dst, uint64_t dst_cap, uint2 *d_rec, uint64_t rec_cap, bool chunk_relative, int cus)
 {
     if (cnt == 0) return hipSuccess;
@@ -264,9 +269,10 @@ hipError_t launch_filter(hipStream_t s, const uint8_t *d_dec, uint64_t dec_strid
         nkeys > 4u)
         return hipErrorInvalidValue;
     const uint32_t stride = filter_side_stride(block_size);
-    hipLaunchKernelGGL(k_filter_match, dim3((cnt + 3u) / 4u), dim3(256), 0, s, d_dec, dec_stride, block_size, cnt, d_dec_status,
-                       (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys, max_att, count_only ? 1u : 0u, stride, d_blocks,
-                       d_side, d_sum);
+    /* the integer-only descriptor keeps its own instantiation: the code it had before byte-string keys */
+    hipLaunchKernelGGL(bytes_keys ? k_filter_match<true> : k_filter_match<false>, dim3((cnt + 3u) / 4u), dim3(256), 0, s, d_dec,
+                       dec_stride, block_size, cnt, d_dec_status, (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys, max_att,
+                       count_only ? 1u : 0u, stride, d_blocks, d_side, d_sum);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || count_only) return e;
     hipLaunchKernelGGL(k_filter_offsets, dim3(1), dim3(256), 0, s, cnt, d_sum, d_base, d_running, d_blocks);

@@ -4,7 +4,8 @@
  * for the aggregate and the grouping -- the capture of column values as the walk passes them ("aggregating a scan", "grouping a
  * scan").  One statement of the walk: the filter instantiates it without capture, and the capture costs it nothing (the same
  * registers, no scratch).  The number of capture slots is a template parameter: four for the aggregate, six for the grouping (two
- * group columns and four aggregate columns).
+ * group columns and four aggregate columns).  Byte-string keys (CRYO_KEY_BYTES) are a second instantiation, chosen by the host when
+ * a descriptor has one: a descriptor of integer keys and null tests alone runs the code it ran before those keys existed.
  */
 #pragma once
 #include <hip/hip_runtime.h>
@@ -13,7 +14,10 @@
 namespace cryo {
 
 constexpr uint32_t kFilterStream = 1, kFilterHeader = 2, kFilterItem = 3, kFilterOverlap = 7, kFilterTuple = 8; /* statuses */
+constexpr uint32_t kFilterUndecided = 9;       /* a status too: a byte-string key met a value whose bytes are not in the tuple */
 constexpr uint32_t kFilterNoMatch = 0xFFFFu;  /* inside the kernels only: a good tuple that fails a key */
+constexpr uint32_t kKeyBytes = 16u;           /* CRYO_KEY_BYTES */
+constexpr uint32_t kWalkNoBytes = 0xFFFFFFFFu; /* inside the walk only: the payload length of a varlena without in-line bytes */
 constexpr uint32_t kOpLt = 1, kOpLe = 2, kOpEq = 3, kOpGe = 4, kOpGt = 5, kOpNe = 6, kOpIsNull = 7, kOpNotNull = 8;
 constexpr uint32_t kAggMaxCols = 4u;
 
@@ -27,6 +31,7 @@ static_assert(sizeof(FilterAtt) == 4 && sizeof(FilterKey) == 16 && sizeof(AggCol
 template <uint32_t SLOTS> struct WalkCaptureN { int64_t v[SLOTS]; uint32_t has; };
 using WalkCapture = WalkCaptureN<kAggMaxCols>; /* the aggregate's */
 template <class T> struct WalkPlain { using type = T; }; /* keeps SLOTS out of deduction: the filter passes a null capture */
+template <bool BYTES> struct WalkKeys {};                /* a tag: whether the keys may hold a CRYO_KEY_BYTES entry */
 
 __device__ inline bool filter_compare(uint32_t op, int64_t v, int64_t k)
 {
@@ -49,19 +54,47 @@ __device__ inline int64_t walk_value(const uint8_t *__restrict__ p, int32_t attl
     return *reinterpret_cast<const int64_t *>(p);
 }
 
-/* The verdict on one tuple of len bytes at t (8-byte aligned): 0 a match, kFilterNoMatch, or kFilterTuple.  `live` is false in
+/* A number with the sign of (payload, constant) in the order of the byte-string keys: memcmp over the shorter length on unsigned bytes, then the
+ * lengths.  p: the plen payload bytes, anywhere; kc: the constant's n bytes, 8-byte aligned and zero-padded to a multiple of 8 (the
+ * host's copy), read a word per trip at addresses that depend on the trip alone -- a uniform load -- and the trip count is n's.
+ * The payload is read bytewise and never past plen: its pad up to MAXALIGN is not the column's.  A lane that is not `on`, whose
+ * sign is known already, or -- by_len: the op is = or <> -- whose length differs from n loads nothing. */
+__device__ inline int32_t walk_bytes_sign(const uint8_t *__restrict__ p, uint32_t plen, bool on, const uint64_t *__restrict__ kc,
+                                          uint32_t n, bool by_len)
+{
+    uint32_t m = plen < n ? plen : n; /* the bytes memcmp looks at */
+    if (!on || (by_len && plen != n)) m = 0;
+    int32_t c = 0;
+    for (uint32_t w = 0; w < n; w += 8u) {
+        const uint64_t kw = kc[w >> 3]; /* uniform */
+        if (c != 0 || w >= m) continue;
+        const uint32_t r = m - w; /* 1 .. : the bytes of this word that count */
+#pragma unroll
+        for (uint32_t j = 0; j < 8u; j++) {
+            if (j >= r) continue;
+            const int32_t d = (int32_t)p[w + j] - (int32_t)((uint32_t)(kw >> (8u * j)) & 0xFFu);
+            c = c != 0 ? c : d; /* the first byte that differs decides */
+        }
+    }
+    if (c == 0) c = plen < n ? -1 : plen > n ? 1 : 0;
+    return c;
+}
+
+/* The verdict on one tuple of len bytes at t (8-byte aligned): 0 a match, kFilterNoMatch, kFilterTuple or -- BYTES alone --
+ * kFilterUndecided.  `live` is false in
  * lanes without a tuple: they make the same trips and load nothing.  Invariant of the walk: hoff + o <= len.  CAPTURE: the walk
  * also notes the value of each of the ncols <= SLOTS columns cols[] names (their att <= max_att, attlen the type's size and
  * attalign at least that: the aggregate's argument rule; an att of 0 names no column) in *cap; cols is read at addresses that
- * depend on the loop counters only. */
-template <bool CAPTURE, uint32_t SLOTS = kAggMaxCols>
+ * depend on the loop counters only.  BYTES: a key of type kKeyBytes compares the column's in-line payload with the rsv bytes at
+ * value (walk_bytes_sign); without BYTES no key has that type. */
+template <bool CAPTURE, uint32_t SLOTS = kAggMaxCols, bool BYTES = false>
 __device__ inline uint32_t walk_tuple(const uint8_t *__restrict__ t, uint32_t len, bool live, const FilterAtt *__restrict__ atts,
                                       const FilterKey *__restrict__ keys, uint32_t nkeys, uint32_t max_att,
                                       const AggCol *__restrict__ cols, uint32_t ncols,
-                                      typename WalkPlain<WalkCaptureN<SLOTS>>::type *cap)
+                                      typename WalkPlain<WalkCaptureN<SLOTS>>::type *cap, WalkKeys<BYTES> = WalkKeys<false>())
 {
     uint32_t tnatts = 0, hoff = 0;
-    bool hasnull = false, bad = false, pass = true;
+    bool hasnull = false, bad = false, pass = true, undecided = false;
     if (live) {
         if (len < 23u) bad = true;
         else {
@@ -81,7 +114,7 @@ __device__ inline uint32_t walk_tuple(const uint8_t *__restrict__ t, uint32_t le
         if (on && col <= tnatts) /* the bitmap's byte lies below hoff: the TUPLE rule */
             isnull = hasnull && ((t[23u + ((col - 1u) >> 3)] >> ((col - 1u) & 7u)) & 1u) == 0;
         const bool here = on && !isnull;
-        uint32_t size = 0;
+        uint32_t size = 0, head = 0; /* head: the varlena's header bytes, kWalkNoBytes when its bytes are not in the tuple */
         if (a.attlen > 0) {
             if (here) {
                 size = (uint32_t)a.attlen;
@@ -98,11 +131,15 @@ __device__ inline uint32_t walk_tuple(const uint8_t *__restrict__ t, uint32_t le
                     if (b == 1u) { /* external: 18 bytes when on-disk TOAST */
                         if (len - pos < 2u || t[pos + 1u] != 18u) bad = true;
                         else size = 18u;
-                    } else if (b & 1u) size = b >> 1;
-                    else if (len - pos < 4u) bad = true;
+                        if (BYTES) head = kWalkNoBytes;
+                    } else if (b & 1u) {
+                        size = b >> 1;
+                        if (BYTES) head = 1u;
+                    } else if (len - pos < 4u) bad = true;
                     else {
                         size = (b | (uint32_t)t[pos + 1u] << 8 | (uint32_t)t[pos + 2u] << 16 | (uint32_t)t[pos + 3u] << 24) >> 2;
                         if (size < 4u) bad = true;
+                        if (BYTES) head = (b & 2u) ? kWalkNoBytes : 4u; /* bit 1 of an even header: compressed in line */
                     }
                     if (!bad && size > len - pos) bad = true;
                 }
@@ -114,7 +151,15 @@ __device__ inline uint32_t walk_tuple(const uint8_t *__restrict__ t, uint32_t le
             if (key.att != col) continue;
             if (key.op == kOpIsNull) pass = pass && isnull;
             else if (key.op == kOpNotNull) pass = pass && !isnull;
-            else {
+            else if (BYTES && key.type == kKeyBytes) {
+                /* the column is a varlena (the argument rule) and [pos, pos + size) lies below len */
+                const bool inl = val && head != kWalkNoBytes;
+                const int32_t c = walk_bytes_sign(t + pos + (inl ? head : 0u), inl ? size - head : 0u, inl,
+                                                  reinterpret_cast<const uint64_t *>(key.value), key.rsv,
+                                                  key.op == kOpEq || key.op == kOpNe);
+                if (val && !inl) undecided = true; /* neither true nor false */
+                else pass = pass && val && filter_compare(key.op, c, 0);
+            } else {
                 /* attlen is the key type's size and pos a multiple of it: the argument rule */
                 const int64_t v = val ? walk_value(t + pos, a.attlen) : 0;
                 pass = pass && val && filter_compare(key.op, v, key.value);
@@ -131,7 +176,7 @@ __device__ inline uint32_t walk_tuple(const uint8_t *__restrict__ t, uint32_t le
         }
         if (val) pos += size;
     }
-    return bad ? kFilterTuple : pass ? 0u : kFilterNoMatch;
+    return bad ? kFilterTuple : !pass ? kFilterNoMatch : (BYTES && undecided) ? kFilterUndecided : 0u;
 }
 
 } // namespace cryo

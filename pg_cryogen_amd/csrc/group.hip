@@ -23,7 +23,8 @@
  *                         run has at most 290 values, so neither half overflows), and writes the group's record and cells to the
  *                         block's row of a side area in handle workspace.
  *                    Descriptor, keys and columns are read at addresses that depend on loop counters only (uniform loads); no
- *                    load leaves [t, t + len).
+ *                    load leaves [t, t + len).  A descriptor with a byte-string key runs k_group_block<true>, whose walk compares
+ *                    those too and counts an undecided tuple in n_bad; every other descriptor runs k_group_block<false>.
  *   k_group_offsets  one workgroup per chunk: the scan of k_filter_offsets over one array, the blocks' n_groups, from the running
  *                    total the chunk before left in device memory; it writes first_group into the rows.
  *   k_group_copy     a grid stride over the blocks: block k's records and cells from the side area to first_group of the call's
@@ -61,6 +62,7 @@ __device__ inline void group_wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+template <bool BYTES>
 __global__ void __launch_bounds__(64 * kGroupWaves)
 k_group_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, uint32_t cnt, const int32_t *__restrict__ dec_status,
               const FilterAtt *__restrict__ atts, const FilterKey *__restrict__ keys, uint32_t nkeys,
@@ -105,9 +107,10 @@ k_group_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, 
 #pragma unroll
                 for (uint32_t j = 0; j < kGroupSlots; j++) cap.v[j] = 0;
                 const uint32_t walked =
-                    walk_tuple<true, kGroupSlots>(p + src, len, live, atts, keys, nkeys, max_att, slots, kGroupSlots, &cap);
+                    walk_tuple<true, kGroupSlots>(p + src, len, live, atts, keys, nkeys, max_att, slots, kGroupSlots, &cap, WalkKeys<BYTES>());
                 if (live) verdict = walked;
-                const bool match = verdict == 0u, bad = verdict == kFilterItem || verdict == kFilterTuple;
+                const bool match = verdict == 0u,
+                           bad = verdict == kFilterItem || verdict == kFilterTuple || (BYTES && verdict == kFilterUndecided);
                 const unsigned long long mm = __ballot(match);
                 if (match) {
                     const uint32_t at = n_match + (uint32_t)__popcll(mm & below); /* below n <= 290 */
@@ -268,7 +271,7 @@ k_group_copy(uint32_t cnt, uint32_t side_stride, uint32_t ncols, const uint4 *__
 
 hipError_t launch_group(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
                         const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,
-                        uint32_t nby, uint32_t ncols, uint32_t max_att, uint4 *d_blocks, void *d_side_rec, void *d_side_cell,
+                        uint32_t nby, uint32_t ncols, uint32_t max_att, bool bytes_keys, uint4 *d_blocks, void *d_side_rec, void *d_side_cell,
                         uint64_t *d_running, void *d_rec, void *d_cells, uint64_t group_cap, int cus)
 {
     if (cnt == 0) return hipSuccess;
@@ -279,7 +282,7 @@ hipError_t launch_group(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride
         !d_slots || !d_side_rec || !d_running || (ncols > 0u && !d_side_cell) || (group_cap > 0u && (!d_rec || (ncols > 0u && !d_cells))))
         return hipErrorInvalidValue;
     const uint32_t stride = filter_side_stride(block_size);
-    hipLaunchKernelGGL(k_group_block, dim3((cnt + kGroupWaves - 1u) / kGroupWaves), dim3(64 * kGroupWaves), 0, s, d_dec, dec_stride,
+    hipLaunchKernelGGL(bytes_keys ? k_group_block<true> : k_group_block<false>, dim3((cnt + kGroupWaves - 1u) / kGroupWaves), dim3(64 * kGroupWaves), 0, s, d_dec, dec_stride,
                        block_size, cnt, d_dec_status, (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys,
                        (const AggCol *)d_slots, nby, ncols, max_att, stride, d_blocks, (GroupRec *)d_side_rec,
                        (GroupCell *)d_side_cell);

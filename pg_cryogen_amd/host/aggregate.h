@@ -23,7 +23,8 @@
 #include "cryo_codec.h"
 
 /* one block's partial aggregate; cells: ncols cells in the order of the aggregate descriptor, valid during the callback only.
- * n_bad > 0: the block holds damaged items, which are in no cell -- cryo_filter_scan lists them */
+ * n_bad > 0: the block holds damaged items or -- under a byte-string key -- undecided ones, which are in no cell --
+ * cryo_filter_scan lists them */
 typedef struct {
     BlockNumber block;
     TransactionId created_xid;
@@ -44,7 +45,7 @@ typedef struct {
     uint64 empty_pages;  /* new pages skipped, as a scan skips them */
     uint64 items;        /* items of the blocks the codec looked into */
     uint64 matches;      /* tuples that passed every key */
-    uint64 bad;          /* bad items (CRYO_FETCH_ITEM, CRYO_FILTER_TUPLE) */
+    uint64 bad;          /* bad items (CRYO_FETCH_ITEM, CRYO_FILTER_TUPLE) and undecided ones (CRYO_FILTER_UNDECIDED) */
     uint64 reports;      /* reports made */
     uint64 codec_calls;  /* agg_blocks calls */
     uint64 bytes_back;   /* what the calls brought back: rows and cells */

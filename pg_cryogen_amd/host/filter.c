@@ -123,6 +123,7 @@ static int window_flush(const CryoCodecOps *ops, const CryoCodecFilterOps *fops,
         for (r = row->rec_first; r < r_end; r++) {
             const cryo_filter_rec *q = &rec[m][r];
             CryoFilteredTuple t;
+            /* any status but OK is passed on as it is: ITEM, TUPLE, and UNDECIDED under a byte-string key */
             if (q->status != CRYO_FETCH_OK) { say(j, e->block, q->status, q->pos); continue; }
             if (q->len == 0 || at + MAXALIGN(q->len) > total[m][0]) { rc = CRYO_E_HIP; break; } /* not a placement */
             t.block = e->block;

@@ -29,7 +29,8 @@ typedef struct {
 } CryoFilteredTuple;
 
 /* reason: a block's status (CRYO_FETCH_STREAM, CRYO_FETCH_HEADER, CRYO_FETCH_OVERLAP: detail 0), a bad item's
- * (CRYO_FETCH_ITEM, CRYO_FILTER_TUPLE: detail = its position), or one of check.h's host-side reasons (CRYO_CHECK_CHAIN: detail =
+ * (CRYO_FETCH_ITEM, CRYO_FILTER_TUPLE, or CRYO_FILTER_UNDECIDED -- a byte-string key met a compressed or external value, the
+ * caller fetches the tuple and rechecks it: detail = its position), or one of check.h's host-side reasons (CRYO_CHECK_CHAIN: detail =
  * the CryoError of cryo_stage_read_chain; CRYO_CHECK_METHOD: detail = the method the first page names) */
 typedef struct {
     BlockNumber block;
@@ -41,7 +42,7 @@ typedef struct {
     uint64 empty_pages;  /* new pages skipped, as a scan skips them */
     uint64 items;        /* items of the blocks the codec looked into */
     uint64 matches;      /* tuples that passed every key (delivered, unless CRYO_FILTER_COUNT_ONLY) */
-    uint64 bad;          /* bad items (CRYO_FETCH_ITEM, CRYO_FILTER_TUPLE) */
+    uint64 bad;          /* bad items (CRYO_FETCH_ITEM, CRYO_FILTER_TUPLE) and undecided ones (CRYO_FILTER_UNDECIDED) */
     uint64 reports;      /* reports made */
     uint64 codec_calls;  /* filter_blocks calls */
     uint64 bytes_back;   /* what the calls brought back: the block table, records and packed tuples */

@@ -28,8 +28,8 @@
 #include "cryo_codec.h"
 
 /* one block's groups: recs n_groups records in the contract's order (ascending, NULLS LAST), cells n_groups * ncols cells (group
- * g's at g * ncols; NULL when ncols == 0); both valid during the callback only.  n_bad > 0: the block holds damaged items, which
- * are in no group -- cryo_filter_scan lists them */
+ * g's at g * ncols; NULL when ncols == 0); both valid during the callback only.  n_bad > 0: the block holds damaged items or --
+ * under a byte-string key -- undecided ones, which are in no group -- cryo_filter_scan lists them */
 typedef struct {
     BlockNumber block;
     TransactionId created_xid;
@@ -49,7 +49,7 @@ typedef struct {
     uint64 empty_pages;  /* new pages skipped, as a scan skips them */
     uint64 items;        /* items of the blocks the codec looked into */
     uint64 matches;      /* tuples that passed every key */
-    uint64 bad;          /* bad items (CRYO_FETCH_ITEM, CRYO_FILTER_TUPLE) */
+    uint64 bad;          /* bad items (CRYO_FETCH_ITEM, CRYO_FILTER_TUPLE) and undecided ones (CRYO_FILTER_UNDECIDED) */
     uint64 reports;      /* reports made */
     uint64 codec_calls;  /* group_blocks calls */
     uint64 bytes_back;   /* what the calls brought back: rows, records and cells */
