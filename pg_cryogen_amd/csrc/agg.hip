@@ -6,8 +6,8 @@
  * tuples that pass the keys it reduces up to four of their integer columns, so that a row and a few cells per block leave the
  * device:
  *   k_agg_block   one wave per block, four blocks per workgroup, as k_filter_match.  A block the decoders rejected gets STREAM
- *                 without a load, a bad header HEADER.  Otherwise a lane takes one item per turn (290 items: five turns): the
- *                 ITEM rule, then the walk of filter_walk.h over the columns 1 .. max(highest key column, highest aggregate
+ *                 without a load, a bad header (heap_header, heap_block.h) HEADER.  Otherwise a lane takes one item per turn (290 items: five turns): the
+ *                 ITEM rule (heap_item), then the walk of filter_walk.h over the columns 1 .. max(highest key column, highest aggregate
  *                 column), which tests the keys and notes the aggregate columns' values as it passes them.  Descriptor, keys and
  *                 aggregate columns are read at addresses that depend on loop counters only (uniform loads); no load leaves
  *                 [t, t + len).  A descriptor with a byte-string key runs k_agg_block<true>, whose walk compares those too and
@@ -48,9 +48,8 @@ k_agg_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, ui
     else {
         const uint8_t *p = dec + (uint64_t)k * dec_stride;
         const uint2 hdr = *reinterpret_cast<const uint2 *>(p);
-        const uint32_t lower = hdr.x, upper = hdr.y;
-        const uint32_t n = (lower - 8u) >> 3;
-        if (lower < 8u || (lower & 7u) != 0u || n > kFilterMaxItems || lower > upper || upper > B || (n == 0u && upper != B))
+        uint32_t n, upper;
+        if (!heap_header(hdr, B, n, upper))
             status = kFilterHeader;
         else {
             n_items = n;
@@ -60,9 +59,7 @@ k_agg_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, ui
                 uint32_t verdict = kFilterNoMatch, len = 0, src = 0;
                 if (valid) {
                     const uint2 it = *reinterpret_cast<const uint2 *>(p + 8u + 8u * i); /* 8 + 8 n = lower <= B */
-                    const uint64_t off = it.x, ln = it.y;
-                    if (ln == 0 || (off & 7u) != 0 || off < upper || off + ((ln + 7u) & ~(uint64_t)7u) > B) verdict = kFilterItem;
-                    else { len = it.y; src = it.x; }
+                    if (!heap_item(it, upper, B, src, len)) verdict = kFilterItem;
                 }
                 const bool live = valid && verdict != kFilterItem;
                 WalkCapture cap;

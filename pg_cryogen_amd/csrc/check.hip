@@ -4,7 +4,7 @@
  * The host (cryo_codec.cpp, check_pass) decodes a batch with the automatic decode routes into handle workspace, the shared
  * decode loop of write verification (decode_pass); on every decoded chunk these kernels apply the layout rules of
  * cryo_init_page / cryo_storage_insert (host/storage.c) to each block:
- *   k_check_items  one wave per block, one lane per item (up to five items per lane): the header rule, the item rule of
+ *   k_check_items  one wave per block, one lane per item (up to five items per lane): the header rule (heap_block.h), the chain rule of
  *                  every item against its stored predecessor (the predecessor's offset comes from the neighbouring lane,
  *                  so each item is read once), the lowest failing item by ballot; when both pass, each tuple's pad is
  *                  checked in the one 8-byte word that holds the tuple's last byte.  It writes the block's verdict, the
@@ -23,8 +23,7 @@ namespace cryo {
 
 constexpr uint32_t kCheckNone = 0xffffffffu;
 constexpr uint32_t kCheckOk = 0, kCheckStream = 1, kCheckHeader = 2, kCheckItem = 3, kCheckNonzero = 4; /* cryo_check_reason */
-constexpr uint32_t kCheckMaxItems = 290u;                 /* MaxHeapTuplesPerPage - 1 (host/storage.c) */
-constexpr uint32_t kCheckItemTurns = (kCheckMaxItems + 63u) / 64u;
+constexpr uint32_t kCheckItemTurns = (kHeapMaxItems + 63u) / 64u;
 constexpr uint32_t kCheckLoads = 4;
 constexpr uint32_t kCheckPiece = 256u * 16u * kCheckLoads; /* bytes of a block one workgroup of k_check_zero covers */
 
@@ -42,9 +41,9 @@ k_check_items(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, 
     }
     const uint8_t *p = dec + (uint64_t)k * dec_stride;
     const uint2 hdr = *reinterpret_cast<const uint2 *>(p);
-    const uint32_t lower = hdr.x, upper = hdr.y;
-    const uint32_t n = (lower - 8u) >> 3;
-    if (lower < 8u || (lower & 7u) != 0u || n > kCheckMaxItems || lower > upper || upper > B || (n == 0u && upper != B)) {
+    const uint32_t lower = hdr.x;
+    uint32_t n, upper;
+    if (!heap_header(hdr, B, n, upper)) {
         if (lane == 0) { verdict[k] = make_uint2(kCheckHeader, 0u); gap[k] = make_uint2(0u, 0u); first[k] = kCheckNone; }
         return;
     }

@@ -359,6 +359,17 @@ int ensure_ws(cryo_codec *c, size_t need)
     return CRYO_OK;
 }
 
+/* a host-buffer entry point: the call behind the exception guard, then the handle's device memory trimmed (ws_trim_after_call) */
+template <class F>
+int host_call(cryo_codec *c, F &&f)
+{
+    return guarded([&] {
+        const int rc = f();
+        if (c) ws_trim_after_call(c);
+        return rc;
+    });
+}
+
 } // namespace
 
 extern "C" {
@@ -892,6 +903,14 @@ struct DecodePass {
     const uint64_t *d_comp_off = nullptr;
     uint64_t comp_stride = 0;
     const uint32_t *d_comp_size = nullptr;
+    /* the pass counts nowhere: decode_pass leaves cryo_codec_counters as it found them, whatever way it returns.  Not set by
+     * write verification (its decodes count as launches of the compress call that asked for it) nor by recompression (its
+     * encodes count as any compress does) */
+    bool quiet = false;
+    DecodePass() = default;
+    /* decode from the caller's stream table */
+    DecodePass(const uint8_t *d_src, const uint64_t *d_src_off, const uint32_t *d_src_size, bool quiet_)
+        : d_comp(d_src), d_comp_off(d_src_off), d_comp_size(d_src_size), quiet(quiet_) {}
     uint64_t fixed = 0;          /* bytes of DecodeChunk::fixed */
     uint64_t own_per_block = 0;  /* bytes per block of DecodeChunk::own */
     /* before a chunk's decodes: fill its stream table (off, sz; the edge blocks' at entries cnt, cnt + 1); none: the decoders
@@ -910,7 +929,7 @@ struct DecodePass {
 };
 } // namespace
 
-static int decode_pass(cryo_codec *c, int method, uint32_t B, uint64_t n, const DecodePass &ps)
+static int decode_chunks(cryo_codec *c, int method, uint32_t B, uint64_t n, const DecodePass &ps)
 {
     uint8_t **buf = ps.buf ? ps.buf : &c->d_vfy;
     size_t *cap = ps.cap ? ps.cap : &c->vfy_cap;
@@ -992,6 +1011,14 @@ static int decode_pass(cryo_codec *c, int method, uint32_t B, uint64_t n, const 
     return CRYO_OK;
 }
 
+static int decode_pass(cryo_codec *c, int method, uint32_t B, uint64_t n, const DecodePass &ps)
+{
+    const cryo_codec_counters keep = c->ctr;
+    const int rc = decode_chunks(c, method, B, n, ps);
+    if (ps.quiet) c->ctr = keep;
+    return rc;
+}
+
 /* ---- write verification ----
  * The shared decode loop over the compressed blocks, then the compare with the raw blocks (verify.hip) and the verdict folded
  * into d_status, chunk by chunk.  The per-block first-mismatch words are the caller's (d_first_user) or held for the whole call
@@ -1027,9 +1054,7 @@ static int check_pass(cryo_codec *c, int method, const uint8_t *d_src, const uin
                       uint32_t B, uint64_t n, cryo_check_result *d_result)
 {
     static_assert(sizeof(cryo_check_result) == sizeof(uint2), "cryo_check_result is the kernels' uint2 {reason, offset}");
-    const cryo_codec_counters keep = c->ctr;
-    DecodePass ps;
-    ps.d_comp = d_src; ps.d_comp_off = d_src_off; ps.d_comp_size = d_src_size;
+    DecodePass ps(d_src, d_src_off, d_src_size, true);
     ps.own_per_block = 8u + 8u + 4u; /* verdict, gap, first nonzero byte */
     ps.run = [&](const DecodeChunk &ch) -> int {
         uint2 *verdict = (uint2 *)ch.own, *gap = verdict + ch.K;
@@ -1037,9 +1062,7 @@ static int check_pass(cryo_codec *c, int method, const uint8_t *d_src, const uin
         HIP_TRY(c, cryo::launch_check(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, verdict, gap, first, (uint2 *)(d_result + ch.lo)));
         return CRYO_OK;
     };
-    const int rc = decode_pass(c, method, B, n, ps);
-    c->ctr = keep;
-    return rc;
+    return decode_pass(c, method, B, n, ps);
 }
 
 static bool check_block_size_ok(size_t block_size) { return block_size >= 16 && block_size % 8 == 0 && block_size <= kMaxBlockSize; }
@@ -1073,11 +1096,9 @@ static int fetch_pass(cryo_codec *c, int method, const uint8_t *d_src, const uin
 {
     static_assert(sizeof(cryo_fetch_result) == sizeof(uint4), "cryo_fetch_result is the kernels' 16-byte record");
     const bool host = io.h_req_first != nullptr;
-    const cryo_codec_counters keep = c->ctr;
     const uint64_t side_bytes = (io.n_req * 8u + 255u) & ~(uint64_t)255u;
     const uint64_t row = ((uint64_t)B + 15u) & ~(uint64_t)15u; /* a block's share of the chunk's staging area */
-    DecodePass ps;
-    ps.d_comp = d_src; ps.d_comp_off = d_src_off; ps.d_comp_size = d_src_size;
+    DecodePass ps(d_src, d_src_off, d_src_size, true);
     ps.fixed = side_bytes + 256u;                 /* side table; the running total of the host-buffer call */
     ps.own_per_block = 32u + (host ? row : 0u);   /* sum u64, K + 1 bases u64 (within 24 K bytes); staging row */
     ps.run = [&](const DecodeChunk &ch) -> int {
@@ -1110,9 +1131,7 @@ static int fetch_pass(cryo_codec *c, int method, const uint8_t *d_src, const uin
         io.h_total = end;
         return CRYO_OK;
     };
-    const int rc = decode_pass(c, method, B, n, ps);
-    c->ctr = keep;
-    return rc;
+    return decode_pass(c, method, B, n, ps);
 }
 
 /* ---- the scan filter ----
@@ -1122,10 +1141,15 @@ static int fetch_pass(cryo_codec *c, int method, const uint8_t *d_src, const uin
  * and, for the host-buffer call, a row of the chunk's staging areas for packed bytes and for records; the pass's fixed bytes hold
  * the host-buffer call's running totals.  Its decodes count nowhere. */
 namespace {
-struct FilterIo {
+/* what every scan call (filter, aggregate, group) tells its kernels about the relation and the keys */
+struct ScanDesc {
     const void *d_atts = nullptr, *d_keys = nullptr; /* device */
-    uint32_t nkeys = 0, max_att = 0;
-    bool count_only = false, bytes_keys = false; /* bytes_keys: d_keys is a key table with a byte-string key */
+    uint32_t nkeys = 0, max_att = 0;                 /* max_att: the highest column the walk has to reach */
+    bool bytes_keys = false;                         /* d_keys is a key table with a byte-string key */
+};
+struct FilterIo {
+    ScanDesc sd;
+    bool count_only = false;
     cryo_filter_block *d_blocks = nullptr;           /* device: n rows */
     uint64_t dst_cap = 0, rec_cap = 0;
     /* device-resident call: the caller's buffers and totals */
@@ -1257,11 +1281,9 @@ static int filter_pass(cryo_codec *c, int method, const uint8_t *d_src, const ui
                       sizeof(cryo_att) == 4 && sizeof(cryo_scan_key) == 16,
                   "the filter's records are the kernels'");
     const bool host = io.host, stage = host && !io.count_only;
-    const cryo_codec_counters keep = c->ctr;
     const uint64_t S = cryo::filter_side_stride(B);
     const uint64_t row = ((uint64_t)B + 15u) & ~(uint64_t)15u; /* a block's share of the chunk's staging area for bytes */
-    DecodePass ps;
-    ps.d_comp = d_src; ps.d_comp_off = d_src_off; ps.d_comp_size = d_src_size;
+    DecodePass ps(d_src, d_src_off, d_src_size, true);
     ps.fixed = 256u;                                                /* the running totals of the host-buffer call */
     ps.own_per_block = 16u * S + 48u + (stage ? row + 8u * S : 0u); /* side; 2 sums, 2 x (K + 1) bases (u64); staging rows */
     ps.run = [&](const DecodeChunk &ch) -> int {
@@ -1271,8 +1293,8 @@ static int filter_pass(cryo_codec *c, int method, const uint8_t *d_src, const ui
         uint8_t *st_dst = ch.own + (16u * S + 48u) * ch.K;
         cryo_filter_rec *st_rec = (cryo_filter_rec *)(st_dst + row * ch.K);
         if (ch.lo == 0) HIP_TRY(c, hipMemsetAsync(running, 0, 2 * sizeof(uint64_t), c->stream));
-        HIP_TRY(c, cryo::launch_filter(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.d_atts, io.d_keys, io.nkeys, io.max_att,
-                                       io.bytes_keys, io.count_only, (uint4 *)(io.d_blocks + ch.lo), side, sum, base, running,
+        HIP_TRY(c, cryo::launch_filter(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.sd.d_atts, io.sd.d_keys, io.sd.nkeys, io.sd.max_att,
+                                       io.sd.bytes_keys, io.count_only, (uint4 *)(io.d_blocks + ch.lo), side, sum, base, running,
                                        stage ? st_dst : io.d_dst, stage ? ch.K * row : io.dst_cap,
                                        stage ? (uint2 *)st_rec : (uint2 *)io.d_rec, stage ? ch.K * S : io.rec_cap, host,
                                        c->lz4_opts.cus));
@@ -1311,9 +1333,7 @@ static int filter_pass(cryo_codec *c, int method, const uint8_t *d_src, const ui
         io.h_recs = rec_end;
         return CRYO_OK;
     };
-    const int rc = decode_pass(c, method, B, n, ps);
-    c->ctr = keep;
-    return rc;
+    return decode_pass(c, method, B, n, ps);
 }
 
 /* ---- the scan aggregate ----
@@ -1322,9 +1342,9 @@ static int filter_pass(cryo_codec *c, int method, const uint8_t *d_src, const ui
  * first block.  The pass asks for no bytes of its own, keeps no totals and waits for nothing.  Its decodes count nowhere. */
 namespace {
 struct AggIo {
-    const void *d_atts = nullptr, *d_keys = nullptr, *d_cols = nullptr; /* device */
-    uint32_t nkeys = 0, ncols = 0, max_att = 0;
-    bool bytes_keys = false;            /* d_keys is a key table with a byte-string key */
+    ScanDesc sd;
+    const void *d_cols = nullptr;       /* device */
+    uint32_t ncols = 0;
     cryo_agg_block *d_blocks = nullptr; /* device: n rows */
     cryo_agg_cell *d_cells = nullptr;   /* device: n * ncols cells */
 };
@@ -1359,18 +1379,14 @@ static int agg_pass(cryo_codec *c, int method, const uint8_t *d_src, const uint6
 {
     static_assert(sizeof(cryo_agg_block) == sizeof(uint4) && sizeof(cryo_agg_cell) == 40 && sizeof(cryo_agg_col) == 8,
                   "the aggregate's records are the kernel's");
-    const cryo_codec_counters keep = c->ctr;
-    DecodePass ps;
-    ps.d_comp = d_src; ps.d_comp_off = d_src_off; ps.d_comp_size = d_src_size;
+    DecodePass ps(d_src, d_src_off, d_src_size, true);
     ps.run = [&](const DecodeChunk &ch) -> int {
-        HIP_TRY(c, cryo::launch_agg(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.d_atts, io.d_keys, io.nkeys, io.d_cols,
-                                    io.ncols, io.max_att, io.bytes_keys, (uint4 *)(io.d_blocks + ch.lo),
+        HIP_TRY(c, cryo::launch_agg(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.sd.d_atts, io.sd.d_keys, io.sd.nkeys, io.d_cols,
+                                    io.ncols, io.sd.max_att, io.sd.bytes_keys, (uint4 *)(io.d_blocks + ch.lo),
                                     io.d_cells + ch.lo * io.ncols));
         return CRYO_OK;
     };
-    const int rc = decode_pass(c, method, B, n, ps);
-    c->ctr = keep;
-    return rc;
+    return decode_pass(c, method, B, n, ps);
 }
 
 /* ---- the grouped scan ----
@@ -1381,11 +1397,10 @@ static int agg_pass(cryo_codec *c, int method, const uint8_t *d_src, const uint6
  * slots when the caller's descriptors come as two arrays.  The pass waits for nothing.  Its decodes count nowhere. */
 namespace {
 struct GroupIo {
-    const void *d_atts = nullptr, *d_keys = nullptr; /* device */
+    ScanDesc sd;
     const void *d_by = nullptr, *d_cols = nullptr;   /* device: the caller's two arrays, or */
     const void *d_slots = nullptr;                   /* device: the six slots laid out already */
-    uint32_t nkeys = 0, nby = 0, ncols = 0, max_att = 0;
-    bool bytes_keys = false;              /* d_keys is a key table with a byte-string key */
+    uint32_t nby = 0, ncols = 0;
     cryo_group_block *d_blocks = nullptr; /* device: n rows */
     cryo_group_rec *d_groups = nullptr;   /* device: group_cap records */
     cryo_agg_cell *d_cells = nullptr;     /* device: group_cap * ncols cells */
@@ -1417,10 +1432,8 @@ static int group_pass(cryo_codec *c, int method, const uint8_t *d_src, const uin
 {
     static_assert(sizeof(cryo_group_block) == 2 * sizeof(uint4) && sizeof(cryo_group_rec) == 24 && sizeof(cryo_group) == 16,
                   "the grouping's records are the kernels'");
-    const cryo_codec_counters keep = c->ctr;
     const uint64_t S = cryo::filter_side_stride(B);
-    DecodePass ps;
-    ps.d_comp = d_src; ps.d_comp_off = d_src_off; ps.d_comp_size = d_src_size;
+    DecodePass ps(d_src, d_src_off, d_src_size, true);
     ps.fixed = 256u;                                                 /* the six column slots */
     ps.own_per_block = S * (sizeof(cryo_group_rec) + io.ncols * sizeof(cryo_agg_cell)); /* the side area */
     ps.run = [&](const DecodeChunk &ch) -> int {
@@ -1435,14 +1448,12 @@ static int group_pass(cryo_codec *c, int method, const uint8_t *d_src, const uin
             }
         }
         uint8_t *side_rec = ch.own, *side_cell = ch.own + ch.K * S * sizeof(cryo_group_rec);
-        HIP_TRY(c, cryo::launch_group(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.d_atts, io.d_keys, io.nkeys, slots, io.nby,
-                                      io.ncols, io.max_att, io.bytes_keys, (uint4 *)(io.d_blocks + ch.lo), side_rec, side_cell, io.d_total,
+        HIP_TRY(c, cryo::launch_group(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.sd.d_atts, io.sd.d_keys, io.sd.nkeys, slots, io.nby,
+                                      io.ncols, io.sd.max_att, io.sd.bytes_keys, (uint4 *)(io.d_blocks + ch.lo), side_rec, side_cell, io.d_total,
                                       io.d_groups, io.d_cells, io.group_cap, c->lz4_opts.cus));
         return CRYO_OK;
     };
-    const int rc = decode_pass(c, method, B, n, ps);
-    c->ctr = keep;
-    return rc;
+    return decode_pass(c, method, B, n, ps);
 }
 
 /* ---- recompression ----
@@ -1479,8 +1490,7 @@ static int recode_pass(cryo_codec *c, int src_method, const uint8_t *d_src, cons
     const uint64_t bound = cryo_codec_bound(dst_method, B);
     const uint64_t dstride = host ? (bound + 15u) & ~(uint64_t)15u : out.dst_stride;
     uint64_t h_run = 0; /* packed bytes of the chunks before this one */
-    DecodePass ps;
-    ps.d_comp = d_src; ps.d_comp_off = d_src_off; ps.d_comp_size = d_src_size;
+    DecodePass ps(d_src, d_src_off, d_src_size, false);
     ps.buf = &c->d_rec; ps.cap = &c->rec_cap;
     ps.fixed = 256u;                                    /* the chunk's packed total (u64) */
     ps.own_per_block = (host ? 2u * dstride : 0u) + 32u; /* slots, packed area; size u32, status i32, K + 1 offsets u64 */
@@ -1609,6 +1619,42 @@ int cryo_codec_fetch_batch(cryo_codec *c, int method, const void *d_src, const u
     });
 }
 
+/* The descriptor of a device-resident scan call: f and, where the call has them, grp and agg (need_agg: the call is nothing
+ * without aggregate columns) are host structs whose arrays live in device memory.  In this order: the pointer and alignment
+ * rules of the structs, which touch no device; the arrays read back and held against the call's *_desc_ok before anything else
+ * is queued; the call's totals (total_words of them at d_total; none: 0) cleared; and -- unless the call has no block -- the key
+ * table of a descriptor with a byte-string key (key_table_device: without such a key nothing more is queued).  *ncols: the
+ * aggregate columns */
+static int scan_desc_device(cryo_codec *c, const cryo_filter *f, const cryo_group *grp, const cryo_agg *agg, bool need_agg,
+                            uint64_t *d_total, size_t total_words, uint64_t n_blocks, ScanDesc &sd, uint32_t *ncols)
+{
+    if (!f || f->natts == 0 || f->natts > CRYO_FILTER_MAX_ATTS || f->nkeys > CRYO_FILTER_MAX_KEYS || !f->atts ||
+        (f->nkeys > 0 && !f->keys) || ((uintptr_t)f->atts & 3u) != 0 || ((uintptr_t)f->keys & 7u) != 0)
+        return CRYO_E_ARG;
+    if (grp && (grp->nby == 0 || grp->nby > CRYO_GROUP_MAX_BY || !grp->by || ((uintptr_t)grp->by & 7u) != 0)) return CRYO_E_ARG;
+    const uint32_t nc = agg ? agg->ncols : 0u;
+    if ((need_agg && nc == 0) || nc > CRYO_AGG_MAX_COLS || (nc > 0 && (!agg->cols || ((uintptr_t)agg->cols & 7u) != 0)))
+        return CRYO_E_ARG;
+    cryo_att atts[CRYO_FILTER_MAX_ATTS]; /* 6 400 bytes */
+    cryo_scan_key keys[CRYO_FILTER_MAX_KEYS];
+    cryo_agg_col by[CRYO_GROUP_MAX_BY], cols[CRYO_AGG_MAX_COLS];
+    HIP_TRY(c, hipMemcpyAsync(atts, f->atts, f->natts * sizeof(cryo_att), hipMemcpyDeviceToHost, c->stream));
+    if (f->nkeys)
+        HIP_TRY(c, hipMemcpyAsync(keys, f->keys, f->nkeys * sizeof(cryo_scan_key), hipMemcpyDeviceToHost, c->stream));
+    if (grp) HIP_TRY(c, hipMemcpyAsync(by, grp->by, grp->nby * sizeof(cryo_agg_col), hipMemcpyDeviceToHost, c->stream));
+    if (nc) HIP_TRY(c, hipMemcpyAsync(cols, agg->cols, nc * sizeof(cryo_agg_col), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    *ncols = nc;
+    const bool ok = grp        ? group_desc_ok(f, atts, keys, grp, by, agg, cols, &sd.max_att, ncols)
+                    : need_agg ? agg_desc_ok(f, atts, keys, agg, cols, &sd.max_att)
+                               : filter_desc_ok(f, atts, keys, &sd.max_att);
+    if (!ok) return CRYO_E_ARG;
+    if (total_words) HIP_TRY(c, hipMemsetAsync(d_total, 0, total_words * sizeof(uint64_t), c->stream));
+    if (n_blocks == 0) return CRYO_OK;
+    sd.d_atts = f->atts; sd.d_keys = f->keys; sd.nkeys = f->nkeys;
+    return key_table_device(c, keys, f->nkeys, &sd.d_keys, &sd.bytes_keys);
+}
+
 int cryo_codec_filter_batch(cryo_codec *c, int method, const void *d_src, const uint64_t *d_src_off, const uint32_t *d_src_size,
                             uint32_t block_size, uint64_t n_blocks, const cryo_filter *f, void *d_dst, uint64_t dst_cap,
                             cryo_filter_rec *d_rec, uint64_t rec_cap, cryo_filter_block *d_blocks, uint64_t *d_total)
@@ -1616,30 +1662,18 @@ int cryo_codec_filter_batch(cryo_codec *c, int method, const void *d_src, const 
     DevGuard dev_(c);
     if (!c || !method_ok(method) || !check_block_size_ok(block_size)) return CRYO_E_ARG;
     if (!d_total || ((uintptr_t)d_total & 7u) != 0) return CRYO_E_ARG;
-    if (!f || f->natts == 0 || f->natts > CRYO_FILTER_MAX_ATTS || f->nkeys > CRYO_FILTER_MAX_KEYS || !f->atts ||
-        (f->nkeys > 0 && !f->keys) || ((uintptr_t)f->atts & 3u) != 0 || ((uintptr_t)f->keys & 7u) != 0)
-        return CRYO_E_ARG;
-    const bool count_only = (f->flags & CRYO_FILTER_COUNT_ONLY) != 0;
+    const bool count_only = f && (f->flags & CRYO_FILTER_COUNT_ONLY) != 0;
     if (n_blocks > 0) {
         if (!d_src || !d_src_off || !d_src_size || !d_blocks || ((uintptr_t)d_blocks & 15u) != 0) return CRYO_E_ARG;
         if (!count_only && ((!d_dst && dst_cap > 0) || (!d_rec && rec_cap > 0))) return CRYO_E_ARG;
         if ((((uintptr_t)d_dst | (uintptr_t)d_rec) & 7u) != 0) return CRYO_E_ARG;
     }
     return guarded([&] {
-        /* the descriptor lives in device memory: read back and checked before anything is queued */
-        std::vector<cryo_att> atts(f->natts);
-        std::vector<cryo_scan_key> keys(f->nkeys ? f->nkeys : 1);
-        HIP_TRY(c, hipMemcpyAsync(atts.data(), f->atts, f->natts * sizeof(cryo_att), hipMemcpyDeviceToHost, c->stream));
-        if (f->nkeys)
-            HIP_TRY(c, hipMemcpyAsync(keys.data(), f->keys, f->nkeys * sizeof(cryo_scan_key), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
         FilterIo io;
-        if (!filter_desc_ok(f, atts.data(), keys.data(), &io.max_att)) return (int)CRYO_E_ARG;
-        HIP_TRY(c, hipMemsetAsync(d_total, 0, 2 * sizeof(uint64_t), c->stream));
-        if (n_blocks == 0) return (int)CRYO_OK;
-        io.d_atts = f->atts; io.d_keys = f->keys; io.nkeys = f->nkeys; io.count_only = count_only;
-        const int krc = key_table_device(c, keys.data(), f->nkeys, &io.d_keys, &io.bytes_keys);
-        if (krc != CRYO_OK) return krc;
+        uint32_t ncols = 0;
+        const int rc = scan_desc_device(c, f, nullptr, nullptr, false, d_total, 2, n_blocks, io.sd, &ncols);
+        if (rc != CRYO_OK || n_blocks == 0) return rc;
+        io.count_only = count_only;
         io.d_blocks = d_blocks; io.dst_cap = count_only ? 0 : dst_cap; io.rec_cap = count_only ? 0 : rec_cap;
         io.d_dst = (uint8_t *)d_dst; io.d_rec = d_rec; io.d_total = d_total;
         return filter_pass(c, method, (const uint8_t *)d_src, d_src_off, d_src_size, block_size, n_blocks, io);
@@ -1652,30 +1686,14 @@ int cryo_codec_agg_batch(cryo_codec *c, int method, const void *d_src, const uin
 {
     DevGuard dev_(c);
     if (!c || !method_ok(method) || !check_block_size_ok(block_size)) return CRYO_E_ARG;
-    if (!f || f->natts == 0 || f->natts > CRYO_FILTER_MAX_ATTS || f->nkeys > CRYO_FILTER_MAX_KEYS || !f->atts ||
-        (f->nkeys > 0 && !f->keys) || ((uintptr_t)f->atts & 3u) != 0 || ((uintptr_t)f->keys & 7u) != 0)
-        return CRYO_E_ARG;
-    if (!agg || agg->ncols == 0 || agg->ncols > CRYO_AGG_MAX_COLS || !agg->cols || ((uintptr_t)agg->cols & 7u) != 0)
-        return CRYO_E_ARG;
     if (n_blocks > 0 && (!d_src || !d_src_off || !d_src_size || !d_blocks || !d_cells || ((uintptr_t)d_blocks & 15u) != 0 ||
                          ((uintptr_t)d_cells & 7u) != 0))
         return CRYO_E_ARG;
     return guarded([&] {
-        /* the descriptors live in device memory: read back and checked before anything is queued */
-        std::vector<cryo_att> atts(f->natts);
-        std::vector<cryo_scan_key> keys(f->nkeys ? f->nkeys : 1);
-        std::vector<cryo_agg_col> cols(agg->ncols);
-        HIP_TRY(c, hipMemcpyAsync(atts.data(), f->atts, f->natts * sizeof(cryo_att), hipMemcpyDeviceToHost, c->stream));
-        if (f->nkeys)
-            HIP_TRY(c, hipMemcpyAsync(keys.data(), f->keys, f->nkeys * sizeof(cryo_scan_key), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(cols.data(), agg->cols, agg->ncols * sizeof(cryo_agg_col), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
         AggIo io;
-        if (!agg_desc_ok(f, atts.data(), keys.data(), agg, cols.data(), &io.max_att)) return (int)CRYO_E_ARG;
-        if (n_blocks == 0) return (int)CRYO_OK;
-        io.d_atts = f->atts; io.d_keys = f->keys; io.d_cols = agg->cols; io.nkeys = f->nkeys; io.ncols = agg->ncols;
-        const int krc = key_table_device(c, keys.data(), f->nkeys, &io.d_keys, &io.bytes_keys);
-        if (krc != CRYO_OK) return krc;
+        const int rc = scan_desc_device(c, f, nullptr, agg, true, nullptr, 0, n_blocks, io.sd, &io.ncols);
+        if (rc != CRYO_OK || n_blocks == 0) return rc;
+        io.d_cols = agg->cols;
         io.d_blocks = d_blocks; io.d_cells = d_cells;
         return agg_pass(c, method, (const uint8_t *)d_src, d_src_off, d_src_size, block_size, n_blocks, io);
     });
@@ -1688,35 +1706,16 @@ int cryo_codec_group_batch(cryo_codec *c, int method, const void *d_src, const u
 {
     DevGuard dev_(c);
     if (!c || !method_ok(method) || !check_block_size_ok(block_size)) return CRYO_E_ARG;
-    if (!d_total || ((uintptr_t)d_total & 7u) != 0) return CRYO_E_ARG;
-    if (!f || f->natts == 0 || f->natts > CRYO_FILTER_MAX_ATTS || f->nkeys > CRYO_FILTER_MAX_KEYS || !f->atts ||
-        (f->nkeys > 0 && !f->keys) || ((uintptr_t)f->atts & 3u) != 0 || ((uintptr_t)f->keys & 7u) != 0)
-        return CRYO_E_ARG;
-    if (!grp || grp->nby == 0 || grp->nby > CRYO_GROUP_MAX_BY || !grp->by || ((uintptr_t)grp->by & 7u) != 0) return CRYO_E_ARG;
+    if (!d_total || ((uintptr_t)d_total & 7u) != 0 || !grp) return CRYO_E_ARG;
     const uint32_t ncols = agg ? agg->ncols : 0u;
-    if (ncols > CRYO_AGG_MAX_COLS || (ncols > 0 && (!agg->cols || ((uintptr_t)agg->cols & 7u) != 0))) return CRYO_E_ARG;
     if ((((uintptr_t)d_groups | (uintptr_t)d_cells) & 7u) != 0 || ((uintptr_t)d_blocks & 15u) != 0) return CRYO_E_ARG;
     if (n_blocks > 0 && (!d_src || !d_src_off || !d_src_size || !d_blocks || (group_cap > 0 && (!d_groups || (ncols > 0 && !d_cells)))))
         return CRYO_E_ARG;
     return guarded([&] {
-        /* the descriptors live in device memory: read back and checked before anything is queued */
-        std::vector<cryo_att> atts(f->natts);
-        std::vector<cryo_scan_key> keys(f->nkeys ? f->nkeys : 1);
-        std::vector<cryo_agg_col> by(grp->nby), cols(ncols ? ncols : 1);
-        HIP_TRY(c, hipMemcpyAsync(atts.data(), f->atts, f->natts * sizeof(cryo_att), hipMemcpyDeviceToHost, c->stream));
-        if (f->nkeys)
-            HIP_TRY(c, hipMemcpyAsync(keys.data(), f->keys, f->nkeys * sizeof(cryo_scan_key), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(by.data(), grp->by, grp->nby * sizeof(cryo_agg_col), hipMemcpyDeviceToHost, c->stream));
-        if (ncols) HIP_TRY(c, hipMemcpyAsync(cols.data(), agg->cols, ncols * sizeof(cryo_agg_col), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
         GroupIo io;
-        if (!group_desc_ok(f, atts.data(), keys.data(), grp, by.data(), agg, cols.data(), &io.max_att, &io.ncols)) return (int)CRYO_E_ARG;
-        HIP_TRY(c, hipMemsetAsync(d_total, 0, sizeof(uint64_t), c->stream));
-        if (n_blocks == 0) return (int)CRYO_OK;
-        io.d_atts = f->atts; io.d_keys = f->keys; io.d_by = grp->by; io.d_cols = ncols ? agg->cols : nullptr;
-        io.nkeys = f->nkeys; io.nby = grp->nby;
-        const int krc = key_table_device(c, keys.data(), f->nkeys, &io.d_keys, &io.bytes_keys);
-        if (krc != CRYO_OK) return krc;
+        const int rc = scan_desc_device(c, f, grp, agg, false, d_total, 1, n_blocks, io.sd, &io.ncols);
+        if (rc != CRYO_OK || n_blocks == 0) return rc;
+        io.d_by = grp->by; io.d_cols = ncols ? agg->cols : nullptr; io.nby = grp->nby;
         io.d_blocks = d_blocks; io.d_groups = d_groups; io.d_cells = d_cells; io.group_cap = group_cap; io.d_total = d_total;
         return group_pass(c, method, (const uint8_t *)d_src, d_src_off, d_src_size, block_size, n_blocks, io);
     });
@@ -2105,20 +2104,21 @@ static int compress_blocks_body(cryo_codec *c, int method, int param, const void
 int cryo_codec_compress_blocks(cryo_codec *c, int method, int param, const void *h_src, size_t block_size,
                                size_t n, void *h_dst, size_t dst_stride, uint32_t *h_out_size)
 {
-    return guarded([&] {
-        const int rc = compress_blocks_body(c, method, param, h_src, block_size, n, h_dst, dst_stride, h_out_size);
-        if (c) ws_trim_after_call(c);
-        return rc;
+    return host_call(c, [&] {
+        return compress_blocks_body(c, method, param, h_src, block_size, n, h_dst, dst_stride, h_out_size);
     });
 }
 
 /* the one-shot staging of n streams given by pointer: [offsets u64 x n][sizes u32 x n][streams, 16-byte aligned] built in the
  * pinned buffer and sent to c->hb_src in one copy (counted in h2d_bytes); the device tables are at o_off and o_sz of c->hb_src.
+ * tail_bytes: room the caller wants in the pinned buffer behind the streams, at o_tail (16-byte aligned), for a table of its own
+ * that it fills and uploads in a second copy -- the layout is this function's alone, and the pinned buffer gets its final size
+ * here, before anything is queued, so it stays where it is.
  * spread: the host copies go over the staging workers (recompression, whose large calls come through here too; a large
  * decompress or check call takes the pipelined staging instead) */
-struct StagedStreams { size_t o_off = 0, o_sz = 0, o_data = 0, total = 0; };
+struct StagedStreams { size_t o_off = 0, o_sz = 0, o_data = 0, total = 0, o_tail = 0; };
 static int stage_streams(cryo_codec *c, const void *const *h_src, const uint32_t *h_src_size, size_t n, StagedStreams &sg,
-                         bool spread = false)
+                         bool spread = false, size_t tail_bytes = 0)
 {
     sg.o_off = 0; sg.o_sz = n * 8; sg.o_data = (n * 12 + 63) & ~(size_t)63;
     sg.total = 0;
@@ -2126,8 +2126,9 @@ static int stage_streams(cryo_codec *c, const void *const *h_src, const uint32_t
         if (h_src_size[i] != 0 && !h_src[i]) return CRYO_E_ARG;
         sg.total += ((size_t)h_src_size[i] + 15) & ~(size_t)15;
     }
+    sg.o_tail = (sg.o_data + sg.total + 64 + 15) & ~(size_t)15; /* = o_data + total + 64: both are multiples of 16 */
     int rc;
-    if ((rc = ensure_pinned(c, sg.o_data + sg.total + 64)) != CRYO_OK) return rc;
+    if ((rc = ensure_pinned(c, sg.o_tail + tail_bytes)) != CRYO_OK) return rc;
     if ((rc = ensure(c, &c->hb_src, &c->hb_src_cap, sg.o_data + sg.total + 64)) != CRYO_OK) return rc;
     uint8_t *pin = (uint8_t *)c->pin;
     uint64_t *p_off = (uint64_t *)(pin + sg.o_off);
@@ -2224,10 +2225,8 @@ int cryo_codec_decompress_blocks(cryo_codec *c, int method, const void *const *h
                                  size_t n, void *h_dst, size_t block_size, int32_t *h_status)
 {
     if (!h_dst) return CRYO_E_ARG;
-    return guarded([&] {
-        const int rc = decompress_blocks_impl(c, method, h_src, h_src_size, n, h_dst, nullptr, block_size, h_status);
-        if (c) ws_trim_after_call(c);
-        return rc;
+    return host_call(c, [&] {
+        return decompress_blocks_impl(c, method, h_src, h_src_size, n, h_dst, nullptr, block_size, h_status);
     });
 }
 
@@ -2235,10 +2234,8 @@ int cryo_codec_decompress_blocks_to(cryo_codec *c, int method, const void *const
                                     size_t n, void *const *h_dst, size_t block_size, int32_t *h_status)
 {
     if (!h_dst) return CRYO_E_ARG;
-    return guarded([&] {
-        const int rc = decompress_blocks_impl(c, method, h_src, h_src_size, n, nullptr, h_dst, block_size, h_status);
-        if (c) ws_trim_after_call(c);
-        return rc;
+    return host_call(c, [&] {
+        return decompress_blocks_impl(c, method, h_src, h_src_size, n, nullptr, h_dst, block_size, h_status);
     });
 }
 
@@ -2248,10 +2245,8 @@ int cryo_codec_check_blocks(cryo_codec *c, int method, const void *const *h_src,
     if (!c || !method_ok(method) || !check_block_size_ok(block_size)) return CRYO_E_ARG;
     if (n == 0) return CRYO_OK;
     if (!h_src || !h_src_size || !h_result) return CRYO_E_ARG;
-    return guarded([&] {
-        const int rc = decompress_blocks_impl(c, method, h_src, h_src_size, n, nullptr, nullptr, block_size, nullptr, h_result);
-        ws_trim_after_call(c);
-        return rc;
+    return host_call(c, [&] {
+        return decompress_blocks_impl(c, method, h_src, h_src_size, n, nullptr, nullptr, block_size, nullptr, h_result);
     });
 }
 
@@ -2285,11 +2280,9 @@ int cryo_codec_recode_blocks(cryo_codec *c, int src_method, const void *const *h
                              size_t block_size, int dst_method, int dst_param, void *h_dst, size_t dst_cap, uint64_t *h_out_off,
                              uint32_t *h_out_size, int32_t *h_status)
 {
-    return guarded([&] {
-        const int rc = recode_blocks_impl(c, src_method, h_src, h_src_size, n, block_size, dst_method, dst_param, h_dst, dst_cap, 0,
+    return host_call(c, [&] {
+        return recode_blocks_impl(c, src_method, h_src, h_src_size, n, block_size, dst_method, dst_param, h_dst, dst_cap, 0,
                                           h_out_off, h_out_size, h_status);
-        if (c) ws_trim_after_call(c);
-        return rc;
     });
 }
 
@@ -2314,17 +2307,12 @@ static int fetch_blocks_impl(cryo_codec *c, int method, const void *const *h_src
     ScopedLocalCpus numa_(n * block_size >= ((size_t)8 << 20) ? c : nullptr);
     /* the request table: [first u64 x (n + 1)][pos u16 x n_req][records x n_req], each part 16-byte aligned */
     const size_t t_first = 0, t_pos = ((n + 1) * 8 + 15) & ~(size_t)15, t_rec = t_pos + ((n_req * 2 + 15) & ~(size_t)15);
-    size_t streams = (n * 12 + 63) & ~(size_t)63; /* what stage_streams lays out in the pinned buffer */
-    for (size_t i = 0; i < n; i++) streams += ((size_t)h_src_size[i] + 15) & ~(size_t)15;
-    const size_t p_tbl = (streams + 64 + 15) & ~(size_t)15;
     int rc;
-    /* every allocation of the call before the uploads are queued; the pinned buffer at its final size, so that the staging of
-     * the streams leaves it where it is */
-    if ((rc = ensure_pinned(c, p_tbl + t_rec)) != CRYO_OK) return rc;
+    /* every allocation of the call before the uploads are queued; the table goes into the tail behind the staged streams */
     if ((rc = ensure(c, &c->hb_meta, &c->hb_meta_cap, t_rec + n_req * sizeof(cryo_fetch_result) + 64)) != CRYO_OK) return rc;
     StagedStreams sg;
-    if ((rc = stage_streams(c, h_src, h_src_size, n, sg, true)) != CRYO_OK) return rc;
-    uint8_t *pin = (uint8_t *)c->pin + p_tbl;
+    if ((rc = stage_streams(c, h_src, h_src_size, n, sg, true, t_rec)) != CRYO_OK) return rc;
+    uint8_t *pin = (uint8_t *)c->pin + sg.o_tail;
     memset(pin, 0, t_rec);
     memcpy(pin + t_first, h_req_first, (n + 1) * 8);
     if (n_req) memcpy(pin + t_pos, h_pos, n_req * 2);
@@ -2348,12 +2336,41 @@ int cryo_codec_fetch_blocks(cryo_codec *c, int method, const void *const *h_src,
                             size_t block_size, const uint64_t *h_req_first, const uint16_t *h_pos, void *h_dst, size_t dst_cap,
                             cryo_fetch_result *h_result, uint64_t *h_total)
 {
-    return guarded([&] {
-        const int rc = fetch_blocks_impl(c, method, h_src, h_src_size, n, block_size, h_req_first, h_pos, h_dst, dst_cap, 0, h_result,
+    return host_call(c, [&] {
+        return fetch_blocks_impl(c, method, h_src, h_src_size, n, block_size, h_req_first, h_pos, h_dst, dst_cap, 0, h_result,
                                          h_total);
-        if (c) ws_trim_after_call(c);
-        return rc;
     });
+}
+
+/* The descriptor of a host-buffer scan call: [atts 4 x natts][keys 16 x nkeys][byte-string constants][the call's extra bytes:
+ * the aggregate's columns, the group's six slots], each part 16-byte aligned.  It takes the first `bytes` of c->hb_meta, where
+ * the call's results follow it */
+struct ScanDescLayout { size_t t_keys = 0, t_extra = 0, bytes = 0; bool bytes_keys = false; };
+static ScanDescLayout scan_desc_layout(const cryo_filter *f, size_t extra_bytes)
+{
+    ScanDescLayout L;
+    L.t_keys = ((size_t)f->natts * 4 + 15) & ~(size_t)15;
+    L.t_extra = L.t_keys + (size_t)f->nkeys * 16 + key_consts_bytes(f->keys, f->nkeys, &L.bytes_keys);
+    L.bytes = L.t_extra + extra_bytes;
+    return L;
+}
+/* stages the streams (stage_streams) with the descriptor in the tail behind them, uploads it in a second copy (counted in
+ * h2d_bytes), both into place before the first decode, and fills sd.  c->hb_meta holds L.bytes and the call's results already:
+ * every allocation of the call is made before the uploads are queued.  extra: the call's extra bytes, zero-padded */
+static int scan_desc_upload(cryo_codec *c, const void *const *h_src, const uint32_t *h_src_size, size_t n, const cryo_filter *f,
+                            uint32_t max_att, const ScanDescLayout &L, const void *extra, StagedStreams &sg, ScanDesc &sd)
+{
+    const int rc = stage_streams(c, h_src, h_src_size, n, sg, true, L.bytes);
+    if (rc != CRYO_OK) return rc;
+    uint8_t *pin = (uint8_t *)c->pin + sg.o_tail;
+    memset(pin, 0, L.bytes);
+    memcpy(pin, f->atts, (size_t)f->natts * 4);
+    (void)key_table_host(pin + L.t_keys, c->hb_meta + L.t_keys, f);
+    if (L.bytes > L.t_extra) memcpy(pin + L.t_extra, extra, L.bytes - L.t_extra);
+    HIP_TRY(c, hipMemcpyAsync(c->hb_meta, pin, L.bytes, hipMemcpyHostToDevice, c->stream));
+    c->xfer_ctr.h2d_bytes += L.bytes;
+    sd.d_atts = c->hb_meta; sd.d_keys = c->hb_meta + L.t_keys; sd.nkeys = f->nkeys; sd.max_att = max_att; sd.bytes_keys = L.bytes_keys;
+    return CRYO_OK;
 }
 
 /* what every host-buffer filter call checks before a device is touched */
@@ -2382,29 +2399,13 @@ static int filter_blocks_impl(cryo_codec *c, int method, const void *const *h_sr
     if (!h_src || !h_src_size || !h_blocks) return CRYO_E_ARG;
     if (!count_only && ((!h_dst && dst_cap > 0) || (!h_rec && rec_cap > 0))) return CRYO_E_ARG;
     ScopedLocalCpus numa_(n * block_size >= ((size_t)8 << 20) ? c : nullptr);
-    /* the descriptor and the table: [atts 4 x natts][keys 16 x nkeys][byte-string constants][rows 32 x n], each part 16-byte
-     * aligned */
-    bool bytes_keys = false;
-    const size_t t_atts = 0, t_keys = ((size_t)f->natts * 4 + 15) & ~(size_t)15;
-    const size_t t_rows = t_keys + (size_t)f->nkeys * 16 + key_consts_bytes(f->keys, f->nkeys, &bytes_keys);
-    size_t streams = (n * 12 + 63) & ~(size_t)63; /* what stage_streams lays out in the pinned buffer */
-    for (size_t i = 0; i < n; i++) streams += ((size_t)h_src_size[i] + 15) & ~(size_t)15;
-    const size_t p_tbl = (streams + 64 + 15) & ~(size_t)15;
-    /* every allocation of the call before the uploads are queued; the pinned buffer at its final size, so that the staging of
-     * the streams leaves it where it is */
-    if ((rc = ensure_pinned(c, p_tbl + t_rows)) != CRYO_OK) return rc;
+    /* the descriptor, then the table: [rows 32 x n] */
+    const ScanDescLayout L = scan_desc_layout(f, 0);
+    const size_t t_rows = L.bytes;
     if ((rc = ensure(c, &c->hb_meta, &c->hb_meta_cap, t_rows + n * sizeof(cryo_filter_block) + 64)) != CRYO_OK) return rc;
     StagedStreams sg;
-    if ((rc = stage_streams(c, h_src, h_src_size, n, sg, true)) != CRYO_OK) return rc;
-    uint8_t *pin = (uint8_t *)c->pin + p_tbl;
-    memset(pin, 0, t_rows);
-    memcpy(pin + t_atts, f->atts, (size_t)f->natts * 4);
-    (void)key_table_host(pin + t_keys, c->hb_meta + t_keys, f);
-    HIP_TRY(c, hipMemcpyAsync(c->hb_meta, pin, t_rows, hipMemcpyHostToDevice, c->stream));
-    c->xfer_ctr.h2d_bytes += t_rows;
     FilterIo io;
-    io.bytes_keys = bytes_keys;
-    io.d_atts = c->hb_meta + t_atts; io.d_keys = c->hb_meta + t_keys; io.nkeys = f->nkeys; io.max_att = max_att;
+    if ((rc = scan_desc_upload(c, h_src, h_src_size, n, f, max_att, L, nullptr, sg, io.sd)) != CRYO_OK) return rc;
     io.count_only = count_only; io.d_blocks = (cryo_filter_block *)(c->hb_meta + t_rows);
     io.dst_cap = count_only ? 0 : dst_cap; io.rec_cap = count_only ? 0 : rec_cap;
     io.host = true; io.h_blocks = h_blocks; io.h_rec = h_rec; io.h_dst = (uint8_t *)h_dst;
@@ -2423,11 +2424,9 @@ int cryo_codec_filter_blocks(cryo_codec *c, int method, const void *const *h_src
                              size_t block_size, const cryo_filter *f, void *h_dst, size_t dst_cap, cryo_filter_rec *h_rec,
                              size_t rec_cap, cryo_filter_block *h_blocks, uint64_t *h_total)
 {
-    return guarded([&] {
-        const int rc = filter_blocks_impl(c, method, h_src, h_src_size, n, block_size, f, h_dst, dst_cap, 0, h_rec, rec_cap, 0,
+    return host_call(c, [&] {
+        return filter_blocks_impl(c, method, h_src, h_src_size, n, block_size, f, h_dst, dst_cap, 0, h_rec, rec_cap, 0,
                                           h_blocks, h_total);
-        if (c) ws_trim_after_call(c);
-        return rc;
     });
 }
 
@@ -2453,32 +2452,17 @@ static int agg_blocks_impl(cryo_codec *c, int method, const void *const *h_src, 
     if (n == 0) return CRYO_OK;
     if (!h_src || !h_src_size || !h_blocks || !h_cells) return CRYO_E_ARG;
     ScopedLocalCpus numa_(n * block_size >= ((size_t)8 << 20) ? c : nullptr);
-    /* the descriptors and the results: [atts 4 x natts][keys 16 x nkeys][byte-string constants][cols 8 x ncols][rows 16 x n]
-     * [cells 40 x n x ncols], each part 16-byte aligned */
-    bool bytes_keys = false;
-    const size_t t_atts = 0, t_keys = ((size_t)f->natts * 4 + 15) & ~(size_t)15;
-    const size_t t_cols = t_keys + (size_t)f->nkeys * 16 + key_consts_bytes(f->keys, f->nkeys, &bytes_keys);
-    const size_t t_rows = t_cols + (((size_t)agg->ncols * 8 + 15) & ~(size_t)15);
+    /* the descriptor with [cols 8 x ncols] as its extra bytes, then the results: [rows 16 x n][cells 40 x n x ncols] */
+    cryo_agg_col cols[CRYO_AGG_MAX_COLS] = {};
+    memcpy(cols, agg->cols, (size_t)agg->ncols * 8);
+    const ScanDescLayout L = scan_desc_layout(f, ((size_t)agg->ncols * 8 + 15) & ~(size_t)15);
+    const size_t t_rows = L.bytes;
     const size_t rows_bytes = n * sizeof(cryo_agg_block), cells_bytes = n * agg->ncols * sizeof(cryo_agg_cell);
-    size_t streams = (n * 12 + 63) & ~(size_t)63; /* what stage_streams lays out in the pinned buffer */
-    for (size_t i = 0; i < n; i++) streams += ((size_t)h_src_size[i] + 15) & ~(size_t)15;
-    const size_t p_tbl = (streams + 64 + 15) & ~(size_t)15;
-    /* every allocation of the call before the uploads are queued; the pinned buffer at its final size, so that the staging of
-     * the streams leaves it where it is */
-    if ((rc = ensure_pinned(c, p_tbl + t_rows)) != CRYO_OK) return rc;
     if ((rc = ensure(c, &c->hb_meta, &c->hb_meta_cap, t_rows + rows_bytes + cells_bytes + 64)) != CRYO_OK) return rc;
     StagedStreams sg;
-    if ((rc = stage_streams(c, h_src, h_src_size, n, sg, true)) != CRYO_OK) return rc;
-    uint8_t *pin = (uint8_t *)c->pin + p_tbl;
-    memset(pin, 0, t_rows);
-    memcpy(pin + t_atts, f->atts, (size_t)f->natts * 4);
-    (void)key_table_host(pin + t_keys, c->hb_meta + t_keys, f);
-    memcpy(pin + t_cols, agg->cols, (size_t)agg->ncols * 8);
-    HIP_TRY(c, hipMemcpyAsync(c->hb_meta, pin, t_rows, hipMemcpyHostToDevice, c->stream));
-    c->xfer_ctr.h2d_bytes += t_rows;
     AggIo io;
-    io.d_atts = c->hb_meta + t_atts; io.d_keys = c->hb_meta + t_keys; io.d_cols = c->hb_meta + t_cols;
-    io.nkeys = f->nkeys; io.ncols = agg->ncols; io.max_att = max_att; io.bytes_keys = bytes_keys;
+    if ((rc = scan_desc_upload(c, h_src, h_src_size, n, f, max_att, L, cols, sg, io.sd)) != CRYO_OK) return rc;
+    io.d_cols = c->hb_meta + L.t_extra; io.ncols = agg->ncols;
     io.d_blocks = (cryo_agg_block *)(c->hb_meta + t_rows);
     io.d_cells = (cryo_agg_cell *)(c->hb_meta + t_rows + rows_bytes);
     rc = agg_pass(c, method, c->hb_src, (const uint64_t *)(c->hb_src + sg.o_off), (const uint32_t *)(c->hb_src + sg.o_sz),
@@ -2499,11 +2483,7 @@ int cryo_codec_agg_blocks(cryo_codec *c, int method, const void *const *h_src, c
                           size_t block_size, const cryo_filter *f, const cryo_agg *agg, cryo_agg_block *h_blocks,
                           cryo_agg_cell *h_cells)
 {
-    return guarded([&] {
-        const int rc = agg_blocks_impl(c, method, h_src, h_src_size, n, block_size, f, agg, h_blocks, h_cells);
-        if (c) ws_trim_after_call(c);
-        return rc;
-    });
+    return host_call(c, [&] { return agg_blocks_impl(c, method, h_src, h_src_size, n, block_size, f, agg, h_blocks, h_cells); });
 }
 
 /* what every host-buffer group call checks before a device is touched */
@@ -2533,36 +2513,22 @@ static int group_blocks_impl(cryo_codec *c, int method, const void *const *h_src
     if (n == 0) return CRYO_OK;
     if (!h_src || !h_src_size || !h_blocks || (group_cap > 0 && (!h_groups || (ncols > 0 && !h_cells)))) return CRYO_E_ARG;
     ScopedLocalCpus numa_(n * block_size >= ((size_t)8 << 20) ? c : nullptr);
-    /* the descriptors and the results: [atts 4 x natts][keys 16 x nkeys][byte-string constants][slots 8 x 6][total 16][rows 32 x n]
-     * [records 24 x cap][cells 40 x cap x ncols], each part 8-byte aligned, the rows 16; cap: what the caller has room for, at most
-     * the worst case */
-    bool bytes_keys = false;
+    /* the descriptor with the kernel's six slots [by 8 x 2][cols 8 x 4] as its extra bytes, then the results: [total 16]
+     * [rows 32 x n][records 24 x cap][cells 40 x cap x ncols], each part 8-byte aligned, the rows 16; cap: what the caller has room
+     * for, at most the worst case */
     const size_t worst = n * (size_t)cryo::filter_side_stride((uint32_t)block_size);
     const size_t cap = group_cap < worst ? group_cap : worst;
-    const size_t t_atts = 0, t_keys = ((size_t)f->natts * 4 + 15) & ~(size_t)15;
-    const size_t t_slots = t_keys + (size_t)f->nkeys * 16 + key_consts_bytes(f->keys, f->nkeys, &bytes_keys);
-    const size_t t_total = t_slots + 48, t_rows = t_total + 16;
+    cryo_agg_col slots[CRYO_GROUP_MAX_BY + CRYO_AGG_MAX_COLS] = {};
+    memcpy(slots, grp->by, (size_t)grp->nby * 8);
+    if (ncols) memcpy(slots + CRYO_GROUP_MAX_BY, agg->cols, (size_t)ncols * 8);
+    const ScanDescLayout L = scan_desc_layout(f, sizeof slots);
+    const size_t t_total = L.bytes, t_rows = t_total + 16;
     const size_t rows_bytes = n * sizeof(cryo_group_block), t_recs = t_rows + rows_bytes, t_cells = t_recs + cap * sizeof(cryo_group_rec);
-    size_t streams = (n * 12 + 63) & ~(size_t)63; /* what stage_streams lays out in the pinned buffer */
-    for (size_t i = 0; i < n; i++) streams += ((size_t)h_src_size[i] + 15) & ~(size_t)15;
-    const size_t p_tbl = (streams + 64 + 15) & ~(size_t)15;
-    /* every allocation of the call before the uploads are queued; the pinned buffer at its final size, so that the staging of
-     * the streams leaves it where it is */
-    if ((rc = ensure_pinned(c, p_tbl + t_total)) != CRYO_OK) return rc;
     if ((rc = ensure(c, &c->hb_meta, &c->hb_meta_cap, t_cells + cap * ncols * sizeof(cryo_agg_cell) + 64)) != CRYO_OK) return rc;
     StagedStreams sg;
-    if ((rc = stage_streams(c, h_src, h_src_size, n, sg, true)) != CRYO_OK) return rc;
-    uint8_t *pin = (uint8_t *)c->pin + p_tbl;
-    memset(pin, 0, t_total);
-    memcpy(pin + t_atts, f->atts, (size_t)f->natts * 4);
-    (void)key_table_host(pin + t_keys, c->hb_meta + t_keys, f);
-    memcpy(pin + t_slots, grp->by, (size_t)grp->nby * 8);
-    if (ncols) memcpy(pin + t_slots + 16, agg->cols, (size_t)ncols * 8);
-    HIP_TRY(c, hipMemcpyAsync(c->hb_meta, pin, t_total, hipMemcpyHostToDevice, c->stream));
-    c->xfer_ctr.h2d_bytes += t_total;
     GroupIo io;
-    io.d_atts = c->hb_meta + t_atts; io.d_keys = c->hb_meta + t_keys; io.d_slots = c->hb_meta + t_slots;
-    io.nkeys = f->nkeys; io.nby = grp->nby; io.ncols = ncols; io.max_att = max_att; io.bytes_keys = bytes_keys;
+    if ((rc = scan_desc_upload(c, h_src, h_src_size, n, f, max_att, L, slots, sg, io.sd)) != CRYO_OK) return rc;
+    io.d_slots = c->hb_meta + L.t_extra; io.nby = grp->nby; io.ncols = ncols;
     io.d_total = (uint64_t *)(c->hb_meta + t_total);
     io.d_blocks = (cryo_group_block *)(c->hb_meta + t_rows);
     io.d_groups = (cryo_group_rec *)(c->hb_meta + t_recs);
@@ -2601,11 +2567,9 @@ int cryo_codec_group_blocks(cryo_codec *c, int method, const void *const *h_src,
                             cryo_group_block *h_blocks, cryo_group_rec *h_groups, size_t group_cap, cryo_agg_cell *h_cells,
                             uint64_t *h_total)
 {
-    return guarded([&] {
-        const int rc = group_blocks_impl(c, method, h_src, h_src_size, n, block_size, f, grp, agg, h_blocks, h_groups, group_cap,
+    return host_call(c, [&] {
+        return group_blocks_impl(c, method, h_src, h_src_size, n, block_size, f, grp, agg, h_blocks, h_groups, group_cap,
                                          h_cells, h_total);
-        if (c) ws_trim_after_call(c);
-        return rc;
     });
 }
 
@@ -2789,10 +2753,8 @@ extern "C" {
 int cryo_codec_decompress_blocks_keyed(cryo_codec *c, int method, const uint64_t *keys, const void *const *h_src,
                                        const uint32_t *h_src_size, size_t n, void *const *h_dst, size_t block_size, int32_t *h_status)
 {
-    return guarded([&] {
-        const int rc = decompress_blocks_keyed_impl(c, method, keys, h_src, h_src_size, n, h_dst, block_size, h_status);
-        if (c) ws_trim_after_call(c);
-        return rc;
+    return host_call(c, [&] {
+        return decompress_blocks_keyed_impl(c, method, keys, h_src, h_src_size, n, h_dst, block_size, h_status);
     });
 }
 
@@ -2911,12 +2873,14 @@ int cryo_multi_count(const cryo_multi *m) { return m ? (int)m->h.size() : 0; }
 const char *cryo_multi_last_error(const cryo_multi *m) { return m ? m->err : ""; }
 
 } /* extern "C" */
-/* block i -> handle i mod G; `fn(g, idx)` runs the block indices of handle g, every handle's share on its own host thread */
-static int multi_run(cryo_multi *m, size_t n, const std::function<int(size_t, const std::vector<size_t> &)> &fn)
+/* block i -> handle owner(i), or i mod G without an owner; `fn(g, idx)` runs the block indices of handle g, every handle's share
+ * on its own host thread */
+static int multi_run(cryo_multi *m, size_t n, const std::function<int(size_t, const std::vector<size_t> &)> &fn,
+                     const std::function<size_t(size_t)> &owner = nullptr)
 {
     const size_t G = m->h.size();
     std::vector<std::vector<size_t>> share(G);
-    for (size_t i = 0; i < n; i++) share[i % G].push_back(i);
+    for (size_t i = 0; i < n; i++) share[owner ? owner(i) : i % G].push_back(i);
     std::vector<int> rc(G, CRYO_OK);
     const std::function<void(unsigned)> one = [&](unsigned g) {
         if (!share[g].empty()) {
@@ -2932,6 +2896,24 @@ static int multi_run(cryo_multi *m, size_t n, const std::function<int(size_t, co
             return rc[g];
         }
     return CRYO_OK;
+}
+namespace {
+/* a share's streams: those of the blocks idx[k], in that order */
+struct ShareStreams {
+    std::vector<const void *> src;
+    std::vector<uint32_t> sz;
+    ShareStreams(const void *const *h_src, const uint32_t *h_src_size, const std::vector<size_t> &idx) : src(idx.size()), sz(idx.size())
+    {
+        for (size_t k = 0; k < idx.size(); k++) { src[k] = h_src[idx[k]]; sz[k] = h_src_size[idx[k]]; }
+    }
+};
+} // namespace
+/* the blocks of a round-robin call of n blocks that the handles before g hold: handle q has blocks q, q + G, ... */
+static uint64_t blocks_before(size_t n, size_t G, size_t g)
+{
+    uint64_t before = 0;
+    for (size_t q = 0; q < g && q < n; q++) before += (uint64_t)((n - q + G - 1) / G);
+    return before;
 }
 extern "C" {
 
@@ -2968,16 +2950,12 @@ static int multi_decompress(cryo_multi *m, int method, const void *const *h_src,
 {
     return guarded([&] {
         return multi_run(m, n, [&](size_t g, const std::vector<size_t> &idx) {
-            std::vector<const void *> src(idx.size());
+            const ShareStreams in(h_src, h_src_size, idx);
             std::vector<void *> dst(idx.size());
-            std::vector<uint32_t> sz(idx.size());
             std::vector<int32_t> st(idx.size());
-            for (size_t k = 0; k < idx.size(); k++) {
-                src[k] = h_src[idx[k]];
-                sz[k] = h_src_size[idx[k]];
+            for (size_t k = 0; k < idx.size(); k++)
                 dst[k] = h_dst_each ? h_dst_each[idx[k]] : (void *)((uint8_t *)h_dst + idx[k] * block_size);
-            }
-            const int rc = decompress_blocks_impl(m->h[g], method, src.data(), sz.data(), idx.size(), nullptr, dst.data(), block_size, st.data());
+            const int rc = decompress_blocks_impl(m->h[g], method, in.src.data(), in.sz.data(), idx.size(), nullptr, dst.data(), block_size, st.data());
             if (rc == CRYO_OK) for (size_t k = 0; k < idx.size(); k++) h_status[idx[k]] = st[k];
             return rc;
         });
@@ -3013,11 +2991,9 @@ int cryo_multi_check_blocks(cryo_multi *m, int method, const void *const *h_src,
     if (m->h.size() == 1) return cryo_codec_check_blocks(m->h[0], method, h_src, h_src_size, n, block_size, h_result);
     return guarded([&] {
         return multi_run(m, n, [&](size_t g, const std::vector<size_t> &idx) {
-            std::vector<const void *> src(idx.size());
-            std::vector<uint32_t> sz(idx.size());
+            const ShareStreams in(h_src, h_src_size, idx);
             std::vector<cryo_check_result> res(idx.size());
-            for (size_t k = 0; k < idx.size(); k++) { src[k] = h_src[idx[k]]; sz[k] = h_src_size[idx[k]]; }
-            const int rc = decompress_blocks_impl(m->h[g], method, src.data(), sz.data(), idx.size(), nullptr, nullptr, block_size, nullptr, res.data());
+            const int rc = decompress_blocks_impl(m->h[g], method, in.src.data(), in.sz.data(), idx.size(), nullptr, nullptr, block_size, nullptr, res.data());
             if (rc == CRYO_OK) for (size_t k = 0; k < idx.size(); k++) h_result[idx[k]] = res[k];
             return rc;
         });
@@ -3044,12 +3020,11 @@ int cryo_multi_recode_blocks(cryo_multi *m, int src_method, const void *const *h
     const size_t region = (dst_cap / G) & ~(size_t)15;
     return guarded([&] {
         return multi_run(m, n, [&](size_t g, const std::vector<size_t> &idx) {
-            std::vector<const void *> src(idx.size());
-            std::vector<uint32_t> sz(idx.size()), osz(idx.size());
+            const ShareStreams in(h_src, h_src_size, idx);
+            std::vector<uint32_t> osz(idx.size());
             std::vector<uint64_t> off(idx.size());
             std::vector<int32_t> st(idx.size());
-            for (size_t k = 0; k < idx.size(); k++) { src[k] = h_src[idx[k]]; sz[k] = h_src_size[idx[k]]; }
-            const int rc = recode_blocks_impl(m->h[g], src_method, src.data(), sz.data(), idx.size(), block_size, dst_method,
+            const int rc = recode_blocks_impl(m->h[g], src_method, in.src.data(), in.sz.data(), idx.size(), block_size, dst_method,
                                               dst_param, (uint8_t *)h_dst + g * region, region, g * region, off.data(), osz.data(),
                                               st.data());
             if (rc != CRYO_OK) return rc;
@@ -3084,26 +3059,19 @@ int cryo_multi_fetch_blocks(cryo_multi *m, int method, const void *const *h_src,
     std::vector<uint64_t> end(G, 0);
     const int rc = guarded([&] {
         return multi_run(m, n, [&](size_t g, const std::vector<size_t> &idx) {
-            /* handles before g hold blocks g' < g of every round of G: (n - g' + G - 1) / G each */
-            uint64_t start = 0;
-            for (size_t q = 0; q < g && q < n; q++) start += (uint64_t)((n - q + G - 1) / G) * block_size;
+            const uint64_t start = blocks_before(n, G, g) * block_size;
             const uint64_t want = (uint64_t)idx.size() * block_size;
             const uint64_t cap = dst_cap > start ? (dst_cap - start < want ? dst_cap - start : want) : 0;
-            std::vector<const void *> src(idx.size());
-            std::vector<uint32_t> sz(idx.size());
+            const ShareStreams in(h_src, h_src_size, idx);
             std::vector<uint64_t> first(idx.size() + 1, 0);
-            for (size_t k = 0; k < idx.size(); k++) {
-                src[k] = h_src[idx[k]];
-                sz[k] = h_src_size[idx[k]];
-                first[k + 1] = first[k] + (h_req_first[idx[k] + 1] - h_req_first[idx[k]]);
-            }
+            for (size_t k = 0; k < idx.size(); k++) first[k + 1] = first[k] + (h_req_first[idx[k] + 1] - h_req_first[idx[k]]);
             std::vector<uint16_t> pos(first.back() ? first.back() : 1);
             std::vector<cryo_fetch_result> res(first.back() ? first.back() : 1);
             for (size_t k = 0; k < idx.size(); k++)
                 if (first[k + 1] > first[k])
                     memcpy(&pos[first[k]], h_pos + h_req_first[idx[k]], (first[k + 1] - first[k]) * sizeof(uint16_t));
             uint64_t tot = 0;
-            const int r = fetch_blocks_impl(m->h[g], method, src.data(), sz.data(), idx.size(), block_size, first.data(), pos.data(),
+            const int r = fetch_blocks_impl(m->h[g], method, in.src.data(), in.sz.data(), idx.size(), block_size, first.data(), pos.data(),
                                             cap ? (uint8_t *)h_dst + start : nullptr, cap, start, res.data(), &tot);
             if (r != CRYO_OK) return r;
             for (size_t k = 0; k < idx.size(); k++)
@@ -3120,8 +3088,8 @@ int cryo_multi_fetch_blocks(cryo_multi *m, int method, const void *const *h_src,
 }
 
 /* block i -> handle i mod G; handle g packs its share, in block order, into a tuple region of block_size * (its blocks) bytes and
- * a record region of 290 * (its blocks) records, the regions in handle order; the table comes back in call order with `off` and
- * rec_first counting from h_dst and h_rec */
+ * a record region of 290 (kHeapMaxItems) * (its blocks) records, whatever the block size, the regions in handle order; the table
+ * comes back in call order with `off` and rec_first counting from h_dst and h_rec */
 int cryo_multi_filter_blocks(cryo_multi *m, int method, const void *const *h_src, const uint32_t *h_src_size, size_t n,
                              size_t block_size, const cryo_filter *f, void *h_dst, size_t dst_cap, cryo_filter_rec *h_rec,
                              size_t rec_cap, cryo_filter_block *h_blocks, uint64_t *h_total)
@@ -3140,19 +3108,15 @@ int cryo_multi_filter_blocks(cryo_multi *m, int method, const void *const *h_src
     std::vector<uint64_t> end_b(G, 0), end_r(G, 0);
     const int rc = guarded([&] {
         return multi_run(m, n, [&](size_t g, const std::vector<size_t> &idx) {
-            /* handles before g hold blocks g' < g of every round of G: (n - g' + G - 1) / G each */
-            uint64_t before = 0;
-            for (size_t q = 0; q < g && q < n; q++) before += (uint64_t)((n - q + G - 1) / G);
-            const uint64_t b0 = before * block_size, r0 = before * 290u;
-            const uint64_t want_b = (uint64_t)idx.size() * block_size, want_r = (uint64_t)idx.size() * 290u;
+            const uint64_t before = blocks_before(n, G, g);
+            const uint64_t b0 = before * block_size, r0 = before * cryo::kHeapMaxItems;
+            const uint64_t want_b = (uint64_t)idx.size() * block_size, want_r = (uint64_t)idx.size() * cryo::kHeapMaxItems;
             const uint64_t cap_b = dst_cap > b0 ? (dst_cap - b0 < want_b ? dst_cap - b0 : want_b) : 0;
             const uint64_t cap_r = rec_cap > r0 ? (rec_cap - r0 < want_r ? rec_cap - r0 : want_r) : 0;
-            std::vector<const void *> src(idx.size());
-            std::vector<uint32_t> sz(idx.size());
+            const ShareStreams in(h_src, h_src_size, idx);
             std::vector<cryo_filter_block> rows(idx.size());
-            for (size_t k = 0; k < idx.size(); k++) { src[k] = h_src[idx[k]]; sz[k] = h_src_size[idx[k]]; }
             uint64_t tot[2] = {0, 0};
-            const int r = filter_blocks_impl(m->h[g], method, src.data(), sz.data(), idx.size(), block_size, f,
+            const int r = filter_blocks_impl(m->h[g], method, in.src.data(), in.sz.data(), idx.size(), block_size, f,
                                              cap_b ? (uint8_t *)h_dst + b0 : nullptr, cap_b, b0, cap_r ? h_rec + r0 : nullptr, cap_r,
                                              r0, rows.data(), tot);
             if (r != CRYO_OK) return r;
@@ -3184,12 +3148,10 @@ int cryo_multi_agg_blocks(cryo_multi *m, int method, const void *const *h_src, c
     const size_t nc = agg->ncols;
     return guarded([&] {
         return multi_run(m, n, [&](size_t g, const std::vector<size_t> &idx) {
-            std::vector<const void *> src(idx.size());
-            std::vector<uint32_t> sz(idx.size());
+            const ShareStreams in(h_src, h_src_size, idx);
             std::vector<cryo_agg_block> rows(idx.size());
             std::vector<cryo_agg_cell> cells(idx.size() * nc);
-            for (size_t k = 0; k < idx.size(); k++) { src[k] = h_src[idx[k]]; sz[k] = h_src_size[idx[k]]; }
-            const int r = agg_blocks_impl(m->h[g], method, src.data(), sz.data(), idx.size(), block_size, f, agg, rows.data(),
+            const int r = agg_blocks_impl(m->h[g], method, in.src.data(), in.sz.data(), idx.size(), block_size, f, agg, rows.data(),
                                           cells.data());
             if (r != CRYO_OK) return r;
             for (size_t k = 0; k < idx.size(); k++) {
@@ -3224,16 +3186,14 @@ int cryo_multi_group_blocks(cryo_multi *m, int method, const void *const *h_src,
     std::vector<uint64_t> tot(G, 0);
     const int rc = guarded([&] {
         return multi_run(m, n, [&](size_t g, const std::vector<size_t> &idx) {
-            std::vector<const void *> src(idx.size());
-            std::vector<uint32_t> sz(idx.size());
-            for (size_t k = 0; k < idx.size(); k++) { src[k] = h_src[idx[k]]; sz[k] = h_src_size[idx[k]]; }
+            const ShareStreams in(h_src, h_src_size, idx);
             /* a share's room: its worst case, or the whole call's room when that is less -- a share that needs more than the
              * call has room for fails the call as the single handle would */
             const size_t cap = idx.size() * S < group_cap ? idx.size() * S : group_cap;
             rows[g].resize(idx.size());
             recs[g].resize(cap ? cap : 1);
             cells[g].resize(cap * nc ? cap * nc : 1);
-            return group_blocks_impl(m->h[g], method, src.data(), sz.data(), idx.size(), block_size, f, grp, agg, rows[g].data(),
+            return group_blocks_impl(m->h[g], method, in.src.data(), in.sz.data(), idx.size(), block_size, f, grp, agg, rows[g].data(),
                                      recs[g].data(), cap, cells[g].data(), &tot[g]);
         });
     });
@@ -3265,34 +3225,22 @@ int cryo_multi_decompress_blocks_keyed(cryo_multi *m, int method, const uint64_t
     if (!keys || !h_src || !h_src_size || !h_dst || !h_status) return CRYO_E_ARG;
     if (m->h.size() == 1) return cryo_codec_decompress_blocks_keyed(m->h[0], method, keys, h_src, h_src_size, n, h_dst, block_size, h_status);
     /* a keyed block always goes to the same handle (its pool entry lives there); unkeyed ones round-robin */
+    const size_t G = m->h.size();
     return guarded([&] {
-        const size_t G = m->h.size();
-        std::vector<std::vector<size_t>> share(G);
-        for (size_t i = 0; i < n; i++) share[keys[i] ? keys[i] % G : i % G].push_back(i);
-        std::vector<int> rc(G, CRYO_OK);
-        const std::function<void(unsigned)> one = [&](unsigned g) {
-            const std::vector<size_t> &idx = share[g];
-            if (idx.empty()) return;
-            rc[g] = guarded([&] {
-                std::vector<const void *> src(idx.size());
+        return multi_run(
+            m, n,
+            [&](size_t g, const std::vector<size_t> &idx) {
+                const ShareStreams in(h_src, h_src_size, idx);
                 std::vector<void *> dst(idx.size());
-                std::vector<uint32_t> sz(idx.size());
                 std::vector<uint64_t> ky(idx.size());
                 std::vector<int32_t> st(idx.size());
-                for (size_t k = 0; k < idx.size(); k++) { src[k] = h_src[idx[k]]; sz[k] = h_src_size[idx[k]]; dst[k] = h_dst[idx[k]]; ky[k] = keys[idx[k]]; }
-                const int r = cryo_codec_decompress_blocks_keyed(m->h[g], method, ky.data(), src.data(), sz.data(), idx.size(), dst.data(), block_size, st.data());
+                for (size_t k = 0; k < idx.size(); k++) { dst[k] = h_dst[idx[k]]; ky[k] = keys[idx[k]]; }
+                const int r = decompress_blocks_keyed_impl(m->h[g], method, ky.data(), in.src.data(), in.sz.data(), idx.size(), dst.data(),
+                                                           block_size, st.data());
                 if (r == CRYO_OK) for (size_t k = 0; k < idx.size(); k++) h_status[idx[k]] = st[k];
                 return r;
-            });
-        };
-        if (m->pool) m->pool->run((unsigned)G, one);
-        else for (unsigned g = 0; g < G; g++) one(g);
-        for (size_t g = 0; g < G; g++)
-            if (rc[g] != CRYO_OK) {
-                snprintf(m->err, sizeof m->err, "device handle %zu: %s", g, cryo_codec_last_error(m->h[g]));
-                return rc[g];
-            }
-        return (int)CRYO_OK;
+            },
+            [&](size_t i) { return (size_t)(keys[i] ? keys[i] % G : i % G); });
     });
 }
 

@@ -5,27 +5,28 @@
  * (decode_pass); these kernels gather the tuples a caller asked for, by item position, out of the decoded chunk and pack them,
  * so that only tuples leave the device:
  *   k_fetch_items    one wave per block, four blocks per workgroup.  A block the decoders rejected gets STREAM without a
- *                    load.  Otherwise the wave reads lower / upper, applies the header rule, and takes its requests 64 per
+ *                    load.  Otherwise the wave reads lower / upper, applies the header rule (heap_header), and takes its requests 64 per
  *                    turn: a lane loads its position, compares it with its left neighbour's (lane 0 with the last of the turn
  *                    before: strictly ascending from 0, which also rejects position 0), loads its 8-byte item and applies
- *                    NOITEM / ITEM.  A wave scan of MAXALIGN(len) places every request inside the block's output.  BADREQ and
+ *                    NOITEM / ITEM (heap_item).  A wave scan of MAXALIGN(len) places every request inside the block's output.  BADREQ and
  *                    OVERLAP are verdicts on the whole block that are known only after the last turn, so the records are
  *                    written in a second sweep over the requests (positions and items come from L2 then).  It writes one
  *                    16-byte record per request with the offset INSIDE the block's output, the same offset and the tuple's
  *                    place in the decoded block into a side table (8 bytes per request, workspace), and the block's sum.
- *   k_fetch_offsets  one workgroup per chunk: the scan of k_recode_offsets over the blocks' sums, starting from the running
- *                    total the chunk before left in device memory; writes every block's base, the chunk's end, and the new
- *                    running total.  (Two levels on purpose: a chunk can hold millions of requests but only K blocks.)
+ *   k_fetch_offsets  one workgroup per chunk: an exclusive scan over the blocks' sums in tiles of 256 (offsets_tile), starting
+ *                    from the running total the chunk before left in device memory; writes every block's base, the chunk's
+ *                    end, and the new running total.  (Two levels on purpose: a chunk can hold millions of requests but only K blocks.)
  *   k_fetch_copy     walks the PACKED side as k_recode_pack does: a fixed grid strides over the 2 KiB pieces of [base[0],
- *                    base[cnt]); a piece finds the block of its first byte by binary search in the bases, then the request
+ *                    base[cnt]); a piece finds the block of its first byte by binary search in the bases (find_last_le), then the request
  *                    by binary search in the block's side table; a lane whose bytes belong to a later block searches on
  *                    from there.  Offsets never decrease and a failed request shares its offset with the next tuple, so "the
  *                    last entry at or below the byte" is always the OK request that owns it.  8 bytes per lane (tuples start
- *                    at multiples of 8 on both sides); the pad [len, MAXALIGN(len)) is masked to zero in registers.  The
+ *                    at multiples of 8 on both sides); the pad [len, MAXALIGN(len)) is masked to zero in registers (mask_tuple_tail).  The
  *                    same grid then strides over the blocks and writes base + offset into the records' `off` (an 8-byte store
  *                    to a field the copy never reads: the copy reads {status, len} and the side table only).
  * A request-side mapping of the copy (a quarter wave per tuple) was considered: it idles on the one-byte tuples and
  * serialises on the tuple that fills a block, both of which the packed side balances; it has not been measured.
+ * The block rules, the scan's tile, the search and the mask are heap_block.h's, shared with the other scan kernels.
  * Every device write is a vector store.  No LDS beyond the scan's four words, no scratch.
  */
 #include "kernels.h"
@@ -34,7 +35,6 @@ namespace cryo {
 
 constexpr uint32_t kFetchOk = 0, kFetchStream = 1, kFetchHeader = 2, kFetchItem = 3, kFetchNoItem = 5, kFetchBadReq = 6,
                    kFetchOverlap = 7;              /* cryo_fetch_status */
-constexpr uint32_t kFetchMaxItems = 290u;          /* MaxHeapTuplesPerPage - 1 (host/storage.c) */
 constexpr uint32_t kFetchPiece = 256u * 8u;        /* packed bytes one workgroup copies per turn */
 
 __device__ inline void fetch_put(uint4 *__restrict__ result, uint2 *__restrict__ side, uint64_t r, uint32_t status, uint32_t len,
@@ -75,9 +75,7 @@ __device__ inline uint64_t fetch_sweep(const uint8_t *__restrict__ p, uint32_t B
             if (q == 0u || q > n) status = kFetchNoItem; /* q == 0 is BADREQ for the whole block; no item is loaded for it */
             else {
                 const uint2 it = *reinterpret_cast<const uint2 *>(p + 8u + 8u * (q - 1u));
-                const uint64_t off = it.x, ln = it.y;
-                if (ln == 0 || (off & 7u) != 0 || off < upper || off + ((ln + 7u) & ~(uint64_t)7u) > B) status = kFetchItem;
-                else { len = it.y; src = it.x; }
+                if (!heap_item(it, upper, B, src, len)) status = kFetchItem;
             }
         }
         const uint64_t a = valid && status == kFetchOk ? ((uint64_t)len + 7u) & ~(uint64_t)7u : 0u;
@@ -116,9 +114,8 @@ k_fetch_items(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, 
     } else {
         const uint8_t *p = dec + (uint64_t)k * dec_stride;
         const uint2 hdr = *reinterpret_cast<const uint2 *>(p);
-        const uint32_t lower = hdr.x, upper = hdr.y;
-        const uint32_t n = (lower - 8u) >> 3;
-        if (lower < 8u || (lower & 7u) != 0u || n > kFetchMaxItems || lower > upper || upper > B || (n == 0u && upper != B)) {
+        uint32_t n, upper;
+        if (!heap_header(hdr, B, n, upper)) {
             fetch_fill(result, side, r0, nreq, lane, kFetchHeader);
         } else {
             bool badreq = false, unused = false;
@@ -139,29 +136,14 @@ __global__ void __launch_bounds__(256)
 k_fetch_offsets(uint32_t cnt, const uint64_t *__restrict__ sum, uint64_t *__restrict__ base, uint64_t *__restrict__ running)
 {
     __shared__ uint64_t wave_sum[4];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint64_t run = *running; /* the same in every thread; written again only after the barriers below */
+    uint64_t run = *running; /* the same in every thread; written again only after the tiles' barriers */
     for (uint32_t t = 0; t < cnt; t += 256u) {
         const uint32_t k = t + threadIdx.x;
-        const uint64_t a = k < cnt ? sum[k] : 0u;
-        uint64_t inc = a;
-#pragma unroll
-        for (uint32_t d = 1; d < 64u; d <<= 1) {
-            const uint64_t up = __shfl_up((unsigned long long)inc, d);
-            if (lane >= d) inc += up;
-        }
-        if (lane == 63u) wave_sum[wave] = inc;
-        __syncthreads();
-        uint64_t before = 0, tile = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < 4u; w++) {
-            const uint64_t s = wave_sum[w];
-            if (w < wave) before += s;
-            tile += s;
-        }
-        if (k < cnt) base[k] = run + before + inc - a;
-        run += tile;
-        __syncthreads(); /* wave_sum is written again in the next turn */
+        const uint64_t a[1] = {k < cnt ? sum[k] : 0u};
+        uint64_t before[1], tile[1];
+        offsets_tile(a, wave_sum, before, tile);
+        if (k < cnt) base[k] = run + before[0];
+        run += tile[0];
     }
     if (threadIdx.x == 0) {
         base[cnt] = run;
@@ -169,16 +151,6 @@ k_fetch_offsets(uint32_t cnt, const uint64_t *__restrict__ sum, uint64_t *__rest
     }
 }
 
-/* the last k in [lo, hi] with v[k] <= x; v[lo] <= x is the caller's */
-__device__ inline uint32_t fetch_find_block(const uint64_t *__restrict__ v, uint32_t lo, uint32_t hi, uint64_t x)
-{
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
-        if (v[mid] <= x) lo = mid;
-        else hi = mid - 1u;
-    }
-    return lo;
-}
 /* the last r in [lo, hi] with side[r].x <= x; side[lo].x <= x is the caller's */
 __device__ inline uint64_t fetch_find_req(const uint2 *__restrict__ side, uint64_t lo, uint64_t hi, uint32_t x)
 {
@@ -205,8 +177,8 @@ k_fetch_copy(uint32_t cnt, const uint8_t *__restrict__ dec, uint64_t dec_stride,
         if (x >= end) continue;
         /* base[cnt] = end > p0: the block of the piece's first byte lies in [0, cnt - 1]; a block without room is never found
          * (its successor starts at the same base) */
-        const uint32_t k0 = fetch_find_block(base, 0u, cnt - 1u, p0);
-        const uint32_t k = base[k0 + 1u] > x ? k0 : fetch_find_block(base, k0 + 1u, cnt - 1u, x);
+        const uint32_t k0 = find_last_le(base, 0u, cnt - 1u, p0);
+        const uint32_t k = base[k0 + 1u] > x ? k0 : find_last_le(base, k0 + 1u, cnt - 1u, x);
         const uint32_t xr = (uint32_t)(x - base[k]); /* below the block's sum, which is below the block size */
         uint64_t r1 = req_first[k + 1u], r0 = req_first[k];
         if (r1 > n_req) r1 = n_req;
@@ -219,13 +191,9 @@ k_fetch_copy(uint32_t cnt, const uint8_t *__restrict__ dec, uint64_t dec_stride,
         if (rec.x != kFetchOk || at >= len) continue; /* cannot happen for a byte below the block's sum */
         const uint64_t tuple_end = base[k] + sd.x + (((uint64_t)len + 7u) & ~(uint64_t)7u) - bias;
         if (tuple_end > dst_cap) continue;
-        uint2 v = *reinterpret_cast<const uint2 *>(dec + (uint64_t)k * dec_stride + sd.y + at);
+        const uint2 v = *reinterpret_cast<const uint2 *>(dec + (uint64_t)k * dec_stride + sd.y + at);
         const uint32_t keep = len - at; /* bytes of the tuple from here on */
-        if (keep < 8u) {                 /* the tuple's last word: its pad is zero whatever the block holds there */
-            if (keep <= 4u) { v.y = 0u; if (keep < 4u) v.x &= (1u << (8u * keep)) - 1u; }
-            else v.y &= (1u << (8u * (keep - 4u))) - 1u;
-        }
-        *reinterpret_cast<uint2 *>(dst + (x - bias)) = v;
+        *reinterpret_cast<uint2 *>(dst + (x - bias)) = mask_tuple_tail(v, keep); /* the tuple's last word: its pad zero */
     }
     /* the records' offsets: inside the block so far, within the call from here on */
     for (uint32_t k = blockIdx.x; k < cnt; k += gridDim.x) {

@@ -6,7 +6,7 @@
  * tuples that pass, so that only matches leave the device:
  *   k_filter_match    one wave per block, four blocks per workgroup, as k_fetch_items.  A block the decoders rejected gets STREAM
  *                     without a load, a bad header HEADER.  Otherwise a lane takes one item per turn (290 items: five turns):
- *                     the fetch's ITEM rule, the TUPLE rule on the tuple's header, then the walk over the columns 1 .. the
+ *                     the ITEM rule (heap_item; the header's is heap_header), the TUPLE rule on the tuple's header, then the walk over the columns 1 .. the
  *                     highest key column.  That loop is the same trip for all 64 lanes -- the column descriptor and the keys
  *                     are read at addresses that depend on the loop counter only, so they are uniform loads; what differs per
  *                     lane is the offset, the null bit and the varlena branch.  A byte-string key (CRYO_KEY_BYTES) reads its
@@ -19,14 +19,15 @@
  *                     sweep sums and a second one writes (items and tuples come from L2 then): per record {offset inside the
  *                     block's output, the tuple's place in the decoded block, len, pos | status << 16} into a side table in
  *                     position order, the first half of the block's row of the table, and the block's two sums.
- *   k_filter_offsets  one workgroup per chunk: the scan of k_fetch_offsets over two arrays at once (bytes, records), from the two
- *                     running totals the chunk before left in device memory; it also writes {rec_first, off} of every row.
- *   k_filter_copy     walks the PACKED side as k_fetch_copy does (2 KiB pieces, a binary search for the block, one for the
- *                     record in the block's side table; bad items share their offset with the next tuple, so "the last entry at
+ *   k_filter_offsets  one workgroup per chunk: the tiled scan of heap_block.h (offsets_tile) over two arrays at once (bytes, records),
+ *                     from the two running totals the chunk before left in device memory; it also writes {rec_first, off} of every row.
+ *   k_filter_copy     walks the PACKED side as k_fetch_copy does (2 KiB pieces, a binary search for the block -- find_last_le --, one
+ *                     for the record in the block's side table; bad items share their offset with the next tuple, so "the last entry at
  *                     or below the byte" is the match that owns it), then the same grid strides over the blocks and writes the
  *                     8-byte records to their final places.
  * The fetch's kernels are not reused: k_fetch_offsets scans one array and its copy finds requests through the caller's CSR table,
- * which a filter does not have.  Every device write is a vector store in plain C++.  No LDS beyond the scan's eight words, no
+ * which a filter does not have; what the two have in common -- the block rules, the scan's tile, the block search, the mask of a
+ * tuple's last word -- is heap_block.h's.  Every device write is a vector store in plain C++.  No LDS beyond the scan's eight words, no
  * scratch.
  */
 #include "kernels.h"
@@ -61,9 +62,7 @@ __device__ inline void filter_sweep(const uint8_t *__restrict__ p, uint32_t B, u
         uint32_t status = kFilterNoMatch, len = 0, src = 0;
         if (valid) {
             const uint2 it = *reinterpret_cast<const uint2 *>(p + 8u + 8u * i);
-            const uint64_t off = it.x, ln = it.y;
-            if (ln == 0 || (off & 7u) != 0 || off < upper || off + ((ln + 7u) & ~(uint64_t)7u) > B) status = kFilterItem;
-            else { len = it.y; src = it.x; }
+            if (!heap_item(it, upper, B, src, len)) status = kFilterItem;
         }
         const bool live = valid && status != kFilterItem;
         const uint32_t verdict = filter_tuple<BYTES>(p + src, len, live, atts, keys, nkeys, max_att);
@@ -118,9 +117,8 @@ k_filter_match(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B,
     else {
         const uint8_t *p = dec + (uint64_t)k * dec_stride;
         const uint2 hdr = *reinterpret_cast<const uint2 *>(p);
-        const uint32_t lower = hdr.x, upper = hdr.y;
-        const uint32_t n = (lower - 8u) >> 3;
-        if (lower < 8u || (lower & 7u) != 0u || n > kFilterMaxItems || lower > upper || upper > B || (n == 0u && upper != B))
+        uint32_t n, upper;
+        if (!heap_header(hdr, B, n, upper))
             status = kFilterHeader;
         else {
             n_items = n; /* lower <= B: n <= side_stride */
@@ -152,36 +150,20 @@ k_filter_offsets(uint32_t cnt, const uint64_t *__restrict__ sum, uint64_t *__res
                  uint4 *__restrict__ blocks)
 {
     __shared__ uint64_t wave_sum[8];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint64_t run_b = running[0], run_r = running[1]; /* the same in every thread; written again only after the barriers below */
+    uint64_t run_b = running[0], run_r = running[1]; /* the same in every thread; written again only after the tiles' barriers */
     for (uint32_t t = 0; t < cnt; t += 256u) {
         const uint32_t k = t + threadIdx.x;
-        const uint64_t ab = k < cnt ? sum[k] : 0u, ar = k < cnt ? sum[cnt + k] : 0u;
-        uint64_t ib = ab, ir = ar;
-#pragma unroll
-        for (uint32_t d = 1; d < 64u; d <<= 1) {
-            const uint64_t ub = __shfl_up((unsigned long long)ib, d), ur = __shfl_up((unsigned long long)ir, d);
-            if (lane >= d) { ib += ub; ir += ur; }
-        }
-        if (lane == 63u) { wave_sum[wave] = ib; wave_sum[4u + wave] = ir; }
-        __syncthreads();
-        uint64_t before_b = 0, tile_b = 0, before_r = 0, tile_r = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < 4u; w++) {
-            const uint64_t sb = wave_sum[w], sr = wave_sum[4u + w];
-            if (w < wave) { before_b += sb; before_r += sr; }
-            tile_b += sb;
-            tile_r += sr;
-        }
+        const uint64_t a[2] = {k < cnt ? sum[k] : 0u, k < cnt ? sum[cnt + k] : 0u}; /* bytes, records */
+        uint64_t before[2], tile[2];
+        offsets_tile(a, wave_sum, before, tile);
         if (k < cnt) {
-            const uint64_t off = run_b + before_b + ib - ab, first = run_r + before_r + ir - ar;
+            const uint64_t off = run_b + before[0], first = run_r + before[1];
             base[k] = off;
             base[cnt + 1u + k] = first;
             blocks[2u * k + 1u] = make_uint4((uint32_t)first, (uint32_t)(first >> 32), (uint32_t)off, (uint32_t)(off >> 32));
         }
-        run_b += tile_b;
-        run_r += tile_r;
-        __syncthreads(); /* wave_sum is written again in the next turn */
+        run_b += tile[0];
+        run_r += tile[1];
     }
     if (threadIdx.x == 0) {
         base[cnt] = run_b;
@@ -191,16 +173,6 @@ k_filter_offsets(uint32_t cnt, const uint64_t *__restrict__ sum, uint64_t *__res
     }
 }
 
-/* the last k in [lo, hi] with v[k] <= x; v[lo] <= x is the caller's */
-__device__ inline uint32_t filter_find_block(const uint64_t *__restrict__ v, uint32_t lo, uint32_t hi, uint64_t x)
-{
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
-        if (v[mid] <= x) lo = mid;
-        else hi = mid - 1u;
-    }
-    return lo;
-}
 /* the last j in [lo, hi] with side[j].x <= x; side[lo].x <= x is the caller's */
 __device__ inline uint32_t filter_find_rec(const uint4 *__restrict__ side, uint32_t lo, uint32_t hi, uint32_t x)
 {
@@ -225,8 +197,8 @@ k_filter_copy(uint32_t cnt, const uint8_t *__restrict__ dec, uint64_t dec_stride
         if (x >= end) continue;
         /* base[cnt] = end > p0: the block of the piece's first byte lies in [0, cnt - 1]; a block without room is never found
          * (its successor starts at the same base) */
-        const uint32_t k0 = filter_find_block(base, 0u, cnt - 1u, p0);
-        const uint32_t k = base[k0 + 1u] > x ? k0 : filter_find_block(base, k0 + 1u, cnt - 1u, x);
+        const uint32_t k0 = find_last_le(base, 0u, cnt - 1u, p0);
+        const uint32_t k = base[k0 + 1u] > x ? k0 : find_last_le(base, k0 + 1u, cnt - 1u, x);
         const uint32_t xr = (uint32_t)(x - base[k]); /* below the block's sum, which is below the block size */
         const uint32_t nrec = (uint32_t)(base_r[k + 1u] - base_r[k]);
         if (nrec == 0u || nrec > side_stride) continue; /* a block with room has records */
@@ -236,13 +208,9 @@ k_filter_copy(uint32_t cnt, const uint8_t *__restrict__ dec, uint64_t dec_stride
         if ((e.w >> 16) != 0u || at >= len) continue; /* cannot happen for a byte below the block's sum */
         const uint64_t tuple_end = base[k] + e.x + (((uint64_t)len + 7u) & ~(uint64_t)7u) - bias;
         if (tuple_end > dst_cap) continue;
-        uint2 v = *reinterpret_cast<const uint2 *>(dec + (uint64_t)k * dec_stride + e.y + at);
+        const uint2 v = *reinterpret_cast<const uint2 *>(dec + (uint64_t)k * dec_stride + e.y + at);
         const uint32_t keep = len - at; /* bytes of the tuple from here on */
-        if (keep < 8u) {                 /* the tuple's last word: its pad is zero whatever the block holds there */
-            if (keep <= 4u) { v.y = 0u; if (keep < 4u) v.x &= (1u << (8u * keep)) - 1u; }
-            else v.y &= (1u << (8u * (keep - 4u))) - 1u;
-        }
-        *reinterpret_cast<uint2 *>(dst + (x - bias)) = v;
+        *reinterpret_cast<uint2 *>(dst + (x - bias)) = mask_tuple_tail(v, keep); /* the tuple's last word: its pad zero */
     }
     /* the records, from the side table to their places within the call */
     for (uint32_t k = blockIdx.x; k < cnt; k += gridDim.x) {

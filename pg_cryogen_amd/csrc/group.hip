@@ -6,8 +6,8 @@
  * matches by one or two integer columns and reduce up to four more columns per group, so that a row per block and a record and a
  * few cells per group leave the device:
  *   k_group_block    one wave per block, two blocks per workgroup (a wave's share of LDS is 16 240 bytes).  A block the decoders
- *                    rejected gets STREAM without a load, a bad header HEADER.  Otherwise the sweep is k_agg_block's -- a lane
- *                    takes one item per turn (290 items: five turns), the ITEM rule, then the walk of filter_walk.h over the
+ *                    rejected gets STREAM without a load, a bad header (heap_header, heap_block.h) HEADER.  Otherwise the sweep is k_agg_block's -- a lane
+ *                    takes one item per turn (290 items: five turns), the ITEM rule (heap_item), then the walk of filter_walk.h over the
  *                    columns 1 .. max(highest key, group, aggregate column) with six capture slots -- and instead of reducing as
  *                    it goes the wave
  *                      1. compacts the matches in position order into LDS (ballot + popcount prefix): per match the two group
@@ -25,7 +25,7 @@
  *                    Descriptor, keys and columns are read at addresses that depend on loop counters only (uniform loads); no
  *                    load leaves [t, t + len).  A descriptor with a byte-string key runs k_group_block<true>, whose walk compares
  *                    those too and counts an undecided tuple in n_bad; every other descriptor runs k_group_block<false>.
- *   k_group_offsets  one workgroup per chunk: the scan of k_filter_offsets over one array, the blocks' n_groups, from the running
+ *   k_group_offsets  one workgroup per chunk: the tiled scan of heap_block.h (offsets_tile) over the blocks' n_groups, from the running
  *                    total the chunk before left in device memory; it writes first_group into the rows.
  *   k_group_copy     a grid stride over the blocks: block k's records and cells from the side area to first_group of the call's
  *                    output, word by word, cut off at group_cap.
@@ -47,10 +47,10 @@ static_assert(sizeof(GroupRec) == 24 && sizeof(GroupCell) == 40, "the records' l
 /* a wave's matches in LDS.  meta: bits 0 .. 1 the group columns' null bits, bits 2 .. 5 set where aggregate column j has a
  * value.  order[s]: the match at place s of the contract's order, bit 16 set when it is a group's head */
 struct GroupLds {
-    int64_t key[kGroupMaxBy][kFilterMaxItems];
-    int64_t val[kAggMaxCols][kFilterMaxItems];
-    uint32_t meta[kFilterMaxItems];
-    uint32_t order[kFilterMaxItems];
+    int64_t key[kGroupMaxBy][kHeapMaxItems];
+    int64_t val[kAggMaxCols][kHeapMaxItems];
+    uint32_t meta[kHeapMaxItems];
+    uint32_t order[kHeapMaxItems];
 };
 static_assert(sizeof(GroupLds) * kGroupWaves <= 65536u, "a workgroup's LDS stays within 64 KiB");
 
@@ -84,9 +84,8 @@ k_group_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, 
     else {
         const uint8_t *p = dec + (uint64_t)k * dec_stride;
         const uint2 hdr = *reinterpret_cast<const uint2 *>(p);
-        const uint32_t lower = hdr.x, upper = hdr.y;
-        const uint32_t n = (lower - 8u) >> 3;
-        if (lower < 8u || (lower & 7u) != 0u || n > kFilterMaxItems || lower > upper || upper > B || (n == 0u && upper != B))
+        uint32_t n, upper;
+        if (!heap_header(hdr, B, n, upper))
             status = kFilterHeader;
         else {
             n_items = n;
@@ -97,9 +96,7 @@ k_group_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, 
                 uint32_t verdict = kFilterNoMatch, len = 0, src = 0;
                 if (valid) {
                     const uint2 it = *reinterpret_cast<const uint2 *>(p + 8u + 8u * i); /* 8 + 8 n = lower <= B */
-                    const uint64_t off = it.x, ln = it.y;
-                    if (ln == 0 || (off & 7u) != 0 || off < upper || off + ((ln + 7u) & ~(uint64_t)7u) > B) verdict = kFilterItem;
-                    else { len = it.y; src = it.x; }
+                    if (!heap_item(it, upper, B, src, len)) verdict = kFilterItem;
                 }
                 const bool live = valid && verdict != kFilterItem;
                 WalkCaptureN<kGroupSlots> cap;
@@ -218,32 +215,17 @@ __global__ void __launch_bounds__(256)
 k_group_offsets(uint32_t cnt, uint64_t *__restrict__ running, uint4 *__restrict__ blocks)
 {
     __shared__ uint64_t wave_sum[4];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint64_t run = running[0]; /* the same in every thread; written again only after the barriers below */
+    uint64_t run = running[0]; /* the same in every thread; written again only after the tiles' barriers */
     for (uint32_t t = 0; t < cnt; t += 256u) {
         const uint32_t k = t + threadIdx.x;
-        const uint64_t a = k < cnt ? blocks[2u * k + 1u].x : 0u;
-        uint64_t inc = a;
-#pragma unroll
-        for (uint32_t d = 1; d < 64u; d <<= 1) {
-            const uint64_t u = __shfl_up((unsigned long long)inc, d);
-            if (lane >= d) inc += u;
-        }
-        if (lane == 63u) wave_sum[wave] = inc;
-        __syncthreads();
-        uint64_t before = 0, tile = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < 4u; w++) {
-            const uint64_t sw = wave_sum[w];
-            if (w < wave) before += sw;
-            tile += sw;
-        }
+        const uint64_t a[1] = {k < cnt ? blocks[2u * k + 1u].x : 0u};
+        uint64_t before[1], tile[1];
+        offsets_tile(a, wave_sum, before, tile);
         if (k < cnt) {
-            const uint64_t first = run + before + inc - a;
-            blocks[2u * k + 1u] = make_uint4((uint32_t)a, 0u, (uint32_t)first, (uint32_t)(first >> 32));
+            const uint64_t first = run + before[0];
+            blocks[2u * k + 1u] = make_uint4((uint32_t)a[0], 0u, (uint32_t)first, (uint32_t)(first >> 32));
         }
-        run += tile;
-        __syncthreads(); /* wave_sum is written again in the next turn */
+        run += tile[0];
     }
     if (threadIdx.x == 0) running[0] = run;
 }

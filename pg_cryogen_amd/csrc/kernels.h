@@ -10,6 +10,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "heap_block.h"
+
 /* Tuning and debugging switches read from the environment exist in -DCRYO_DEBUG builds only (the A/B builds under
  * profiles/): the product library reads no environment variable but CRYO_HOST_THREADS (cryo_codec.cpp); what a
  * deployment may change is a per-handle option (cryo_codec_set_option). */
@@ -248,11 +250,10 @@ hipError_t launch_fetch(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride
  * and its records to d_rec at their places within the call, or -- chunk_relative -- at those less the chunk's first; a tuple that
  * would end beyond dst_cap and a record at or beyond rec_cap are not written.  count_only: k_filter_match alone; rec_first and
  * off of the table are 0 and nothing else is written. */
-constexpr uint32_t kFilterMaxItems = 290u; /* MaxHeapTuplesPerPage - 1 (host/storage.c) */
 inline uint32_t filter_side_stride(uint32_t block_size)
 {
     const uint32_t fit = (block_size - 8u) / 8u; /* lower <= B: no more item ids than this */
-    return fit < kFilterMaxItems ? fit : kFilterMaxItems;
+    return fit < kHeapMaxItems ? fit : kHeapMaxItems;
 }
 hipError_t launch_filter(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
                          const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, uint32_t max_att,

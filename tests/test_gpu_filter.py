@@ -282,6 +282,49 @@ def test_chunks_give_the_same_results(flt, oracle, method):
     flt.set_option(cc.OPT_WORKSPACE_MAX_BYTES, 0)
 
 
+# ---- more than 256 blocks in one chunk: the second tile of the offset scan ----
+TILE_B, TILE_N, TILE_CUT = 4096, 330, 262
+
+
+@pytest.fixture(scope="module")
+def two_tiles(oracle):
+    """ten generator blocks of 4 KiB, repeated to 330: at this size the WIDE and RANDOM blocks hold 290 bad items each (records
+    without bytes), the others 56 and 102 tuples or none; the keys pass some tuples of blocks 1 and 2 and none of blocks 6 and 7.
+    Block 262 stands for a stream the decoders reject.  (raws, keys, the reference's result: one for both methods)"""
+    raws = [oracle.synth(77, k, TILE_B, k % 5) for k in range(10)]
+    keys = range_keys(311, 650)
+    blocks = [None if i == TILE_CUT else raws[i % 10] for i in range(TILE_N)]
+    return raws, keys, fr.filter_call(blocks, SYNTH_ATTS, keys)
+
+
+@pytest.mark.parametrize("method", [METHOD_LZ4, METHOD_ZSTD])
+def test_second_tile_of_the_offset_scan(flt, oracle, two_tiles, method):
+    """330 blocks are one chunk under the default budget, so k_filter_offsets runs two tiles of 256 and 74 rows: the running
+    totals carried into the second tile and the sums inside it, with a rejected stream, a block without a match and partly
+    matching blocks beyond row 256; device buffers and host buffers against the reference, nothing left out"""
+    raws, keys, want = two_tiles
+    enc = [oracle_encode(oracle, method, r) for r in raws]
+    comps = [enc[i % 10] for i in range(TILE_N)]
+    comps[TILE_CUT] = comps[TILE_CUT][:len(comps[TILE_CUT]) - 9]
+    assert all(np.array_equal(fr.decode(oracle, method, c, TILE_B), r) for c, r in zip(enc, raws))
+    assert fr.decode(oracle, method, comps[TILE_CUT], TILE_B) is None
+    t = want[0]
+    assert t["status"][TILE_CUT] == fr.STREAM and set(t["status"].tolist()) == {0, fr.STREAM}
+    assert (t["n_items"][256], t["n_match"][256], t["n_bad"][256]) == (56, 0, 0)      # tuples, and none of them passes
+    assert 0 < t["n_match"][261] < t["n_items"][261] and 0 < t["n_match"][272] < t["n_items"][272]
+    assert t["n_bad"][255] == 290 and t["rec_first"][256] > 0 and t["off"][256] > 0
+    for what, got in (("device buffers", filter_batch(flt, method, comps, TILE_B, SYNTH_ATTS, keys)),
+                      ("host buffers", host_call(flt, method, comps, TILE_B, SYNTH_ATTS, keys))):
+        same(got, want, (method, what))
+        # every row starts where the one before ended, across row 256 as anywhere else
+        g, recs = got[0], got[1][:got[3][1]]
+        nrec = g["n_match"].astype(np.uint64) + g["n_bad"]
+        assert (g["rec_first"][1:] == g["rec_first"][:-1] + nrec[:-1]).all(), (method, what)
+        room = np.where(recs["status"] == 0, (recs["len"].astype(np.uint64) + 7) & ~np.uint64(7), 0)
+        upto = np.concatenate([[0], np.cumsum(room, dtype=np.uint64)]).astype(np.uint64)
+        assert (g["off"] == upto[g["rec_first"]]).all() and got[3][0] == upto[-1], (method, what)
+
+
 # ---- the caps ----
 @pytest.mark.parametrize("method", [METHOD_LZ4, METHOD_ZSTD])
 def test_caps(flt, oracle, method):

@@ -250,6 +250,47 @@ def test_chunks_give_the_same_results(grp, oracle, sixty_four, method):
     grp.set_option(cc.OPT_WORKSPACE_MAX_BYTES, 0)
 
 
+# ---- more than 256 blocks in one chunk: the second tile of the offset scan ----
+TILE_B, TILE_N, TILE_CUT = 4096, 330, 262
+
+
+@pytest.fixture(scope="module")
+def two_tiles(oracle):
+    """ten generator blocks of 4 KiB, repeated to 330: at this size the WIDE and RANDOM blocks hold 290 bad items each, the others
+    56 and 102 tuples or none; the keys pass some tuples of blocks 1 and 2 and none of blocks 6 and 7.  Block 262 stands for a
+    stream the decoders reject.  Grouped by the rowid column every match is a group.  (raws, keys, the reference's result: one
+    for both methods)"""
+    raws = [oracle.synth(77, k, TILE_B, k % 5) for k in range(10)]
+    keys = [(1, fr.INT4, fr.GE, 311), (1, fr.INT4, fr.LT, 650)]
+    blocks = [None if i == TILE_CUT else raws[i % 10] for i in range(TILE_N)]
+    return raws, keys, gr.group_call(blocks, SYNTH_ATTS, keys, ROWID, ROWID)
+
+
+@pytest.mark.parametrize("method", METHODS)
+def test_second_tile_of_the_offset_scan(grp, oracle, two_tiles, method):
+    """330 blocks are one chunk under the default budget, so k_group_offsets runs two tiles of 256 and 74 rows: the running
+    total carried into the second tile and the sums inside it, with a rejected stream, a block without a match and partly
+    matching blocks beyond row 256; device buffers and host buffers against the reference, nothing left out"""
+    raws, keys, want = two_tiles
+    enc = [oracle_encode(oracle, method, r) for r in raws]
+    comps = [enc[i % 10] for i in range(TILE_N)]
+    comps[TILE_CUT] = comps[TILE_CUT][:len(comps[TILE_CUT]) - 9]
+    assert all(np.array_equal(ar.decode(oracle, method, c, TILE_B), r) for c, r in zip(enc, raws))
+    assert ar.decode(oracle, method, comps[TILE_CUT], TILE_B) is None
+    t = want[0]
+    assert t["status"][TILE_CUT] == fr.STREAM and set(t["status"].tolist()) == {0, fr.STREAM}
+    assert (t["n_items"][256], t["n_match"][256], t["n_groups"][256]) == (56, 0, 0)   # tuples, and none of them passes
+    assert 0 < t["n_match"][261] < t["n_items"][261] and 0 < t["n_match"][272] < t["n_items"][272]
+    assert t["n_bad"][255] == 290 and t["first_group"][256] > 0 and want[3] == int(t["n_match"].sum())
+    for what, got in (("device buffers", group_batch(grp, method, comps, TILE_B, SYNTH_ATTS, keys, ROWID, ROWID)),
+                      ("host buffers", host_call(grp, method, comps, TILE_B, SYNTH_ATTS, keys, ROWID, ROWID))):
+        same(got, want, (method, what))
+        # every row starts where the one before ended, across row 256 as anywhere else
+        g = got[0]
+        assert g["first_group"][0] == 0 and (g["first_group"][1:] == g["first_group"][:-1] + g["n_groups"][:-1]).all(), (method, what)
+        assert got[3] == int(g["first_group"][-1]) + int(g["n_groups"][-1]), (method, what)
+
+
 # ---- caps ----
 def test_caps(grp, oracle):
     blocks = [gc.turn_block("distinct", 65), gc.turn_block("alternate", 64), gc.turn_block("runs3", 129)]
