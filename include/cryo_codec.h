@@ -608,6 +608,74 @@ int cryo_codec_group_batch(cryo_codec *c, int method, const void *d_src, const u
                            const cryo_group *grp, const cryo_agg *agg, cryo_group_block *d_blocks, cryo_group_rec *d_groups,
                            uint64_t group_cap, cryo_agg_cell *d_cells, uint64_t *d_total);
 
+/* ---- projecting a scan: stored streams -> decoded in handle workspace -> keys tested, the named fixed-width columns of every
+ *      match copied into a fixed row -> a row per block, an 8-byte record and a row of 8 .. 64 bytes per match come back ----
+ * The SELECT list of the query the filter answers: SELECT id, ts, revenue FROM t WHERE ts >= a AND ts < b.  Through the filter
+ * every matching tuple crosses PCIe whole -- 23 bytes of header, the null bitmap and every text column the query never asked for --
+ * and the host deforms it a second time to pick three integers; here the columns are picked where the decoded block lies, and 8
+ * + row_bytes bytes per match leave the device instead of 8 + MAXALIGN(len) (pg_cryogen_amd/host/project.h walks a relation with
+ * it).  A projected column is only copied, never compared or added, so it needs no type: float4, float8, bool, date, timestamp
+ * and oid columns come back bit for bit.
+ * A call names n_blocks stored streams as cryo_codec_check_batch does, the filter's descriptor *f (columns and up to four ANDed
+ * keys, unchanged; byte-string keys are allowed exactly as in the aggregate) and a projection *prj: ncols columns, each {att}.
+ * Out of scope: varlena columns in the projection (text stays with the filter), fixed columns wider than 8 bytes (uuid, name),
+ * expressions, more than 8 columns, and a combined project-and-aggregate call.
+ *
+ * Descriptor.  CRYO_E_ARG when: *f breaks one of the filter's descriptor rules above; f->flags != 0 (a bare count is
+ * CRYO_FILTER_COUNT_ONLY's job); ncols is 0 or above 8; a column's att outside 1 .. f->natts; the column's attlen not 1, 2, 4 or
+ * 8, or its attalign below its attlen (varlena and wider fixed columns are not projected); a reserved field (prj->rsv, a column's
+ * rsv or rsv2) that is not zero.  The same column may be named twice, and it may also carry a key.
+ *
+ * Row layout, fixed by the descriptor alone and the same for every match of the call: column j of the descriptor, of width w_j =
+ * its attlen, lies at o_j, with o_0 = 0 and o_j = align(o_(j-1) + w_(j-1), w_j); row_bytes = MAXALIGN(o_last + w_last), 8 .. 64
+ * (CRYO_PROJECT_COL_OFFSET and CRYO_PROJECT_ROW_BYTES below).  A non-NULL column is the column's w_j bytes as they lie in the tuple
+ * (little-endian), bit for bit; a NULL column -- its bitmap bit is clear, or it lies beyond the tuple's natts -- is zero, and so is
+ * every pad byte.
+ *
+ * Per block (names as in the check's, the filter's and the aggregate's rules above):
+ *   CRYO_FETCH_STREAM (1), CRYO_FETCH_HEADER (2)   exactly the filter's; no item is examined, the block has no record and no row
+ *   otherwise (status 0, n_items = n) every item 1 .. n is examined with the filter's ITEM rule and TUPLE rule.  The walk is the
+ *   aggregate's: over the columns 1 .. max(highest key column, highest projected column) -- that far for every tuple, whatever the
+ *   keys on the way said, and not a column further.  So a tuple whose bytes end before a projected column that lies beyond the
+ *   last key column is CRYO_FILTER_TUPLE here, where the same keys alone would pass it in the filter.  An undecided tuple is a bad
+ *   item (CRYO_FILTER_UNDECIDED).
+ *   OVERLAP is never reported: a block places at most 290 * row_bytes bytes whatever it holds, so status 7 does not occur here.
+ *
+ * Results.  One cryo_project_block per block, in call order.  One cryo_project_rec per match {pos, 0, nulls} -- bit j of nulls is
+ * set when projected column j is NULL, and no other bit is -- and one per bad item {pos, CRYO_FETCH_ITEM, CRYO_FILTER_TUPLE or
+ * CRYO_FILTER_UNDECIDED, 0}, in position order within the block; the block's records are records rec_first .. rec_first +
+ * n_match + n_bad - 1 of the call: exactly the filter's record rule.  One row per match: the block's rows are rows row_first ..
+ * row_first + n_match - 1 of the call, in position order, so the k-th match record of the block belongs to row row_first + k;
+ * row r lies at byte r * row_bytes of the rows.  rec_first and row_first are the sums over the blocks before the block (a STREAM
+ * or HEADER block carries the values at which the next block starts).  total[0] = the rows, total[1] = the records of the whole
+ * call, counted in full even where a cap cuts the writing off: no row at or beyond row_cap rows, no record at or beyond rec_cap,
+ * and nothing at or beyond either total is written.  row_cap >= 290 * n_blocks and rec_cap >= 290 * n_blocks always suffice.
+ * The output of a call is defined byte for byte. */
+typedef struct { uint16_t att; uint16_t rsv; uint32_t rsv2; } cryo_project_col;              /* att 1-based; 8 bytes */
+typedef struct { uint32_t ncols, rsv; const cryo_project_col *cols; } cryo_project;
+#define CRYO_PROJECT_MAX_COLS 8u
+typedef struct { uint32_t status, n_items, n_match, n_bad; uint64_t rec_first, row_first; } cryo_project_block; /* 32 bytes */
+typedef struct { uint16_t pos, status; uint32_t nulls; } cryo_project_rec;                    /* 8 bytes */
+/* the row layout, column by column: with `end` the end of the column before (0 for the first), a column of width w lies at
+ * CRYO_PROJECT_COL_OFFSET(end, w) and ends at that plus w; the row takes CRYO_PROJECT_ROW_BYTES(the last column's end) bytes */
+#define CRYO_PROJECT_COL_OFFSET(end, w) (((uint32_t)(end) + (uint32_t)(w) - 1u) & ~((uint32_t)(w) - 1u))
+#define CRYO_PROJECT_ROW_BYTES(end) (((uint32_t)(end) + 7u) & ~7u)
+/* Device buffers.  The structs *f and *prj are host memory; f->atts, f->keys and prj->cols are DEVICE arrays (4-byte / 8-byte /
+ * 8-byte aligned).  The host validates the descriptors before anything is queued: it reads the three arrays back on the handle's
+ * stream (one wait for what the stream held before the call; with a byte-string key the filter's two more), then puts the
+ * kernel's column table -- 64 bytes: att, width and offset per column -- into handle workspace (one more wait); from there on the
+ * call is asynchronous, with no host wait between its internal chunks.  d_rows (row_cap rows of row_bytes), d_rec (rec_cap
+ * records) and d_total 8-byte, d_blocks (n_blocks rows) 16-byte aligned (CRYO_E_ARG otherwise); d_total has two entries and is also
+ * where the two running totals live between the call's internal chunks.  Decode as in the filter: the automatic routes, handle
+ * workspace, chunks within CRYO_OPT_WORKSPACE_MAX_BYTES (the workspace also holds a side area of 8 + row_bytes bytes per possible
+ * item of a chunk: up to 290 per block); the device pool is neither read nor filled, nothing counts in cryo_codec_counters.
+ * CRYO_E_ARG as for cryo_codec_filter_batch (the same block-size rule), a bad descriptor, a null prj, a null d_total, a null
+ * d_blocks, a null d_rows with row_cap > 0 or a null d_rec with rec_cap > 0; n_blocks == 0: CRYO_OK, totals 0. */
+int cryo_codec_project_batch(cryo_codec *c, int method, const void *d_src, const uint64_t *d_src_off,
+                             const uint32_t *d_src_size, uint32_t block_size, uint64_t n_blocks, const cryo_filter *f,
+                             const cryo_project *prj, void *d_rows, uint64_t row_cap, cryo_project_rec *d_rec,
+                             uint64_t rec_cap, cryo_project_block *d_blocks, uint64_t *d_total);
+
 /* ---- single block, HOST buffers: what cryo_compress()/cryo_decompress()
  *      (compression.c:125-159) call.  Synchronous: H2D, kernel, D2H. ---- */
 int cryo_codec_compress_block(cryo_codec *c, int method, int param,
@@ -723,6 +791,24 @@ int cryo_codec_group_blocks(cryo_codec *c, int method, const void *const *h_src,
                             const cryo_agg *agg, cryo_group_block *h_blocks, cryo_group_rec *h_groups, size_t group_cap,
                             cryo_agg_cell *h_cells, uint64_t *h_total);
 
+/* cryo_codec_project_batch on host buffers (stream i: h_src[i], h_src_size[i] bytes; f->atts, f->keys and prj->cols are HOST
+ * arrays), synchronous.  Only compressed bytes and the descriptors travel towards the device, only the block table, records and
+ * rows come back.
+ *   Upload   the streams staged and uploaded as by cryo_codec_filter_blocks, then the descriptors in a second copy: h2d_bytes
+ *            grows by another align16(4 * natts) + 16 * nkeys + align16(8 * ncols) (plus, as everywhere, the constants of
+ *            byte-string keys).
+ *   Return   after the last chunk the rows of the block table of the whole call, then -- their numbers known from the last row of
+ *            the table -- exactly the call's records and rows (two waits): d2h_bytes grows by exactly
+ *            32 * n_blocks + 8 * h_total[1] + row_bytes * h_total[0].
+ *   Errors   more rows than row_cap or more records than rec_cap: CRYO_E_DSTSIZE, and h_rows and h_rec hold nothing to rely on
+ *            (row_cap >= 290 * n_blocks and rec_cap >= 290 * n_blocks always fit).  CRYO_E_ARG as cryo_codec_project_batch; a bad
+ *            descriptor is refused before a device is touched.  n_blocks == 0: CRYO_OK, totals 0.
+ * h_total has two entries.  Returns CRYO_OK when the batch ran, whatever the table says. */
+int cryo_codec_project_blocks(cryo_codec *c, int method, const void *const *h_src, const uint32_t *h_src_size,
+                              size_t n_blocks, size_t block_size, const cryo_filter *f, const cryo_project *prj,
+                              void *h_rows, size_t row_cap, cryo_project_rec *h_rec, size_t rec_cap,
+                              cryo_project_block *h_blocks, uint64_t *h_total);
+
 /* ---- device-resident block pool ("optional device-resident compressed/decompressed pool so
  *      repeated scans skip PCIe"; the reference's cache is host-only: cache.c:17-50).
  *      With CRYO_OPT_POOL_BYTES > 0 the decoded blocks of keyed calls stay in HBM (first in, first out).  A key is the
@@ -831,6 +917,18 @@ int cryo_multi_group_blocks(cryo_multi *m, int method, const void *const *h_src,
                             size_t n_blocks, size_t block_size, const cryo_filter *f, const cryo_group *grp,
                             const cryo_agg *agg, cryo_group_block *h_blocks, cryo_group_rec *h_groups, size_t group_cap,
                             cryo_agg_cell *h_cells, uint64_t *h_total);
+
+/* cryo_codec_project_blocks across the devices: block i -> handle i mod G.  Regions as in cryo_multi_filter_blocks: handle g, whose
+ * share is the blocks g, g + G, ..., has one row region of 290 * share rows and one record region of 290 * share records, the
+ * regions laid out in handle order from h_rows and h_rec on (a region that reaches beyond its cap is cut there, so row_cap >= 290
+ * * n_blocks and rec_cap >= 290 * n_blocks always suffice).  The block table comes back in call order and finds everything:
+ * row_first counts from h_rows and rec_first from h_rec, but with more than one handle they are running sums only within one
+ * handle's blocks (from its regions' starts).  h_total[0] / h_total[1]: the end of the last row / record used (0: none).  One
+ * handle: exactly cryo_codec_project_blocks. */
+int cryo_multi_project_blocks(cryo_multi *m, int method, const void *const *h_src, const uint32_t *h_src_size,
+                              size_t n_blocks, size_t block_size, const cryo_filter *f, const cryo_project *prj,
+                              void *h_rows, size_t row_cap, cryo_project_rec *h_rec, size_t rec_cap,
+                              cryo_project_block *h_blocks, uint64_t *h_total);
 
 /* ---- batch helpers used by staging, tests and the benchmark ---- */
 

@@ -62,6 +62,12 @@ GROUP_MAX_BY = 2
 GROUP_BLOCK = np.dtype([("status", "<u4"), ("n_items", "<u4"), ("n_match", "<u4"), ("n_bad", "<u4"),
                         ("n_groups", "<u4"), ("rsv", "<u4"), ("first_group", "<u8")])                             # cryo_group_block
 GROUP_REC = np.dtype([("key", "<i8", (2,)), ("n_rows", "<u4"), ("nulls", "<u4")])                                # cryo_group_rec
+# the projecting scan (include/cryo_codec.h): a block's statuses are the aggregate's, a record's the filter's
+PROJECT_MAX_COLS = 8
+PROJECT_COL = np.dtype([("att", "<u2"), ("rsv", "<u2"), ("rsv2", "<u4")])                                       # cryo_project_col
+PROJECT_BLOCK = np.dtype([("status", "<u4"), ("n_items", "<u4"), ("n_match", "<u4"), ("n_bad", "<u4"),
+                          ("rec_first", "<u8"), ("row_first", "<u8")])                                          # cryo_project_block
+PROJECT_REC = np.dtype([("pos", "<u2"), ("status", "<u2"), ("nulls", "<u4")])                                   # cryo_project_rec
 LZ4_PATH_AUTO, LZ4_PATH_RING, LZ4_PATH_INDEXED, LZ4_PATH_FEW_BLOCKS = 0, 1, 2, 3
 
 DIST_WIDE, DIST_NARROW, DIST_INT4, DIST_RANDOM, DIST_ZEROS = range(5)
@@ -92,6 +98,7 @@ ABI_SYMBOLS = [
     "cryo_codec_filter_batch", "cryo_codec_filter_blocks", "cryo_multi_filter_blocks",
     "cryo_codec_agg_batch", "cryo_codec_agg_blocks", "cryo_multi_agg_blocks",
     "cryo_codec_group_batch", "cryo_codec_group_blocks", "cryo_multi_group_blocks",
+    "cryo_codec_project_batch", "cryo_codec_project_blocks", "cryo_multi_project_blocks",
     "cryo_codec_lz4_index_cap", "cryo_codec_lz4_index_rows",
 ]
 
@@ -116,6 +123,11 @@ class CryoAgg(C.Structure):
 class CryoGroup(C.Structure):
     """cryo_group: by points to a device array for group_batch, to a host array for group_blocks"""
     _fields_ = [("nby", C.c_uint32), ("rsv", C.c_uint32), ("by", C.c_void_p)]
+
+
+class CryoProject(C.Structure):
+    """cryo_project: cols points to a device array for project_batch, to a host array for project_blocks"""
+    _fields_ = [("ncols", C.c_uint32), ("rsv", C.c_uint32), ("cols", C.c_void_p)]
 
 
 class TransferCounters(C.Structure):
@@ -214,6 +226,10 @@ def lib():
     L.cryo_codec_group_batch.argtypes = [vp, i32, vp, vp, vp, u32, u64, fp, gp, ap, vp, vp, u64, vp, vp]
     L.cryo_codec_group_blocks.argtypes = [vp, i32, vp, vp, sz, sz, fp, gp, ap, vp, vp, sz, vp, C.POINTER(u64)]
     L.cryo_multi_group_blocks.argtypes = [vp, i32, vp, vp, sz, sz, fp, gp, ap, vp, vp, sz, vp, C.POINTER(u64)]
+    pp = C.POINTER(CryoProject)
+    L.cryo_codec_project_batch.argtypes = [vp, i32, vp, vp, vp, u32, u64, fp, pp, vp, u64, vp, u64, vp, vp]
+    L.cryo_codec_project_blocks.argtypes = [vp, i32, vp, vp, sz, sz, fp, pp, vp, sz, vp, sz, vp, vp]
+    L.cryo_multi_project_blocks.argtypes = [vp, i32, vp, vp, sz, sz, fp, pp, vp, sz, vp, sz, vp, vp]
     L.cryo_codec_lz4_index_cap.argtypes = [u32]
     L.cryo_codec_lz4_index_cap.restype = u32
     L.cryo_codec_lz4_index_rows.argtypes = [vp, vp, vp, vp, u32, u64, i32, vp, vp]
@@ -411,6 +427,48 @@ def group_blocks_call(fn, handle, chk, method, comps, block_size, desc, gdesc, a
     chk(fn(handle, method, src, szs, n, block_size, C.byref(desc[0]), C.byref(gdesc[0]), C.byref(adesc[0]) if adesc else None,
            rows.ctypes.data, recs.ctypes.data, cap, cells.ctypes.data if ncols else None, C.byref(total)), "group_blocks")
     return rows[:n], recs[:total.value], cells[:total.value, :ncols], total.value
+
+
+def project_desc(cols):
+    """the projection of a project call as a host array: cols a list of column numbers (1-based).  Returns (CryoProject, cols
+    array); the struct points into the array, which the caller keeps alive"""
+    a = np.zeros(max(len(cols), 1), PROJECT_COL)
+    for j, att in enumerate(cols):
+        a[j] = (att, 0, 0)
+    return CryoProject(len(cols), 0, a.ctypes.data), a
+
+
+def project_row_layout(atts, cols):
+    """the row layout rule of include/cryo_codec.h: atts a list of (attlen, attalign), cols a list of column numbers (1-based)
+    of width 1, 2, 4 or 8.  Returns (offsets, row_bytes): o_0 = 0, o_j = align(o_(j-1) + w_(j-1), w_j), row_bytes =
+    MAXALIGN(o_last + w_last)"""
+    offsets, end = [], 0
+    for att in cols:
+        w = atts[att - 1][0]
+        o = (end + w - 1) & ~(w - 1)
+        offsets.append(o)
+        end = o + w
+    return offsets, (end + 7) & ~7
+
+
+def project_blocks_call(fn, handle, chk, method, comps, block_size, desc, pdesc, row_bytes, rows=None, rec=None):
+    """cryo_codec_project_blocks / cryo_multi_project_blocks (fn) on a list of host streams with the descriptors filter_desc and
+    project_desc made; row_bytes: what project_row_layout says.  Returns (table: PROJECT_BLOCK array in call order, records: the
+    PROJECT_REC buffer, rows: a uint8 buffer of shape (row_cap, row_bytes), (total rows, total records)).  rows / rec: the
+    caller's buffers (their capacities are their lengths), else fresh ones of the worst-case size, 290 per block"""
+    n = len(comps)
+    arrs = [np.ascontiguousarray(np.asarray(c, dtype=np.uint8)) for c in comps]
+    src = (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.nbytes else None for a in arrs])
+    szs = (C.c_uint32 * max(n, 1))(*[a.nbytes for a in arrs])
+    if rows is None:
+        rows = np.zeros((max(n, 1) * 290, row_bytes), np.uint8)
+    if rec is None:
+        rec = np.zeros(max(n, 1) * 290, PROJECT_REC)
+    table = np.zeros(max(n, 1), PROJECT_BLOCK)
+    total = (C.c_uint64 * 2)()
+    chk(fn(handle, method, src, szs, n, block_size, C.byref(desc[0]), C.byref(pdesc[0]), rows.ctypes.data if rows.size else None,
+           rows.shape[0], rec.ctypes.data if rec.size else None, rec.size, table.ctypes.data, total), "project_blocks")
+    return table[:n], rec, rows, (total[0], total[1])
 
 
 def cell_sum(cell):
@@ -666,6 +724,27 @@ class Codec:
         per group and one column per aggregate column; cell_sum gives a cell's 128-bit sum"""
         return group_blocks_call(self.L.cryo_codec_group_blocks, self.h, self._chk, method, comps, block_size, desc, gdesc, adesc,
                                  group_cap)
+
+    def project_batch(self, method, d_src, d_off, d_sizes, block_size, n, natts, d_atts, nkeys, d_keys, ncols, d_cols, d_rows,
+                      row_cap, d_rec, rec_cap, d_blocks, d_total):
+        """test the keys on every tuple of the n stored blocks and copy the ncols fixed-width columns d_cols names (PROJECT_COL;
+        d_keys: FILTER_KEY, d_atts: FILTER_ATT, device arrays) of every match into a row: one PROJECT_BLOCK row per block in
+        d_blocks, one PROJECT_REC per match and per bad item in d_rec, one row of row_bytes per match in d_rows (at most row_cap
+        rows and rec_cap records are written), the two totals {rows, records} in d_total (2 x u64).  Asynchronous once the
+        descriptors are read back and the column table is in place."""
+        f = CryoFilter(natts, nkeys, 0, 0, d_atts.ptr if d_atts else None, d_keys.ptr if d_keys else None)
+        p = CryoProject(ncols, 0, d_cols.ptr if d_cols else None)
+        self._chk(self.L.cryo_codec_project_batch(self.h, method, d_src.ptr, d_off.ptr, d_sizes.ptr, block_size, n, C.byref(f),
+                                                  C.byref(p), d_rows.ptr if d_rows else None, row_cap,
+                                                  d_rec.ptr if d_rec else None, rec_cap, d_blocks.ptr if d_blocks else None,
+                                                  d_total.ptr if d_total else None), "project_batch")
+
+    def project_blocks(self, method, comps, block_size, desc, pdesc, row_bytes, rows=None, rec=None):
+        """project host streams (desc: what filter_desc returns, pdesc: project_desc, row_bytes: project_row_layout's); returns
+        (table, records, rows, (total rows, total records)): block i's records are records[table[i]["rec_first"]:][:n_match +
+        n_bad], the row of its k-th match is rows[table[i]["row_first"] + k]"""
+        return project_blocks_call(self.L.cryo_codec_project_blocks, self.h, self._chk, method, comps, block_size, desc, pdesc,
+                                   row_bytes, rows, rec)
 
     def last_verify_failure(self):
         """(block, first mismatch) that made the last host-buffer compress call fail verification, or None"""

@@ -1456,6 +1456,85 @@ static int group_pass(cryo_codec *c, int method, const uint8_t *d_src, const uin
     return decode_pass(c, method, B, n, ps);
 }
 
+/* ---- the projecting scan ----
+ * The shared decode loop over the caller's stream table; on every decoded chunk project.hip tests the keys on every tuple and
+ * writes a record per match and bad item and a row per match to a side area, places the blocks behind the two running totals --
+ * which stay in device memory (d_total) from chunk to chunk -- and copies records and rows to their places in the call's output.
+ * Per chunk (own) each block has 8 + row_bytes bytes per possible item of side area; the pass's fixed bytes hold the kernel's
+ * column table when the caller's columns come as a device array.  The pass waits once, for that table, and then for nothing.
+ * Its decodes count nowhere. */
+namespace {
+/* the kernel's column table (launch_project): {att, width, offset within the row, 0} per column, unused entries all zero */
+struct ProjectTab {
+    cryo_agg_col tab[CRYO_PROJECT_MAX_COLS] = {};
+    uint32_t ncols = 0, row_bytes = 0;
+};
+struct ProjectIo {
+    ScanDesc sd;
+    ProjectTab pt;
+    const void *d_tab = nullptr;            /* device: pt.tab in place already, or null: the pass uploads it */
+    cryo_project_block *d_blocks = nullptr; /* device: n rows of the block table */
+    void *d_rows = nullptr;                 /* device: row_cap rows */
+    cryo_project_rec *d_rec = nullptr;      /* device: rec_cap records */
+    uint64_t row_cap = 0, rec_cap = 0;
+    uint64_t *d_total = nullptr;            /* device: the two running totals */
+};
+} // namespace
+
+/* the projection's descriptor rules (include/cryo_codec.h); every array is host memory here.  *max_att: the highest key or
+ * projected column; *pt: the kernel's column table and the row's size */
+static bool project_desc_ok(const cryo_filter *f, const cryo_att *atts, const cryo_scan_key *keys, const cryo_project *prj,
+                            const cryo_project_col *cols, uint32_t *max_att, ProjectTab *pt)
+{
+    if (!filter_desc_ok(f, atts, keys, max_att)) return false;
+    if (f->flags != 0 || !prj || prj->ncols == 0 || prj->ncols > CRYO_PROJECT_MAX_COLS || prj->rsv != 0 || !cols) return false;
+    *pt = ProjectTab();
+    uint32_t end = 0;
+    for (uint32_t j = 0; j < prj->ncols; j++) {
+        const cryo_project_col &q = cols[j];
+        if (q.rsv != 0 || q.rsv2 != 0 || q.att == 0 || q.att > f->natts) return false;
+        const cryo_att &a = atts[q.att - 1];
+        if ((a.attlen != 1 && a.attlen != 2 && a.attlen != 4 && a.attlen != 8) || a.attalign < a.attlen) return false;
+        if (q.att > *max_att) *max_att = q.att;
+        const uint32_t at = CRYO_PROJECT_COL_OFFSET(end, a.attlen);
+        pt->tab[j].att = q.att;
+        pt->tab[j].type = (uint8_t)a.attlen;
+        pt->tab[j].rsv = (uint8_t)at;
+        end = at + (uint32_t)a.attlen;
+    }
+    pt->ncols = prj->ncols;
+    pt->row_bytes = CRYO_PROJECT_ROW_BYTES(end);
+    return true;
+}
+
+static int project_pass(cryo_codec *c, int method, const uint8_t *d_src, const uint64_t *d_src_off, const uint32_t *d_src_size,
+                        uint32_t B, uint64_t n, const ProjectIo &io)
+{
+    static_assert(sizeof(cryo_project_block) == 2 * sizeof(uint4) && sizeof(cryo_project_rec) == sizeof(uint2) &&
+                      sizeof(cryo_project_col) == sizeof(cryo_agg_col) && sizeof(cryo_project) == 16,
+                  "the projection's records are the kernels'");
+    const uint64_t S = cryo::filter_side_stride(B);
+    DecodePass ps(d_src, d_src_off, d_src_size, true);
+    ps.fixed = 256u;                                                           /* the column table */
+    ps.own_per_block = S * (sizeof(cryo_project_rec) + io.pt.row_bytes);       /* the side area */
+    ps.run = [&](const DecodeChunk &ch) -> int {
+        const void *tab = io.d_tab ? io.d_tab : ch.fixed;
+        if (ch.lo == 0) {
+            HIP_TRY(c, hipMemsetAsync(io.d_total, 0, 2 * sizeof(uint64_t), c->stream));
+            if (!io.d_tab) { /* io is the call's own: the table is in place before the call goes on */
+                HIP_TRY(c, hipMemcpyAsync(ch.fixed, io.pt.tab, sizeof io.pt.tab, hipMemcpyHostToDevice, c->stream));
+                HIP_TRY(c, hipStreamSynchronize(c->stream));
+            }
+        }
+        uint8_t *side_rec = ch.own, *side_rows = ch.own + ch.K * S * sizeof(cryo_project_rec);
+        HIP_TRY(c, cryo::launch_project(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.sd.d_atts, io.sd.d_keys, io.sd.nkeys, tab,
+                                        io.pt.ncols, io.pt.row_bytes, io.sd.max_att, io.sd.bytes_keys, (uint4 *)(io.d_blocks + ch.lo),
+                                        side_rec, side_rows, io.d_total, io.d_rec, io.rec_cap, io.d_rows, io.row_cap, c->lz4_opts.cus));
+        return CRYO_OK;
+    };
+    return decode_pass(c, method, B, n, ps);
+}
+
 /* ---- recompression ----
  * The shared decode loop over the caller's stream table; every decoded chunk is encoded by cryo_codec_compress_batch -- the
  * path of every compress call, so the handle's encode options (segment mode, checksums, verification) apply as they are --
@@ -1624,9 +1703,10 @@ int cryo_codec_fetch_batch(cryo_codec *c, int method, const void *d_src, const u
  * rules of the structs, which touch no device; the arrays read back and held against the call's *_desc_ok before anything else
  * is queued; the call's totals (total_words of them at d_total; none: 0) cleared; and -- unless the call has no block -- the key
  * table of a descriptor with a byte-string key (key_table_device: without such a key nothing more is queued).  *ncols: the
- * aggregate columns */
+ * aggregate columns.  prj: the call is a projection (grp and agg null); *pt: its column table */
 static int scan_desc_device(cryo_codec *c, const cryo_filter *f, const cryo_group *grp, const cryo_agg *agg, bool need_agg,
-                            uint64_t *d_total, size_t total_words, uint64_t n_blocks, ScanDesc &sd, uint32_t *ncols)
+                            uint64_t *d_total, size_t total_words, uint64_t n_blocks, ScanDesc &sd, uint32_t *ncols,
+                            const cryo_project *prj = nullptr, ProjectTab *pt = nullptr)
 {
     if (!f || f->natts == 0 || f->natts > CRYO_FILTER_MAX_ATTS || f->nkeys > CRYO_FILTER_MAX_KEYS || !f->atts ||
         (f->nkeys > 0 && !f->keys) || ((uintptr_t)f->atts & 3u) != 0 || ((uintptr_t)f->keys & 7u) != 0)
@@ -1635,17 +1715,21 @@ static int scan_desc_device(cryo_codec *c, const cryo_filter *f, const cryo_grou
     const uint32_t nc = agg ? agg->ncols : 0u;
     if ((need_agg && nc == 0) || nc > CRYO_AGG_MAX_COLS || (nc > 0 && (!agg->cols || ((uintptr_t)agg->cols & 7u) != 0)))
         return CRYO_E_ARG;
+    if (prj && (prj->ncols == 0 || prj->ncols > CRYO_PROJECT_MAX_COLS || !prj->cols || ((uintptr_t)prj->cols & 7u) != 0)) return CRYO_E_ARG;
     cryo_att atts[CRYO_FILTER_MAX_ATTS]; /* 6 400 bytes */
     cryo_scan_key keys[CRYO_FILTER_MAX_KEYS];
     cryo_agg_col by[CRYO_GROUP_MAX_BY], cols[CRYO_AGG_MAX_COLS];
+    cryo_project_col pcols[CRYO_PROJECT_MAX_COLS];
     HIP_TRY(c, hipMemcpyAsync(atts, f->atts, f->natts * sizeof(cryo_att), hipMemcpyDeviceToHost, c->stream));
     if (f->nkeys)
         HIP_TRY(c, hipMemcpyAsync(keys, f->keys, f->nkeys * sizeof(cryo_scan_key), hipMemcpyDeviceToHost, c->stream));
     if (grp) HIP_TRY(c, hipMemcpyAsync(by, grp->by, grp->nby * sizeof(cryo_agg_col), hipMemcpyDeviceToHost, c->stream));
     if (nc) HIP_TRY(c, hipMemcpyAsync(cols, agg->cols, nc * sizeof(cryo_agg_col), hipMemcpyDeviceToHost, c->stream));
+    if (prj) HIP_TRY(c, hipMemcpyAsync(pcols, prj->cols, prj->ncols * sizeof(cryo_project_col), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     *ncols = nc;
-    const bool ok = grp        ? group_desc_ok(f, atts, keys, grp, by, agg, cols, &sd.max_att, ncols)
+    const bool ok = prj        ? project_desc_ok(f, atts, keys, prj, pcols, &sd.max_att, pt)
+                    : grp      ? group_desc_ok(f, atts, keys, grp, by, agg, cols, &sd.max_att, ncols)
                     : need_agg ? agg_desc_ok(f, atts, keys, agg, cols, &sd.max_att)
                                : filter_desc_ok(f, atts, keys, &sd.max_att);
     if (!ok) return CRYO_E_ARG;
@@ -1718,6 +1802,27 @@ int cryo_codec_group_batch(cryo_codec *c, int method, const void *d_src, const u
         io.d_by = grp->by; io.d_cols = ncols ? agg->cols : nullptr; io.nby = grp->nby;
         io.d_blocks = d_blocks; io.d_groups = d_groups; io.d_cells = d_cells; io.group_cap = group_cap; io.d_total = d_total;
         return group_pass(c, method, (const uint8_t *)d_src, d_src_off, d_src_size, block_size, n_blocks, io);
+    });
+}
+
+int cryo_codec_project_batch(cryo_codec *c, int method, const void *d_src, const uint64_t *d_src_off, const uint32_t *d_src_size,
+                             uint32_t block_size, uint64_t n_blocks, const cryo_filter *f, const cryo_project *prj, void *d_rows,
+                             uint64_t row_cap, cryo_project_rec *d_rec, uint64_t rec_cap, cryo_project_block *d_blocks,
+                             uint64_t *d_total)
+{
+    DevGuard dev_(c);
+    if (!c || !method_ok(method) || !check_block_size_ok(block_size)) return CRYO_E_ARG;
+    if (!d_total || ((uintptr_t)d_total & 7u) != 0 || !prj) return CRYO_E_ARG;
+    if ((((uintptr_t)d_rows | (uintptr_t)d_rec) & 7u) != 0 || ((uintptr_t)d_blocks & 15u) != 0) return CRYO_E_ARG;
+    if (n_blocks > 0 && (!d_src || !d_src_off || !d_src_size || !d_blocks || (!d_rows && row_cap > 0) || (!d_rec && rec_cap > 0)))
+        return CRYO_E_ARG;
+    return guarded([&] {
+        ProjectIo io;
+        uint32_t ncols = 0;
+        const int rc = scan_desc_device(c, f, nullptr, nullptr, false, d_total, 2, n_blocks, io.sd, &ncols, prj, &io.pt);
+        if (rc != CRYO_OK || n_blocks == 0) return rc;
+        io.d_blocks = d_blocks; io.d_rows = d_rows; io.row_cap = row_cap; io.d_rec = d_rec; io.rec_cap = rec_cap; io.d_total = d_total;
+        return project_pass(c, method, (const uint8_t *)d_src, d_src_off, d_src_size, block_size, n_blocks, io);
     });
 }
 
@@ -2573,6 +2678,93 @@ int cryo_codec_group_blocks(cryo_codec *c, int method, const void *const *h_src,
     });
 }
 
+/* what every host-buffer project call checks before a device is touched */
+static int project_blocks_args(int method, size_t block_size, const cryo_filter *f, const cryo_project *prj, uint64_t *h_total,
+                               uint32_t *max_att, ProjectTab *pt)
+{
+    if (!method_ok(method) || !check_block_size_ok(block_size) || !h_total) return CRYO_E_ARG;
+    if (!f || !prj || !project_desc_ok(f, f->atts, f->keys, prj, prj->cols, max_att, pt)) return CRYO_E_ARG;
+    return CRYO_OK;
+}
+
+/* the projecting scan of n streams given by pointer: the streams staged and uploaded as the aggregate's (stage_streams), the
+ * descriptors -- the columns as the kernel's table -- from the same pinned buffer in a second copy, both into place before the
+ * first decode; the block table of the whole call comes back after the last chunk (project_pass waits for nothing here), then --
+ * their numbers known from the last row -- its records and rows.  w_base / r_base: what row_first / rec_first count from (a
+ * multi-GPU share's regions within the caller's buffers); h_total is relative to h_rows / h_rec as given here */
+static int project_blocks_impl(cryo_codec *c, int method, const void *const *h_src, const uint32_t *h_src_size, size_t n,
+                               size_t block_size, const cryo_filter *f, const cryo_project *prj, void *h_rows, size_t row_cap,
+                               uint64_t w_base, cryo_project_rec *h_rec, size_t rec_cap, uint64_t r_base,
+                               cryo_project_block *h_blocks, uint64_t *h_total)
+{
+    uint32_t max_att = 0;
+    ProjectIo io;
+    int rc = project_blocks_args(method, block_size, f, prj, h_total, &max_att, &io.pt);
+    if (rc != CRYO_OK || !c) return CRYO_E_ARG;
+    DevGuard dev_(c);
+    h_total[0] = h_total[1] = 0;
+    if (n == 0) return CRYO_OK;
+    if (!h_src || !h_src_size || !h_blocks || (!h_rows && row_cap > 0) || (!h_rec && rec_cap > 0)) return CRYO_E_ARG;
+    ScopedLocalCpus numa_(n * block_size >= ((size_t)8 << 20) ? c : nullptr);
+    /* the descriptor with the column table [8 x ncols] as its extra bytes, then the results: [totals 16][table 32 x n]
+     * [records 8 x cap_r][rows row_bytes x cap_w], each part 8-byte aligned, the table 16; the caps: what the caller has room for, at
+     * most the worst case */
+    const size_t worst = n * (size_t)cryo::filter_side_stride((uint32_t)block_size), rb = io.pt.row_bytes;
+    const size_t cap_w = row_cap < worst ? row_cap : worst, cap_r = rec_cap < worst ? rec_cap : worst;
+    const ScanDescLayout L = scan_desc_layout(f, ((size_t)io.pt.ncols * 8 + 15) & ~(size_t)15);
+    const size_t t_total = L.bytes, t_table = t_total + 16, table_bytes = n * sizeof(cryo_project_block);
+    const size_t t_recs = t_table + table_bytes, t_rows = t_recs + cap_r * sizeof(cryo_project_rec);
+    if ((rc = ensure(c, &c->hb_meta, &c->hb_meta_cap, t_rows + cap_w * rb + 64)) != CRYO_OK) return rc;
+    StagedStreams sg;
+    if ((rc = scan_desc_upload(c, h_src, h_src_size, n, f, max_att, L, io.pt.tab, sg, io.sd)) != CRYO_OK) return rc;
+    io.d_tab = c->hb_meta + L.t_extra;
+    io.d_total = (uint64_t *)(c->hb_meta + t_total);
+    io.d_blocks = (cryo_project_block *)(c->hb_meta + t_table);
+    io.d_rec = (cryo_project_rec *)(c->hb_meta + t_recs);
+    io.d_rows = c->hb_meta + t_rows;
+    io.rec_cap = cap_r; io.row_cap = cap_w;
+    rc = project_pass(c, method, c->hb_src, (const uint64_t *)(c->hb_src + sg.o_off), (const uint32_t *)(c->hb_src + sg.o_sz),
+                      (uint32_t)block_size, n, io);
+    if (rc == CRYO_OK) {
+        const hipError_t e = hipMemcpyAsync(h_blocks, io.d_blocks, table_bytes, hipMemcpyDeviceToHost, c->stream);
+        if (e != hipSuccess) rc = fail(c, e, "hipMemcpyAsync of the block table");
+        else c->xfer_ctr.d2h_bytes += table_bytes;
+    }
+    /* nothing in flight from the pinned buffer or into the caller's memory afterwards */
+    hipError_t es = hipStreamSynchronize(c->stream);
+    if (rc == CRYO_OK && es != hipSuccess) rc = fail(c, es, "hipStreamSynchronize");
+    if (rc != CRYO_OK) return rc;
+    const cryo_project_block &last = h_blocks[n - 1];
+    const uint64_t last_recs = (uint64_t)last.n_match + last.n_bad;
+    if (last.row_first > worst || last.n_match > worst - last.row_first || last.rec_first > worst || last_recs > worst - last.rec_first)
+        return CRYO_E_HIP; /* not a placement */
+    const uint64_t rows = last.row_first + last.n_match, recs = last.rec_first + last_recs;
+    h_total[0] = rows;
+    h_total[1] = recs;
+    if (rows > row_cap || recs > rec_cap) return CRYO_E_DSTSIZE;
+    if (recs) {
+        hipError_t e = hipMemcpyAsync(h_rec, io.d_rec, recs * sizeof(cryo_project_rec), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && rows) e = hipMemcpyAsync(h_rows, io.d_rows, rows * rb, hipMemcpyDeviceToHost, c->stream);
+        if (e != hipSuccess) rc = fail(c, e, "hipMemcpyAsync of records and rows");
+        else c->xfer_ctr.d2h_bytes += recs * sizeof(cryo_project_rec) + rows * rb;
+        es = hipStreamSynchronize(c->stream);
+        if (rc == CRYO_OK && es != hipSuccess) rc = fail(c, es, "hipStreamSynchronize");
+    }
+    if (rc == CRYO_OK && (w_base || r_base))
+        for (size_t i = 0; i < n; i++) { h_blocks[i].row_first += w_base; h_blocks[i].rec_first += r_base; }
+    return rc;
+}
+
+int cryo_codec_project_blocks(cryo_codec *c, int method, const void *const *h_src, const uint32_t *h_src_size, size_t n,
+                              size_t block_size, const cryo_filter *f, const cryo_project *prj, void *h_rows, size_t row_cap,
+                              cryo_project_rec *h_rec, size_t rec_cap, cryo_project_block *h_blocks, uint64_t *h_total)
+{
+    return host_call(c, [&] {
+        return project_blocks_impl(c, method, h_src, h_src_size, n, block_size, f, prj, h_rows, row_cap, 0, h_rec, rec_cap, 0, h_blocks,
+                                   h_total);
+    });
+}
+
 } /* extern "C" */
 
 /* ---- device-resident block pool ---- */
@@ -3213,6 +3405,50 @@ int cryo_multi_group_blocks(cryo_multi *m, int method, const void *const *h_src,
         row.first_group = at;
         at += row.n_groups;
         h_blocks[i] = row;
+    }
+    return CRYO_OK;
+}
+
+/* block i -> handle i mod G; handle g projects its share, in block order, into a row region and a record region of 290
+ * (kHeapMaxItems) * (its blocks) entries each, whatever the block size, the regions in handle order; the table comes back in call
+ * order with row_first and rec_first counting from h_rows and h_rec */
+int cryo_multi_project_blocks(cryo_multi *m, int method, const void *const *h_src, const uint32_t *h_src_size, size_t n,
+                              size_t block_size, const cryo_filter *f, const cryo_project *prj, void *h_rows, size_t row_cap,
+                              cryo_project_rec *h_rec, size_t rec_cap, cryo_project_block *h_blocks, uint64_t *h_total)
+{
+    uint32_t max_att = 0;
+    ProjectTab pt;
+    if (!m || m->h.empty() || project_blocks_args(method, block_size, f, prj, h_total, &max_att, &pt) != CRYO_OK) return CRYO_E_ARG;
+    const size_t G = m->h.size();
+    if (G == 1)
+        return cryo_codec_project_blocks(m->h[0], method, h_src, h_src_size, n, block_size, f, prj, h_rows, row_cap, h_rec, rec_cap,
+                                         h_blocks, h_total);
+    h_total[0] = h_total[1] = 0;
+    if (n == 0) return CRYO_OK;
+    if (!h_src || !h_src_size || !h_blocks || (!h_rows && row_cap > 0) || (!h_rec && rec_cap > 0)) return CRYO_E_ARG;
+    std::vector<uint64_t> end_w(G, 0), end_r(G, 0);
+    const int rc = guarded([&] {
+        return multi_run(m, n, [&](size_t g, const std::vector<size_t> &idx) {
+            const uint64_t first = blocks_before(n, G, g) * cryo::kHeapMaxItems, want = (uint64_t)idx.size() * cryo::kHeapMaxItems;
+            const uint64_t cap_w = row_cap > first ? (row_cap - first < want ? row_cap - first : want) : 0;
+            const uint64_t cap_r = rec_cap > first ? (rec_cap - first < want ? rec_cap - first : want) : 0;
+            const ShareStreams in(h_src, h_src_size, idx);
+            std::vector<cryo_project_block> rows(idx.size());
+            uint64_t tot[2] = {0, 0};
+            const int r = project_blocks_impl(m->h[g], method, in.src.data(), in.sz.data(), idx.size(), block_size, f, prj,
+                                              cap_w ? (uint8_t *)h_rows + first * pt.row_bytes : nullptr, cap_w, first,
+                                              cap_r ? h_rec + first : nullptr, cap_r, first, rows.data(), tot);
+            if (r != CRYO_OK) return r;
+            for (size_t k = 0; k < idx.size(); k++) h_blocks[idx[k]] = rows[k];
+            end_w[g] = tot[0] ? first + tot[0] : 0;
+            end_r[g] = tot[1] ? first + tot[1] : 0;
+            return (int)CRYO_OK;
+        });
+    });
+    if (rc != CRYO_OK) return rc;
+    for (size_t g = 0; g < G; g++) {
+        if (end_w[g] > h_total[0]) h_total[0] = end_w[g];
+        if (end_r[g] > h_total[1]) h_total[1] = end_r[g];
     }
     return CRYO_OK;
 }

@@ -1,6 +1,6 @@
 /*
- * filter_walk.h -- the walk over one heap tuple that the scan filter (filter.hip), the scan aggregate (agg.hip) and the grouped
- * scan (group.hip) share: the TUPLE rule, the column walk and the key tests of include/cryo_codec.h ("filtering a scan"), and --
+ * filter_walk.h -- the walk over one heap tuple that the scan filter (filter.hip), the scan aggregate (agg.hip), the grouped
+ * scan (group.hip) and the projection (project.hip, eight capture slots) share: the TUPLE rule, the column walk and the key tests of include/cryo_codec.h ("filtering a scan"), and --
  * for the aggregate and the grouping -- the capture of column values as the walk passes them ("aggregating a scan", "grouping a
  * scan").  One statement of the walk: the filter instantiates it without capture, and the capture costs it nothing (the same
  * registers, no scratch).  The number of capture slots is a template parameter: four for the aggregate, six for the grouping (two
@@ -54,6 +54,14 @@ __device__ inline int64_t walk_value(const uint8_t *__restrict__ p, int32_t attl
     return *reinterpret_cast<const int64_t *>(p);
 }
 
+/* the same with attlen 1 as well: the projection's load (project.hip), whose columns may be one byte wide.  A load of its own:
+ * a fourth width in walk_value costs the aggregate's and the grouping's kernels two scalar registers each */
+__device__ inline int64_t walk_value_narrow(const uint8_t *__restrict__ p, int32_t attlen)
+{
+    if (attlen == 1) return *reinterpret_cast<const int8_t *>(p);
+    return walk_value(p, attlen);
+}
+
 /* A number with the sign of (payload, constant) in the order of the byte-string keys: memcmp over the shorter length on unsigned bytes, then the
  * lengths.  p: the plen payload bytes, anywhere; kc: the constant's n bytes, 8-byte aligned and zero-padded to a multiple of 8 (the
  * host's copy), read a word per trip at addresses that depend on the trip alone -- a uniform load -- and the trip count is n's.
@@ -86,8 +94,9 @@ __device__ inline int32_t walk_bytes_sign(const uint8_t *__restrict__ p, uint32_
  * also notes the value of each of the ncols <= SLOTS columns cols[] names (their att <= max_att, attlen the type's size and
  * attalign at least that: the aggregate's argument rule; an att of 0 names no column) in *cap; cols is read at addresses that
  * depend on the loop counters only.  BYTES: a key of type kKeyBytes compares the column's in-line payload with the rsv bytes at
- * value (walk_bytes_sign); without BYTES no key has that type. */
-template <bool CAPTURE, uint32_t SLOTS = kAggMaxCols, bool BYTES = false>
+ * value (walk_bytes_sign); without BYTES no key has that type.  NARROW: a captured column may have attlen 1 (the projection's
+ * argument rule: attlen 1, 2, 4 or 8 and attalign at least that). */
+template <bool CAPTURE, uint32_t SLOTS = kAggMaxCols, bool BYTES = false, bool NARROW = false>
 __device__ inline uint32_t walk_tuple(const uint8_t *__restrict__ t, uint32_t len, bool live, const FilterAtt *__restrict__ atts,
                                       const FilterKey *__restrict__ keys, uint32_t nkeys, uint32_t max_att,
                                       const AggCol *__restrict__ cols, uint32_t ncols,
@@ -170,7 +179,7 @@ __device__ inline uint32_t walk_tuple(const uint8_t *__restrict__ t, uint32_t le
             for (uint32_t j = 0; j < SLOTS; j++) { /* unrolled: v[j] stays in registers */
                 if (j >= ncols || cols[j].att != col) continue; /* uniform */
                 /* as for a key: the column's [pos, pos + attlen) lies below len, aligned by the aggregate's argument rule */
-                cap->v[j] = val ? walk_value(t + pos, a.attlen) : 0;
+                cap->v[j] = !val ? 0 : NARROW ? walk_value_narrow(t + pos, a.attlen) : walk_value(t + pos, a.attlen);
                 if (val) cap->has |= 1u << j;
             }
         }

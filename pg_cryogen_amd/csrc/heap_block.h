@@ -1,5 +1,5 @@
 /*
- * heap_block.h -- the decoded heap block as the scan kernels see it (check.hip, fetch.hip, filter.hip, agg.hip, group.hip): the
+ * heap_block.h -- the decoded heap block as the scan kernels see it (check.hip, fetch.hip, filter.hip, agg.hip, group.hip, project.hip): the
  * rules of the stored-block format (cryo_init_page / cryo_storage_insert, host/storage.c; include/cryo_codec.h: HEADER, ITEM)
  * and the small pieces the kernels that place and copy tuples share.  One copy of each, so that a rule is fixed in one place:
  *   kHeapMaxItems        the items a block can hold
@@ -10,7 +10,7 @@
  *   find_last_le         the last index of an ascending uint64_t array with v[i] <= x (the block of a packed byte)
  *   mask_tuple_tail      zeroes the pad in the 8-byte word that holds a tuple's last byte
  * Everything is plain C++; the functions take their inputs by value, so a wave-uniform header stays in scalar registers in
- * the kernels that derive the block from readfirstlane (k_filter_match, k_agg_block, k_group_block).
+ * the kernels that derive the block from readfirstlane (k_filter_match, k_agg_block, k_group_block, k_project_block).
  */
 #ifndef CRYO_HEAP_BLOCK_H
 #define CRYO_HEAP_BLOCK_H

@@ -286,6 +286,22 @@ hipError_t launch_group(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride
                         void *d_side_cell,
                         uint64_t *d_running, void *d_rec, void *d_cells, uint64_t group_cap, int cus);
 
+/* the projecting scan (project.hip) on one decoded chunk of cnt blocks (laid out as for launch_filter): k_project_block,
+ * k_project_offsets, k_project_copy.  The descriptors are validated by the caller (cryo_codec.cpp, project_desc_ok): d_atts and
+ * d_keys as for launch_filter; d_cols the staged column table, ncols (1 .. 8) entries of 8 bytes (device memory, 8-byte aligned):
+ * {u16 att, u8 width (the column's attlen: 1, 2, 4, 8), u8 offset within the row (a multiple of the width, below row_bytes), u32
+ * 0} -- the walk reads it as cryo_agg_col and looks at att alone; row_bytes the row's size, 8 .. 64 and a multiple of 8 (both from
+ * CRYO_PROJECT_COL_OFFSET / CRYO_PROJECT_ROW_BYTES); max_att the highest key or projected column; bytes_keys as for launch_filter (k_project_block<true> /
+ * <false>; an undecided tuple gets a record {pos, 9, 0}, counts in n_bad and has no row).  d_blocks: the chunk's rows of the
+ * block table (cryo_project_block, 16-byte aligned).  Scratch: d_side_rec 8 bytes and d_side_rows row_bytes bytes per possible
+ * item (cnt * filter_side_stride(block_size) items; both 8-byte aligned).  d_running: the two totals {rows, records} before the
+ * chunk in, after it out.  The chunk's records go to d_rec and its rows to d_rows (8-byte aligned) at rec_first / row_first within
+ * the call; no record at or beyond rec_cap and no row at or beyond row_cap is written.  cus as for launch_fetch. */
+hipError_t launch_project(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
+                          const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_cols,
+                          uint32_t ncols, uint32_t row_bytes, uint32_t max_att, bool bytes_keys, uint4 *d_blocks, void *d_side_rec,
+                          void *d_side_rows, uint64_t *d_running, void *d_rec, uint64_t rec_cap, void *d_rows, uint64_t row_cap, int cus);
+
 } // namespace cryo
 
 #define CRYO_WAVE 64

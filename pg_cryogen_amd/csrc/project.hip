@@ -1,0 +1,201 @@
+/*
+ * project.hip -- the device side of the projecting scan (cryo_codec_project_batch / _blocks, include/cryo_codec.h: the rules).
+ *
+ * The host (cryo_codec.cpp, project_pass) decodes a chunk of stored streams into handle workspace with the shared decode loop
+ * (decode_pass); these kernels look into every heap tuple of the decoded chunk as the scan aggregate does, and of every tuple that
+ * passes the keys only the named fixed-width columns leave the device, as one row of 8 .. 64 bytes, with an 8-byte record:
+ *   k_project_block    one wave per block, four blocks per workgroup, as k_filter_match and k_agg_block.  A block the decoders
+ *                      rejected gets STREAM without a load, a bad header (heap_header, heap_block.h) HEADER.  Otherwise a lane
+ *                      takes one item per turn (290 items: five turns): the ITEM rule (heap_item), then the walk of filter_walk.h
+ *                      over the columns 1 .. max(highest key column, highest projected column) with eight capture slots.  The
+ *                      wave ballots the matches and the bad items of the turn; a lane's rank among both is its record's place, its
+ *                      rank among the matches its row's.  A matching lane assembles its row in registers -- the column table
+ *                      (width and offset per column, the host's) is wave-uniform, so the word a column lands
+ *                      in is a scalar compare, and NULL columns and pads are the zeros the words start with -- and writes it as
+ *                      whole 8-byte words, with its record, to the block's share of a side area in handle workspace.  There is
+ *                      no OVERLAP verdict: a block places at most 290 rows whatever it holds, so nothing about the block has to
+ *                      be known before its first row is written and ONE sweep suffices (the filter needs two).  Descriptor, keys
+ *                      and column table are read at addresses that depend on loop counters only (uniform loads); no load leaves
+ *                      [t, t + len).  A descriptor with a byte-string key runs k_project_block<true>, whose walk compares those
+ *                      too and gives an undecided tuple a record and no row; every other descriptor runs k_project_block<false>.
+ *   k_project_offsets  one workgroup per chunk: the tiled scan of heap_block.h (offsets_tile<2>) over rows and records at once,
+ *                      from the two running totals the chunk before left in device memory; it writes rec_first and row_first.
+ *   k_project_copy     a grid stride over the blocks: block k's rows and records from the side area to row_first / rec_first of
+ *                      the call's output, 8 bytes per access (row_bytes is a multiple of 8), cut off at row_cap and rec_cap.
+ * Every device write is a vector store in plain C++.  No LDS beyond the scan's eight words, no scratch, no global atomics.
+ */
+#include "kernels.h"
+#include "filter_walk.h"
+
+namespace cryo {
+
+constexpr uint32_t kProjectMaxCols = 8u; /* CRYO_PROJECT_MAX_COLS */
+
+/* The staged column table: entry j is an AggCol to the walk (which reads att alone) and carries in `type` the column's width
+ * w_j (1, 2, 4, 8) and in `rsv` its offset o_j within the row (0 .. 56, a multiple of w_j): launch_project's rule */
+
+template <bool BYTES>
+__global__ void __launch_bounds__(256)
+k_project_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, uint32_t cnt, const int32_t *__restrict__ dec_status,
+                const FilterAtt *__restrict__ atts, const FilterKey *__restrict__ keys, uint32_t nkeys,
+                const AggCol *__restrict__ cols, uint32_t ncols, uint32_t max_att, uint32_t row_words, uint32_t side_stride,
+                uint4 *__restrict__ blocks, uint2 *__restrict__ side_rec, uint2 *__restrict__ side_rows)
+{
+    /* the wave's number through readfirstlane, as in k_filter_match: the block, its header and the trip counts are the same in
+     * all 64 lanes and stay, with the descriptor reads, in scalar registers */
+    const uint32_t k = blockIdx.x * 4u + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t lane = threadIdx.x & 63u;
+    if (k >= cnt) return;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const uint32_t col_mask = (1u << ncols) - 1u; /* ncols <= 8 */
+    uint32_t status = 0, n_items = 0, n_match = 0, n_bad = 0;
+    if (dec_status[k] != 0) status = kFilterStream; /* the decoders rejected the stream: nothing decoded to look at */
+    else {
+        const uint8_t *p = dec + (uint64_t)k * dec_stride;
+        const uint2 hdr = *reinterpret_cast<const uint2 *>(p);
+        uint32_t n, upper;
+        if (!heap_header(hdr, B, n, upper))
+            status = kFilterHeader;
+        else {
+            n_items = n; /* lower <= B: n <= side_stride */
+            uint2 *out_rec = side_rec + (uint64_t)k * side_stride;
+            uint2 *out_rows = side_rows + (uint64_t)k * side_stride * row_words;
+            for (uint32_t t0 = 0; t0 < n; t0 += 64u) {
+                const uint32_t i = t0 + lane;
+                const bool valid = i < n;
+                uint32_t verdict = kFilterNoMatch, len = 0, src = 0;
+                if (valid) {
+                    const uint2 it = *reinterpret_cast<const uint2 *>(p + 8u + 8u * i); /* 8 + 8 n = lower <= B */
+                    if (!heap_item(it, upper, B, src, len)) verdict = kFilterItem;
+                }
+                const bool live = valid && verdict != kFilterItem;
+                WalkCaptureN<kProjectMaxCols> cap;
+                cap.has = 0;
+#pragma unroll
+                for (uint32_t j = 0; j < kProjectMaxCols; j++) cap.v[j] = 0;
+                const uint32_t walked = walk_tuple<true, kProjectMaxCols, BYTES, true>(p + src, len, live, atts, keys, nkeys, max_att, cols,
+                                                                                      ncols, &cap, WalkKeys<BYTES>());
+                if (live) verdict = walked;
+                const bool match = verdict == 0u,
+                           bad = verdict == kFilterItem || verdict == kFilterTuple || (BYTES && verdict == kFilterUndecided);
+                const unsigned long long mm = __ballot(match), mb = __ballot(bad);
+                if (match || bad) { /* records in position order: the rank among the matches and the bad items */
+                    const uint32_t r = n_match + n_bad + (uint32_t)__popcll((mm | mb) & below); /* below n <= side_stride */
+                    out_rec[r] = make_uint2((i + 1u) | (match ? 0u : verdict << 16), match ? ~cap.has & col_mask : 0u);
+                }
+                if (match) {
+                    /* the row in registers: a captured value is sign-extended and 0 when NULL, so its low w_j bytes are the
+                     * column's and shifting them to o_j touches no other column (o_j is a multiple of w_j: no word is crossed) */
+                    uint64_t word[kProjectMaxCols];
+#pragma unroll
+                    for (uint32_t q = 0; q < kProjectMaxCols; q++) word[q] = 0;
+#pragma unroll
+                    for (uint32_t j = 0; j < kProjectMaxCols; j++) {
+                        if (j >= ncols) continue; /* uniform */
+                        const AggCol c = cols[j];  /* uniform */
+                        const uint32_t w = c.type, o = c.rsv;
+                        const uint64_t bits = w >= 8u ? (uint64_t)cap.v[j] : (uint64_t)cap.v[j] & ((1ull << (8u * w)) - 1ull);
+                        const uint64_t placed = bits << (8u * (o & 7u));
+#pragma unroll
+                        for (uint32_t q = 0; q < kProjectMaxCols; q++)
+                            if ((o >> 3) == q) word[q] |= placed; /* uniform: the register is picked by a scalar compare */
+                    }
+                    const uint32_t r = n_match + (uint32_t)__popcll(mm & below); /* below n <= side_stride */
+                    uint2 *row = out_rows + (uint64_t)r * row_words;
+#pragma unroll
+                    for (uint32_t q = 0; q < kProjectMaxCols; q++)
+                        if (q < row_words) row[q] = make_uint2((uint32_t)word[q], (uint32_t)(word[q] >> 32));
+                }
+                n_match += (uint32_t)__popcll(mm);
+                n_bad += (uint32_t)__popcll(mb);
+            }
+        }
+    }
+    if (lane == 0) {
+        blocks[2u * k] = make_uint4(status, n_items, n_match, n_bad);
+        blocks[2u * k + 1u] = make_uint4(0u, 0u, 0u, 0u); /* rec_first, row_first: k_project_offsets */
+    }
+}
+
+/* rec_first and row_first of every row of the chunk: the records and the rows before block k, counted from the call's start;
+ * running[0], running[1]: the rows and the records before the chunk in, after it out */
+__global__ void __launch_bounds__(256)
+k_project_offsets(uint32_t cnt, uint64_t *__restrict__ running, uint4 *__restrict__ blocks)
+{
+    __shared__ uint64_t wave_sum[8];
+    uint64_t run_rows = running[0], run_recs = running[1]; /* the same in every thread; written again only after the tiles' barriers */
+    for (uint32_t t = 0; t < cnt; t += 256u) {
+        const uint32_t k = t + threadIdx.x;
+        uint4 b = make_uint4(0u, 0u, 0u, 0u);
+        if (k < cnt) b = blocks[2u * k];
+        const uint64_t a[2] = {b.z, (uint64_t)b.z + b.w}; /* rows, records */
+        uint64_t before[2], tile[2];
+        offsets_tile(a, wave_sum, before, tile);
+        if (k < cnt) {
+            const uint64_t row_first = run_rows + before[0], rec_first = run_recs + before[1];
+            blocks[2u * k + 1u] = make_uint4((uint32_t)rec_first, (uint32_t)(rec_first >> 32), (uint32_t)row_first, (uint32_t)(row_first >> 32));
+        }
+        run_rows += tile[0];
+        run_recs += tile[1];
+    }
+    if (threadIdx.x == 0) {
+        running[0] = run_rows;
+        running[1] = run_recs;
+    }
+}
+
+/* rows (row_words words each) and records (one word each) of the chunk's blocks from the side area to their places within the
+ * call */
+__global__ void __launch_bounds__(256)
+k_project_copy(uint32_t cnt, uint32_t side_stride, uint32_t row_words, const uint4 *__restrict__ blocks,
+               const uint2 *__restrict__ side_rec, const uint2 *__restrict__ side_rows, uint2 *__restrict__ rec, uint64_t rec_cap,
+               uint2 *__restrict__ rows, uint64_t row_cap)
+{
+    for (uint32_t k = blockIdx.x; k < cnt; k += gridDim.x) {
+        const uint4 head = blocks[2u * k], place = blocks[2u * k + 1u];
+        const uint64_t rec_first = (uint64_t)place.x | (uint64_t)place.y << 32, row_first = (uint64_t)place.z | (uint64_t)place.w << 32;
+        uint32_t nrow = head.z < side_stride ? head.z : side_stride;
+        uint32_t nrec = head.z + head.w < side_stride ? head.z + head.w : side_stride; /* n_match + n_bad <= n_items <= side_stride */
+        /* nothing at or beyond the caps */
+        if (rec_first >= rec_cap) nrec = 0;
+        else if (rec_cap - rec_first < nrec) nrec = (uint32_t)(rec_cap - rec_first);
+        if (row_first >= row_cap) nrow = 0;
+        else if (row_cap - row_first < nrow) nrow = (uint32_t)(row_cap - row_first);
+        const uint2 *sr = side_rec + (uint64_t)k * side_stride;
+        for (uint32_t w = threadIdx.x; w < nrec; w += 256u) rec[rec_first + w] = sr[w];
+        const uint2 *sw = side_rows + (uint64_t)k * side_stride * row_words;
+        for (uint32_t w = threadIdx.x; w < nrow * row_words; w += 256u) rows[row_first * row_words + w] = sw[w];
+    }
+}
+
+hipError_t launch_project(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
+                          const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_cols,
+                          uint32_t ncols, uint32_t row_bytes, uint32_t max_att, bool bytes_keys, uint4 *d_blocks, void *d_side_rec,
+                          void *d_side_rows, uint64_t *d_running, void *d_rec, uint64_t rec_cap, void *d_rows, uint64_t row_cap, int cus)
+{
+    if (cnt == 0) return hipSuccess;
+    if ((dec_stride & 15u) != 0 || (((uintptr_t)d_dec | (uintptr_t)d_blocks) & 15u) != 0 ||
+        (((uintptr_t)d_rec | (uintptr_t)d_rows | (uintptr_t)d_keys | (uintptr_t)d_cols | (uintptr_t)d_side_rec | (uintptr_t)d_side_rows |
+          (uintptr_t)d_running) & 7u) != 0 ||
+        ((uintptr_t)d_atts & 3u) != 0 || block_size < 16u || nkeys > 4u || ncols == 0u || ncols > kProjectMaxCols || row_bytes < 8u ||
+        row_bytes > 8u * kProjectMaxCols || (row_bytes & 7u) != 0 || !d_cols || !d_side_rec || !d_side_rows || !d_running ||
+        (rec_cap > 0u && !d_rec) || (row_cap > 0u && !d_rows))
+        return hipErrorInvalidValue;
+    const uint32_t stride = filter_side_stride(block_size), row_words = row_bytes / 8u;
+    hipLaunchKernelGGL(bytes_keys ? k_project_block<true> : k_project_block<false>, dim3((cnt + 3u) / 4u), dim3(256), 0, s, d_dec,
+                       dec_stride, block_size, cnt, d_dec_status, (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys,
+                       (const AggCol *)d_cols, ncols, max_att, row_words, stride, d_blocks, (uint2 *)d_side_rec, (uint2 *)d_side_rows);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_project_offsets, dim3(1), dim3(256), 0, s, cnt, d_running, d_blocks);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    /* four workgroups per compute unit, but never more than the chunk has blocks */
+    uint64_t grid = (uint64_t)(cus > 0 ? cus : 256) * 4u;
+    if (grid > cnt) grid = cnt;
+    hipLaunchKernelGGL(k_project_copy, dim3((uint32_t)grid), dim3(256), 0, s, cnt, stride, row_words, (const uint4 *)d_blocks,
+                       (const uint2 *)d_side_rec, (const uint2 *)d_side_rows, (uint2 *)d_rec, rec_cap, (uint2 *)d_rows, row_cap);
+    return hipGetLastError();
+}
+
+} // namespace cryo

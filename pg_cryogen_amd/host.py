@@ -39,6 +39,9 @@ AGG_BLOCKS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p),
 GROUP_BLOCKS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_size_t,
                               C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                               C.POINTER(C.c_uint64))
+PROJECT_BLOCKS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_size_t,
+                                C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                C.POINTER(C.c_uint64))
 CRYO_CHECK_CHAIN, CRYO_CHECK_METHOD = 16, 17   # host-only reasons of check.h (beside cryo_check_reason 0..4)
 
 
@@ -86,6 +89,12 @@ class CryoCodecGroupOps(C.Structure):
     """host/compression.h's one-function table of the grouped scan (GROUP_BLOCKS_FN), bound beside a CryoCodecOps double with
     cryo_host_set_group_ops (test build)"""
     _fields_ = [("group_blocks", GROUP_BLOCKS_FN)]
+
+
+class CryoCodecProjectOps(C.Structure):
+    """host/compression.h's one-function table of the projecting scan (PROJECT_BLOCKS_FN), bound beside a CryoCodecOps double
+    with cryo_host_set_project_ops (test build)"""
+    _fields_ = [("project_blocks", PROJECT_BLOCKS_FN)]
 
 
 class CryoRel(C.Structure):
@@ -160,6 +169,17 @@ class CryoGroupTotals(C.Structure):
                                           "bytes_back", "groups")]
 
 
+class CryoProjectedRow(C.Structure):
+    _fields_ = [("block", C.c_uint32), ("pos", C.c_uint16), ("created_xid", C.c_uint32), ("nulls", C.c_uint32),
+                ("data", C.c_void_p), ("row_bytes", C.c_uint32)]
+
+
+class CryoProjectTotals(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("blocks", "empty_pages", "items", "matches", "bad", "reports", "codec_calls",
+                                          "bytes_back")]
+
+
+PROJECT_ROW_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(CryoProjectedRow))
 AGG_BLOCK_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(CryoAggBlock))
 GROUP_BLOCK_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(CryoGroupBlock))
 FETCH_TUPLE_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(CryoFetchedTuple))
@@ -218,6 +238,11 @@ def lib():
         L.cryo_host_set_group_ops.restype = None
         L.cryo_group_set_window.argtypes = [i32, sz]
         L.cryo_group_set_window.restype = None
+    if hasattr(L, "cryo_host_set_project_ops"):  # test build only
+        L.cryo_host_set_project_ops.argtypes = [C.POINTER(CryoCodecProjectOps)]
+        L.cryo_host_set_project_ops.restype = None
+        L.cryo_project_set_window.argtypes = [i32, sz]
+        L.cryo_project_set_window.restype = None
     L.cryo_host_codec_error.restype = C.c_char_p
     L.cryo_compat_set_error_handler.argtypes = [ERROR_HANDLER]
     L.cryo_compat_set_error_handler.restype = None
@@ -288,6 +313,8 @@ def lib():
     L.cryo_aggregate_scan.argtypes = [C.POINTER(CryoRel), vp, vp, AGG_BLOCK_FN, FETCH_REPORT_FN, vp, C.POINTER(CryoAggTotals)]
     # CryoGroupReport has the layout of the fetch's CryoFetchReport
     L.cryo_group_scan.argtypes = [C.POINTER(CryoRel), vp, vp, vp, GROUP_BLOCK_FN, FETCH_REPORT_FN, vp, C.POINTER(CryoGroupTotals)]
+    # CryoProjectReport has the layout of the fetch's CryoFetchReport
+    L.cryo_project_scan.argtypes = [C.POINTER(CryoRel), vp, vp, PROJECT_ROW_FN, FETCH_REPORT_FN, vp, C.POINTER(CryoProjectTotals)]
     for n in ("cryo_cache_hits", "cryo_cache_misses", "cryo_cache_codec_calls"):
         getattr(L, n).restype = C.c_uint64
     _libs[prod] = L
@@ -468,6 +495,35 @@ def group_scan(rel, atts, keys, by, cols=None):
     totals = {f: getattr(t, f) for f, _ in CryoGroupTotals._fields_}
     if rc != 0:
         raise GroupScanError(rc, events, totals)
+    return events, totals
+
+
+class ProjectScanError(RuntimeError):
+    def __init__(self, code, events, totals):
+        self.code, self.events, self.totals = code, events, totals
+        super().__init__("cryo_project_scan failed: %d" % code)
+
+
+def project_scan(rel, atts, keys, cols):
+    """cryo_project_scan (host/project.h) with the descriptors codec.filter_desc and codec.project_desc make of atts [(attlen,
+    attalign)], keys [(att, type, op, value)] and cols [att].  Returns (events, totals): events in delivery order, ("row", block,
+    pos, created_xid, nulls, the row's bytes) or ("report", block, reason, detail); totals a dict.  A nonzero status raises
+    ProjectScanError (which carries what was delivered)."""
+    from . import codec
+    desc, pdesc = codec.filter_desc(atts, keys), codec.project_desc(cols)
+    events = []
+
+    def on_row(arg, r):
+        r = r.contents
+        events.append(("row", r.block, r.pos, r.created_xid, r.nulls, C.string_at(r.data, r.row_bytes)))
+
+    wcb = PROJECT_ROW_FN(on_row)
+    rcb = FETCH_REPORT_FN(lambda arg, r: events.append(("report", r.contents.block, r.contents.reason, r.contents.detail)))
+    t = CryoProjectTotals()
+    rc = lib().cryo_project_scan(C.byref(rel), C.byref(desc[0]), C.byref(pdesc[0]), wcb, rcb, None, C.byref(t))
+    totals = {f: getattr(t, f) for f, _ in CryoProjectTotals._fields_}
+    if rc != 0:
+        raise ProjectScanError(rc, events, totals)
     return events, totals
 
 

@@ -155,6 +155,20 @@ static const CryoCodecGroupOps *bound_group_ops; /* the group table of a bound d
 void cryo_host_set_group_ops(const CryoCodecGroupOps *ops) { bound_group_ops = ops; }
 #endif
 const CryoCodecGroupOps *cryo_host_group_ops(void) { return bound_ops ? bound_group_ops : &hip_group_ops; }
+static int hip_project_blocks(void *ctx, int method, const void *const *src, const uint32_t *sz, size_t n, size_t bs,
+                              const void *filter, const void *project, void *rows, size_t row_cap, void *rec, size_t rec_cap,
+                              void *blocks, uint64_t *total)
+{
+    return cryo_multi_project_blocks((cryo_multi *)ctx, method, src, sz, n, bs, (const cryo_filter *)filter,
+                                     (const cryo_project *)project, rows, row_cap, (cryo_project_rec *)rec, rec_cap,
+                                     (cryo_project_block *)blocks, total);
+}
+static const CryoCodecProjectOps hip_project_ops = {hip_project_blocks};
+static const CryoCodecProjectOps *bound_project_ops; /* the project table of a bound double (CRYO_HOST_TEST_HOOKS builds only) */
+#ifdef CRYO_HOST_TEST_HOOKS
+void cryo_host_set_project_ops(const CryoCodecProjectOps *ops) { bound_project_ops = ops; }
+#endif
+const CryoCodecProjectOps *cryo_host_project_ops(void) { return bound_ops ? bound_project_ops : &hip_project_ops; }
 const char *cryo_host_codec_error(void) { return codec_err; }
 
 const CryoCodecOps *cryo_host_codec_ops(void)

@@ -154,6 +154,21 @@ const CryoCodecGroupOps *cryo_host_group_ops(void);
 #ifdef CRYO_HOST_TEST_HOOKS
 void cryo_host_set_group_ops(const CryoCodecGroupOps *ops); /* test builds only: the group table of the bound double, or NULL */
 #endif
+/* the projecting scan (project.h, cryo_project_scan) is bound through a table of its own as well.  project_blocks is
+ * cryo_multi_project_blocks (include/cryo_codec.h): filter is a const cryo_filter * and project a const cryo_project *, both with
+ * host arrays; rows gets up to row_cap rows of row_bytes (the layout rule of include/cryo_codec.h), rec up to rec_cap
+ * cryo_project_rec (8 bytes), blocks one cryo_project_block (32 bytes) per stream in call order, total[0] / total[1] the end of
+ * the last row / record used */
+typedef struct CryoCodecProjectOps {
+    int (*project_blocks)(void *ctx, int method, const void *const *src, const uint32_t *src_size, size_t n, size_t block_size,
+                          const void *filter, const void *project, void *rows, size_t row_cap, void *rec, size_t rec_cap,
+                          void *blocks, uint64_t *total);
+} CryoCodecProjectOps;
+/* the project table that goes with cryo_host_codec_ops(): production's binds the GPU codec; NULL when a bound double has none */
+const CryoCodecProjectOps *cryo_host_project_ops(void);
+#ifdef CRYO_HOST_TEST_HOOKS
+void cryo_host_set_project_ops(const CryoCodecProjectOps *ops); /* test builds only: the project table of the bound double, or NULL */
+#endif
 const CryoCodecOps *cryo_host_codec_ops(void);         /* lazily opens the GPU codec */
 void cryo_host_codec_trim(void);                         /* idle backend: free the binding's device workspace and staging buffers */
 size_t cryo_host_codec_bound(int method, size_t n);      /* cryo_codec_bound (or the bound double's): never opens the GPU */
