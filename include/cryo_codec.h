@@ -406,7 +406,9 @@ int cryo_codec_fetch_batch(cryo_codec *c, int method, const void *d_src, const u
  *   t_hoff = the byte at t + 22;  the null bitmap starts at t + 23, bit i - 1 (byte (i - 1) / 8, bit (i - 1) % 8) SET means column
  *   i is NOT null.
  *   TUPLE rule, checked before anything else of the tuple is read: len >= 23, hoff % 8 == 0,
- *   hoff >= MAXALIGN(23 + (HASNULL ? (tnatts + 7) / 8 : 0)), hoff <= len.
+ *   hoff >= MAXALIGN(23 + (HASNULL ? (tnatts + 7) / 8 : 0)), hoff <= len.  Any larger multiple of 8 is as good, with HASNULL clear
+ *   as with HASNULL set: the bytes between the header (and its bitmap) and t + hoff are not looked at.  Nothing else of the two
+ *   infomask words is looked at either: the bits of t_infomask2 above HEAP_NATTS_MASK and every bit of t_infomask but HASNULL.
  *   A column i > tnatts is NULL (missing-attribute defaults are not known here: the binder must not push down a key on a column
  *   with atthasmissing).  With HASNULL, a column whose bitmap bit is clear is NULL.  A NULL column takes no room.
  *   The walk keeps an offset o from t + hoff, starting at 0, over the columns i = 1 .. the highest key column -- that far for

@@ -16,12 +16,12 @@ import bytes_key_cases as bc
 import bytes_key_ref as br
 import tuple_craft as tc
 from pg_cryogen_amd import METHOD_LZ4, METHOD_ZSTD, CryoError, codec as cc
+from scan_calls import (REC_SENTINEL, SENTINEL, Device, Encoder, agg_batch, agg_host, filter_batch, filter_host, group_batch,
+                        group_host, multi_call, same_agg, same_fields, same_filter, same_group)
 from tuple_craft import Long, Toast
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0xA5
-REC_SENTINEL = np.frombuffer(bytes([SENTINEL] * 8), cc.FILTER_REC)[0]
 METHODS = [METHOD_LZ4, METHOD_ZSTD]
 
 
@@ -31,159 +31,9 @@ def dev(codec):
     codec.set_option(cc.OPT_WORKSPACE_MAX_BYTES, 0)
 
 
-class Encoder:
-    """the oracle's stream of a block, encoded once per method"""
-
-    def __init__(self, oracle):
-        self.oracle, self.seen = oracle, {}
-
-    def __call__(self, method, block):
-        key = (method, block.tobytes())
-        if key not in self.seen:
-            self.seen[key] = self.oracle.lz4_compress(block, 1) if method == METHOD_LZ4 else self.oracle.zstd_compress(block, 1)
-        return self.seen[key]
-
-
 @pytest.fixture(scope="module")
 def enc(oracle):
     return Encoder(oracle)
-
-
-# ---- device-resident calls ----
-class Device:
-    """the device buffers of one call: streams, descriptor, constants; freed on exit"""
-
-    def __init__(self, codec, comps, atts, keys, shift=0):
-        self.codec, self.bufs, self.n = codec, [], len(comps)
-        sizes = np.array([len(c) for c in comps], np.uint32)
-        offs = np.zeros(self.n, np.uint64)
-        at = 0
-        for i, c in enumerate(comps):
-            offs[i] = at
-            at += (len(c) + 15) & ~15
-        packed = np.zeros(max(at, 16), np.uint8)
-        for i, c in enumerate(comps):
-            packed[int(offs[i]):int(offs[i]) + len(c)] = np.asarray(c, np.uint8)
-        a, self.k, consts, rebase = cc.filter_desc_device(atts, keys)
-        self.src, self.off, self.sz = self.put(packed), self.put(offs), self.put(sizes)
-        self.atts = self.put(a)
-        self.consts = self.alloc(consts.nbytes + 8)
-        self.consts.upload(consts, shift)                              # the constants back to back from ptr + shift on
-        rebase(self.consts.ptr + shift)
-        self.natts, self.nkeys = len(atts), len(keys)
-        self.keys = self.put(self.k)
-
-    def alloc(self, nbytes, fill=None):
-        b = self.codec.alloc(max(int(nbytes), 8))
-        self.bufs.append(b)
-        if fill is not None:
-            b.memset(fill)
-        return b
-
-    def put(self, arr):
-        b = self.alloc(arr.nbytes)
-        b.upload(arr)
-        return b
-
-    def keys_untouched(self):
-        assert np.array_equal(self.keys.download(self.k.nbytes).view(cc.FILTER_KEY), self.k), "the caller's key array was written"
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        for b in self.bufs:
-            b.free()
-
-
-def filter_batch(codec, method, comps, B, atts, keys, flags=0, shift=0):
-    n = len(comps)
-    with Device(codec, comps, atts, keys, shift) as d:
-        dst, rec = d.alloc(n * B + 64, SENTINEL), d.alloc(8 * 290 * n + 64, SENTINEL)
-        tab, tot = d.alloc(32 * n, 0xEE), d.alloc(16, 0xEE)
-        codec.filter_batch(method, d.src, d.off, d.sz, B, n, d.natts, d.atts, d.nkeys, d.keys if keys else None, flags, dst, n * B,
-                           rec, 290 * n, tab, tot)
-        codec.sync()
-        d.keys_untouched()
-        t = tot.download(dtype=np.uint64)
-        return (tab.download(dtype=np.uint8).view(cc.FILTER_BLOCK).copy(), rec.download(dtype=np.uint8).view(cc.FILTER_REC).copy(),
-                dst.download(), (int(t[0]), int(t[1])))
-
-
-def agg_batch(codec, method, comps, B, atts, keys, cols, shift=0):
-    n, nc = len(comps), len(cols)
-    with Device(codec, comps, atts, keys, shift) as d:
-        g = d.put(cc.agg_desc(cols)[1])
-        rows, cells = d.alloc(16 * n + 64, SENTINEL), d.alloc(40 * n * nc + 64, SENTINEL)
-        codec.agg_batch(method, d.src, d.off, d.sz, B, n, d.natts, d.atts, d.nkeys, d.keys if keys else None, nc, g, rows, cells)
-        codec.sync()
-        d.keys_untouched()
-        r, c = rows.download(), cells.download()
-        assert (r[16 * n:] == SENTINEL).all() and (c[40 * n * nc:] == SENTINEL).all(), "a byte beyond the call's output was written"
-        return r[:16 * n].view(cc.AGG_BLOCK).copy(), c[:40 * n * nc].view(cc.AGG_CELL).reshape(n, nc).copy()
-
-
-def group_batch(codec, method, comps, B, atts, keys, by, cols, shift=0):
-    n, nc, cap = len(comps), len(cols), 290 * len(comps)
-    with Device(codec, comps, atts, keys, shift) as d:
-        b, g = d.put(cc.group_desc(by)[1]), d.put(cc.agg_desc(cols)[1])
-        rows, recs, cells, total = (d.alloc(32 * n + 64, SENTINEL), d.alloc(24 * cap + 64, SENTINEL),
-                                    d.alloc(40 * cap * nc + 64, SENTINEL), d.alloc(8, SENTINEL))
-        codec.group_batch(method, d.src, d.off, d.sz, B, n, d.natts, d.atts, d.nkeys, d.keys if keys else None, len(by), b, nc,
-                          g if nc else None, rows, recs, cap, cells if nc else None, total)
-        codec.sync()
-        d.keys_untouched()
-        r, q, c = rows.download(), recs.download(), cells.download()
-        tot = int(total.download().view("<u8")[0])
-        assert tot <= cap and (r[32 * n:] == SENTINEL).all() and (q[24 * tot:] == SENTINEL).all() and (c[40 * tot * nc:] == SENTINEL).all()
-        return (r[:32 * n].view(cc.GROUP_BLOCK).copy(), q[:24 * tot].view(cc.GROUP_REC).copy(),
-                c[:40 * tot * nc].view(cc.AGG_CELL).reshape(tot, nc).copy(), tot)
-
-
-# ---- host-buffer calls ----
-def filter_host(codec, method, comps, B, atts, keys, flags=0):
-    n = max(len(comps), 1)
-    return codec.filter_blocks(method, comps, B, cc.filter_desc(atts, keys, flags), dst=np.full(n * B, SENTINEL, np.uint8),
-                               rec=np.full(n * 290, REC_SENTINEL, cc.FILTER_REC))
-
-
-def agg_host(codec, method, comps, B, atts, keys, cols):
-    return codec.agg_blocks(method, comps, B, cc.filter_desc(atts, keys), cc.agg_desc(cols))
-
-
-def group_host(codec, method, comps, B, atts, keys, by, cols):
-    return codec.group_blocks(method, comps, B, cc.filter_desc(atts, keys), cc.group_desc(by), cc.agg_desc(cols) if cols else None)
-
-
-# ---- comparing ----
-def same_fields(got, want, what):
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    for f in want.dtype.names:
-        bad = np.argwhere(got[f] != want[f])
-        assert bad.size == 0, (what, f, [(tuple(int(x) for x in i), got[tuple(i)], want[tuple(i)]) for i in bad[:5]])
-
-
-def same_filter(got, want, what=""):
-    table, recs, dst, total = got
-    etable, erecs, packed, etotal = want
-    same_fields(table, etable, what)
-    assert tuple(total) == tuple(etotal), (what, total, etotal)
-    same_fields(recs[:erecs.size], erecs, what)
-    assert (recs[erecs.size:].view(np.uint8) == SENTINEL).all(), (what, "a record at or beyond the total was written")
-    diff = np.flatnonzero(dst[:packed.size] != packed)
-    assert diff.size == 0, (what, "first differing byte", int(diff[0]))
-    assert (dst[packed.size:] == SENTINEL).all(), (what, "a byte at or beyond the total was written")
-
-
-def same_agg(got, want, what=""):
-    same_fields(got[0], want[0], what)
-    same_fields(got[1], want[1], what)
-
-
-def same_group(got, want, what=""):
-    assert got[3] == want[3], (what, got[3], want[3])
-    for g, w in zip(got[:3], want[:3]):
-        same_fields(g, w, what)
 
 
 def columns(atts):
@@ -382,19 +232,6 @@ def test_chunks_keep_the_constants(dev, enc, random_blocks):
 
 
 # ---- several handles ----
-def multi_call(devices, fn):
-    L = cc.lib()
-    h = C.c_void_p()
-    devs = (C.c_int * len(devices))(*devices)
-    assert L.cryo_multi_open(devs, len(devices), C.byref(h)) == 0
-    try:
-        def chk(rc, what):
-            assert rc == 0, (what, rc, L.cryo_multi_last_error(h))
-        return fn(L, h, chk)
-    finally:
-        L.cryo_multi_close(h)
-
-
 def test_multi_handles(dev, enc, random_blocks):
     """one handle, two handles on one device, and two devices where the machine has them"""
     blocks = random_blocks[:11]

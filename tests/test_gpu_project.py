@@ -14,10 +14,10 @@ import filter_ref as fr
 import project_cases as pc
 import project_ref as pr
 from pg_cryogen_amd import METHOD_LZ4, METHOD_ZSTD, CryoError, codec as cc
+from scan_calls import pack_streams, project_batch, project_host as host_call, same_project as same
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0xA5
 SYNTH_ATTS = [(4, 4), (-1, 4)]
 METHODS = [METHOD_LZ4, METHOD_ZSTD]
 
@@ -31,85 +31,6 @@ def prj(codec):
 
 def oracle_encode(oracle, method, raw):
     return oracle.lz4_compress(raw, 1) if method == METHOD_LZ4 else oracle.zstd_compress(raw, 1)
-
-
-def pack_streams(comps):
-    n = len(comps)
-    sizes = np.array([len(c) for c in comps], np.uint32)
-    offs = np.zeros(n, np.uint64)
-    at = 0
-    for i, c in enumerate(comps):
-        offs[i] = at
-        at += (len(c) + 15) & ~15
-    packed = np.zeros(max(at, 16), np.uint8)
-    for i, c in enumerate(comps):
-        packed[int(offs[i]):int(offs[i]) + len(c)] = np.asarray(c, np.uint8)
-    return packed, offs, sizes
-
-
-def project_batch(codec, method, comps, B, atts, keys, cols, row_cap=None, rec_cap=None):
-    """cryo_codec_project_batch on device copies of the streams and of the descriptors (the constants of byte-string keys
-    included): (table, records, rows of shape (rows written, row_bytes), (total rows, total records)).  Table, records and rows are
-    filled with SENTINEL before the call; the 64 bytes behind the table and everything at or beyond min(total, cap) of records and
-    rows must still hold it afterwards"""
-    n = len(comps)
-    _, rb = pr.row_layout(atts, cols)
-    wcap = 290 * n if row_cap is None else row_cap
-    rcap = 290 * n if rec_cap is None else rec_cap
-    packed, offs, sizes = pack_streams(comps)
-    a, k, consts, rebase = cc.filter_desc_device(atts, keys)
-    _, p = cc.project_desc(cols)
-    bufs = [codec.alloc(packed.nbytes), codec.alloc(8 * n), codec.alloc(4 * n), codec.alloc(a.nbytes), codec.alloc(k.nbytes),
-            codec.alloc(consts.nbytes + 16), codec.alloc(p.nbytes), codec.alloc(32 * n + 64), codec.alloc(8 * rcap + 64),
-            codec.alloc(rb * wcap + 64), codec.alloc(16)]
-    d_src, d_off, d_sz, d_atts, d_keys, d_consts, d_cols, d_table, d_rec, d_rows, d_total = bufs
-    try:
-        for d, h in ((d_src, packed), (d_off, offs), (d_sz, sizes), (d_atts, a), (d_consts, consts), (d_cols, p)):
-            d.upload(h)
-        d_keys.upload(rebase(d_consts.ptr))
-        for d in (d_table, d_rec, d_rows, d_total):
-            d.memset(SENTINEL)
-        codec.project_batch(method, d_src, d_off, d_sz, B, n, len(atts), d_atts, len(keys), d_keys if keys else None, len(cols), d_cols,
-                            d_rows, wcap, d_rec, rcap, d_table, d_total)
-        codec.sync()
-        table, rec, rows = d_table.download(), d_rec.download(), d_rows.download()
-        tw, tr = (int(v) for v in d_total.download()[:16].view("<u8"))
-        ww, wr = min(tw, wcap), min(tr, rcap)
-        assert (table[32 * n:] == SENTINEL).all(), "a byte beyond the block table was written"
-        assert (rec[8 * wr:] == SENTINEL).all(), "a byte at or beyond the records' total or cap was written"
-        assert (rows[rb * ww:] == SENTINEL).all(), "a byte at or beyond the rows' total or cap was written"
-        return (table[:32 * n].view(cc.PROJECT_BLOCK).copy(), rec[:8 * wr].view(cc.PROJECT_REC).copy(),
-                rows[:rb * ww].reshape(ww, rb).copy(), (tw, tr))
-    finally:
-        for x in bufs:
-            x.free()
-
-
-def host_call(codec, method, comps, B, atts, keys, cols, row_cap=None, rec_cap=None):
-    """cryo_codec_project_blocks with sentinel-filled buffers of the given capacities; the same tuple as project_batch"""
-    n = len(comps)
-    _, rb = pr.row_layout(atts, cols)
-    rows = np.full((max(n, 1) * 290 if row_cap is None else row_cap, rb), SENTINEL, np.uint8)
-    rec = np.full(8 * (max(n, 1) * 290 if rec_cap is None else rec_cap), SENTINEL, np.uint8).view(cc.PROJECT_REC)
-    table, rec, rows, (tw, tr) = codec.project_blocks(method, comps, B, cc.filter_desc(atts, keys), cc.project_desc(cols), rb, rows, rec)
-    assert (rows[tw:] == SENTINEL).all() and (rec[tr:].view(np.uint8) == SENTINEL).all(), "a byte beyond the totals was written"
-    return table, rec[:tr].copy(), rows[:tw].copy(), (tw, tr)
-
-
-def same(got, want, what=""):
-    table, rec, rows, total = got
-    etable, erec, erows, etotal = want
-    assert tuple(total) == tuple(etotal), (what, total, etotal)
-    assert table.shape == etable.shape and rec.shape == erec.shape and rows.shape == erows.shape, \
-        (what, table.shape, etable.shape, rec.shape, erec.shape, rows.shape, erows.shape)
-    for f in etable.dtype.names:
-        bad = np.flatnonzero(table[f] != etable[f])
-        assert bad.size == 0, (what, f, [(int(i), tuple(table[i]), tuple(etable[i])) for i in bad[:5]])
-    for f in erec.dtype.names:
-        bad = np.flatnonzero(rec[f] != erec[f])
-        assert bad.size == 0, (what, f, [(int(i), tuple(rec[i]), tuple(erec[i])) for i in bad[:5]])
-    bad = np.flatnonzero((rows != erows).any(axis=1)) if rows.size else np.zeros(0, int)
-    assert bad.size == 0, (what, "rows", [(int(i), bytes(rows[i]).hex(), bytes(erows[i]).hex()) for i in bad[:5]])
 
 
 def both(codec, oracle, blocks, B, atts, keys, cols, what, methods=METHODS):

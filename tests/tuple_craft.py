@@ -35,15 +35,22 @@ def maxalign(x):
     return (x + 7) & ~7
 
 
-def form_tuple(atts, values, xmin=1000):
+def form_tuple(atts, values, xmin=1000, infomask2_flags=0, infomask_flags=0, extra_hoff=0, force_bitmap=False):
     """the bytes of a tuple with len(values) attributes (may be fewer than the relation has: columns added later).  atts:
-    [(attlen, attalign)]; values[i]: None (NULL), an int (fixed width), bytes / Long / Toast (varlena)"""
+    [(attlen, attalign)]; values[i]: None (NULL), an int (fixed width), bytes / Long / Toast (varlena).
+
+    The header is the minimal one unless a knob says otherwise: infomask2_flags is OR-ed into bits 11 .. 15 of t_infomask2
+    (HEAP_KEYS_UPDATED 0x2000, HEAP_HOT_UPDATED 0x4000, HEAP_ONLY_TUPLE 0x8000); infomask_flags into t_infomask, whose bits 0 and 1
+    (HASNULL, HASVARWIDTH) stay this function's; extra_hoff, a multiple of 8, is added to t_hoff and the gap holds zeros;
+    force_bitmap writes HASNULL and a bitmap (every bit set) although no value is NULL"""
     natts = len(values)
-    hasnull = any(v is None for v in values)
+    assert infomask2_flags & ~0xF800 == 0 and infomask_flags & ~0xFFFC == 0 and extra_hoff % 8 == 0 and extra_hoff >= 0
+    hasnull = force_bitmap or any(v is None for v in values)
     bitmap = bytearray((natts + 7) // 8 if hasnull else 0)
-    hoff = maxalign(23 + len(bitmap))
+    hoff = maxalign(23 + len(bitmap)) + extra_hoff
+    assert hoff <= 255
     data = bytearray()
-    infomask = XMAX_INVALID | (HASNULL if hasnull else 0)
+    infomask = XMAX_INVALID | (HASNULL if hasnull else 0) | infomask_flags
     for i, v in enumerate(values):
         attlen, attalign = atts[i]
         if v is None:
@@ -65,7 +72,7 @@ def form_tuple(atts, values, xmin=1000):
             data += bytes([((len(v) + 1) << 1) | 1]) + bytes(v)
     head = bytearray(23)
     struct.pack_into("<I", head, 0, xmin)
-    struct.pack_into("<HH", head, 18, natts, infomask)
+    struct.pack_into("<HH", head, 18, natts | infomask2_flags, infomask)
     head[22] = hoff
     return bytes(head) + bytes(bitmap) + bytes(hoff - 23 - len(bitmap)) + bytes(data)
 
