@@ -384,9 +384,21 @@ int cryo_codec_fetch_batch(cryo_codec *c, int method, const void *d_src, const u
  * constant's length n, 0 .. CRYO_KEY_BYTES_MAX, and value the address of its n bytes -- a device address for cryo_codec_*_batch,
  * a host address for cryo_codec_*_blocks and cryo_multi_*_blocks; any alignment; not looked at when n == 0.  CRYO_E_ARG when the
  * key's column is not a varlena (attlen != -1), n > CRYO_KEY_BYTES_MAX, or n > 0 with a null address.  For every other type and
- * for the null tests rsv != 0 stays refused.  The caller's arrays are never written: the library makes its own device copy of
+ * for the null tests rsv != 0 stays refused (a set key, below, apart).  The caller's arrays are never written: the library makes its own device copy of
  * the keys and of the constants, in which the kernels find each constant 8-byte aligned and zero-padded to a multiple of 8.
  * Such a key is no aggregate and no group column (CRYO_E_ARG there, as any unknown type).
+ * Set keys.  CRYO_OP_IN (9) and CRYO_OP_NOT_IN (10) test an integer column against a list of integers (WHERE app_id IN (3, 17, 40),
+ * campaign_id = ANY($1)): type is CRYO_KEY_INT2, CRYO_KEY_INT4 or CRYO_KEY_INT8, rsv the number of list members n, 1 ..
+ * CRYO_KEY_SET_MAX, and value the address of n int64_t members -- a device address for cryo_codec_*_batch, a host address for
+ * cryo_codec_*_blocks and cryo_multi_*_blocks; any alignment: the library only copies from it, as for a byte-string constant.
+ * Members come in any order and may repeat; a member outside the range of the key's type is allowed and equals no value, so
+ * that validating a descriptor never depends on the list's contents.  The column rule is the comparison key's: attlen is the
+ * type's size and attalign at least that.  CRYO_E_ARG when n == 0, n > CRYO_KEY_SET_MAX, the address is null, or the type is not
+ * one of the three integer types (CRYO_KEY_BYTES included).  A set key counts as one of the four keys; several may be used, also
+ * on one column and beside comparisons, null tests and byte-string keys.  The library's device copy holds a set as its distinct
+ * members, ascending as signed 64-bit integers and 8-byte aligned; the caller's key array and lists are only read.  The binder's
+ * part, not enforced here: drop NULL members from an IN list, never push down a NOT IN whose list holds a NULL, and fold an
+ * empty list itself.
  *
  * Per block (names as in the check's rules above: lower, upper, n, off_i, len_i, MAXALIGN, B), the first failing rule wins:
  *   CRYO_FETCH_STREAM (1), CRYO_FETCH_HEADER (2)   exactly the fetch's; no item is examined, the block has no record
@@ -432,6 +444,9 @@ int cryo_codec_fetch_batch(cryo_codec *c, int method, const void *d_src, const u
  *   With plen the payload's length and n the constant's: c = memcmp(payload, constant, min(plen, n)) on UNSIGNED bytes, and when
  *   that is 0, c = sign(plen - n); the six ops are the obvious tests on c (= is c == 0, < is c < 0, ...).  Only the payload's
  *   plen bytes are read, never the pad behind them.
+ *   Set keys: on a NULL column (a column beyond tnatts included) CRYO_OP_IN and CRYO_OP_NOT_IN are both false.  Otherwise, with v
+ *   the column's value as above, sign-extended to 64 bits: IN is true when v equals some member of the list, NOT_IN when it
+ *   equals none.  A set key is never undecided, and the walk still goes to the highest key column for every tuple.
  *   The verdict on a tuple, the first rule that applies: CRYO_FILTER_TUPLE if the walk fails anywhere up to the highest column
  *   it visits (it still goes that far whatever the keys said); no match if some key is decidedly false (false AND unknown is
  *   false); CRYO_FILTER_UNDECIDED if a byte-string key met an undecided value; otherwise a match.
@@ -458,7 +473,8 @@ typedef enum {
     CRYO_KEY_BYTES = 16                                      /* a byte string: rsv its length, value its address */
 } cryo_key_type;
 typedef enum {
-    CRYO_OP_LT = 1, CRYO_OP_LE, CRYO_OP_EQ, CRYO_OP_GE, CRYO_OP_GT, CRYO_OP_NE, CRYO_OP_ISNULL, CRYO_OP_NOTNULL
+    CRYO_OP_LT = 1, CRYO_OP_LE, CRYO_OP_EQ, CRYO_OP_GE, CRYO_OP_GT, CRYO_OP_NE, CRYO_OP_ISNULL, CRYO_OP_NOTNULL,
+    CRYO_OP_IN = 9, CRYO_OP_NOT_IN = 10 /* a set key: rsv the number of members, value the address of that many int64_t */
 } cryo_key_op;
 typedef struct { uint16_t att; uint8_t type, op; uint32_t rsv; int64_t value; } cryo_scan_key; /* att 1-based; 16 bytes */
 typedef struct {
@@ -470,6 +486,7 @@ typedef struct {
 #define CRYO_FILTER_TUPLE 8u      /* a record's status beside CRYO_FETCH_ITEM: the tuple breaks a tuple rule */
 #define CRYO_FILTER_UNDECIDED 9u  /* a record's status: a byte-string key met a compressed or external value */
 #define CRYO_KEY_BYTES_MAX 256u   /* the longest constant of a CRYO_KEY_BYTES key */
+#define CRYO_KEY_SET_MAX 1024u    /* the most members of a CRYO_OP_IN / CRYO_OP_NOT_IN list */
 #define CRYO_FILTER_MAX_ATTS 1600u
 #define CRYO_FILTER_MAX_KEYS 4u
 typedef struct { uint32_t status, n_items, n_match, n_bad; uint64_t rec_first, off; } cryo_filter_block; /* 32 bytes, one per block */
@@ -477,7 +494,7 @@ typedef struct { uint16_t pos, status; uint32_t len; } cryo_filter_rec;         
 /* Device buffers.  The struct *f itself is host memory; f->atts and f->keys are DEVICE arrays (4-byte / 8-byte aligned).  The
  * host validates the descriptor before anything is queued: it reads the two arrays back on the handle's stream (one wait for
  * what the stream held before the call, at most 6400 + 64 bytes); from there on the call is asynchronous.  With a byte-string
- * key the constants are read back too (at most 1 024 more bytes) and the library's copy of keys and constants goes into
+ * or a set key the constants and lists are read back too (at most 4 x 8 192 more bytes) and the library's copy of keys and constants goes into
  * handle-owned device memory: two more waits before the call turns asynchronous; the copy serves all of the call's internal
  * chunks.  d_dst 8-byte, d_rec
  * 8-byte, d_blocks 16-byte, d_total 8-byte aligned (CRYO_E_ARG otherwise); d_total has two entries and is also where the two

@@ -47,6 +47,8 @@ KEY_INT2, KEY_INT4, KEY_INT8 = 1, 2, 3
 KEY_BYTES = 16              # a byte string: the key's value is bytes, compared unsigned, then by length
 KEY_BYTES_MAX = 256
 OP_LT, OP_LE, OP_EQ, OP_GE, OP_GT, OP_NE, OP_ISNULL, OP_NOTNULL = range(1, 9)
+OP_IN, OP_NOT_IN = 9, 10    # a set key: the key's value is a sequence of ints, its type KEY_INT2 / KEY_INT4 / KEY_INT8
+KEY_SET_MAX = 1024
 FILTER_ATT = np.dtype([("attlen", "<i2"), ("attalign", "u1"), ("rsv", "u1")])                                  # cryo_att
 FILTER_KEY = np.dtype([("att", "<u2"), ("type", "u1"), ("op", "u1"), ("rsv", "<u4"), ("value", "<i8")])        # cryo_scan_key
 FILTER_BLOCK = np.dtype([("status", "<u4"), ("n_items", "<u4"), ("n_match", "<u4"), ("n_bad", "<u4"),
@@ -300,7 +302,8 @@ def fetch_blocks_call(fn, handle, chk, method, comps, block_size, requests, dst=
 
 def filter_desc(atts, keys=(), flags=0):
     """the descriptor of a filter call as host arrays: atts a list of (attlen, attalign), keys a list of (att, type, op, value)
-    (att 1-based; type KEY_*, op OP_*; the value of a KEY_BYTES comparison is a bytes object).  Returns (CryoFilter, atts array,
+    (att 1-based; type KEY_*, op OP_*; the value of a KEY_BYTES comparison is a bytes object, that of an OP_IN / OP_NOT_IN key
+    a sequence of ints).  Returns (CryoFilter, atts array,
     keys array); the struct points into the two arrays, which the caller keeps alive.  The constants of KEY_BYTES keys live in
     one uint8 array the struct holds (f.consts), so they live as long as it does"""
     a = np.zeros(max(len(atts), 1), FILTER_ATT)
@@ -318,8 +321,14 @@ def _is_bytes_key(key):
     return key[1] == KEY_BYTES and isinstance(key[3], (bytes, bytearray, memoryview, type(None)))
 
 
+def _is_set_key(key):
+    """a key whose value is a list of integers (None under OP_IN / OP_NOT_IN: no members and a null address)"""
+    return isinstance(key[3], (list, tuple, range, np.ndarray)) or (key[3] is None and key[2] in (OP_IN, OP_NOT_IN))
+
+
 def _filter_keys(keys):
-    """(keys array with rsv = the length and value = the offset of each KEY_BYTES constant, the constants packed back to back)"""
+    """(keys array with rsv = the length and value = the offset of each KEY_BYTES constant, rsv = the number of members and
+    value = the offset of each set key's list -- little-endian int64 --, constants and lists packed back to back)"""
     k = np.zeros(max(len(keys), 1), FILTER_KEY)
     parts, at = [], 0
     for i, key in enumerate(keys):
@@ -329,6 +338,12 @@ def _filter_keys(keys):
             k[i] = (att, typ, op, len(value), at)
             parts.append(value)
             at += len(value)
+        elif _is_set_key(key):
+            value = () if value is None else value
+            members = b"".join(int(m).to_bytes(8, "little", signed=True) for m in value)
+            k[i] = (att, typ, op, len(value), at)
+            parts.append(members)
+            at += len(members)
         else:
             k[i] = (att, typ, op, 0, value)
     consts = np.frombuffer(b"".join(parts) + b"\0", np.uint8).copy()        # never empty: it has an address
@@ -338,14 +353,14 @@ def _filter_keys(keys):
 def _rebase_keys(k, keys, base):
     """offsets into the packed constants -> addresses from `base` on; an empty constant keeps a null address"""
     for i, key in enumerate(keys):
-        if _is_bytes_key(key):
-            k[i]["value"] = base + int(k[i]["value"]) if key[3] else 0
+        if _is_bytes_key(key) or _is_set_key(key):
+            k[i]["value"] = base + int(k[i]["value"]) if (key[3] is not None and len(key[3])) else 0
 
 
 def filter_desc_device(atts, keys=()):
-    """the device form of a descriptor with KEY_BYTES keys: returns (atts array, keys array, consts array, rebase).  The caller
-    uploads consts to device memory at some address d and calls rebase(d), which sets every KEY_BYTES key's value to the
-    device address of its constant (constants lie back to back in consts, at any alignment); then it uploads the keys"""
+    """the device form of a descriptor with KEY_BYTES keys or set keys: returns (atts array, keys array, consts array, rebase).  The caller
+    uploads consts to device memory at some address d and calls rebase(d), which sets every KEY_BYTES key's and set key's value to the
+    device address of its constant or list (they lie back to back in consts, at any alignment); then it uploads the keys"""
     a = np.zeros(max(len(atts), 1), FILTER_ATT)
     for i, (attlen, attalign) in enumerate(atts):
         a[i] = (attlen, attalign, 0)

@@ -9,6 +9,7 @@
 #include "cryo_codec.h"
 #include "kernels.h"
 
+#include <algorithm>
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
@@ -1145,7 +1146,7 @@ namespace {
 struct ScanDesc {
     const void *d_atts = nullptr, *d_keys = nullptr; /* device */
     uint32_t nkeys = 0, max_att = 0;                 /* max_att: the highest column the walk has to reach */
-    bool bytes_keys = false;                         /* d_keys is a key table with a byte-string key */
+    bool table_keys = false;                         /* d_keys is a key table: some key is a byte-string key or a set key */
 };
 struct FilterIo {
     ScanDesc sd;
@@ -1180,13 +1181,15 @@ static bool filter_desc_ok(const cryo_filter *f, const cryo_att *atts, const cry
     }
     for (uint32_t k = 0; k < f->nkeys; k++) {
         const cryo_scan_key &q = keys[k];
-        const bool cmp = q.op >= CRYO_OP_LT && q.op <= CRYO_OP_NE;
-        if ((q.rsv != 0 && !(cmp && q.type == CRYO_KEY_BYTES)) || q.att == 0 || q.att > f->natts || q.op < CRYO_OP_LT ||
-            q.op > CRYO_OP_NOTNULL)
+        const bool cmp = q.op >= CRYO_OP_LT && q.op <= CRYO_OP_NE, set = q.op == CRYO_OP_IN || q.op == CRYO_OP_NOT_IN;
+        if ((q.rsv != 0 && !(cmp && q.type == CRYO_KEY_BYTES) && !set) || q.att == 0 || q.att > f->natts || q.op < CRYO_OP_LT ||
+            q.op > CRYO_OP_NOT_IN)
             return false;
         if (q.att > *max_att) *max_att = q.att;
         if (q.op == CRYO_OP_ISNULL || q.op == CRYO_OP_NOTNULL) continue;
-        if (q.type == CRYO_KEY_BYTES) { /* rsv: the constant's length; value: its address, not looked at here beyond null */
+        /* a set key: rsv the members, value their address, not looked at here beyond null; the members are never looked at */
+        if (set && (q.rsv == 0 || q.rsv > CRYO_KEY_SET_MAX || q.value == 0)) return false;
+        if (q.type == CRYO_KEY_BYTES && !set) { /* rsv: the constant's length; value: its address, not looked at here beyond null */
             if (atts[q.att - 1].attlen != -1 || q.rsv > CRYO_KEY_BYTES_MAX || (q.rsv > 0 && q.value == 0)) return false;
             continue;
         }
@@ -1194,6 +1197,7 @@ static bool filter_desc_ok(const cryo_filter *f, const cryo_att *atts, const cry
         const int size = q.type == CRYO_KEY_INT2 ? 2 : q.type == CRYO_KEY_INT4 ? 4 : 8;
         const cryo_att &a = atts[q.att - 1];
         if (a.attlen != size || a.attalign < size) return false;
+        if (set) continue; /* value is an address */
         if (size == 2 && (q.value < INT16_MIN || q.value > INT16_MAX)) return false;
         if (size == 4 && (q.value < INT32_MIN || q.value > INT32_MAX)) return false;
     }
@@ -1204,18 +1208,26 @@ static bool filter_desc_ok(const cryo_filter *f, const cryo_att *atts, const cry
  * A descriptor with a CRYO_KEY_BYTES key reaches the kernels as a key table: [keys 16 x nkeys][the constants in key order, each
  * zero-padded to a multiple of 8], the whole a multiple of 16 bytes, with the value of every such key rewritten to the device
  * address of its constant in the table -- 8-byte aligned there, whatever the caller's address was.  The caller's arrays are only
- * read.  A descriptor without such a key has no table: its keys go to the device as they are. */
-static constexpr size_t kKeyTableBytes = CRYO_FILTER_MAX_KEYS * (sizeof(cryo_scan_key) + CRYO_KEY_BYTES_MAX);
+ * read.  A set key (CRYO_OP_IN, CRYO_OP_NOT_IN) takes the same road: its list lies among the constants as its distinct members,
+ * ascending as signed 64-bit integers, in the room of the rsv members the caller named; the table's copy of the key has rsv
+ * rewritten to the distinct count and value to the set's device address.  A descriptor without either kind of key has no table:
+ * its keys go to the device as they are. */
+static constexpr size_t kKeyConstMax = 8u * CRYO_KEY_SET_MAX; /* the most bytes one key's constant or list takes */
+static_assert(kKeyConstMax >= CRYO_KEY_BYTES_MAX, "a list is the largest constant");
+static constexpr size_t kKeyTableBytes = CRYO_FILTER_MAX_KEYS * (sizeof(cryo_scan_key) + kKeyConstMax);
 
 static bool key_is_bytes(const cryo_scan_key &q) { return q.type == CRYO_KEY_BYTES && q.op >= CRYO_OP_LT && q.op <= CRYO_OP_NE; }
+static bool key_is_set(const cryo_scan_key &q) { return q.op == CRYO_OP_IN || q.op == CRYO_OP_NOT_IN; }
+/* the bytes at a (valid) key's address: a byte-string constant's, a list's; 0: the key has none */
+static size_t key_const_len(const cryo_scan_key &q) { return key_is_set(q) ? (size_t)q.rsv * 8 : key_is_bytes(q) ? (size_t)q.rsv : 0; }
 
-/* the bytes the constants take behind the keys of a (valid) descriptor, a multiple of 16; 0: no byte-string key */
+/* the bytes the constants take behind the keys of a (valid) descriptor, a multiple of 16; *any: some key needs the table */
 static size_t key_consts_bytes(const cryo_scan_key *keys, uint32_t nkeys, bool *any)
 {
     size_t b = 0;
     *any = false;
     for (uint32_t k = 0; k < nkeys; k++)
-        if (key_is_bytes(keys[k])) { *any = true; b += ((size_t)keys[k].rsv + 7) & ~(size_t)7; }
+        if (key_is_bytes(keys[k]) || key_is_set(keys[k])) { *any = true; b += (key_const_len(keys[k]) + 7) & ~(size_t)7; }
     return (b + 15) & ~(size_t)15;
 }
 
@@ -1226,7 +1238,16 @@ static void key_table_fill(uint8_t *tab, uint64_t d_tab, const cryo_scan_key *ke
     size_t at = (size_t)nkeys * sizeof(cryo_scan_key);
     for (uint32_t k = 0; k < nkeys; k++) {
         cryo_scan_key q = keys[k];
-        if (key_is_bytes(q)) {
+        if (key_is_set(q)) { /* at is a multiple of 8: the table is 8-byte aligned wherever it is built */
+            int64_t *m = reinterpret_cast<int64_t *>(tab + at);
+            memcpy(m, consts[k], (size_t)q.rsv * 8);
+            std::sort(m, m + q.rsv);
+            const uint32_t distinct = (uint32_t)(std::unique(m, m + q.rsv) - m);
+            memset(m + distinct, 0, (size_t)(q.rsv - distinct) * 8);
+            q.value = (int64_t)(d_tab + at);
+            at += (size_t)q.rsv * 8;
+            q.rsv = distinct;
+        } else if (key_is_bytes(q)) {
             if (q.rsv) memcpy(tab + at, consts[k], q.rsv);
             q.value = (int64_t)(d_tab + at);
             at += ((size_t)q.rsv + 7) & ~(size_t)7;
@@ -1235,19 +1256,20 @@ static void key_table_fill(uint8_t *tab, uint64_t d_tab, const cryo_scan_key *ke
     }
 }
 
-/* the device-resident calls: keys (host copy, validated) name constants in DEVICE memory.  Reads them back (at most 1 024 bytes),
- * builds the table in handle-owned device memory and gives its address; one more wait on the stream.  Without a byte-string key:
- * *d_keys stays the caller's array and nothing is queued. */
-static int key_table_device(cryo_codec *c, const cryo_scan_key *keys, uint32_t nkeys, const void **d_keys, bool *bytes_keys)
+/* the device-resident calls: keys (host copy, validated) name constants and lists in DEVICE memory.  Reads them back together (at
+ * most 4 x 8 192 bytes, one wait), builds the table in handle-owned device memory and gives its address; one more wait on the
+ * stream.  Without a byte-string key or a set key: *d_keys stays the caller's array and nothing is queued. */
+static int key_table_device(cryo_codec *c, const cryo_scan_key *keys, uint32_t nkeys, const void **d_keys, bool *table_keys)
 {
-    const size_t cb = key_consts_bytes(keys, nkeys, bytes_keys);
-    if (!*bytes_keys) return CRYO_OK;
-    std::vector<uint8_t> consts(CRYO_FILTER_MAX_KEYS * CRYO_KEY_BYTES_MAX), tab((size_t)nkeys * sizeof(cryo_scan_key) + cb, 0);
+    const size_t cb = key_consts_bytes(keys, nkeys, table_keys);
+    if (!*table_keys) return CRYO_OK;
+    std::vector<uint8_t> consts(CRYO_FILTER_MAX_KEYS * kKeyConstMax), tab((size_t)nkeys * sizeof(cryo_scan_key) + cb, 0);
     const void *where[CRYO_FILTER_MAX_KEYS] = {nullptr, nullptr, nullptr, nullptr};
     for (uint32_t k = 0; k < nkeys; k++) {
-        if (!key_is_bytes(keys[k]) || keys[k].rsv == 0) continue;
-        where[k] = consts.data() + (size_t)k * CRYO_KEY_BYTES_MAX;
-        HIP_TRY(c, hipMemcpyAsync((void *)where[k], (const void *)(uintptr_t)keys[k].value, keys[k].rsv, hipMemcpyDeviceToHost, c->stream));
+        const size_t len = key_const_len(keys[k]);
+        if (len == 0) continue;
+        where[k] = consts.data() + (size_t)k * kKeyConstMax;
+        HIP_TRY(c, hipMemcpyAsync((void *)where[k], (const void *)(uintptr_t)keys[k].value, len, hipMemcpyDeviceToHost, c->stream));
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (!c->d_keytab) HIP_TRY(c, hipMalloc(&c->d_keytab, kKeyTableBytes));
@@ -1259,7 +1281,7 @@ static int key_table_device(cryo_codec *c, const cryo_scan_key *keys, uint32_t n
 }
 
 /* the host-buffer calls: the table into the pinned copy of the descriptor at pin_keys, which the upload puts at d_keys.  Returns
- * whether the descriptor has a byte-string key */
+ * whether the descriptor has a key that needs the table */
 static bool key_table_host(uint8_t *pin_keys, const uint8_t *d_keys, const cryo_filter *f)
 {
     bool any = false;
@@ -1294,7 +1316,7 @@ static int filter_pass(cryo_codec *c, int method, const uint8_t *d_src, const ui
         cryo_filter_rec *st_rec = (cryo_filter_rec *)(st_dst + row * ch.K);
         if (ch.lo == 0) HIP_TRY(c, hipMemsetAsync(running, 0, 2 * sizeof(uint64_t), c->stream));
         HIP_TRY(c, cryo::launch_filter(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.sd.d_atts, io.sd.d_keys, io.sd.nkeys, io.sd.max_att,
-                                       io.sd.bytes_keys, io.count_only, (uint4 *)(io.d_blocks + ch.lo), side, sum, base, running,
+                                       io.sd.table_keys, io.count_only, (uint4 *)(io.d_blocks + ch.lo), side, sum, base, running,
                                        stage ? st_dst : io.d_dst, stage ? ch.K * row : io.dst_cap,
                                        stage ? (uint2 *)st_rec : (uint2 *)io.d_rec, stage ? ch.K * S : io.rec_cap, host,
                                        c->lz4_opts.cus));
@@ -1382,7 +1404,7 @@ static int agg_pass(cryo_codec *c, int method, const uint8_t *d_src, const uint6
     DecodePass ps(d_src, d_src_off, d_src_size, true);
     ps.run = [&](const DecodeChunk &ch) -> int {
         HIP_TRY(c, cryo::launch_agg(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.sd.d_atts, io.sd.d_keys, io.sd.nkeys, io.d_cols,
-                                    io.ncols, io.sd.max_att, io.sd.bytes_keys, (uint4 *)(io.d_blocks + ch.lo),
+                                    io.ncols, io.sd.max_att, io.sd.table_keys, (uint4 *)(io.d_blocks + ch.lo),
                                     io.d_cells + ch.lo * io.ncols));
         return CRYO_OK;
     };
@@ -1449,7 +1471,7 @@ static int group_pass(cryo_codec *c, int method, const uint8_t *d_src, const uin
         }
         uint8_t *side_rec = ch.own, *side_cell = ch.own + ch.K * S * sizeof(cryo_group_rec);
         HIP_TRY(c, cryo::launch_group(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.sd.d_atts, io.sd.d_keys, io.sd.nkeys, slots, io.nby,
-                                      io.ncols, io.sd.max_att, io.sd.bytes_keys, (uint4 *)(io.d_blocks + ch.lo), side_rec, side_cell, io.d_total,
+                                      io.ncols, io.sd.max_att, io.sd.table_keys, (uint4 *)(io.d_blocks + ch.lo), side_rec, side_cell, io.d_total,
                                       io.d_groups, io.d_cells, io.group_cap, c->lz4_opts.cus));
         return CRYO_OK;
     };
@@ -1528,7 +1550,7 @@ static int project_pass(cryo_codec *c, int method, const uint8_t *d_src, const u
         }
         uint8_t *side_rec = ch.own, *side_rows = ch.own + ch.K * S * sizeof(cryo_project_rec);
         HIP_TRY(c, cryo::launch_project(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.sd.d_atts, io.sd.d_keys, io.sd.nkeys, tab,
-                                        io.pt.ncols, io.pt.row_bytes, io.sd.max_att, io.sd.bytes_keys, (uint4 *)(io.d_blocks + ch.lo),
+                                        io.pt.ncols, io.pt.row_bytes, io.sd.max_att, io.sd.table_keys, (uint4 *)(io.d_blocks + ch.lo),
                                         side_rec, side_rows, io.d_total, io.d_rec, io.rec_cap, io.d_rows, io.row_cap, c->lz4_opts.cus));
         return CRYO_OK;
     };
@@ -1736,7 +1758,7 @@ static int scan_desc_device(cryo_codec *c, const cryo_filter *f, const cryo_grou
     if (total_words) HIP_TRY(c, hipMemsetAsync(d_total, 0, total_words * sizeof(uint64_t), c->stream));
     if (n_blocks == 0) return CRYO_OK;
     sd.d_atts = f->atts; sd.d_keys = f->keys; sd.nkeys = f->nkeys;
-    return key_table_device(c, keys, f->nkeys, &sd.d_keys, &sd.bytes_keys);
+    return key_table_device(c, keys, f->nkeys, &sd.d_keys, &sd.table_keys);
 }
 
 int cryo_codec_filter_batch(cryo_codec *c, int method, const void *d_src, const uint64_t *d_src_off, const uint32_t *d_src_size,
@@ -2450,12 +2472,12 @@ int cryo_codec_fetch_blocks(cryo_codec *c, int method, const void *const *h_src,
 /* The descriptor of a host-buffer scan call: [atts 4 x natts][keys 16 x nkeys][byte-string constants][the call's extra bytes:
  * the aggregate's columns, the group's six slots], each part 16-byte aligned.  It takes the first `bytes` of c->hb_meta, where
  * the call's results follow it */
-struct ScanDescLayout { size_t t_keys = 0, t_extra = 0, bytes = 0; bool bytes_keys = false; };
+struct ScanDescLayout { size_t t_keys = 0, t_extra = 0, bytes = 0; bool table_keys = false; };
 static ScanDescLayout scan_desc_layout(const cryo_filter *f, size_t extra_bytes)
 {
     ScanDescLayout L;
     L.t_keys = ((size_t)f->natts * 4 + 15) & ~(size_t)15;
-    L.t_extra = L.t_keys + (size_t)f->nkeys * 16 + key_consts_bytes(f->keys, f->nkeys, &L.bytes_keys);
+    L.t_extra = L.t_keys + (size_t)f->nkeys * 16 + key_consts_bytes(f->keys, f->nkeys, &L.table_keys);
     L.bytes = L.t_extra + extra_bytes;
     return L;
 }
@@ -2474,7 +2496,7 @@ static int scan_desc_upload(cryo_codec *c, const void *const *h_src, const uint3
     if (L.bytes > L.t_extra) memcpy(pin + L.t_extra, extra, L.bytes - L.t_extra);
     HIP_TRY(c, hipMemcpyAsync(c->hb_meta, pin, L.bytes, hipMemcpyHostToDevice, c->stream));
     c->xfer_ctr.h2d_bytes += L.bytes;
-    sd.d_atts = c->hb_meta; sd.d_keys = c->hb_meta + L.t_keys; sd.nkeys = f->nkeys; sd.max_att = max_att; sd.bytes_keys = L.bytes_keys;
+    sd.d_atts = c->hb_meta; sd.d_keys = c->hb_meta + L.t_keys; sd.nkeys = f->nkeys; sd.max_att = max_att; sd.table_keys = L.table_keys;
     return CRYO_OK;
 }
 

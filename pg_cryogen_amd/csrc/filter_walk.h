@@ -5,7 +5,8 @@
  * scan").  One statement of the walk: the filter instantiates it without capture, and the capture costs it nothing (the same
  * registers, no scratch).  The number of capture slots is a template parameter: four for the aggregate, six for the grouping (two
  * group columns and four aggregate columns).  Byte-string keys (CRYO_KEY_BYTES) are a second instantiation, chosen by the host when
- * a descriptor has one: a descriptor of integer keys and null tests alone runs the code it ran before those keys existed.
+ * a descriptor has one: a descriptor of integer keys and null tests alone runs the code it ran before those keys existed.  Set keys
+ * (CRYO_OP_IN, CRYO_OP_NOT_IN) live in that second instantiation too: the host chooses it when a descriptor has either kind.
  */
 #pragma once
 #include <hip/hip_runtime.h>
@@ -19,6 +20,9 @@ constexpr uint32_t kFilterNoMatch = 0xFFFFu;  /* inside the kernels only: a good
 constexpr uint32_t kKeyBytes = 16u;           /* CRYO_KEY_BYTES */
 constexpr uint32_t kWalkNoBytes = 0xFFFFFFFFu; /* inside the walk only: the payload length of a varlena without in-line bytes */
 constexpr uint32_t kOpLt = 1, kOpLe = 2, kOpEq = 3, kOpGe = 4, kOpGt = 5, kOpNe = 6, kOpIsNull = 7, kOpNotNull = 8;
+constexpr uint32_t kOpIn = 9, kOpNotIn = 10;  /* set keys: rsv the members, value their address in the key table */
+constexpr uint32_t kSetLinear = 8u;           /* sets up to this size are scanned, larger ones searched; where the scan stops paying
+                                                 is not measured: tools/set_key_cost.py reports both sides of this figure */
 constexpr uint32_t kAggMaxCols = 4u;
 
 struct FilterAtt { int16_t attlen; uint8_t attalign, rsv; };                           /* cryo_att */
@@ -31,7 +35,7 @@ static_assert(sizeof(FilterAtt) == 4 && sizeof(FilterKey) == 16 && sizeof(AggCol
 template <uint32_t SLOTS> struct WalkCaptureN { int64_t v[SLOTS]; uint32_t has; };
 using WalkCapture = WalkCaptureN<kAggMaxCols>; /* the aggregate's */
 template <class T> struct WalkPlain { using type = T; }; /* keeps SLOTS out of deduction: the filter passes a null capture */
-template <bool BYTES> struct WalkKeys {};                /* a tag: whether the keys may hold a CRYO_KEY_BYTES entry */
+template <bool BYTES> struct WalkKeys {};                /* a tag: whether the keys may hold a CRYO_KEY_BYTES entry or a set key */
 
 __device__ inline bool filter_compare(uint32_t op, int64_t v, int64_t k)
 {
@@ -88,13 +92,39 @@ __device__ inline int32_t walk_bytes_sign(const uint8_t *__restrict__ p, uint32_
     return c;
 }
 
+/* Whether v is among the n >= 1 members at set: distinct, ascending as signed 64-bit integers, 8-byte aligned (the host's copy).
+ * Up to kSetLinear members are read one per trip at addresses that depend on the trip alone -- uniform loads, as the byte-string
+ * constant's words.  A larger set is searched: [lo, lo + len) always holds the last member <= v if there is one, lo + len <= n,
+ * and a trip halves len (rounding up) with one 8-byte load per lane at lo + len / 2 < lo + len; after ceil(log2 n) trips len is 1
+ * and set[lo] is that member or, when every member is above v, the first.  Either way the trip count is n's, the same in every
+ * lane, every index is below n, and a lane that is not `on` loads nothing. */
+__device__ inline bool walk_set_has(const int64_t *__restrict__ set, uint32_t n, int64_t v, bool on)
+{
+    if (n <= kSetLinear) { /* uniform */
+        bool hit = false;
+        for (uint32_t i = 0; i < n; i++) {
+            const int64_t m = set[i]; /* uniform */
+            hit = hit || m == v;
+        }
+        return on && hit;
+    }
+    uint32_t lo = 0;
+    for (uint32_t len = n; len > 1u;) {
+        const uint32_t half = len >> 1;
+        if (on && set[lo + half] <= v) lo += half;
+        len -= half;
+    }
+    return on && set[lo] == v;
+}
+
 /* The verdict on one tuple of len bytes at t (8-byte aligned): 0 a match, kFilterNoMatch, kFilterTuple or -- BYTES alone --
  * kFilterUndecided.  `live` is false in
  * lanes without a tuple: they make the same trips and load nothing.  Invariant of the walk: hoff + o <= len.  CAPTURE: the walk
  * also notes the value of each of the ncols <= SLOTS columns cols[] names (their att <= max_att, attlen the type's size and
  * attalign at least that: the aggregate's argument rule; an att of 0 names no column) in *cap; cols is read at addresses that
  * depend on the loop counters only.  BYTES: a key of type kKeyBytes compares the column's in-line payload with the rsv bytes at
- * value (walk_bytes_sign); without BYTES no key has that type.  NARROW: a captured column may have attlen 1 (the projection's
+ * value (walk_bytes_sign), and a key of op kOpIn / kOpNotIn tests the column's value against the rsv sorted members at value
+ * (walk_set_has); without BYTES no key has that type or those ops.  NARROW: a captured column may have attlen 1 (the projection's
  * argument rule: attlen 1, 2, 4 or 8 and attalign at least that). */
 template <bool CAPTURE, uint32_t SLOTS = kAggMaxCols, bool BYTES = false, bool NARROW = false>
 __device__ inline uint32_t walk_tuple(const uint8_t *__restrict__ t, uint32_t len, bool live, const FilterAtt *__restrict__ atts,
@@ -160,7 +190,12 @@ __device__ inline uint32_t walk_tuple(const uint8_t *__restrict__ t, uint32_t le
             if (key.att != col) continue;
             if (key.op == kOpIsNull) pass = pass && isnull;
             else if (key.op == kOpNotNull) pass = pass && !isnull;
-            else if (BYTES && key.type == kKeyBytes) {
+            else if (BYTES && key.op >= kOpIn) {
+                /* the column rule is the comparison key's: the same load.  Never undecided; false on a NULL column */
+                const int64_t v = val ? walk_value(t + pos, a.attlen) : 0;
+                const bool in = walk_set_has(reinterpret_cast<const int64_t *>(key.value), key.rsv, v, val);
+                pass = pass && val && in == (key.op == kOpIn);
+            } else if (BYTES && key.type == kKeyBytes) {
                 /* the column is a varlena (the argument rule) and [pos, pos + size) lies below len */
                 const bool inl = val && head != kWalkNoBytes;
                 const int32_t c = walk_bytes_sign(t + pos + (inl ? head : 0u), inl ? size - head : 0u, inl,

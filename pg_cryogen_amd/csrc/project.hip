@@ -102,9 +102,28 @@ k_project_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B
                     }
                     const uint32_t r = n_match + (uint32_t)__popcll(mm & below); /* below n <= side_stride */
                     uint2 *row = out_rows + (uint64_t)r * row_words;
+                    if (BYTES) {
+                        /* with BYTES the walk leaves no scalar registers for eight loop-invariant compares q < row_words kept
+                         * as lane masks across the item loop (the compiler spilled eleven of them to vector lanes): one scalar
+                         * branch on the row's length, 1 .. 8 words, and the stores from the last word down */
+#define CRYO_ROW_WORD(q) row[q] = make_uint2((uint32_t)word[q], (uint32_t)(word[q] >> 32))
+                        switch (row_words) {
+                        case 0: break;
+                        default: CRYO_ROW_WORD(7); [[fallthrough]];
+                        case 7: CRYO_ROW_WORD(6); [[fallthrough]];
+                        case 6: CRYO_ROW_WORD(5); [[fallthrough]];
+                        case 5: CRYO_ROW_WORD(4); [[fallthrough]];
+                        case 4: CRYO_ROW_WORD(3); [[fallthrough]];
+                        case 3: CRYO_ROW_WORD(2); [[fallthrough]];
+                        case 2: CRYO_ROW_WORD(1); [[fallthrough]];
+                        case 1: CRYO_ROW_WORD(0);
+                        }
+#undef CRYO_ROW_WORD
+                    } else {
 #pragma unroll
-                    for (uint32_t q = 0; q < kProjectMaxCols; q++)
-                        if (q < row_words) row[q] = make_uint2((uint32_t)word[q], (uint32_t)(word[q] >> 32));
+                        for (uint32_t q = 0; q < kProjectMaxCols; q++)
+                            if (q < row_words) row[q] = make_uint2((uint32_t)word[q], (uint32_t)(word[q] >> 32));
+                    }
                 }
                 n_match += (uint32_t)__popcll(mm);
                 n_bad += (uint32_t)__popcll(mb);
@@ -170,7 +189,7 @@ k_project_copy(uint32_t cnt, uint32_t side_stride, uint32_t row_words, const uin
 
 hipError_t launch_project(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
                           const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_cols,
-                          uint32_t ncols, uint32_t row_bytes, uint32_t max_att, bool bytes_keys, uint4 *d_blocks, void *d_side_rec,
+                          uint32_t ncols, uint32_t row_bytes, uint32_t max_att, bool table_keys, uint4 *d_blocks, void *d_side_rec,
                           void *d_side_rows, uint64_t *d_running, void *d_rec, uint64_t rec_cap, void *d_rows, uint64_t row_cap, int cus)
 {
     if (cnt == 0) return hipSuccess;
@@ -182,7 +201,7 @@ hipError_t launch_project(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stri
         (rec_cap > 0u && !d_rec) || (row_cap > 0u && !d_rows))
         return hipErrorInvalidValue;
     const uint32_t stride = filter_side_stride(block_size), row_words = row_bytes / 8u;
-    hipLaunchKernelGGL(bytes_keys ? k_project_block<true> : k_project_block<false>, dim3((cnt + 3u) / 4u), dim3(256), 0, s, d_dec,
+    hipLaunchKernelGGL(table_keys ? k_project_block<true> : k_project_block<false>, dim3((cnt + 3u) / 4u), dim3(256), 0, s, d_dec,
                        dec_stride, block_size, cnt, d_dec_status, (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys,
                        (const AggCol *)d_cols, ncols, max_att, row_words, stride, d_blocks, (uint2 *)d_side_rec, (uint2 *)d_side_rows);
     hipError_t e = hipGetLastError();
