@@ -370,7 +370,8 @@ int cryo_codec_fetch_batch(cryo_codec *c, int method, const void *d_src, const u
  * scan keys in cryo_beginscan and ignores them (pg_cryogen.c:185-211), so every decoded byte crosses PCIe and the executor throws
  * most of them away.  Here the test runs where the decoded block lies (pg_cryogen_amd/host/filter.h walks a relation with it).
  * A call names n_blocks stored streams as cryo_codec_check_batch does and one descriptor: the relation's columns as far as the
- * keys need them (pg_attribute.attlen, and attalign as 1 / 2 / 4 / 8 bytes) and up to four scan keys, which are ANDed.
+ * keys need them (pg_attribute.attlen, and attalign as 1 / 2 / 4 / 8 bytes) and up to four scan keys, which are ANDed -- or,
+ * under CRYO_FILTER_TRUTH, combined by a truth table ("Truth table" below).
  *
  * Descriptor.  CRYO_E_ARG when: natts is 0 or above 1600 (MaxHeapAttributeNumber), or nkeys above 4 (nkeys == 0 is allowed:
  * every well-formed tuple matches); a key's att outside 1 .. natts; an attlen of 0, below -1 (cstring is not supported) or above
@@ -399,6 +400,23 @@ int cryo_codec_fetch_batch(cryo_codec *c, int method, const void *d_src, const u
  * members, ascending as signed 64-bit integers and 8-byte aligned; the caller's key array and lists are only read.  The binder's
  * part, not enforced here: drop NULL members from an IN list, never push down a NOT IN whose list holds a NULL, and fold an
  * empty list itself.
+ * Truth table.  CRYO_FILTER_TRUTH (4) in flags: the keys are not ANDed but combined by any tree of AND and OR (WHERE country =
+ * 'de' OR app_id = 3; WHERE ts >= a AND ts < b AND (campaign_id IN (..) OR source IS NULL)).  f->rsv is then not reserved: it
+ * holds the truth table W of the tree over its nkeys leaves.  Bit m of W, 0 <= m < 2^nkeys, says whether a tuple matches when
+ * exactly the keys whose index bit is set in m are true: bit k of m is keys[k].  Four keys have 16 combinations, so every such
+ * tree is 16 bits.  Without the flag nothing changes: rsv != 0 is refused and the keys are ANDed.  Flag 2 stays unknown and
+ * refused.  The filter takes CRYO_FILTER_TRUTH alone or with CRYO_FILTER_COUNT_ONLY; the aggregate, the grouping and the
+ * projection take flags == 0 or flags == CRYO_FILTER_TRUTH and refuse CRYO_FILTER_COUNT_ONLY as before.  CRYO_E_ARG with the
+ * flag set when: nkeys == 0; W == 0 (a constant false is the binder's to fold); a bit at or above 2^nkeys is set; or W is not
+ * monotone -- W is monotone when W[m] implies W[m | 1 << k] for every k < nkeys.  The all-ones table (constant true) and tables
+ * that ignore a key are valid; an ignored key is still evaluated, the walk still goes to the highest key column for every
+ * tuple, and the TUPLE rule is unchanged.  The key count stays four.
+ * Why monotone: every key here is already false on NULL, while SQL's a OR b is three-valued.  For a formula built of AND and OR
+ * alone, Kleene's result is TRUE exactly when the formula is true with every unknown leaf replaced by false, which is why W may
+ * be indexed by "key is true" bits alone; and exactly the formulas of AND and OR have monotone tables.  NOT is the binder's to
+ * push into the leaves (<>, >=, CRYO_OP_NOT_IN, CRYO_OP_NOTNULL), which is exact under three-valued logic for every op here; the
+ * NULL caveats of set keys stand as they are.  cryo_filter_truth_dnf (pg_cryogen_amd/host/filter.h) builds W from a disjunctive
+ * normal form and is monotone by construction: binders use it and do not hand-roll tables.
  *
  * Per block (names as in the check's rules above: lower, upper, n, off_i, len_i, MAXALIGN, B), the first failing rule wins:
  *   CRYO_FETCH_STREAM (1), CRYO_FETCH_HEADER (2)   exactly the fetch's; no item is examined, the block has no record
@@ -406,7 +424,9 @@ int cryo_codec_fetch_batch(cryo_codec *c, int method, const void *d_src, const u
  *     CRYO_FETCH_ITEM (3)    the item fails the fetch's ITEM rule (len == 0, off % 8 != 0, off < upper, off + MAXALIGN(len) > B)
  *     CRYO_FILTER_TUPLE (8)  the tuple fails a tuple rule below
  *     CRYO_FILTER_UNDECIDED (9)  no key is false on the tuple, and a byte-string key met a value whose bytes are not in it
- *     the items that pass these and pass every key are the block's matches; the rest is silently no match
+ *                                (under CRYO_FILTER_TRUTH: the keys that are decided do not decide W, see the verdict below)
+ *     the items that pass these and pass every key (under CRYO_FILTER_TRUTH: and match by W) are the block's matches; the rest
+ *     is silently no match
  *   CRYO_FETCH_OVERLAP (7)   the MAXALIGNed lengths of the matches sum to more than B - upper: the block delivers no tuple and no
  *                            match record (n_match = 0); its bad items keep their records
  *
@@ -450,6 +470,12 @@ int cryo_codec_fetch_batch(cryo_codec *c, int method, const void *d_src, const u
  *   The verdict on a tuple, the first rule that applies: CRYO_FILTER_TUPLE if the walk fails anywhere up to the highest column
  *   it visits (it still goes that far whatever the keys said); no match if some key is decidedly false (false AND unknown is
  *   false); CRYO_FILTER_UNDECIDED if a byte-string key met an undecided value; otherwise a match.
+ *   Under CRYO_FILTER_TRUTH the verdict is sharper.  With t the mask of keys that are true on the tuple and u the mask of keys
+ *   that are undecided on it (a byte-string key on a value compressed in line or external; t & u == 0), the first rule that
+ *   applies: CRYO_FILTER_TUPLE as above; a match if W[t] -- true even if every undecided key were false; no match if not
+ *   W[t | u] -- false even if every undecided key were true; otherwise CRYO_FILTER_UNDECIDED.  So country = 'de' OR app_id = 3
+ *   with a toasted country and app_id = 3 is a match, not a bad item.  With the AND table W = 1 << (2^nkeys - 1) this is the
+ *   rule without the flag, word for word: W[t] says every key is true, not W[t | u] that some key is decidedly false.
  *
  * Results.  One cryo_filter_block per block, in call order.  One cryo_filter_rec per match {pos, 0, len} and one per bad item
  * {pos, CRYO_FETCH_ITEM, CRYO_FILTER_TUPLE or CRYO_FILTER_UNDECIDED, 0} -- a damaged tuple is never silently absent from a scan,
@@ -478,11 +504,12 @@ typedef enum {
 } cryo_key_op;
 typedef struct { uint16_t att; uint8_t type, op; uint32_t rsv; int64_t value; } cryo_scan_key; /* att 1-based; 16 bytes */
 typedef struct {
-    uint32_t natts, nkeys, flags, rsv;
+    uint32_t natts, nkeys, flags, rsv; /* rsv: 0, or under CRYO_FILTER_TRUTH the truth table W */
     const cryo_att *atts;      /* natts entries */
     const cryo_scan_key *keys; /* nkeys entries (may be null when nkeys == 0) */
 } cryo_filter;
 #define CRYO_FILTER_COUNT_ONLY 1u /* per-block table only: no records, no tuples */
+#define CRYO_FILTER_TRUTH 4u      /* f->rsv is a truth table over the keys, which are not ANDed but combined by it */
 #define CRYO_FILTER_TUPLE 8u      /* a record's status beside CRYO_FETCH_ITEM: the tuple breaks a tuple rule */
 #define CRYO_FILTER_UNDECIDED 9u  /* a record's status: a byte-string key met a compressed or external value */
 #define CRYO_KEY_BYTES_MAX 256u   /* the longest constant of a CRYO_KEY_BYTES key */
@@ -520,8 +547,8 @@ int cryo_codec_filter_batch(cryo_codec *c, int method, const void *d_src, const 
  * keys, unchanged) and an aggregate descriptor *agg: ncols columns, each {att, type}, whose values are reduced over the block's
  * matches.
  *
- * Descriptor.  CRYO_E_ARG when: *f breaks one of the filter's descriptor rules above; f->flags != 0 (CRYO_FILTER_COUNT_ONLY has
- * no meaning here); ncols is 0 or above 4 (a bare count is CRYO_FILTER_COUNT_ONLY's job); a column's att outside 1 .. f->natts; a
+ * Descriptor.  CRYO_E_ARG when: *f breaks one of the filter's descriptor rules above; f->flags is neither 0 nor
+ * CRYO_FILTER_TRUTH (CRYO_FILTER_COUNT_ONLY has no meaning here); ncols is 0 or above 4 (a bare count is CRYO_FILTER_COUNT_ONLY's job); a column's att outside 1 .. f->natts; a
  * column's type not a cryo_key_type; the column's attlen not the type's size, or its attalign below its attlen (the comparison
  * key's rules); a reserved field (agg->rsv, a column's rsv or rsv2) that is not zero.  The same column may be named twice, and it
  * may also carry a key.
@@ -575,7 +602,7 @@ int cryo_codec_agg_batch(cryo_codec *c, int method, const void *d_src, const uin
  * A call names n_blocks stored streams as cryo_codec_check_batch does, the filter's descriptor *f (unchanged), a group
  * descriptor *grp: nby columns, each {att, type}, and an aggregate descriptor *agg (may be NULL): ncols columns.
  *
- * Descriptors.  CRYO_E_ARG when: *f breaks one of the filter's descriptor rules above; f->flags != 0; nby is 0 or above 2; a
+ * Descriptors.  CRYO_E_ARG when: *f breaks one of the filter's descriptor rules above; f->flags is neither 0 nor CRYO_FILTER_TRUTH; nby is 0 or above 2; a
  * group column breaks a rule of an aggregate column above (att outside 1 .. f->natts; a type that is not a cryo_key_type; the
  * column's attlen not the type's size, or its attalign below its attlen; rsv or rsv2 not zero); grp->rsv not zero; ncols above 4;
  * with ncols > 0, anything cryo_codec_agg_batch refuses in *agg.  ncols == 0 is allowed here -- agg NULL, or agg->ncols 0 with
@@ -640,7 +667,7 @@ int cryo_codec_group_batch(cryo_codec *c, int method, const void *d_src, const u
  * Out of scope: varlena columns in the projection (text stays with the filter), fixed columns wider than 8 bytes (uuid, name),
  * expressions, more than 8 columns, and a combined project-and-aggregate call.
  *
- * Descriptor.  CRYO_E_ARG when: *f breaks one of the filter's descriptor rules above; f->flags != 0 (a bare count is
+ * Descriptor.  CRYO_E_ARG when: *f breaks one of the filter's descriptor rules above; f->flags is neither 0 nor CRYO_FILTER_TRUTH (a bare count is
  * CRYO_FILTER_COUNT_ONLY's job); ncols is 0 or above 8; a column's att outside 1 .. f->natts; the column's attlen not 1, 2, 4 or
  * 8, or its attalign below its attlen (varlena and wider fixed columns are not projected); a reserved field (prj->rsv, a column's
  * rsv or rsv2) that is not zero.  The same column may be named twice, and it may also carry a key.

@@ -43,6 +43,8 @@ FETCH_RESULT = np.dtype([("status", "<u4"), ("len", "<u4"), ("off", "<u8")])
 FILTER_TUPLE = 8
 FILTER_UNDECIDED = 9        # a record's status: a byte-string key met a compressed or external value
 FILTER_COUNT_ONLY = 1
+FILTER_MAX_KEYS = 4
+FILTER_TRUTH = 4            # the descriptor's rsv is a truth table over its keys (truth_dnf), not reserved
 KEY_INT2, KEY_INT4, KEY_INT8 = 1, 2, 3
 KEY_BYTES = 16              # a byte string: the key's value is bytes, compared unsigned, then by length
 KEY_BYTES_MAX = 256
@@ -300,18 +302,36 @@ def fetch_blocks_call(fn, handle, chk, method, comps, block_size, requests, dst=
     return res[:n_req], dst, total.value
 
 
-def filter_desc(atts, keys=(), flags=0):
+def truth_dnf(terms, nkeys):
+    """the truth table (CRYO_FILTER_TRUTH) of a disjunctive normal form over nkeys keys: each term a mask of the keys that are
+    ANDed (bit k: keys[k]), the terms ORed.  Bit m of the result is set when some term lies within m, so the table is monotone.
+    0 -- no valid table -- for no term, an empty term, a term beyond nkeys, or nkeys outside 1 .. 4 (cryo_filter_truth_dnf,
+    host/filter.h)"""
+    terms = [int(t) for t in terms]
+    if not 1 <= nkeys <= FILTER_MAX_KEYS or not terms or any(t <= 0 or t >> nkeys for t in terms):
+        return 0
+    return sum(1 << m for m in range(1 << nkeys) if any(t & m == t for t in terms))
+
+
+def truth_flags(flags=0, truth=None):
+    """(flags, rsv) of a descriptor: with a truth table FILTER_TRUTH is set and rsv is the table; without one rsv is 0"""
+    return (flags, 0) if truth is None else (flags | FILTER_TRUTH, int(truth))
+
+
+def filter_desc(atts, keys=(), flags=0, truth=None):
     """the descriptor of a filter call as host arrays: atts a list of (attlen, attalign), keys a list of (att, type, op, value)
     (att 1-based; type KEY_*, op OP_*; the value of a KEY_BYTES comparison is a bytes object, that of an OP_IN / OP_NOT_IN key
     a sequence of ints).  Returns (CryoFilter, atts array,
     keys array); the struct points into the two arrays, which the caller keeps alive.  The constants of KEY_BYTES keys live in
-    one uint8 array the struct holds (f.consts), so they live as long as it does"""
+    one uint8 array the struct holds (f.consts), so they live as long as it does.  truth: a truth table over the keys (truth_dnf):
+    FILTER_TRUTH is set in flags and the table goes into rsv"""
     a = np.zeros(max(len(atts), 1), FILTER_ATT)
     for i, (attlen, attalign) in enumerate(atts):
         a[i] = (attlen, attalign, 0)
     k, consts = _filter_keys(keys)
     _rebase_keys(k, keys, consts.ctypes.data)
-    f = CryoFilter(len(atts), len(keys), flags, 0, a.ctypes.data, k.ctypes.data if len(keys) else None)
+    flags, rsv = truth_flags(flags, truth)
+    f = CryoFilter(len(atts), len(keys), flags, rsv, a.ctypes.data, k.ctypes.data if len(keys) else None)
     f.consts = consts
     return f, a, k
 
@@ -357,10 +377,12 @@ def _rebase_keys(k, keys, base):
             k[i]["value"] = base + int(k[i]["value"]) if (key[3] is not None and len(key[3])) else 0
 
 
-def filter_desc_device(atts, keys=()):
+def filter_desc_device(atts, keys=(), flags=0, truth=None):
     """the device form of a descriptor with KEY_BYTES keys or set keys: returns (atts array, keys array, consts array, rebase).  The caller
     uploads consts to device memory at some address d and calls rebase(d), which sets every KEY_BYTES key's and set key's value to the
-    device address of its constant or list (they lie back to back in consts, at any alignment); then it uploads the keys"""
+    device address of its constant or list (they lie back to back in consts, at any alignment); then it uploads the keys.
+    rebase.flags and rebase.rsv are the struct's two words (truth_flags of flags and truth), which the *_batch calls take as
+    flags and truth"""
     a = np.zeros(max(len(atts), 1), FILTER_ATT)
     for i, (attlen, attalign) in enumerate(atts):
         a[i] = (attlen, attalign, 0)
@@ -371,6 +393,7 @@ def filter_desc_device(atts, keys=()):
         k["value"] = offs
         _rebase_keys(k, keys, int(d_consts))
         return k
+    rebase.flags, rebase.rsv = truth_flags(flags, truth)
     return a, k, consts, rebase
 
 
@@ -687,11 +710,13 @@ class Codec:
         return fetch_blocks_call(self.L.cryo_codec_fetch_blocks, self.h, self._chk, method, comps, block_size, requests, dst)
 
     def filter_batch(self, method, d_src, d_off, d_sizes, block_size, n, natts, d_atts, nkeys, d_keys, flags, d_dst, dst_cap,
-                     d_rec, rec_cap, d_blocks, d_total):
+                     d_rec, rec_cap, d_blocks, d_total, truth=None):
         """test the keys (d_keys: FILTER_KEY, d_atts: FILTER_ATT, device arrays) on every tuple of the n stored blocks: one
         FILTER_BLOCK row per block in d_blocks, one FILTER_REC per match and per bad item in d_rec, the matches packed into
-        d_dst, the two totals {bytes, records} in d_total (2 x u64).  Asynchronous once the descriptor is read back."""
-        f = CryoFilter(natts, nkeys, flags, 0, d_atts.ptr if d_atts else None, d_keys.ptr if d_keys else None)
+        d_dst, the two totals {bytes, records} in d_total (2 x u64).  truth: a truth table over the keys (truth_dnf; FILTER_TRUTH
+        is set for it).  Asynchronous once the descriptor is read back."""
+        flags, rsv = truth_flags(flags, truth)
+        f = CryoFilter(natts, nkeys, flags, rsv, d_atts.ptr if d_atts else None, d_keys.ptr if d_keys else None)
         self._chk(self.L.cryo_codec_filter_batch(self.h, method, d_src.ptr, d_off.ptr, d_sizes.ptr, block_size, n, C.byref(f),
                                                  d_dst.ptr if d_dst else None, dst_cap, d_rec.ptr if d_rec else None, rec_cap,
                                                  d_blocks.ptr if d_blocks else None, d_total.ptr if d_total else None),
@@ -703,11 +728,11 @@ class Codec:
         return filter_blocks_call(self.L.cryo_codec_filter_blocks, self.h, self._chk, method, comps, block_size, desc, dst, rec)
 
     def agg_batch(self, method, d_src, d_off, d_sizes, block_size, n, natts, d_atts, nkeys, d_keys, ncols, d_cols, d_blocks,
-                  d_cells):
+                  d_cells, truth=None):
         """test the keys on every tuple of the n stored blocks and reduce the ncols columns d_cols names (AGG_COL; d_keys:
         FILTER_KEY, d_atts: FILTER_ATT, device arrays) over each block's matches: one AGG_BLOCK row per block in d_blocks, ncols
-        AGG_CELL cells per block in d_cells.  Asynchronous once the descriptors are read back."""
-        f = CryoFilter(natts, nkeys, 0, 0, d_atts.ptr if d_atts else None, d_keys.ptr if d_keys else None)
+        AGG_CELL cells per block in d_cells.  truth: as for filter_batch.  Asynchronous once the descriptors are read back."""
+        f = CryoFilter(natts, nkeys, *truth_flags(0, truth), d_atts.ptr if d_atts else None, d_keys.ptr if d_keys else None)
         a = CryoAgg(ncols, 0, d_cols.ptr if d_cols else None)
         self._chk(self.L.cryo_codec_agg_batch(self.h, method, d_src.ptr, d_off.ptr, d_sizes.ptr, block_size, n, C.byref(f),
                                               C.byref(a), d_blocks.ptr if d_blocks else None, d_cells.ptr if d_cells else None),
@@ -719,13 +744,13 @@ class Codec:
         return agg_blocks_call(self.L.cryo_codec_agg_blocks, self.h, self._chk, method, comps, block_size, desc, adesc)
 
     def group_batch(self, method, d_src, d_off, d_sizes, block_size, n, natts, d_atts, nkeys, d_keys, nby, d_by, ncols, d_cols,
-                    d_blocks, d_groups, group_cap, d_cells, d_total):
+                    d_blocks, d_groups, group_cap, d_cells, d_total, truth=None):
         """test the keys on every tuple of the n stored blocks, partition each block's matches by the nby columns d_by names and
         reduce the ncols columns d_cols names per group (both AGG_COL; d_keys: FILTER_KEY, d_atts: FILTER_ATT, device arrays):
         one GROUP_BLOCK row per block in d_blocks, one GROUP_REC per group in d_groups and ncols AGG_CELL per group in d_cells (at
         most group_cap groups are written), the call's number of groups in d_total (u64).  ncols 0: d_cols and d_cells may be
-        None.  Asynchronous once the descriptors are read back."""
-        f = CryoFilter(natts, nkeys, 0, 0, d_atts.ptr if d_atts else None, d_keys.ptr if d_keys else None)
+        None.  truth: as for filter_batch.  Asynchronous once the descriptors are read back."""
+        f = CryoFilter(natts, nkeys, *truth_flags(0, truth), d_atts.ptr if d_atts else None, d_keys.ptr if d_keys else None)
         g = CryoGroup(nby, 0, d_by.ptr if d_by else None)
         a = CryoAgg(ncols, 0, d_cols.ptr if d_cols else None)
         self._chk(self.L.cryo_codec_group_batch(self.h, method, d_src.ptr, d_off.ptr, d_sizes.ptr, block_size, n, C.byref(f),
@@ -741,13 +766,13 @@ class Codec:
                                  group_cap)
 
     def project_batch(self, method, d_src, d_off, d_sizes, block_size, n, natts, d_atts, nkeys, d_keys, ncols, d_cols, d_rows,
-                      row_cap, d_rec, rec_cap, d_blocks, d_total):
+                      row_cap, d_rec, rec_cap, d_blocks, d_total, truth=None):
         """test the keys on every tuple of the n stored blocks and copy the ncols fixed-width columns d_cols names (PROJECT_COL;
         d_keys: FILTER_KEY, d_atts: FILTER_ATT, device arrays) of every match into a row: one PROJECT_BLOCK row per block in
         d_blocks, one PROJECT_REC per match and per bad item in d_rec, one row of row_bytes per match in d_rows (at most row_cap
-        rows and rec_cap records are written), the two totals {rows, records} in d_total (2 x u64).  Asynchronous once the
+        rows and rec_cap records are written), the two totals {rows, records} in d_total (2 x u64).  truth: as for filter_batch.  Asynchronous once the
         descriptors are read back and the column table is in place."""
-        f = CryoFilter(natts, nkeys, 0, 0, d_atts.ptr if d_atts else None, d_keys.ptr if d_keys else None)
+        f = CryoFilter(natts, nkeys, *truth_flags(0, truth), d_atts.ptr if d_atts else None, d_keys.ptr if d_keys else None)
         p = CryoProject(ncols, 0, d_cols.ptr if d_cols else None)
         self._chk(self.L.cryo_codec_project_batch(self.h, method, d_src.ptr, d_off.ptr, d_sizes.ptr, block_size, n, C.byref(f),
                                                   C.byref(p), d_rows.ptr if d_rows else None, row_cap,

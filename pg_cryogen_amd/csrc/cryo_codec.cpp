@@ -1146,7 +1146,8 @@ namespace {
 struct ScanDesc {
     const void *d_atts = nullptr, *d_keys = nullptr; /* device */
     uint32_t nkeys = 0, max_att = 0;                 /* max_att: the highest column the walk has to reach */
-    bool table_keys = false;                         /* d_keys is a key table: some key is a byte-string key or a set key */
+    uint32_t truth = 0;                              /* 0: the keys are ANDed by the kernels' <false> instantiation; otherwise the
+                                                        truth table of the <true> one (scan_truth) */
 };
 struct FilterIo {
     ScanDesc sd;
@@ -1166,13 +1167,34 @@ struct FilterIo {
 };
 } // namespace
 
+/* CRYO_FILTER_TRUTH's rules for the table W of a descriptor of nkeys <= 4 keys (include/cryo_codec.h): some key, some bit, no bit
+ * at or above 2^nkeys, and monotone -- W[m] implies W[m | 1 << k] for every k < nkeys */
+static bool truth_table_ok(uint32_t W, uint32_t nkeys)
+{
+    if (nkeys == 0 || W == 0 || (W >> (1u << nkeys)) != 0) return false;
+    for (uint32_t m = 0; m < (1u << nkeys); m++)
+        for (uint32_t k = 0; k < nkeys; k++)
+            if (((W >> m) & 1u) && !((W >> (m | 1u << k)) & 1u)) return false;
+    return true;
+}
+
+/* what the kernels get of a (valid) descriptor's combination of keys: the caller's table under CRYO_FILTER_TRUTH; without the
+ * flag the AND table when a key needs the <true> instantiation (table_keys), which has that one verdict path, and 0 -- the
+ * <false> instantiation, the code a flag-less descriptor of integer keys and null tests has always run -- otherwise */
+static uint32_t scan_truth(const cryo_filter *f, bool table_keys)
+{
+    if (f->flags & CRYO_FILTER_TRUTH) return f->rsv;
+    return table_keys ? 1u << ((1u << f->nkeys) - 1u) : 0u; /* table_keys: nkeys is 1 .. 4 */
+}
+
 /* the descriptor's rules (include/cryo_codec.h); atts and keys are host memory here.  *max_att: the highest key column */
 static bool filter_desc_ok(const cryo_filter *f, const cryo_att *atts, const cryo_scan_key *keys, uint32_t *max_att)
 {
     *max_att = 0;
-    if (!f || f->natts == 0 || f->natts > CRYO_FILTER_MAX_ATTS || f->nkeys > CRYO_FILTER_MAX_KEYS || f->rsv != 0 ||
-        (f->flags & ~CRYO_FILTER_COUNT_ONLY) != 0 || !atts || (f->nkeys > 0 && !keys))
+    if (!f || f->natts == 0 || f->natts > CRYO_FILTER_MAX_ATTS || f->nkeys > CRYO_FILTER_MAX_KEYS ||
+        (f->flags & ~(CRYO_FILTER_COUNT_ONLY | CRYO_FILTER_TRUTH)) != 0 || !atts || (f->nkeys > 0 && !keys))
         return false;
+    if ((f->flags & CRYO_FILTER_TRUTH) ? !truth_table_ok(f->rsv, f->nkeys) : f->rsv != 0) return false;
     for (uint32_t i = 0; i < f->natts; i++) {
         const cryo_att &a = atts[i];
         if (a.rsv != 0 || a.attlen == 0 || a.attlen < -1) return false; /* an int16 is never above 32767 */
@@ -1316,7 +1338,7 @@ static int filter_pass(cryo_codec *c, int method, const uint8_t *d_src, const ui
         cryo_filter_rec *st_rec = (cryo_filter_rec *)(st_dst + row * ch.K);
         if (ch.lo == 0) HIP_TRY(c, hipMemsetAsync(running, 0, 2 * sizeof(uint64_t), c->stream));
         HIP_TRY(c, cryo::launch_filter(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.sd.d_atts, io.sd.d_keys, io.sd.nkeys, io.sd.max_att,
-                                       io.sd.table_keys, io.count_only, (uint4 *)(io.d_blocks + ch.lo), side, sum, base, running,
+                                       io.sd.truth, io.count_only, (uint4 *)(io.d_blocks + ch.lo), side, sum, base, running,
                                        stage ? st_dst : io.d_dst, stage ? ch.K * row : io.dst_cap,
                                        stage ? (uint2 *)st_rec : (uint2 *)io.d_rec, stage ? ch.K * S : io.rec_cap, host,
                                        c->lz4_opts.cus));
@@ -1390,7 +1412,7 @@ static bool agg_desc_ok(const cryo_filter *f, const cryo_att *atts, const cryo_s
                         const cryo_agg_col *cols, uint32_t *max_att)
 {
     if (!filter_desc_ok(f, atts, keys, max_att)) return false;
-    if (f->flags != 0 || !agg || agg->ncols == 0 || agg->ncols > CRYO_AGG_MAX_COLS || agg->rsv != 0 || !cols) return false;
+    if ((f->flags & ~CRYO_FILTER_TRUTH) != 0 || !agg || agg->ncols == 0 || agg->ncols > CRYO_AGG_MAX_COLS || agg->rsv != 0 || !cols) return false;
     for (uint32_t j = 0; j < agg->ncols; j++)
         if (!agg_col_ok(f, atts, cols[j], max_att)) return false;
     return true;
@@ -1404,7 +1426,7 @@ static int agg_pass(cryo_codec *c, int method, const uint8_t *d_src, const uint6
     DecodePass ps(d_src, d_src_off, d_src_size, true);
     ps.run = [&](const DecodeChunk &ch) -> int {
         HIP_TRY(c, cryo::launch_agg(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.sd.d_atts, io.sd.d_keys, io.sd.nkeys, io.d_cols,
-                                    io.ncols, io.sd.max_att, io.sd.table_keys, (uint4 *)(io.d_blocks + ch.lo),
+                                    io.ncols, io.sd.max_att, io.sd.truth, (uint4 *)(io.d_blocks + ch.lo),
                                     io.d_cells + ch.lo * io.ncols));
         return CRYO_OK;
     };
@@ -1438,7 +1460,7 @@ static bool group_desc_ok(const cryo_filter *f, const cryo_att *atts, const cryo
 {
     *ncols = 0;
     if (!filter_desc_ok(f, atts, keys, max_att)) return false;
-    if (f->flags != 0 || !grp || grp->nby == 0 || grp->nby > CRYO_GROUP_MAX_BY || grp->rsv != 0 || !by) return false;
+    if ((f->flags & ~CRYO_FILTER_TRUTH) != 0 || !grp || grp->nby == 0 || grp->nby > CRYO_GROUP_MAX_BY || grp->rsv != 0 || !by) return false;
     for (uint32_t j = 0; j < grp->nby; j++)
         if (!agg_col_ok(f, atts, by[j], max_att)) return false;
     if (!agg) return true;
@@ -1471,7 +1493,7 @@ static int group_pass(cryo_codec *c, int method, const uint8_t *d_src, const uin
         }
         uint8_t *side_rec = ch.own, *side_cell = ch.own + ch.K * S * sizeof(cryo_group_rec);
         HIP_TRY(c, cryo::launch_group(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.sd.d_atts, io.sd.d_keys, io.sd.nkeys, slots, io.nby,
-                                      io.ncols, io.sd.max_att, io.sd.table_keys, (uint4 *)(io.d_blocks + ch.lo), side_rec, side_cell, io.d_total,
+                                      io.ncols, io.sd.max_att, io.sd.truth, (uint4 *)(io.d_blocks + ch.lo), side_rec, side_cell, io.d_total,
                                       io.d_groups, io.d_cells, io.group_cap, c->lz4_opts.cus));
         return CRYO_OK;
     };
@@ -1509,7 +1531,7 @@ static bool project_desc_ok(const cryo_filter *f, const cryo_att *atts, const cr
                             const cryo_project_col *cols, uint32_t *max_att, ProjectTab *pt)
 {
     if (!filter_desc_ok(f, atts, keys, max_att)) return false;
-    if (f->flags != 0 || !prj || prj->ncols == 0 || prj->ncols > CRYO_PROJECT_MAX_COLS || prj->rsv != 0 || !cols) return false;
+    if ((f->flags & ~CRYO_FILTER_TRUTH) != 0 || !prj || prj->ncols == 0 || prj->ncols > CRYO_PROJECT_MAX_COLS || prj->rsv != 0 || !cols) return false;
     *pt = ProjectTab();
     uint32_t end = 0;
     for (uint32_t j = 0; j < prj->ncols; j++) {
@@ -1550,7 +1572,7 @@ static int project_pass(cryo_codec *c, int method, const uint8_t *d_src, const u
         }
         uint8_t *side_rec = ch.own, *side_rows = ch.own + ch.K * S * sizeof(cryo_project_rec);
         HIP_TRY(c, cryo::launch_project(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.sd.d_atts, io.sd.d_keys, io.sd.nkeys, tab,
-                                        io.pt.ncols, io.pt.row_bytes, io.sd.max_att, io.sd.table_keys, (uint4 *)(io.d_blocks + ch.lo),
+                                        io.pt.ncols, io.pt.row_bytes, io.sd.max_att, io.sd.truth, (uint4 *)(io.d_blocks + ch.lo),
                                         side_rec, side_rows, io.d_total, io.d_rec, io.rec_cap, io.d_rows, io.row_cap, c->lz4_opts.cus));
         return CRYO_OK;
     };
@@ -1758,7 +1780,10 @@ static int scan_desc_device(cryo_codec *c, const cryo_filter *f, const cryo_grou
     if (total_words) HIP_TRY(c, hipMemsetAsync(d_total, 0, total_words * sizeof(uint64_t), c->stream));
     if (n_blocks == 0) return CRYO_OK;
     sd.d_atts = f->atts; sd.d_keys = f->keys; sd.nkeys = f->nkeys;
-    return key_table_device(c, keys, f->nkeys, &sd.d_keys, &sd.table_keys);
+    bool table_keys = false;
+    const int rc = key_table_device(c, keys, f->nkeys, &sd.d_keys, &table_keys);
+    sd.truth = scan_truth(f, table_keys);
+    return rc;
 }
 
 int cryo_codec_filter_batch(cryo_codec *c, int method, const void *d_src, const uint64_t *d_src_off, const uint32_t *d_src_size,
@@ -2496,7 +2521,7 @@ static int scan_desc_upload(cryo_codec *c, const void *const *h_src, const uint3
     if (L.bytes > L.t_extra) memcpy(pin + L.t_extra, extra, L.bytes - L.t_extra);
     HIP_TRY(c, hipMemcpyAsync(c->hb_meta, pin, L.bytes, hipMemcpyHostToDevice, c->stream));
     c->xfer_ctr.h2d_bytes += L.bytes;
-    sd.d_atts = c->hb_meta; sd.d_keys = c->hb_meta + L.t_keys; sd.nkeys = f->nkeys; sd.max_att = max_att; sd.table_keys = L.table_keys;
+    sd.d_atts = c->hb_meta; sd.d_keys = c->hb_meta + L.t_keys; sd.nkeys = f->nkeys; sd.max_att = max_att; sd.truth = scan_truth(f, L.table_keys);
     return CRYO_OK;
 }
 

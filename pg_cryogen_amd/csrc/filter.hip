@@ -228,18 +228,18 @@ k_filter_copy(uint32_t cnt, const uint8_t *__restrict__ dec, uint64_t dec_stride
 
 hipError_t launch_filter(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
                          const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, uint32_t max_att,
-                         bool table_keys, bool count_only, uint4 *d_blocks, uint4 *d_side, uint64_t *d_sum, uint64_t *d_base, uint64_t *d_running,
+                         uint32_t truth, bool count_only, uint4 *d_blocks, uint4 *d_side, uint64_t *d_sum, uint64_t *d_base, uint64_t *d_running,
                          uint8_t *d_dst, uint64_t dst_cap, uint2 *d_rec, uint64_t rec_cap, bool chunk_relative, int cus)
 {
     if (cnt == 0) return hipSuccess;
     if ((dec_stride & 15u) != 0 || (((uintptr_t)d_dec | (uintptr_t)d_blocks | (uintptr_t)d_side) & 15u) != 0 ||
         (((uintptr_t)d_dst | (uintptr_t)d_rec | (uintptr_t)d_keys) & 7u) != 0 || ((uintptr_t)d_atts & 3u) != 0 || block_size < 16u ||
-        nkeys > 4u)
+        nkeys > 4u || truth > 0xFFFFu)
         return hipErrorInvalidValue;
     const uint32_t stride = filter_side_stride(block_size);
     /* the integer-only descriptor keeps its own instantiation: the code it had before byte-string keys */
-    hipLaunchKernelGGL(table_keys ? k_filter_match<true> : k_filter_match<false>, dim3((cnt + 3u) / 4u), dim3(256), 0, s, d_dec,
-                       dec_stride, block_size, cnt, d_dec_status, (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys, max_att,
+    hipLaunchKernelGGL(truth ? k_filter_match<true> : k_filter_match<false>, dim3((cnt + 3u) / 4u), dim3(256), 0, s, d_dec,
+                       dec_stride, block_size, cnt, d_dec_status, (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys | truth << 16, max_att,
                        count_only ? 1u : 0u, stride, d_blocks, d_side, d_sum);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || count_only) return e;

@@ -7,6 +7,9 @@
  * group columns and four aggregate columns).  Byte-string keys (CRYO_KEY_BYTES) are a second instantiation, chosen by the host when
  * a descriptor has one: a descriptor of integer keys and null tests alone runs the code it ran before those keys existed.  Set keys
  * (CRYO_OP_IN, CRYO_OP_NOT_IN) live in that second instantiation too: the host chooses it when a descriptor has either kind.
+ * So does the truth table (CRYO_FILTER_TRUTH): the second instantiation keeps, per tuple, the mask of keys that are true and the
+ * mask of keys that are undecided, and reads the verdict off a 16-bit table that rides in the high half of its nkeys argument --
+ * the caller's under the flag, the AND table from the host otherwise, so that it has one verdict path.
  */
 #pragma once
 #include <hip/hip_runtime.h>
@@ -36,6 +39,14 @@ template <uint32_t SLOTS> struct WalkCaptureN { int64_t v[SLOTS]; uint32_t has; 
 using WalkCapture = WalkCaptureN<kAggMaxCols>; /* the aggregate's */
 template <class T> struct WalkPlain { using type = T; }; /* keeps SLOTS out of deduction: the filter passes a null capture */
 template <bool BYTES> struct WalkKeys {};                /* a tag: whether the keys may hold a CRYO_KEY_BYTES entry or a set key */
+
+/* what the walk notes of key k's test on a tuple: without BYTES the keys are ANDed into pass; with BYTES bit k of t says that
+ * key k is true, and the truth table decides at the end */
+template <bool BYTES> __device__ inline void walk_note(bool &pass, uint32_t &t, uint32_t k, bool hit)
+{
+    if (BYTES) t |= hit ? 1u << k : 0u;
+    else pass = pass && hit;
+}
 
 __device__ inline bool filter_compare(uint32_t op, int64_t v, int64_t k)
 {
@@ -124,7 +135,10 @@ __device__ inline bool walk_set_has(const int64_t *__restrict__ set, uint32_t n,
  * attalign at least that: the aggregate's argument rule; an att of 0 names no column) in *cap; cols is read at addresses that
  * depend on the loop counters only.  BYTES: a key of type kKeyBytes compares the column's in-line payload with the rsv bytes at
  * value (walk_bytes_sign), and a key of op kOpIn / kOpNotIn tests the column's value against the rsv sorted members at value
- * (walk_set_has); without BYTES no key has that type or those ops.  NARROW: a captured column may have attlen 1 (the projection's
+ * (walk_set_has); without BYTES no key has that type or those ops.  BYTES again: nkeys is the key count in its low half and the
+ * truth table W in its high half (bit m of W: a match when exactly the keys of mask m are true; monotone, the host's rule), and
+ * the verdict on a good tuple with t the keys that are true and u those that are undecided is a match if W[t], no match if not
+ * W[t | u], undecided otherwise; without BYTES nkeys is the count alone and the keys are ANDed.  NARROW: a captured column may have attlen 1 (the projection's
  * argument rule: attlen 1, 2, 4 or 8 and attalign at least that). */
 template <bool CAPTURE, uint32_t SLOTS = kAggMaxCols, bool BYTES = false, bool NARROW = false>
 __device__ inline uint32_t walk_tuple(const uint8_t *__restrict__ t, uint32_t len, bool live, const FilterAtt *__restrict__ atts,
@@ -132,8 +146,10 @@ __device__ inline uint32_t walk_tuple(const uint8_t *__restrict__ t, uint32_t le
                                       const AggCol *__restrict__ cols, uint32_t ncols,
                                       typename WalkPlain<WalkCaptureN<SLOTS>>::type *cap, WalkKeys<BYTES> = WalkKeys<false>())
 {
-    uint32_t tnatts = 0, hoff = 0;
-    bool hasnull = false, bad = false, pass = true, undecided = false;
+    uint32_t tnatts = 0, hoff = 0, tmask = 0, umask = 0; /* tmask, umask: BYTES alone */
+    bool hasnull = false, bad = false, pass = true;
+    const uint32_t truth = BYTES ? nkeys >> 16 : 0u; /* uniform */
+    if (BYTES) nkeys &= 0xFFFFu;
     if (live) {
         if (len < 23u) bad = true;
         else {
@@ -188,25 +204,25 @@ __device__ inline uint32_t walk_tuple(const uint8_t *__restrict__ t, uint32_t le
         for (uint32_t k = 0; k < nkeys; k++) {
             const FilterKey key = keys[k]; /* uniform */
             if (key.att != col) continue;
-            if (key.op == kOpIsNull) pass = pass && isnull;
-            else if (key.op == kOpNotNull) pass = pass && !isnull;
+            if (key.op == kOpIsNull) walk_note<BYTES>(pass, tmask, k, isnull);
+            else if (key.op == kOpNotNull) walk_note<BYTES>(pass, tmask, k, !isnull);
             else if (BYTES && key.op >= kOpIn) {
                 /* the column rule is the comparison key's: the same load.  Never undecided; false on a NULL column */
                 const int64_t v = val ? walk_value(t + pos, a.attlen) : 0;
                 const bool in = walk_set_has(reinterpret_cast<const int64_t *>(key.value), key.rsv, v, val);
-                pass = pass && val && in == (key.op == kOpIn);
+                walk_note<BYTES>(pass, tmask, k, val && in == (key.op == kOpIn));
             } else if (BYTES && key.type == kKeyBytes) {
                 /* the column is a varlena (the argument rule) and [pos, pos + size) lies below len */
                 const bool inl = val && head != kWalkNoBytes;
                 const int32_t c = walk_bytes_sign(t + pos + (inl ? head : 0u), inl ? size - head : 0u, inl,
                                                   reinterpret_cast<const uint64_t *>(key.value), key.rsv,
                                                   key.op == kOpEq || key.op == kOpNe);
-                if (val && !inl) undecided = true; /* neither true nor false */
-                else pass = pass && val && filter_compare(key.op, c, 0);
+                if (val && !inl) umask |= 1u << k; /* neither true nor false */
+                else walk_note<BYTES>(pass, tmask, k, val && filter_compare(key.op, c, 0));
             } else {
                 /* attlen is the key type's size and pos a multiple of it: the argument rule */
                 const int64_t v = val ? walk_value(t + pos, a.attlen) : 0;
-                pass = pass && val && filter_compare(key.op, v, key.value);
+                walk_note<BYTES>(pass, tmask, k, val && filter_compare(key.op, v, key.value));
             }
         }
         if (CAPTURE) {
@@ -220,7 +236,9 @@ __device__ inline uint32_t walk_tuple(const uint8_t *__restrict__ t, uint32_t le
         }
         if (val) pos += size;
     }
-    return bad ? kFilterTuple : !pass ? kFilterNoMatch : (BYTES && undecided) ? kFilterUndecided : 0u;
+    if (BYTES) /* tmask and umask are below 16: both shifts stay within the table's 16 bits */
+        return bad ? kFilterTuple : ((truth >> tmask) & 1u) ? 0u : ((truth >> (tmask | umask)) & 1u) ? kFilterUndecided : kFilterNoMatch;
+    return bad ? kFilterTuple : !pass ? kFilterNoMatch : 0u;
 }
 
 } // namespace cryo

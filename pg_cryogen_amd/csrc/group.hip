@@ -253,19 +253,19 @@ k_group_copy(uint32_t cnt, uint32_t side_stride, uint32_t ncols, const uint4 *__
 
 hipError_t launch_group(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
                         const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,
-                        uint32_t nby, uint32_t ncols, uint32_t max_att, bool table_keys, uint4 *d_blocks, void *d_side_rec, void *d_side_cell,
+                        uint32_t nby, uint32_t ncols, uint32_t max_att, uint32_t truth, uint4 *d_blocks, void *d_side_rec, void *d_side_cell,
                         uint64_t *d_running, void *d_rec, void *d_cells, uint64_t group_cap, int cus)
 {
     if (cnt == 0) return hipSuccess;
     if ((dec_stride & 15u) != 0 || (((uintptr_t)d_dec | (uintptr_t)d_blocks) & 15u) != 0 ||
         (((uintptr_t)d_rec | (uintptr_t)d_cells | (uintptr_t)d_keys | (uintptr_t)d_slots | (uintptr_t)d_side_rec |
           (uintptr_t)d_side_cell | (uintptr_t)d_running) & 7u) != 0 ||
-        ((uintptr_t)d_atts & 3u) != 0 || block_size < 16u || nkeys > 4u || nby == 0u || nby > kGroupMaxBy || ncols > kAggMaxCols ||
+        ((uintptr_t)d_atts & 3u) != 0 || block_size < 16u || nkeys > 4u || truth > 0xFFFFu || nby == 0u || nby > kGroupMaxBy || ncols > kAggMaxCols ||
         !d_slots || !d_side_rec || !d_running || (ncols > 0u && !d_side_cell) || (group_cap > 0u && (!d_rec || (ncols > 0u && !d_cells))))
         return hipErrorInvalidValue;
     const uint32_t stride = filter_side_stride(block_size);
-    hipLaunchKernelGGL(table_keys ? k_group_block<true> : k_group_block<false>, dim3((cnt + kGroupWaves - 1u) / kGroupWaves), dim3(64 * kGroupWaves), 0, s, d_dec, dec_stride,
-                       block_size, cnt, d_dec_status, (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys,
+    hipLaunchKernelGGL(truth ? k_group_block<true> : k_group_block<false>, dim3((cnt + kGroupWaves - 1u) / kGroupWaves), dim3(64 * kGroupWaves), 0, s, d_dec, dec_stride,
+                       block_size, cnt, d_dec_status, (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys | truth << 16,
                        (const AggCol *)d_slots, nby, ncols, max_att, stride, d_blocks, (GroupRec *)d_side_rec,
                        (GroupCell *)d_side_cell);
     hipError_t e = hipGetLastError();

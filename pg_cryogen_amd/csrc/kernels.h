@@ -241,9 +241,12 @@ hipError_t launch_fetch(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride
 /* the scan filter (filter.hip) on one decoded chunk of cnt blocks (laid out as for launch_fetch): k_filter_match,
  * k_filter_offsets, k_filter_copy.  The descriptor is validated by the caller (cryo_codec.cpp, filter_desc_ok): d_atts natts
  * entries of {i16 attlen, u8 attalign, u8 0}, d_keys nkeys <= 4 entries of cryo_scan_key (device memory), max_att the highest
- * key column (0: no key).  table_keys: a key has type CRYO_KEY_BYTES or is a set key (CRYO_OP_IN, CRYO_OP_NOT_IN: rsv distinct members, ascending, at the device address in value); d_keys is then the caller's key table (cryo_codec.cpp,
+ * key column (0: no key).  A key may have type CRYO_KEY_BYTES or be a set key (CRYO_OP_IN, CRYO_OP_NOT_IN: rsv distinct members, ascending, at the device address in value) when d_keys is the library's key table (cryo_codec.cpp,
  * key_table_fill): the value of such a key is the device address of its constant, 8-byte aligned and zero-padded to a multiple
- * of 8, and k_filter_match<true> runs; otherwise k_filter_match<false>, which knows no such key.  An undecided tuple gets a
+ * of 8.  truth: 0 -- the keys are ANDed and none is of those kinds: k_filter_match<false>, which knows no such key and no table;
+ * otherwise the descriptor's truth table (CRYO_FILTER_TRUTH; the AND table 1 << (2^nkeys - 1) for a descriptor without the flag
+ * that has such a key), at most 16 bits: k_filter_match<true> runs and finds it in the high half of its nkeys argument
+ * (filter_walk.h).  An undecided tuple gets a
  * record {pos, 9, 0} and counts in n_bad.  d_blocks: the chunk's rows of the block table (cryo_filter_block, 16-byte aligned).  Scratch: d_side
  * 16 bytes per possible item (cnt * filter_side_stride(block_size) entries), d_sum 2 * cnt and d_base 2 * (cnt + 1) entries.
  * d_running: the two totals {bytes, records} before the chunk in, after it out.  The chunk's tuples go to d_dst (8-byte aligned)
@@ -257,32 +260,32 @@ inline uint32_t filter_side_stride(uint32_t block_size)
 }
 hipError_t launch_filter(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
                          const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, uint32_t max_att,
-                         bool table_keys, bool count_only, uint4 *d_blocks, uint4 *d_side, uint64_t *d_sum, uint64_t *d_base, uint64_t *d_running,
+                         uint32_t truth, bool count_only, uint4 *d_blocks, uint4 *d_side, uint64_t *d_sum, uint64_t *d_base, uint64_t *d_running,
                          uint8_t *d_dst, uint64_t dst_cap, uint2 *d_rec, uint64_t rec_cap, bool chunk_relative, int cus);
 
 /* the scan aggregate (agg.hip) on one decoded chunk of cnt blocks (laid out as for launch_filter): k_agg_block alone.  The
  * descriptors are validated by the caller (cryo_codec.cpp, agg_desc_ok): d_atts and d_keys as for launch_filter, d_cols ncols
- * (1 .. 4) entries of cryo_agg_col (device memory, 8-byte aligned), max_att the highest key or aggregate column, table_keys as
+ * (1 .. 4) entries of cryo_agg_col (device memory, 8-byte aligned), max_att the highest key or aggregate column, truth as
  * for launch_filter (k_agg_block<true> / <false>; an undecided tuple counts in n_bad and is in no cell).  d_blocks: the
  * chunk's rows (cryo_agg_block, 16-byte aligned); d_cells: its cnt * ncols cells (cryo_agg_cell, 8-byte aligned), block k's at
  * k * ncols.  Workspace rule: none -- the kernel keeps everything in registers and writes only the rows and the cells, so a pass
  * over it asks the shared decode loop for no bytes of its own. */
 hipError_t launch_agg(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
                       const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_cols,
-                      uint32_t ncols, uint32_t max_att, bool table_keys, uint4 *d_blocks, void *d_cells);
+                      uint32_t ncols, uint32_t max_att, uint32_t truth, uint4 *d_blocks, void *d_cells);
 
 /* the grouped scan (group.hip) on one decoded chunk of cnt blocks (laid out as for launch_filter): k_group_block,
  * k_group_offsets, k_group_copy.  The descriptors are validated by the caller (cryo_codec.cpp, group_desc_ok): d_atts and d_keys as
  * for launch_filter; d_slots six entries of cryo_agg_col (device memory, 8-byte aligned): the nby (1 .. 2) group columns in
  * entries 0 .. 1, the ncols (0 .. 4) aggregate columns in entries 2 .. 5, every unused entry all zero; max_att the highest key,
- * group or aggregate column; table_keys as for launch_filter (k_group_block<true> / <false>; an undecided tuple counts in n_bad
+ * group or aggregate column; truth as for launch_filter (k_group_block<true> / <false>; an undecided tuple counts in n_bad
  * and is in no group).  d_blocks: the chunk's rows (cryo_group_block, 16-byte aligned).  Scratch: d_side_rec 24 bytes and
  * d_side_cell 40 * ncols bytes per possible group (cnt * filter_side_stride(block_size) groups; both 8-byte aligned).
  * *d_running: the groups before the chunk in, after it out.  The chunk's records go to d_rec and its cells to d_cells (8-byte
  * aligned) at first_group within the call; nothing at or beyond group_cap groups is written.  cus as for launch_fetch. */
 hipError_t launch_group(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
                         const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,
-                        uint32_t nby, uint32_t ncols, uint32_t max_att, bool table_keys, uint4 *d_blocks, void *d_side_rec,
+                        uint32_t nby, uint32_t ncols, uint32_t max_att, uint32_t truth, uint4 *d_blocks, void *d_side_rec,
                         void *d_side_cell,
                         uint64_t *d_running, void *d_rec, void *d_cells, uint64_t group_cap, int cus);
 
@@ -291,7 +294,7 @@ hipError_t launch_group(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride
  * d_keys as for launch_filter; d_cols the staged column table, ncols (1 .. 8) entries of 8 bytes (device memory, 8-byte aligned):
  * {u16 att, u8 width (the column's attlen: 1, 2, 4, 8), u8 offset within the row (a multiple of the width, below row_bytes), u32
  * 0} -- the walk reads it as cryo_agg_col and looks at att alone; row_bytes the row's size, 8 .. 64 and a multiple of 8 (both from
- * CRYO_PROJECT_COL_OFFSET / CRYO_PROJECT_ROW_BYTES); max_att the highest key or projected column; table_keys as for launch_filter (k_project_block<true> /
+ * CRYO_PROJECT_COL_OFFSET / CRYO_PROJECT_ROW_BYTES); max_att the highest key or projected column; truth as for launch_filter (k_project_block<true> /
  * <false>; an undecided tuple gets a record {pos, 9, 0}, counts in n_bad and has no row).  d_blocks: the chunk's rows of the
  * block table (cryo_project_block, 16-byte aligned).  Scratch: d_side_rec 8 bytes and d_side_rows row_bytes bytes per possible
  * item (cnt * filter_side_stride(block_size) items; both 8-byte aligned).  d_running: the two totals {rows, records} before the
@@ -299,7 +302,7 @@ hipError_t launch_group(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride
  * the call; no record at or beyond rec_cap and no row at or beyond row_cap is written.  cus as for launch_fetch. */
 hipError_t launch_project(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
                           const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_cols,
-                          uint32_t ncols, uint32_t row_bytes, uint32_t max_att, bool table_keys, uint4 *d_blocks, void *d_side_rec,
+                          uint32_t ncols, uint32_t row_bytes, uint32_t max_att, uint32_t truth, uint4 *d_blocks, void *d_side_rec,
                           void *d_side_rows, uint64_t *d_running, void *d_rec, uint64_t rec_cap, void *d_rows, uint64_t row_cap, int cus);
 
 } // namespace cryo

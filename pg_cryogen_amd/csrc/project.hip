@@ -189,20 +189,20 @@ k_project_copy(uint32_t cnt, uint32_t side_stride, uint32_t row_words, const uin
 
 hipError_t launch_project(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
                           const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_cols,
-                          uint32_t ncols, uint32_t row_bytes, uint32_t max_att, bool table_keys, uint4 *d_blocks, void *d_side_rec,
+                          uint32_t ncols, uint32_t row_bytes, uint32_t max_att, uint32_t truth, uint4 *d_blocks, void *d_side_rec,
                           void *d_side_rows, uint64_t *d_running, void *d_rec, uint64_t rec_cap, void *d_rows, uint64_t row_cap, int cus)
 {
     if (cnt == 0) return hipSuccess;
     if ((dec_stride & 15u) != 0 || (((uintptr_t)d_dec | (uintptr_t)d_blocks) & 15u) != 0 ||
         (((uintptr_t)d_rec | (uintptr_t)d_rows | (uintptr_t)d_keys | (uintptr_t)d_cols | (uintptr_t)d_side_rec | (uintptr_t)d_side_rows |
           (uintptr_t)d_running) & 7u) != 0 ||
-        ((uintptr_t)d_atts & 3u) != 0 || block_size < 16u || nkeys > 4u || ncols == 0u || ncols > kProjectMaxCols || row_bytes < 8u ||
+        ((uintptr_t)d_atts & 3u) != 0 || block_size < 16u || nkeys > 4u || truth > 0xFFFFu || ncols == 0u || ncols > kProjectMaxCols || row_bytes < 8u ||
         row_bytes > 8u * kProjectMaxCols || (row_bytes & 7u) != 0 || !d_cols || !d_side_rec || !d_side_rows || !d_running ||
         (rec_cap > 0u && !d_rec) || (row_cap > 0u && !d_rows))
         return hipErrorInvalidValue;
     const uint32_t stride = filter_side_stride(block_size), row_words = row_bytes / 8u;
-    hipLaunchKernelGGL(table_keys ? k_project_block<true> : k_project_block<false>, dim3((cnt + 3u) / 4u), dim3(256), 0, s, d_dec,
-                       dec_stride, block_size, cnt, d_dec_status, (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys,
+    hipLaunchKernelGGL(truth ? k_project_block<true> : k_project_block<false>, dim3((cnt + 3u) / 4u), dim3(256), 0, s, d_dec,
+                       dec_stride, block_size, cnt, d_dec_status, (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys | truth << 16,
                        (const AggCol *)d_cols, ncols, max_att, row_words, stride, d_blocks, (uint2 *)d_side_rec, (uint2 *)d_side_rows);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;

@@ -400,13 +400,13 @@ class FilterScanError(RuntimeError):
         super().__init__("cryo_filter_scan failed: %d" % code)
 
 
-def filter_scan(rel, atts, keys=(), flags=0):
+def filter_scan(rel, atts, keys=(), flags=0, truth=None):
     """cryo_filter_scan (host/filter.h) with the descriptor codec.filter_desc makes of atts [(attlen, attalign)], keys [(att,
-    type, op, value)] and flags.  Returns (events, totals): events in delivery order, ("tuple", block, pos, created_xid, bytes of
+    type, op, value)], flags and truth (a truth table over the keys, codec.truth_dnf).  Returns (events, totals): events in delivery order, ("tuple", block, pos, created_xid, bytes of
     MAXALIGN(len), len) or ("report", block, reason, detail); totals a dict.  A nonzero status raises FilterScanError (which
     carries what was delivered)."""
     from . import codec
-    desc = codec.filter_desc(atts, keys, flags)
+    desc = codec.filter_desc(atts, keys, flags, truth)
     events = []
 
     def on_tuple(arg, t):
@@ -434,14 +434,14 @@ def _cell(c):
     return (c.n, c.min, c.max, (c.sum_hi << 64) + c.sum_lo)
 
 
-def aggregate_scan(rel, atts, keys, cols):
+def aggregate_scan(rel, atts, keys, cols, truth=None):
     """cryo_aggregate_scan (host/aggregate.h) with the descriptors codec.filter_desc and codec.agg_desc make of atts [(attlen,
     attalign)], keys [(att, type, op, value)] and cols [(att, type)].  Returns (events, totals): events in delivery order,
     ("block", block, created_xid, n_items, n_match, n_bad, [(n, min, max, sum) per column]) or ("report", block, reason, detail);
     totals a dict whose "cells" are the combined [(n, min, max, sum) per column].  A nonzero status raises AggregateScanError
     (which carries what was delivered)."""
     from . import codec
-    desc, adesc = codec.filter_desc(atts, keys), codec.agg_desc(cols)
+    desc, adesc = codec.filter_desc(atts, keys, 0, truth), codec.agg_desc(cols)
     ncols = len(cols)
     events = []
 
@@ -466,14 +466,14 @@ class GroupScanError(RuntimeError):
         super().__init__("cryo_group_scan failed: %d" % code)
 
 
-def group_scan(rel, atts, keys, by, cols=None):
+def group_scan(rel, atts, keys, by, cols=None, truth=None):
     """cryo_group_scan (host/group.h) with the descriptors codec.filter_desc, codec.group_desc and codec.agg_desc make of atts
     [(attlen, attalign)], keys [(att, type, op, value)], by and cols [(att, type)] (cols None: a null aggregate descriptor).
     Returns (events, totals): events in delivery order, ("block", block, created_xid, n_items, n_match, n_bad, [(key tuple with
     None for NULL, n_rows, [(n, min, max, sum) per column]) per group]) or ("report", block, reason, detail); totals a dict.  A
     nonzero status raises GroupScanError (which carries what was delivered)."""
     from . import codec
-    desc, gdesc = codec.filter_desc(atts, keys), codec.group_desc(by)
+    desc, gdesc = codec.filter_desc(atts, keys, 0, truth), codec.group_desc(by)
     adesc = None if cols is None else codec.agg_desc(cols)
     nby, ncols = len(by), len(cols or ())
     events = []
@@ -504,13 +504,13 @@ class ProjectScanError(RuntimeError):
         super().__init__("cryo_project_scan failed: %d" % code)
 
 
-def project_scan(rel, atts, keys, cols):
+def project_scan(rel, atts, keys, cols, truth=None):
     """cryo_project_scan (host/project.h) with the descriptors codec.filter_desc and codec.project_desc make of atts [(attlen,
     attalign)], keys [(att, type, op, value)] and cols [att].  Returns (events, totals): events in delivery order, ("row", block,
     pos, created_xid, nulls, the row's bytes) or ("report", block, reason, detail); totals a dict.  A nonzero status raises
     ProjectScanError (which carries what was delivered)."""
     from . import codec
-    desc, pdesc = codec.filter_desc(atts, keys), codec.project_desc(cols)
+    desc, pdesc = codec.filter_desc(atts, keys, 0, truth), codec.project_desc(cols)
     events = []
 
     def on_row(arg, r):

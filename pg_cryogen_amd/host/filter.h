@@ -68,4 +68,22 @@ int cryo_filter_scan(CryoRel *rel, const cryo_filter *f,
                      void (*tuple)(void *arg, const CryoFilteredTuple *t),
                      void (*report)(void *arg, const CryoFilterReport *r), void *arg, CryoFilterTotals *totals);
 
+/* The truth table of a WHERE clause in disjunctive normal form, for f->rsv under CRYO_FILTER_TRUTH (include/cryo_codec.h,
+ * "Truth table"): terms[i] is a mask of the keys that are ANDed in term i (bit k: keys[k]) and the nterms terms are ORed --
+ * A AND B AND (C OR D) over keys A, B, C, D is {0x7, 0xB}.  Bit m of the result is set when some term lies within m, so the
+ * table is monotone by construction: binders build their tables here.  Returns 0 -- no table, the codec refuses it -- for no
+ * term, a null array, an empty term, a term with a bit at or beyond nkeys, or nkeys outside 1 .. CRYO_FILTER_MAX_KEYS.  The four
+ * walks (this one, aggregate.h, group.h, project.h) pass flags and rsv of the descriptor through untouched. */
+static inline uint32_t cryo_filter_truth_dnf(const uint32_t *terms, uint32_t nterms, uint32_t nkeys)
+{
+    uint32_t w = 0, i, m;
+    if (!terms || nterms == 0 || nkeys == 0 || nkeys > CRYO_FILTER_MAX_KEYS) return 0;
+    for (i = 0; i < nterms; i++)
+        if (terms[i] == 0 || (terms[i] >> nkeys) != 0) return 0;
+    for (m = 0; m < (1u << nkeys); m++)
+        for (i = 0; i < nterms; i++)
+            if ((terms[i] & m) == terms[i]) w |= 1u << m;
+    return w;
+}
+
 #endif
