@@ -380,8 +380,8 @@ int cryo_codec_fetch_batch(cryo_codec *c, int method, const void *d_src, const u
  * a value outside the type's range; an unknown op; a reserved field that is not zero; an unknown bit in flags.  For
  * CRYO_OP_ISNULL and CRYO_OP_NOTNULL, type and value are ignored.  Key values are signed and compared as such; tuples are
  * little-endian.
- * Byte-string keys.  A comparison key (CRYO_OP_LT .. CRYO_OP_NE) of type CRYO_KEY_BYTES (16; 4 .. 15 stay free for fixed-width
- * types, and they, 0 and anything above 16 are unknown) compares a text / varchar / bytea column with a constant: rsv is the
+ * Byte-string keys.  A comparison key (CRYO_OP_LT .. CRYO_OP_NE) of type CRYO_KEY_BYTES (16; 4 .. 15 are kept for fixed-width
+ * types, of which 8 and 9 are the float types below; the rest of them, 0 and anything above 16 are unknown) compares a text / varchar / bytea column with a constant: rsv is the
  * constant's length n, 0 .. CRYO_KEY_BYTES_MAX, and value the address of its n bytes -- a device address for cryo_codec_*_batch,
  * a host address for cryo_codec_*_blocks and cryo_multi_*_blocks; any alignment; not looked at when n == 0.  CRYO_E_ARG when the
  * key's column is not a varlena (attlen != -1), n > CRYO_KEY_BYTES_MAX, or n > 0 with a null address.  For every other type and
@@ -400,6 +400,19 @@ int cryo_codec_fetch_batch(cryo_codec *c, int method, const void *d_src, const u
  * members, ascending as signed 64-bit integers and 8-byte aligned; the caller's key array and lists are only read.  The binder's
  * part, not enforced here: drop NULL members from an IN list, never push down a NOT IN whose list holds a NULL, and fold an
  * empty list itself.
+ * Float keys.  A comparison key (CRYO_OP_LT .. CRYO_OP_NE) of type CRYO_KEY_FLOAT4 (8: the column's attlen is 4, its attalign
+ * at least 4) or CRYO_KEY_FLOAT8 (9: attlen 8, attalign 8) compares a float4 / float8 column with a constant (WHERE revenue > 0).
+ * For both types value holds the 64 bits of an IEEE DOUBLE: a float4 column's value is widened to double -- exactly, a subnormal
+ * included -- and compared with it, which serves PostgreSQL's float4, float8, float48 and float84 operator families alike; the
+ * binder widens a float4 constant.  Every bit pattern is a valid constant, NaN included; rsv must be 0.  The order is
+ * PostgreSQL's float8_cmp_internal: -Inf < every finite value < +Inf < NaN; all NaNs are equal to each other, whatever their
+ * sign or payload, so x = 'NaN' is true on a NaN; -0 equals +0.  A comparison is false on a NULL, as for integers, and the null
+ * tests ignore the type, as always.  CRYO_OP_IN / CRYO_OP_NOT_IN with a float type is CRYO_E_ARG (no lists of floats), and so is a
+ * float type as a group column (no GROUP BY a float); as an aggregate column it is allowed ("A float column's cell", below).
+ * The order as integers: the double bits b map to the signed 64-bit integer m(b) = INT64_MAX for a NaN, 0 for either zero, and
+ * otherwise b ^ ((b >> 63, arithmetic) & 0x7FFFFFFFFFFFFFFF), whose integer order is the order above; m is its own inverse apart
+ * from the two canonical cases.  The library's own copy of a float key holds m(value) -- the caller's arrays are never written
+ * -- and the kernels map a column's value the same way, so the compare, the minimum and the maximum are the integers'.
  * Truth table.  CRYO_FILTER_TRUTH (4) in flags: the keys are not ANDed but combined by any tree of AND and OR (WHERE country =
  * 'de' OR app_id = 3; WHERE ts >= a AND ts < b AND (campaign_id IN (..) OR source IS NULL)).  f->rsv is then not reserved: it
  * holds the truth table W of the tree over its nkeys leaves.  Bit m of W, 0 <= m < 2^nkeys, says whether a tuple matches when
@@ -496,6 +509,7 @@ int cryo_codec_fetch_batch(cryo_codec *c, int method, const void *d_src, const u
 typedef struct { int16_t attlen; uint8_t attalign; uint8_t rsv; } cryo_att; /* pg_attribute.attlen; attalign as 1/2/4/8; 4 bytes */
 typedef enum {
     CRYO_KEY_INT2 = 1, CRYO_KEY_INT4 = 2, CRYO_KEY_INT8 = 3, /* signed, little-endian */
+    CRYO_KEY_FLOAT4 = 8, CRYO_KEY_FLOAT8 = 9,                /* IEEE single / double columns; a key's value: the bits of a double */
     CRYO_KEY_BYTES = 16                                      /* a byte string: rsv its length, value its address */
 } cryo_key_type;
 typedef enum {
@@ -535,7 +549,7 @@ int cryo_codec_filter_batch(cryo_codec *c, int method, const void *d_src, const 
                             void *d_dst, uint64_t dst_cap, cryo_filter_rec *d_rec, uint64_t rec_cap,
                             cryo_filter_block *d_blocks, uint64_t *d_total);
 
-/* ---- aggregating a scan: stored streams -> decoded in handle workspace -> keys tested, integer columns reduced per block -> a
+/* ---- aggregating a scan: stored streams -> decoded in handle workspace -> keys tested, integer and float columns reduced per block -> a
  *      row and a few cells per block come back ----
  * The query an append-only analytics store answers most: SELECT sum(x), min(ts), max(ts), count(x) FROM t WHERE ts >= a AND
  * ts < b.  The filter above ships every matching tuple back and the host deforms it a second time to add up one column; here the
@@ -574,12 +588,44 @@ int cryo_codec_filter_batch(cryo_codec *c, int method, const void *d_src, const 
  *                   bits, signed).  A block has at most 290 items, so it never overflows.
  *   n == 0          min = max = 0 and the sum is 0
  * count(col) is n, count(*) is n_match, avg is the caller's division; the partials of blocks combine by adding n and the 128-bit
- * sums (with carry) and taking min / max over the cells with n > 0. */
+ * sums (with carry) and taking min / max over the cells with n > 0.
+ *
+ * A float column's cell.  An aggregate column of type CRYO_KEY_FLOAT4 or CRYO_KEY_FLOAT8 (the float key's column rule) may stand
+ * beside integer columns in one descriptor; an integer column's cell is byte for byte what it is without them.  The float
+ * column's 40 bytes are a cryo_agg_cell_f {n, min, max, sum, err}:
+ *   n           as above; n == 0 gives all-zero bytes
+ *   min, max    over the non-NULL matches in the float keys' order: max is NaN if any value is NaN, min only if all are.
+ *               Returned widened to double and canonical: any NaN as 0x7FF8000000000000, any zero as +0.0
+ *   sum, err    with P / M / Q "some value is +Inf / -Inf / NaN": if Q, or both P and M, sum = the canonical NaN and err = +0;
+ *               else if P (or M), sum = +Inf (or -Inf) and err = +0; otherwise (sum, err) is the double-double result of the
+ *               reduction below over the FINITE values: sum + err is the answer and sum = RN(sum + err).  If the finite values
+ *               leave the double range inside the reduction, sum and err both come out as the canonical NaN; err is NaN in no
+ *               other case.  PostgreSQL raises "value out of range: overflow" there, and so should the binder.
+ * The reduction is part of the contract, so that a call's output stays defined byte for byte.  Every operation is IEEE
+ * binary64, round to nearest, nothing fused, subnormals kept:
+ *   TwoSum(a, b):      s = a + b; bb = s - a; e = (a - (s - bb)) + (b - bb)
+ *   FastTwoSum(s, t):  h = s + t; l = t - (h - s)
+ *   x (+) y on pairs:  (s, t) = TwoSum(x.hi, y.hi); t = t + (x.lo + y.lo); the result is FastTwoSum(s, t).  Commutative.
+ *   aggregate call:    leaf S_l, l = 0 .. 63, starts at (+0, +0) and takes S_l <- S_l (+) (v, +0) for the finite non-NULL values
+ *                      of the matches at positions p with (p - 1) mod 64 = l, in ascending p; then for d = 32, 16, .., 1 every
+ *                      S_l <- S_l (+) S_(l xor d) at once; the result is S_0
+ *   grouped call:      from (+0, +0), (+) (v, +0) over the group's matches in position order
+ *   blocks and groups combine on the host (cryo_agg_cell_f_combine, pg_cryogen_amd/host/aggregate.h): add n, take min / max in
+ *                      the order above, fold the P / M / Q rule, and (+) over (sum, err) in block order.
+ * Accuracy: for finite inputs without overflow |sum + err - exact| <= 2^-90 * sum |v|.  A block has at most 290 items, each
+ * (+) errs by an amount of order 2^-104 relative to the magnitudes it adds, and 290 steps stay below 2^-95: the bound has
+ * margin, and it is still 2^30 tighter than the best guarantee plain double summation can give. */
 typedef struct { uint16_t att; uint8_t type, rsv; uint32_t rsv2; } cryo_agg_col;   /* att 1-based; type: cryo_key_type; 8 bytes */
 typedef struct { uint32_t ncols, rsv; const cryo_agg_col *cols; } cryo_agg;
 #define CRYO_AGG_MAX_COLS 4u
 typedef struct { uint32_t status, n_items, n_match, n_bad; } cryo_agg_block;      /* 16 bytes, one per block */
 typedef struct { uint64_t n; int64_t min, max; uint64_t sum_lo; int64_t sum_hi; } cryo_agg_cell; /* 40 bytes */
+typedef struct { uint64_t n; double min, max, sum, err; } cryo_agg_cell_f; /* a float column's cell: the same 40 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(cryo_agg_cell_f) == 40, "a float column's cell is a cryo_agg_cell's 40 bytes");
+#else
+_Static_assert(sizeof(cryo_agg_cell_f) == 40, "a float column's cell is a cryo_agg_cell's 40 bytes");
+#endif
 /* Device buffers.  The structs *f and *agg are host memory; f->atts, f->keys and agg->cols are DEVICE arrays (4-byte / 8-byte /
  * 8-byte aligned).  The host validates the descriptors before anything is queued: it reads the three arrays back on the handle's
  * stream (one wait for what the stream held before the call); from there on the call is asynchronous, with no host wait between

@@ -6,6 +6,7 @@ reference's domain (cryo blocks, methods, acceleration/level), see
 reference compression.h:7-24.
 """
 import ctypes as C
+import struct
 
 import numpy as np
 
@@ -46,6 +47,7 @@ FILTER_COUNT_ONLY = 1
 FILTER_MAX_KEYS = 4
 FILTER_TRUTH = 4            # the descriptor's rsv is a truth table over its keys (truth_dnf), not reserved
 KEY_INT2, KEY_INT4, KEY_INT8 = 1, 2, 3
+KEY_FLOAT4, KEY_FLOAT8 = 8, 9   # float4 / float8 columns: a comparison key's value is a Python float (or the bits of a double)
 KEY_BYTES = 16              # a byte string: the key's value is bytes, compared unsigned, then by length
 KEY_BYTES_MAX = 256
 OP_LT, OP_LE, OP_EQ, OP_GE, OP_GT, OP_NE, OP_ISNULL, OP_NOTNULL = range(1, 9)
@@ -61,6 +63,7 @@ AGG_MAX_COLS = 4
 AGG_COL = np.dtype([("att", "<u2"), ("type", "u1"), ("rsv", "u1"), ("rsv2", "<u4")])                            # cryo_agg_col
 AGG_BLOCK = np.dtype([("status", "<u4"), ("n_items", "<u4"), ("n_match", "<u4"), ("n_bad", "<u4")])             # cryo_agg_block
 AGG_CELL = np.dtype([("n", "<u8"), ("min", "<i8"), ("max", "<i8"), ("sum_lo", "<u8"), ("sum_hi", "<i8")])       # cryo_agg_cell
+AGG_CELL_F = np.dtype([("n", "<u8"), ("min", "<f8"), ("max", "<f8"), ("sum", "<f8"), ("err", "<f8")])               # cryo_agg_cell_f
 # the grouped scan (include/cryo_codec.h): a block's statuses are the aggregate's; cells are AGG_CELL, one per group and column
 GROUP_MAX_BY = 2
 GROUP_BLOCK = np.dtype([("status", "<u4"), ("n_items", "<u4"), ("n_match", "<u4"), ("n_bad", "<u4"),
@@ -321,7 +324,7 @@ def truth_flags(flags=0, truth=None):
 def filter_desc(atts, keys=(), flags=0, truth=None):
     """the descriptor of a filter call as host arrays: atts a list of (attlen, attalign), keys a list of (att, type, op, value)
     (att 1-based; type KEY_*, op OP_*; the value of a KEY_BYTES comparison is a bytes object, that of an OP_IN / OP_NOT_IN key
-    a sequence of ints).  Returns (CryoFilter, atts array,
+    a sequence of ints, that of a KEY_FLOAT4 / KEY_FLOAT8 comparison a Python float or, as an int, the 64 bits of a double).  Returns (CryoFilter, atts array,
     keys array); the struct points into the two arrays, which the caller keeps alive.  The constants of KEY_BYTES keys live in
     one uint8 array the struct holds (f.consts), so they live as long as it does.  truth: a truth table over the keys (truth_dnf):
     FILTER_TRUTH is set in flags and the table goes into rsv"""
@@ -346,6 +349,13 @@ def _is_set_key(key):
     return isinstance(key[3], (list, tuple, range, np.ndarray)) or (key[3] is None and key[2] in (OP_IN, OP_NOT_IN))
 
 
+def float_key_bits(value):
+    """the value field of a float key: the 64 bits of the double `value` (a Python float), or of the bits given as an int, as
+    the signed integer the field is"""
+    bits = struct.unpack("<Q", struct.pack("<d", value))[0] if isinstance(value, float) else int(value) & (1 << 64) - 1
+    return bits - (1 << 64) if bits >> 63 else bits
+
+
 def _filter_keys(keys):
     """(keys array with rsv = the length and value = the offset of each KEY_BYTES constant, rsv = the number of members and
     value = the offset of each set key's list -- little-endian int64 --, constants and lists packed back to back)"""
@@ -364,6 +374,8 @@ def _filter_keys(keys):
             k[i] = (att, typ, op, len(value), at)
             parts.append(members)
             at += len(members)
+        elif typ in (KEY_FLOAT4, KEY_FLOAT8) and OP_LT <= op <= OP_NE:
+            k[i] = (att, typ, op, 0, float_key_bits(value))
         else:
             k[i] = (att, typ, op, 0, value)
     consts = np.frombuffer(b"".join(parts) + b"\0", np.uint8).copy()        # never empty: it has an address
@@ -512,6 +524,77 @@ def project_blocks_call(fn, handle, chk, method, comps, block_size, desc, pdesc,
 def cell_sum(cell):
     """the exact sum of an AGG_CELL as a Python integer"""
     return (int(cell["sum_hi"]) << 64) + int(cell["sum_lo"])
+
+
+FLOAT_NAN_BITS = 0x7FF8000000000000            # the canonical NaN of a float cell
+
+
+def _f64(bits):
+    return struct.unpack("<d", struct.pack("<Q", bits))[0]
+
+
+def _bits(x):
+    return struct.unpack("<Q", struct.pack("<d", x))[0]
+
+
+def cell_float(cell):
+    """(n, min, max, sum, err) of an AGG_CELL that holds a float column's cell (cryo_agg_cell_f): Python floats, bit for bit"""
+    c = np.frombuffer(np.asarray(cell).tobytes(), AGG_CELL_F)[0]
+    return int(c["n"]), float(c["min"]), float(c["max"]), float(c["sum"]), float(c["err"])
+
+
+def float_order(x):
+    """the signed integer whose order is the float keys' order of the double x: a NaN INT64_MAX, a zero 0"""
+    b = _bits(x)
+    if b & 0x7FFFFFFFFFFFFFFF > 0x7FF0000000000000:
+        return (1 << 63) - 1
+    if b & 0x7FFFFFFFFFFFFFFF == 0:
+        return 0
+    return -(b & 0x7FFFFFFFFFFFFFFF) - 1 if b >> 63 else b
+
+
+def float_pair_add(x, y):
+    """x (+) y of include/cryo_codec.h ("The reduction") on pairs (hi, lo) of Python floats, which are IEEE doubles"""
+    s = x[0] + y[0]
+    bb = s - x[0]
+    e = (x[0] - (s - bb)) + (y[0] - bb)
+    t = e + (x[1] + y[1])
+    h = s + t
+    return h, t - (h - s)
+
+
+def cell_float_combine(a, b):
+    """the float cell of two blocks' (or groups') float cells, a before b, as cryo_agg_cell_f_combine (host/aggregate.h): each
+    and the result (n, min, max, sum, err) as cell_float gives them.  n adds; min / max in the float keys' order, canonical;
+    NaN, or both infinities, give (NaN, +0), one infinity (that, +0); otherwise (sum, err) is a (+) b, and a pair that left the
+    double range (NaN, NaN)"""
+    if a[0] == 0 or b[0] == 0:
+        return tuple(b if a[0] == 0 else a)
+    nan = _f64(FLOAT_NAN_BITS)
+    lo = min(a[1], b[1], key=float_order)
+    hi = max(a[2], b[2], key=float_order)
+    lo, hi = (nan if x != x else x + 0.0 if x == 0 else x for x in (lo, hi))
+    inf = float("inf")
+
+    def kind(c):
+        # (P, M, Q, overflow) of a cell's (sum, err)
+        s, e = c[3], c[4]
+        if e != e:
+            return False, False, False, True
+        return s == inf, s == -inf, s != s, False
+    ka, kb = kind(a), kind(b)
+    P, M, Q, V = (ka[i] or kb[i] for i in range(4))
+    if Q or (P and M):
+        s, e = nan, 0.0
+    elif P or M:
+        s, e = (inf if P else -inf), 0.0
+    elif V:
+        s, e = nan, nan
+    else:
+        s, e = float_pair_add((a[3], a[4]), (b[3], b[4]))
+        if s != s or e != e or abs(s) == inf or abs(e) == inf:
+            s, e = nan, nan
+    return a[0] + b[0], lo, hi, s, e
 
 
 class DeviceBuffer:

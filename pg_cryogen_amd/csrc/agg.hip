@@ -16,6 +16,7 @@
  *                 32 bits of every value summed unsigned, the high 32 bits summed signed -- at most 290 values, so neither half
  *                 overflows.  After the sweep a butterfly (__shfl_xor) reduces the five words per column across the wave; lane 0
  *                 joins the halves into the 128-bit sum and writes the block's row and its cells straight to the call's output.
+ * A descriptor with a float key or a float aggregate column runs agg_float.hip's k_aggf_block instead (launch_agg's `floats`).
  * Every device write is a vector store in plain C++.  No LDS, no scratch, no atomics; no running totals, no second kernel.
  */
 #include "kernels.h"
@@ -119,13 +120,16 @@ k_agg_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, ui
 
 hipError_t launch_agg(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
                       const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_cols,
-                      uint32_t ncols, uint32_t max_att, uint32_t truth, uint4 *d_blocks, void *d_cells)
+                      uint32_t ncols, uint32_t max_att, uint32_t truth, bool floats, uint4 *d_blocks, void *d_cells)
 {
     if (cnt == 0) return hipSuccess;
     if ((dec_stride & 15u) != 0 || (((uintptr_t)d_dec | (uintptr_t)d_blocks) & 15u) != 0 ||
         (((uintptr_t)d_cells | (uintptr_t)d_keys | (uintptr_t)d_cols) & 7u) != 0 || ((uintptr_t)d_atts & 3u) != 0 || block_size < 16u ||
         nkeys > 4u || truth > 0xFFFFu || ncols == 0u || ncols > kAggMaxCols)
         return hipErrorInvalidValue;
+    if (floats) /* a float key or a float aggregate column: agg_float.hip's kernel */
+        return launch_aggf(s, d_dec, dec_stride, block_size, cnt, d_dec_status, d_atts, d_keys, nkeys, d_cols, ncols, max_att, truth,
+                           d_blocks, d_cells);
     hipLaunchKernelGGL(truth ? k_agg_block<true> : k_agg_block<false>, dim3((cnt + 3u) / 4u), dim3(256), 0, s, d_dec, dec_stride,
                        block_size, cnt, d_dec_status, (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys | truth << 16,
                        (const AggCol *)d_cols, ncols, max_att, d_blocks, (AggCell *)d_cells);

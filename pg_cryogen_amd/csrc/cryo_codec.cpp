@@ -1148,6 +1148,8 @@ struct ScanDesc {
     uint32_t nkeys = 0, max_att = 0;                 /* max_att: the highest column the walk has to reach */
     uint32_t truth = 0;                              /* 0: the keys are ANDed by the kernels' <false> instantiation; otherwise the
                                                         truth table of the <true> one (scan_truth) */
+    bool floats = false;                             /* a float key or a float aggregate column: the float kernels, which have
+                                                        the truth table's verdict path alone (truth is not 0 then) */
 };
 struct FilterIo {
     ScanDesc sd;
@@ -1184,7 +1186,29 @@ static bool truth_table_ok(uint32_t W, uint32_t nkeys)
 static uint32_t scan_truth(const cryo_filter *f, bool table_keys)
 {
     if (f->flags & CRYO_FILTER_TRUTH) return f->rsv;
-    return table_keys ? 1u << ((1u << f->nkeys) - 1u) : 0u; /* table_keys: nkeys is 1 .. 4 */
+    return table_keys ? 1u << ((1u << f->nkeys) - 1u) : 0u; /* table_keys: nkeys is 1 .. 4, or 0 with a float aggregate column
+                                                               alone (the callers count that in): table 1, every tuple a match */
+}
+
+/* ---- float keys and float aggregate columns ---- */
+static bool type_is_float(uint32_t type) { return type == CRYO_KEY_FLOAT4 || type == CRYO_KEY_FLOAT8; }
+/* the signed integer whose order is the float order of the double of bits b (include/cryo_codec.h: "Float keys"; filter_walk.h:
+ * float_map) */
+static int64_t float_map_host(uint64_t b)
+{
+    const uint64_t mag = b & 0x7FFFFFFFFFFFFFFFull;
+    if (mag > 0x7FF0000000000000ull) return INT64_MAX;
+    if (mag == 0) return 0;
+    return (int64_t)(b ^ ((b >> 63) ? 0x7FFFFFFFFFFFFFFFull : 0ull));
+}
+/* whether a (valid) descriptor needs the float kernels: keys and cols are host memory */
+static bool desc_has_float(const cryo_scan_key *keys, uint32_t nkeys, const cryo_agg_col *cols, uint32_t ncols)
+{
+    for (uint32_t k = 0; k < nkeys; k++)
+        if (type_is_float(keys[k].type) && keys[k].op >= CRYO_OP_LT && keys[k].op <= CRYO_OP_NE) return true;
+    for (uint32_t j = 0; j < ncols; j++)
+        if (type_is_float(cols[j].type)) return true;
+    return false;
 }
 
 /* the descriptor's rules (include/cryo_codec.h); atts and keys are host memory here.  *max_att: the highest key column */
@@ -1215,6 +1239,12 @@ static bool filter_desc_ok(const cryo_filter *f, const cryo_att *atts, const cry
             if (atts[q.att - 1].attlen != -1 || q.rsv > CRYO_KEY_BYTES_MAX || (q.rsv > 0 && q.value == 0)) return false;
             continue;
         }
+        if (type_is_float(q.type)) { /* value: the bits of a double, every pattern a constant; no lists of floats */
+            const int size = q.type == CRYO_KEY_FLOAT4 ? 4 : 8;
+            const cryo_att &a = atts[q.att - 1];
+            if (set || a.attlen != size || a.attalign < size) return false;
+            continue;
+        }
         if (q.type < CRYO_KEY_INT2 || q.type > CRYO_KEY_INT8) return false;
         const int size = q.type == CRYO_KEY_INT2 ? 2 : q.type == CRYO_KEY_INT4 ? 4 : 8;
         const cryo_att &a = atts[q.att - 1];
@@ -1232,14 +1262,17 @@ static bool filter_desc_ok(const cryo_filter *f, const cryo_att *atts, const cry
  * address of its constant in the table -- 8-byte aligned there, whatever the caller's address was.  The caller's arrays are only
  * read.  A set key (CRYO_OP_IN, CRYO_OP_NOT_IN) takes the same road: its list lies among the constants as its distinct members,
  * ascending as signed 64-bit integers, in the room of the rsv members the caller named; the table's copy of the key has rsv
- * rewritten to the distinct count and value to the set's device address.  A descriptor without either kind of key has no table:
- * its keys go to the device as they are. */
+ * rewritten to the distinct count and value to the set's device address.  A float key (CRYO_KEY_FLOAT4, CRYO_KEY_FLOAT8) has no
+ * constant behind the keys, but the table's copy of it has value rewritten to the mapped form of the double (float_map_host),
+ * which the kernels compare as an integer.  A descriptor without any of these kinds of key has no table: its keys go to the
+ * device as they are. */
 static constexpr size_t kKeyConstMax = 8u * CRYO_KEY_SET_MAX; /* the most bytes one key's constant or list takes */
 static_assert(kKeyConstMax >= CRYO_KEY_BYTES_MAX, "a list is the largest constant");
 static constexpr size_t kKeyTableBytes = CRYO_FILTER_MAX_KEYS * (sizeof(cryo_scan_key) + kKeyConstMax);
 
 static bool key_is_bytes(const cryo_scan_key &q) { return q.type == CRYO_KEY_BYTES && q.op >= CRYO_OP_LT && q.op <= CRYO_OP_NE; }
 static bool key_is_set(const cryo_scan_key &q) { return q.op == CRYO_OP_IN || q.op == CRYO_OP_NOT_IN; }
+static bool key_is_float(const cryo_scan_key &q) { return type_is_float(q.type) && q.op >= CRYO_OP_LT && q.op <= CRYO_OP_NE; }
 /* the bytes at a (valid) key's address: a byte-string constant's, a list's; 0: the key has none */
 static size_t key_const_len(const cryo_scan_key &q) { return key_is_set(q) ? (size_t)q.rsv * 8 : key_is_bytes(q) ? (size_t)q.rsv : 0; }
 
@@ -1250,6 +1283,7 @@ static size_t key_consts_bytes(const cryo_scan_key *keys, uint32_t nkeys, bool *
     *any = false;
     for (uint32_t k = 0; k < nkeys; k++)
         if (key_is_bytes(keys[k]) || key_is_set(keys[k])) { *any = true; b += (key_const_len(keys[k]) + 7) & ~(size_t)7; }
+        else if (key_is_float(keys[k])) *any = true;
     return (b + 15) & ~(size_t)15;
 }
 
@@ -1273,7 +1307,8 @@ static void key_table_fill(uint8_t *tab, uint64_t d_tab, const cryo_scan_key *ke
             if (q.rsv) memcpy(tab + at, consts[k], q.rsv);
             q.value = (int64_t)(d_tab + at);
             at += ((size_t)q.rsv + 7) & ~(size_t)7;
-        }
+        } else if (key_is_float(q))
+            q.value = float_map_host((uint64_t)q.value);
         memcpy(tab + (size_t)k * sizeof(cryo_scan_key), &q, sizeof q);
     }
 }
@@ -1338,7 +1373,7 @@ static int filter_pass(cryo_codec *c, int method, const uint8_t *d_src, const ui
         cryo_filter_rec *st_rec = (cryo_filter_rec *)(st_dst + row * ch.K);
         if (ch.lo == 0) HIP_TRY(c, hipMemsetAsync(running, 0, 2 * sizeof(uint64_t), c->stream));
         HIP_TRY(c, cryo::launch_filter(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.sd.d_atts, io.sd.d_keys, io.sd.nkeys, io.sd.max_att,
-                                       io.sd.truth, io.count_only, (uint4 *)(io.d_blocks + ch.lo), side, sum, base, running,
+                                       io.sd.truth, io.sd.floats, io.count_only, (uint4 *)(io.d_blocks + ch.lo), side, sum, base, running,
                                        stage ? st_dst : io.d_dst, stage ? ch.K * row : io.dst_cap,
                                        stage ? (uint2 *)st_rec : (uint2 *)io.d_rec, stage ? ch.K * S : io.rec_cap, host,
                                        c->lz4_opts.cus));
@@ -1396,12 +1431,13 @@ struct AggIo {
 
 /* the aggregate's descriptor rules (include/cryo_codec.h); every array is host memory here.  *max_att: the highest key or
  * aggregate column */
-/* the rule of one aggregate (or group) column; raises *max_att to it */
-static bool agg_col_ok(const cryo_filter *f, const cryo_att *atts, const cryo_agg_col &q, uint32_t *max_att)
+/* the rule of one aggregate (or group) column; raises *max_att to it.  floats: a float type is allowed (an aggregate column; a
+ * group column is an integer) */
+static bool agg_col_ok(const cryo_filter *f, const cryo_att *atts, const cryo_agg_col &q, uint32_t *max_att, bool floats)
 {
     if (q.rsv != 0 || q.rsv2 != 0 || q.att == 0 || q.att > f->natts) return false;
-    if (q.type < CRYO_KEY_INT2 || q.type > CRYO_KEY_INT8) return false;
-    const int size = q.type == CRYO_KEY_INT2 ? 2 : q.type == CRYO_KEY_INT4 ? 4 : 8;
+    if ((q.type < CRYO_KEY_INT2 || q.type > CRYO_KEY_INT8) && !(floats && type_is_float(q.type))) return false;
+    const int size = q.type == CRYO_KEY_INT2 ? 2 : (q.type == CRYO_KEY_INT4 || q.type == CRYO_KEY_FLOAT4) ? 4 : 8;
     const cryo_att &a = atts[q.att - 1];
     if (a.attlen != size || a.attalign < size) return false;
     if (q.att > *max_att) *max_att = q.att;
@@ -1414,7 +1450,7 @@ static bool agg_desc_ok(const cryo_filter *f, const cryo_att *atts, const cryo_s
     if (!filter_desc_ok(f, atts, keys, max_att)) return false;
     if ((f->flags & ~CRYO_FILTER_TRUTH) != 0 || !agg || agg->ncols == 0 || agg->ncols > CRYO_AGG_MAX_COLS || agg->rsv != 0 || !cols) return false;
     for (uint32_t j = 0; j < agg->ncols; j++)
-        if (!agg_col_ok(f, atts, cols[j], max_att)) return false;
+        if (!agg_col_ok(f, atts, cols[j], max_att, true)) return false;
     return true;
 }
 
@@ -1426,7 +1462,7 @@ static int agg_pass(cryo_codec *c, int method, const uint8_t *d_src, const uint6
     DecodePass ps(d_src, d_src_off, d_src_size, true);
     ps.run = [&](const DecodeChunk &ch) -> int {
         HIP_TRY(c, cryo::launch_agg(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.sd.d_atts, io.sd.d_keys, io.sd.nkeys, io.d_cols,
-                                    io.ncols, io.sd.max_att, io.sd.truth, (uint4 *)(io.d_blocks + ch.lo),
+                                    io.ncols, io.sd.max_att, io.sd.truth, io.sd.floats, (uint4 *)(io.d_blocks + ch.lo),
                                     io.d_cells + ch.lo * io.ncols));
         return CRYO_OK;
     };
@@ -1462,11 +1498,11 @@ static bool group_desc_ok(const cryo_filter *f, const cryo_att *atts, const cryo
     if (!filter_desc_ok(f, atts, keys, max_att)) return false;
     if ((f->flags & ~CRYO_FILTER_TRUTH) != 0 || !grp || grp->nby == 0 || grp->nby > CRYO_GROUP_MAX_BY || grp->rsv != 0 || !by) return false;
     for (uint32_t j = 0; j < grp->nby; j++)
-        if (!agg_col_ok(f, atts, by[j], max_att)) return false;
+        if (!agg_col_ok(f, atts, by[j], max_att, false)) return false;
     if (!agg) return true;
     if (agg->ncols > CRYO_AGG_MAX_COLS || agg->rsv != 0 || (agg->ncols > 0 && !cols)) return false;
     for (uint32_t j = 0; j < agg->ncols; j++)
-        if (!agg_col_ok(f, atts, cols[j], max_att)) return false;
+        if (!agg_col_ok(f, atts, cols[j], max_att, true)) return false;
     *ncols = agg->ncols;
     return true;
 }
@@ -1493,7 +1529,7 @@ static int group_pass(cryo_codec *c, int method, const uint8_t *d_src, const uin
         }
         uint8_t *side_rec = ch.own, *side_cell = ch.own + ch.K * S * sizeof(cryo_group_rec);
         HIP_TRY(c, cryo::launch_group(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.sd.d_atts, io.sd.d_keys, io.sd.nkeys, slots, io.nby,
-                                      io.ncols, io.sd.max_att, io.sd.truth, (uint4 *)(io.d_blocks + ch.lo), side_rec, side_cell, io.d_total,
+                                      io.ncols, io.sd.max_att, io.sd.truth, io.sd.floats, (uint4 *)(io.d_blocks + ch.lo), side_rec, side_cell, io.d_total,
                                       io.d_groups, io.d_cells, io.group_cap, c->lz4_opts.cus));
         return CRYO_OK;
     };
@@ -1572,7 +1608,7 @@ static int project_pass(cryo_codec *c, int method, const uint8_t *d_src, const u
         }
         uint8_t *side_rec = ch.own, *side_rows = ch.own + ch.K * S * sizeof(cryo_project_rec);
         HIP_TRY(c, cryo::launch_project(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.sd.d_atts, io.sd.d_keys, io.sd.nkeys, tab,
-                                        io.pt.ncols, io.pt.row_bytes, io.sd.max_att, io.sd.truth, (uint4 *)(io.d_blocks + ch.lo),
+                                        io.pt.ncols, io.pt.row_bytes, io.sd.max_att, io.sd.truth, io.sd.floats, (uint4 *)(io.d_blocks + ch.lo),
                                         side_rec, side_rows, io.d_total, io.d_rec, io.rec_cap, io.d_rows, io.row_cap, c->lz4_opts.cus));
         return CRYO_OK;
     };
@@ -1782,7 +1818,8 @@ static int scan_desc_device(cryo_codec *c, const cryo_filter *f, const cryo_grou
     sd.d_atts = f->atts; sd.d_keys = f->keys; sd.nkeys = f->nkeys;
     bool table_keys = false;
     const int rc = key_table_device(c, keys, f->nkeys, &sd.d_keys, &table_keys);
-    sd.truth = scan_truth(f, table_keys);
+    sd.floats = desc_has_float(keys, f->nkeys, cols, *ncols);
+    sd.truth = scan_truth(f, table_keys || sd.floats);
     return rc;
 }
 
@@ -2497,10 +2534,12 @@ int cryo_codec_fetch_blocks(cryo_codec *c, int method, const void *const *h_src,
 /* The descriptor of a host-buffer scan call: [atts 4 x natts][keys 16 x nkeys][byte-string constants][the call's extra bytes:
  * the aggregate's columns, the group's six slots], each part 16-byte aligned.  It takes the first `bytes` of c->hb_meta, where
  * the call's results follow it */
-struct ScanDescLayout { size_t t_keys = 0, t_extra = 0, bytes = 0; bool table_keys = false; };
-static ScanDescLayout scan_desc_layout(const cryo_filter *f, size_t extra_bytes)
+struct ScanDescLayout { size_t t_keys = 0, t_extra = 0, bytes = 0; bool table_keys = false, floats = false; };
+/* cols: the call's ncols aggregate columns, where it has some */
+static ScanDescLayout scan_desc_layout(const cryo_filter *f, size_t extra_bytes, const cryo_agg_col *cols = nullptr, uint32_t ncols = 0)
 {
     ScanDescLayout L;
+    L.floats = desc_has_float(f->keys, f->nkeys, cols, ncols);
     L.t_keys = ((size_t)f->natts * 4 + 15) & ~(size_t)15;
     L.t_extra = L.t_keys + (size_t)f->nkeys * 16 + key_consts_bytes(f->keys, f->nkeys, &L.table_keys);
     L.bytes = L.t_extra + extra_bytes;
@@ -2521,7 +2560,7 @@ static int scan_desc_upload(cryo_codec *c, const void *const *h_src, const uint3
     if (L.bytes > L.t_extra) memcpy(pin + L.t_extra, extra, L.bytes - L.t_extra);
     HIP_TRY(c, hipMemcpyAsync(c->hb_meta, pin, L.bytes, hipMemcpyHostToDevice, c->stream));
     c->xfer_ctr.h2d_bytes += L.bytes;
-    sd.d_atts = c->hb_meta; sd.d_keys = c->hb_meta + L.t_keys; sd.nkeys = f->nkeys; sd.max_att = max_att; sd.truth = scan_truth(f, L.table_keys);
+    sd.d_atts = c->hb_meta; sd.d_keys = c->hb_meta + L.t_keys; sd.nkeys = f->nkeys; sd.max_att = max_att; sd.floats = L.floats; sd.truth = scan_truth(f, L.table_keys || L.floats);
     return CRYO_OK;
 }
 
@@ -2607,7 +2646,7 @@ static int agg_blocks_impl(cryo_codec *c, int method, const void *const *h_src, 
     /* the descriptor with [cols 8 x ncols] as its extra bytes, then the results: [rows 16 x n][cells 40 x n x ncols] */
     cryo_agg_col cols[CRYO_AGG_MAX_COLS] = {};
     memcpy(cols, agg->cols, (size_t)agg->ncols * 8);
-    const ScanDescLayout L = scan_desc_layout(f, ((size_t)agg->ncols * 8 + 15) & ~(size_t)15);
+    const ScanDescLayout L = scan_desc_layout(f, ((size_t)agg->ncols * 8 + 15) & ~(size_t)15, cols, agg->ncols);
     const size_t t_rows = L.bytes;
     const size_t rows_bytes = n * sizeof(cryo_agg_block), cells_bytes = n * agg->ncols * sizeof(cryo_agg_cell);
     if ((rc = ensure(c, &c->hb_meta, &c->hb_meta_cap, t_rows + rows_bytes + cells_bytes + 64)) != CRYO_OK) return rc;
@@ -2673,7 +2712,7 @@ static int group_blocks_impl(cryo_codec *c, int method, const void *const *h_src
     cryo_agg_col slots[CRYO_GROUP_MAX_BY + CRYO_AGG_MAX_COLS] = {};
     memcpy(slots, grp->by, (size_t)grp->nby * 8);
     if (ncols) memcpy(slots + CRYO_GROUP_MAX_BY, agg->cols, (size_t)ncols * 8);
-    const ScanDescLayout L = scan_desc_layout(f, sizeof slots);
+    const ScanDescLayout L = scan_desc_layout(f, sizeof slots, slots + CRYO_GROUP_MAX_BY, ncols);
     const size_t t_total = L.bytes, t_rows = t_total + 16;
     const size_t rows_bytes = n * sizeof(cryo_group_block), t_recs = t_rows + rows_bytes, t_cells = t_recs + cap * sizeof(cryo_group_rec);
     if ((rc = ensure(c, &c->hb_meta, &c->hb_meta_cap, t_cells + cap * ncols * sizeof(cryo_agg_cell) + 64)) != CRYO_OK) return rc;

@@ -11,7 +11,8 @@
  *                     are read at addresses that depend on the loop counter only, so they are uniform loads; what differs per
  *                     lane is the offset, the null bit and the varlena branch.  A byte-string key (CRYO_KEY_BYTES) reads its
  *                     constant the same way, a word per trip, and the payload bytewise; a descriptor with one runs
- *                     k_filter_match<true>, every other k_filter_match<false>.  Keys are evaluated as the walk passes their
+ *                     k_filter_match<true>, every other k_filter_match<false>; a descriptor with a float key (CRYO_KEY_FLOAT4,
+ *                     CRYO_KEY_FLOAT8) runs k_filterf_match, the same body with the walk's FLOATS parameter set.  Keys are evaluated as the walk passes their
  *                     column (the walk itself is filter_walk.h's, shared with agg.hip).  A key's value is loaded at its proven alignment (tuples start at multiples of 8, hoff is one,
  *                     attalign >= attlen is the argument rule); everything else of a tuple is read bytewise or, the three header
  *                     fields, at their fixed even offsets.  No load leaves [t, t + len): every read is preceded by its bound.
@@ -38,17 +39,18 @@ namespace cryo {
 constexpr uint32_t kFilterPiece = 256u * 8u;  /* packed bytes one workgroup copies per turn */
 
 /* the walk of filter_walk.h without capture: 0 a match, kFilterNoMatch, kFilterTuple or -- BYTES -- kFilterUndecided */
-template <bool BYTES>
+template <bool BYTES, bool FLOATS = false>
 __device__ inline uint32_t filter_tuple(const uint8_t *__restrict__ t, uint32_t len, bool live, const FilterAtt *__restrict__ atts,
                                         const FilterKey *__restrict__ keys, uint32_t nkeys, uint32_t max_att)
 {
-    return walk_tuple<false>(t, len, live, atts, keys, nkeys, max_att, nullptr, 0u, nullptr, WalkKeys<BYTES>());
+    return walk_tuple<false, kAggMaxCols, BYTES, false, FLOATS>(t, len, live, atts, keys, nkeys, max_att, nullptr, 0u, nullptr,
+                                                                 WalkKeys<BYTES>());
 }
 
 /* One sweep over a block's items.  WRITE = false: the sums {MAXALIGNed bytes of the matches, matches, bad items}.  WRITE = true:
  * the side table's entries in position order; `overlap` drops the matches.  An undecided tuple is a bad item: counted, and listed
  * with its status and no bytes. */
-template <bool WRITE, bool BYTES>
+template <bool WRITE, bool BYTES, bool FLOATS = false>
 __device__ inline void filter_sweep(const uint8_t *__restrict__ p, uint32_t B, uint32_t n, uint32_t upper, uint32_t lane,
                                     const FilterAtt *__restrict__ atts, const FilterKey *__restrict__ keys, uint32_t nkeys,
                                     uint32_t max_att, bool overlap, uint4 *__restrict__ side, uint64_t &bytes, uint32_t &n_match,
@@ -65,7 +67,7 @@ __device__ inline void filter_sweep(const uint8_t *__restrict__ p, uint32_t B, u
             if (!heap_item(it, upper, B, src, len)) status = kFilterItem;
         }
         const bool live = valid && status != kFilterItem;
-        const uint32_t verdict = filter_tuple<BYTES>(p + src, len, live, atts, keys, nkeys, max_att);
+        const uint32_t verdict = filter_tuple<BYTES, FLOATS>(p + src, len, live, atts, keys, nkeys, max_att);
         if (live) status = verdict;
         const bool match = status == 0u, bad = status == kFilterItem || status == kFilterTuple || (BYTES && status == kFilterUndecided);
         const unsigned long long mm = __ballot(match), mb = __ballot(bad);
@@ -99,12 +101,13 @@ __device__ inline void filter_sweep(const uint8_t *__restrict__ p, uint32_t B, u
     n_bad = bads;
 }
 
-template <bool BYTES>
-__global__ void __launch_bounds__(256)
-k_filter_match(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, uint32_t cnt,
-               const int32_t *__restrict__ dec_status, const FilterAtt *__restrict__ atts, const FilterKey *__restrict__ keys,
-               uint32_t nkeys, uint32_t max_att, uint32_t count_only, uint32_t side_stride, uint4 *__restrict__ blocks,
-               uint4 *__restrict__ side, uint64_t *__restrict__ sum)
+/* the body of k_filter_match and of k_filterf_match, the kernel of descriptors with a float key */
+template <bool BYTES, bool FLOATS>
+__device__ inline void filter_block_body(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, uint32_t cnt,
+                                         const int32_t *__restrict__ dec_status, const FilterAtt *__restrict__ atts,
+                                         const FilterKey *__restrict__ keys, uint32_t nkeys, uint32_t max_att, uint32_t count_only,
+                                         uint32_t side_stride, uint4 *__restrict__ blocks, uint4 *__restrict__ side,
+                                         uint64_t *__restrict__ sum)
 {
     /* the wave's number through readfirstlane: the compiler then knows the block, its header and the trip counts to be the same
      * in all 64 lanes, and keeps them and the descriptor reads in scalar registers */
@@ -122,12 +125,12 @@ k_filter_match(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B,
             status = kFilterHeader;
         else {
             n_items = n; /* lower <= B: n <= side_stride */
-            filter_sweep<false, BYTES>(p, B, n, upper, lane, atts, keys, nkeys, max_att, false, nullptr, bytes, n_match, n_bad);
+            filter_sweep<false, BYTES, FLOATS>(p, B, n, upper, lane, atts, keys, nkeys, max_att, false, nullptr, bytes, n_match, n_bad);
             if (!count_only) {
                 const bool overlap = bytes > (uint64_t)(B - upper);
                 uint64_t b2;
                 uint32_t m2, x2;
-                filter_sweep<true, BYTES>(p, B, n, upper, lane, atts, keys, nkeys, max_att, overlap, side + (uint64_t)k * side_stride, b2,
+                filter_sweep<true, BYTES, FLOATS>(p, B, n, upper, lane, atts, keys, nkeys, max_att, overlap, side + (uint64_t)k * side_stride, b2,
                                    m2, x2);
                 if (overlap) { status = kFilterOverlap; n_match = 0; bytes = 0; }
             }
@@ -141,6 +144,28 @@ k_filter_match(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B,
             sum[cnt + k] = (uint64_t)n_match + n_bad;
         }
     }
+}
+
+template <bool BYTES>
+__global__ void __launch_bounds__(256)
+k_filter_match(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, uint32_t cnt,
+               const int32_t *__restrict__ dec_status, const FilterAtt *__restrict__ atts, const FilterKey *__restrict__ keys,
+               uint32_t nkeys, uint32_t max_att, uint32_t count_only, uint32_t side_stride, uint4 *__restrict__ blocks,
+               uint4 *__restrict__ side, uint64_t *__restrict__ sum)
+{
+    filter_block_body<BYTES, false>(dec, dec_stride, B, cnt, dec_status, atts, keys, nkeys, max_att, count_only, side_stride, blocks,
+                                    side, sum);
+}
+
+/* k_filter_match<true> whose walk also maps the columns of float keys: the one verdict path, the truth table's */
+__global__ void __launch_bounds__(256)
+k_filterf_match(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, uint32_t cnt,
+                const int32_t *__restrict__ dec_status, const FilterAtt *__restrict__ atts, const FilterKey *__restrict__ keys,
+                uint32_t nkeys, uint32_t max_att, uint32_t count_only, uint32_t side_stride, uint4 *__restrict__ blocks,
+                uint4 *__restrict__ side, uint64_t *__restrict__ sum)
+{
+    filter_block_body<true, true>(dec, dec_stride, B, cnt, dec_status, atts, keys, nkeys, max_att, count_only, side_stride, blocks,
+                                  side, sum);
 }
 
 /* base[k], base[cnt + 1 + k]: the bytes / records before block k of the chunk, counted from the call's start; entries cnt of both:
@@ -228,17 +253,18 @@ k_filter_copy(uint32_t cnt, const uint8_t *__restrict__ dec, uint64_t dec_stride
 
 hipError_t launch_filter(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
                          const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, uint32_t max_att,
-                         uint32_t truth, bool count_only, uint4 *d_blocks, uint4 *d_side, uint64_t *d_sum, uint64_t *d_base, uint64_t *d_running,
+                         uint32_t truth, bool floats, bool count_only, uint4 *d_blocks, uint4 *d_side, uint64_t *d_sum, uint64_t *d_base, uint64_t *d_running,
                          uint8_t *d_dst, uint64_t dst_cap, uint2 *d_rec, uint64_t rec_cap, bool chunk_relative, int cus)
 {
     if (cnt == 0) return hipSuccess;
     if ((dec_stride & 15u) != 0 || (((uintptr_t)d_dec | (uintptr_t)d_blocks | (uintptr_t)d_side) & 15u) != 0 ||
         (((uintptr_t)d_dst | (uintptr_t)d_rec | (uintptr_t)d_keys) & 7u) != 0 || ((uintptr_t)d_atts & 3u) != 0 || block_size < 16u ||
-        nkeys > 4u || truth > 0xFFFFu)
+        nkeys > 4u || truth > 0xFFFFu || (floats && truth == 0u))
         return hipErrorInvalidValue;
     const uint32_t stride = filter_side_stride(block_size);
-    /* the integer-only descriptor keeps its own instantiation: the code it had before byte-string keys */
-    hipLaunchKernelGGL(truth ? k_filter_match<true> : k_filter_match<false>, dim3((cnt + 3u) / 4u), dim3(256), 0, s, d_dec,
+    /* the integer-only descriptor keeps its own instantiation: the code it had before byte-string keys; a float key has a kernel
+     * of its own */
+    hipLaunchKernelGGL(floats ? k_filterf_match : truth ? k_filter_match<true> : k_filter_match<false>, dim3((cnt + 3u) / 4u), dim3(256), 0, s, d_dec,
                        dec_stride, block_size, cnt, d_dec_status, (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys | truth << 16, max_att,
                        count_only ? 1u : 0u, stride, d_blocks, d_side, d_sum);
     hipError_t e = hipGetLastError();

@@ -10,6 +10,10 @@
  * So does the truth table (CRYO_FILTER_TRUTH): the second instantiation keeps, per tuple, the mask of keys that are true and the
  * mask of keys that are undecided, and reads the verdict off a 16-bit table that rides in the high half of its nkeys argument --
  * the caller's under the flag, the AND table from the host otherwise, so that it has one verdict path.
+ * Float keys (CRYO_KEY_FLOAT4, CRYO_KEY_FLOAT8) are a further template parameter, FLOATS, of the walk: the kernels of float
+ * descriptors (k_filterf_match, k_projectf_block, k_aggf_block, k_groupf_block) set it, every other instantiation is textually
+ * what it was.  With it a loaded column value is mapped onto the signed integer whose order is the float order (float_map)
+ * when the key's type is a float type; the host has mapped the key's constant the same way, so the compare is filter_compare's.
  */
 #pragma once
 #include <hip/hip_runtime.h>
@@ -27,6 +31,8 @@ constexpr uint32_t kOpIn = 9, kOpNotIn = 10;  /* set keys: rsv the members, valu
 constexpr uint32_t kSetLinear = 8u;           /* sets up to this size are scanned, larger ones searched; where the scan stops paying
                                                  is not measured: tools/set_key_cost.py reports both sides of this figure */
 constexpr uint32_t kAggMaxCols = 4u;
+constexpr uint32_t kKeyFloat4 = 8u, kKeyFloat8 = 9u; /* CRYO_KEY_FLOAT4, CRYO_KEY_FLOAT8 */
+constexpr uint64_t kFloatNan = 0x7FF8000000000000ull; /* the canonical NaN a float cell reports */
 
 struct FilterAtt { int16_t attlen; uint8_t attalign, rsv; };                           /* cryo_att */
 struct FilterKey { uint16_t att; uint8_t type, op; uint32_t rsv; int64_t value; };    /* cryo_scan_key */
@@ -59,6 +65,46 @@ __device__ inline bool filter_compare(uint32_t op, int64_t v, int64_t k)
     case kOpNe: return v != k;
     default: return false; /* the host lets no other op through */
     }
+}
+
+/* The bits of the IEEE double that equals the IEEE single of bits f, in integer arithmetic: exact for every value, a subnormal
+ * included, whatever the wave's denormal mode; a NaN keeps its sign and its payload's high bits */
+__device__ inline uint64_t float4_widen(uint32_t f)
+{
+    const uint64_t sign = (uint64_t)(f >> 31) << 63;
+    uint32_t e = (f >> 23) & 0xFFu, m = f & 0x7FFFFFu;
+    if (e == 255u) return sign | 0x7FF0000000000000ull | (uint64_t)m << 29;
+    if (e == 0u) {
+        if (m == 0u) return sign;
+        const uint32_t sh = (uint32_t)__clz((int)m) - 8u; /* 1 .. 23: the leading one goes to bit 23 */
+        m = (m << sh) & 0x7FFFFFu;
+        return sign | (uint64_t)(897u - sh) << 52 | (uint64_t)m << 29; /* 2^(-126 - sh): 1023 - 126 - sh */
+    }
+    return sign | (uint64_t)(e + 896u) << 52 | (uint64_t)m << 29; /* 1023 - 127 */
+}
+
+/* The signed integer whose order is the float order of the double of bits b (PostgreSQL's float8_cmp_internal: -Inf < finite <
+ * +Inf < NaN, all NaNs equal, -0 = +0): a NaN INT64_MAX, a zero 0, else b with its low 63 bits flipped when negative.  Its own
+ * inverse apart from those two cases (float_unmap) */
+__device__ inline int64_t float_map(uint64_t b)
+{
+    const uint64_t mag = b & 0x7FFFFFFFFFFFFFFFull;
+    if (mag > 0x7FF0000000000000ull) return INT64_MAX;
+    if (mag == 0u) return 0;
+    return (int64_t)(b ^ ((uint64_t)((int64_t)b >> 63) & 0x7FFFFFFFFFFFFFFFull));
+}
+
+/* the double bits of a mapped value, canonical: the NaN kFloatNan, the zero +0 */
+__device__ inline uint64_t float_unmap(int64_t m)
+{
+    if (m == INT64_MAX) return kFloatNan;
+    return (uint64_t)m ^ ((uint64_t)(m >> 63) & 0x7FFFFFFFFFFFFFFFull);
+}
+
+/* the double bits of a column value as walk_value loaded it: a float4's 32 bits, sign-extended, are widened */
+__device__ inline uint64_t float_bits(int64_t raw, bool is_float4)
+{
+    return is_float4 ? float4_widen((uint32_t)raw) : (uint64_t)raw;
 }
 
 /* the signed integer of attlen 2, 4 or 8 bytes at p, which is aligned to attlen */
@@ -139,8 +185,10 @@ __device__ inline bool walk_set_has(const int64_t *__restrict__ set, uint32_t n,
  * truth table W in its high half (bit m of W: a match when exactly the keys of mask m are true; monotone, the host's rule), and
  * the verdict on a good tuple with t the keys that are true and u those that are undecided is a match if W[t], no match if not
  * W[t | u], undecided otherwise; without BYTES nkeys is the count alone and the keys are ANDed.  NARROW: a captured column may have attlen 1 (the projection's
- * argument rule: attlen 1, 2, 4 or 8 and attalign at least that). */
-template <bool CAPTURE, uint32_t SLOTS = kAggMaxCols, bool BYTES = false, bool NARROW = false>
+ * argument rule: attlen 1, 2, 4 or 8 and attalign at least that).  FLOATS (with BYTES alone): a comparison key of type kKeyFloat4 or
+ * kKeyFloat8 holds its constant mapped (float_map, the host's rewrite) and the column's value is mapped before the compare;
+ * a capture stays the raw bits. */
+template <bool CAPTURE, uint32_t SLOTS = kAggMaxCols, bool BYTES = false, bool NARROW = false, bool FLOATS = false>
 __device__ inline uint32_t walk_tuple(const uint8_t *__restrict__ t, uint32_t len, bool live, const FilterAtt *__restrict__ atts,
                                       const FilterKey *__restrict__ keys, uint32_t nkeys, uint32_t max_att,
                                       const AggCol *__restrict__ cols, uint32_t ncols,
@@ -221,7 +269,9 @@ __device__ inline uint32_t walk_tuple(const uint8_t *__restrict__ t, uint32_t le
                 else walk_note<BYTES>(pass, tmask, k, val && filter_compare(key.op, c, 0));
             } else {
                 /* attlen is the key type's size and pos a multiple of it: the argument rule */
-                const int64_t v = val ? walk_value(t + pos, a.attlen) : 0;
+                int64_t v = val ? walk_value(t + pos, a.attlen) : 0;
+                if (FLOATS && key.type >= kKeyFloat4 && key.type <= kKeyFloat8) /* uniform */
+                    v = float_map(float_bits(v, key.type == kKeyFloat4));
                 walk_note<BYTES>(pass, tmask, k, val && filter_compare(key.op, v, key.value));
             }
         }

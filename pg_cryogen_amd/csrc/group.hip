@@ -29,38 +29,15 @@
  *                    total the chunk before left in device memory; it writes first_group into the rows.
  *   k_group_copy     a grid stride over the blocks: block k's records and cells from the side area to first_group of the call's
  *                    output, word by word, cut off at group_cap.
+ * A descriptor with a float key or a float aggregate column runs group_float.hip's k_groupf_block in k_group_block's place
+ * (launch_group's `floats`); the other two kernels serve both.
  * Every device write is a vector store in plain C++.  No scratch, no global atomics.
  */
 #include "kernels.h"
 #include "filter_walk.h"
+#include "group_lds.h"
 
 namespace cryo {
-
-constexpr uint32_t kGroupMaxBy = 2u;
-constexpr uint32_t kGroupSlots = kGroupMaxBy + kAggMaxCols; /* capture slots: the group columns, then the aggregate columns */
-constexpr uint32_t kGroupWaves = 2u;                        /* blocks per workgroup */
-
-struct GroupRec { int64_t key[2]; uint32_t n_rows, nulls; };                        /* cryo_group_rec */
-struct GroupCell { uint64_t n; int64_t min, max; uint64_t sum_lo; int64_t sum_hi; }; /* cryo_agg_cell */
-static_assert(sizeof(GroupRec) == 24 && sizeof(GroupCell) == 40, "the records' layout is the header's");
-
-/* a wave's matches in LDS.  meta: bits 0 .. 1 the group columns' null bits, bits 2 .. 5 set where aggregate column j has a
- * value.  order[s]: the match at place s of the contract's order, bit 16 set when it is a group's head */
-struct GroupLds {
-    int64_t key[kGroupMaxBy][kHeapMaxItems];
-    int64_t val[kAggMaxCols][kHeapMaxItems];
-    uint32_t meta[kHeapMaxItems];
-    uint32_t order[kHeapMaxItems];
-};
-static_assert(sizeof(GroupLds) * kGroupWaves <= 65536u, "a workgroup's LDS stays within 64 KiB");
-
-/* the wave's LDS writes are done before its next LDS reads */
-__device__ inline void group_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 template <bool BYTES>
 __global__ void __launch_bounds__(64 * kGroupWaves)
@@ -253,22 +230,28 @@ k_group_copy(uint32_t cnt, uint32_t side_stride, uint32_t ncols, const uint4 *__
 
 hipError_t launch_group(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
                         const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,
-                        uint32_t nby, uint32_t ncols, uint32_t max_att, uint32_t truth, uint4 *d_blocks, void *d_side_rec, void *d_side_cell,
+                        uint32_t nby, uint32_t ncols, uint32_t max_att, uint32_t truth, bool floats, uint4 *d_blocks, void *d_side_rec, void *d_side_cell,
                         uint64_t *d_running, void *d_rec, void *d_cells, uint64_t group_cap, int cus)
 {
     if (cnt == 0) return hipSuccess;
     if ((dec_stride & 15u) != 0 || (((uintptr_t)d_dec | (uintptr_t)d_blocks) & 15u) != 0 ||
         (((uintptr_t)d_rec | (uintptr_t)d_cells | (uintptr_t)d_keys | (uintptr_t)d_slots | (uintptr_t)d_side_rec |
           (uintptr_t)d_side_cell | (uintptr_t)d_running) & 7u) != 0 ||
-        ((uintptr_t)d_atts & 3u) != 0 || block_size < 16u || nkeys > 4u || truth > 0xFFFFu || nby == 0u || nby > kGroupMaxBy || ncols > kAggMaxCols ||
+        ((uintptr_t)d_atts & 3u) != 0 || block_size < 16u || nkeys > 4u || truth > 0xFFFFu || (floats && truth == 0u) || nby == 0u || nby > kGroupMaxBy || ncols > kAggMaxCols ||
         !d_slots || !d_side_rec || !d_running || (ncols > 0u && !d_side_cell) || (group_cap > 0u && (!d_rec || (ncols > 0u && !d_cells))))
         return hipErrorInvalidValue;
     const uint32_t stride = filter_side_stride(block_size);
-    hipLaunchKernelGGL(truth ? k_group_block<true> : k_group_block<false>, dim3((cnt + kGroupWaves - 1u) / kGroupWaves), dim3(64 * kGroupWaves), 0, s, d_dec, dec_stride,
-                       block_size, cnt, d_dec_status, (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys | truth << 16,
-                       (const AggCol *)d_slots, nby, ncols, max_att, stride, d_blocks, (GroupRec *)d_side_rec,
-                       (GroupCell *)d_side_cell);
-    hipError_t e = hipGetLastError();
+    hipError_t e;
+    if (floats) /* a float key or a float aggregate column: group_float.hip's block kernel, then the same two */
+        e = launch_groupf_block(s, d_dec, dec_stride, block_size, cnt, d_dec_status, d_atts, d_keys, nkeys, d_slots, nby, ncols, max_att,
+                                truth, stride, d_blocks, d_side_rec, d_side_cell);
+    else {
+        hipLaunchKernelGGL(truth ? k_group_block<true> : k_group_block<false>, dim3((cnt + kGroupWaves - 1u) / kGroupWaves), dim3(64 * kGroupWaves), 0, s, d_dec, dec_stride,
+                           block_size, cnt, d_dec_status, (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys | truth << 16,
+                           (const AggCol *)d_slots, nby, ncols, max_att, stride, d_blocks, (GroupRec *)d_side_rec,
+                           (GroupCell *)d_side_cell);
+        e = hipGetLastError();
+    }
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_group_offsets, dim3(1), dim3(256), 0, s, cnt, d_running, d_blocks);
     e = hipGetLastError();

@@ -246,7 +246,10 @@ hipError_t launch_fetch(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride
  * of 8.  truth: 0 -- the keys are ANDed and none is of those kinds: k_filter_match<false>, which knows no such key and no table;
  * otherwise the descriptor's truth table (CRYO_FILTER_TRUTH; the AND table 1 << (2^nkeys - 1) for a descriptor without the flag
  * that has such a key), at most 16 bits: k_filter_match<true> runs and finds it in the high half of its nkeys argument
- * (filter_walk.h).  An undecided tuple gets a
+ * (filter_walk.h).  floats (here and in launch_agg, launch_group, launch_project): a key has a float type (CRYO_KEY_FLOAT4,
+ * CRYO_KEY_FLOAT8; its value in the key table is the mapped constant, float_map) or an aggregate column has one; truth is then
+ * not 0 and the float kernel runs in the <true> one's place (k_filterf_match, k_aggf_block, k_groupf_block, k_projectf_block).
+ * An undecided tuple gets a
  * record {pos, 9, 0} and counts in n_bad.  d_blocks: the chunk's rows of the block table (cryo_filter_block, 16-byte aligned).  Scratch: d_side
  * 16 bytes per possible item (cnt * filter_side_stride(block_size) entries), d_sum 2 * cnt and d_base 2 * (cnt + 1) entries.
  * d_running: the two totals {bytes, records} before the chunk in, after it out.  The chunk's tuples go to d_dst (8-byte aligned)
@@ -260,7 +263,7 @@ inline uint32_t filter_side_stride(uint32_t block_size)
 }
 hipError_t launch_filter(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
                          const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, uint32_t max_att,
-                         uint32_t truth, bool count_only, uint4 *d_blocks, uint4 *d_side, uint64_t *d_sum, uint64_t *d_base, uint64_t *d_running,
+                         uint32_t truth, bool floats, bool count_only, uint4 *d_blocks, uint4 *d_side, uint64_t *d_sum, uint64_t *d_base, uint64_t *d_running,
                          uint8_t *d_dst, uint64_t dst_cap, uint2 *d_rec, uint64_t rec_cap, bool chunk_relative, int cus);
 
 /* the scan aggregate (agg.hip) on one decoded chunk of cnt blocks (laid out as for launch_filter): k_agg_block alone.  The
@@ -272,7 +275,11 @@ hipError_t launch_filter(hipStream_t s, const uint8_t *d_dec, uint64_t dec_strid
  * over it asks the shared decode loop for no bytes of its own. */
 hipError_t launch_agg(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
                       const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_cols,
-                      uint32_t ncols, uint32_t max_att, uint32_t truth, uint4 *d_blocks, void *d_cells);
+                      uint32_t ncols, uint32_t max_att, uint32_t truth, bool floats, uint4 *d_blocks, void *d_cells);
+/* launch_agg's float branch (agg_float.hip): k_aggf_block alone, on arguments launch_agg has checked; truth is not 0 */
+hipError_t launch_aggf(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
+                       const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_cols,
+                       uint32_t ncols, uint32_t max_att, uint32_t truth, uint4 *d_blocks, void *d_cells);
 
 /* the grouped scan (group.hip) on one decoded chunk of cnt blocks (laid out as for launch_filter): k_group_block,
  * k_group_offsets, k_group_copy.  The descriptors are validated by the caller (cryo_codec.cpp, group_desc_ok): d_atts and d_keys as
@@ -285,9 +292,14 @@ hipError_t launch_agg(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, 
  * aligned) at first_group within the call; nothing at or beyond group_cap groups is written.  cus as for launch_fetch. */
 hipError_t launch_group(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
                         const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,
-                        uint32_t nby, uint32_t ncols, uint32_t max_att, uint32_t truth, uint4 *d_blocks, void *d_side_rec,
+                        uint32_t nby, uint32_t ncols, uint32_t max_att, uint32_t truth, bool floats, uint4 *d_blocks, void *d_side_rec,
                         void *d_side_cell,
                         uint64_t *d_running, void *d_rec, void *d_cells, uint64_t group_cap, int cus);
+/* launch_group's float branch (group_float.hip): k_groupf_block alone, on arguments launch_group has checked; truth is not 0 */
+hipError_t launch_groupf_block(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
+                               const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,
+                               uint32_t nby, uint32_t ncols, uint32_t max_att, uint32_t truth, uint32_t side_stride, uint4 *d_blocks,
+                               void *d_side_rec, void *d_side_cell);
 
 /* the projecting scan (project.hip) on one decoded chunk of cnt blocks (laid out as for launch_filter): k_project_block,
  * k_project_offsets, k_project_copy.  The descriptors are validated by the caller (cryo_codec.cpp, project_desc_ok): d_atts and
@@ -302,7 +314,7 @@ hipError_t launch_group(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride
  * the call; no record at or beyond rec_cap and no row at or beyond row_cap is written.  cus as for launch_fetch. */
 hipError_t launch_project(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
                           const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_cols,
-                          uint32_t ncols, uint32_t row_bytes, uint32_t max_att, uint32_t truth, uint4 *d_blocks, void *d_side_rec,
+                          uint32_t ncols, uint32_t row_bytes, uint32_t max_att, uint32_t truth, bool floats, uint4 *d_blocks, void *d_side_rec,
                           void *d_side_rows, uint64_t *d_running, void *d_rec, uint64_t rec_cap, void *d_rows, uint64_t row_cap, int cus);
 
 } // namespace cryo

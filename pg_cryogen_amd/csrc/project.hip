@@ -18,6 +18,8 @@
  *                      and column table are read at addresses that depend on loop counters only (uniform loads); no load leaves
  *                      [t, t + len).  A descriptor with a byte-string key runs k_project_block<true>, whose walk compares those
  *                      too and gives an undecided tuple a record and no row; every other descriptor runs k_project_block<false>.
+ *                      A descriptor with a float key (CRYO_KEY_FLOAT4, CRYO_KEY_FLOAT8) runs k_projectf_block, the same body
+ *                      with the walk's FLOATS parameter set.
  *   k_project_offsets  one workgroup per chunk: the tiled scan of heap_block.h (offsets_tile<2>) over rows and records at once,
  *                      from the two running totals the chunk before left in device memory; it writes rec_first and row_first.
  *   k_project_copy     a grid stride over the blocks: block k's rows and records from the side area to row_first / rec_first of
@@ -34,12 +36,13 @@ constexpr uint32_t kProjectMaxCols = 8u; /* CRYO_PROJECT_MAX_COLS */
 /* The staged column table: entry j is an AggCol to the walk (which reads att alone) and carries in `type` the column's width
  * w_j (1, 2, 4, 8) and in `rsv` its offset o_j within the row (0 .. 56, a multiple of w_j): launch_project's rule */
 
-template <bool BYTES>
-__global__ void __launch_bounds__(256)
-k_project_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, uint32_t cnt, const int32_t *__restrict__ dec_status,
-                const FilterAtt *__restrict__ atts, const FilterKey *__restrict__ keys, uint32_t nkeys,
-                const AggCol *__restrict__ cols, uint32_t ncols, uint32_t max_att, uint32_t row_words, uint32_t side_stride,
-                uint4 *__restrict__ blocks, uint2 *__restrict__ side_rec, uint2 *__restrict__ side_rows)
+/* the body of k_project_block and of k_projectf_block, the kernel of descriptors with a float key */
+template <bool BYTES, bool FLOATS>
+__device__ inline void project_block_body(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, uint32_t cnt,
+                                          const int32_t *__restrict__ dec_status, const FilterAtt *__restrict__ atts,
+                                          const FilterKey *__restrict__ keys, uint32_t nkeys, const AggCol *__restrict__ cols,
+                                          uint32_t ncols, uint32_t max_att, uint32_t row_words, uint32_t side_stride,
+                                          uint4 *__restrict__ blocks, uint2 *__restrict__ side_rec, uint2 *__restrict__ side_rows)
 {
     /* the wave's number through readfirstlane, as in k_filter_match: the block, its header and the trip counts are the same in
      * all 64 lanes and stay, with the descriptor reads, in scalar registers */
@@ -73,7 +76,7 @@ k_project_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B
                 cap.has = 0;
 #pragma unroll
                 for (uint32_t j = 0; j < kProjectMaxCols; j++) cap.v[j] = 0;
-                const uint32_t walked = walk_tuple<true, kProjectMaxCols, BYTES, true>(p + src, len, live, atts, keys, nkeys, max_att, cols,
+                const uint32_t walked = walk_tuple<true, kProjectMaxCols, BYTES, true, FLOATS>(p + src, len, live, atts, keys, nkeys, max_att, cols,
                                                                                       ncols, &cap, WalkKeys<BYTES>());
                 if (live) verdict = walked;
                 const bool match = verdict == 0u,
@@ -136,6 +139,28 @@ k_project_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B
     }
 }
 
+template <bool BYTES>
+__global__ void __launch_bounds__(256)
+k_project_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, uint32_t cnt, const int32_t *__restrict__ dec_status,
+                const FilterAtt *__restrict__ atts, const FilterKey *__restrict__ keys, uint32_t nkeys,
+                const AggCol *__restrict__ cols, uint32_t ncols, uint32_t max_att, uint32_t row_words, uint32_t side_stride,
+                uint4 *__restrict__ blocks, uint2 *__restrict__ side_rec, uint2 *__restrict__ side_rows)
+{
+    project_block_body<BYTES, false>(dec, dec_stride, B, cnt, dec_status, atts, keys, nkeys, cols, ncols, max_att, row_words, side_stride,
+                                     blocks, side_rec, side_rows);
+}
+
+/* k_project_block<true> whose walk also maps the columns of float keys; a projected float column comes back bit for bit */
+__global__ void __launch_bounds__(256)
+k_projectf_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, uint32_t cnt, const int32_t *__restrict__ dec_status,
+                 const FilterAtt *__restrict__ atts, const FilterKey *__restrict__ keys, uint32_t nkeys,
+                 const AggCol *__restrict__ cols, uint32_t ncols, uint32_t max_att, uint32_t row_words, uint32_t side_stride,
+                 uint4 *__restrict__ blocks, uint2 *__restrict__ side_rec, uint2 *__restrict__ side_rows)
+{
+    project_block_body<true, true>(dec, dec_stride, B, cnt, dec_status, atts, keys, nkeys, cols, ncols, max_att, row_words, side_stride,
+                                   blocks, side_rec, side_rows);
+}
+
 /* rec_first and row_first of every row of the chunk: the records and the rows before block k, counted from the call's start;
  * running[0], running[1]: the rows and the records before the chunk in, after it out */
 __global__ void __launch_bounds__(256)
@@ -189,19 +214,19 @@ k_project_copy(uint32_t cnt, uint32_t side_stride, uint32_t row_words, const uin
 
 hipError_t launch_project(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
                           const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_cols,
-                          uint32_t ncols, uint32_t row_bytes, uint32_t max_att, uint32_t truth, uint4 *d_blocks, void *d_side_rec,
+                          uint32_t ncols, uint32_t row_bytes, uint32_t max_att, uint32_t truth, bool floats, uint4 *d_blocks, void *d_side_rec,
                           void *d_side_rows, uint64_t *d_running, void *d_rec, uint64_t rec_cap, void *d_rows, uint64_t row_cap, int cus)
 {
     if (cnt == 0) return hipSuccess;
     if ((dec_stride & 15u) != 0 || (((uintptr_t)d_dec | (uintptr_t)d_blocks) & 15u) != 0 ||
         (((uintptr_t)d_rec | (uintptr_t)d_rows | (uintptr_t)d_keys | (uintptr_t)d_cols | (uintptr_t)d_side_rec | (uintptr_t)d_side_rows |
           (uintptr_t)d_running) & 7u) != 0 ||
-        ((uintptr_t)d_atts & 3u) != 0 || block_size < 16u || nkeys > 4u || truth > 0xFFFFu || ncols == 0u || ncols > kProjectMaxCols || row_bytes < 8u ||
+        ((uintptr_t)d_atts & 3u) != 0 || block_size < 16u || nkeys > 4u || truth > 0xFFFFu || (floats && truth == 0u) || ncols == 0u || ncols > kProjectMaxCols || row_bytes < 8u ||
         row_bytes > 8u * kProjectMaxCols || (row_bytes & 7u) != 0 || !d_cols || !d_side_rec || !d_side_rows || !d_running ||
         (rec_cap > 0u && !d_rec) || (row_cap > 0u && !d_rows))
         return hipErrorInvalidValue;
     const uint32_t stride = filter_side_stride(block_size), row_words = row_bytes / 8u;
-    hipLaunchKernelGGL(truth ? k_project_block<true> : k_project_block<false>, dim3((cnt + 3u) / 4u), dim3(256), 0, s, d_dec,
+    hipLaunchKernelGGL(floats ? k_projectf_block : truth ? k_project_block<true> : k_project_block<false>, dim3((cnt + 3u) / 4u), dim3(256), 0, s, d_dec,
                        dec_stride, block_size, cnt, d_dec_status, (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys | truth << 16,
                        (const AggCol *)d_cols, ncols, max_att, row_words, stride, d_blocks, (uint2 *)d_side_rec, (uint2 *)d_side_rows);
     hipError_t e = hipGetLastError();

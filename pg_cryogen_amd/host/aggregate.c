@@ -114,7 +114,17 @@ static int window_flush(const CryoCodecOps *ops, const CryoCodecAggOps *aops, Jo
         b.n_match = row->n_match;
         b.n_bad = row->n_bad;
         b.cells = cells[e->method] + e->at * nc;
-        for (c = 0; c < nc; c++) cell_combine(&j->t.cells[c], &b.cells[c]);
+        for (c = 0; c < nc; c++) {
+            const uint8_t type = j->agg->cols[c].type;
+            if (type == CRYO_KEY_FLOAT4 || type == CRYO_KEY_FLOAT8) { /* the same 40 bytes as a cryo_agg_cell_f */
+                cryo_agg_cell_f tf, cf;
+                memcpy(&tf, &j->t.cells[c], sizeof tf);
+                memcpy(&cf, &b.cells[c], sizeof cf);
+                cryo_agg_cell_f_combine(&tf, &cf);
+                memcpy(&j->t.cells[c], &tf, sizeof tf);
+            } else
+                cell_combine(&j->t.cells[c], &b.cells[c]);
+        }
         if (j->block_cb) j->block_cb(j->arg, &b);
     }
     for (m = 0; m < 2; m++) {

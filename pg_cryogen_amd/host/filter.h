@@ -16,6 +16,8 @@
 #ifndef CRYO_FILTER_H
 #define CRYO_FILTER_H
 
+#include <string.h>
+
 #include "check.h"
 #include "cryo_codec.h"
 
@@ -74,6 +76,15 @@ int cryo_filter_scan(CryoRel *rel, const cryo_filter *f,
  * table is monotone by construction: binders build their tables here.  Returns 0 -- no table, the codec refuses it -- for no
  * term, a null array, an empty term, a term with a bit at or beyond nkeys, or nkeys outside 1 .. CRYO_FILTER_MAX_KEYS.  The four
  * walks (this one, aggregate.h, group.h, project.h) pass flags and rsv of the descriptor through untouched. */
+/* A float key (include/cryo_codec.h, "Float keys"): column att of type CRYO_KEY_FLOAT4 or CRYO_KEY_FLOAT8 compared by op
+ * (CRYO_OP_LT .. CRYO_OP_NE) with the double x -- a float4 constant widened by the caller's cast */
+static inline cryo_scan_key cryo_filter_float_key(uint16_t att, uint8_t type, uint8_t op, double x)
+{
+    cryo_scan_key k = {att, type, op, 0, 0};
+    memcpy(&k.value, &x, sizeof k.value);
+    return k;
+}
+
 static inline uint32_t cryo_filter_truth_dnf(const uint32_t *terms, uint32_t nterms, uint32_t nkeys)
 {
     uint32_t w = 0, i, m;

@@ -19,7 +19,8 @@
  *
  * Where it does not pay: one block per call, and high cardinality -- a block of 290 distinct groups returns 64 + 40 * ncols bytes
  * per tuple, more than the filter returns for a narrow tuple.  More than two group columns, non-integer keys and HAVING go
- * through filter.h.
+ * through filter.h.  An aggregate column may be a float column (CRYO_KEY_FLOAT4, CRYO_KEY_FLOAT8): its cell is a cryo_agg_cell_f, and
+ * the cells of one key from several blocks combine in block order with cryo_agg_cell_f_combine (aggregate.h).
  */
 #ifndef CRYO_GROUP_H
 #define CRYO_GROUP_H
