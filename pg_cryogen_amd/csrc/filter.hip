@@ -4,18 +4,11 @@
  * The host (cryo_codec.cpp, filter_pass) decodes a chunk of stored streams into handle workspace with the shared decode loop
  * (decode_pass); these kernels look into every heap tuple of the decoded chunk, test up to four scan keys on it and pack the
  * tuples that pass, so that only matches leave the device:
- *   k_filter_match    one wave per block, four blocks per workgroup, as k_fetch_items.  A block the decoders rejected gets STREAM
- *                     without a load, a bad header HEADER.  Otherwise a lane takes one item per turn (290 items: five turns):
- *                     the ITEM rule (heap_item; the header's is heap_header), the TUPLE rule on the tuple's header, then the walk over the columns 1 .. the
- *                     highest key column.  That loop is the same trip for all 64 lanes -- the column descriptor and the keys
- *                     are read at addresses that depend on the loop counter only, so they are uniform loads; what differs per
- *                     lane is the offset, the null bit and the varlena branch.  A byte-string key (CRYO_KEY_BYTES) reads its
- *                     constant the same way, a word per trip, and the payload bytewise; a descriptor with one runs
- *                     k_filter_match<true>, every other k_filter_match<false>; a descriptor with a float key (CRYO_KEY_FLOAT4,
- *                     CRYO_KEY_FLOAT8) runs k_filterf_match, the same body with the walk's FLOATS parameter set.  Keys are evaluated as the walk passes their
- *                     column (the walk itself is filter_walk.h's, shared with agg.hip).  A key's value is loaded at its proven alignment (tuples start at multiples of 8, hoff is one,
- *                     attalign >= attlen is the argument rule); everything else of a tuple is read bytewise or, the three header
- *                     fields, at their fixed even offsets.  No load leaves [t, t + len): every read is preceded by its bound.
+ *   k_filter_match    one wave per block, four blocks per workgroup, as k_fetch_items: the sweep of scan_sweep.h, whose walk runs over
+ *                     the columns 1 .. the highest key column and captures nothing.  A descriptor with a byte-string key
+ *                     (CRYO_KEY_BYTES) runs k_filter_match<true>, every other k_filter_match<false>; a descriptor with a float
+ *                     key (CRYO_KEY_FLOAT4, CRYO_KEY_FLOAT8) runs k_filterf_match, the same body with the walk's FLOATS
+ *                     parameter set.
  *                     OVERLAP is a verdict on the block that is known only after the last turn, so -- as in the fetch -- a first
  *                     sweep sums and a second one writes (items and tuples come from L2 then): per record {offset inside the
  *                     block's output, the tuple's place in the decoded block, len, pos | status << 16} into a side table in
@@ -32,20 +25,11 @@
  * scratch.
  */
 #include "kernels.h"
-#include "filter_walk.h"
+#include "scan_sweep.h"
 
 namespace cryo {
 
 constexpr uint32_t kFilterPiece = 256u * 8u;  /* packed bytes one workgroup copies per turn */
-
-/* the walk of filter_walk.h without capture: 0 a match, kFilterNoMatch, kFilterTuple or -- BYTES -- kFilterUndecided */
-template <bool BYTES, bool FLOATS = false>
-__device__ inline uint32_t filter_tuple(const uint8_t *__restrict__ t, uint32_t len, bool live, const FilterAtt *__restrict__ atts,
-                                        const FilterKey *__restrict__ keys, uint32_t nkeys, uint32_t max_att)
-{
-    return walk_tuple<false, kAggMaxCols, BYTES, false, FLOATS>(t, len, live, atts, keys, nkeys, max_att, nullptr, 0u, nullptr,
-                                                                 WalkKeys<BYTES>());
-}
 
 /* One sweep over a block's items.  WRITE = false: the sums {MAXALIGNed bytes of the matches, matches, bad items}.  WRITE = true:
  * the side table's entries in position order; `overlap` drops the matches.  An undecided tuple is a bad item: counted, and listed
@@ -60,16 +44,10 @@ __device__ inline void filter_sweep(const uint8_t *__restrict__ p, uint32_t B, u
     uint32_t recs = 0, matches = 0, bads = 0;
     for (uint32_t t0 = 0; t0 < n; t0 += 64u) {
         const uint32_t i = t0 + lane;
-        const bool valid = i < n;
-        uint32_t status = kFilterNoMatch, len = 0, src = 0;
-        if (valid) {
-            const uint2 it = *reinterpret_cast<const uint2 *>(p + 8u + 8u * i);
-            if (!heap_item(it, upper, B, src, len)) status = kFilterItem;
-        }
-        const bool live = valid && status != kFilterItem;
-        const uint32_t verdict = filter_tuple<BYTES, FLOATS>(p + src, len, live, atts, keys, nkeys, max_att);
-        if (live) status = verdict;
-        const bool match = status == 0u, bad = status == kFilterItem || status == kFilterTuple || (BYTES && status == kFilterUndecided);
+        const SweepItem it = sweep_turn<false, kAggMaxCols, BYTES, false, FLOATS>(p, B, n, upper, i, atts, keys, nkeys, max_att, nullptr, 0u,
+                                                                                 nullptr); /* the walk without capture */
+        const uint32_t status = it.verdict, len = it.len, src = it.src;
+        const bool match = it.match, bad = it.bad;
         const unsigned long long mm = __ballot(match), mb = __ballot(bad);
         if (WRITE) {
             const bool rec = bad || (match && !overlap);
@@ -109,35 +87,27 @@ __device__ inline void filter_block_body(const uint8_t *__restrict__ dec, uint64
                                          uint32_t side_stride, uint4 *__restrict__ blocks, uint4 *__restrict__ side,
                                          uint64_t *__restrict__ sum)
 {
-    /* the wave's number through readfirstlane: the compiler then knows the block, its header and the trip counts to be the same
-     * in all 64 lanes, and keeps them and the descriptor reads in scalar registers */
-    const uint32_t k = blockIdx.x * 4u + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t k, lane;
+    sweep_wave(4u, k, lane);
     if (k >= cnt) return;
-    uint32_t status = 0, n_items = 0, n_match = 0, n_bad = 0;
+    uint32_t n_match = 0, n_bad = 0;
     uint64_t bytes = 0;
-    if (dec_status[k] != 0) status = kFilterStream; /* the decoders rejected the stream: nothing decoded to look at */
-    else {
-        const uint8_t *p = dec + (uint64_t)k * dec_stride;
-        const uint2 hdr = *reinterpret_cast<const uint2 *>(p);
-        uint32_t n, upper;
-        if (!heap_header(hdr, B, n, upper))
-            status = kFilterHeader;
-        else {
-            n_items = n; /* lower <= B: n <= side_stride */
-            filter_sweep<false, BYTES, FLOATS>(p, B, n, upper, lane, atts, keys, nkeys, max_att, false, nullptr, bytes, n_match, n_bad);
-            if (!count_only) {
-                const bool overlap = bytes > (uint64_t)(B - upper);
-                uint64_t b2;
-                uint32_t m2, x2;
-                filter_sweep<true, BYTES, FLOATS>(p, B, n, upper, lane, atts, keys, nkeys, max_att, overlap, side + (uint64_t)k * side_stride, b2,
-                                   m2, x2);
-                if (overlap) { status = kFilterOverlap; n_match = 0; bytes = 0; }
-            }
+    const uint8_t *__restrict__ p;
+    uint32_t n, upper; /* lower <= B: n <= side_stride */
+    uint32_t status = sweep_open(dec, dec_stride, B, dec_status, k, p, n, upper);
+    if (status == 0u) {
+        filter_sweep<false, BYTES, FLOATS>(p, B, n, upper, lane, atts, keys, nkeys, max_att, false, nullptr, bytes, n_match, n_bad);
+        if (!count_only) {
+            const bool overlap = bytes > (uint64_t)(B - upper);
+            uint64_t b2;
+            uint32_t m2, x2;
+            filter_sweep<true, BYTES, FLOATS>(p, B, n, upper, lane, atts, keys, nkeys, max_att, overlap, side + (uint64_t)k * side_stride, b2,
+                                              m2, x2);
+            if (overlap) { status = kFilterOverlap; n_match = 0; bytes = 0; }
         }
     }
     if (lane == 0) {
-        blocks[2u * k] = make_uint4(status, n_items, n_match, n_bad);
+        blocks[2u * k] = make_uint4(status, n, n_match, n_bad);
         if (count_only) blocks[2u * k + 1u] = make_uint4(0u, 0u, 0u, 0u);
         else {
             sum[k] = bytes;
@@ -257,9 +227,8 @@ hipError_t launch_filter(hipStream_t s, const uint8_t *d_dec, uint64_t dec_strid
                          uint8_t *d_dst, uint64_t dst_cap, uint2 *d_rec, uint64_t rec_cap, bool chunk_relative, int cus)
 {
     if (cnt == 0) return hipSuccess;
-    if ((dec_stride & 15u) != 0 || (((uintptr_t)d_dec | (uintptr_t)d_blocks | (uintptr_t)d_side) & 15u) != 0 ||
-        (((uintptr_t)d_dst | (uintptr_t)d_rec | (uintptr_t)d_keys) & 7u) != 0 || ((uintptr_t)d_atts & 3u) != 0 || block_size < 16u ||
-        nkeys > 4u || truth > 0xFFFFu || (floats && truth == 0u))
+    if (!scan_launch_ok(dec_stride, d_dec, d_blocks, d_atts, d_keys, (uintptr_t)d_dst | (uintptr_t)d_rec, block_size, nkeys, truth, floats) ||
+        ((uintptr_t)d_side & 15u) != 0)
         return hipErrorInvalidValue;
     const uint32_t stride = filter_side_stride(block_size);
     /* the integer-only descriptor keeps its own instantiation: the code it had before byte-string keys; a float key has a kernel

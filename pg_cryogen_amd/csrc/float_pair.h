@@ -7,6 +7,7 @@
  * in the build.  Doubles keep their subnormals on this hardware whatever the single-precision mode is.
  */
 #pragma once
+#include "agg_cell.h"
 #include "filter_walk.h"
 
 namespace cryo {
@@ -35,6 +36,27 @@ __device__ inline FloatPair float_pair_add(FloatPair x, FloatPair y)
     r.hi = h;
     r.lo = l;
     return r;
+}
+
+/* a pair kept in the two 64-bit registers where an integer column keeps its sum's halves: hi's bits in a, lo's in b */
+__device__ inline FloatPair float_pair_of(uint64_t a, uint64_t b)
+{
+    FloatPair x;
+    x.hi = __longlong_as_double((long long)a);
+    x.lo = __longlong_as_double((long long)b);
+    return x;
+}
+
+__device__ inline void float_pair_to(FloatPair x, uint64_t &a, uint64_t &b)
+{
+    a = (uint64_t)__double_as_longlong(x.hi);
+    b = (uint64_t)__double_as_longlong(x.lo);
+}
+
+/* the finite double of bits v joins the pair in (a, b) */
+__device__ inline void float_pair_take(uint64_t v, uint64_t &a, uint64_t &b)
+{
+    float_pair_to(float_pair_add(float_pair_of(a, b), float_pair_of(v, 0u)), a, b); /* bits 0: +0.0 */
 }
 
 /* the flag of the double of bits b when it is not finite, else 0 */

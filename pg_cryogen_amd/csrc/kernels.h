@@ -261,6 +261,15 @@ inline uint32_t filter_side_stride(uint32_t block_size)
     const uint32_t fit = (block_size - 8u) / 8u; /* lower <= B: no more item ids than this */
     return fit < kHeapMaxItems ? fit : kHeapMaxItems;
 }
+/* what the launchers of the four scan calls ask of their arguments alike: the chunk and the block table 16-byte aligned, the
+ * keys and -- eight: the call's other 8-byte tables and outputs, ORed -- 8-byte aligned, the column descriptor 4-byte aligned, a
+ * block that holds a header and an item, at most four keys, a table of 16 bits, and a table wherever a float kernel runs */
+inline bool scan_launch_ok(uint64_t dec_stride, const void *d_dec, const void *d_blocks, const void *d_atts, const void *d_keys,
+                           uintptr_t eight, uint32_t block_size, uint32_t nkeys, uint32_t truth, bool floats)
+{
+    return (dec_stride & 15u) == 0 && (((uintptr_t)d_dec | (uintptr_t)d_blocks) & 15u) == 0 && (((uintptr_t)d_keys | eight) & 7u) == 0 &&
+           ((uintptr_t)d_atts & 3u) == 0 && block_size >= 16u && nkeys <= 4u && truth <= 0xFFFFu && !(floats && truth == 0u);
+}
 hipError_t launch_filter(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
                          const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, uint32_t max_att,
                          uint32_t truth, bool floats, bool count_only, uint4 *d_blocks, uint4 *d_side, uint64_t *d_sum, uint64_t *d_base, uint64_t *d_running,

@@ -4,19 +4,16 @@
  * The host (cryo_codec.cpp, project_pass) decodes a chunk of stored streams into handle workspace with the shared decode loop
  * (decode_pass); these kernels look into every heap tuple of the decoded chunk as the scan aggregate does, and of every tuple that
  * passes the keys only the named fixed-width columns leave the device, as one row of 8 .. 64 bytes, with an 8-byte record:
- *   k_project_block    one wave per block, four blocks per workgroup, as k_filter_match and k_agg_block.  A block the decoders
- *                      rejected gets STREAM without a load, a bad header (heap_header, heap_block.h) HEADER.  Otherwise a lane
- *                      takes one item per turn (290 items: five turns): the ITEM rule (heap_item), then the walk of filter_walk.h
- *                      over the columns 1 .. max(highest key column, highest projected column) with eight capture slots.  The
+ *   k_project_block    one wave per block, four blocks per workgroup: the sweep of scan_sweep.h, whose walk runs over the columns
+ *                      1 .. max(highest key column, highest projected column) with eight capture slots.  The
  *                      wave ballots the matches and the bad items of the turn; a lane's rank among both is its record's place, its
  *                      rank among the matches its row's.  A matching lane assembles its row in registers -- the column table
  *                      (width and offset per column, the host's) is wave-uniform, so the word a column lands
  *                      in is a scalar compare, and NULL columns and pads are the zeros the words start with -- and writes it as
  *                      whole 8-byte words, with its record, to the block's share of a side area in handle workspace.  There is
  *                      no OVERLAP verdict: a block places at most 290 rows whatever it holds, so nothing about the block has to
- *                      be known before its first row is written and ONE sweep suffices (the filter needs two).  Descriptor, keys
- *                      and column table are read at addresses that depend on loop counters only (uniform loads); no load leaves
- *                      [t, t + len).  A descriptor with a byte-string key runs k_project_block<true>, whose walk compares those
+ *                      be known before its first row is written and ONE sweep suffices (the filter needs two).  A descriptor with
+ *                      a byte-string key runs k_project_block<true>, whose walk compares those
  *                      too and gives an undecided tuple a record and no row; every other descriptor runs k_project_block<false>.
  *                      A descriptor with a float key (CRYO_KEY_FLOAT4, CRYO_KEY_FLOAT8) runs k_projectf_block, the same body
  *                      with the walk's FLOATS parameter set.
@@ -27,7 +24,7 @@
  * Every device write is a vector store in plain C++.  No LDS beyond the scan's eight words, no scratch, no global atomics.
  */
 #include "kernels.h"
-#include "filter_walk.h"
+#include "scan_sweep.h"
 
 namespace cryo {
 
@@ -44,97 +41,74 @@ __device__ inline void project_block_body(const uint8_t *__restrict__ dec, uint6
                                           uint32_t ncols, uint32_t max_att, uint32_t row_words, uint32_t side_stride,
                                           uint4 *__restrict__ blocks, uint2 *__restrict__ side_rec, uint2 *__restrict__ side_rows)
 {
-    /* the wave's number through readfirstlane, as in k_filter_match: the block, its header and the trip counts are the same in
-     * all 64 lanes and stay, with the descriptor reads, in scalar registers */
-    const uint32_t k = blockIdx.x * 4u + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t k, lane;
+    sweep_wave(4u, k, lane);
     if (k >= cnt) return;
     const unsigned long long below = (1ull << lane) - 1ull;
     const uint32_t col_mask = (1u << ncols) - 1u; /* ncols <= 8 */
-    uint32_t status = 0, n_items = 0, n_match = 0, n_bad = 0;
-    if (dec_status[k] != 0) status = kFilterStream; /* the decoders rejected the stream: nothing decoded to look at */
-    else {
-        const uint8_t *p = dec + (uint64_t)k * dec_stride;
-        const uint2 hdr = *reinterpret_cast<const uint2 *>(p);
-        uint32_t n, upper;
-        if (!heap_header(hdr, B, n, upper))
-            status = kFilterHeader;
-        else {
-            n_items = n; /* lower <= B: n <= side_stride */
-            uint2 *out_rec = side_rec + (uint64_t)k * side_stride;
-            uint2 *out_rows = side_rows + (uint64_t)k * side_stride * row_words;
-            for (uint32_t t0 = 0; t0 < n; t0 += 64u) {
-                const uint32_t i = t0 + lane;
-                const bool valid = i < n;
-                uint32_t verdict = kFilterNoMatch, len = 0, src = 0;
-                if (valid) {
-                    const uint2 it = *reinterpret_cast<const uint2 *>(p + 8u + 8u * i); /* 8 + 8 n = lower <= B */
-                    if (!heap_item(it, upper, B, src, len)) verdict = kFilterItem;
-                }
-                const bool live = valid && verdict != kFilterItem;
-                WalkCaptureN<kProjectMaxCols> cap;
-                cap.has = 0;
+    uint32_t n_match = 0, n_bad = 0;
+    const uint8_t *__restrict__ p;
+    uint32_t n, upper; /* lower <= B: n <= side_stride */
+    const uint32_t status = sweep_open(dec, dec_stride, B, dec_status, k, p, n, upper);
+    uint2 *out_rec = side_rec + (uint64_t)k * side_stride;
+    uint2 *out_rows = side_rows + (uint64_t)k * side_stride * row_words;
+    for (uint32_t t0 = 0; t0 < n; t0 += 64u) {
+        const uint32_t i = t0 + lane;
+        WalkCaptureN<kProjectMaxCols> cap;
+        const SweepItem it = sweep_turn<true, kProjectMaxCols, BYTES, true, FLOATS>(p, B, n, upper, i, atts, keys, nkeys, max_att, cols,
+                                                                                     ncols, &cap);
+        const unsigned long long mm = __ballot(it.match), mb = __ballot(it.bad);
+        if (it.match || it.bad) { /* records in position order: the rank among the matches and the bad items */
+            const uint32_t r = n_match + n_bad + (uint32_t)__popcll((mm | mb) & below); /* below n <= side_stride */
+            out_rec[r] = make_uint2((i + 1u) | (it.match ? 0u : it.verdict << 16), it.match ? ~cap.has & col_mask : 0u);
+        }
+        if (it.match) {
+            /* the row in registers: a captured value is sign-extended and 0 when NULL, so its low w_j bytes are the
+             * column's and shifting them to o_j touches no other column (o_j is a multiple of w_j: no word is crossed) */
+            uint64_t word[kProjectMaxCols];
 #pragma unroll
-                for (uint32_t j = 0; j < kProjectMaxCols; j++) cap.v[j] = 0;
-                const uint32_t walked = walk_tuple<true, kProjectMaxCols, BYTES, true, FLOATS>(p + src, len, live, atts, keys, nkeys, max_att, cols,
-                                                                                      ncols, &cap, WalkKeys<BYTES>());
-                if (live) verdict = walked;
-                const bool match = verdict == 0u,
-                           bad = verdict == kFilterItem || verdict == kFilterTuple || (BYTES && verdict == kFilterUndecided);
-                const unsigned long long mm = __ballot(match), mb = __ballot(bad);
-                if (match || bad) { /* records in position order: the rank among the matches and the bad items */
-                    const uint32_t r = n_match + n_bad + (uint32_t)__popcll((mm | mb) & below); /* below n <= side_stride */
-                    out_rec[r] = make_uint2((i + 1u) | (match ? 0u : verdict << 16), match ? ~cap.has & col_mask : 0u);
-                }
-                if (match) {
-                    /* the row in registers: a captured value is sign-extended and 0 when NULL, so its low w_j bytes are the
-                     * column's and shifting them to o_j touches no other column (o_j is a multiple of w_j: no word is crossed) */
-                    uint64_t word[kProjectMaxCols];
+            for (uint32_t q = 0; q < kProjectMaxCols; q++) word[q] = 0;
 #pragma unroll
-                    for (uint32_t q = 0; q < kProjectMaxCols; q++) word[q] = 0;
+            for (uint32_t j = 0; j < kProjectMaxCols; j++) {
+                if (j >= ncols) continue; /* uniform */
+                const AggCol c = cols[j];  /* uniform */
+                const uint32_t w = c.type, o = c.rsv;
+                const uint64_t bits = w >= 8u ? (uint64_t)cap.v[j] : (uint64_t)cap.v[j] & ((1ull << (8u * w)) - 1ull);
+                const uint64_t placed = bits << (8u * (o & 7u));
 #pragma unroll
-                    for (uint32_t j = 0; j < kProjectMaxCols; j++) {
-                        if (j >= ncols) continue; /* uniform */
-                        const AggCol c = cols[j];  /* uniform */
-                        const uint32_t w = c.type, o = c.rsv;
-                        const uint64_t bits = w >= 8u ? (uint64_t)cap.v[j] : (uint64_t)cap.v[j] & ((1ull << (8u * w)) - 1ull);
-                        const uint64_t placed = bits << (8u * (o & 7u));
-#pragma unroll
-                        for (uint32_t q = 0; q < kProjectMaxCols; q++)
-                            if ((o >> 3) == q) word[q] |= placed; /* uniform: the register is picked by a scalar compare */
-                    }
-                    const uint32_t r = n_match + (uint32_t)__popcll(mm & below); /* below n <= side_stride */
-                    uint2 *row = out_rows + (uint64_t)r * row_words;
-                    if (BYTES) {
-                        /* with BYTES the walk leaves no scalar registers for eight loop-invariant compares q < row_words kept
-                         * as lane masks across the item loop (the compiler spilled eleven of them to vector lanes): one scalar
-                         * branch on the row's length, 1 .. 8 words, and the stores from the last word down */
+                for (uint32_t q = 0; q < kProjectMaxCols; q++)
+                    if ((o >> 3) == q) word[q] |= placed; /* uniform: the register is picked by a scalar compare */
+            }
+            const uint32_t r = n_match + (uint32_t)__popcll(mm & below); /* below n <= side_stride */
+            uint2 *row = out_rows + (uint64_t)r * row_words;
+            if (BYTES) {
+                /* with BYTES the walk leaves no scalar registers for eight loop-invariant compares q < row_words kept
+                 * as lane masks across the item loop (the compiler spilled eleven of them to vector lanes): one scalar
+                 * branch on the row's length, 1 .. 8 words, and the stores from the last word down */
 #define CRYO_ROW_WORD(q) row[q] = make_uint2((uint32_t)word[q], (uint32_t)(word[q] >> 32))
-                        switch (row_words) {
-                        case 0: break;
-                        default: CRYO_ROW_WORD(7); [[fallthrough]];
-                        case 7: CRYO_ROW_WORD(6); [[fallthrough]];
-                        case 6: CRYO_ROW_WORD(5); [[fallthrough]];
-                        case 5: CRYO_ROW_WORD(4); [[fallthrough]];
-                        case 4: CRYO_ROW_WORD(3); [[fallthrough]];
-                        case 3: CRYO_ROW_WORD(2); [[fallthrough]];
-                        case 2: CRYO_ROW_WORD(1); [[fallthrough]];
-                        case 1: CRYO_ROW_WORD(0);
-                        }
-#undef CRYO_ROW_WORD
-                    } else {
-#pragma unroll
-                        for (uint32_t q = 0; q < kProjectMaxCols; q++)
-                            if (q < row_words) row[q] = make_uint2((uint32_t)word[q], (uint32_t)(word[q] >> 32));
-                    }
+                switch (row_words) {
+                case 0: break;
+                default: CRYO_ROW_WORD(7); [[fallthrough]];
+                case 7: CRYO_ROW_WORD(6); [[fallthrough]];
+                case 6: CRYO_ROW_WORD(5); [[fallthrough]];
+                case 5: CRYO_ROW_WORD(4); [[fallthrough]];
+                case 4: CRYO_ROW_WORD(3); [[fallthrough]];
+                case 3: CRYO_ROW_WORD(2); [[fallthrough]];
+                case 2: CRYO_ROW_WORD(1); [[fallthrough]];
+                case 1: CRYO_ROW_WORD(0);
                 }
-                n_match += (uint32_t)__popcll(mm);
-                n_bad += (uint32_t)__popcll(mb);
+#undef CRYO_ROW_WORD
+            } else {
+#pragma unroll
+                for (uint32_t q = 0; q < kProjectMaxCols; q++)
+                    if (q < row_words) row[q] = make_uint2((uint32_t)word[q], (uint32_t)(word[q] >> 32));
             }
         }
+        n_match += (uint32_t)__popcll(mm);
+        n_bad += (uint32_t)__popcll(mb);
     }
     if (lane == 0) {
-        blocks[2u * k] = make_uint4(status, n_items, n_match, n_bad);
+        blocks[2u * k] = make_uint4(status, n, n_match, n_bad);
         blocks[2u * k + 1u] = make_uint4(0u, 0u, 0u, 0u); /* rec_first, row_first: k_project_offsets */
     }
 }
@@ -218,10 +192,11 @@ hipError_t launch_project(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stri
                           void *d_side_rows, uint64_t *d_running, void *d_rec, uint64_t rec_cap, void *d_rows, uint64_t row_cap, int cus)
 {
     if (cnt == 0) return hipSuccess;
-    if ((dec_stride & 15u) != 0 || (((uintptr_t)d_dec | (uintptr_t)d_blocks) & 15u) != 0 ||
-        (((uintptr_t)d_rec | (uintptr_t)d_rows | (uintptr_t)d_keys | (uintptr_t)d_cols | (uintptr_t)d_side_rec | (uintptr_t)d_side_rows |
-          (uintptr_t)d_running) & 7u) != 0 ||
-        ((uintptr_t)d_atts & 3u) != 0 || block_size < 16u || nkeys > 4u || truth > 0xFFFFu || (floats && truth == 0u) || ncols == 0u || ncols > kProjectMaxCols || row_bytes < 8u ||
+    if (!scan_launch_ok(dec_stride, d_dec, d_blocks, d_atts, d_keys,
+                        (uintptr_t)d_rec | (uintptr_t)d_rows | (uintptr_t)d_cols | (uintptr_t)d_side_rec | (uintptr_t)d_side_rows |
+                            (uintptr_t)d_running,
+                        block_size, nkeys, truth, floats) ||
+        ncols == 0u || ncols > kProjectMaxCols || row_bytes < 8u ||
         row_bytes > 8u * kProjectMaxCols || (row_bytes & 7u) != 0 || !d_cols || !d_side_rec || !d_side_rows || !d_running ||
         (rec_cap > 0u && !d_rec) || (row_cap > 0u && !d_rows))
         return hipErrorInvalidValue;

@@ -79,11 +79,14 @@ def test_agg_source_is_in_the_build():
     assert "asm" not in re.sub(r"/\*.*?\*/", "", txt, flags=re.S)                     # plain C++ only
     assert re.search(r"^SRCS\s*:=.*\bagg\.hip\b", open(os.path.join(csrc, "Makefile")).read(), flags=re.M)
     assert "launch_agg" in open(os.path.join(csrc, "kernels.h")).read()
-    # the walk exists once: both kernels' sources take it from the shared header
+    # the walk exists once and is called once, from the sweep header that both kernels' sources take their turn from
     walk = open(os.path.join(csrc, "filter_walk.h")).read()
     assert len(re.findall(r"\bwalk_tuple\s*\(const uint8_t", walk)) == 1
+    sweep = open(os.path.join(csrc, "scan_sweep.h")).read()
+    assert '#include "filter_walk.h"' in sweep and len(re.findall(r"\bwalk_tuple<", sweep)) == 1
     for name in ("agg.hip", "filter.hip"):
         src = open(os.path.join(csrc, name)).read()
-        assert '#include "filter_walk.h"' in src and "walk_tuple<" in src and "t[22]" not in src, name   # no second header parse
+        assert '#include "scan_sweep.h"' in src and "sweep_turn<" in src and "walk_tuple<" not in src, name
+        assert "t[22]" not in src, name                                               # no second header parse
     hmk = open(os.path.join(ROOT, "pg_cryogen_amd", "host", "Makefile")).read()
     assert re.search(r"^SRCS\s*:=.*\baggregate\.c\b", hmk, flags=re.M)

@@ -104,9 +104,13 @@ def test_group_source_is_in_the_build():
     assert "asm" not in code and "atomic" not in code.replace("__ATOMIC_", "")        # plain C++ only, no global atomics
     assert re.search(r"^SRCS\s*:=.*\bgroup\.hip\b", open(os.path.join(csrc, "Makefile")).read(), flags=re.M)
     assert "launch_group" in open(os.path.join(csrc, "kernels.h")).read()
-    # the walk exists once: the three kernels' sources take it from the shared header
+    # the walk exists once and is called once, from the sweep header; the grouped scan's turn (six capture slots) is in group_lds.h
     walk = open(os.path.join(csrc, "filter_walk.h")).read()
     assert len(re.findall(r"\bwalk_tuple\s*\(const uint8_t", walk)) == 1
-    assert '#include "filter_walk.h"' in txt and "walk_tuple<true, kGroupSlots>" in txt and "t[22]" not in txt
+    sweep = open(os.path.join(csrc, "scan_sweep.h")).read()
+    assert '#include "filter_walk.h"' in sweep and len(re.findall(r"\bwalk_tuple<", sweep)) == 1
+    lds = open(os.path.join(csrc, "group_lds.h")).read()
+    assert '#include "scan_sweep.h"' in lds and "sweep_turn<true, kGroupSlots, BYTES" in lds and "walk_tuple<" not in lds
+    assert '#include "group_lds.h"' in txt and "group_matches<BYTES" in txt and "walk_tuple<" not in txt and "t[22]" not in txt
     hmk = open(os.path.join(ROOT, "pg_cryogen_amd", "host", "Makefile")).read()
     assert re.search(r"^SRCS\s*:=.*\bgroup\.c\b", hmk, flags=re.M)

@@ -113,10 +113,13 @@ def test_project_source_is_in_the_build():
     assert "asm" not in code and "atomic" not in code                        # plain C++ only, no global atomics
     assert re.search(r"^SRCS\s*:=.*\bproject\.hip\b", open(os.path.join(csrc, "Makefile")).read(), flags=re.M)
     assert "launch_project" in open(os.path.join(csrc, "kernels.h")).read()
-    # the walk exists once: the four kernels' sources take it from the shared header
+    # the walk exists once and is called once, from the sweep header that the four kernels' sources take their turn from
     walk = open(os.path.join(csrc, "filter_walk.h")).read()
     assert len(re.findall(r"\bwalk_tuple\s*\(const uint8_t", walk)) == 1
-    assert '#include "filter_walk.h"' in txt and "walk_tuple<true, kProjectMaxCols, BYTES" in txt and "t[22]" not in txt
+    sweep = open(os.path.join(csrc, "scan_sweep.h")).read()
+    assert '#include "filter_walk.h"' in sweep and len(re.findall(r"\bwalk_tuple<", sweep)) == 1
+    assert '#include "scan_sweep.h"' in txt and "sweep_turn<true, kProjectMaxCols, BYTES" in txt and "walk_tuple<" not in txt
+    assert "t[22]" not in txt
     assert "offsets_tile" in txt
     hmk = open(os.path.join(ROOT, "pg_cryogen_amd", "host", "Makefile")).read()
     assert re.search(r"^SRCS\s*:=.*\bproject\.c\b", hmk, flags=re.M)
