@@ -32,6 +32,8 @@ struct CopyLds {
     uint8_t *in;                   /* kInRing + 16: input ring; the extra bytes mirror its first 16 (16-byte reads near the end) */
     uint32_t *mmeta;               /* 64: dependent match -> (start of its match inside the batch minus its position in match space: 11 bits) | offset << 11 */
     uint32_t *mbm;                 /* kBmW + kNc: bitmap of match starts in match space, then per-chunk bases */
+    /* seq_copy expects the bitmap words zero and leaves them so: once at the kernel's start */
+    __device__ inline void zero_bitmap(const uint32_t lane) const { if (lane < kBmW) mbm[lane] = 0u; }
 };
 
 /*
@@ -60,7 +62,9 @@ __device__ inline void lane_runs(uint8_t *ring, const uint8_t *sbase, uint32_t r
             if (go && di + 16u > R) spill = di + 16u - R;
             const uint32_t step = go ? 16u : 0u;
             sv += step; dv += step; rem -= step; it += step;
-            go = rem >= 16u;
+            /* a remainder of exactly 16 is the lap's (one copy that ends where the run ends), not another turn of the whole
+             * wave; a far run has no lap, and 16 bytes would fall through the piece ladder: it keeps its turn */
+            go = rem >= (far ? 16u : 17u);
         } while (wave_any(go));
     }
     /* what is left of a run that already moved 16 bytes: one more 16-byte copy that ends where the run ends (it
@@ -196,8 +200,7 @@ __device__ inline void seq_copy(Wave<R> &w, const CopyLds<R, TMAX> &L, const uin
     const uint32_t drank = __builtin_amdgcn_mbcnt_hi((uint32_t)(depm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)depm, 0u));
 
     {
-    if (lane < kBmW) L.mbm[lane] = 0u;
-    LDS_FENCE();
+    /* (the bitmap words are zero: the kernel's start and the end of the match space before left them so) */
     if (dep) {
         /* bit (start - 1) for every dependent match that starts at a position >= 1 of match space: the number of set
          * bits BELOW a position is the rank of the match it belongs to.
@@ -205,6 +208,18 @@ __device__ inline void seq_copy(Wave<R> &w, const CopyLds<R, TMAX> &L, const uin
         static_assert(TMAX < 2048u, "11 bits");
         L.mmeta[drank] = (mrel - mcum) | (off << 11); /* off < 2^21: LZ4's 16 bits, zstd's window */
         if (mcum != 0u) atomicOr(&L.mbm[(mcum - 1u) >> 5], 1u << ((mcum - 1u) & 31u));
+    }
+    {
+        /* bits before each match-space chunk: those below byte 64c are the dependent matches with 1 <= mcum <= 64c, which is
+         * the rank of the match that holds byte 64c (the rank-0 match has mcum 0 and sets no bit) -- so the lane whose match
+         * covers [mcum, mend) writes its rank for every boundary in there.  Only a match above 64 bytes has more than one
+         * (LZ4's reach 273 in a batch, zstd's go beyond); 64c < mend <= TMAX keeps c below kNc. */
+        uint32_t c = (mcum + 63u) >> 6;
+        if ((c << 6) < mend) L.mbm[kBmW + c] = drank;
+        if (wave_any(mlx > 64u)) {
+            for (c++; wave_any((c << 6) < mend); c++)
+                if ((c << 6) < mend) L.mbm[kBmW + c] = drank;
+        }
     }
     LDS_FENCE();
     }
@@ -227,18 +242,6 @@ __device__ inline void seq_copy(Wave<R> &w, const CopyLds<R, TMAX> &L, const uin
     }
     LDS_FENCE();
     stamp(st, 5);
-    {
-        /* bits before each match-space chunk */
-        static_assert(kNc <= 64, "one lane per chunk");
-        uint32_t cnt = 0;
-        if (lane < kNc) {
-            const uint2 wv = *reinterpret_cast<const uint2 *>(&L.mbm[lane * 2u]);
-            cnt = (uint32_t)(__popc(wv.x) + __popc(wv.y));
-        }
-        const uint32_t exc = scan64_incl(cnt) - cnt;
-        if (lane < kNc) L.mbm[kBmW + lane] = exc;
-    }
-    LDS_FENCE();
 
     /* ---- match space: chunks in order ---- */
     {
@@ -300,6 +303,7 @@ __device__ inline void seq_copy(Wave<R> &w, const CopyLds<R, TMAX> &L, const uin
             }
         }
     }
+    L.zero_bitmap(lane); /* for the next batch: its atomicOr then waits for nothing */
     stamp(st, 6);
     w.op = op0 + T; /* flushed by the next batch (or the general path), together with its own requests */
 }

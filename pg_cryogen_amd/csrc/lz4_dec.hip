@@ -305,6 +305,7 @@ k_lz4_dec_ring(const uint8_t *__restrict__ src_base, const uint64_t *__restrict_
     Wave<R> w;
     const WaveLds<R> L = {s_ring[wid], s_in[wid], s_d1[wid], s_d2[wid], s_d4[wid],
                           reinterpret_cast<uint32_t *>(s_d1[wid]), s_bm[wid], s_lut};
+    if (lane < CopyLds<R, kTMax>::kBmW) L.bm[lane] = 0u; /* the copy engine expects its bitmap zero and leaves it so */
     {
         uint32_t v = 0;
 #pragma unroll

@@ -354,6 +354,7 @@ k_lz4_dec_seq(const uint8_t *__restrict__ src_base, const uint64_t *__restrict__
 
     Wave<R> w;
     const CopyLds<R, kT2> L = {s_ring[wid], s_in[wid], s_mmeta[wid], s_mbm[wid]};
+    L.zero_bitmap(lane);
     w.ring = L.ring;
     w.in = L.in;
     w.lane = lane;
@@ -610,6 +611,7 @@ k_lz4_dec_dual(const uint8_t *__restrict__ src_base, const uint64_t *__restrict_
     if (role == 1u) {
         /* ---- wave B: the output-ring half of every batch ---- */
         const CopyLds<R, kT2> L = {D.ring, D.in, D.mmeta, D.mbm};
+        L.zero_bitmap(lane);
         uint32_t buf = 0;
         for (;;) {
             DUAL_BARRIER();
@@ -820,7 +822,7 @@ hipError_t launch_lz4_decompress_indexed(hipStream_t s, const uint8_t *d_src, co
                 h_st[0], h_st[1], h_st[2], h_st[3], h_st[4], h_st[5]);
         unsigned long long tot = 0;
         for (int k = 0; k < 8; k++) tot += h_st[8 + k];
-        static const char *nm[8] = {"stage", "decode+validate", "flush", "requests", "bitmap+meta", "lane runs", "chunk bases+match space", "general+other"};
+        static const char *nm[8] = {"stage", "decode+validate", "flush", "requests", "bitmap+meta+bases", "lane runs", "match space", "general+other"};
         for (int k = 0; k < 8; k++) fprintf(stderr, "[lz4 seq cycles] %-16s %5.1f%%\n", nm[k], 100.0 * (double)h_st[8 + k] / (double)(tot ? tot : 1));
         fprintf(stderr, "[lz4 seq stops] not a candidate %llu, offset outside the window %llu, chain %llu, literal 255-run %llu, match 255-run %llu, "
                         "overlapping match %llu, offset too far %llu, end of input %llu, batch full (T) %llu, end of output %llu, far and long %llu\n",

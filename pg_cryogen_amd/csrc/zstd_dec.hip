@@ -305,6 +305,7 @@ k_zstd_dec(const uint8_t *__restrict__ src_base, const uint64_t *__restrict__ sr
     st.on = stats != nullptr; /* diagnostic phase stamps (CRYO_ZSTD_STATS) */
     if (st.on) st.t0 = __builtin_amdgcn_s_memtime();
     uint8_t *litbuf = workspace + (uint64_t)blockIdx.x * kLitBuf;
+    if (lane < CopyLds<ZR, kTMax>::kBmW) L.bm[lane] = 0u; /* the copy engine expects its bitmap zero and leaves it so */
 
     /* with a list (the batch pipeline's irregular frames) decode blocks list_base + list[0 .. *list_n) */
     if (list) n_blocks = uni(*list_n);

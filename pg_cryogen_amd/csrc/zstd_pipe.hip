@@ -1694,6 +1694,7 @@ __global__ void __launch_bounds__(64, kZexecOcc) k_zexec(ZPipe P)
     const uint8_t *src = P.src_base + uni64(P.src_off[blk]);
     const uint32_t nblk = uni(P.frames[f].nblk);
     const uint32_t B = P.B;
+    if (lane < CopyLds<kZR, kZT>::kBmW) L.bm[lane] = 0u; /* the copy engine expects its bitmap zero and leaves it so */
     Stats st = {};
     Wave<kZR> w;
     w.ring = L.ring;
