@@ -440,8 +440,8 @@ def test_check_recode_and_fetch(c, oracle, stock, method, param):
 
 # ---------------- the upper limit ----------------
 def test_block_size_limit_of_every_entry_point(c):
-    """block_size = 0x7E000000 is taken and 0x7E000001 (check and fetch: 0x7E000000 + 8, they want multiples of 8) gets
-    CRYO_E_ARG from every entry point that takes a block size -- with no blocks, so that nothing is launched"""
+    """block_size = 0x7E000000 is taken and 0x7E000001 (check, fetch and the four scans: 0x7E000000 + 8, they want multiples
+    of 8) gets CRYO_E_ARG from every entry point that takes a block size -- with no blocks, so that nothing is launched"""
     L, h = cc.lib(), c.h
     one = np.zeros(64, np.uint8)
     p = one.ctypes.data
@@ -451,9 +451,31 @@ def test_block_size_limit_of_every_entry_point(c):
     first = np.zeros(2, np.uint64)
     total = C.c_uint64()
     d = c.alloc(256)
+    # the scan calls: valid one-column descriptors (an int4 column, no key; that column aggregated, grouped by and projected).
+    # The batch forms read their descriptors from device memory even for an empty call: real device arrays at 0, 64 and 128 of
+    # `desc`, their outputs and totals in `d`
+    desc = c.alloc(256)
+    f_h, g_h, a_h, p_h = cc.filter_desc([(4, 4)]), cc.group_desc([(1, 2)]), cc.agg_desc([(1, 2)]), cc.project_desc([1])
+    scan_total = (C.c_uint64 * 2)()
     try:
         dp = d.ptr
+        desc.upload(f_h[1], 0)
+        desc.upload(a_h[1], 64)
+        desc.upload(p_h[1], 128)
+        f_d = cc.CryoFilter(1, 0, 0, 0, desc.ptr, None)
+        a_d, g_d, p_d = cc.CryoAgg(1, 0, desc.ptr + 64), cc.CryoGroup(1, 0, desc.ptr + 64), cc.CryoProject(1, 0, desc.ptr + 128)
+        F, A, G, P = C.byref(f_d), C.byref(a_d), C.byref(g_d), C.byref(p_d)
+        FH, AH, GH, PH = C.byref(f_h[0]), C.byref(a_h[0]), C.byref(g_h[0]), C.byref(p_h[0])
+        scans = ("filter", "agg", "group", "project", "multi_filter", "multi_agg", "multi_group", "multi_project")
         calls = {
+            "filter_batch": lambda B: L.cryo_codec_filter_batch(h, 0, dp, dp, dp, B, 0, F, dp, 0, dp, 0, dp, dp),
+            "agg_batch": lambda B: L.cryo_codec_agg_batch(h, 0, dp, dp, dp, B, 0, F, A, dp, dp),
+            "group_batch": lambda B: L.cryo_codec_group_batch(h, 0, dp, dp, dp, B, 0, F, G, A, dp, dp, 0, dp, dp),
+            "project_batch": lambda B: L.cryo_codec_project_batch(h, 0, dp, dp, dp, B, 0, F, P, dp, 0, dp, 0, dp, dp),
+            "filter_blocks": lambda B: L.cryo_codec_filter_blocks(h, 0, ptrs, szs, 0, B, FH, p, 0, p, 0, p, scan_total),
+            "agg_blocks": lambda B: L.cryo_codec_agg_blocks(h, 0, ptrs, szs, 0, B, FH, AH, p, p),
+            "group_blocks": lambda B: L.cryo_codec_group_blocks(h, 0, ptrs, szs, 0, B, FH, GH, AH, p, p, 0, p, C.byref(total)),
+            "project_blocks": lambda B: L.cryo_codec_project_blocks(h, 0, ptrs, szs, 0, B, FH, PH, p, 0, p, 0, p, scan_total),
             "compress_batch": lambda B: L.cryo_codec_compress_batch(h, 0, 1, dp, B, B, 0, dp, B + B // 255 + 16, dp, dp),
             "decompress_batch": lambda B: L.cryo_codec_decompress_batch(h, 0, dp, dp, dp, dp, B, B, 0, dp),
             "verify_batch": lambda B: L.cryo_codec_verify_batch(h, 0, dp, B, B, 0, dp, dp, dp, dp, None),
@@ -472,7 +494,7 @@ def test_block_size_limit_of_every_entry_point(c):
                                                                 C.byref(total)),
         }
         for name, call in calls.items():
-            over = MAX_BLOCK + (8 if name.startswith(("check", "fetch")) else 1)
+            over = MAX_BLOCK + (8 if name.startswith(("check", "fetch") + scans) else 1)
             assert call(MAX_BLOCK) == cc.OK, (name, "0x7E000000 refused", call(MAX_BLOCK))
             assert call(over) == cc.E_ARG, (name, hex(over), call(over))
         # the single-block host calls have no empty form: only the refusal (the arguments are checked before anything else)
@@ -494,12 +516,17 @@ def test_block_size_limit_of_every_entry_point(c):
                 "multi_recode_blocks": lambda B: L.cryo_multi_recode_blocks(mh, 0, ptrs, szs, 0, B, 1, 3, p, 64, p, p, p),
                 "multi_fetch_blocks": lambda B: L.cryo_multi_fetch_blocks(mh, 0, ptrs, szs, 0, B, first.ctypes.data, None, None, 0,
                                                                           None, C.byref(total)),
+                "multi_filter_blocks": lambda B: L.cryo_multi_filter_blocks(mh, 0, ptrs, szs, 0, B, FH, p, 0, p, 0, p, scan_total),
+                "multi_agg_blocks": lambda B: L.cryo_multi_agg_blocks(mh, 0, ptrs, szs, 0, B, FH, AH, p, p),
+                "multi_group_blocks": lambda B: L.cryo_multi_group_blocks(mh, 0, ptrs, szs, 0, B, FH, GH, AH, p, p, 0, p, C.byref(total)),
+                "multi_project_blocks": lambda B: L.cryo_multi_project_blocks(mh, 0, ptrs, szs, 0, B, FH, PH, p, 0, p, 0, p, scan_total),
             }
             for name, call in multi.items():
-                over = MAX_BLOCK + (8 if "check" in name or "fetch" in name else 1)
+                over = MAX_BLOCK + (8 if "check" in name or "fetch" in name or name.startswith(scans) else 1)
                 assert call(MAX_BLOCK) == cc.OK, (name, "0x7E000000 refused", call(MAX_BLOCK))
                 assert call(over) == cc.E_ARG, (name, hex(over), call(over))
         finally:
             L.cryo_multi_close(mh)
     finally:
         d.free()
+        desc.free()
