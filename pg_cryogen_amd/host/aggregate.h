@@ -29,7 +29,7 @@
 
 #include <string.h>
 
-#include "check.h"
+#include "walk.h"
 #include "cryo_codec.h"
 
 /* one block's partial aggregate; cells: ncols cells in the order of the aggregate descriptor, valid during the callback only.
@@ -45,10 +45,7 @@ typedef struct {
 /* reason: a block's status (CRYO_FETCH_STREAM, CRYO_FETCH_HEADER: detail 0) or one of check.h's host-side reasons
  * (CRYO_CHECK_CHAIN: detail = the CryoError of cryo_stage_read_chain; CRYO_CHECK_METHOD: detail = the method the first page
  * names) */
-typedef struct {
-    BlockNumber block;
-    uint32 reason, detail;
-} CryoAggReport;
+typedef CryoWalkReport CryoAggReport;
 
 typedef struct {
     uint64 blocks;       /* chains examined (every page the walk took for a block start, bad ones included) */

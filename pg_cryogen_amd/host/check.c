@@ -1,7 +1,9 @@
 /* check.c -- see check.h */
 #include "check.h"
 #include "cryo_codec.h"
-#include "scan_iterator.h"
+#include "walk.h"
+
+#include <string.h>
 
 /* a codec call per method takes at most this many blocks, or this many compressed bytes, whichever comes first */
 #define CHECK_BATCH_BLOCKS 4096
@@ -65,84 +67,69 @@ static int batch_flush(const CryoCodecOps *ops, int method, CheckBatch *b, uint3
     return rc;
 }
 
+typedef struct {
+    const CryoCodecOps *ops;
+    CheckBatch batch[2];
+    uint32_t *res;
+    ReportList list;
+    CryoCheckTotals t;
+} Check;
+
+/* a block of the walk: one that was not read is a report, a stream joins the batch of its method */
+static int visit(void *arg, CryoWalkBlock *b)
+{
+    Check *c = arg;
+    CheckBatch *bt;
+    int rc = CRYO_OK;
+    if (b->method < 0) return add_report(&c->list, b->block, b->reason, b->detail, b->npages);
+    bt = &c->batch[b->method];
+    if (bt->n > 0 && bt->bytes + b->csize > CHECK_BATCH_BYTES) rc = batch_flush(c->ops, b->method, bt, c->res, &c->list, &c->t);
+    bt->comp[bt->n] = b->comp;
+    bt->size[bt->n] = b->csize;
+    bt->block[bt->n] = b->block;
+    bt->npages[bt->n] = b->npages;
+    bt->n++;
+    bt->bytes += b->csize;
+    if (rc == CRYO_OK && bt->n == CHECK_BATCH_BLOCKS) rc = batch_flush(c->ops, b->method, bt, c->res, &c->list, &c->t);
+    return rc;
+}
+
 int cryo_check_relation(CryoRel *rel, void (*report)(void *arg, const CryoCheckReport *r), void *arg,
                         CryoCheckTotals *totals)
 {
-    const CryoCodecOps *ops = cryo_host_codec_ops();
-    const Size ba = cryo_host_codec_bound(COMP_LZ4, cryo_blcksz), bb = cryo_host_codec_bound(COMP_ZSTD, cryo_blcksz);
-    const uint32 max_chain = (uint32)cryo_pages_needed(ba > bb ? ba : bb);
-    const BlockNumber nblocks = rel->ops->nblocks(rel->handle);
-    CryoCheckTotals t = {0, 0, 0, 0};
-    CheckBatch batch[2];
-    ReportList list = {NULL, 0, 0};
-    SeqScanIterator *iter = NULL;
-    BlockNumber *chain = NULL;
-    uint32_t *res = NULL;
+    Check c;
     int m, rc = CRYO_OK;
     size_t i;
 
-    if (totals) *totals = t;
-    if (!ops) return CRYO_E_NODEV;
-    if (!ops->check_blocks) return CRYO_E_UNSUPPORTED;
-    memset(batch, 0, sizeof batch);
-    iter = cryo_seqscan_iter_create();
-    chain = malloc((size_t)max_chain * sizeof *chain);
-    res = malloc((size_t)CHECK_BATCH_BLOCKS * 2 * sizeof *res);
+    memset(&c, 0, sizeof c);
+    if (totals) *totals = c.t;
+    c.ops = cryo_host_codec_ops();
+    if (!c.ops) return CRYO_E_NODEV;
+    if (!c.ops->check_blocks) return CRYO_E_UNSUPPORTED;
+    c.res = malloc((size_t)CHECK_BATCH_BLOCKS * 2 * sizeof *c.res);
+    if (!c.res) rc = CRYO_E_NOMEM;
     for (m = 0; m < 2; m++) {
-        batch[m].comp = malloc(CHECK_BATCH_BLOCKS * sizeof *batch[m].comp);
-        batch[m].size = malloc(CHECK_BATCH_BLOCKS * sizeof *batch[m].size);
-        batch[m].block = malloc(CHECK_BATCH_BLOCKS * sizeof *batch[m].block);
-        batch[m].npages = malloc(CHECK_BATCH_BLOCKS * sizeof *batch[m].npages);
-        if (!batch[m].comp || !batch[m].size || !batch[m].block || !batch[m].npages) rc = CRYO_E_NOMEM;
+        CheckBatch *bt = &c.batch[m];
+        bt->comp = malloc(CHECK_BATCH_BLOCKS * sizeof *bt->comp);
+        bt->size = malloc(CHECK_BATCH_BLOCKS * sizeof *bt->size);
+        bt->block = malloc(CHECK_BATCH_BLOCKS * sizeof *bt->block);
+        bt->npages = malloc(CHECK_BATCH_BLOCKS * sizeof *bt->npages);
+        if (!bt->comp || !bt->size || !bt->block || !bt->npages) rc = CRYO_E_NOMEM;
     }
-    if (!iter || !chain || !res) rc = CRYO_E_NOMEM;
-
-    while (rc == CRYO_OK) {
-        const BlockNumber b = cryo_seqscan_iter_next(iter);
-        char *comp = NULL;
-        Size csize = 0;
-        CompressionMethod method = COMP_LZ4;
-        TransactionId xid = 0;
-        uint32 nb = 0, j;
-        CryoError err;
-        if (!BlockNumberIsValid(b) || b >= nblocks) break;
-        err = cryo_stage_read_chain(rel, b, &comp, &csize, &method, &xid, chain, max_chain, &nb);
-        if (err == CRYO_ERR_EMPTY_BLOCK) { t.empty_pages++; continue; }
-        t.blocks++;
-        /* the chain's continuation pages are not block starts (a chain that broke off keeps the pages it did read) */
-        for (j = 1; j < nb; j++) cryo_seqscan_iter_exclude(iter, chain[j], true);
-        if (err != CRYO_ERR_SUCCESS) { rc = add_report(&list, b, CRYO_CHECK_CHAIN, (uint32)err, nb); continue; }
-        if (method != COMP_LZ4 && method != COMP_ZSTD) {
-            free(comp);
-            rc = add_report(&list, b, CRYO_CHECK_METHOD, (uint32)method, nb);
-            continue;
-        }
-        {
-            CheckBatch *bt = &batch[method];
-            if (bt->n > 0 && bt->bytes + csize > CHECK_BATCH_BYTES) rc = batch_flush(ops, (int)method, bt, res, &list, &t);
-            bt->comp[bt->n] = comp;
-            bt->size[bt->n] = (uint32_t)csize;
-            bt->block[bt->n] = b;
-            bt->npages[bt->n] = nb;
-            bt->n++;
-            bt->bytes += csize;
-            if (rc == CRYO_OK && bt->n == CHECK_BATCH_BLOCKS) rc = batch_flush(ops, (int)method, bt, res, &list, &t);
-        }
-    }
+    if (rc == CRYO_OK) rc = cryo_walk_relation(rel, visit, &c, &c.t.blocks, &c.t.empty_pages);
     for (m = 0; m < 2; m++) {
-        if (rc == CRYO_OK && batch[m].comp) rc = batch_flush(ops, m, &batch[m], res, &list, &t);
-        if (batch[m].comp) batch_clear(&batch[m]);
-        free(batch[m].comp); free(batch[m].size); free(batch[m].block); free(batch[m].npages);
+        CheckBatch *bt = &c.batch[m];
+        if (rc == CRYO_OK) rc = batch_flush(c.ops, m, bt, c.res, &c.list, &c.t);
+        if (bt->comp) batch_clear(bt);
+        free(bt->comp); free(bt->size); free(bt->block); free(bt->npages);
     }
     /* the walk meets blocks in ascending order, the batches answer later: the reports are sorted before they go out */
-    if (list.n) qsort(list.r, list.n, sizeof *list.r, cmp_report);
-    t.bad = list.n;
+    if (c.list.n) qsort(c.list.r, c.list.n, sizeof *c.list.r, cmp_report);
+    c.t.bad = c.list.n;
     if (report)
-        for (i = 0; i < list.n; i++) report(arg, &list.r[i]);
-    if (totals) *totals = t;
-    free(list.r);
-    free(res);
-    free(chain);
-    cryo_seqscan_iter_free(iter);
+        for (i = 0; i < c.list.n; i++) report(arg, &c.list.r[i]);
+    if (totals) *totals = c.t;
+    free(c.list.r);
+    free(c.res);
     return rc;
 }

@@ -16,7 +16,7 @@
 #ifndef CRYO_FETCH_H
 #define CRYO_FETCH_H
 
-#include "check.h"
+#include "walk.h"
 
 /* one page of a TID bitmap: TBMIterateResult's fields */
 typedef struct {
@@ -37,10 +37,7 @@ typedef struct {
 /* reason: a cryo_fetch_status (detail: the position asked for; for CRYO_FETCH_STREAM, _HEADER and _BADREQ, which hold for the
  * whole block, one report per page with the first position asked for), or one of check.h's host-side reasons (CRYO_CHECK_CHAIN:
  * detail = the CryoError of cryo_stage_read_chain; CRYO_CHECK_METHOD: detail = the method the first page names) */
-typedef struct {
-    BlockNumber block;
-    uint32 reason, detail;
-} CryoFetchReport;
+typedef CryoWalkReport CryoFetchReport;
 
 typedef struct {
     uint64 pages;            /* pages handed in */
@@ -55,6 +52,9 @@ typedef struct {
 /* a codec call per method takes at most this many chains, or this many compressed bytes, whichever comes first */
 #define CRYO_FETCH_WINDOW_BLOCKS 4096
 #define CRYO_FETCH_WINDOW_BYTES ((Size)256 << 20)
+#ifdef CRYO_HOST_TEST_HOOKS
+void cryo_fetch_set_window(int blocks, Size bytes); /* test builds only: lower the window; 0, 0 restores the constants */
+#endif
 
 /* Fetches the tuples the pages name.  Pages come in ascending block order, as a TID bitmap iterates; tuples are delivered
  * through tuple(arg, t) in page order, then position order.  A lossy page asks for positions 1 .. 290 and delivers up to the first

@@ -1,41 +1,19 @@
 /* filter.c -- see filter.h */
 #include "filter.h"
-#include "scan_iterator.h"
-
-#include <sys/mman.h>
 
 #define FILTER_MAX_ITEMS (MaxHeapTuplesPerPage - 1) /* records a block can have: one per item */
 
-static int window_blocks = CRYO_FILTER_WINDOW_BLOCKS;
-static Size window_bytes = CRYO_FILTER_WINDOW_BYTES;
+static CryoWindowLimits window = {CRYO_FILTER_WINDOW_BLOCKS, CRYO_FILTER_WINDOW_BYTES};
 #ifdef CRYO_HOST_TEST_HOOKS
 void cryo_filter_set_window(int blocks, Size bytes)
 {
-    window_blocks = blocks > 0 && blocks < CRYO_FILTER_WINDOW_BLOCKS ? blocks : CRYO_FILTER_WINDOW_BLOCKS;
-    window_bytes = bytes > 0 && bytes < CRYO_FILTER_WINDOW_BYTES ? bytes : CRYO_FILTER_WINDOW_BYTES;
+    window = cryo_window_limits(blocks, bytes, CRYO_FILTER_WINDOW_BLOCKS, CRYO_FILTER_WINDOW_BYTES);
 }
 #endif
 
 typedef struct {
-    BlockNumber block;
-    int method;            /* -1: not read (reason, detail say why) */
-    TransactionId xid;
-    char *comp;
-    uint32 csize;
-    uint32 reason, detail;
-    size_t at;             /* its place within the codec call of its method */
-} Entry;
-
-typedef struct {
-    Entry *e;
-    int n;
-    Size bytes;
-    /* one codec call: the streams of one method */
-    const void **src;
-    uint32_t *src_size;
-} Window;
-
-typedef struct {
+    const CryoCodecOps *ops;
+    const CryoCodecFilterOps *fops;
     const cryo_filter *f;
     void (*tuple)(void *, const CryoFilteredTuple *);
     void (*report)(void *, const CryoFilterReport *);
@@ -43,34 +21,16 @@ typedef struct {
     CryoFilterTotals t;
 } Job;
 
-static void window_clear(Window *w)
-{
-    int i;
-    for (i = 0; i < w->n; i++) free(w->e[i].comp);
-    w->n = 0;
-    w->bytes = 0;
-}
-
 static void say(Job *j, BlockNumber block, uint32 reason, uint32 detail)
 {
-    CryoFilterReport r;
-    r.block = block;
-    r.reason = reason;
-    r.detail = detail;
     j->t.reports++;
-    if (j->report) j->report(j->arg, &r);
-}
-
-/* the worst case as untouched virtual memory: only the used part is ever written */
-static void *reserve(size_t bytes)
-{
-    void *p = mmap(NULL, bytes, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS | MAP_NORESERVE, -1, 0);
-    return p == MAP_FAILED ? NULL : p;
+    cryo_walk_say(j->report, j->arg, block, reason, detail);
 }
 
 /* the window's codec calls (one per method present), then its tuples and reports in block order */
-static int window_flush(const CryoCodecOps *ops, const CryoCodecFilterOps *fops, Job *j, Window *w)
+static int window_flush(void *arg, CryoWindow *w)
 {
+    Job *j = arg;
     const bool count_only = (j->f->flags & CRYO_FILTER_COUNT_ONLY) != 0;
     char *packed[2] = {NULL, NULL};
     cryo_filter_rec *rec[2] = {NULL, NULL};
@@ -79,34 +39,26 @@ static int window_flush(const CryoCodecOps *ops, const CryoCodecFilterOps *fops,
     uint64_t total[2][2] = {{0, 0}, {0, 0}};
     int m, i, rc = CRYO_OK;
 
-    if (w->n == 0) return CRYO_OK;
     for (m = 0; m < 2 && rc == CRYO_OK; m++) {
-        size_t k = 0;
-        for (i = 0; i < w->n; i++) {
-            Entry *e = &w->e[i];
-            if (e->method != m) continue;
-            w->src[k] = e->comp;
-            w->src_size[k] = e->csize;
-            e->at = k++;
-        }
+        const size_t k = cryo_window_gather(w, m);
         if (k == 0) continue;
         rows[m] = malloc(k * sizeof *rows[m]);
         if (!rows[m]) { rc = CRYO_E_NOMEM; break; }
         if (!count_only) {
             cap[m] = k * cryo_blcksz;
             rcap[m] = k * FILTER_MAX_ITEMS;
-            packed[m] = reserve(cap[m]);
-            rec[m] = reserve(rcap[m] * sizeof *rec[m]);
+            packed[m] = cryo_walk_reserve(cap[m]);
+            rec[m] = cryo_walk_reserve(rcap[m] * sizeof *rec[m]);
             if (!packed[m] || !rec[m]) { rc = CRYO_E_NOMEM; break; }
         }
-        rc = fops->filter_blocks(ops->ctx, m, w->src, w->src_size, k, cryo_blcksz, j->f, packed[m], cap[m], rec[m], rcap[m], rows[m],
-                                 total[m]);
+        rc = j->fops->filter_blocks(j->ops->ctx, m, w->src, w->src_size, k, cryo_blcksz, j->f, packed[m], cap[m], rec[m], rcap[m],
+                                    rows[m], total[m]);
         j->t.codec_calls++;
         if (rc == CRYO_OK && (total[m][0] > cap[m] || total[m][1] > rcap[m])) rc = CRYO_E_HIP; /* not a placement */
         if (rc == CRYO_OK) j->t.bytes_back += k * sizeof *rows[m] + total[m][1] * sizeof *rec[m] + total[m][0];
     }
     for (i = 0; rc == CRYO_OK && i < w->n; i++) {
-        const Entry *e = &w->e[i];
+        const CryoWalkBlock *e = &w->e[i];
         const cryo_filter_block *row;
         uint64_t at, r, r_end;
         if (e->method < 0) { say(j, e->block, e->reason, e->detail); continue; }
@@ -136,11 +88,10 @@ static int window_flush(const CryoCodecOps *ops, const CryoCodecFilterOps *fops,
         }
     }
     for (m = 0; m < 2; m++) {
-        if (packed[m]) munmap(packed[m], cap[m]);
-        if (rec[m]) munmap(rec[m], rcap[m] * sizeof *rec[m]);
+        cryo_walk_release(packed[m], cap[m]);
+        cryo_walk_release(rec[m], rcap[m] * sizeof *rec[m]);
         free(rows[m]);
     }
-    window_clear(w);
     return rc;
 }
 
@@ -148,71 +99,18 @@ int cryo_filter_scan(CryoRel *rel, const cryo_filter *f,
                      void (*tuple)(void *arg, const CryoFilteredTuple *t),
                      void (*report)(void *arg, const CryoFilterReport *r), void *arg, CryoFilterTotals *totals)
 {
-    const CryoCodecOps *ops;
-    const CryoCodecFilterOps *fops;
-    const Size ba = cryo_host_codec_bound(COMP_LZ4, cryo_blcksz), bb = cryo_host_codec_bound(COMP_ZSTD, cryo_blcksz);
-    const uint32 max_chain = (uint32)cryo_pages_needed(ba > bb ? ba : bb);
-    const int W = window_blocks;
-    SeqScanIterator *iter = NULL;
-    BlockNumber *chain = NULL, nblocks;
     Job j;
-    Window w;
-    int rc = CRYO_OK;
+    int rc;
 
     memset(&j, 0, sizeof j);
-    memset(&w, 0, sizeof w);
     if (totals) *totals = j.t;
     if (!rel || !f) return CRYO_E_ARG;
-    ops = cryo_host_codec_ops();
-    if (!ops) return CRYO_E_NODEV;
-    fops = cryo_host_filter_ops();
-    if (!fops || !fops->filter_blocks) return CRYO_E_UNSUPPORTED;
+    j.ops = cryo_host_codec_ops();
+    if (!j.ops) return CRYO_E_NODEV;
+    j.fops = cryo_host_filter_ops();
+    if (!j.fops || !j.fops->filter_blocks) return CRYO_E_UNSUPPORTED;
     j.f = f; j.tuple = tuple; j.report = report; j.arg = arg;
-    nblocks = rel->ops->nblocks(rel->handle);
-    iter = cryo_seqscan_iter_create();
-    chain = malloc((size_t)max_chain * sizeof *chain);
-    w.e = malloc((size_t)W * sizeof *w.e);
-    w.src = malloc((size_t)W * sizeof *w.src);
-    w.src_size = malloc((size_t)W * sizeof *w.src_size);
-    if (!iter || !chain || !w.e || !w.src || !w.src_size) rc = CRYO_E_NOMEM;
-
-    while (rc == CRYO_OK) {
-        const BlockNumber b = cryo_seqscan_iter_next(iter);
-        char *comp = NULL;
-        Size csize = 0;
-        CompressionMethod sm = COMP_LZ4;
-        TransactionId xid = 0;
-        uint32 nb = 0, q;
-        CryoError err;
-        Entry *e;
-        if (!BlockNumberIsValid(b) || b >= nblocks) break;
-        err = cryo_stage_read_chain(rel, b, &comp, &csize, &sm, &xid, chain, max_chain, &nb);
-        if (err == CRYO_ERR_EMPTY_BLOCK) { j.t.empty_pages++; continue; }
-        j.t.blocks++;
-        /* the chain's continuation pages are not block starts (a chain that broke off keeps the pages it did read) */
-        for (q = 1; q < nb; q++) cryo_seqscan_iter_exclude(iter, chain[q], true);
-        if (err == CRYO_ERR_SUCCESS && w.n > 0 && w.bytes + csize > window_bytes) rc = window_flush(ops, fops, &j, &w);
-        if (rc != CRYO_OK) { free(comp); break; }
-        e = &w.e[w.n++];
-        memset(e, 0, sizeof *e);
-        e->block = b;
-        e->xid = xid;
-        if (err != CRYO_ERR_SUCCESS) {
-            e->method = -1; e->reason = CRYO_CHECK_CHAIN; e->detail = (uint32)err;
-        } else if (sm != COMP_LZ4 && sm != COMP_ZSTD) {
-            free(comp);
-            e->method = -1; e->reason = CRYO_CHECK_METHOD; e->detail = (uint32)sm;
-        } else {
-            e->method = (int)sm; e->comp = comp; e->csize = (uint32)csize;
-            w.bytes += csize;
-        }
-        if (w.n == W) rc = window_flush(ops, fops, &j, &w);
-    }
-    if (rc == CRYO_OK && w.e) rc = window_flush(ops, fops, &j, &w);
-    if (w.e) window_clear(&w);
+    rc = cryo_walk_windowed(rel, window, window_flush, &j, &j.t.blocks, &j.t.empty_pages);
     if (totals) *totals = j.t;
-    free(w.e); free(w.src); free(w.src_size);
-    free(chain);
-    if (iter) cryo_seqscan_iter_free(iter);
     return rc;
 }

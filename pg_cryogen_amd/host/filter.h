@@ -18,7 +18,7 @@
 
 #include <string.h>
 
-#include "check.h"
+#include "walk.h"
 #include "cryo_codec.h"
 
 /* data: the tuple's len bytes, zero up to MAXALIGN(len), at a MAXALIGNed address; valid during the callback only */
@@ -34,10 +34,7 @@ typedef struct {
  * (CRYO_FETCH_ITEM, CRYO_FILTER_TUPLE, or CRYO_FILTER_UNDECIDED -- a byte-string key met a compressed or external value, the
  * caller fetches the tuple and rechecks it: detail = its position), or one of check.h's host-side reasons (CRYO_CHECK_CHAIN: detail =
  * the CryoError of cryo_stage_read_chain; CRYO_CHECK_METHOD: detail = the method the first page names) */
-typedef struct {
-    BlockNumber block;
-    uint32 reason, detail;
-} CryoFilterReport;
+typedef CryoWalkReport CryoFilterReport;
 
 typedef struct {
     uint64 blocks;       /* chains examined (every page the walk took for a block start, bad ones included) */

@@ -25,7 +25,7 @@
 #ifndef CRYO_GROUP_H
 #define CRYO_GROUP_H
 
-#include "check.h"
+#include "walk.h"
 #include "cryo_codec.h"
 
 /* one block's groups: recs n_groups records in the contract's order (ascending, NULLS LAST), cells n_groups * ncols cells (group
@@ -40,10 +40,7 @@ typedef struct {
 } CryoGroupBlock;
 
 /* reason and detail as CryoAggReport's */
-typedef struct {
-    BlockNumber block;
-    uint32 reason, detail;
-} CryoGroupReport;
+typedef CryoWalkReport CryoGroupReport;
 
 typedef struct {
     uint64 blocks;       /* chains examined (every page the walk took for a block start, bad ones included) */

@@ -16,7 +16,7 @@
 #ifndef CRYO_PROJECT_H
 #define CRYO_PROJECT_H
 
-#include "check.h"
+#include "walk.h"
 #include "cryo_codec.h"
 
 /* data: the row's row_bytes bytes in the layout of include/cryo_codec.h (CRYO_PROJECT_COL_OFFSET / CRYO_PROJECT_ROW_BYTES), at a MAXALIGNed address;
@@ -31,10 +31,7 @@ typedef struct {
 } CryoProjectedRow;
 
 /* reason and detail as CryoFilterReport's (OVERLAP does not occur) */
-typedef struct {
-    BlockNumber block;
-    uint32 reason, detail;
-} CryoProjectReport;
+typedef CryoWalkReport CryoProjectReport;
 
 typedef struct {
     uint64 blocks;       /* chains examined (every page the walk took for a block start, bad ones included) */

@@ -30,6 +30,9 @@
 
 #define CRYO_RECOMPRESS_WINDOW_BLOCKS 4096
 #define CRYO_RECOMPRESS_WINDOW_BYTES ((Size)256 << 20)
+#ifdef CRYO_HOST_TEST_HOOKS
+void cryo_recompress_set_window(int blocks, Size bytes); /* test builds only: lower the window; 0, 0 restores the constants */
+#endif
 
 typedef struct {
     uint64 blocks;       /* chains the walk took for a block start: recoded + verbatim + skipped */
