@@ -1047,6 +1047,23 @@ int cryo_codec_compare_batch(cryo_codec *c, const void *d_a, uint64_t a_stride,
                              uint64_t n_blocks, uint64_t *d_mismatch);
 /* host-side reference of the checksum, for tests */
 uint64_t cryo_checksum64(const void *p, size_t n);
+/* Every handle-owned buffer filled with one byte over its whole capacity (test support: a handle's buffers are grow-only, never
+ * cleared and shared between very different calls, so a call is correct only if it writes what it reads; a test fills them with
+ * a hostile byte between two calls and compares the second call's results with the reference).  Waits for all the handle's
+ * streams (main, transfer, zstd lanes and sides, the LZ4 side stream), fills the device buffers with hipMemsetAsync on the main stream and, once
+ * that stream is idle again, the pinned staging buffers with a host memset: nothing is pending when it returns.  *out (may be NULL): the bytes filled per buffer, 0 for one that is not
+ * allocated; a capacity that differs between two reports means the buffer was reallocated in between.  Not filled: the keyed
+ * pool (it holds valid blocks by contract).  The device copies of set-key lists and byte-string constants are not cached: the
+ * device-resident scan calls rebuild them in d_keytab at every call, the host-buffer calls in the pinned and meta staging, so
+ * they are filled with the rest.  Allocates nothing, frees nothing, changes no option; on no production path. */
+typedef struct {
+    uint64_t d_ws, d_vfy, d_rec;          /* kernels' workspace, verification / scan chunk, recode chunk */
+    uint64_t hb_src, hb_dst, hb_meta;     /* device staging of the host-buffer calls */
+    uint64_t d_in, d_out, d_scalars;      /* single-block scratch; d_scalars: its offset, size and status words (16 bytes) */
+    uint64_t d_keytab;                    /* key table of the device-resident scan calls */
+    uint64_t pin, pipe_pin[4];            /* pinned host staging */
+} cryo_codec_fill_report;
+int cryo_codec_debug_fill(cryo_codec *c, int value, cryo_codec_fill_report *out);
 
 /* ---- timing on the handle's stream (HIP events) ---- */
 int cryo_codec_timer_start(cryo_codec *c);

@@ -106,7 +106,7 @@ ABI_SYMBOLS = [
     "cryo_codec_agg_batch", "cryo_codec_agg_blocks", "cryo_multi_agg_blocks",
     "cryo_codec_group_batch", "cryo_codec_group_blocks", "cryo_multi_group_blocks",
     "cryo_codec_project_batch", "cryo_codec_project_blocks", "cryo_multi_project_blocks",
-    "cryo_codec_lz4_index_cap", "cryo_codec_lz4_index_rows",
+    "cryo_codec_lz4_index_cap", "cryo_codec_lz4_index_rows", "cryo_codec_debug_fill",
 ]
 
 
@@ -140,6 +140,13 @@ class CryoProject(C.Structure):
 class TransferCounters(C.Structure):
     _fields_ = [("h2d_bytes", C.c_uint64), ("d2h_bytes", C.c_uint64), ("pool_hits", C.c_uint64),
                 ("pool_misses", C.c_uint64), ("pool_blocks", C.c_uint64), ("pool_capacity", C.c_uint64)]
+
+
+class FillReport(C.Structure):
+    """cryo_codec_fill_report: the bytes cryo_codec_debug_fill filled per handle-owned buffer"""
+    _fields_ = [("d_ws", C.c_uint64), ("d_vfy", C.c_uint64), ("d_rec", C.c_uint64), ("hb_src", C.c_uint64),
+                ("hb_dst", C.c_uint64), ("hb_meta", C.c_uint64), ("d_in", C.c_uint64), ("d_out", C.c_uint64),
+                ("d_scalars", C.c_uint64), ("d_keytab", C.c_uint64), ("pin", C.c_uint64), ("pipe_pin", C.c_uint64 * 4)]
 
 
 class Counters(C.Structure):
@@ -240,6 +247,7 @@ def lib():
     L.cryo_codec_lz4_index_cap.argtypes = [u32]
     L.cryo_codec_lz4_index_cap.restype = u32
     L.cryo_codec_lz4_index_rows.argtypes = [vp, vp, vp, vp, u32, u64, i32, vp, vp]
+    L.cryo_codec_debug_fill.argtypes = [vp, i32, C.POINTER(FillReport)]
     _bound = True
     return L
 
@@ -687,6 +695,16 @@ class Codec:
 
     def trim(self):
         self._chk(self.L.cryo_codec_trim(self.h), "cryo_codec_trim")
+
+    def debug_fill(self, value):
+        """test aid: wait for the handle's streams and fill every handle-owned buffer (not the keyed pool) with the byte `value`
+        over its whole capacity; returns the bytes filled per buffer as a dict (pipe_pin0 .. pipe_pin3 for the four pipeline
+        staging buffers), 0 for a buffer that is not allocated"""
+        r = FillReport()
+        self._chk(self.L.cryo_codec_debug_fill(self.h, value, C.byref(r)), "cryo_codec_debug_fill")
+        out = {f: int(getattr(r, f)) for f, _ in FillReport._fields_ if f != "pipe_pin"}
+        out.update(("pipe_pin%d" % i, int(r.pipe_pin[i])) for i in range(4))
+        return out
 
     def pool_invalidate(self, key_hi=0, everything=False):
         self._chk(self.L.cryo_codec_pool_invalidate(self.h, key_hi, 1 if everything else 0), "pool_invalidate")

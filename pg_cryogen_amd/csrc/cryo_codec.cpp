@@ -3686,6 +3686,45 @@ int cryo_codec_compare_batch(cryo_codec *c, const void *d_a, uint64_t a_stride, 
     return CRYO_OK;
 }
 
+static int sync_all_streams(cryo_codec *c)
+{
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (c->xfer) HIP_TRY(c, hipStreamSynchronize(c->xfer));
+    for (int l = 0; l < cryo::kZstdLanes; l++) {
+        if (c->aux.lane[l]) HIP_TRY(c, hipStreamSynchronize(c->aux.lane[l]));
+        if (c->aux.side[l]) HIP_TRY(c, hipStreamSynchronize(c->aux.side[l]));
+    }
+    if (c->lz4_opts.side) HIP_TRY(c, hipStreamSynchronize(c->lz4_opts.side));
+    return CRYO_OK;
+}
+
+int cryo_codec_debug_fill(cryo_codec *c, int value, cryo_codec_fill_report *out)
+{
+    DevGuard dev_(c);
+    if (!c || value < 0 || value > 255) return CRYO_E_ARG;
+    int rc = sync_all_streams(c);
+    if (rc != CRYO_OK) return rc;
+    cryo_codec_fill_report r = {};
+    struct { void *p; size_t cap; uint64_t *filled; } dev[] = {
+        {c->d_ws, c->ws_cap, &r.d_ws},         {c->d_vfy, c->vfy_cap, &r.d_vfy},       {c->d_rec, c->rec_cap, &r.d_rec},
+        {c->hb_src, c->hb_src_cap, &r.hb_src}, {c->hb_dst, c->hb_dst_cap, &r.hb_dst},  {c->hb_meta, c->hb_meta_cap, &r.hb_meta},
+        {c->d_in, c->in_cap, &r.d_in},         {c->d_out, c->out_cap, &r.d_out},       {c->d_off, sizeof(uint64_t), &r.d_scalars},
+        {c->d_size, sizeof(uint32_t), &r.d_scalars}, {c->d_status, sizeof(int32_t), &r.d_scalars},
+        {c->d_keytab, kKeyTableBytes, &r.d_keytab},
+    };
+    for (auto &b : dev) {
+        if (!b.p || b.cap == 0) continue;
+        HIP_TRY(c, hipMemsetAsync(b.p, value, b.cap, c->stream));
+        *b.filled += b.cap;
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (c->pin && c->pin_cap) { memset(c->pin, value, c->pin_cap); r.pin = c->pin_cap; }
+    for (int i = 0; i < 4; i++)
+        if (c->pipe_pin[i] && c->pipe_pin_cap[i]) { memset(c->pipe_pin[i], value, c->pipe_pin_cap[i]); r.pipe_pin[i] = c->pipe_pin_cap[i]; }
+    if (out) *out = r;
+    return CRYO_OK;
+}
+
 /* ---- timing ---- */
 int cryo_codec_timer_start(cryo_codec *c)
 {
