@@ -1,5 +1,6 @@
-"""GPU: every LZ4 and zstd decode route against the oracle on crafted LZ4 streams (tests/lz4_craft.py) and non-default zstd
-frames (tests/zstd_craft.py) -- the corpora tests/test_decode_conformance_cpu.py pins the oracle to the stock libraries on.
+"""GPU: every LZ4 and zstd decode route against the oracle on crafted LZ4 streams (tests/lz4_craft.py), non-default zstd
+frames (tests/zstd_craft.py) and hand-assembled zstd frames (tests/zstd_asm.py) -- the corpora
+tests/test_decode_conformance_cpu.py pins the oracle to the stock libraries on.
 
 For every route: status 0 exactly when the oracle returns B, then the oracle's bytes; and nothing written outside a block's
 B bytes, accepted or rejected (the device batch call with dst_stride = B + 256 over a poisoned destination, compressed items
@@ -11,6 +12,7 @@ import pytest
 
 import lz4_craft
 import oracle_lib
+import zstd_asm
 import zstd_craft
 from pg_cryogen_amd import METHOD_LZ4, METHOD_ZSTD
 from pg_cryogen_amd import codec as cc
@@ -20,7 +22,7 @@ pytestmark = pytest.mark.gpu
 POISON = 0xE7
 GAP = 256
 LZ4_SIZES = [(4096, 300), (32768, 300), (131072, 300), (300001, 150), (1 << 20, 12)]
-LZ4_SEED, ZSTD_SEED = 1, 5
+LZ4_SEED, ZSTD_SEED, CRAFT_SEED = 1, 5, 11
 
 
 def _truth(oracle, method, items, B):
@@ -49,6 +51,17 @@ def zstd_corpus(oracle):
         pytest.fail("libzstd.so.1 is needed to write the non-default frames")
     by_b = {}
     for name, B, f in zstd_craft.zstd_corpus(stock, oracle, ZSTD_SEED):
+        by_b.setdefault(B, ([], []))
+        by_b[B][0].append(name)
+        by_b[B][1].append(f)
+    return {B: list(zip(names, items, _truth(oracle, METHOD_ZSTD, items, B))) for B, (names, items) in by_b.items()}
+
+
+@pytest.fixture(scope="module")
+def crafted_corpus(oracle):
+    """{B: [(name, hand-assembled frame, the oracle's block or None)]}"""
+    by_b = {}
+    for name, B, f, _ in zstd_asm.crafted_corpus(CRAFT_SEED):
         by_b.setdefault(B, ([], []))
         by_b[B][0].append(name)
         by_b[B][1].append(f)
@@ -170,13 +183,41 @@ def test_zstd_decode_paths_on_nondefault_frames(codec, zstd_corpus, path):
                 _batch_check(codec, METHOD_ZSTD, part, B, ("zstd", path, B, shape))
 
 
+CRAFT_SIZES = [255, 256, 4096, 8192, 32768, 65791, 131072, 262144]
+
+
+@pytest.mark.parametrize("B", CRAFT_SIZES)
+@pytest.mark.parametrize("path", ZSTD_PATHS)
+def test_zstd_decode_paths_on_crafted_frames(codec, crafted_corpus, path, B):
+    """hand-assembled frames: every frame alone, chunks of at most 64 (at B = 32768 what reaches the k_zlat_* kernels), and the
+    corpus tiled to 300 frames"""
+    cases = crafted_corpus[B]
+    assert any(c[2] is not None for c in cases)
+    with _options(codec, {cc.OPT_ZSTD_DECODE_PATH: path}):
+        for shape, part in _shapes(cases, singles=len(cases), big=300 if B <= 131072 else 0):
+            _batch_check(codec, METHOD_ZSTD, part, B, ("crafted", path, B, shape))
+        if B == 32768 and path == 2:
+            # the frames at k_zlat_count's edges (total * 64 against B, total against lat_nmax) in one call the few-frames
+            # execution takes and in one of 65 frames, which it does not: the same verdicts and bytes
+            edges = [c for c in cases if c[0].startswith("B/lat_total/")]
+            assert len(edges) == 4 and all(c[2] is not None for c in edges)
+            _batch_check(codec, METHOD_ZSTD, (edges * 16)[:64], B, ("crafted", path, B, "edges64"))
+            _batch_check(codec, METHOD_ZSTD, (edges * 17)[:65], B, ("crafted", path, B, "edges65"))
+        if B == 4096 and path in (0, 2):
+            # B / 3 sequences per frame, 70 frames: twice the sequence pool's B / 6 per frame, so part of the batch leaves
+            # the pipeline for the fused kernel
+            third = [c for c in cases if c[0].startswith("B/third_of_B/")]
+            assert len(third) == 3 and all(c[2] is not None for c in third)
+            _batch_check(codec, METHOD_ZSTD, (third * 24)[:70], B, ("crafted", path, B, "third70"))
+
+
 # ---------------- host contract ----------------
 @pytest.mark.parametrize("method", [METHOD_LZ4, METHOD_ZSTD])
-def test_decompress_blocks_to_leaves_rejected_destinations_untouched(codec, lz4_corpus, zstd_corpus, method):
+def test_decompress_blocks_to_leaves_rejected_destinations_untouched(codec, lz4_corpus, zstd_corpus, crafted_corpus, method):
     """cryo_codec_decompress_blocks_to (include/cryo_codec.h): block i -> h_dst[i]; a block whose status is not CRYO_OK
     leaves its destination untouched -- one mixed batch of accepted and rejected streams into separate poisoned buffers"""
     B = 131072
-    cases = (lz4_corpus if method == METHOD_LZ4 else zstd_corpus)[B]
+    cases = lz4_corpus[B] if method == METHOD_LZ4 else zstd_corpus[B] + crafted_corpus[B]
     items, expect = [c[1] for c in cases], [c[2] for c in cases]
     assert any(e is None for e in expect) and any(e is not None for e in expect)
     n = len(items)

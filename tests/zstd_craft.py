@@ -7,7 +7,9 @@ decoders take a different path for such tables (two-level lookup in the batch pi
 walk(): the structure of a frame (header flags, window, blocks, literal section types, sequence-table modes).
 zstd_corpus(): frames libzstd writes only with non-default parameters (ZSTD_compress2): content checksums and broken
 copies of them, small windows, no content size, forced literal modes, minMatch 3, long-distance matching,
-targetCBlockSize, blocks of few sequences, and mutations of them."""
+targetCBlockSize, blocks of few sequences, and mutations of them.
+
+tests/zstd_asm.py assembles whole frames from a description (sequences, table modes, headers) and shares huf_codes()."""
 import numpy as np
 
 # 13 listed weights + 1 implied: 3 x 2^10 + 2^9 + ... + 2^0 + 2^0 = 4096 -> table log 12, code lengths 2..12
@@ -15,16 +17,26 @@ WEIGHTS = [11, 11, 11, 10, 9, 8, 7, 6, 5, 4, 3, 2, 1, 1]  # symbol 13's weight i
 LOG = 12
 
 
-def _codes():
-    """canonical codes as the decoder assigns them: weights ascending, symbols ascending inside a weight"""
+def huf_codes(weights):
+    """canonical codes as the decoder assigns them (RFC 8878 4.2.1): weights ascending, symbols ascending inside a weight.
+    weights holds every symbol's, the implied last one included.  -> ({symbol: (value, nbits)}, table log)"""
+    total = sum((1 << w) >> 1 for w in weights)
+    log = total.bit_length() - 1
+    assert total == 1 << log, weights
     codes, nxt = {}, 0
-    for w in range(1, LOG + 1):
-        for s, ws in enumerate(WEIGHTS):
+    for w in range(1, log + 1):
+        for s, ws in enumerate(weights):
             if ws == w:
                 span = 1 << (w - 1)
-                codes[s] = (nxt // span, LOG + 1 - w)  # (value, nbits)
+                codes[s] = (nxt // span, log + 1 - w)
                 nxt += span
-    assert nxt == 1 << LOG
+    assert nxt == 1 << log
+    return codes, log
+
+
+def _codes():
+    codes, log = huf_codes(WEIGHTS)
+    assert log == LOG
     return codes
 
 
