@@ -650,7 +650,8 @@ int cryo_codec_agg_batch(cryo_codec *c, int method, const void *d_src, const uin
  *
  * Descriptors.  CRYO_E_ARG when: *f breaks one of the filter's descriptor rules above; f->flags is neither 0 nor CRYO_FILTER_TRUTH; nby is 0 or above 2; a
  * group column breaks a rule of an aggregate column above (att outside 1 .. f->natts; a type that is not a cryo_key_type; the
- * column's attlen not the type's size, or its attalign below its attlen; rsv or rsv2 not zero); grp->rsv not zero; ncols above 4;
+ * column's attlen not the type's size, or its attalign below its attlen; rsv or rsv2 not zero); grp->rsv neither zero nor
+ * CRYO_GROUP_BUCKETS ("Bucketed group columns" below); ncols above 4;
  * with ncols > 0, anything cryo_codec_agg_batch refuses in *agg.  ncols == 0 is allowed here -- agg NULL, or agg->ncols 0 with
  * agg->rsv 0 (agg->cols is not looked at) --: SELECT g, count(*) ... GROUP BY g needs no cell.  A column may be a group column,
  * an aggregate column and a key column at once, and may be named twice.
@@ -685,6 +686,44 @@ typedef struct { uint32_t nby, rsv; const cryo_agg_col *by; } cryo_group;
 #define CRYO_GROUP_MAX_BY 2u
 typedef struct { uint32_t status, n_items, n_match, n_bad; uint32_t n_groups, rsv; uint64_t first_group; } cryo_group_block; /* 32 bytes, one per block */
 typedef struct { int64_t key[2]; uint32_t n_rows, nulls; } cryo_group_rec;                                    /* 24 bytes, one per group */
+/* Bucketed group columns: SELECT date_trunc('day', ts), app_id, count(*), sum(revenue) ... GROUP BY 1, 2.  A raw timestamp is
+ * unique per row; what a report groups by is its hour, day, week or month.  cryo_group keeps its 16 bytes and its meaning: with
+ * rsv == 0 a call is what it was.  With rsv == CRYO_GROUP_BUCKETS (1) the cryo_group pointer a call is handed points to a
+ * cryo_group_b -- cryo_group's two words and `by`, then `buckets`: nby entries, one per group column, a DEVICE array for
+ * cryo_codec_group_batch and a host array for cryo_codec_group_blocks / cryo_multi_group_blocks, exactly as `by` is; 8-byte
+ * aligned.  The key of group column j is then a function of its non-NULL value v (sign-extended from its type), by kind:
+ *   CRYO_BUCKET_NONE (0)    key = v, as without buckets.  flags, n, origin and value are 0.
+ *   CRYO_BUCKET_WIDTH (1)   origin = o, value = w >= 1, n = 0: key = v - ((v - o) mod w), the difference and the modulus taken in
+ *                           exact integers and the modulus in [0, w) -- o + w * floor((v - o) / w), PostgreSQL's date_bin: floored,
+ *                           not truncated, below the origin.  The key is an int64_t and is not clamped to the column's type; a
+ *                           key below INT64_MIN is not representable, and that value is undecided.
+ *   CRYO_BUCKET_BOUNDS (2)  n = the number of boundaries, 1 .. CRYO_BUCKET_BOUNDS_MAX; value = the address of n int64_t -- a device
+ *                           address for cryo_codec_group_batch, a host address for the other two --, origin = 0.  Any alignment,
+ *                           any order, duplicates allowed: the contents never decide whether the descriptor is valid, the memory
+ *                           is only read, and the library searches an ascending, duplicate-free copy of its own.  key = the
+ *                           greatest boundary <= v; a value below the smallest boundary is undecided (a caller who wants every
+ *                           value in a bucket adds INT64_MIN as a boundary).
+ * flags bit CRYO_BUCKET_INFINITE (1), with kinds 1 and 2: the column is a date or timestamp, whose type minimum and maximum (of
+ * int2, int4 or int8, by the group column's type) are -infinity and +infinity.  Such a value is its own bucket, key = v, as
+ * date_bin and date_trunc return it; a value that is not an extreme but whose key would equal one is undecided.
+ * NULL stays the NULL group.  A tuple that passes the keys but has an undecided bucket in any group column is counted in n_bad and
+ * not in n_match, and is in no group and no cell -- the rule of an undecided byte-string key --, so a block's n_rows still sum to
+ * its n_match and the caller reads a block with n_bad > 0 through the filter.  Everything else is unchanged: the order (ascending
+ * by key 1, then key 2, NULLS LAST), records, cells, first_group, group_cap, *total, chunking, float aggregate columns and every
+ * kind of key beside the grouping.  A column may be a bucketed group column, a raw aggregate column and a key at once (min(ts),
+ * max(ts) per day), and may be named twice with two different buckets (hour and day).  With every kind CRYO_BUCKET_NONE the
+ * result is byte for byte that of the rsv == 0 call.
+ * CRYO_E_ARG when: grp->rsv is neither 0 nor 1; buckets is null or not 8-byte aligned; a kind is unknown; WIDTH with value < 1 or
+ * n != 0; BOUNDS with n == 0, n > CRYO_BUCKET_BOUNDS_MAX, a null address or origin != 0; NONE with flags, n, origin or value not
+ * 0; an unknown flag bit, or CRYO_BUCKET_INFINITE with NONE; a bucket's rsv not 0. */
+#define CRYO_GROUP_BUCKETS 1u          /* cryo_group.rsv: the struct is a cryo_group_b */
+#define CRYO_BUCKET_NONE 0
+#define CRYO_BUCKET_WIDTH 1
+#define CRYO_BUCKET_BOUNDS 2
+#define CRYO_BUCKET_INFINITE 1u        /* cryo_bucket.flags */
+#define CRYO_BUCKET_BOUNDS_MAX 1024u   /* the most boundaries of a list: CRYO_KEY_SET_MAX */
+typedef struct { uint8_t kind, flags; uint16_t rsv; uint32_t n; int64_t origin; int64_t value; } cryo_bucket; /* 24 bytes, one per group column */
+typedef struct { uint32_t nby, rsv; const cryo_agg_col *by; const cryo_bucket *buckets; } cryo_group_b;       /* 24 bytes; rsv = CRYO_GROUP_BUCKETS */
 /* Device buffers.  The structs *f, *grp and *agg are host memory; f->atts, f->keys, grp->by and agg->cols are DEVICE arrays (4-byte
  * / 8-byte / 8-byte / 8-byte aligned).  The host validates the descriptors before anything is queued: it reads the arrays back on
  * the handle's stream (one wait for what the stream held before the call); from there on the call is asynchronous, with no host

@@ -69,6 +69,12 @@ GROUP_MAX_BY = 2
 GROUP_BLOCK = np.dtype([("status", "<u4"), ("n_items", "<u4"), ("n_match", "<u4"), ("n_bad", "<u4"),
                         ("n_groups", "<u4"), ("rsv", "<u4"), ("first_group", "<u8")])                             # cryo_group_block
 GROUP_REC = np.dtype([("key", "<i8", (2,)), ("n_rows", "<u4"), ("nulls", "<u4")])                                # cryo_group_rec
+# bucketed group columns: a bucket is (kind, flags, origin, value); the value of a BUCKET_BOUNDS bucket is a sequence of ints
+GROUP_BUCKETS = 1           # cryo_group.rsv: the struct is a cryo_group_b
+BUCKET_NONE, BUCKET_WIDTH, BUCKET_BOUNDS = 0, 1, 2
+BUCKET_INFINITE = 1         # a bucket's flag: the column type's extremes are -infinity and +infinity, each its own bucket
+BUCKET_BOUNDS_MAX = 1024
+BUCKET = np.dtype([("kind", "u1"), ("flags", "u1"), ("rsv", "<u2"), ("n", "<u4"), ("origin", "<i8"), ("value", "<i8")])  # cryo_bucket
 # the projecting scan (include/cryo_codec.h): a block's statuses are the aggregate's, a record's the filter's
 PROJECT_MAX_COLS = 8
 PROJECT_COL = np.dtype([("att", "<u2"), ("rsv", "<u2"), ("rsv2", "<u4")])                                       # cryo_project_col
@@ -130,6 +136,11 @@ class CryoAgg(C.Structure):
 class CryoGroup(C.Structure):
     """cryo_group: by points to a device array for group_batch, to a host array for group_blocks"""
     _fields_ = [("nby", C.c_uint32), ("rsv", C.c_uint32), ("by", C.c_void_p)]
+
+
+class CryoGroupB(CryoGroup):
+    """cryo_group_b: cryo_group with rsv = GROUP_BUCKETS and, behind by, the buckets array (device / host memory as by is)"""
+    _fields_ = [("buckets", C.c_void_p)]
 
 
 class CryoProject(C.Structure):
@@ -459,13 +470,47 @@ def agg_blocks_call(fn, handle, chk, method, comps, block_size, desc, adesc):
     return rows[:n], cells[:n]
 
 
-def group_desc(by):
+def bucket_array(buckets):
+    """buckets, a list of (kind, flags, origin, value) with one entry per group column (value: a WIDTH bucket's width, a
+    BOUNDS bucket's sequence of boundaries, in any order), as (BUCKET array, lists array, rebase): the lists lie back to back in
+    the uint8 array `lists` as little-endian int64 (behind one pad byte: at no alignment); once the caller knows where they lie --
+    host memory, or device memory after an upload -- rebase(address) sets every BOUNDS bucket's value and returns the array"""
+    b = np.zeros(max(len(buckets), 1), BUCKET)
+    parts, at, offs = [b"\0"], 1, {}
+    for j, (kind, flags, origin, value) in enumerate(buckets):
+        if kind == BUCKET_BOUNDS and value is not None and not isinstance(value, int):
+            members = b"".join(int(m).to_bytes(8, "little", signed=True) for m in value)
+            b[j] = (kind, flags, 0, len(value), origin, 0)
+            if len(value):
+                offs[j] = at
+            parts.append(members)
+            at += len(members)
+        else:
+            b[j] = (kind, flags, 0, 0, origin, value or 0)
+    lists = np.frombuffer(b"".join(parts), np.uint8).copy()
+
+    def rebase(base):
+        for j, off in offs.items():
+            b[j]["value"] = int(base) + off
+        return b
+    return b, lists, rebase
+
+
+def group_desc(by, buckets=None):
     """the group descriptor of a group call as a host array: by a list of (att, type) (att 1-based; type KEY_*).  Returns
-    (CryoGroup, by array); the struct points into the array, which the caller keeps alive"""
+    (CryoGroup, by array); the struct points into the array, which the caller keeps alive.  buckets: one (kind, flags, origin,
+    value) per group column (bucket_array) -- the struct is then a CryoGroupB, which holds the buckets array and the lists of
+    boundaries it points into (g.bucket_arr, g.bucket_lists)"""
     a = np.zeros(max(len(by), 1), AGG_COL)
     for j, (att, typ) in enumerate(by):
         a[j] = (att, typ, 0, 0)
-    return CryoGroup(len(by), 0, a.ctypes.data), a
+    if buckets is None:
+        return CryoGroup(len(by), 0, a.ctypes.data), a
+    b, lists, rebase = bucket_array(buckets)
+    rebase(lists.ctypes.data)
+    g = CryoGroupB(len(by), GROUP_BUCKETS, a.ctypes.data, b.ctypes.data)
+    g.bucket_arr, g.bucket_lists = b, lists
+    return g, a
 
 
 def group_blocks_call(fn, handle, chk, method, comps, block_size, desc, gdesc, adesc=None, group_cap=None):
@@ -845,24 +890,30 @@ class Codec:
         return agg_blocks_call(self.L.cryo_codec_agg_blocks, self.h, self._chk, method, comps, block_size, desc, adesc)
 
     def group_batch(self, method, d_src, d_off, d_sizes, block_size, n, natts, d_atts, nkeys, d_keys, nby, d_by, ncols, d_cols,
-                    d_blocks, d_groups, group_cap, d_cells, d_total, truth=None):
+                    d_blocks, d_groups, group_cap, d_cells, d_total, truth=None, buckets=None):
         """test the keys on every tuple of the n stored blocks, partition each block's matches by the nby columns d_by names and
         reduce the ncols columns d_cols names per group (both AGG_COL; d_keys: FILTER_KEY, d_atts: FILTER_ATT, device arrays):
         one GROUP_BLOCK row per block in d_blocks, one GROUP_REC per group in d_groups and ncols AGG_CELL per group in d_cells (at
         most group_cap groups are written), the call's number of groups in d_total (u64).  ncols 0: d_cols and d_cells may be
-        None.  truth: as for filter_batch.  Asynchronous once the descriptors are read back."""
+        None.  truth: as for filter_batch.  buckets: a device array of nby BUCKET entries whose lists of boundaries lie in device
+        memory (bucket_array).  Asynchronous once the descriptors are read back."""
         f = CryoFilter(natts, nkeys, *truth_flags(0, truth), d_atts.ptr if d_atts else None, d_keys.ptr if d_keys else None)
         g = CryoGroup(nby, 0, d_by.ptr if d_by else None)
+        if buckets is not None:
+            g = CryoGroupB(nby, GROUP_BUCKETS, d_by.ptr if d_by else None, buckets.ptr)
         a = CryoAgg(ncols, 0, d_cols.ptr if d_cols else None)
         self._chk(self.L.cryo_codec_group_batch(self.h, method, d_src.ptr, d_off.ptr, d_sizes.ptr, block_size, n, C.byref(f),
                                                 C.byref(g), C.byref(a), d_blocks.ptr if d_blocks else None,
                                                 d_groups.ptr if d_groups else None, group_cap, d_cells.ptr if d_cells else None,
                                                 d_total.ptr if d_total else None), "group_batch")
 
-    def group_blocks(self, method, comps, block_size, desc, gdesc, adesc=None, group_cap=None):
+    def group_blocks(self, method, comps, block_size, desc, gdesc, adesc=None, group_cap=None, buckets=None):
         """group host streams (desc: what filter_desc returns, gdesc: group_desc, adesc: agg_desc or None); returns (rows,
         records, cells, total): block i's groups are records[rows[i]["first_group"]:][:rows[i]["n_groups"]], cells has one row
-        per group and one column per aggregate column; cell_sum gives a cell's 128-bit sum"""
+        per group and one column per aggregate column; cell_sum gives a cell's 128-bit sum.  buckets: as for group_desc, for
+        gdesc's columns"""
+        if buckets is not None:
+            gdesc = group_desc([(int(c["att"]), int(c["type"])) for c in gdesc[1][:gdesc[0].nby]], buckets)
         return group_blocks_call(self.L.cryo_codec_group_blocks, self.h, self._chk, method, comps, block_size, desc, gdesc, adesc,
                                  group_cap)
 

@@ -128,7 +128,8 @@ struct cryo_codec {
     size_t ws_cap = 0;
     /* host-buffer batch API: grow-only device buffers and one pinned staging buffer */
     uint8_t *hb_src = nullptr, *hb_dst = nullptr, *hb_meta = nullptr;
-    uint8_t *d_keytab = nullptr; /* the device-resident scan calls' copy of keys and byte-string constants (kKeyTableBytes) */
+    uint8_t *d_keytab = nullptr; /* the device-resident scan calls' copy of keys and byte-string constants (kKeyTableBytes), then
+                                    the grouping's bucket table (kBucketTableBytes): kDescTablesBytes in all */
     size_t hb_src_cap = 0, hb_dst_cap = 0, hb_meta_cap = 0;
     void *pin = nullptr;
     size_t pin_cap = 0;
@@ -1150,6 +1151,8 @@ struct ScanDesc {
                                                         truth table of the <true> one (scan_truth) */
     bool floats = false;                             /* a float key or a float aggregate column: the float kernels, which have
                                                         the truth table's verdict path alone (truth is not 0 then) */
+    const void *d_buckets = nullptr;                 /* device: the grouping's bucket table under CRYO_GROUP_BUCKETS (truth is not 0
+                                                        then), else null */
 };
 struct FilterIo {
     ScanDesc sd;
@@ -1270,6 +1273,11 @@ static constexpr size_t kKeyConstMax = 8u * CRYO_KEY_SET_MAX; /* the most bytes 
 static_assert(kKeyConstMax >= CRYO_KEY_BYTES_MAX, "a list is the largest constant");
 static constexpr size_t kKeyTableBytes = CRYO_FILTER_MAX_KEYS * (sizeof(cryo_scan_key) + kKeyConstMax);
 
+/* the grouping's bucket table (below) lies behind the key table in the same allocation */
+static constexpr size_t kBucketTableBytes = CRYO_GROUP_MAX_BY * (sizeof(cryo_bucket) + 8u * CRYO_BUCKET_BOUNDS_MAX);
+static constexpr size_t kDescTablesBytes = kKeyTableBytes + kBucketTableBytes;
+static_assert(kKeyTableBytes % 16 == 0 && kBucketTableBytes % 16 == 0, "both tables are 16-byte aligned");
+
 static bool key_is_bytes(const cryo_scan_key &q) { return q.type == CRYO_KEY_BYTES && q.op >= CRYO_OP_LT && q.op <= CRYO_OP_NE; }
 static bool key_is_set(const cryo_scan_key &q) { return q.op == CRYO_OP_IN || q.op == CRYO_OP_NOT_IN; }
 static bool key_is_float(const cryo_scan_key &q) { return type_is_float(q.type) && q.op >= CRYO_OP_LT && q.op <= CRYO_OP_NE; }
@@ -1329,7 +1337,7 @@ static int key_table_device(cryo_codec *c, const cryo_scan_key *keys, uint32_t n
         HIP_TRY(c, hipMemcpyAsync((void *)where[k], (const void *)(uintptr_t)keys[k].value, len, hipMemcpyDeviceToHost, c->stream));
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (!c->d_keytab) HIP_TRY(c, hipMalloc(&c->d_keytab, kKeyTableBytes));
+    if (!c->d_keytab) HIP_TRY(c, hipMalloc(&c->d_keytab, kDescTablesBytes));
     key_table_fill(tab.data(), (uint64_t)(uintptr_t)c->d_keytab, keys, nkeys, where);
     HIP_TRY(c, hipMemcpyAsync(c->d_keytab, tab.data(), tab.size(), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream)); /* tab is the call's own: gone when it returns */
@@ -1489,16 +1497,105 @@ struct GroupIo {
 };
 } // namespace
 
-/* the grouping's descriptor rules (include/cryo_codec.h); every array is host memory here.  *max_att: the highest key, group or
- * aggregate column; *ncols: the aggregate columns (0 with a null agg) */
+/* ---- bucketed group columns (CRYO_GROUP_BUCKETS): the library's own copy ----
+ * Such a descriptor reaches the kernels (group_bucket.hip) as a bucket table: [buckets 24 x CRYO_GROUP_MAX_BY][the lists of
+ * boundaries in column order], a multiple of 16 bytes.  A list lies there as its distinct boundaries, ascending as signed 64-bit
+ * integers, in the room of the n the caller named; the table's copy of the bucket has n rewritten to the distinct count and value
+ * to the list's device address -- 8-byte aligned there, whatever the caller's address was.  The caller's arrays are only read.
+ * The device-resident call builds the table behind the key table in c->d_keytab (bucket_table_device), the host-buffer calls in
+ * the descriptor's extra bytes behind the six column slots (group_blocks_impl): the pass's fixed 256 bytes hold the slots alone. */
+
+/* where a group descriptor's buckets are: null without CRYO_GROUP_BUCKETS */
+static const cryo_bucket *group_buckets(const cryo_group *grp)
+{
+    return grp->rsv == CRYO_GROUP_BUCKETS ? reinterpret_cast<const cryo_group_b *>(grp)->buckets : nullptr;
+}
+
+/* the rules of the nby buckets at bk (host memory); a list's address is not looked at beyond null, its members never */
+static bool bucket_desc_ok(const cryo_bucket *bk, uint32_t nby)
+{
+    for (uint32_t j = 0; j < nby; j++) {
+        const cryo_bucket &b = bk[j];
+        if (b.rsv != 0 || (b.flags & ~CRYO_BUCKET_INFINITE) != 0) return false;
+        if (b.kind == CRYO_BUCKET_NONE) {
+            if (b.flags != 0 || b.n != 0 || b.origin != 0 || b.value != 0) return false;
+        } else if (b.kind == CRYO_BUCKET_WIDTH) {
+            if (b.value < 1 || b.n != 0) return false;
+        } else if (b.kind == CRYO_BUCKET_BOUNDS) {
+            if (b.n == 0 || b.n > CRYO_BUCKET_BOUNDS_MAX || b.value == 0 || b.origin != 0) return false;
+        } else return false;
+    }
+    return true;
+}
+
+/* the bytes of the bucket table of nby (valid) buckets, a multiple of 16 */
+static size_t bucket_table_bytes(const cryo_bucket *bk, uint32_t nby)
+{
+    size_t b = CRYO_GROUP_MAX_BY * sizeof(cryo_bucket);
+    for (uint32_t j = 0; j < nby; j++)
+        if (bk[j].kind == CRYO_BUCKET_BOUNDS) b += (size_t)bk[j].n * 8;
+    return (b + 15) & ~(size_t)15;
+}
+
+/* the bucket table of nby (valid) buckets at tab (zeroed, 8-byte aligned, bucket_table_bytes bytes), which will lie at device
+ * address d_tab; lists[j]: where the host finds the boundaries of bucket j */
+static void bucket_table_fill(uint8_t *tab, uint64_t d_tab, const cryo_bucket *bk, uint32_t nby, const void *const *lists)
+{
+    size_t at = CRYO_GROUP_MAX_BY * sizeof(cryo_bucket);
+    for (uint32_t j = 0; j < nby; j++) {
+        cryo_bucket b = bk[j];
+        if (b.kind == CRYO_BUCKET_BOUNDS) {
+            int64_t *m = reinterpret_cast<int64_t *>(tab + at);
+            memcpy(m, lists[j], (size_t)b.n * 8);
+            std::sort(m, m + b.n);
+            const uint32_t distinct = (uint32_t)(std::unique(m, m + b.n) - m);
+            memset(m + distinct, 0, (size_t)(b.n - distinct) * 8);
+            b.value = (int64_t)(d_tab + at);
+            at += (size_t)b.n * 8;
+            b.n = distinct;
+        }
+        memcpy(tab + (size_t)j * sizeof(cryo_bucket), &b, sizeof b);
+    }
+}
+
+/* the device-resident call: bk (host copy, validated) names lists in DEVICE memory.  Reads them back together (at most 2 x 8 192
+ * bytes, one wait), builds the table behind the key table in handle-owned device memory and gives its address; one more wait */
+static int bucket_table_device(cryo_codec *c, const cryo_bucket *bk, uint32_t nby, const void **d_buckets)
+{
+    std::vector<uint64_t> lists((size_t)CRYO_GROUP_MAX_BY * CRYO_BUCKET_BOUNDS_MAX), tab(bucket_table_bytes(bk, nby) / 8, 0);
+    const void *where[CRYO_GROUP_MAX_BY] = {nullptr, nullptr};
+    for (uint32_t j = 0; j < nby; j++) {
+        if (bk[j].kind != CRYO_BUCKET_BOUNDS) continue;
+        where[j] = lists.data() + (size_t)j * CRYO_BUCKET_BOUNDS_MAX;
+        HIP_TRY(c, hipMemcpyAsync((void *)where[j], (const void *)(uintptr_t)bk[j].value, (size_t)bk[j].n * 8, hipMemcpyDeviceToHost,
+                                  c->stream));
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (!c->d_keytab) HIP_TRY(c, hipMalloc(&c->d_keytab, kDescTablesBytes));
+    uint8_t *d_tab = c->d_keytab + kKeyTableBytes;
+    bucket_table_fill((uint8_t *)tab.data(), (uint64_t)(uintptr_t)d_tab, bk, nby, where);
+    HIP_TRY(c, hipMemcpyAsync(d_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream)); /* tab is the call's own: gone when it returns */
+    *d_buckets = d_tab;
+    return CRYO_OK;
+}
+
+/* the grouping's descriptor rules (include/cryo_codec.h); every array is host memory here -- bk: the nby buckets of a
+ * CRYO_GROUP_BUCKETS descriptor, whose pointer within *grp is held against its rules here too.  *max_att: the highest key, group
+ * or aggregate column; *ncols: the aggregate columns (0 with a null agg) */
 static bool group_desc_ok(const cryo_filter *f, const cryo_att *atts, const cryo_scan_key *keys, const cryo_group *grp,
-                          const cryo_agg_col *by, const cryo_agg *agg, const cryo_agg_col *cols, uint32_t *max_att, uint32_t *ncols)
+                          const cryo_agg_col *by, const cryo_bucket *bk, const cryo_agg *agg, const cryo_agg_col *cols, uint32_t *max_att,
+                          uint32_t *ncols)
 {
     *ncols = 0;
     if (!filter_desc_ok(f, atts, keys, max_att)) return false;
-    if ((f->flags & ~CRYO_FILTER_TRUTH) != 0 || !grp || grp->nby == 0 || grp->nby > CRYO_GROUP_MAX_BY || grp->rsv != 0 || !by) return false;
+    if ((f->flags & ~CRYO_FILTER_TRUTH) != 0 || !grp || grp->nby == 0 || grp->nby > CRYO_GROUP_MAX_BY || grp->rsv > CRYO_GROUP_BUCKETS || !by)
+        return false;
     for (uint32_t j = 0; j < grp->nby; j++)
         if (!agg_col_ok(f, atts, by[j], max_att, false)) return false;
+    if (grp->rsv == CRYO_GROUP_BUCKETS &&
+        (!group_buckets(grp) || ((uintptr_t)group_buckets(grp) & 7u) != 0 || !bk || !bucket_desc_ok(bk, grp->nby)))
+        return false;
     if (!agg) return true;
     if (agg->ncols > CRYO_AGG_MAX_COLS || agg->rsv != 0 || (agg->ncols > 0 && !cols)) return false;
     for (uint32_t j = 0; j < agg->ncols; j++)
@@ -1530,7 +1627,7 @@ static int group_pass(cryo_codec *c, int method, const uint8_t *d_src, const uin
         uint8_t *side_rec = ch.own, *side_cell = ch.own + ch.K * S * sizeof(cryo_group_rec);
         HIP_TRY(c, cryo::launch_group(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.sd.d_atts, io.sd.d_keys, io.sd.nkeys, slots, io.nby,
                                       io.ncols, io.sd.max_att, io.sd.truth, io.sd.floats, (uint4 *)(io.d_blocks + ch.lo), side_rec, side_cell, io.d_total,
-                                      io.d_groups, io.d_cells, io.group_cap, c->lz4_opts.cus));
+                                      io.d_groups, io.d_cells, io.group_cap, c->lz4_opts.cus, io.sd.d_buckets));
         return CRYO_OK;
     };
     return decode_pass(c, method, B, n, ps);
@@ -1782,7 +1879,8 @@ int cryo_codec_fetch_batch(cryo_codec *c, int method, const void *d_src, const u
  * without aggregate columns) are host structs whose arrays live in device memory.  In this order: the pointer and alignment
  * rules of the structs, which touch no device; the arrays read back and held against the call's *_desc_ok before anything else
  * is queued; the call's totals (total_words of them at d_total; none: 0) cleared; and -- unless the call has no block -- the key
- * table of a descriptor with a byte-string key (key_table_device: without such a key nothing more is queued).  *ncols: the
+ * table of a descriptor with a byte-string key (key_table_device: without such a key nothing more is queued) and the bucket table
+ * of a CRYO_GROUP_BUCKETS group descriptor, whose buckets array is read back beside by (bucket_table_device).  *ncols: the
  * aggregate columns.  prj: the call is a projection (grp and agg null); *pt: its column table */
 static int scan_desc_device(cryo_codec *c, const cryo_filter *f, const cryo_group *grp, const cryo_agg *agg, bool need_agg,
                             uint64_t *d_total, size_t total_words, uint64_t n_blocks, ScanDesc &sd, uint32_t *ncols,
@@ -1792,6 +1890,10 @@ static int scan_desc_device(cryo_codec *c, const cryo_filter *f, const cryo_grou
         (f->nkeys > 0 && !f->keys) || ((uintptr_t)f->atts & 3u) != 0 || ((uintptr_t)f->keys & 7u) != 0)
         return CRYO_E_ARG;
     if (grp && (grp->nby == 0 || grp->nby > CRYO_GROUP_MAX_BY || !grp->by || ((uintptr_t)grp->by & 7u) != 0)) return CRYO_E_ARG;
+    if (grp && (grp->rsv > CRYO_GROUP_BUCKETS ||
+                (grp->rsv == CRYO_GROUP_BUCKETS && (!group_buckets(grp) || ((uintptr_t)group_buckets(grp) & 7u) != 0))))
+        return CRYO_E_ARG;
+    const cryo_bucket *d_bk = grp ? group_buckets(grp) : nullptr; /* device */
     const uint32_t nc = agg ? agg->ncols : 0u;
     if ((need_agg && nc == 0) || nc > CRYO_AGG_MAX_COLS || (nc > 0 && (!agg->cols || ((uintptr_t)agg->cols & 7u) != 0)))
         return CRYO_E_ARG;
@@ -1799,17 +1901,19 @@ static int scan_desc_device(cryo_codec *c, const cryo_filter *f, const cryo_grou
     cryo_att atts[CRYO_FILTER_MAX_ATTS]; /* 6 400 bytes */
     cryo_scan_key keys[CRYO_FILTER_MAX_KEYS];
     cryo_agg_col by[CRYO_GROUP_MAX_BY], cols[CRYO_AGG_MAX_COLS];
+    cryo_bucket bk[CRYO_GROUP_MAX_BY];
     cryo_project_col pcols[CRYO_PROJECT_MAX_COLS];
     HIP_TRY(c, hipMemcpyAsync(atts, f->atts, f->natts * sizeof(cryo_att), hipMemcpyDeviceToHost, c->stream));
     if (f->nkeys)
         HIP_TRY(c, hipMemcpyAsync(keys, f->keys, f->nkeys * sizeof(cryo_scan_key), hipMemcpyDeviceToHost, c->stream));
     if (grp) HIP_TRY(c, hipMemcpyAsync(by, grp->by, grp->nby * sizeof(cryo_agg_col), hipMemcpyDeviceToHost, c->stream));
+    if (d_bk) HIP_TRY(c, hipMemcpyAsync(bk, d_bk, grp->nby * sizeof(cryo_bucket), hipMemcpyDeviceToHost, c->stream));
     if (nc) HIP_TRY(c, hipMemcpyAsync(cols, agg->cols, nc * sizeof(cryo_agg_col), hipMemcpyDeviceToHost, c->stream));
     if (prj) HIP_TRY(c, hipMemcpyAsync(pcols, prj->cols, prj->ncols * sizeof(cryo_project_col), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     *ncols = nc;
     const bool ok = prj        ? project_desc_ok(f, atts, keys, prj, pcols, &sd.max_att, pt)
-                    : grp      ? group_desc_ok(f, atts, keys, grp, by, agg, cols, &sd.max_att, ncols)
+                    : grp      ? group_desc_ok(f, atts, keys, grp, by, d_bk ? bk : nullptr, agg, cols, &sd.max_att, ncols)
                     : need_agg ? agg_desc_ok(f, atts, keys, agg, cols, &sd.max_att)
                                : filter_desc_ok(f, atts, keys, &sd.max_att);
     if (!ok) return CRYO_E_ARG;
@@ -1817,9 +1921,10 @@ static int scan_desc_device(cryo_codec *c, const cryo_filter *f, const cryo_grou
     if (n_blocks == 0) return CRYO_OK;
     sd.d_atts = f->atts; sd.d_keys = f->keys; sd.nkeys = f->nkeys;
     bool table_keys = false;
-    const int rc = key_table_device(c, keys, f->nkeys, &sd.d_keys, &table_keys);
+    int rc = key_table_device(c, keys, f->nkeys, &sd.d_keys, &table_keys);
+    if (rc == CRYO_OK && d_bk) rc = bucket_table_device(c, bk, grp->nby, &sd.d_buckets);
     sd.floats = desc_has_float(keys, f->nkeys, cols, *ncols);
-    sd.truth = scan_truth(f, table_keys || sd.floats);
+    sd.truth = scan_truth(f, table_keys || sd.floats || d_bk); /* the bucket kernels have the table's verdict path alone */
     return rc;
 }
 
@@ -2682,7 +2787,7 @@ static int group_blocks_args(int method, size_t block_size, const cryo_filter *f
                              uint64_t *h_total, uint32_t *max_att, uint32_t *ncols)
 {
     if (!method_ok(method) || !check_block_size_ok(block_size) || !h_total) return CRYO_E_ARG;
-    if (!f || !grp || !group_desc_ok(f, f->atts, f->keys, grp, grp->by, agg, agg ? agg->cols : nullptr, max_att, ncols))
+    if (!f || !grp || !group_desc_ok(f, f->atts, f->keys, grp, grp->by, group_buckets(grp), agg, agg ? agg->cols : nullptr, max_att, ncols))
         return CRYO_E_ARG;
     return CRYO_OK;
 }
@@ -2704,21 +2809,34 @@ static int group_blocks_impl(cryo_codec *c, int method, const void *const *h_src
     if (n == 0) return CRYO_OK;
     if (!h_src || !h_src_size || !h_blocks || (group_cap > 0 && (!h_groups || (ncols > 0 && !h_cells)))) return CRYO_E_ARG;
     ScopedLocalCpus numa_(n * block_size >= ((size_t)8 << 20) ? c : nullptr);
-    /* the descriptor with the kernel's six slots [by 8 x 2][cols 8 x 4] as its extra bytes, then the results: [total 16]
+    /* the descriptor with the kernel's six slots [by 8 x 2][cols 8 x 4] and -- CRYO_GROUP_BUCKETS -- the bucket table (built for
+     * the address it will have in c->hb_meta, from the caller's host lists) as its extra bytes, then the results: [total 16]
      * [rows 32 x n][records 24 x cap][cells 40 x cap x ncols], each part 8-byte aligned, the rows 16; cap: what the caller has room
      * for, at most the worst case */
     const size_t worst = n * (size_t)cryo::filter_side_stride((uint32_t)block_size);
     const size_t cap = group_cap < worst ? group_cap : worst;
-    cryo_agg_col slots[CRYO_GROUP_MAX_BY + CRYO_AGG_MAX_COLS] = {};
+    const cryo_bucket *bk = group_buckets(grp);
+    constexpr size_t kSlots = CRYO_GROUP_MAX_BY + CRYO_AGG_MAX_COLS;
+    std::vector<uint64_t> extra(kSlots + (bk ? bucket_table_bytes(bk, grp->nby) / 8 : 0), 0); /* 8-byte aligned, zeroed */
+    cryo_agg_col *slots = (cryo_agg_col *)extra.data();
+    static_assert(sizeof(cryo_agg_col) == 8, "a slot is a word of the extra bytes");
     memcpy(slots, grp->by, (size_t)grp->nby * 8);
     if (ncols) memcpy(slots + CRYO_GROUP_MAX_BY, agg->cols, (size_t)ncols * 8);
-    const ScanDescLayout L = scan_desc_layout(f, sizeof slots, slots + CRYO_GROUP_MAX_BY, ncols);
+    ScanDescLayout L = scan_desc_layout(f, extra.size() * 8, slots + CRYO_GROUP_MAX_BY, ncols);
+    if (bk) L.table_keys = true; /* the bucket kernels have the table's verdict path alone */
     const size_t t_total = L.bytes, t_rows = t_total + 16;
     const size_t rows_bytes = n * sizeof(cryo_group_block), t_recs = t_rows + rows_bytes, t_cells = t_recs + cap * sizeof(cryo_group_rec);
     if ((rc = ensure(c, &c->hb_meta, &c->hb_meta_cap, t_cells + cap * ncols * sizeof(cryo_agg_cell) + 64)) != CRYO_OK) return rc;
     StagedStreams sg;
     GroupIo io;
-    if ((rc = scan_desc_upload(c, h_src, h_src_size, n, f, max_att, L, slots, sg, io.sd)) != CRYO_OK) return rc;
+    if (bk) {
+        const void *lists[CRYO_GROUP_MAX_BY] = {nullptr, nullptr};
+        for (uint32_t j = 0; j < grp->nby; j++) lists[j] = (const void *)(uintptr_t)bk[j].value;
+        uint8_t *d_tab = c->hb_meta + L.t_extra + kSlots * 8;
+        bucket_table_fill((uint8_t *)(extra.data() + kSlots), (uint64_t)(uintptr_t)d_tab, bk, grp->nby, lists);
+        io.sd.d_buckets = d_tab;
+    }
+    if ((rc = scan_desc_upload(c, h_src, h_src_size, n, f, max_att, L, extra.data(), sg, io.sd)) != CRYO_OK) return rc;
     io.d_slots = c->hb_meta + L.t_extra; io.nby = grp->nby; io.ncols = ncols;
     io.d_total = (uint64_t *)(c->hb_meta + t_total);
     io.d_blocks = (cryo_group_block *)(c->hb_meta + t_rows);
@@ -3710,7 +3828,7 @@ int cryo_codec_debug_fill(cryo_codec *c, int value, cryo_codec_fill_report *out)
         {c->hb_src, c->hb_src_cap, &r.hb_src}, {c->hb_dst, c->hb_dst_cap, &r.hb_dst},  {c->hb_meta, c->hb_meta_cap, &r.hb_meta},
         {c->d_in, c->in_cap, &r.d_in},         {c->d_out, c->out_cap, &r.d_out},       {c->d_off, sizeof(uint64_t), &r.d_scalars},
         {c->d_size, sizeof(uint32_t), &r.d_scalars}, {c->d_status, sizeof(int32_t), &r.d_scalars},
-        {c->d_keytab, kKeyTableBytes, &r.d_keytab},
+        {c->d_keytab, kDescTablesBytes, &r.d_keytab},
     };
     for (auto &b : dev) {
         if (!b.p || b.cap == 0) continue;

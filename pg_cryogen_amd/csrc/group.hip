@@ -22,7 +22,8 @@
  *   k_group_copy     a grid stride over the blocks: block k's records and cells from the side area to first_group of the call's
  *                    output, word by word, cut off at group_cap.
  * A descriptor with a float key or a float aggregate column runs group_float.hip's k_groupf_block in k_group_block's place
- * (launch_group's `floats`); the other two kernels serve both.
+ * (launch_group's `floats`), a descriptor with bucketed group columns group_bucket.hip's k_groupb_block (launch_group's
+ * d_buckets); the other two kernels serve all of them.
  * Every device write is a vector store in plain C++.  No scratch, no global atomics.
  */
 #include "kernels.h"
@@ -140,7 +141,7 @@ k_group_copy(uint32_t cnt, uint32_t side_stride, uint32_t ncols, const uint4 *__
 hipError_t launch_group(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
                         const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,
                         uint32_t nby, uint32_t ncols, uint32_t max_att, uint32_t truth, bool floats, uint4 *d_blocks, void *d_side_rec, void *d_side_cell,
-                        uint64_t *d_running, void *d_rec, void *d_cells, uint64_t group_cap, int cus)
+                        uint64_t *d_running, void *d_rec, void *d_cells, uint64_t group_cap, int cus, const void *d_buckets)
 {
     if (cnt == 0) return hipSuccess;
     if (!scan_launch_ok(dec_stride, d_dec, d_blocks, d_atts, d_keys,
@@ -152,7 +153,10 @@ hipError_t launch_group(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride
         return hipErrorInvalidValue;
     const uint32_t stride = filter_side_stride(block_size);
     hipError_t e;
-    if (floats) /* a float key or a float aggregate column: group_float.hip's block kernel, then the same two */
+    if (d_buckets) /* a CRYO_GROUP_BUCKETS descriptor: group_bucket.hip's block kernels, then the same two */
+        e = launch_groupb_block(s, d_dec, dec_stride, block_size, cnt, d_dec_status, d_atts, d_keys, nkeys, d_slots, d_buckets, nby, ncols,
+                                max_att, truth, floats, stride, d_blocks, d_side_rec, d_side_cell);
+    else if (floats) /* a float key or a float aggregate column: group_float.hip's block kernel, then the same two */
         e = launch_groupf_block(s, d_dec, dec_stride, block_size, cnt, d_dec_status, d_atts, d_keys, nkeys, d_slots, nby, ncols, max_att,
                                 truth, stride, d_blocks, d_side_rec, d_side_cell);
     else {

@@ -1,7 +1,8 @@
 /*
  * group_lds.h -- what the grouped scan's two block kernels (group.hip: k_group_block; group_float.hip: k_groupf_block) share: the
  * records' layout, a wave's matches in LDS, the wave's barrier between its LDS writes and reads, and the two steps that lead up
- * to a kernel's own reduction: the matches into LDS (group_matches) and their ranks (group_rank).
+ * to a kernel's own reduction: the matches into LDS (group_matches) and their ranks (group_rank).  group_bucket.hip's
+ * k_groupb_block is a third user: it hands group_matches a step that maps the captured group values (GroupRawKeys: none).
  */
 #pragma once
 #include "kernels.h"
@@ -35,20 +36,27 @@ __device__ inline void group_wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+/* group_matches' step between a turn's capture and its compaction: the kernels that group by the raw values pass this one, which
+ * does nothing; group_bucket.hip passes the step that maps a group value to its bucket and turns an undecided match into a bad item */
+struct GroupRawKeys { __device__ void operator()(WalkCaptureN<kGroupSlots> &, SweepItem &) const {} };
+
 /* Step 1 of a block kernel: the sweep of scan_sweep.h over an opened block, with six capture slots (slots: the nby group columns,
  * then the aggregate columns) and the walk's BYTES and FLOATS as the kernel's.  The wave compacts the matches in position order
- * into L (ballot + popcount prefix): per match the two group values, the null bits and the captured aggregate values */
-template <bool BYTES, bool FLOATS>
+ * into L (ballot + popcount prefix): per match the two group values, the null bits and the captured aggregate values.  keys_of
+ * sees every turn's capture and verdict first, the same call in all 64 lanes */
+template <bool BYTES, bool FLOATS, class KEYS = GroupRawKeys>
 __device__ inline void group_matches(GroupLds &L, const uint8_t *__restrict__ p, uint32_t B, uint32_t n, uint32_t upper, uint32_t lane,
                                      const FilterAtt *__restrict__ atts, const FilterKey *__restrict__ keys, uint32_t nkeys,
-                                     uint32_t max_att, const AggCol *__restrict__ slots, uint32_t nby, uint32_t &n_match, uint32_t &n_bad)
+                                     uint32_t max_att, const AggCol *__restrict__ slots, uint32_t nby, uint32_t &n_match, uint32_t &n_bad,
+                                     const KEYS keys_of = KEYS())
 {
     const unsigned long long below = (1ull << lane) - 1ull;
     const uint32_t by_mask = (1u << nby) - 1u;
     for (uint32_t t0 = 0; t0 < n; t0 += 64u) {
         WalkCaptureN<kGroupSlots> cap;
-        const SweepItem it = sweep_turn<true, kGroupSlots, BYTES, false, FLOATS>(p, B, n, upper, t0 + lane, atts, keys, nkeys, max_att, slots,
-                                                                                kGroupSlots, &cap);
+        SweepItem it = sweep_turn<true, kGroupSlots, BYTES, false, FLOATS>(p, B, n, upper, t0 + lane, atts, keys, nkeys, max_att, slots,
+                                                                          kGroupSlots, &cap);
+        keys_of(cap, it);
         const unsigned long long mm = __ballot(it.match);
         if (it.match) {
             const uint32_t at = n_match + (uint32_t)__popcll(mm & below); /* below n <= 290 */

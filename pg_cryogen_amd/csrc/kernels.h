@@ -298,12 +298,21 @@ hipError_t launch_aggf(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride,
  * and is in no group).  d_blocks: the chunk's rows (cryo_group_block, 16-byte aligned).  Scratch: d_side_rec 24 bytes and
  * d_side_cell 40 * ncols bytes per possible group (cnt * filter_side_stride(block_size) groups; both 8-byte aligned).
  * *d_running: the groups before the chunk in, after it out.  The chunk's records go to d_rec and its cells to d_cells (8-byte
- * aligned) at first_group within the call; nothing at or beyond group_cap groups is written.  cus as for launch_fetch. */
+ * aligned) at first_group within the call; nothing at or beyond group_cap groups is written.  cus as for launch_fetch.
+ * d_buckets: null, or -- a CRYO_GROUP_BUCKETS descriptor -- the staged bucket table (launch_groupb_block), whose kernels run in
+ * the block kernel's place; truth is not 0 then. */
 hipError_t launch_group(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
                         const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,
                         uint32_t nby, uint32_t ncols, uint32_t max_att, uint32_t truth, bool floats, uint4 *d_blocks, void *d_side_rec,
                         void *d_side_cell,
-                        uint64_t *d_running, void *d_rec, void *d_cells, uint64_t group_cap, int cus);
+                        uint64_t *d_running, void *d_rec, void *d_cells, uint64_t group_cap, int cus, const void *d_buckets);
+/* launch_group's bucket branch (group_bucket.hip): k_groupb_block<floats> alone, on arguments launch_group has checked; truth is
+ * not 0; d_buckets the staged bucket table, 8-byte aligned: two entries of 24 bytes (cryo_bucket; a list's n its distinct
+ * boundaries and value the device address of the library's sorted copy) */
+hipError_t launch_groupb_block(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
+                               const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,
+                               const void *d_buckets, uint32_t nby, uint32_t ncols, uint32_t max_att, uint32_t truth, bool floats,
+                               uint32_t side_stride, uint4 *d_blocks, void *d_side_rec, void *d_side_cell);
 /* launch_group's float branch (group_float.hip): k_groupf_block alone, on arguments launch_group has checked; truth is not 0 */
 hipError_t launch_groupf_block(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
                                const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,

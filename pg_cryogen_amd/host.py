@@ -466,14 +466,15 @@ class GroupScanError(RuntimeError):
         super().__init__("cryo_group_scan failed: %d" % code)
 
 
-def group_scan(rel, atts, keys, by, cols=None, truth=None):
+def group_scan(rel, atts, keys, by, cols=None, truth=None, buckets=None):
     """cryo_group_scan (host/group.h) with the descriptors codec.filter_desc, codec.group_desc and codec.agg_desc make of atts
-    [(attlen, attalign)], keys [(att, type, op, value)], by and cols [(att, type)] (cols None: a null aggregate descriptor).
+    [(attlen, attalign)], keys [(att, type, op, value)], by and cols [(att, type)] (cols None: a null aggregate descriptor);
+    buckets: one (kind, flags, origin, value) per group column, as for codec.group_desc.
     Returns (events, totals): events in delivery order, ("block", block, created_xid, n_items, n_match, n_bad, [(key tuple with
     None for NULL, n_rows, [(n, min, max, sum) per column]) per group]) or ("report", block, reason, detail); totals a dict.  A
     nonzero status raises GroupScanError (which carries what was delivered)."""
     from . import codec
-    desc, gdesc = codec.filter_desc(atts, keys, 0, truth), codec.group_desc(by)
+    desc, gdesc = codec.filter_desc(atts, keys, 0, truth), codec.group_desc(by, buckets)
     adesc = None if cols is None else codec.agg_desc(cols)
     nby, ncols = len(by), len(cols or ())
     events = []
