@@ -8,6 +8,7 @@
  */
 #include "cryo_codec.h"
 #include "kernels.h"
+#include "multi_share.h"
 
 #include <algorithm>
 #include <condition_variable>
@@ -237,6 +238,9 @@ struct ScopedLocalCpus {
         if (pthread_getaffinity_np(pthread_self(), sizeof old, &old) != 0) return;
         active = pthread_setaffinity_np(pthread_self(), sizeof c->local_cpus, &c->local_cpus) == 0;
     }
+    /* for a K-block call: only one that stages kMinCallBytes or more repays the move */
+    static constexpr size_t kMinCallBytes = (size_t)8 << 20;
+    ScopedLocalCpus(const cryo_codec *c, size_t n, size_t block_size) : ScopedLocalCpus(n * block_size >= kMinCallBytes ? c : nullptr) {}
     ~ScopedLocalCpus() { if (active) (void)pthread_setaffinity_np(pthread_self(), sizeof old, &old); }
 };
 
@@ -2355,7 +2359,7 @@ static int compress_blocks_body(cryo_codec *c, int method, int param, const void
     if (!h_src || !h_dst || !h_out_size) return CRYO_E_ARG;
     const size_t bound = cryo_codec_bound(method, block_size);
     if (dst_stride < bound) return CRYO_E_DSTSIZE;
-    ScopedLocalCpus numa_(n * block_size >= ((size_t)8 << 20) ? c : nullptr); /* the caller's share of the copies next to the GPU */
+    ScopedLocalCpus numa_(c, n, block_size); /* the caller's share of the copies next to the GPU */
     c->vfy_failed = false;
     if (pipe_worth_it(c, n, block_size)) {
         const int rc = compress_blocks_piped(c, method, param, (const uint8_t *)h_src, nullptr, block_size, n, (uint8_t *)h_dst, nullptr, dst_stride, h_out_size);
@@ -2453,7 +2457,7 @@ static int decompress_blocks_impl(cryo_codec *c, int method, const void *const *
     if (check && !check_block_size_ok(block_size)) return CRYO_E_ARG;
     if (n == 0) return CRYO_OK;
     if (!h_src || !h_src_size || (!check && ((!h_dst && !h_dst_each) || !h_status))) return CRYO_E_ARG;
-    ScopedLocalCpus numa_(n * block_size >= ((size_t)8 << 20) ? c : nullptr);
+    ScopedLocalCpus numa_(c, n, block_size);
     if (pipe_worth_it(c, n, block_size)) {
         const int rc = decompress_blocks_piped(c, method, h_src, h_src_size, n, (uint8_t *)h_dst, h_dst_each, block_size, h_status, h_result);
         /* an error return must not leave copies in flight into the handle's pinned buffers or the caller's memory */
@@ -2556,7 +2560,7 @@ static int recode_blocks_impl(cryo_codec *c, int src_method, const void *const *
     if (ok != CRYO_OK) return ok;
     if (n == 0) return CRYO_OK;
     if (!h_src || !h_src_size || !h_dst || !h_out_off || !h_out_size || !h_status) return CRYO_E_ARG;
-    ScopedLocalCpus numa_(n * block_size >= ((size_t)8 << 20) ? c : nullptr);
+    ScopedLocalCpus numa_(c, n, block_size);
     StagedStreams sg;
     int rc;
     if ((rc = stage_streams(c, h_src, h_src_size, n, sg, true)) != CRYO_OK) return rc;
@@ -2598,7 +2602,7 @@ static int fetch_blocks_impl(cryo_codec *c, int method, const void *const *h_src
     const uint64_t n_req = h_req_first[n];
     if (n_req > 0 && (!h_pos || !h_result)) return CRYO_E_ARG;
     if (!h_dst && dst_cap > 0) return CRYO_E_ARG;
-    ScopedLocalCpus numa_(n * block_size >= ((size_t)8 << 20) ? c : nullptr);
+    ScopedLocalCpus numa_(c, n, block_size);
     /* the request table: [first u64 x (n + 1)][pos u16 x n_req][records x n_req], each part 16-byte aligned */
     const size_t t_first = 0, t_pos = ((n + 1) * 8 + 15) & ~(size_t)15, t_rec = t_pos + ((n_req * 2 + 15) & ~(size_t)15);
     int rc;
@@ -2694,7 +2698,7 @@ static int filter_blocks_impl(cryo_codec *c, int method, const void *const *h_sr
     const bool count_only = (f->flags & CRYO_FILTER_COUNT_ONLY) != 0;
     if (!h_src || !h_src_size || !h_blocks) return CRYO_E_ARG;
     if (!count_only && ((!h_dst && dst_cap > 0) || (!h_rec && rec_cap > 0))) return CRYO_E_ARG;
-    ScopedLocalCpus numa_(n * block_size >= ((size_t)8 << 20) ? c : nullptr);
+    ScopedLocalCpus numa_(c, n, block_size);
     /* the descriptor, then the table: [rows 32 x n] */
     const ScanDescLayout L = scan_desc_layout(f, 0);
     const size_t t_rows = L.bytes;
@@ -2734,6 +2738,23 @@ static int agg_blocks_args(int method, size_t block_size, const cryo_filter *f, 
     return CRYO_OK;
 }
 
+/* the readback of a host-buffer scan call: after a pass that went well, up to two device-to-host copies (one of no bytes is left
+ * out), counted in d2h_bytes when they were queued; then, whatever rc says, the wait for the stream -- nothing in flight from the
+ * pinned buffer or into the caller's memory afterwards.  The first error is the call's; `what` names the copies for it */
+struct Readback { void *dst; const void *src; size_t bytes; };
+static int read_back(cryo_codec *c, int rc, const Readback &a, const Readback &b, const char *what)
+{
+    if (rc == CRYO_OK) {
+        hipError_t e = hipMemcpyAsync(a.dst, a.src, a.bytes, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && b.bytes) e = hipMemcpyAsync(b.dst, b.src, b.bytes, hipMemcpyDeviceToHost, c->stream);
+        if (e != hipSuccess) rc = fail(c, e, what);
+        else c->xfer_ctr.d2h_bytes += a.bytes + b.bytes;
+    }
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (rc == CRYO_OK && es != hipSuccess) rc = fail(c, es, "hipStreamSynchronize");
+    return rc;
+}
+
 /* the scan aggregate of n streams given by pointer: the streams staged and uploaded as the filter's (stage_streams), the
  * descriptors from the same pinned buffer in a second copy, both into place before the first decode; rows and cells of the whole
  * call come back after the last chunk (agg_pass waits for nothing) */
@@ -2747,7 +2768,7 @@ static int agg_blocks_impl(cryo_codec *c, int method, const void *const *h_src, 
     DevGuard dev_(c);
     if (n == 0) return CRYO_OK;
     if (!h_src || !h_src_size || !h_blocks || !h_cells) return CRYO_E_ARG;
-    ScopedLocalCpus numa_(n * block_size >= ((size_t)8 << 20) ? c : nullptr);
+    ScopedLocalCpus numa_(c, n, block_size);
     /* the descriptor with [cols 8 x ncols] as its extra bytes, then the results: [rows 16 x n][cells 40 x n x ncols] */
     cryo_agg_col cols[CRYO_AGG_MAX_COLS] = {};
     memcpy(cols, agg->cols, (size_t)agg->ncols * 8);
@@ -2763,16 +2784,8 @@ static int agg_blocks_impl(cryo_codec *c, int method, const void *const *h_src, 
     io.d_cells = (cryo_agg_cell *)(c->hb_meta + t_rows + rows_bytes);
     rc = agg_pass(c, method, c->hb_src, (const uint64_t *)(c->hb_src + sg.o_off), (const uint32_t *)(c->hb_src + sg.o_sz),
                   (uint32_t)block_size, n, io);
-    if (rc == CRYO_OK) {
-        hipError_t e = hipMemcpyAsync(h_blocks, io.d_blocks, rows_bytes, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(h_cells, io.d_cells, cells_bytes, hipMemcpyDeviceToHost, c->stream);
-        if (e != hipSuccess) rc = fail(c, e, "hipMemcpyAsync of rows and cells");
-        else c->xfer_ctr.d2h_bytes += rows_bytes + cells_bytes;
-    }
-    /* the call's one wait: nothing in flight from the pinned buffer or into the caller's memory afterwards */
-    const hipError_t es = hipStreamSynchronize(c->stream);
-    if (rc == CRYO_OK && es != hipSuccess) rc = fail(c, es, "hipStreamSynchronize");
-    return rc;
+    /* the call's one wait */
+    return read_back(c, rc, {h_blocks, io.d_blocks, rows_bytes}, {h_cells, io.d_cells, cells_bytes}, "hipMemcpyAsync of rows and cells");
 }
 
 int cryo_codec_agg_blocks(cryo_codec *c, int method, const void *const *h_src, const uint32_t *h_src_size, size_t n,
@@ -2808,7 +2821,7 @@ static int group_blocks_impl(cryo_codec *c, int method, const void *const *h_src
     *h_total = 0;
     if (n == 0) return CRYO_OK;
     if (!h_src || !h_src_size || !h_blocks || (group_cap > 0 && (!h_groups || (ncols > 0 && !h_cells)))) return CRYO_E_ARG;
-    ScopedLocalCpus numa_(n * block_size >= ((size_t)8 << 20) ? c : nullptr);
+    ScopedLocalCpus numa_(c, n, block_size);
     /* the descriptor with the kernel's six slots [by 8 x 2][cols 8 x 4] and -- CRYO_GROUP_BUCKETS -- the bucket table (built for
      * the address it will have in c->hb_meta, from the caller's host lists) as its extra bytes, then the results: [total 16]
      * [rows 32 x n][records 24 x cap][cells 40 x cap x ncols], each part 8-byte aligned, the rows 16; cap: what the caller has room
@@ -2845,29 +2858,16 @@ static int group_blocks_impl(cryo_codec *c, int method, const void *const *h_src
     io.group_cap = cap;
     rc = group_pass(c, method, c->hb_src, (const uint64_t *)(c->hb_src + sg.o_off), (const uint32_t *)(c->hb_src + sg.o_sz),
                     (uint32_t)block_size, n, io);
-    if (rc == CRYO_OK) {
-        const hipError_t e = hipMemcpyAsync(h_blocks, io.d_blocks, rows_bytes, hipMemcpyDeviceToHost, c->stream);
-        if (e != hipSuccess) rc = fail(c, e, "hipMemcpyAsync of rows");
-        else c->xfer_ctr.d2h_bytes += rows_bytes;
-    }
-    /* nothing in flight from the pinned buffer or into the caller's memory afterwards */
-    hipError_t es = hipStreamSynchronize(c->stream);
-    if (rc == CRYO_OK && es != hipSuccess) rc = fail(c, es, "hipStreamSynchronize");
+    rc = read_back(c, rc, {h_blocks, io.d_blocks, rows_bytes}, {}, "hipMemcpyAsync of rows");
     if (rc != CRYO_OK) return rc;
     const cryo_group_block &last = h_blocks[n - 1];
     if (last.first_group > worst || last.n_groups > worst - last.first_group) return CRYO_E_HIP; /* not a placement */
     const uint64_t total = last.first_group + last.n_groups;
     *h_total = total;
     if (total > group_cap) return CRYO_E_DSTSIZE;
-    if (total) {
-        hipError_t e = hipMemcpyAsync(h_groups, io.d_groups, total * sizeof(cryo_group_rec), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && ncols)
-            e = hipMemcpyAsync(h_cells, io.d_cells, total * ncols * sizeof(cryo_agg_cell), hipMemcpyDeviceToHost, c->stream);
-        if (e != hipSuccess) rc = fail(c, e, "hipMemcpyAsync of records and cells");
-        else c->xfer_ctr.d2h_bytes += total * (sizeof(cryo_group_rec) + ncols * sizeof(cryo_agg_cell));
-        es = hipStreamSynchronize(c->stream);
-        if (rc == CRYO_OK && es != hipSuccess) rc = fail(c, es, "hipStreamSynchronize");
-    }
+    if (total)
+        rc = read_back(c, rc, {h_groups, io.d_groups, total * sizeof(cryo_group_rec)},
+                       {h_cells, io.d_cells, total * ncols * sizeof(cryo_agg_cell)}, "hipMemcpyAsync of records and cells");
     return rc;
 }
 
@@ -2909,7 +2909,7 @@ static int project_blocks_impl(cryo_codec *c, int method, const void *const *h_s
     h_total[0] = h_total[1] = 0;
     if (n == 0) return CRYO_OK;
     if (!h_src || !h_src_size || !h_blocks || (!h_rows && row_cap > 0) || (!h_rec && rec_cap > 0)) return CRYO_E_ARG;
-    ScopedLocalCpus numa_(n * block_size >= ((size_t)8 << 20) ? c : nullptr);
+    ScopedLocalCpus numa_(c, n, block_size);
     /* the descriptor with the column table [8 x ncols] as its extra bytes, then the results: [totals 16][table 32 x n]
      * [records 8 x cap_r][rows row_bytes x cap_w], each part 8-byte aligned, the table 16; the caps: what the caller has room for, at
      * most the worst case */
@@ -2929,14 +2929,7 @@ static int project_blocks_impl(cryo_codec *c, int method, const void *const *h_s
     io.rec_cap = cap_r; io.row_cap = cap_w;
     rc = project_pass(c, method, c->hb_src, (const uint64_t *)(c->hb_src + sg.o_off), (const uint32_t *)(c->hb_src + sg.o_sz),
                       (uint32_t)block_size, n, io);
-    if (rc == CRYO_OK) {
-        const hipError_t e = hipMemcpyAsync(h_blocks, io.d_blocks, table_bytes, hipMemcpyDeviceToHost, c->stream);
-        if (e != hipSuccess) rc = fail(c, e, "hipMemcpyAsync of the block table");
-        else c->xfer_ctr.d2h_bytes += table_bytes;
-    }
-    /* nothing in flight from the pinned buffer or into the caller's memory afterwards */
-    hipError_t es = hipStreamSynchronize(c->stream);
-    if (rc == CRYO_OK && es != hipSuccess) rc = fail(c, es, "hipStreamSynchronize");
+    rc = read_back(c, rc, {h_blocks, io.d_blocks, table_bytes}, {}, "hipMemcpyAsync of the block table");
     if (rc != CRYO_OK) return rc;
     const cryo_project_block &last = h_blocks[n - 1];
     const uint64_t last_recs = (uint64_t)last.n_match + last.n_bad;
@@ -2946,14 +2939,9 @@ static int project_blocks_impl(cryo_codec *c, int method, const void *const *h_s
     h_total[0] = rows;
     h_total[1] = recs;
     if (rows > row_cap || recs > rec_cap) return CRYO_E_DSTSIZE;
-    if (recs) {
-        hipError_t e = hipMemcpyAsync(h_rec, io.d_rec, recs * sizeof(cryo_project_rec), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && rows) e = hipMemcpyAsync(h_rows, io.d_rows, rows * rb, hipMemcpyDeviceToHost, c->stream);
-        if (e != hipSuccess) rc = fail(c, e, "hipMemcpyAsync of records and rows");
-        else c->xfer_ctr.d2h_bytes += recs * sizeof(cryo_project_rec) + rows * rb;
-        es = hipStreamSynchronize(c->stream);
-        if (rc == CRYO_OK && es != hipSuccess) rc = fail(c, es, "hipStreamSynchronize");
-    }
+    if (recs)
+        rc = read_back(c, rc, {h_rec, io.d_rec, recs * sizeof(cryo_project_rec)}, {h_rows, io.d_rows, rows * rb},
+                       "hipMemcpyAsync of records and rows");
     if (rc == CRYO_OK && (w_base || r_base))
         for (size_t i = 0; i < n; i++) { h_blocks[i].row_first += w_base; h_blocks[i].rec_first += r_base; }
     return rc;
@@ -3193,7 +3181,7 @@ static int compress_blocks_ptrs(cryo_codec *c, int method, int param, const void
     if (n == 0) return CRYO_OK;
     const size_t bound = cryo_codec_bound(method, block_size);
     const size_t dstride = (bound + 15) & ~(size_t)15;
-    ScopedLocalCpus numa_(n * block_size >= ((size_t)8 << 20) ? c : nullptr);
+    ScopedLocalCpus numa_(c, n, block_size);
     c->vfy_failed = false;
     if (pipe_worth_it(c, n, block_size)) { /* the single-handle path's staging: pinned double buffers, second stream, worker threads */
         const int rc = compress_blocks_piped(c, method, param, nullptr, h_src, block_size, n, nullptr, h_dst, dstride, out_size);
@@ -3269,74 +3257,86 @@ int cryo_multi_count(const cryo_multi *m) { return m ? (int)m->h.size() : 0; }
 const char *cryo_multi_last_error(const cryo_multi *m) { return m ? m->err : ""; }
 
 } /* extern "C" */
-/* block i -> handle owner(i), or i mod G without an owner; `fn(g, idx)` runs the block indices of handle g, every handle's share
- * on its own host thread */
-static int multi_run(cryo_multi *m, size_t n, const std::function<int(size_t, const std::vector<size_t> &)> &fn,
-                     const std::function<size_t(size_t)> &owner = nullptr)
+/* The deal, a share's region and the scatter are stated in multi_share.h.  `fn(c, g, idx)` runs the block indices idx of handle g
+ * (c), every handle's share on its own host thread; a handle without a share is not touched.  owner(i) names block i's handle.
+ * The lowest-numbered failing handle's code is the call's */
+template <class Fn, class Owner> static int multi_run(cryo_multi *m, size_t n, const Fn &fn, const Owner &owner)
 {
-    const size_t G = m->h.size();
-    std::vector<std::vector<size_t>> share(G);
-    for (size_t i = 0; i < n; i++) share[owner ? owner(i) : i % G].push_back(i);
-    std::vector<int> rc(G, CRYO_OK);
-    const std::function<void(unsigned)> one = [&](unsigned g) {
-        if (!share[g].empty()) {
-            rc[g] = guarded([&] { return fn(g, share[g]); });
-            ws_trim_after_call(m->h[g]); /* the keep limit holds per handle, whoever dispatched the call */
-        }
-    };
-    if (m->pool) m->pool->run((unsigned)G, one);
-    else for (unsigned g = 0; g < G; g++) one(g);
-    for (size_t g = 0; g < G; g++)
-        if (rc[g] != CRYO_OK) {
-            snprintf(m->err, sizeof m->err, "device handle %zu: %s", g, cryo_codec_last_error(m->h[g]));
-            return rc[g];
-        }
-    return CRYO_OK;
+    return guarded([&] {
+        const size_t G = m->h.size();
+        const std::vector<std::vector<size_t>> share = cryo::deal_shares(n, G, owner);
+        std::vector<int> rc(G, CRYO_OK);
+        const std::function<void(unsigned)> one = [&](unsigned g) {
+            if (!share[g].empty()) {
+                rc[g] = guarded([&] { return fn(m->h[g], (size_t)g, share[g]); });
+                ws_trim_after_call(m->h[g]); /* the keep limit holds per handle, whoever dispatched the call */
+            }
+        };
+        if (m->pool) m->pool->run((unsigned)G, one);
+        else for (unsigned g = 0; g < G; g++) one(g);
+        for (size_t g = 0; g < G; g++)
+            if (rc[g] != CRYO_OK) {
+                snprintf(m->err, sizeof m->err, "device handle %zu: %s", g, cryo_codec_last_error(m->h[g]));
+                return rc[g];
+            }
+        return (int)CRYO_OK;
+    });
+}
+/* round-robin */
+template <class Fn> static int multi_run(cryo_multi *m, size_t n, const Fn &fn)
+{
+    const cryo::RoundRobin deal{n, m->h.size()};
+    return multi_run(m, n, fn, [&](size_t i) { return deal.handle_of(i); });
 }
 namespace {
 /* a share's streams: those of the blocks idx[k], in that order */
 struct ShareStreams {
     std::vector<const void *> src;
     std::vector<uint32_t> sz;
-    ShareStreams(const void *const *h_src, const uint32_t *h_src_size, const std::vector<size_t> &idx) : src(idx.size()), sz(idx.size())
-    {
-        for (size_t k = 0; k < idx.size(); k++) { src[k] = h_src[idx[k]]; sz[k] = h_src_size[idx[k]]; }
-    }
+    ShareStreams(const void *const *h_src, const uint32_t *h_src_size, const std::vector<size_t> &idx)
+        : src(cryo::gather(idx, h_src)), sz(cryo::gather(idx, h_src_size)) {}
 };
 } // namespace
-/* the blocks of a round-robin call of n blocks that the handles before g hold: handle q has blocks q, q + G, ... */
-static uint64_t blocks_before(size_t n, size_t G, size_t g)
+/* how compress, check and the decompress calls begin: CRYO_E_ARG without a handle or with bad arguments, CRYO_OK for no block,
+ * CRYO_E_ARG for a null pointer -- in that order -- else MULTI_GO.  The scan calls, recode and fetch keep an order of their own */
+enum { MULTI_GO = 1 };
+static int multi_begin(const cryo_multi *m, bool args_ok, size_t n, bool ptrs_ok)
 {
-    uint64_t before = 0;
-    for (size_t q = 0; q < g && q < n; q++) before += (uint64_t)((n - q + G - 1) / G);
-    return before;
+    if (!m || m->h.empty() || !args_ok) return CRYO_E_ARG;
+    if (n == 0) return CRYO_OK;
+    return ptrs_ok ? (int)MULTI_GO : (int)CRYO_E_ARG;
+}
+/* one call on every handle; the first error ends it */
+template <class Call> static int multi_each(cryo_multi *m, Call call)
+{
+    for (cryo_codec *c : m->h) {
+        const int rc = call(c);
+        if (rc != CRYO_OK) return rc;
+    }
+    return CRYO_OK;
 }
 extern "C" {
 
 int cryo_multi_compress_blocks(cryo_multi *m, int method, int param, const void *h_src, size_t block_size, size_t n,
                                void *h_dst, size_t dst_stride, uint32_t *h_out_size)
 {
-    if (!m || m->h.empty() || !method_ok(method) || !block_size_ok(block_size)) return CRYO_E_ARG;
-    if (n == 0) return CRYO_OK;
-    if (!h_src || !h_dst || !h_out_size) return CRYO_E_ARG;
+    const int go = multi_begin(m, method_ok(method) && block_size_ok(block_size), n, h_src && h_dst && h_out_size);
+    if (go != MULTI_GO) return go;
     if (dst_stride < cryo_codec_bound(method, block_size)) return CRYO_E_DSTSIZE;
     for (cryo_codec *c : m->h) c->vfy_failed = false; /* a handle with no share in this call reports nothing */
     if (m->h.size() == 1) return cryo_codec_compress_blocks(m->h[0], method, param, h_src, block_size, n, h_dst, dst_stride, h_out_size);
-    return guarded([&] {
-        return multi_run(m, n, [&](size_t g, const std::vector<size_t> &idx) {
-            std::vector<const void *> src(idx.size());
-            std::vector<void *> dst(idx.size());
-            std::vector<uint32_t> sz(idx.size());
-            for (size_t k = 0; k < idx.size(); k++) {
-                src[k] = (const uint8_t *)h_src + idx[k] * block_size;
-                dst[k] = (uint8_t *)h_dst + idx[k] * dst_stride;
-            }
-            const int rc = compress_blocks_ptrs(m->h[g], method, param, src.data(), block_size, idx.size(), dst.data(), sz.data());
-            if (rc == CRYO_OK) for (size_t k = 0; k < idx.size(); k++) h_out_size[idx[k]] = sz[k];
-            if (rc == CRYO_E_VERIFY && m->h[g]->vfy_failed) /* the block's index in the whole call */
-                set_verify_failure(m->h[g], idx[m->h[g]->vfy_block], m->h[g]->vfy_off);
-            return rc;
-        });
+    return multi_run(m, n, [&](cryo_codec *c, size_t, const std::vector<size_t> &idx) {
+        std::vector<const void *> src(idx.size());
+        std::vector<void *> dst(idx.size());
+        std::vector<uint32_t> sz(idx.size());
+        for (size_t k = 0; k < idx.size(); k++) {
+            src[k] = (const uint8_t *)h_src + idx[k] * block_size;
+            dst[k] = (uint8_t *)h_dst + idx[k] * dst_stride;
+        }
+        const int rc = compress_blocks_ptrs(c, method, param, src.data(), block_size, idx.size(), dst.data(), sz.data());
+        if (rc == CRYO_OK) cryo::scatter(idx, sz.data(), h_out_size);
+        if (rc == CRYO_E_VERIFY && c->vfy_failed) set_verify_failure(c, idx[c->vfy_block], c->vfy_off); /* the index in the whole call */
+        return rc;
     });
 }
 
@@ -3344,26 +3344,23 @@ int cryo_multi_compress_blocks(cryo_multi *m, int method, int param, const void 
 static int multi_decompress(cryo_multi *m, int method, const void *const *h_src, const uint32_t *h_src_size, size_t n,
                             void *h_dst, void *const *h_dst_each, size_t block_size, int32_t *h_status)
 {
-    return guarded([&] {
-        return multi_run(m, n, [&](size_t g, const std::vector<size_t> &idx) {
-            const ShareStreams in(h_src, h_src_size, idx);
-            std::vector<void *> dst(idx.size());
-            std::vector<int32_t> st(idx.size());
-            for (size_t k = 0; k < idx.size(); k++)
-                dst[k] = h_dst_each ? h_dst_each[idx[k]] : (void *)((uint8_t *)h_dst + idx[k] * block_size);
-            const int rc = decompress_blocks_impl(m->h[g], method, in.src.data(), in.sz.data(), idx.size(), nullptr, dst.data(), block_size, st.data());
-            if (rc == CRYO_OK) for (size_t k = 0; k < idx.size(); k++) h_status[idx[k]] = st[k];
-            return rc;
-        });
+    return multi_run(m, n, [&](cryo_codec *c, size_t, const std::vector<size_t> &idx) {
+        const ShareStreams in(h_src, h_src_size, idx);
+        std::vector<void *> dst(idx.size());
+        std::vector<int32_t> st(idx.size());
+        for (size_t k = 0; k < idx.size(); k++)
+            dst[k] = h_dst_each ? h_dst_each[idx[k]] : (void *)((uint8_t *)h_dst + idx[k] * block_size);
+        const int rc = decompress_blocks_impl(c, method, in.src.data(), in.sz.data(), idx.size(), nullptr, dst.data(), block_size, st.data());
+        if (rc == CRYO_OK) cryo::scatter(idx, st.data(), h_status);
+        return rc;
     });
 }
 
 int cryo_multi_decompress_blocks(cryo_multi *m, int method, const void *const *h_src, const uint32_t *h_src_size, size_t n,
                                  void *h_dst, size_t block_size, int32_t *h_status)
 {
-    if (!m || m->h.empty() || !method_ok(method) || !block_size_ok(block_size)) return CRYO_E_ARG;
-    if (n == 0) return CRYO_OK;
-    if (!h_src || !h_src_size || !h_dst || !h_status) return CRYO_E_ARG;
+    const int go = multi_begin(m, method_ok(method) && block_size_ok(block_size), n, h_src && h_src_size && h_dst && h_status);
+    if (go != MULTI_GO) return go;
     if (m->h.size() == 1) return cryo_codec_decompress_blocks(m->h[0], method, h_src, h_src_size, n, h_dst, block_size, h_status);
     return multi_decompress(m, method, h_src, h_src_size, n, h_dst, nullptr, block_size, h_status);
 }
@@ -3371,9 +3368,8 @@ int cryo_multi_decompress_blocks(cryo_multi *m, int method, const void *const *h
 int cryo_multi_decompress_blocks_to(cryo_multi *m, int method, const void *const *h_src, const uint32_t *h_src_size, size_t n,
                                     void *const *h_dst, size_t block_size, int32_t *h_status)
 {
-    if (!m || m->h.empty() || !method_ok(method) || !block_size_ok(block_size)) return CRYO_E_ARG;
-    if (n == 0) return CRYO_OK;
-    if (!h_src || !h_src_size || !h_dst || !h_status) return CRYO_E_ARG;
+    const int go = multi_begin(m, method_ok(method) && block_size_ok(block_size), n, h_src && h_src_size && h_dst && h_status);
+    if (go != MULTI_GO) return go;
     if (m->h.size() == 1) return cryo_codec_decompress_blocks_to(m->h[0], method, h_src, h_src_size, n, h_dst, block_size, h_status);
     return multi_decompress(m, method, h_src, h_src_size, n, nullptr, h_dst, block_size, h_status);
 }
@@ -3381,18 +3377,15 @@ int cryo_multi_decompress_blocks_to(cryo_multi *m, int method, const void *const
 int cryo_multi_check_blocks(cryo_multi *m, int method, const void *const *h_src, const uint32_t *h_src_size, size_t n,
                             size_t block_size, cryo_check_result *h_result)
 {
-    if (!m || m->h.empty() || !method_ok(method) || !check_block_size_ok(block_size)) return CRYO_E_ARG;
-    if (n == 0) return CRYO_OK;
-    if (!h_src || !h_src_size || !h_result) return CRYO_E_ARG;
+    const int go = multi_begin(m, method_ok(method) && check_block_size_ok(block_size), n, h_src && h_src_size && h_result);
+    if (go != MULTI_GO) return go;
     if (m->h.size() == 1) return cryo_codec_check_blocks(m->h[0], method, h_src, h_src_size, n, block_size, h_result);
-    return guarded([&] {
-        return multi_run(m, n, [&](size_t g, const std::vector<size_t> &idx) {
-            const ShareStreams in(h_src, h_src_size, idx);
-            std::vector<cryo_check_result> res(idx.size());
-            const int rc = decompress_blocks_impl(m->h[g], method, in.src.data(), in.sz.data(), idx.size(), nullptr, nullptr, block_size, nullptr, res.data());
-            if (rc == CRYO_OK) for (size_t k = 0; k < idx.size(); k++) h_result[idx[k]] = res[k];
-            return rc;
-        });
+    return multi_run(m, n, [&](cryo_codec *c, size_t, const std::vector<size_t> &idx) {
+        const ShareStreams in(h_src, h_src_size, idx);
+        std::vector<cryo_check_result> res(idx.size());
+        const int rc = decompress_blocks_impl(c, method, in.src.data(), in.sz.data(), idx.size(), nullptr, nullptr, block_size, nullptr, res.data());
+        if (rc == CRYO_OK) cryo::scatter(idx, res.data(), h_result);
+        return rc;
     });
 }
 
@@ -3414,23 +3407,18 @@ int cryo_multi_recode_blocks(cryo_multi *m, int src_method, const void *const *h
     const size_t slot = (cryo_codec_bound(dst_method, block_size) + 15) & ~(size_t)15;
     if (dst_cap / G / slot < (n + G - 1) / G) return CRYO_E_DSTSIZE;
     const size_t region = (dst_cap / G) & ~(size_t)15;
-    return guarded([&] {
-        return multi_run(m, n, [&](size_t g, const std::vector<size_t> &idx) {
-            const ShareStreams in(h_src, h_src_size, idx);
-            std::vector<uint32_t> osz(idx.size());
-            std::vector<uint64_t> off(idx.size());
-            std::vector<int32_t> st(idx.size());
-            const int rc = recode_blocks_impl(m->h[g], src_method, in.src.data(), in.sz.data(), idx.size(), block_size, dst_method,
-                                              dst_param, (uint8_t *)h_dst + g * region, region, g * region, off.data(), osz.data(),
-                                              st.data());
-            if (rc != CRYO_OK) return rc;
-            for (size_t k = 0; k < idx.size(); k++) {
-                h_out_off[idx[k]] = off[k];
-                h_out_size[idx[k]] = osz[k];
-                h_status[idx[k]] = st[k];
-            }
-            return (int)CRYO_OK;
-        });
+    return multi_run(m, n, [&](cryo_codec *c, size_t g, const std::vector<size_t> &idx) {
+        const ShareStreams in(h_src, h_src_size, idx);
+        std::vector<uint32_t> osz(idx.size());
+        std::vector<uint64_t> off(idx.size());
+        std::vector<int32_t> st(idx.size());
+        const int rc = recode_blocks_impl(c, src_method, in.src.data(), in.sz.data(), idx.size(), block_size, dst_method, dst_param,
+                                          (uint8_t *)h_dst + g * region, region, g * region, off.data(), osz.data(), st.data());
+        if (rc != CRYO_OK) return rc;
+        cryo::scatter(idx, off.data(), h_out_off);
+        cryo::scatter(idx, osz.data(), h_out_size);
+        cryo::scatter(idx, st.data(), h_status);
+        return (int)CRYO_OK;
     });
 }
 
@@ -3452,34 +3440,32 @@ int cryo_multi_fetch_blocks(cryo_multi *m, int method, const void *const *h_src,
         if (h_req_first[i + 1] < h_req_first[i]) return CRYO_E_ARG;
     if (h_req_first[n] > 0 && (!h_pos || !h_result)) return CRYO_E_ARG;
     if (!h_dst && dst_cap > 0) return CRYO_E_ARG;
+    const cryo::RoundRobin deal{n, G};
     std::vector<uint64_t> end(G, 0);
-    const int rc = guarded([&] {
-        return multi_run(m, n, [&](size_t g, const std::vector<size_t> &idx) {
-            const uint64_t start = blocks_before(n, G, g) * block_size;
-            const uint64_t want = (uint64_t)idx.size() * block_size;
-            const uint64_t cap = dst_cap > start ? (dst_cap - start < want ? dst_cap - start : want) : 0;
-            const ShareStreams in(h_src, h_src_size, idx);
-            std::vector<uint64_t> first(idx.size() + 1, 0);
-            for (size_t k = 0; k < idx.size(); k++) first[k + 1] = first[k] + (h_req_first[idx[k] + 1] - h_req_first[idx[k]]);
-            std::vector<uint16_t> pos(first.back() ? first.back() : 1);
-            std::vector<cryo_fetch_result> res(first.back() ? first.back() : 1);
-            for (size_t k = 0; k < idx.size(); k++)
-                if (first[k + 1] > first[k])
-                    memcpy(&pos[first[k]], h_pos + h_req_first[idx[k]], (first[k + 1] - first[k]) * sizeof(uint16_t));
-            uint64_t tot = 0;
-            const int r = fetch_blocks_impl(m->h[g], method, in.src.data(), in.sz.data(), idx.size(), block_size, first.data(), pos.data(),
-                                            cap ? (uint8_t *)h_dst + start : nullptr, cap, start, res.data(), &tot);
-            if (r != CRYO_OK) return r;
-            for (size_t k = 0; k < idx.size(); k++)
-                if (first[k + 1] > first[k])
-                    memcpy(h_result + h_req_first[idx[k]], &res[first[k]], (first[k + 1] - first[k]) * sizeof(cryo_fetch_result));
-            end[g] = tot ? start + tot : 0;
-            return (int)CRYO_OK;
-        });
+    const int rc = multi_run(m, n, [&](cryo_codec *c, size_t g, const std::vector<size_t> &idx) {
+        const cryo::ShareRegion bytes(dst_cap, deal.before(g), idx.size(), block_size);
+        const ShareStreams in(h_src, h_src_size, idx);
+        /* a block's requests are a range of the call's, of any length: they are gathered and their records scattered range by
+         * range here, not by the per-block scatter of multi_share.h */
+        std::vector<uint64_t> first(idx.size() + 1, 0);
+        for (size_t k = 0; k < idx.size(); k++) first[k + 1] = first[k] + (h_req_first[idx[k] + 1] - h_req_first[idx[k]]);
+        std::vector<uint16_t> pos(first.back() ? first.back() : 1);
+        std::vector<cryo_fetch_result> res(first.back() ? first.back() : 1);
+        for (size_t k = 0; k < idx.size(); k++)
+            if (first[k + 1] > first[k])
+                memcpy(&pos[first[k]], h_pos + h_req_first[idx[k]], (first[k + 1] - first[k]) * sizeof(uint16_t));
+        uint64_t tot = 0;
+        const int r = fetch_blocks_impl(c, method, in.src.data(), in.sz.data(), idx.size(), block_size, first.data(), pos.data(),
+                                        bytes.in((uint8_t *)h_dst), bytes.cap, bytes.first, res.data(), &tot);
+        if (r != CRYO_OK) return r;
+        for (size_t k = 0; k < idx.size(); k++)
+            if (first[k + 1] > first[k])
+                memcpy(h_result + h_req_first[idx[k]], &res[first[k]], (first[k + 1] - first[k]) * sizeof(cryo_fetch_result));
+        end[g] = bytes.end(tot);
+        return (int)CRYO_OK;
     });
     if (rc != CRYO_OK) return rc;
-    for (size_t g = 0; g < G; g++)
-        if (end[g] > *h_total) *h_total = end[g];
+    *h_total = cryo::last_end(end);
     return CRYO_OK;
 }
 
@@ -3501,32 +3487,25 @@ int cryo_multi_filter_blocks(cryo_multi *m, int method, const void *const *h_src
     const bool count_only = (f->flags & CRYO_FILTER_COUNT_ONLY) != 0;
     if (!h_src || !h_src_size || !h_blocks) return CRYO_E_ARG;
     if (!count_only && ((!h_dst && dst_cap > 0) || (!h_rec && rec_cap > 0))) return CRYO_E_ARG;
+    const cryo::RoundRobin deal{n, G};
     std::vector<uint64_t> end_b(G, 0), end_r(G, 0);
-    const int rc = guarded([&] {
-        return multi_run(m, n, [&](size_t g, const std::vector<size_t> &idx) {
-            const uint64_t before = blocks_before(n, G, g);
-            const uint64_t b0 = before * block_size, r0 = before * cryo::kHeapMaxItems;
-            const uint64_t want_b = (uint64_t)idx.size() * block_size, want_r = (uint64_t)idx.size() * cryo::kHeapMaxItems;
-            const uint64_t cap_b = dst_cap > b0 ? (dst_cap - b0 < want_b ? dst_cap - b0 : want_b) : 0;
-            const uint64_t cap_r = rec_cap > r0 ? (rec_cap - r0 < want_r ? rec_cap - r0 : want_r) : 0;
-            const ShareStreams in(h_src, h_src_size, idx);
-            std::vector<cryo_filter_block> rows(idx.size());
-            uint64_t tot[2] = {0, 0};
-            const int r = filter_blocks_impl(m->h[g], method, in.src.data(), in.sz.data(), idx.size(), block_size, f,
-                                             cap_b ? (uint8_t *)h_dst + b0 : nullptr, cap_b, b0, cap_r ? h_rec + r0 : nullptr, cap_r,
-                                             r0, rows.data(), tot);
-            if (r != CRYO_OK) return r;
-            for (size_t k = 0; k < idx.size(); k++) h_blocks[idx[k]] = rows[k];
-            end_b[g] = tot[0] ? b0 + tot[0] : 0;
-            end_r[g] = tot[1] ? r0 + tot[1] : 0;
-            return (int)CRYO_OK;
-        });
+    const int rc = multi_run(m, n, [&](cryo_codec *c, size_t g, const std::vector<size_t> &idx) {
+        const cryo::ShareRegion bytes(dst_cap, deal.before(g), idx.size(), block_size);
+        const cryo::ShareRegion recs(rec_cap, deal.before(g), idx.size(), cryo::kHeapMaxItems);
+        const ShareStreams in(h_src, h_src_size, idx);
+        std::vector<cryo_filter_block> rows(idx.size());
+        uint64_t tot[2] = {0, 0};
+        const int r = filter_blocks_impl(c, method, in.src.data(), in.sz.data(), idx.size(), block_size, f, bytes.in((uint8_t *)h_dst),
+                                         bytes.cap, bytes.first, recs.in(h_rec), recs.cap, recs.first, rows.data(), tot);
+        if (r != CRYO_OK) return r;
+        cryo::scatter(idx, rows.data(), h_blocks);
+        end_b[g] = bytes.end(tot[0]);
+        end_r[g] = recs.end(tot[1]);
+        return (int)CRYO_OK;
     });
     if (rc != CRYO_OK) return rc;
-    for (size_t g = 0; g < G; g++) {
-        if (end_b[g] > h_total[0]) h_total[0] = end_b[g];
-        if (end_r[g] > h_total[1]) h_total[1] = end_r[g];
-    }
+    h_total[0] = cryo::last_end(end_b);
+    h_total[1] = cryo::last_end(end_r);
     return CRYO_OK;
 }
 
@@ -3542,20 +3521,15 @@ int cryo_multi_agg_blocks(cryo_multi *m, int method, const void *const *h_src, c
     if (n == 0) return CRYO_OK;
     if (!h_src || !h_src_size || !h_blocks || !h_cells) return CRYO_E_ARG;
     const size_t nc = agg->ncols;
-    return guarded([&] {
-        return multi_run(m, n, [&](size_t g, const std::vector<size_t> &idx) {
-            const ShareStreams in(h_src, h_src_size, idx);
-            std::vector<cryo_agg_block> rows(idx.size());
-            std::vector<cryo_agg_cell> cells(idx.size() * nc);
-            const int r = agg_blocks_impl(m->h[g], method, in.src.data(), in.sz.data(), idx.size(), block_size, f, agg, rows.data(),
-                                          cells.data());
-            if (r != CRYO_OK) return r;
-            for (size_t k = 0; k < idx.size(); k++) {
-                h_blocks[idx[k]] = rows[k];
-                memcpy(h_cells + idx[k] * nc, &cells[k * nc], nc * sizeof(cryo_agg_cell));
-            }
-            return (int)CRYO_OK;
-        });
+    return multi_run(m, n, [&](cryo_codec *c, size_t, const std::vector<size_t> &idx) {
+        const ShareStreams in(h_src, h_src_size, idx);
+        std::vector<cryo_agg_block> rows(idx.size());
+        std::vector<cryo_agg_cell> cells(idx.size() * nc);
+        const int r = agg_blocks_impl(c, method, in.src.data(), in.sz.data(), idx.size(), block_size, f, agg, rows.data(), cells.data());
+        if (r != CRYO_OK) return r;
+        cryo::scatter(idx, rows.data(), h_blocks);
+        cryo::scatter(idx, cells.data(), h_cells, nc);
+        return (int)CRYO_OK;
     });
 }
 
@@ -3580,27 +3554,26 @@ int cryo_multi_group_blocks(cryo_multi *m, int method, const void *const *h_src,
     std::vector<std::vector<cryo_group_rec>> recs(G);
     std::vector<std::vector<cryo_agg_cell>> cells(G);
     std::vector<uint64_t> tot(G, 0);
-    const int rc = guarded([&] {
-        return multi_run(m, n, [&](size_t g, const std::vector<size_t> &idx) {
-            const ShareStreams in(h_src, h_src_size, idx);
-            /* a share's room: its worst case, or the whole call's room when that is less -- a share that needs more than the
-             * call has room for fails the call as the single handle would */
-            const size_t cap = idx.size() * S < group_cap ? idx.size() * S : group_cap;
-            rows[g].resize(idx.size());
-            recs[g].resize(cap ? cap : 1);
-            cells[g].resize(cap * nc ? cap * nc : 1);
-            return group_blocks_impl(m->h[g], method, in.src.data(), in.sz.data(), idx.size(), block_size, f, grp, agg, rows[g].data(),
-                                     recs[g].data(), cap, cells[g].data(), &tot[g]);
-        });
+    const int rc = multi_run(m, n, [&](cryo_codec *c, size_t g, const std::vector<size_t> &idx) {
+        const ShareStreams in(h_src, h_src_size, idx);
+        /* a share's room: its worst case, or the whole call's room when that is less -- a share that needs more than the
+         * call has room for fails the call as the single handle would */
+        const size_t cap = idx.size() * S < group_cap ? idx.size() * S : group_cap;
+        rows[g].resize(idx.size());
+        recs[g].resize(cap ? cap : 1);
+        cells[g].resize(cap * nc ? cap * nc : 1);
+        return group_blocks_impl(c, method, in.src.data(), in.sz.data(), idx.size(), block_size, f, grp, agg, rows[g].data(),
+                                 recs[g].data(), cap, cells[g].data(), &tot[g]);
     });
     uint64_t total = 0;
     for (size_t g = 0; g < G; g++) total += tot[g];
     if (rc != CRYO_OK) return rc;
     *h_total = total;
     if (total > group_cap) return CRYO_E_DSTSIZE;
+    const cryo::RoundRobin deal{n, G};
     uint64_t at = 0;
     for (size_t i = 0; i < n; i++) {
-        const size_t g = i % G, k = i / G;
+        const size_t g = deal.handle_of(i), k = deal.entry_of(i);
         cryo_group_block row = rows[g][k];
         if (row.n_groups) {
             memcpy(h_groups + at, &recs[g][row.first_group], row.n_groups * sizeof(cryo_group_rec));
@@ -3630,58 +3603,49 @@ int cryo_multi_project_blocks(cryo_multi *m, int method, const void *const *h_sr
     h_total[0] = h_total[1] = 0;
     if (n == 0) return CRYO_OK;
     if (!h_src || !h_src_size || !h_blocks || (!h_rows && row_cap > 0) || (!h_rec && rec_cap > 0)) return CRYO_E_ARG;
+    const cryo::RoundRobin deal{n, G};
     std::vector<uint64_t> end_w(G, 0), end_r(G, 0);
-    const int rc = guarded([&] {
-        return multi_run(m, n, [&](size_t g, const std::vector<size_t> &idx) {
-            const uint64_t first = blocks_before(n, G, g) * cryo::kHeapMaxItems, want = (uint64_t)idx.size() * cryo::kHeapMaxItems;
-            const uint64_t cap_w = row_cap > first ? (row_cap - first < want ? row_cap - first : want) : 0;
-            const uint64_t cap_r = rec_cap > first ? (rec_cap - first < want ? rec_cap - first : want) : 0;
-            const ShareStreams in(h_src, h_src_size, idx);
-            std::vector<cryo_project_block> rows(idx.size());
-            uint64_t tot[2] = {0, 0};
-            const int r = project_blocks_impl(m->h[g], method, in.src.data(), in.sz.data(), idx.size(), block_size, f, prj,
-                                              cap_w ? (uint8_t *)h_rows + first * pt.row_bytes : nullptr, cap_w, first,
-                                              cap_r ? h_rec + first : nullptr, cap_r, first, rows.data(), tot);
-            if (r != CRYO_OK) return r;
-            for (size_t k = 0; k < idx.size(); k++) h_blocks[idx[k]] = rows[k];
-            end_w[g] = tot[0] ? first + tot[0] : 0;
-            end_r[g] = tot[1] ? first + tot[1] : 0;
-            return (int)CRYO_OK;
-        });
+    const int rc = multi_run(m, n, [&](cryo_codec *c, size_t g, const std::vector<size_t> &idx) {
+        const cryo::ShareRegion rows(row_cap, deal.before(g), idx.size(), cryo::kHeapMaxItems);
+        const cryo::ShareRegion recs(rec_cap, deal.before(g), idx.size(), cryo::kHeapMaxItems);
+        const ShareStreams in(h_src, h_src_size, idx);
+        std::vector<cryo_project_block> table(idx.size());
+        uint64_t tot[2] = {0, 0};
+        const int r = project_blocks_impl(c, method, in.src.data(), in.sz.data(), idx.size(), block_size, f, prj,
+                                          rows.in((uint8_t *)h_rows, pt.row_bytes), rows.cap, rows.first, recs.in(h_rec), recs.cap,
+                                          recs.first, table.data(), tot);
+        if (r != CRYO_OK) return r;
+        cryo::scatter(idx, table.data(), h_blocks);
+        end_w[g] = rows.end(tot[0]);
+        end_r[g] = recs.end(tot[1]);
+        return (int)CRYO_OK;
     });
     if (rc != CRYO_OK) return rc;
-    for (size_t g = 0; g < G; g++) {
-        if (end_w[g] > h_total[0]) h_total[0] = end_w[g];
-        if (end_r[g] > h_total[1]) h_total[1] = end_r[g];
-    }
+    h_total[0] = cryo::last_end(end_w);
+    h_total[1] = cryo::last_end(end_r);
     return CRYO_OK;
 }
 
 int cryo_multi_decompress_blocks_keyed(cryo_multi *m, int method, const uint64_t *keys, const void *const *h_src,
                                        const uint32_t *h_src_size, size_t n, void *const *h_dst, size_t block_size, int32_t *h_status)
 {
-    if (!m || m->h.empty() || !method_ok(method) || !block_size_ok(block_size)) return CRYO_E_ARG;
-    if (n == 0) return CRYO_OK;
-    if (!keys || !h_src || !h_src_size || !h_dst || !h_status) return CRYO_E_ARG;
+    const int go = multi_begin(m, method_ok(method) && block_size_ok(block_size), n, keys && h_src && h_src_size && h_dst && h_status);
+    if (go != MULTI_GO) return go;
     if (m->h.size() == 1) return cryo_codec_decompress_blocks_keyed(m->h[0], method, keys, h_src, h_src_size, n, h_dst, block_size, h_status);
-    /* a keyed block always goes to the same handle (its pool entry lives there); unkeyed ones round-robin */
     const size_t G = m->h.size();
-    return guarded([&] {
-        return multi_run(
-            m, n,
-            [&](size_t g, const std::vector<size_t> &idx) {
-                const ShareStreams in(h_src, h_src_size, idx);
-                std::vector<void *> dst(idx.size());
-                std::vector<uint64_t> ky(idx.size());
-                std::vector<int32_t> st(idx.size());
-                for (size_t k = 0; k < idx.size(); k++) { dst[k] = h_dst[idx[k]]; ky[k] = keys[idx[k]]; }
-                const int r = decompress_blocks_keyed_impl(m->h[g], method, ky.data(), in.src.data(), in.sz.data(), idx.size(), dst.data(),
-                                                           block_size, st.data());
-                if (r == CRYO_OK) for (size_t k = 0; k < idx.size(); k++) h_status[idx[k]] = st[k];
-                return r;
-            },
-            [&](size_t i) { return (size_t)(keys[i] ? keys[i] % G : i % G); });
-    });
+    return multi_run(
+        m, n,
+        [&](cryo_codec *c, size_t, const std::vector<size_t> &idx) {
+            const ShareStreams in(h_src, h_src_size, idx);
+            const std::vector<void *> dst = cryo::gather(idx, h_dst);
+            const std::vector<uint64_t> ky = cryo::gather(idx, keys);
+            std::vector<int32_t> st(idx.size());
+            const int r = decompress_blocks_keyed_impl(c, method, ky.data(), in.src.data(), in.sz.data(), idx.size(), dst.data(),
+                                                       block_size, st.data());
+            if (r == CRYO_OK) cryo::scatter(idx, st.data(), h_status);
+            return r;
+        },
+        [&](size_t i) { return cryo::keyed_owner(keys[i], i, G); });
 }
 
 int cryo_multi_set_option(cryo_multi *m, int option, int64_t value)
@@ -3689,31 +3653,17 @@ int cryo_multi_set_option(cryo_multi *m, int option, int64_t value)
     if (!m || m->h.empty()) return CRYO_E_ARG;
     /* a pool capacity is the total over the handles */
     const int64_t v = option == CRYO_OPT_POOL_BYTES ? value / (int64_t)m->h.size() : value;
-    for (cryo_codec *c : m->h) {
-        const int rc = cryo_codec_set_option(c, option, v);
-        if (rc != CRYO_OK) return rc;
-    }
-    return CRYO_OK;
+    return multi_each(m, [&](cryo_codec *c) { return cryo_codec_set_option(c, option, v); });
 }
 
 int cryo_multi_trim(cryo_multi *m)
 {
-    if (!m) return CRYO_E_ARG;
-    for (cryo_codec *c : m->h) {
-        const int rc = cryo_codec_trim(c);
-        if (rc != CRYO_OK) return rc;
-    }
-    return CRYO_OK;
+    return m ? multi_each(m, [](cryo_codec *c) { return cryo_codec_trim(c); }) : (int)CRYO_E_ARG;
 }
 
 int cryo_multi_pool_invalidate(cryo_multi *m, uint32_t key_hi, int all_entries)
 {
-    if (!m) return CRYO_E_ARG;
-    for (cryo_codec *c : m->h) {
-        const int rc = cryo_codec_pool_invalidate(c, key_hi, all_entries);
-        if (rc != CRYO_OK) return rc;
-    }
-    return CRYO_OK;
+    return m ? multi_each(m, [&](cryo_codec *c) { return cryo_codec_pool_invalidate(c, key_hi, all_entries); }) : (int)CRYO_E_ARG;
 }
 
 int cryo_multi_last_verify_failure(const cryo_multi *m, uint64_t *block, uint32_t *first_mismatch)

@@ -13,6 +13,7 @@ import numpy as np
 import agg_ref as ar
 import filter_ref as fr
 import group_ref as gr
+import multi_ref
 from filter_ref import (COUNT_ONLY, EQ, GE, GT, HEADER, INT2, INT4, INT8, ISNULL, ITEM, KEY_SIZE, LE, LT, MAX_ITEMS, NE, NOMATCH,  # noqa: F401
                         NOTNULL, OK, OVERLAP, STREAM, TUPLE, decode, maxalign)
 
@@ -235,20 +236,7 @@ def filter_call(blocks, atts, keys, flags=0, b_base=0, r_base=0):
 def multi_filter_call(blocks, atts, keys, G, B, flags=0):
     """what cryo_multi_filter_blocks with G handles gives (filter_ref.multi_call's layout): (table in call order, [(byte start,
     packed bytes, record start, records)] per handle with a share, (end of the last byte, of the last record used))"""
-    n = len(blocks)
-    table = np.zeros(n, fr.BLOCK)
-    regions, before, end_b, end_r = [], 0, 0, 0
-    for g in range(min(G, n)):
-        idx = list(range(g, n, G))
-        t, recs, packed, (tb, tr) = filter_call([blocks[i] for i in idx], atts, keys, flags, before * B, before * MAX_ITEMS)
-        table[idx] = t
-        regions.append((before * B, packed, before * MAX_ITEMS, recs))
-        if tb:
-            end_b = max(end_b, before * B + tb)
-        if tr:
-            end_r = max(end_r, before * MAX_ITEMS + tr)
-        before += len(idx)
-    return table, regions, (end_b, end_r)
+    return multi_ref.filter_multi(filter_call, fr.BLOCK, blocks, atts, keys, G, B, flags)
 
 
 # ---- the aggregate ----

@@ -16,6 +16,7 @@ import struct
 
 import numpy as np
 
+import multi_ref
 from layout_ref import decode, maxalign  # noqa: F401  (decode: the oracle's decode of a stream, or None)
 
 OK, STREAM, HEADER, ITEM, NOITEM, BADREQ, OVERLAP = 0, 1, 2, 3, 5, 6, 7
@@ -73,23 +74,7 @@ def multi_call(blocks, requests, G, B):
     """what cryo_multi_fetch_blocks with G handles gives: block i -> handle i mod G, handle g packs its share into a region of
     B * (its blocks) bytes, the regions in handle order.  Returns (records in call order, [(region start, packed bytes)] per
     handle with a share, total: the end of the last byte used)"""
-    n = len(blocks)
-    first = np.concatenate([[0], np.cumsum([len(r) for r in requests])]).astype(int)
-    records = np.zeros(int(first[-1]), RESULT)
-    regions, start, total = [], 0, 0
-    for g in range(min(G, n)):
-        idx = list(range(g, n, G))
-        recs, packed, tot = fetch_call([blocks[i] for i in idx], [requests[i] for i in idx], base=start)
-        at = 0
-        for i in idx:
-            k = len(requests[i])
-            records[first[i]:first[i] + k] = recs[at:at + k]
-            at += k
-        regions.append((start, packed))
-        if tot:
-            total = max(total, start + tot)
-        start += len(idx) * B
-    return records, regions, total
+    return multi_ref.fetch_multi(fetch_call, RESULT, blocks, requests, G, B)
 
 
 def build_block(B, lens, pad=0xEE, fill=None):

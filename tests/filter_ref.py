@@ -8,6 +8,7 @@ import struct
 
 import numpy as np
 
+import multi_ref
 from layout_ref import decode, maxalign  # noqa: F401  (decode: the oracle's decode of a stream, or None)
 
 OK, STREAM, HEADER, ITEM, OVERLAP, TUPLE = 0, 1, 2, 3, 7, 8
@@ -191,20 +192,7 @@ def multi_call(blocks, atts, keys, G, B, flags=0):
     """what cryo_multi_filter_blocks with G handles gives: block i -> handle i mod G; handle g has a tuple region of B x (its
     blocks) bytes and a record region of 290 x (its blocks) records, in handle order.  Returns (table in call order, [(byte
     start, packed bytes, record start, records)] per handle with a share, (end of the last byte, of the last record used))"""
-    n = len(blocks)
-    table = np.zeros(n, BLOCK)
-    regions, before, end_b, end_r = [], 0, 0, 0
-    for g in range(min(G, n)):
-        idx = list(range(g, n, G))
-        t, recs, packed, (tb, tr) = filter_call([blocks[i] for i in idx], atts, keys, flags, before * B, before * MAX_ITEMS)
-        table[idx] = t
-        regions.append((before * B, packed, before * MAX_ITEMS, recs))
-        if tb:
-            end_b = max(end_b, before * B + tb)
-        if tr:
-            end_r = max(end_r, before * MAX_ITEMS + tr)
-        before += len(idx)
-    return table, regions, (end_b, end_r)
+    return multi_ref.filter_multi(filter_call, BLOCK, blocks, atts, keys, G, B, flags)
 
 
 def tuples_of(table, records, dst, i):

@@ -9,6 +9,7 @@ import numpy as np
 
 import bytes_key_ref as br
 import filter_ref as fr
+import multi_ref
 from bytes_key_ref import HEADER, ITEM, MAX_ITEMS, NOMATCH, OK, STREAM, TUPLE, UNDECIDED, decode, maxalign  # noqa: F401
 
 MAX_COLS = 8
@@ -114,21 +115,7 @@ def multi_call(blocks, atts, keys, cols, G):
     """what cryo_multi_project_blocks with G handles gives: block i -> handle i mod G; handle g has a row region and a record
     region of 290 x (its blocks) entries each, in handle order.  Returns (table in call order, [(first entry of both regions,
     rows, records)] per handle with a share, (end of the last row, of the last record used))"""
-    n = len(blocks)
-    table = np.zeros(n, BLOCK)
-    regions, before, end_w, end_r = [], 0, 0, 0
-    for g in range(min(G, n)):
-        idx = list(range(g, n, G))
-        first = before * MAX_ITEMS
-        t, recs, rows, (tw, tr) = project_call([blocks[i] for i in idx], atts, keys, cols, first, first)
-        table[idx] = t
-        regions.append((first, rows, recs))
-        if tw:
-            end_w = max(end_w, first + tw)
-        if tr:
-            end_r = max(end_r, first + tr)
-        before += len(idx)
-    return table, regions, (end_w, end_r)
+    return multi_ref.project_multi(project_call, BLOCK, blocks, atts, keys, cols, G)
 
 
 def rows_of(table, records, rows, i):

@@ -2,6 +2,8 @@
 Python, for the CPU and GPU tests and the codec double.  Test infrastructure only."""
 import numpy as np
 
+import multi_ref
+
 
 def align16(x):
     return (int(x) + 15) & ~15
@@ -21,15 +23,7 @@ def pack_offsets(sizes, statuses, base=0):
 def multi_offsets(sizes, statuses, G, dst_cap):
     """block i -> handle i mod G; handle g packs its share, in block order, from g * region on, region = dst_cap // G
     rounded down to 16 bytes"""
-    region = (int(dst_cap) // G) & ~15
-    n = len(sizes)
-    out_s, out_o = [0] * n, [0] * n
-    for g in range(G):
-        idx = list(range(g, n, G))
-        s, o, _ = pack_offsets([sizes[i] for i in idx], [statuses[i] for i in idx], g * region)
-        for k, i in enumerate(idx):
-            out_s[i], out_o[i] = s[k], o[k]
-    return out_s, out_o, region
+    return multi_ref.offsets_multi(pack_offsets, sizes, statuses, G, dst_cap)
 
 
 def pack_buffer(streams, statuses, dst, base=0):

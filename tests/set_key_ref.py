@@ -12,6 +12,7 @@ import agg_ref as ar
 import bytes_key_ref as br
 import filter_ref as fr
 import group_ref as gr
+import multi_ref
 import project_ref as pr
 from bytes_key_ref import (BYTES, BYTES_MAX, COUNT_ONLY, EQ, GE, GT, HEADER, INT2, INT4, INT8, ISNULL, ITEM, KEY_SIZE, LE, LT,  # noqa: F401
                            MAX_ITEMS, NE, NOMATCH, NOTNULL, OK, OVERLAP, STREAM, TUPLE, UNDECIDED, decode, maxalign)
@@ -137,20 +138,7 @@ def filter_call(blocks, atts, keys, flags=0, b_base=0, r_base=0):
 
 def multi_filter_call(blocks, atts, keys, G, B, flags=0):
     """what cryo_multi_filter_blocks with G handles gives (filter_ref.multi_call's layout)"""
-    n = len(blocks)
-    table = np.zeros(n, fr.BLOCK)
-    regions, before, end_b, end_r = [], 0, 0, 0
-    for g in range(min(G, n)):
-        idx = list(range(g, n, G))
-        t, recs, packed, (tb, tr) = filter_call([blocks[i] for i in idx], atts, keys, flags, before * B, before * MAX_ITEMS)
-        table[idx] = t
-        regions.append((before * B, packed, before * MAX_ITEMS, recs))
-        if tb:
-            end_b = max(end_b, before * B + tb)
-        if tr:
-            end_r = max(end_r, before * MAX_ITEMS + tr)
-        before += len(idx)
-    return table, regions, (end_b, end_r)
+    return multi_ref.filter_multi(filter_call, fr.BLOCK, blocks, atts, keys, G, B, flags)
 
 
 # ---- the aggregate and the grouped scan ----
@@ -264,18 +252,4 @@ def project_call(blocks, atts, keys, cols, w_base=0, r_base=0):
 
 def multi_project_call(blocks, atts, keys, cols, G):
     """what cryo_multi_project_blocks with G handles gives (project_ref.multi_call's layout)"""
-    n = len(blocks)
-    table = np.zeros(n, pr.BLOCK)
-    regions, before, end_w, end_r = [], 0, 0, 0
-    for g in range(min(G, n)):
-        idx = list(range(g, n, G))
-        first = before * MAX_ITEMS
-        t, recs, rows, (tw, tr) = project_call([blocks[i] for i in idx], atts, keys, cols, first, first)
-        table[idx] = t
-        regions.append((first, rows, recs))
-        if tw:
-            end_w = max(end_w, first + tw)
-        if tr:
-            end_r = max(end_r, first + tr)
-        before += len(idx)
-    return table, regions, (end_w, end_r)
+    return multi_ref.project_multi(project_call, pr.BLOCK, blocks, atts, keys, cols, G)
