@@ -7,6 +7,7 @@
  * point fails with CRYO_E_NODEV / CRYO_E_HIP.
  */
 #include "cryo_codec.h"
+#include "host_stage.h"
 #include "kernels.h"
 #include "multi_share.h"
 
@@ -1830,6 +1831,18 @@ static int verify_failure(cryo_codec *c, uint64_t at)
     set_verify_failure(c, at, off);
     return CRYO_E_VERIFY;
 }
+/* what the encoders said of n blocks, once statuses and sizes are on the host: the first block that did not come out right ends
+ * the call; the sizes go to out_size (which may be `size` itself) */
+static int take_encoded(cryo_codec *c, const int32_t *status, const uint32_t *size, size_t n, size_t bound, uint32_t *out_size)
+{
+    for (size_t i = 0; i < n; i++) {
+        if (status[i] == CRYO_E_VERIFY) return verify_failure(c, i);
+        if (status[i] != CRYO_OK) return status[i];
+        if (size[i] == 0 || size[i] > bound) return CRYO_E_HIP;
+        out_size[i] = size[i];
+    }
+    return CRYO_OK;
+}
 
 int cryo_codec_verify_batch(cryo_codec *c, int method, const void *d_raw, uint64_t raw_stride, uint32_t block_size,
                             uint64_t n_blocks, const void *d_comp, const uint64_t *d_comp_off, const uint32_t *d_comp_size,
@@ -2068,9 +2081,7 @@ int cryo_codec_compress_block(cryo_codec *c, int method, int param, const void *
     HIP_TRY(c, hipMemcpyAsync(&csize, c->d_size, sizeof csize, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(&st, c->d_status, sizeof st, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (st == CRYO_E_VERIFY) return verify_failure(c, 0);
-    if (st != CRYO_OK) return st;
-    if (csize == 0 || csize > bound) return CRYO_E_HIP;
+    if ((rc = take_encoded(c, &st, &csize, 1, bound, &csize)) != CRYO_OK) return rc;
     HIP_TRY(c, hipMemcpyAsync(h_dst, c->d_out, csize, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     *out_size = csize;
@@ -2114,230 +2125,8 @@ int cryo_codec_decompress_block(cryo_codec *c, int method, const void *h_src, si
  * caller's memory.  One chunk's life: host gather -> H2D (codec stream) -> kernel(s) (codec stream) -> D2H
  * (transfer stream) -> host scatter.  The one-shot path (one H2D of everything, the kernel, one D2H from pageable
  * memory, single-threaded copies) reached 13-19 GB/s on 4096 x 128 KiB, a quarter of the link. */
-static size_t pipe_chunk_blocks(size_t n, size_t block_size, int method)
-{
-    (void)method;
-    size_t k = (n + 7) / 8;
-    const size_t min_blocks = (8u << 20) / block_size + 1; /* at least 8 MiB per chunk */
-    if (k < min_blocks) k = min_blocks;
-    return (k + 63) & ~(size_t)63;
-}
-/* one block is one wavefront's serial job: a launch needs thousands of blocks to fill the chip, so kernels run per
- * chunk only when a chunk still has that many (LZ4 decode of 128 KiB blocks); otherwise the transfers are chunked
- * around ONE launch over the whole call (the encoders took 8 x longer cut in eight) */
-static bool pipe_kernel_per_chunk(size_t chunk_blocks, int method, bool encode)
-{
-    return !encode && method == CRYO_METHOD_LZ4 && chunk_blocks >= 512;
-}
-
-/* h_src / h_dst: contiguous K-block buffers; or (multi-GPU shares, where a handle's blocks are every G-th of the call)
- * one pointer per block in h_src_each / h_dst_each */
-static int compress_blocks_piped(cryo_codec *c, int method, int param, const uint8_t *h_src, const void *const *h_src_each,
-                                 size_t block_size, size_t n, uint8_t *h_dst, void *const *h_dst_each, size_t dst_stride,
-                                 uint32_t *h_out_size)
-{
-    const size_t bound = cryo_codec_bound(method, block_size);
-    const size_t dstride = (bound + 15) & ~(size_t)15;
-    const size_t K = pipe_chunk_blocks(n, block_size, method), nch = (n + K - 1) / K;
-    int rc;
-    if ((rc = ensure_pipe_streams(c)) != CRYO_OK) return rc;
-    if ((rc = ensure(c, &c->hb_src, &c->hb_src_cap, n * block_size + 64)) != CRYO_OK) return rc;
-    if ((rc = ensure(c, &c->hb_dst, &c->hb_dst_cap, n * dstride + 64)) != CRYO_OK) return rc;
-    if ((rc = ensure(c, &c->hb_meta, &c->hb_meta_cap, n * 16 + 64)) != CRYO_OK) return rc;
-    if ((rc = ensure_pinned(c, n * 8 + 64)) != CRYO_OK) return rc;
-    for (int b = 0; b < 2; b++) {
-        if ((rc = ensure_pipe(c, b, K * block_size)) != CRYO_OK) return rc;
-        if ((rc = ensure_pipe(c, 2 + b, K * dstride)) != CRYO_OK) return rc;
-    }
-    uint32_t *d_sz = (uint32_t *)c->hb_meta;
-    int32_t *d_st = (int32_t *)(c->hb_meta + ((n * 4 + 15) & ~(size_t)15));
-    uint32_t *p_sz = (uint32_t *)c->pin;
-    int32_t *p_st = (int32_t *)((uint8_t *)c->pin + n * 4);
-    /* in: host gather of chunk c+1 overlaps the H2D of chunk c */
-    for (size_t ch = 0; ch < nch; ch++) {
-        const size_t lo = ch * K, hi = lo + K < n ? lo + K : n, cnt = hi - lo;
-        const int b = (int)(ch & 1);
-        if (ch >= 2) HIP_TRY(c, hipEventSynchronize(c->ev_in[b])); /* staging buffer b has left for the device */
-        if (h_src) parallel_copy(c, {{c->pipe_pin[b], h_src + lo * block_size, cnt * block_size}});
-        else {
-            std::vector<CopyJob> jobs;
-            for (size_t i = lo; i < hi; i++) jobs.push_back({(uint8_t *)c->pipe_pin[b] + (i - lo) * block_size, h_src_each[i], block_size});
-            parallel_copy(c, jobs);
-        }
-        HIP_TRY(c, hipMemcpyAsync(c->hb_src + lo * block_size, c->pipe_pin[b], cnt * block_size, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipEventRecord(c->ev_in[b], c->stream));
-    }
-    rc = cryo_codec_compress_batch(c, method, param, c->hb_src, block_size, (uint32_t)block_size, n, c->hb_dst, dstride, d_sz, d_st);
-    if (rc != CRYO_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
-    HIP_TRY(c, hipMemcpyAsync(p_sz, d_sz, n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(p_st, d_st, n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (size_t i = 0; i < n; i++) {
-        if (p_st[i] == CRYO_E_VERIFY) return verify_failure(c, i);
-        if (p_st[i] != CRYO_OK) return p_st[i];
-        if (p_sz[i] == 0 || p_sz[i] > bound) return CRYO_E_HIP;
-        h_out_size[i] = p_sz[i];
-    }
-    /* out: the D2H of chunk c+1 overlaps the host scatter of chunk c; only the bytes the blocks occupy travel */
-    auto d2h = [&](size_t ch) -> int {
-        const size_t lo = ch * K, hi = lo + K < n ? lo + K : n;
-        HIP_TRY(c, hipMemcpyAsync(c->pipe_pin[2 + (ch & 1)], c->hb_dst + lo * dstride, (hi - lo - 1) * dstride + p_sz[hi - 1],
-                                  hipMemcpyDeviceToHost, c->xfer));
-        HIP_TRY(c, hipEventRecord(c->ev_out[ch & 1], c->xfer));
-        return CRYO_OK;
-    };
-    if ((rc = d2h(0)) != CRYO_OK) return rc;
-    for (size_t ch = 0; ch < nch; ch++) {
-        const size_t lo = ch * K, hi = lo + K < n ? lo + K : n;
-        if (ch + 1 < nch && (rc = d2h(ch + 1)) != CRYO_OK) return rc;
-        HIP_TRY(c, hipEventSynchronize(c->ev_out[ch & 1]));
-        const uint8_t *po = (const uint8_t *)c->pipe_pin[2 + (ch & 1)];
-        std::vector<CopyJob> jobs;
-        for (size_t i = lo; i < hi; i++) jobs.push_back({h_dst ? (void *)(h_dst + i * dst_stride) : h_dst_each[i], po + (i - lo) * dstride, p_sz[i]});
-        parallel_copy(c, jobs);
-    }
-    return CRYO_OK;
-}
-
-/* h_dst: one contiguous K-block buffer; or one destination per block in h_dst_each (the cache's slots, a multi-GPU share):
- * then a block that failed leaves its destination untouched -- the statuses of a chunk travel with its blocks */
-/* h_result (the stored-block check): the same staging and uploads, the check instead of the decode, and only the results come
- * back (no decoded blocks, no statuses) */
-static int decompress_blocks_piped(cryo_codec *c, int method, const void *const *h_src, const uint32_t *h_src_size, size_t n,
-                                   uint8_t *h_dst, void *const *h_dst_each, size_t block_size, int32_t *h_status,
-                                   cryo_check_result *h_result = nullptr)
-{
-    const bool check = h_result != nullptr;
-    const size_t K = pipe_chunk_blocks(n, block_size, method), nch = (n + K - 1) / K;
-    const bool per_chunk = pipe_kernel_per_chunk(K, method, false);
-    /* device layout of the compressed side: [offsets u64 x n][sizes u32 x n][blocks, 16-byte aligned] */
-    const size_t o_off = 0, o_sz = n * 8, o_data = (n * 12 + 63) & ~(size_t)63;
-    std::vector<uint64_t> pos(n + 1);
-    size_t total = 0, max_chunk_in = 0;
-    for (size_t i = 0; i < n; i++) {
-        if (h_src_size[i] != 0 && !h_src[i]) return CRYO_E_ARG;
-        pos[i] = total;
-        total += ((size_t)h_src_size[i] + 15) & ~(size_t)15;
-    }
-    pos[n] = total;
-    for (size_t ch = 0; ch < nch; ch++) {
-        const size_t lo = ch * K, hi = lo + K < n ? lo + K : n;
-        if (pos[hi] - pos[lo] > max_chunk_in) max_chunk_in = pos[hi] - pos[lo];
-    }
-    int rc;
-    if ((rc = ensure_pipe_streams(c)) != CRYO_OK) return rc;
-    if ((rc = ensure_pinned(c, o_data + n * 4 + 64)) != CRYO_OK) return rc;
-    if ((rc = ensure(c, &c->hb_src, &c->hb_src_cap, o_data + total + 64)) != CRYO_OK) return rc;
-    if (!check && (rc = ensure(c, &c->hb_dst, &c->hb_dst_cap, n * block_size + 64)) != CRYO_OK) return rc;
-    if ((rc = ensure(c, &c->hb_meta, &c->hb_meta_cap, n * 16 + 64)) != CRYO_OK) return rc;
-    for (int b = 0; b < 2; b++) {
-        if ((rc = ensure_pipe(c, b, max_chunk_in + 64)) != CRYO_OK) return rc;
-        if (!check && (rc = ensure_pipe(c, 2 + b, K * block_size)) != CRYO_OK) return rc;
-    }
-    uint8_t *pin = (uint8_t *)c->pin;
-    uint64_t *p_off = (uint64_t *)(pin + o_off);
-    uint32_t *p_sz = (uint32_t *)(pin + o_sz);
-    int32_t *p_st = (int32_t *)(pin + o_data);
-    for (size_t i = 0; i < n; i++) { p_off[i] = o_data + pos[i]; p_sz[i] = h_src_size[i]; }
-    HIP_TRY(c, hipMemcpyAsync(c->hb_src, pin, o_data, hipMemcpyHostToDevice, c->stream));
-    c->xfer_ctr.h2d_bytes += o_data + total;
-    c->xfer_ctr.d2h_bytes += check ? n * sizeof(cryo_check_result) : n * block_size + n * sizeof(int32_t);
-    int32_t *d_st = (int32_t *)c->hb_meta;
-    cryo_check_result *d_res = (cryo_check_result *)c->hb_meta;
-    const uint64_t *d_off = (const uint64_t *)(c->hb_src + o_off);
-    const uint32_t *d_sz = (const uint32_t *)(c->hb_src + o_sz);
-    auto scatter = [&](size_t ch) -> int {
-        const size_t lo = ch * K, hi = lo + K < n ? lo + K : n;
-        HIP_TRY(c, hipEventSynchronize(c->ev_out[ch & 1]));
-        if (h_dst) { parallel_copy(c, {{h_dst + lo * block_size, c->pipe_pin[2 + (ch & 1)], (hi - lo) * block_size}}); return CRYO_OK; }
-        std::vector<CopyJob> jobs;
-        for (size_t i = lo; i < hi; i++) {
-            if (p_st[i] != CRYO_OK) continue;
-            if (!h_dst_each[i]) return CRYO_E_ARG;
-            jobs.push_back({h_dst_each[i], (const uint8_t *)c->pipe_pin[2 + (ch & 1)] + (i - lo) * block_size, block_size});
-        }
-        parallel_copy(c, jobs);
-        return CRYO_OK;
-    };
-    for (size_t ch = 0; ch < nch; ch++) {
-        const size_t lo = ch * K, hi = lo + K < n ? lo + K : n, cnt = hi - lo;
-        const int b = (int)(ch & 1);
-        if (ch >= 2) HIP_TRY(c, hipEventSynchronize(c->ev_in[b]));
-        {
-            uint8_t *pi = (uint8_t *)c->pipe_pin[b];
-            std::vector<CopyJob> jobs;
-            for (size_t i = lo; i < hi; i++)
-                if (h_src_size[i]) jobs.push_back({pi + (pos[i] - pos[lo]), h_src[i], h_src_size[i]});
-            parallel_copy(c, jobs);
-        }
-        if (pos[hi] > pos[lo])
-            HIP_TRY(c, hipMemcpyAsync(c->hb_src + o_data + pos[lo], c->pipe_pin[b], pos[hi] - pos[lo], hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipEventRecord(c->ev_in[b], c->stream));
-        if (!per_chunk) continue;
-        if (check) {
-            rc = check_pass(c, method, c->hb_src, d_off + lo, d_sz + lo, (uint32_t)block_size, cnt, d_res + lo);
-            if (rc != CRYO_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
-            continue;
-        }
-        rc = cryo_codec_decompress_batch(c, method, c->hb_src, d_off + lo, d_sz + lo, c->hb_dst + lo * block_size, block_size,
-                                         (uint32_t)block_size, cnt, d_st + lo);
-        if (rc != CRYO_OK) { (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(c->xfer); return rc; }
-        HIP_TRY(c, hipEventRecord(c->ev_k[b], c->stream));
-        if (ch >= 2 && (rc = scatter(ch - 2)) != CRYO_OK) return rc; /* frees output buffer b */
-        HIP_TRY(c, hipStreamWaitEvent(c->xfer, c->ev_k[b], 0));
-        HIP_TRY(c, hipMemcpyAsync(c->pipe_pin[2 + b], c->hb_dst + lo * block_size, cnt * block_size, hipMemcpyDeviceToHost, c->xfer));
-        if (!h_dst) HIP_TRY(c, hipMemcpyAsync(p_st + lo, d_st + lo, cnt * 4, hipMemcpyDeviceToHost, c->xfer)); /* the scatter skips failed blocks */
-        HIP_TRY(c, hipEventRecord(c->ev_out[b], c->xfer));
-    }
-    if (check) {
-        if (!per_chunk) {
-            rc = check_pass(c, method, c->hb_src, d_off, d_sz, (uint32_t)block_size, n, d_res);
-            if (rc != CRYO_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
-        }
-        HIP_TRY(c, hipMemcpyAsync(h_result, d_res, n * sizeof *d_res, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        return CRYO_OK;
-    }
-    if (!per_chunk) {
-        /* one launch over the whole call, then the D2H of chunk c+1 overlaps the host scatter of chunk c */
-        rc = cryo_codec_decompress_batch(c, method, c->hb_src, d_off, d_sz, c->hb_dst, block_size, (uint32_t)block_size, n, d_st);
-        if (rc != CRYO_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
-        HIP_TRY(c, hipEventRecord(c->ev_k[0], c->stream));
-        HIP_TRY(c, hipStreamWaitEvent(c->xfer, c->ev_k[0], 0));
-        if (!h_dst) HIP_TRY(c, hipMemcpyAsync(p_st, d_st, n * 4, hipMemcpyDeviceToHost, c->xfer)); /* before the first chunk's event */
-        auto d2h = [&](size_t ch) -> int {
-            const size_t lo = ch * K, hi = lo + K < n ? lo + K : n;
-            HIP_TRY(c, hipMemcpyAsync(c->pipe_pin[2 + (ch & 1)], c->hb_dst + lo * block_size, (hi - lo) * block_size, hipMemcpyDeviceToHost, c->xfer));
-            HIP_TRY(c, hipEventRecord(c->ev_out[ch & 1], c->xfer));
-            return CRYO_OK;
-        };
-        if ((rc = d2h(0)) != CRYO_OK) return rc;
-        for (size_t ch = 0; ch < nch; ch++) {
-            if (ch + 1 < nch) {
-                if (ch >= 1) { /* buffer (ch+1)&1 was scattered in the previous iteration */ }
-                if ((rc = d2h(ch + 1)) != CRYO_OK) return rc;
-            }
-            if ((rc = scatter(ch)) != CRYO_OK) return rc;
-        }
-        HIP_TRY(c, hipMemcpyAsync(p_st, d_st, n * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        memcpy(h_status, p_st, n * 4);
-        return CRYO_OK;
-    }
-    /* the trailing scatters read p_st on the host (which blocks failed): the whole-call status copy goes out behind them,
-     * not under them */
-    for (size_t ch = nch >= 2 ? nch - 2 : 0; ch < nch; ch++)
-        if ((rc = scatter(ch)) != CRYO_OK) return rc;
-    HIP_TRY(c, hipMemcpyAsync(p_st, d_st, n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    memcpy(h_status, p_st, n * 4);
-    return CRYO_OK;
-}
-
-static bool pipe_worth_it(const cryo_codec *c, size_t n, size_t block_size)
-{
-    return n * block_size >= c->pipe_min_bytes && n >= 128;
-}
+/* the chunk cut and the staged-stream layout are stated in host_stage.h */
+static bool pipe_worth_it(const cryo_codec *c, size_t n, size_t block_size) { return n * block_size >= c->pipe_min_bytes && n >= 128; }
 /* the four pinned staging buffers of the pipelined calls are K x block_size each: a 4096 x 1 MiB call leaves 2.3 GB of
  * pinned host memory behind.  What exceeds this cap is given back when the call ends. */
 static void pipe_trim(cryo_codec *c)
@@ -2346,177 +2135,388 @@ static void pipe_trim(cryo_codec *c)
     for (int i = 0; i < 4; i++)
         if (c->pipe_pin_cap[i] > kKeep) { (void)hipHostFree(c->pipe_pin[i]); c->pipe_pin[i] = nullptr; c->pipe_pin_cap[i] = 0; }
 }
-extern "C" {
+/* a pipelined body: an error return must not leave copies in flight into the handle's pinned buffers or the caller's memory */
+template <class Body> static int piped(cryo_codec *c, Body body)
+{
+    const int rc = body();
+    if (rc != CRYO_OK) { (void)hipStreamSynchronize(c->stream); if (c->xfer) (void)hipStreamSynchronize(c->xfer); }
+    pipe_trim(c);
+    return rc;
+}
+/* the return leg of a pipelined call whose kernel has run over the whole call: the D2H of chunk c+1 (bytes(c+1) from its first
+ * slot, the slots d_stride apart) on the transfer stream under landed(c), which waits for chunk c's event and scatters it */
+template <class Bytes, class Landed> static int pipe_return(cryo_codec *c, const cryo::ChunkCut &cut, const uint8_t *d_from, size_t d_stride, Bytes bytes, Landed landed)
+{
+    auto d2h = [&](size_t ch) -> int {
+        HIP_TRY(c, hipMemcpyAsync(c->pipe_pin[2 + (ch & 1)], d_from + cut.lo(ch) * d_stride, bytes(ch), hipMemcpyDeviceToHost, c->xfer));
+        HIP_TRY(c, hipEventRecord(c->ev_out[ch & 1], c->xfer));
+        return CRYO_OK;
+    };
+    int rc;
+    if ((rc = d2h(0)) != CRYO_OK) return rc;
+    for (size_t ch = 0; ch < cut.chunks(); ch++) {
+        if (ch + 1 < cut.chunks() && (rc = d2h(ch + 1)) != CRYO_OK) return rc; /* its buffer was scattered in the previous turn */
+        if ((rc = landed(ch)) != CRYO_OK) return rc;
+    }
+    return CRYO_OK;
+}
+/* decoded blocks, block_size apart from `from` (pinned memory, or the device: then the copies are queued on the codec stream), to
+ * one destination each: a block that failed leaves its destination untouched, an OK block without one is the caller's error */
+static int hand_back(cryo_codec *c, const int32_t *status, void *const *dst, const uint8_t *from, bool from_device, size_t n, size_t block_size)
+{
+    std::vector<CopyJob> jobs;
+    for (size_t i = 0; i < n; i++) {
+        if (status[i] != CRYO_OK) continue;
+        if (!dst[i]) return CRYO_E_ARG;
+        if (from_device) HIP_TRY(c, hipMemcpyAsync(dst[i], from + i * block_size, block_size, hipMemcpyDeviceToHost, c->stream));
+        else jobs.push_back({dst[i], from + i * block_size, block_size});
+    }
+    parallel_copy(c, jobs);
+    return CRYO_OK;
+}
 
-/* K blocks from / to host memory.  Device buffers and the pinned staging buffer live in the handle
- * (grow-only); transfers are bulk: one H2D of the K blocks, one D2H of the K output slots. */
-static int compress_blocks_body(cryo_codec *c, int method, int param, const void *h_src, size_t block_size,
-                                size_t n, void *h_dst, size_t dst_stride, uint32_t *h_out_size)
+/* ---- compress: K blocks from / to host memory ---- */
+/* the host blocks of a compress call: contiguous (block i at src + i * block_size, its slot at dst + i * dst_stride), or -- a
+ * multi-GPU share, where a handle's blocks are every G-th of the call -- one pointer per block */
+struct CompressIo {
+    const uint8_t *src; uint8_t *dst; size_t dst_stride;
+    const void *const *src_each; void *const *dst_each;
+    bool contiguous() const { return !src_each; }
+    void *out(size_t i) const { return dst_each ? dst_each[i] : dst + i * dst_stride; }
+};
+
+static int compress_blocks_piped(cryo_codec *c, int method, int param, const CompressIo &io, size_t block_size, size_t n, uint32_t *h_out_size)
+{
+    const size_t bound = cryo_codec_bound(method, block_size);
+    const size_t dstride = (bound + 15) & ~(size_t)15;
+    const cryo::ChunkCut cut(n, block_size);
+    int rc;
+    if ((rc = ensure_pipe_streams(c)) != CRYO_OK) return rc;
+    if ((rc = ensure(c, &c->hb_src, &c->hb_src_cap, n * block_size + 64)) != CRYO_OK) return rc;
+    if ((rc = ensure(c, &c->hb_dst, &c->hb_dst_cap, n * dstride + 64)) != CRYO_OK) return rc;
+    if ((rc = ensure(c, &c->hb_meta, &c->hb_meta_cap, n * 16 + 64)) != CRYO_OK) return rc;
+    if ((rc = ensure_pinned(c, n * 8 + 64)) != CRYO_OK) return rc;
+    for (int b = 0; b < 2; b++) {
+        if ((rc = ensure_pipe(c, b, cut.K * block_size)) != CRYO_OK) return rc;
+        if ((rc = ensure_pipe(c, 2 + b, cut.K * dstride)) != CRYO_OK) return rc;
+    }
+    uint32_t *d_sz = (uint32_t *)c->hb_meta;
+    int32_t *d_st = (int32_t *)(c->hb_meta + ((n * 4 + 15) & ~(size_t)15));
+    uint32_t *p_sz = (uint32_t *)c->pin;
+    int32_t *p_st = (int32_t *)((uint8_t *)c->pin + n * 4);
+    for (size_t ch = 0; ch < cut.chunks(); ch++) {
+        const size_t lo = cut.lo(ch), cnt = cut.cnt(ch);
+        uint8_t *buf = (uint8_t *)c->pipe_pin[ch & 1];
+        if (ch >= 2) HIP_TRY(c, hipEventSynchronize(c->ev_in[ch & 1])); /* the staging buffer has left for the device */
+        std::vector<CopyJob> jobs;
+        if (io.contiguous()) jobs.push_back({buf, io.src + lo * block_size, cnt * block_size});
+        else for (size_t i = 0; i < cnt; i++) jobs.push_back({buf + i * block_size, io.src_each[lo + i], block_size});
+        parallel_copy(c, jobs); /* the host gather of chunk c+1 overlaps the H2D of chunk c */
+        HIP_TRY(c, hipMemcpyAsync(c->hb_src + lo * block_size, buf, cnt * block_size, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipEventRecord(c->ev_in[ch & 1], c->stream));
+    }
+    rc = cryo_codec_compress_batch(c, method, param, c->hb_src, block_size, (uint32_t)block_size, n, c->hb_dst, dstride, d_sz, d_st);
+    if (rc != CRYO_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
+    HIP_TRY(c, hipMemcpyAsync(p_sz, d_sz, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(p_st, d_st, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if ((rc = take_encoded(c, p_st, p_sz, n, bound, h_out_size)) != CRYO_OK) return rc;
+    /* out: only the bytes the blocks occupy travel */
+    return pipe_return(c, cut, c->hb_dst, dstride, [&](size_t ch) { return (cut.cnt(ch) - 1) * dstride + p_sz[cut.hi(ch) - 1]; },
+        [&](size_t ch) -> int {
+            HIP_TRY(c, hipEventSynchronize(c->ev_out[ch & 1]));
+            const uint8_t *po = (const uint8_t *)c->pipe_pin[2 + (ch & 1)];
+            std::vector<CopyJob> jobs;
+            for (size_t i = cut.lo(ch); i < cut.hi(ch); i++) jobs.push_back({io.out(i), po + (i - cut.lo(ch)) * dstride, p_sz[i]});
+            parallel_copy(c, jobs);
+            return (int)CRYO_OK;
+        });
+}
+
+/* Device buffers and the pinned staging buffer live in the handle (grow-only).  A large call takes the pipeline; else contiguous
+ * blocks go up straight from the caller's memory, and blocks given by pointer go through the pinned buffer both ways, on the
+ * worker threads.  The caller has checked the arguments */
+static int compress_blocks_host(cryo_codec *c, int method, int param, const CompressIo &io, size_t block_size, size_t n, uint32_t *h_out_size)
 {
     DevGuard dev_(c);
-    if (!c || !method_ok(method) || !block_size_ok(block_size)) return CRYO_E_ARG;
     if (n == 0) return CRYO_OK;
-    if (!h_src || !h_dst || !h_out_size) return CRYO_E_ARG;
     const size_t bound = cryo_codec_bound(method, block_size);
-    if (dst_stride < bound) return CRYO_E_DSTSIZE;
     ScopedLocalCpus numa_(c, n, block_size); /* the caller's share of the copies next to the GPU */
     c->vfy_failed = false;
-    if (pipe_worth_it(c, n, block_size)) {
-        const int rc = compress_blocks_piped(c, method, param, (const uint8_t *)h_src, nullptr, block_size, n, (uint8_t *)h_dst, nullptr, dst_stride, h_out_size);
-        if (rc != CRYO_OK) { (void)hipStreamSynchronize(c->stream); if (c->xfer) (void)hipStreamSynchronize(c->xfer); }
-        pipe_trim(c);
-        return rc;
-    }
-    /* the device slots use the caller's stride, so the output goes back in one copy (a slot may be
-     * written beyond out_size[i], up to bound) */
-    const bool bulk = dst_stride <= bound + 4096;
-    const size_t dstride = bulk ? dst_stride : ((bound + 15) & ~(size_t)15);
+    if (pipe_worth_it(c, n, block_size))
+        return piped(c, [&] { return compress_blocks_piped(c, method, param, io, block_size, n, h_out_size); });
+    /* bulk: the device slots use the caller's stride, so the output goes back in one copy (a slot may be written beyond
+     * out_size[i], up to bound) */
+    const bool bulk = io.contiguous() && io.dst_stride <= bound + 4096;
+    const size_t dstride = bulk ? io.dst_stride : ((bound + 15) & ~(size_t)15);
     int rc;
     if ((rc = ensure(c, &c->hb_src, &c->hb_src_cap, n * block_size + 64)) != CRYO_OK) return rc;
     if ((rc = ensure(c, &c->hb_dst, &c->hb_dst_cap, n * dstride + 64)) != CRYO_OK) return rc;
     if ((rc = ensure(c, &c->hb_meta, &c->hb_meta_cap, n * 16 + 64)) != CRYO_OK) return rc;
     uint32_t *d_sz = (uint32_t *)c->hb_meta;
     int32_t *d_st = (int32_t *)(c->hb_meta + ((n * 4 + 15) & ~(size_t)15));
-    if ((rc = ensure_pinned(c, n * 4)) != CRYO_OK) return rc;
-    int32_t *h_st = (int32_t *)c->pin;
-    HIP_TRY(c, hipMemcpyAsync(c->hb_src, h_src, n * block_size, hipMemcpyHostToDevice, c->stream));
+    /* pinned: the statuses; by pointer the blocks of both directions before them (dstride >= block_size) and the sizes behind */
+    if ((rc = ensure_pinned(c, io.contiguous() ? n * 4 : n * dstride + n * 8 + 64)) != CRYO_OK) return rc;
+    uint8_t *pin = (uint8_t *)c->pin;
+    int32_t *h_st = (int32_t *)(io.contiguous() ? pin : pin + n * dstride);
+    uint32_t *h_sz = io.contiguous() ? h_out_size : (uint32_t *)(pin + n * dstride + n * 4);
+    if (!io.contiguous()) {
+        std::vector<CopyJob> jobs;
+        for (size_t i = 0; i < n; i++) jobs.push_back({pin + i * block_size, io.src_each[i], block_size});
+        parallel_copy(c, jobs);
+    }
+    HIP_TRY(c, hipMemcpyAsync(c->hb_src, io.contiguous() ? io.src : pin, n * block_size, hipMemcpyHostToDevice, c->stream));
     rc = cryo_codec_compress_batch(c, method, param, c->hb_src, block_size, (uint32_t)block_size, n, c->hb_dst, dstride, d_sz, d_st);
     if (rc != CRYO_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
-    HIP_TRY(c, hipMemcpyAsync(h_out_size, d_sz, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(h_sz, d_sz, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(h_st, d_st, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    if (bulk) HIP_TRY(c, hipMemcpyAsync(h_dst, c->hb_dst, (n - 1) * dstride + bound, hipMemcpyDeviceToHost, c->stream));
+    if (bulk) HIP_TRY(c, hipMemcpyAsync(io.dst, c->hb_dst, (n - 1) * dstride + bound, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (size_t i = 0; i < n; i++) {
-        if (h_st[i] == CRYO_E_VERIFY) return verify_failure(c, i);
-        if (h_st[i] != CRYO_OK) return h_st[i];
-        if (h_out_size[i] == 0 || h_out_size[i] > bound) return CRYO_E_HIP;
-    }
-    if (!bulk) {
+    if ((rc = take_encoded(c, h_st, h_sz, n, bound, h_out_size)) != CRYO_OK) return rc;
+    if (bulk) return CRYO_OK;
+    if (io.contiguous()) {
         for (size_t i = 0; i < n; i++)
-            HIP_TRY(c, hipMemcpyAsync((uint8_t *)h_dst + i * dst_stride, c->hb_dst + i * dstride, h_out_size[i], hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(io.out(i), c->hb_dst + i * dstride, h_out_size[i], hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return CRYO_OK;
     }
+    /* the compressed blocks come back in ONE copy into the pinned buffer (its input side is no longer needed) and go to
+     * their destinations from there on the worker threads; round 3 copied block by block into pageable memory */
+    HIP_TRY(c, hipMemcpyAsync(pin, c->hb_dst, (n - 1) * dstride + h_out_size[n - 1], hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    std::vector<CopyJob> jobs;
+    for (size_t i = 0; i < n; i++) jobs.push_back({io.out(i), pin + i * dstride, h_out_size[i]});
+    parallel_copy(c, jobs);
     return CRYO_OK;
 }
+
+/* ---- decompress and check: streams given by pointer, staged for the device ---- */
+/* a stream with bytes needs a place to read them from */
+static bool streams_ok(const void *const *h_src, const uint32_t *h_src_size, size_t n)
+{
+    for (size_t i = 0; i < n; i++) if (h_src_size[i] != 0 && !h_src[i]) return false;
+    return true;
+}
+/* the whole of layout L (host_stage.h) written at `at`: the two tables, and stream k's bytes from src_of(k).  spread: the copies go
+ * over the staging workers */
+template <class SrcOf, class SizeOf> static void write_staged(cryo_codec *c, const cryo::StreamLayout &L, uint8_t *at, SrcOf src_of, SizeOf size_of, bool spread)
+{
+    L.fill_tables(at, size_of);
+    std::vector<CopyJob> jobs;
+    for (size_t k = 0; k < L.m; k++) {
+        if (!size_of(k)) continue;
+        if (spread) jobs.push_back({at + L.offset(k), src_of(k), size_of(k)});
+        else memcpy(at + L.offset(k), src_of(k), size_of(k));
+    }
+    parallel_copy(c, jobs);
+}
+/* the one-shot staging of n streams given by pointer: the layout of host_stage.h built in the pinned buffer and sent to c->hb_src
+ * in one copy (counted in h2d_bytes); the device tables are at o_off and o_sz of c->hb_src.
+ * tail_bytes: room the caller wants in the pinned buffer behind the streams, at o_tail (16-byte aligned), for a table of its own
+ * that it fills and uploads in a second copy; the pinned buffer gets its final size here, before anything is queued, so it stays
+ * where it is.
+ * spread: the host copies go over the staging workers (recompression, whose large calls come through here too; a large
+ * decompress or check call takes the pipelined staging instead) */
+struct StagedStreams { size_t o_off = 0, o_sz = 0, o_data = 0, total = 0, o_tail = 0; };
+static int stage_streams(cryo_codec *c, const void *const *h_src, const uint32_t *h_src_size, size_t n, StagedStreams &sg, bool spread = false, size_t tail_bytes = 0)
+{
+    if (!streams_ok(h_src, h_src_size, n)) return CRYO_E_ARG;
+    const auto size_of = [&](size_t i) { return h_src_size[i]; };
+    const cryo::StreamLayout L(n, size_of);
+    sg = {L.o_off, L.o_sz, L.o_data, L.total, (L.bytes() + 64 + 15) & ~(size_t)15}; /* o_tail = bytes + 64: both are multiples of 16 */
+    int rc;
+    if ((rc = ensure_pinned(c, sg.o_tail + tail_bytes)) != CRYO_OK) return rc;
+    if ((rc = ensure(c, &c->hb_src, &c->hb_src_cap, L.bytes() + 64)) != CRYO_OK) return rc;
+    write_staged(c, L, (uint8_t *)c->pin, [&](size_t i) { return h_src[i]; }, size_of, spread);
+    HIP_TRY(c, hipMemcpyAsync(c->hb_src, c->pin, L.bytes(), hipMemcpyHostToDevice, c->stream));
+    c->xfer_ctr.h2d_bytes += L.bytes();
+    return CRYO_OK;
+}
+
+/* Decode or check: what a staged call runs on the blocks lo .. lo+cnt of the device tables, and what comes back.  The staging
+ * (staged_piped, staged_blocks) takes both from one of these two and asks no further.  p_st: the pipelined call's room for n
+ * statuses in the pinned buffer */
+struct CheckOp { /* only the results come back: no decoded blocks, no statuses */
+    cryo_codec *c; int method; size_t block_size, n; cryo_check_result *h_result;
+    cryo_check_result *d_res() const { return (cryo_check_result *)c->hb_meta; }
+    size_t out_block() const { return 0; } /* the bytes per block that are decoded to come back: the staging reserves their room */
+    size_t back_bytes() const { return n * sizeof(cryo_check_result); } /* what the call adds to d2h_bytes */
+    /* the kernels over blocks lo .. lo+cnt, on the codec stream */
+    int run(const uint64_t *d_off, const uint32_t *d_sz, size_t lo, size_t cnt)
+    {
+        const int rc = check_pass(c, method, c->hb_src, d_off + lo, d_sz + lo, (uint32_t)block_size, cnt, d_res() + lo);
+        if (rc != CRYO_OK) (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    /* pipelined, kernels per chunk: chunk ch's uploads are queued */
+    int run_chunk(const uint64_t *d_off, const uint32_t *d_sz, const cryo::ChunkCut &cut, size_t ch, int32_t *) { return run(d_off, d_sz, cut.lo(ch), cut.cnt(ch)); }
+    /* every launch is queued: of the pipelined call, of the one-shot call */
+    int finish_piped(const cryo::ChunkCut &, bool, int32_t *) { return finish(); }
+    int finish()
+    {
+        HIP_TRY(c, hipMemcpyAsync(h_result, d_res(), n * sizeof(cryo_check_result), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return CRYO_OK;
+    }
+};
+/* h_dst: one contiguous K-block buffer; or one destination per block in h_dst_each (the cache's slots, a multi-GPU share): then a
+ * block that failed leaves its destination untouched -- the statuses of a chunk travel with its blocks */
+struct DecodeOp {
+    cryo_codec *c; int method; size_t block_size, n;
+    uint8_t *h_dst; void *const *h_dst_each; int32_t *h_status;
+    int32_t *d_st() const { return (int32_t *)c->hb_meta; }
+    size_t out_block() const { return block_size; }
+    size_t back_bytes() const { return n * block_size + n * sizeof(int32_t); }
+    int run(const uint64_t *d_off, const uint32_t *d_sz, size_t lo, size_t cnt)
+    {
+        const int rc = cryo_codec_decompress_batch(c, method, c->hb_src, d_off + lo, d_sz + lo, c->hb_dst + lo * block_size, block_size, (uint32_t)block_size, cnt, d_st() + lo);
+        if (rc != CRYO_OK) (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    /* chunk ch, once it lies in its pinned buffer, to the caller */
+    int landed(const cryo::ChunkCut &cut, size_t ch, const int32_t *p_st)
+    {
+        const size_t lo = cut.lo(ch), cnt = cut.cnt(ch);
+        const uint8_t *from = (const uint8_t *)c->pipe_pin[2 + (ch & 1)];
+        HIP_TRY(c, hipEventSynchronize(c->ev_out[ch & 1]));
+        if (!h_dst) return hand_back(c, p_st + lo, h_dst_each + lo, from, false, cnt, block_size);
+        parallel_copy(c, {{h_dst + lo * block_size, from, cnt * block_size}});
+        return CRYO_OK;
+    }
+    /* chunk ch leaves on the transfer stream behind its kernel, into the buffer that chunk ch-2 has been scattered from */
+    int run_chunk(const uint64_t *d_off, const uint32_t *d_sz, const cryo::ChunkCut &cut, size_t ch, int32_t *p_st)
+    {
+        const size_t lo = cut.lo(ch), cnt = cut.cnt(ch);
+        const int b = (int)(ch & 1);
+        int rc = run(d_off, d_sz, lo, cnt);
+        if (rc != CRYO_OK) { (void)hipStreamSynchronize(c->xfer); return rc; }
+        HIP_TRY(c, hipEventRecord(c->ev_k[b], c->stream));
+        if (ch >= 2 && (rc = landed(cut, ch - 2, p_st)) != CRYO_OK) return rc; /* frees output buffer b */
+        HIP_TRY(c, hipStreamWaitEvent(c->xfer, c->ev_k[b], 0));
+        HIP_TRY(c, hipMemcpyAsync(c->pipe_pin[2 + b], c->hb_dst + lo * block_size, cnt * block_size, hipMemcpyDeviceToHost, c->xfer));
+        if (!h_dst) HIP_TRY(c, hipMemcpyAsync(p_st + lo, d_st() + lo, cnt * 4, hipMemcpyDeviceToHost, c->xfer)); /* the scatter skips failed blocks */
+        HIP_TRY(c, hipEventRecord(c->ev_out[b], c->xfer));
+        return CRYO_OK;
+    }
+    int finish_piped(const cryo::ChunkCut &cut, bool per_chunk, int32_t *p_st)
+    {
+        int rc = CRYO_OK;
+        if (per_chunk) {
+            for (size_t ch = cut.chunks() >= 2 ? cut.chunks() - 2 : 0; ch < cut.chunks() && rc == CRYO_OK; ch++) rc = landed(cut, ch, p_st);
+        } else {
+            HIP_TRY(c, hipEventRecord(c->ev_k[0], c->stream));
+            HIP_TRY(c, hipStreamWaitEvent(c->xfer, c->ev_k[0], 0));
+            if (!h_dst) HIP_TRY(c, hipMemcpyAsync(p_st, d_st(), n * 4, hipMemcpyDeviceToHost, c->xfer)); /* before the first chunk's event */
+            rc = pipe_return(c, cut, c->hb_dst, block_size, [&](size_t ch) { return cut.cnt(ch) * block_size; },
+                             [&](size_t ch) { return landed(cut, ch, p_st); });
+        }
+        if (rc != CRYO_OK) return rc;
+        /* the scatters read p_st on the host (which blocks failed): the whole-call status copy goes out behind them, not under them */
+        HIP_TRY(c, hipMemcpyAsync(p_st, d_st(), n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        memcpy(h_status, p_st, n * 4);
+        return CRYO_OK;
+    }
+    /* one destination per block: the blocks come back in ONE copy into the pinned buffer (the compressed side of it is no longer
+     * needed) and are handed to their destinations from there; without the room for that, block by block from the device */
+    int finish()
+    {
+        HIP_TRY(c, hipMemcpyAsync(h_status, d_st(), n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        const bool by_pin = !h_dst && ensure_pinned(c, n * block_size) == CRYO_OK;
+        if (h_dst || by_pin) HIP_TRY(c, hipMemcpyAsync(h_dst ? h_dst : c->pin, c->hb_dst, n * block_size, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (h_dst) return CRYO_OK;
+        const int rc = hand_back(c, h_status, h_dst_each, by_pin ? (const uint8_t *)c->pin : c->hb_dst, !by_pin, n, block_size);
+        if (rc != CRYO_OK || by_pin) return rc;
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return CRYO_OK;
+    }
+};
+
+/* the pipelined staging: the tables go up first, the streams chunk by chunk through the two pinned input buffers (host gather of
+ * chunk c+1 under the H2D of chunk c), the kernels per chunk or once over the whole call (host_stage.h) */
+template <class Op> static int staged_piped(cryo_codec *c, int method, const void *const *h_src, const uint32_t *h_src_size, size_t n, size_t block_size, Op &op)
+{
+    if (!streams_ok(h_src, h_src_size, n)) return CRYO_E_ARG;
+    const cryo::ChunkCut cut(n, block_size);
+    const bool per_chunk = cryo::kernel_per_chunk(cut.K, method == CRYO_METHOD_LZ4, false);
+    const auto size_of = [&](size_t i) { return h_src_size[i]; };
+    const cryo::StreamLayout L(n, size_of);
+    int rc;
+    if ((rc = ensure_pipe_streams(c)) != CRYO_OK) return rc;
+    if ((rc = ensure_pinned(c, L.o_data + n * 4 + 64)) != CRYO_OK) return rc;
+    if ((rc = ensure(c, &c->hb_src, &c->hb_src_cap, L.bytes() + 64)) != CRYO_OK) return rc;
+    if (op.out_block() && (rc = ensure(c, &c->hb_dst, &c->hb_dst_cap, n * op.out_block() + 64)) != CRYO_OK) return rc;
+    if ((rc = ensure(c, &c->hb_meta, &c->hb_meta_cap, n * 16 + 64)) != CRYO_OK) return rc;
+    const size_t max_chunk_in = L.max_chunk_in(cut);
+    for (int b = 0; b < 2; b++) {
+        if ((rc = ensure_pipe(c, b, max_chunk_in + 64)) != CRYO_OK) return rc;
+        if (op.out_block() && (rc = ensure_pipe(c, 2 + b, cut.K * op.out_block())) != CRYO_OK) return rc;
+    }
+    uint8_t *pin = (uint8_t *)c->pin;
+    int32_t *p_st = (int32_t *)(pin + L.o_data);
+    L.fill_tables(pin, size_of);
+    HIP_TRY(c, hipMemcpyAsync(c->hb_src, pin, L.o_data, hipMemcpyHostToDevice, c->stream));
+    c->xfer_ctr.h2d_bytes += L.bytes();
+    c->xfer_ctr.d2h_bytes += op.back_bytes();
+    const uint64_t *d_off = (const uint64_t *)(c->hb_src + L.o_off);
+    const uint32_t *d_sz = (const uint32_t *)(c->hb_src + L.o_sz);
+    for (size_t ch = 0; ch < cut.chunks(); ch++) {
+        const size_t lo = cut.lo(ch), hi = cut.hi(ch);
+        const int b = (int)(ch & 1);
+        if (ch >= 2) HIP_TRY(c, hipEventSynchronize(c->ev_in[b]));
+        std::vector<CopyJob> jobs;
+        for (size_t i = lo; i < hi; i++)
+            if (h_src_size[i]) jobs.push_back({(uint8_t *)c->pipe_pin[b] + L.span(lo, i), h_src[i], h_src_size[i]});
+        parallel_copy(c, jobs);
+        if (L.span(lo, hi)) HIP_TRY(c, hipMemcpyAsync(c->hb_src + L.offset(lo), c->pipe_pin[b], L.span(lo, hi), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipEventRecord(c->ev_in[b], c->stream));
+        if (per_chunk && (rc = op.run_chunk(d_off, d_sz, cut, ch, p_st)) != CRYO_OK) return rc;
+    }
+    if (!per_chunk && (rc = op.run(d_off, d_sz, 0, n)) != CRYO_OK) return rc;
+    return op.finish_piped(cut, per_chunk, p_st);
+}
+
+/* n streams given by pointer through op: pipelined when the call is large, else staged, uploaded and run in one piece.  The caller
+ * has checked the arguments */
+template <class Op> static int staged_blocks(cryo_codec *c, int method, const void *const *h_src, const uint32_t *h_src_size, size_t n, size_t block_size, Op op)
+{
+    DevGuard dev_(c);
+    ScopedLocalCpus numa_(c, n, block_size);
+    if (pipe_worth_it(c, n, block_size))
+        return piped(c, [&] { return staged_piped(c, method, h_src, h_src_size, n, block_size, op); });
+    StagedStreams sg;
+    int rc;
+    /* every allocation of the call before the upload is queued and counted */
+    if (op.out_block() && (rc = ensure(c, &c->hb_dst, &c->hb_dst_cap, n * op.out_block() + 64)) != CRYO_OK) return rc;
+    if ((rc = ensure(c, &c->hb_meta, &c->hb_meta_cap, n * 16 + 64)) != CRYO_OK) return rc;
+    if ((rc = stage_streams(c, h_src, h_src_size, n, sg)) != CRYO_OK) return rc;
+    c->xfer_ctr.d2h_bytes += op.back_bytes();
+    if ((rc = op.run((const uint64_t *)(c->hb_src + sg.o_off), (const uint32_t *)(c->hb_src + sg.o_sz), 0, n)) != CRYO_OK) return rc;
+    return op.finish();
+}
+
+static int decompress_blocks_host(cryo_codec *c, int method, const void *const *h_src, const uint32_t *h_src_size, size_t n,
+                                  void *h_dst, void *const *h_dst_each, size_t block_size, int32_t *h_status)
+{
+    if (!c || !method_ok(method) || !block_size_ok(block_size)) return CRYO_E_ARG;
+    if (n == 0) return CRYO_OK;
+    if (!h_src || !h_src_size || (!h_dst && !h_dst_each) || !h_status) return CRYO_E_ARG;
+    return staged_blocks(c, method, h_src, h_src_size, n, block_size, DecodeOp{c, method, block_size, n, (uint8_t *)h_dst, h_dst_each, h_status});
+}
+
+extern "C" {
 
 int cryo_codec_compress_blocks(cryo_codec *c, int method, int param, const void *h_src, size_t block_size,
                                size_t n, void *h_dst, size_t dst_stride, uint32_t *h_out_size)
 {
-    return host_call(c, [&] {
-        return compress_blocks_body(c, method, param, h_src, block_size, n, h_dst, dst_stride, h_out_size);
+    return host_call(c, [&]() -> int {
+        if (!c || !method_ok(method) || !block_size_ok(block_size)) return CRYO_E_ARG;
+        if (n == 0) return CRYO_OK;
+        if (!h_src || !h_dst || !h_out_size) return CRYO_E_ARG;
+        if (dst_stride < cryo_codec_bound(method, block_size)) return CRYO_E_DSTSIZE;
+        return compress_blocks_host(c, method, param, {(const uint8_t *)h_src, (uint8_t *)h_dst, dst_stride, nullptr, nullptr}, block_size, n, h_out_size);
     });
-}
-
-/* the one-shot staging of n streams given by pointer: [offsets u64 x n][sizes u32 x n][streams, 16-byte aligned] built in the
- * pinned buffer and sent to c->hb_src in one copy (counted in h2d_bytes); the device tables are at o_off and o_sz of c->hb_src.
- * tail_bytes: room the caller wants in the pinned buffer behind the streams, at o_tail (16-byte aligned), for a table of its own
- * that it fills and uploads in a second copy -- the layout is this function's alone, and the pinned buffer gets its final size
- * here, before anything is queued, so it stays where it is.
- * spread: the host copies go over the staging workers (recompression, whose large calls come through here too; a large
- * decompress or check call takes the pipelined staging instead) */
-struct StagedStreams { size_t o_off = 0, o_sz = 0, o_data = 0, total = 0, o_tail = 0; };
-static int stage_streams(cryo_codec *c, const void *const *h_src, const uint32_t *h_src_size, size_t n, StagedStreams &sg,
-                         bool spread = false, size_t tail_bytes = 0)
-{
-    sg.o_off = 0; sg.o_sz = n * 8; sg.o_data = (n * 12 + 63) & ~(size_t)63;
-    sg.total = 0;
-    for (size_t i = 0; i < n; i++) {
-        if (h_src_size[i] != 0 && !h_src[i]) return CRYO_E_ARG;
-        sg.total += ((size_t)h_src_size[i] + 15) & ~(size_t)15;
-    }
-    sg.o_tail = (sg.o_data + sg.total + 64 + 15) & ~(size_t)15; /* = o_data + total + 64: both are multiples of 16 */
-    int rc;
-    if ((rc = ensure_pinned(c, sg.o_tail + tail_bytes)) != CRYO_OK) return rc;
-    if ((rc = ensure(c, &c->hb_src, &c->hb_src_cap, sg.o_data + sg.total + 64)) != CRYO_OK) return rc;
-    uint8_t *pin = (uint8_t *)c->pin;
-    uint64_t *p_off = (uint64_t *)(pin + sg.o_off);
-    uint32_t *p_sz = (uint32_t *)(pin + sg.o_sz);
-    std::vector<CopyJob> jobs;
-    size_t pos = 0;
-    for (size_t i = 0; i < n; i++) {
-        p_off[i] = sg.o_data + pos;
-        p_sz[i] = h_src_size[i];
-        if (h_src_size[i] && spread) jobs.push_back({pin + sg.o_data + pos, h_src[i], h_src_size[i]});
-        else if (h_src_size[i]) memcpy(pin + sg.o_data + pos, h_src[i], h_src_size[i]);
-        pos += ((size_t)h_src_size[i] + 15) & ~(size_t)15;
-    }
-    parallel_copy(c, jobs);
-    HIP_TRY(c, hipMemcpyAsync(c->hb_src, pin, sg.o_data + sg.total, hipMemcpyHostToDevice, c->stream));
-    c->xfer_ctr.h2d_bytes += sg.o_data + sg.total;
-    return CRYO_OK;
-}
-
-/* h_result: the stored-block check of the staged streams instead of their decode; only the results come back */
-static int decompress_blocks_impl(cryo_codec *c, int method, const void *const *h_src, const uint32_t *h_src_size,
-                                  size_t n, void *h_dst, void *const *h_dst_each, size_t block_size, int32_t *h_status,
-                                  cryo_check_result *h_result = nullptr)
-{
-    DevGuard dev_(c);
-    const bool check = h_result != nullptr;
-    if (!c || !method_ok(method) || !block_size_ok(block_size)) return CRYO_E_ARG;
-    if (check && !check_block_size_ok(block_size)) return CRYO_E_ARG;
-    if (n == 0) return CRYO_OK;
-    if (!h_src || !h_src_size || (!check && ((!h_dst && !h_dst_each) || !h_status))) return CRYO_E_ARG;
-    ScopedLocalCpus numa_(c, n, block_size);
-    if (pipe_worth_it(c, n, block_size)) {
-        const int rc = decompress_blocks_piped(c, method, h_src, h_src_size, n, (uint8_t *)h_dst, h_dst_each, block_size, h_status, h_result);
-        /* an error return must not leave copies in flight into the handle's pinned buffers or the caller's memory */
-        if (rc != CRYO_OK) { (void)hipStreamSynchronize(c->stream); if (c->xfer) (void)hipStreamSynchronize(c->xfer); }
-        pipe_trim(c);
-        return rc;
-    }
-    /* pinned staging: [offsets u64 x n][sizes u32 x n][compressed blocks, 16-byte aligned], sent in one copy */
-    StagedStreams sg;
-    int rc;
-    /* every allocation of the call before the upload is queued and counted */
-    if (!check && (rc = ensure(c, &c->hb_dst, &c->hb_dst_cap, n * block_size + 64)) != CRYO_OK) return rc;
-    if ((rc = ensure(c, &c->hb_meta, &c->hb_meta_cap, n * 16 + 64)) != CRYO_OK) return rc;
-    if ((rc = stage_streams(c, h_src, h_src_size, n, sg)) != CRYO_OK) return rc;
-    const size_t o_off = sg.o_off, o_sz = sg.o_sz;
-    int32_t *d_st = (int32_t *)c->hb_meta;
-    if (check) {
-        c->xfer_ctr.d2h_bytes += n * sizeof(cryo_check_result);
-        cryo_check_result *d_res = (cryo_check_result *)c->hb_meta;
-        rc = check_pass(c, method, c->hb_src, (const uint64_t *)(c->hb_src + o_off), (const uint32_t *)(c->hb_src + o_sz),
-                        (uint32_t)block_size, n, d_res);
-        if (rc != CRYO_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
-        HIP_TRY(c, hipMemcpyAsync(h_result, d_res, n * sizeof *d_res, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        return CRYO_OK;
-    }
-    c->xfer_ctr.d2h_bytes += n * block_size + n * sizeof(int32_t);
-    rc = cryo_codec_decompress_batch(c, method, c->hb_src, (const uint64_t *)(c->hb_src + o_off), (const uint32_t *)(c->hb_src + o_sz),
-                                     c->hb_dst, block_size, (uint32_t)block_size, n, d_st);
-    if (rc != CRYO_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
-    HIP_TRY(c, hipMemcpyAsync(h_status, d_st, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    if (h_dst) {
-        HIP_TRY(c, hipMemcpyAsync(h_dst, c->hb_dst, n * block_size, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        return CRYO_OK;
-    }
-    /* one destination per block: the blocks come back in ONE copy into the pinned buffer (the compressed side of it
-     * is no longer needed) and are handed to their destinations from there; a block that failed leaves its destination
-     * untouched */
-    if (ensure_pinned(c, n * block_size) == CRYO_OK) {
-        HIP_TRY(c, hipMemcpyAsync(c->pin, c->hb_dst, n * block_size, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        std::vector<CopyJob> jobs;
-        for (size_t i = 0; i < n; i++) {
-            if (h_status[i] != CRYO_OK) continue;
-            if (!h_dst_each[i]) return CRYO_E_ARG;
-            jobs.push_back({h_dst_each[i], (const uint8_t *)c->pin + i * block_size, block_size});
-        }
-        parallel_copy(c, jobs);
-        return CRYO_OK;
-    }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (size_t i = 0; i < n; i++) {
-        if (h_status[i] != CRYO_OK) continue;
-        if (!h_dst_each[i]) return CRYO_E_ARG;
-        HIP_TRY(c, hipMemcpyAsync(h_dst_each[i], c->hb_dst + i * block_size, block_size, hipMemcpyDeviceToHost, c->stream));
-    }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return CRYO_OK;
 }
 
 int cryo_codec_decompress_blocks(cryo_codec *c, int method, const void *const *h_src, const uint32_t *h_src_size,
@@ -2524,7 +2524,7 @@ int cryo_codec_decompress_blocks(cryo_codec *c, int method, const void *const *h
 {
     if (!h_dst) return CRYO_E_ARG;
     return host_call(c, [&] {
-        return decompress_blocks_impl(c, method, h_src, h_src_size, n, h_dst, nullptr, block_size, h_status);
+        return decompress_blocks_host(c, method, h_src, h_src_size, n, h_dst, nullptr, block_size, h_status);
     });
 }
 
@@ -2533,7 +2533,7 @@ int cryo_codec_decompress_blocks_to(cryo_codec *c, int method, const void *const
 {
     if (!h_dst) return CRYO_E_ARG;
     return host_call(c, [&] {
-        return decompress_blocks_impl(c, method, h_src, h_src_size, n, nullptr, h_dst, block_size, h_status);
+        return decompress_blocks_host(c, method, h_src, h_src_size, n, nullptr, h_dst, block_size, h_status);
     });
 }
 
@@ -2543,9 +2543,7 @@ int cryo_codec_check_blocks(cryo_codec *c, int method, const void *const *h_src,
     if (!c || !method_ok(method) || !check_block_size_ok(block_size)) return CRYO_E_ARG;
     if (n == 0) return CRYO_OK;
     if (!h_src || !h_src_size || !h_result) return CRYO_E_ARG;
-    return host_call(c, [&] {
-        return decompress_blocks_impl(c, method, h_src, h_src_size, n, nullptr, nullptr, block_size, nullptr, h_result);
-    });
+    return host_call(c, [&] { return staged_blocks(c, method, h_src, h_src_size, n, block_size, CheckOp{c, method, block_size, n, h_result}); });
 }
 
 /* recompression of n streams given by pointer: staged and uploaded as the stored-block check's (stage_streams), recoded chunk
@@ -3023,7 +3021,7 @@ static int decompress_blocks_keyed_impl(cryo_codec *c, int method, const uint64_
     if (!c || !method_ok(method) || !block_size_ok(block_size)) return CRYO_E_ARG;
     if (n == 0) return CRYO_OK;
     if (!keys || !h_src || !h_src_size || !h_dst || !h_status) return CRYO_E_ARG;
-    if (!pool_ready(c, block_size)) return decompress_blocks_impl(c, method, h_src, h_src_size, n, nullptr, h_dst, block_size, h_status);
+    if (!pool_ready(c, block_size)) return decompress_blocks_host(c, method, h_src, h_src_size, n, nullptr, h_dst, block_size, h_status);
     const uint32_t S = (uint32_t)c->pool_slots.size();
     /* who is in the pool already */
     std::vector<uint32_t> slot(n, 0xffffffffu), miss;
@@ -3067,26 +3065,17 @@ static int decompress_blocks_keyed_impl(cryo_codec *c, int method, const uint64_
     std::vector<int32_t> mst(miss.size(), 0);
     for (size_t lo = 0; lo < miss.size(); lo += S) {
         const size_t m = miss.size() - lo < S ? miss.size() - lo : S;
-        const size_t o_off = 0, o_sz = m * 8, o_data = (m * 12 + 63) & ~(size_t)63;
-        size_t total = 0;
-        for (size_t k = 0; k < m; k++) total += ((size_t)h_src_size[miss[lo + k]] + 15) & ~(size_t)15;
-        if ((rc = ensure(c, &c->hb_src, &c->hb_src_cap, o_data + total + 64)) != CRYO_OK) return rc;
+        /* the round's streams: the layout of host_stage.h over this part of the misses */
+        const auto size_of = [&](size_t k) { return h_src_size[miss[lo + k]]; };
+        const cryo::StreamLayout L(m, size_of);
+        if ((rc = ensure(c, &c->hb_src, &c->hb_src_cap, L.bytes() + 64)) != CRYO_OK) return rc;
         if ((rc = ensure(c, &c->hb_meta, &c->hb_meta_cap, m * 16 + 64)) != CRYO_OK) return rc;
         /* staging of the compressed side lives behind the output staging in the pinned buffer */
-        if (c->pin_cap < n * block_size + o_data + total + m * 4 + 128 && (rc = ensure_pinned(c, n * block_size + o_data + total + m * 4 + 128)) != CRYO_OK) return rc;
+        if (c->pin_cap < n * block_size + L.bytes() + m * 4 + 128 && (rc = ensure_pinned(c, n * block_size + L.bytes() + m * 4 + 128)) != CRYO_OK) return rc;
         uint8_t *pin = (uint8_t *)c->pin + n * block_size;
-        uint64_t *p_off = (uint64_t *)(pin + o_off);
-        uint32_t *p_sz = (uint32_t *)(pin + o_sz);
-        size_t pos = 0;
-        for (size_t k = 0; k < m; k++) {
-            const uint32_t i = miss[lo + k];
-            p_off[k] = o_data + pos;
-            p_sz[k] = h_src_size[i];
-            if (h_src_size[i]) memcpy(pin + o_data + pos, h_src[i], h_src_size[i]);
-            pos += ((size_t)h_src_size[i] + 15) & ~(size_t)15;
-        }
-        HIP_TRY(c, hipMemcpyAsync(c->hb_src, pin, o_data + total, hipMemcpyHostToDevice, c->stream));
-        c->xfer_ctr.h2d_bytes += o_data + total;
+        write_staged(c, L, pin, [&](size_t k) { return h_src[miss[lo + k]]; }, size_of, false);
+        HIP_TRY(c, hipMemcpyAsync(c->hb_src, pin, L.bytes(), hipMemcpyHostToDevice, c->stream));
+        c->xfer_ctr.h2d_bytes += L.bytes();
         int32_t *d_st = (int32_t *)c->hb_meta;
         /* ring slots head .. head+m-1 (two launches when the ring wraps) */
         for (size_t done = 0; done < m;) {
@@ -3098,19 +3087,19 @@ static int decompress_blocks_keyed_impl(cryo_codec *c, int method, const uint64_
                 ps.valid = false;
                 slot[miss[lo + done + k]] = head + (uint32_t)k;
             }
-            rc = cryo_codec_decompress_batch(c, method, c->hb_src, (const uint64_t *)(c->hb_src + o_off) + done, (const uint32_t *)(c->hb_src + o_sz) + done,
+            rc = cryo_codec_decompress_batch(c, method, c->hb_src, (const uint64_t *)(c->hb_src + L.o_off) + done, (const uint32_t *)(c->hb_src + L.o_sz) + done,
                                              c->d_pool + (size_t)head * block_size, block_size, (uint32_t)block_size, run, d_st + done);
             if (rc != CRYO_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
             c->pool_head = (uint32_t)((head + run) % S);
             done += run;
         }
-        HIP_TRY(c, hipMemcpyAsync(pin + o_data + total, d_st, m * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(pin + L.bytes(), d_st, m * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
         {
             std::vector<uint32_t> who(miss.begin() + lo, miss.begin() + lo + m);
             if ((rc = gather(who)) != CRYO_OK) return rc;
         }
         HIP_TRY(c, hipStreamSynchronize(c->stream)); /* the statuses of this round, and the compressed staging is free again */
-        const int32_t *pst = (const int32_t *)(pin + o_data + total);
+        const int32_t *pst = (const int32_t *)(pin + L.bytes());
         for (size_t k = 0; k < m; k++) {
             const uint32_t i = miss[lo + k];
             h_status[i] = pst[k];
@@ -3126,11 +3115,7 @@ static int decompress_blocks_keyed_impl(cryo_codec *c, int method, const uint64_
     HIP_TRY(c, hipMemcpyAsync(c->pin, c->hb_dst, n * block_size, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->xfer_ctr.d2h_bytes += n * block_size;
-    std::vector<CopyJob> jobs;
-    for (size_t i = 0; i < n; i++)
-        if (h_status[i] == CRYO_OK) jobs.push_back({h_dst[i], (const uint8_t *)c->pin + i * block_size, block_size});
-    parallel_copy(c, jobs);
-    return CRYO_OK;
+    return hand_back(c, h_status, h_dst, (const uint8_t *)c->pin, false, n, block_size);
 }
 
 extern "C" {
@@ -3172,59 +3157,6 @@ struct cryo_multi {
     WorkerPool *pool = nullptr; /* one worker per further device */
     char err[320] = {0};
 };
-
-/* K blocks given by pointer, results to pointers: what one device's host thread runs for its share */
-static int compress_blocks_ptrs(cryo_codec *c, int method, int param, const void *const *h_src, size_t block_size, size_t n,
-                                void *const *h_dst, uint32_t *out_size)
-{
-    DevGuard dev_(c);
-    if (n == 0) return CRYO_OK;
-    const size_t bound = cryo_codec_bound(method, block_size);
-    const size_t dstride = (bound + 15) & ~(size_t)15;
-    ScopedLocalCpus numa_(c, n, block_size);
-    c->vfy_failed = false;
-    if (pipe_worth_it(c, n, block_size)) { /* the single-handle path's staging: pinned double buffers, second stream, worker threads */
-        const int rc = compress_blocks_piped(c, method, param, nullptr, h_src, block_size, n, nullptr, h_dst, dstride, out_size);
-        if (rc != CRYO_OK) { (void)hipStreamSynchronize(c->stream); if (c->xfer) (void)hipStreamSynchronize(c->xfer); }
-        pipe_trim(c);
-        return rc;
-    }
-    int rc;
-    if ((rc = ensure(c, &c->hb_src, &c->hb_src_cap, n * block_size + 64)) != CRYO_OK) return rc;
-    if ((rc = ensure(c, &c->hb_dst, &c->hb_dst_cap, n * dstride + 64)) != CRYO_OK) return rc;
-    if ((rc = ensure(c, &c->hb_meta, &c->hb_meta_cap, n * 16 + 64)) != CRYO_OK) return rc;
-    if ((rc = ensure_pinned(c, n * dstride + n * 8 + 64)) != CRYO_OK) return rc; /* dstride >= block_size: both directions fit */
-    uint8_t *pin = (uint8_t *)c->pin;
-    {
-        std::vector<CopyJob> jobs;
-        for (size_t i = 0; i < n; i++) jobs.push_back({pin + i * block_size, h_src[i], block_size});
-        parallel_copy(c, jobs);
-    }
-    uint32_t *d_sz = (uint32_t *)c->hb_meta;
-    int32_t *d_st = (int32_t *)(c->hb_meta + ((n * 4 + 15) & ~(size_t)15));
-    HIP_TRY(c, hipMemcpyAsync(c->hb_src, pin, n * block_size, hipMemcpyHostToDevice, c->stream));
-    rc = cryo_codec_compress_batch(c, method, param, c->hb_src, block_size, (uint32_t)block_size, n, c->hb_dst, dstride, d_sz, d_st);
-    if (rc != CRYO_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
-    int32_t *h_st = (int32_t *)(pin + n * dstride);
-    uint32_t *h_sz = (uint32_t *)(pin + n * dstride + n * 4);
-    HIP_TRY(c, hipMemcpyAsync(h_sz, d_sz, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(h_st, d_st, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (size_t i = 0; i < n; i++) {
-        if (h_st[i] == CRYO_E_VERIFY) return verify_failure(c, i);
-        if (h_st[i] != CRYO_OK) return h_st[i];
-        if (h_sz[i] == 0 || h_sz[i] > bound) return CRYO_E_HIP;
-        out_size[i] = h_sz[i];
-    }
-    /* the compressed blocks come back in ONE copy into the pinned buffer (its input side is no longer needed) and go to
-     * their destinations from there on the worker threads; round 3 copied block by block into pageable memory */
-    HIP_TRY(c, hipMemcpyAsync(pin, c->hb_dst, (n - 1) * dstride + out_size[n - 1], hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    std::vector<CopyJob> jobs;
-    for (size_t i = 0; i < n; i++) jobs.push_back({h_dst[i], pin + i * dstride, out_size[i]});
-    parallel_copy(c, jobs);
-    return CRYO_OK;
-}
 
 int cryo_multi_open(const int *devices, int n_devices, cryo_multi **out)
 {
@@ -3333,7 +3265,7 @@ int cryo_multi_compress_blocks(cryo_multi *m, int method, int param, const void 
             src[k] = (const uint8_t *)h_src + idx[k] * block_size;
             dst[k] = (uint8_t *)h_dst + idx[k] * dst_stride;
         }
-        const int rc = compress_blocks_ptrs(c, method, param, src.data(), block_size, idx.size(), dst.data(), sz.data());
+        const int rc = compress_blocks_host(c, method, param, {nullptr, nullptr, 0, src.data(), dst.data()}, block_size, idx.size(), sz.data());
         if (rc == CRYO_OK) cryo::scatter(idx, sz.data(), h_out_size);
         if (rc == CRYO_E_VERIFY && c->vfy_failed) set_verify_failure(c, idx[c->vfy_block], c->vfy_off); /* the index in the whole call */
         return rc;
@@ -3350,7 +3282,7 @@ static int multi_decompress(cryo_multi *m, int method, const void *const *h_src,
         std::vector<int32_t> st(idx.size());
         for (size_t k = 0; k < idx.size(); k++)
             dst[k] = h_dst_each ? h_dst_each[idx[k]] : (void *)((uint8_t *)h_dst + idx[k] * block_size);
-        const int rc = decompress_blocks_impl(c, method, in.src.data(), in.sz.data(), idx.size(), nullptr, dst.data(), block_size, st.data());
+        const int rc = decompress_blocks_host(c, method, in.src.data(), in.sz.data(), idx.size(), nullptr, dst.data(), block_size, st.data());
         if (rc == CRYO_OK) cryo::scatter(idx, st.data(), h_status);
         return rc;
     });
@@ -3383,7 +3315,7 @@ int cryo_multi_check_blocks(cryo_multi *m, int method, const void *const *h_src,
     return multi_run(m, n, [&](cryo_codec *c, size_t, const std::vector<size_t> &idx) {
         const ShareStreams in(h_src, h_src_size, idx);
         std::vector<cryo_check_result> res(idx.size());
-        const int rc = decompress_blocks_impl(c, method, in.src.data(), in.sz.data(), idx.size(), nullptr, nullptr, block_size, nullptr, res.data());
+        const int rc = staged_blocks(c, method, in.src.data(), in.sz.data(), idx.size(), block_size, CheckOp{c, method, block_size, idx.size(), res.data()});
         if (rc == CRYO_OK) cryo::scatter(idx, res.data(), h_result);
         return rc;
     });

@@ -253,7 +253,7 @@ def test_option_on_host_buffer_calls_and_multi(vc, oracle, method, param):
     assert all(np.array_equal(got[i], ref[i]) for i in range(160))
     assert vc.last_verify_failure() is None
     assert vc.counters()["blocks_decompressed"] == before
-    # cryo_multi over two handles of device 0 (compress_blocks_ptrs per handle)
+    # cryo_multi over two handles of device 0 (compress_blocks_host by pointer per handle)
     L = vc.L
     h = C.c_void_p()
     devs = (C.c_int * 2)(0, 0)
