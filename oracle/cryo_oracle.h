@@ -51,6 +51,35 @@ long cryo_oracle_zstd_decompress(const uint8_t *src, size_t csize, uint8_t *dst,
 /* returns frame size; every level -5…22 (all nine strategies, see zstd_enc_oracle.c; sources up to 1 MiB at the
  * optimal-parser levels), 0 if unsupported */
 size_t cryo_oracle_zstd_compress(const uint8_t *src, size_t n, uint8_t *dst, size_t cap, int level);
+/* the strategy (1 fast .. 9 btultra2) the encoder above takes for a source of n bytes at a level; 0 if unsupported */
+int cryo_oracle_zstd_enc_strategy(int level, size_t n);
+
+/* Branch counters of the encoder's entropy stage (literals, Huffman, sequence tables, sequence bitstream): how often each
+ * branch was taken since the last reset, over all blocks of all cryo_oracle_zstd_compress calls.  They show what no frame
+ * shows (the depth clip, the secondary normalisation, HUF_validateCTable, the thresholds) and change no byte of output.
+ * seq_bits_*: one sequence's bits in the stream (three state fields, three extra-bit fields) are more than 64, or with
+ * their bit offset in a 32-bit word more than 64 / 96: they spread over three / four words.
+ * The names are declared here, once: X(name) per counter, index = position in the list. */
+#define CRYO_ZSTD_ENC_TRACE(X)                                                                                          \
+    X(lit_disabled) X(lit_le63_raw) X(lit_rle) X(lit_flat_raw) X(lit_huf_raw) X(lit_mingain_raw) X(lit_compressed)      \
+    X(lit_treeless) X(lit_single_stream) X(lit_four_streams)                                                            \
+    X(huf_validate_fail) X(huf_prefer_repeat) X(huf_treeless_by_cost) X(huf_new_table_over_old) X(huf_hsz12_treeless)   \
+    X(huf_hsz12_raw) X(huf_undescribable) X(huf_weights_direct) X(huf_weights_fse) X(huf_weights_fse_above_128)          \
+    X(huf_streams_too_big)                                                                                              \
+    X(huf_clip) X(huf_clip_by_2_or_more) X(huf_clip_overshoot)                                                          \
+    X(seq_count_1byte) X(seq_count_2bytes) X(seq_count_3bytes)                                                          \
+    X(ll_basic) X(ll_rle) X(ll_compressed) X(ll_repeat) X(of_basic) X(of_rle) X(of_compressed) X(of_repeat)             \
+    X(ml_basic) X(ml_rle) X(ml_compressed) X(ml_repeat)                                                                 \
+    X(sel_one_code_basic) X(sel_one_code_rle) X(sel_below_dyn_min) X(sel_below_most) X(sel_threshold_compressed)        \
+    X(sel_cost_basic) X(sel_cost_repeat) X(sel_cost_compressed) X(sel_default_disallowed)                               \
+    X(tab_low_prob) X(tab_no_low_prob) X(tab_norm_m2) X(tab_norm_fail) X(tab_zero_run_3) X(tab_zero_run_24)             \
+    X(seq_long_ll) X(seq_long_ml) X(seq_bits_3_dwords) X(seq_bits_over_64) X(seq_bits_4_dwords) X(seq_over_cap)         \
+    X(seq_last_ncount_raw) X(block_mingain_raw) X(block_compressed)
+int cryo_oracle_zstd_enc_trace_count(void);
+const char *cryo_oracle_zstd_enc_trace_name(int i);    /* NULL outside 0 .. count - 1 */
+void cryo_oracle_zstd_enc_trace_reset(void);
+void cryo_oracle_zstd_enc_trace_from_block(int k);     /* count from a frame's block k on (0, the default: every block) */
+void cryo_oracle_zstd_enc_trace_get(uint64_t *out);    /* count values */
 
 #ifdef __cplusplus
 }

@@ -40,6 +40,27 @@
 #define HUF_LOG_DEFAULT 11
 
 static int hb(uint32_t v) { int r = 0; while (v >>= 1) r++; return r; }
+
+/* ------------------------------------------------------------ branch counters of the entropy stage (cryo_oracle.h) */
+#define X(name) T_##name,
+enum { CRYO_ZSTD_ENC_TRACE(X) T_COUNT };
+#undef X
+static uint64_t g_trace[T_COUNT];
+static int g_trace_from = 0; /* the first block of a frame that counts */
+static uint64_t g_trace_on = 1; /* 0 within the blocks in front of it */
+#define HIT(name) (g_trace[T_##name] += g_trace_on)
+static int g_trace_written = 0; /* 1 while a table description that goes into the block is made (not one that is only priced) */
+int cryo_oracle_zstd_enc_trace_count(void) { return T_COUNT; }
+const char *cryo_oracle_zstd_enc_trace_name(int i)
+{
+#define X(name) #name,
+    static const char *const names[] = {CRYO_ZSTD_ENC_TRACE(X)};
+#undef X
+    return i >= 0 && i < T_COUNT ? names[i] : NULL;
+}
+void cryo_oracle_zstd_enc_trace_reset(void) { memset(g_trace, 0, sizeof g_trace); }
+void cryo_oracle_zstd_enc_trace_from_block(int k) { g_trace_from = k; }
+void cryo_oracle_zstd_enc_trace_get(uint64_t *out) { memcpy(out, g_trace, sizeof g_trace); }
 static uint32_t rd32(const uint8_t *p) { uint32_t v; memcpy(&v, p, 4); return v; }
 static uint64_t rd64(const uint8_t *p) { uint64_t v; memcpy(&v, p, 8); return v; }
 
@@ -172,7 +193,10 @@ static int fse_normalize(int16_t *norm, int log, const uint32_t *count, size_t t
             still -= proba;
         }
     }
-    if (-still >= (norm[largest] >> 1)) { if (fse_norm_m2(norm, log, count, total, max_sym, low_prob)) return -1; }
+    if (-still >= (norm[largest] >> 1)) {
+        if (g_trace_written) HIT(tab_norm_m2);
+        if (fse_norm_m2(norm, log, count, total, max_sym, low_prob)) return -1;
+    }
     else norm[largest] += (int16_t)still;
     return log;
 }
@@ -192,6 +216,8 @@ static size_t fse_write_ncount(uint8_t *dst, const int16_t *norm, uint32_t max_s
             uint32_t start = sym;
             while (sym < alpha && !norm[sym]) sym++;
             if (sym == alpha) break;
+            if (g_trace_written && sym >= start + 24) HIT(tab_zero_run_24);
+            else if (g_trace_written && sym >= start + 3) HIT(tab_zero_run_3);
             while (sym >= start + 24) { start += 24; bw_add(&b, 0xFFFF, 16); }
             while (sym >= start + 3) { start += 3; bw_add(&b, 3, 2); }
             bw_add(&b, sym - start, 2);
@@ -292,6 +318,8 @@ static uint32_t huf_set_max_height(huf_node *node, uint32_t last, uint32_t max_n
     {
         int total = 0, n = (int)last;
         const uint32_t base = 1u << (largest - max_nb);
+        HIT(huf_clip);
+        if (largest - max_nb >= 2) HIT(huf_clip_by_2_or_more);
         while (node[n].nb > max_nb) { total += (int)(base - (1u << (largest - node[n].nb))); node[n].nb = (uint8_t)max_nb; n--; }
         while (node[n].nb == max_nb) n--;
         total >>= (largest - max_nb);
@@ -324,6 +352,7 @@ static uint32_t huf_set_max_height(huf_node *node, uint32_t last, uint32_t max_n
                     if (node[rank_last[dec]].nb != max_nb - dec) rank_last[dec] = none;
                 }
             }
+            if (total < 0) HIT(huf_clip_overshoot);
             while (total < 0) {
                 if (rank_last[1] == none) {
                     while (node[n].nb == max_nb) n--;
@@ -452,8 +481,9 @@ static size_t huf_write_table(uint8_t *dst, const huf_elt *tree, uint32_t max_sy
     for (n = 1; n < log + 1; n++) bits2w[n] = (uint8_t)(log + 1 - n);
     for (n = 0; n < max_sym; n++) w[n] = bits2w[tree[n].nb];
     hsz = huf_compress_weights(dst + 1, w, max_sym);
-    if (hsz > 1 && hsz < max_sym / 2) { dst[0] = (uint8_t)hsz; return hsz + 1; }
-    if (max_sym > 128) return 0; /* library returns an error: literals stay uncompressed */
+    if (hsz > 1 && hsz < max_sym / 2) { HIT(huf_weights_fse); if (max_sym > 128) HIT(huf_weights_fse_above_128); dst[0] = (uint8_t)hsz; return hsz + 1; }
+    if (max_sym > 128) { HIT(huf_undescribable); return 0; } /* library returns an error: literals stay uncompressed */
+    HIT(huf_weights_direct);
     dst[0] = (uint8_t)(128 + (max_sym - 1));
     w[max_sym] = 0;
     for (n = 0; n < max_sym; n += 2) dst[n / 2 + 1] = (uint8_t)((w[n] << 4) + w[n + 1]);
@@ -486,7 +516,7 @@ static size_t huf_encode_streams(uint8_t *dst, size_t hsz, const uint8_t *src, s
             total += (bits + 7) >> 3;
         }
         if (!single && n < 12) return 0;
-        if (total >= n - 1) return 0;
+        if (total >= n - 1) { HIT(huf_streams_too_big); return 0; }
     }
     if (single) {
         op += huf_encode_1x(dst + op, src, n, tree);
@@ -525,14 +555,14 @@ static size_t huf_compress(uint8_t *dst, const uint8_t *src, size_t n, int singl
     for (i = 0; i < n; i++) count[src[i]]++;
     while (!count[max_sym]) max_sym--;
     for (s = 0; s <= max_sym; s++) if (count[s] > largest) largest = count[s];
-    if (largest == n) { dst[0] = src[0]; return 1; }
-    if (largest <= (n >> 7) + 4) return 0;
+    if (largest == n) { HIT(lit_rle); dst[0] = src[0]; return 1; }
+    if (largest <= (n >> 7) + 4) { HIT(lit_flat_raw); return 0; }
     if (mode == 1) { /* HUF_validateCTable */
         int bad = 0;
         for (s = 0; s <= max_sym; s++) bad |= (count[s] != 0) & (st->tree[s].nb == 0);
-        if (bad) mode = 0;
+        if (bad) { HIT(huf_validate_fail); mode = 0; }
     }
-    if (prefer_repeat && mode != 0) { *reused = 1; return huf_encode_streams(dst, 0, src, n, st->tree, single); }
+    if (prefer_repeat && mode != 0) { HIT(huf_prefer_repeat); *reused = 1; return huf_encode_streams(dst, 0, src, n, st->tree, single); }
     log = (uint32_t)fse_optimal_log(HUF_LOG_DEFAULT, n, max_sym, 1);
     memset(tree, 0, sizeof tree);
     log = huf_build(tree, count, max_sym, log);
@@ -542,11 +572,13 @@ static size_t huf_compress(uint8_t *dst, const uint8_t *src, size_t n, int singl
         size_t old_bits = 0, new_bits = 0;
         for (s = 0; s <= max_sym; s++) { old_bits += (size_t)st->tree[s].nb * count[s]; new_bits += (size_t)tree[s].nb * count[s]; }
         if ((old_bits >> 3) <= hsz + (new_bits >> 3) || hsz + 12 >= n) {
+            if ((old_bits >> 3) <= hsz + (new_bits >> 3)) HIT(huf_treeless_by_cost); else HIT(huf_hsz12_treeless);
             *reused = 1;
             return huf_encode_streams(dst, 0, src, n, st->tree, single);
         }
     }
-    if (hsz + 12 >= n) return 0;
+    if (hsz + 12 >= n) { HIT(huf_hsz12_raw); return 0; }
+    if (mode != 0) HIT(huf_new_table_over_old);
     st->mode = 0; /* *repeat = HUF_repeat_none: the new table replaces the old one */
     memcpy(st->tree, tree, sizeof tree);
     return huf_encode_streams(dst, hsz, src, n, tree, single);
@@ -586,12 +618,18 @@ static size_t compress_literals(uint8_t *dst, const uint8_t *src, size_t n, cons
     size_t c;
     *next = *prev;
     /* ZSTD_disableLiteralsCompression: strategy fast with targetLength > 0 (negative levels) */
-    if (disable) return lit_raw(dst, src, n);
-    if (n <= 63) return lit_raw(dst, src, n);
+    if (disable) { HIT(lit_disabled); return lit_raw(dst, src, n); }
+    if (n <= 63) { HIT(lit_le63_raw); return lit_raw(dst, src, n); }
     c = huf_compress(dst + lh, src, n, single, next, g_strategy < 4 ? n <= 1024 : 0, &reused);
     if (reused) htype = 3;
-    if (c == 0 || c >= n - min_gain(n)) { *next = *prev; return lit_raw(dst, src, n); }
+    if (c == 0 || c >= n - min_gain(n)) {
+        if (c == 0) HIT(lit_huf_raw); else HIT(lit_mingain_raw);
+        *next = *prev;
+        return lit_raw(dst, src, n);
+    }
     if (c == 1) { *next = *prev; return lit_rle(dst, src, n); }
+    if (reused) HIT(lit_treeless); else HIT(lit_compressed);
+    if (single) HIT(lit_single_stream); else HIT(lit_four_streams);
     if (htype == 2) next->mode = 1; /* a freshly built table is "check" for the next block */
     if (lh == 3) {
         const uint32_t h = htype + ((uint32_t)(!single) << 2) + ((uint32_t)n << 4) + ((uint32_t)c << 14);
@@ -708,20 +746,32 @@ static size_t ncount_cost(const uint32_t *count, uint32_t max, size_t nseq, int 
 static int select_type(const uint32_t *count, uint32_t max, size_t most, size_t nseq, int fse_log, const fse_ct *prev, int *rep_mode,
                        const int16_t *def_norm, int def_log, int def_allowed)
 {
-    if (most == nseq) { *rep_mode = 0; return (def_allowed && nseq <= 2) ? SET_BASIC : SET_RLE; }
+    if (!def_allowed) HIT(sel_default_disallowed);
+    if (most == nseq) {
+        *rep_mode = 0;
+        if (def_allowed && nseq <= 2) { HIT(sel_one_code_basic); return SET_BASIC; }
+        HIT(sel_one_code_rle);
+        return SET_RLE;
+    }
     if (g_strategy < 4) {
         if (def_allowed) {
             const size_t mult = 10 - (size_t)g_strategy;
             const size_t dyn_min = (((size_t)1 << def_log) * mult) >> 3;
-            if (nseq < dyn_min || most < (nseq >> (def_log - 1))) { *rep_mode = 0; return SET_BASIC; }
+            if (nseq < dyn_min || most < (nseq >> (def_log - 1))) {
+                if (nseq < dyn_min) HIT(sel_below_dyn_min); else HIT(sel_below_most);
+                *rep_mode = 0;
+                return SET_BASIC;
+            }
         }
+        HIT(sel_threshold_compressed);
     } else {
         const size_t basic = def_allowed ? cross_entropy_cost(def_norm, (unsigned)def_log, count, max) : COST_ERR;
         const size_t repeat = *rep_mode != 0 ? fse_bit_cost(prev, count, max) : COST_ERR;
         const size_t nc = ncount_cost(count, max, nseq, fse_log);
         const size_t compressed = (nc << 3) + entropy_cost(count, max, nseq);
-        if (basic <= repeat && basic <= compressed) { *rep_mode = 0; return SET_BASIC; }
-        if (repeat <= compressed) return SET_REPEAT;
+        if (basic <= repeat && basic <= compressed) { HIT(sel_cost_basic); *rep_mode = 0; return SET_BASIC; }
+        if (repeat <= compressed) { HIT(sel_cost_repeat); return SET_REPEAT; }
+        HIT(sel_cost_compressed);
     }
     *rep_mode = 1;
     return SET_COMPRESSED;
@@ -739,8 +789,11 @@ static size_t build_ctable(uint8_t *dst, fse_ct *ct, int fse_log, int type, uint
         size_t n1 = nseq, sz;
         const int log = fse_optimal_log(fse_log, nseq, max, 2);
         if (count[codes[nseq - 1]] > 1) { count[codes[nseq - 1]]--; n1--; }
-        if (fse_normalize(norm, log, count, n1, max, n1 >= 2048) <= 0) return (size_t)-1;
+        if (n1 >= 2048) HIT(tab_low_prob); else HIT(tab_no_low_prob);
+        g_trace_written = 1;
+        if (fse_normalize(norm, log, count, n1, max, n1 >= 2048) <= 0) { g_trace_written = 0; HIT(tab_norm_fail); return (size_t)-1; }
         sz = fse_write_ncount(dst, norm, max, log);
+        g_trace_written = 0;
         if (!sz) return (size_t)-1;
         fse_build_ct(ct, norm, max, log);
         return sz;
@@ -765,6 +818,7 @@ static size_t compress_sequences(uint8_t *dst, const seq_t *seqs, size_t nseq, c
     int tll, tof, tml;
     *fnext = *fprev;
     op = compress_literals(dst, lits, nlit, hprev, hnext, disable_lit);
+    if (nseq < 128) HIT(seq_count_1byte); else if (nseq < 0x7F00) HIT(seq_count_2bytes); else HIT(seq_count_3bytes);
     if (nseq < 128) dst[op++] = (uint8_t)nseq;
     else if (nseq < 0x7F00) { dst[op] = (uint8_t)((nseq >> 8) + 0x80); dst[op + 1] = (uint8_t)nseq; op += 2; }
     else { dst[op] = 0xFF; dst[op + 1] = (uint8_t)(nseq - 0x7F00); dst[op + 2] = (uint8_t)((nseq - 0x7F00) >> 8); op += 3; }
@@ -775,8 +829,8 @@ static size_t compress_sequences(uint8_t *dst, const seq_t *seqs, size_t nseq, c
         ofc[i] = (uint8_t)hb(seqs[i].off);
         mlc[i] = (uint8_t)ml_code(seqs[i].ml);
     }
-    if (long_kind == 1) llc[long_pos] = MaxLL;
-    if (long_kind == 2) mlc[long_pos] = MaxML;
+    if (long_kind == 1) { HIT(seq_long_ll); llc[long_pos] = MaxLL; }
+    if (long_kind == 2) { HIT(seq_long_ml); mlc[long_pos] = MaxML; }
 #define HIST(codes, maxv)                                                                                 \
     do {                                                                                                  \
         memset(count, 0, sizeof count);                                                                   \
@@ -809,6 +863,9 @@ static size_t compress_sequences(uint8_t *dst, const seq_t *seqs, size_t nseq, c
     }
 #undef HIST
     *seq_head = (uint8_t)((tll << 6) + (tof << 4) + (tml << 2));
+    g_trace[tll == SET_BASIC ? T_ll_basic : tll == SET_RLE ? T_ll_rle : tll == SET_COMPRESSED ? T_ll_compressed : T_ll_repeat] += g_trace_on;
+    g_trace[tof == SET_BASIC ? T_of_basic : tof == SET_RLE ? T_of_rle : tof == SET_COMPRESSED ? T_of_compressed : T_of_repeat] += g_trace_on;
+    g_trace[tml == SET_BASIC ? T_ml_basic : tml == SET_RLE ? T_ml_rle : tml == SET_COMPRESSED ? T_ml_compressed : T_ml_repeat] += g_trace_on;
     {
         bitw b;
         uint32_t sm, so, sl;
@@ -822,22 +879,31 @@ static size_t compress_sequences(uint8_t *dst, const seq_t *seqs, size_t nseq, c
         bw_add(&b, seqs[n].ml, ML_bits[mlc[n]]);
         bw_add(&b, seqs[n].off, ofc[n]);
         while (n-- > 0) {
+            const size_t bit0 = b.len * 8 + (size_t)b.n;
             so = fse_encode(&b, &ct_of, so, ofc[n]);
             sm = fse_encode(&b, &ct_ml, sm, mlc[n]);
             sl = fse_encode(&b, &ct_ll, sl, llc[n]);
             bw_add(&b, seqs[n].ll, LL_bits[llc[n]]);
             bw_add(&b, seqs[n].ml, ML_bits[mlc[n]]);
             bw_add(&b, seqs[n].off, ofc[n]);
+            {
+                const size_t tb = b.len * 8 + (size_t)b.n - bit0, sh = bit0 & 31;
+                if (tb > 64) HIT(seq_bits_over_64);
+                if (sh + tb > 64) HIT(seq_bits_3_dwords);
+                if (sh + tb > 96) HIT(seq_bits_4_dwords);
+            }
         }
         bw_add(&b, sm, ct_ml.log);
         bw_add(&b, so, ct_of.log);
         bw_add(&b, sl, ct_ll.log);
         bs = bw_close(&b);
+        if (bs > b.cap) HIT(seq_over_cap);
         op += bs;
-        if (last_ncount && (size_t)(dst + op - last_ncount) < 4) return 0;
+        if (last_ncount && (size_t)(dst + op - last_ncount) < 4) { HIT(seq_last_ncount_raw); return 0; }
     }
 check:
-    if (op >= src_size - min_gain(src_size)) return 0;
+    if (op >= src_size - min_gain(src_size)) { HIT(block_mingain_raw); return 0; }
+    HIT(block_compressed);
     return op;
 #undef ct_ll
 #undef ct_of
@@ -1783,6 +1849,13 @@ static int get_cpar(int level, size_t n, cpar *cp)
     return 0;
 }
 
+int cryo_oracle_zstd_enc_strategy(int level, size_t n)
+{
+    cpar cp;
+    if (get_cpar(level, n, &cp)) return 0;
+    return cp.bt ? 6 + cp.opt : (cp.lazy_depth >= 0 ? 3 + cp.lazy_depth : (cp.dfast ? 2 : 1));
+}
+
 /* ------------------------------------------------------------ frame */
 size_t cryo_oracle_zstd_compress(const uint8_t *src, size_t n, uint8_t *dst, size_t cap, int level)
 {
@@ -1828,6 +1901,7 @@ size_t cryo_oracle_zstd_compress(const uint8_t *src, size_t n, uint8_t *dst, siz
         const size_t bs = (n - ip < ZBLOCK_MAX) ? n - ip : ZBLOCK_MAX;
         const int last = (ip + bs == n);
         size_t csize = 0;
+        g_trace_on = ip / ZBLOCK_MAX >= (size_t)(g_trace_from > 0 ? g_trace_from : 0);
         /* libzstd 1.4.8's ZSTD_compress_frameChunk only calls ZSTD_checkDictValidity here (no dictionary: a
          * no-op); window.dictLimit stays 1 for the whole frame and the window is enforced per block through
          * ZSTD_getLowestPrefixIndex.  (Raising dict_limit like ZSTD_window_enforceMaxDist gives the same prefix

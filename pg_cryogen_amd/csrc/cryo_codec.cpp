@@ -2270,7 +2270,9 @@ static int compress_blocks_host(cryo_codec *c, int method, int param, const Comp
     if (rc != CRYO_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
     HIP_TRY(c, hipMemcpyAsync(h_sz, d_sz, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(h_st, d_st, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    if (bulk) HIP_TRY(c, hipMemcpyAsync(io.dst, c->hb_dst, (n - 1) * dstride + bound, hipMemcpyDeviceToHost, c->stream));
+    /* a padded stride: rows of `bound` bytes, so that the caller's bytes between the slots stay the caller's */
+    if (bulk && dstride == bound) HIP_TRY(c, hipMemcpyAsync(io.dst, c->hb_dst, n * bound, hipMemcpyDeviceToHost, c->stream));
+    else if (bulk) HIP_TRY(c, hipMemcpy2DAsync(io.dst, dstride, c->hb_dst, dstride, bound, n, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if ((rc = take_encoded(c, h_st, h_sz, n, bound, h_out_size)) != CRYO_OK) return rc;
     if (bulk) return CRYO_OK;

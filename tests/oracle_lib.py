@@ -40,6 +40,19 @@ class Oracle:
         if hasattr(L, "cryo_oracle_zstd_compress"):
             L.cryo_oracle_zstd_compress.argtypes = [vp, sz, vp, sz, C.c_int]
             L.cryo_oracle_zstd_compress.restype = sz
+        L.cryo_oracle_zstd_enc_strategy.argtypes = [C.c_int, sz]
+        L.cryo_oracle_zstd_enc_strategy.restype = C.c_int
+        # the entropy stage's branch counters: names and order come from the library (oracle/cryo_oracle.h declares them once)
+        L.cryo_oracle_zstd_enc_trace_count.restype = C.c_int
+        L.cryo_oracle_zstd_enc_trace_name.argtypes = [C.c_int]
+        L.cryo_oracle_zstd_enc_trace_name.restype = C.c_char_p
+        L.cryo_oracle_zstd_enc_trace_reset.restype = None
+        L.cryo_oracle_zstd_enc_trace_from_block.argtypes = [C.c_int]
+        L.cryo_oracle_zstd_enc_trace_from_block.restype = None
+        L.cryo_oracle_zstd_enc_trace_get.argtypes = [vp]
+        L.cryo_oracle_zstd_enc_trace_get.restype = None
+        self.zstd_enc_trace_names = tuple(L.cryo_oracle_zstd_enc_trace_name(i).decode()
+                                          for i in range(L.cryo_oracle_zstd_enc_trace_count()))
 
     def synth(self, seed, block, B, dist):
         a = np.empty(B, np.uint8)
@@ -74,6 +87,29 @@ class Oracle:
         d = np.empty(max(cap, 1), np.uint8)
         r = self.L.cryo_oracle_zstd_compress(a.ctypes.data, a.nbytes, d.ctypes.data, cap, level)
         return d[:r].copy()
+
+    def zstd_enc_strategy(self, level, n):
+        """1 `fast` .. 9 `btultra2`: what zstd_compress takes for n bytes at a level"""
+        return self.L.cryo_oracle_zstd_enc_strategy(level, n)
+
+    def zstd_enc_trace_reset(self):
+        self.L.cryo_oracle_zstd_enc_trace_reset()
+
+    def zstd_enc_trace(self):
+        """{counter name: hits since the last reset} of the encoder's entropy stage"""
+        v = np.zeros(len(self.zstd_enc_trace_names), np.uint64)
+        self.L.cryo_oracle_zstd_enc_trace_get(v.ctypes.data)
+        return {k: int(x) for k, x in zip(self.zstd_enc_trace_names, v)}
+
+    def zstd_compress_traced(self, a, level=1, from_block=0):
+        """(frame, {counter: hits}) of one zstd_compress call, counted from the frame's zstd block `from_block` on"""
+        self.zstd_enc_trace_reset()
+        self.L.cryo_oracle_zstd_enc_trace_from_block(from_block)
+        try:
+            f = self.zstd_compress(a, level)
+        finally:
+            self.L.cryo_oracle_zstd_enc_trace_from_block(0)
+        return f, self.zstd_enc_trace()
 
 
 class _ZstdBounds(C.Structure):

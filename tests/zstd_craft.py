@@ -135,6 +135,53 @@ def _walk_block(b):
     return out
 
 
+def walk_entropy(frame):
+    """walk() with the entropy stage's header fields on every compressed block (header reading, no entropy decoding):
+        lit          raw | rle | compressed | treeless
+        lit_format   the 2-bit size format of the literals section header
+        lit_header   bytes of that header (1, 2, 3 | 3, 4, 5)
+        regen        regenerated size: the number of literals
+        lit_csize    compressed size (Huffman literals), else None
+        streams      1 or 4 (Huffman literals), else None
+        tree         the tree description's first byte (compressed literals): < 128 FSE-compressed weights of that many
+                     bytes, >= 128 direct 4-bit weights of (byte - 127) symbols; else None
+        nseq, nseq_bytes   the sequence count and the bytes it takes (1, 2 or 3)
+        modes        (LL, OF, ML) table modes, None without sequences
+    Raises AssertionError where walk() finds the structure broken."""
+    info = walk(frame)
+    assert info is not None, "broken frame"
+    b = bytes(frame)
+    fhd = b[4]
+    fcs_flag, single, did = fhd >> 6, (fhd >> 5) & 1, fhd & 3
+    p = 5 + (0 if single else 1) + (0, 1, 2, 4)[did] + ((1 if single else 0), 2, 4, 8)[fcs_flag]
+    for blk in info["blocks"]:
+        body = b[p + 3:p + 3 + blk["size"]]
+        p += 3 + (1 if blk["type"] == "rle" else blk["size"])
+        if blk["type"] != "compressed":
+            continue
+        assert not blk.get("broken"), blk
+        b0 = body[0]
+        lt, sf = b0 & 3, (b0 >> 2) & 3
+        blk["lit_format"] = sf
+        if lt < 2:
+            hl = (1, 2, 1, 3)[sf]
+            blk["regen"] = b0 >> 3 if hl == 1 else int.from_bytes(body[:hl], "little") >> 4
+            blk["lit_csize"] = blk["streams"] = blk["tree"] = None
+            q = hl + (blk["regen"] if lt == 0 else 1)
+        else:
+            hl, bits = (3, 3, 4, 5)[sf], (10, 10, 14, 18)[sf]
+            h = int.from_bytes(body[:hl], "little")
+            blk["regen"] = (h >> 4) & ((1 << bits) - 1)
+            blk["lit_csize"] = (h >> (4 + bits)) & ((1 << bits) - 1)
+            blk["streams"] = 1 if sf == 0 else 4
+            blk["tree"] = body[hl] if lt == 2 else None
+            q = hl + blk["lit_csize"]
+        blk["lit_header"] = hl
+        s0 = body[q]
+        blk["nseq_bytes"] = 1 if s0 < 128 else (2 if s0 < 255 else 3)
+    return info
+
+
 def zstd_nbmax(B):
     """blocks per frame the batch planner takes (zstd_pipe.hip make_layout: B / 128 KiB + 2); more go to the fused kernel"""
     return min(B // 131072 + 2, 254)
