@@ -807,6 +807,71 @@ int cryo_codec_project_batch(cryo_codec *c, int method, const void *d_src, const
                              const cryo_project *prj, void *d_rows, uint64_t row_cap, cryo_project_rec *d_rec,
                              uint64_t rec_cap, cryo_project_block *d_blocks, uint64_t *d_total);
 
+/* ---- ordering a scan: stored streams -> decoded in handle workspace -> keys tested, each block's matches ranked by one or two
+ *      columns -> a row per block, and of every block only its first `limit` matches come back: a 24-byte record and the
+ *      projection's row each ----
+ * The "latest rows" query: SELECT id, ts, revenue FROM t WHERE app_id IN (3, 17) AND ts >= a ORDER BY ts DESC LIMIT 100.  Through
+ * the projection a block returns every match, up to 290 rows, and the host sorts them and keeps 100 of the whole relation.  A
+ * block is the unit of visibility (one created_xid per block), so the exact answer under any snapshot is "the first N rows, in
+ * order, of every visible block, merged": each block's first N are selected where the decoded block lies, and 24 + row_bytes bytes
+ * per KEPT row leave the device (pg_cryogen_amd/host/topn.h walks a relation with it and merges).
+ * A call names n_blocks stored streams as cryo_codec_check_batch does, the filter's descriptor *f and the projection *prj, both
+ * unchanged, and an order *ord: nby order columns, each {att, type, flags}, and limit.
+ * Out of scope: text, bytea or bucketed order columns; more than two order columns; WITH TIES and DISTINCT ON; a call-wide cut
+ * across blocks on the device (visibility is the caller's, per block: the merge is the host's); OFFSET (the binder asks for
+ * LIMIT + OFFSET and drops the first rows after the merge).
+ *
+ * Descriptor.  CRYO_E_ARG when: *f or *prj is refused by cryo_codec_project_batch; nby is 0 or above CRYO_ORDER_MAX_BY; limit is 0;
+ * an order column breaks the aggregate column's rules (att outside 1 .. f->natts, attlen not the type's size, attalign below
+ * attlen) or its type is not CRYO_KEY_INT2, _INT4, _INT8, _FLOAT4 or _FLOAT8; a flag bit other than CRYO_ORDER_DESC and
+ * CRYO_ORDER_NULLS_FIRST is set; a column's rsv is not 0.  A column may be an order column, a projected column and carry a key at
+ * once; the same column may be both order columns.
+ *
+ * Per block: statuses, the ITEM and TUPLE rules and n_items, n_match, n_bad exactly as in the projection, except that the walk
+ * runs over the columns 1 .. max(highest key column, highest projected column, highest order column) for every tuple.  Bad and
+ * undecided items count in n_bad and are in no ranking; the call writes no record for them (the aggregate's rule: the caller reads
+ * such a block through the filter).
+ *
+ * Order of a block's matches: ascending by order column 1, then by order column 2, each under its own flags; ties are broken by
+ * position, ascending, so the order is total and stable.  Within a column: CRYO_ORDER_DESC reverses the order of the values.
+ * NULLs -- a clear bitmap bit, or a column beyond the tuple's natts -- sort after every value, or before every value with
+ * CRYO_ORDER_NULLS_FIRST, whatever the direction; all NULLs are equal.  Integer columns compare as sign-extended 64-bit integers.
+ * Float columns compare in PostgreSQL's order: -Inf < finite < +Inf < NaN, all NaNs equal, -0 = +0; a float4 is widened exactly.
+ * That order is the signed order of the value's image: with b the bits of the (widened) double, the image is INT64_MAX for a NaN,
+ * 0 for either zero, b for any other positive value and b ^ 0x7FFFFFFFFFFFFFFF for a negative one.
+ * Kept rows: the first min(limit, n_match) matches of that order.  limit >= 290 is an ordered projection of every match.
+ *
+ * Results.  One cryo_topn_block per block, in call order: n_match is counted in full, n_rows is the kept rows, row_first the sum of
+ * n_rows over the blocks before (a STREAM or HEADER block carries the value at which the next block starts).  One cryo_topn_rec and
+ * one row per kept row, in rank order: the block's are entries row_first .. row_first + n_rows - 1 of both outputs, record r
+ * belongs to row r, and row r lies at byte r * row_bytes of the rows.  key[j] is the signed 64-bit integer the order compared,
+ * BEFORE the direction is applied: the sign-extended value, or a float column's image; 0 when the column is NULL or j >= nby.  Bit j
+ * of key_nulls is set when order column j is NULL, and no other bit is.  So a merge of blocks needs nothing but integer compares
+ * and the descriptor's flags.  pos and nulls are cryo_project_rec's; the row is the projection's row, bit for bit.
+ * *total (one entry) = the kept rows of the whole call, counted in full even where row_cap cuts the writing off: no record and no
+ * row at or beyond row_cap, and nothing at or beyond the total, is written.  row_cap >= min(limit, 290) * n_blocks always suffices.
+ * The output of a call is defined byte for byte. */
+#define CRYO_ORDER_DESC        1u   /* cryo_order_col.flags */
+#define CRYO_ORDER_NULLS_FIRST 2u
+#define CRYO_ORDER_MAX_BY      2u
+typedef struct { uint16_t att; uint8_t type, flags; uint32_t rsv; } cryo_order_col;           /* att 1-based; 8 bytes */
+typedef struct { uint32_t nby, limit; const cryo_order_col *by; } cryo_order;                  /* 16 bytes */
+typedef struct { uint32_t status, n_items, n_match, n_bad; uint32_t n_rows, rsv; uint64_t row_first; } cryo_topn_block; /* 32 bytes */
+typedef struct { int64_t key[2]; uint16_t pos, key_nulls; uint32_t nulls; } cryo_topn_rec;    /* 24 bytes */
+/* Device buffers.  The structs *f, *ord and *prj are host memory; f->atts, f->keys, ord->by and prj->cols are DEVICE arrays (4-byte
+ * / 8-byte / 8-byte / 8-byte aligned).  The host validates the descriptors before anything is queued, as the projection does (the
+ * same waits), then puts the kernel's table -- 80 bytes: the order columns, then the projection's column table -- into handle
+ * workspace (one more wait); from there on the call is asynchronous, with no host wait between its internal chunks.  d_rows
+ * (row_cap rows of row_bytes), d_rec (row_cap records) and d_total 8-byte, d_blocks (n_blocks rows) 16-byte aligned (CRYO_E_ARG
+ * otherwise); d_total has one entry and is also where the running total lives between the call's internal chunks.  Decode as in
+ * the projection (the workspace also holds a side area of 28 + row_bytes bytes per possible item of a chunk); the device pool is
+ * neither read nor filled, nothing counts in cryo_codec_counters.  CRYO_E_ARG as for cryo_codec_project_batch, a bad descriptor, a
+ * null ord or prj, a null d_total, a null d_blocks, a null d_rows or d_rec with row_cap > 0; n_blocks == 0: CRYO_OK, total 0. */
+int cryo_codec_topn_batch(cryo_codec *c, int method, const void *d_src, const uint64_t *d_src_off,
+                          const uint32_t *d_src_size, uint32_t block_size, uint64_t n_blocks, const cryo_filter *f,
+                          const cryo_order *ord, const cryo_project *prj, void *d_rows, cryo_topn_rec *d_rec, uint64_t row_cap,
+                          cryo_topn_block *d_blocks, uint64_t *d_total);
+
 /* ---- single block, HOST buffers: what cryo_compress()/cryo_decompress()
  *      (compression.c:125-159) call.  Synchronous: H2D, kernel, D2H. ---- */
 int cryo_codec_compress_block(cryo_codec *c, int method, int param,
@@ -940,6 +1005,23 @@ int cryo_codec_project_blocks(cryo_codec *c, int method, const void *const *h_sr
                               void *h_rows, size_t row_cap, cryo_project_rec *h_rec, size_t rec_cap,
                               cryo_project_block *h_blocks, uint64_t *h_total);
 
+/* cryo_codec_topn_batch on host buffers (stream i: h_src[i], h_src_size[i] bytes; f->atts, f->keys, ord->by and prj->cols are HOST
+ * arrays), synchronous.  Only compressed bytes and the descriptors travel towards the device, only the block table and the kept
+ * rows' records and rows come back.
+ *   Upload   the streams staged and uploaded as by cryo_codec_filter_blocks, then the descriptors in a second copy: h2d_bytes
+ *            grows by another align16(4 * natts) + 16 * nkeys + 80 (plus, as everywhere, the constants of byte-string keys).
+ *   Return   after the last chunk the rows of the block table of the whole call, then -- their number known from the last row of
+ *            the table -- exactly the call's records and rows (two waits): d2h_bytes grows by exactly
+ *            32 * n_blocks + (24 + row_bytes) * *h_total.
+ *   Errors   more kept rows than row_cap: CRYO_E_DSTSIZE, *h_total is the full count and h_rows and h_rec hold nothing to rely on
+ *            (row_cap >= min(limit, 290) * n_blocks always fits).  CRYO_E_ARG as cryo_codec_topn_batch; a bad descriptor is
+ *            refused before a device is touched.  n_blocks == 0: CRYO_OK, total 0.
+ * h_total has one entry.  Returns CRYO_OK when the batch ran, whatever the table says. */
+int cryo_codec_topn_blocks(cryo_codec *c, int method, const void *const *h_src, const uint32_t *h_src_size,
+                           size_t n_blocks, size_t block_size, const cryo_filter *f, const cryo_order *ord,
+                           const cryo_project *prj, void *h_rows, cryo_topn_rec *h_rec, size_t row_cap,
+                           cryo_topn_block *h_blocks, uint64_t *h_total);
+
 /* ---- device-resident block pool ("optional device-resident compressed/decompressed pool so
  *      repeated scans skip PCIe"; the reference's cache is host-only: cache.c:17-50).
  *      With CRYO_OPT_POOL_BYTES > 0 the decoded blocks of keyed calls stay in HBM (first in, first out).  A key is the
@@ -1060,6 +1142,17 @@ int cryo_multi_project_blocks(cryo_multi *m, int method, const void *const *h_sr
                               size_t n_blocks, size_t block_size, const cryo_filter *f, const cryo_project *prj,
                               void *h_rows, size_t row_cap, cryo_project_rec *h_rec, size_t rec_cap,
                               cryo_project_block *h_blocks, uint64_t *h_total);
+
+/* cryo_codec_topn_blocks across the devices: block i -> handle i mod G.  cryo_multi_project_blocks' scheme with min(limit, 290)
+ * entries per block: handle g, whose share is the blocks g, g + G, ..., owns one region of min(limit, 290) * share entries of
+ * h_rows and of h_rec alike, the regions laid out in handle order (a region that reaches beyond row_cap is cut there, so row_cap
+ * >= min(limit, 290) * n_blocks always suffices).  The block table comes back in call order and finds everything: row_first
+ * counts from h_rows / h_rec, but with more than one handle it is a running sum only within one handle's blocks (from its
+ * region's start).  *h_total: the end of the last entry used (0: none).  One handle: exactly cryo_codec_topn_blocks. */
+int cryo_multi_topn_blocks(cryo_multi *m, int method, const void *const *h_src, const uint32_t *h_src_size,
+                           size_t n_blocks, size_t block_size, const cryo_filter *f, const cryo_order *ord,
+                           const cryo_project *prj, void *h_rows, cryo_topn_rec *h_rec, size_t row_cap,
+                           cryo_topn_block *h_blocks, uint64_t *h_total);
 
 /* ---- batch helpers used by staging, tests and the benchmark ---- */
 

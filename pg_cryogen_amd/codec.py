@@ -81,6 +81,13 @@ PROJECT_COL = np.dtype([("att", "<u2"), ("rsv", "<u2"), ("rsv2", "<u4")])       
 PROJECT_BLOCK = np.dtype([("status", "<u4"), ("n_items", "<u4"), ("n_match", "<u4"), ("n_bad", "<u4"),
                           ("rec_first", "<u8"), ("row_first", "<u8")])                                          # cryo_project_block
 PROJECT_REC = np.dtype([("pos", "<u2"), ("status", "<u2"), ("nulls", "<u4")])                                   # cryo_project_rec
+# the ordered scan (include/cryo_codec.h): a block's statuses are the aggregate's; rows are the projection's
+ORDER_DESC, ORDER_NULLS_FIRST = 1, 2    # cryo_order_col.flags
+ORDER_MAX_BY = 2
+ORDER_COL = np.dtype([("att", "<u2"), ("type", "u1"), ("flags", "u1"), ("rsv", "<u4")])                          # cryo_order_col
+TOPN_BLOCK = np.dtype([("status", "<u4"), ("n_items", "<u4"), ("n_match", "<u4"), ("n_bad", "<u4"),
+                       ("n_rows", "<u4"), ("rsv", "<u4"), ("row_first", "<u8")])                                 # cryo_topn_block
+TOPN_REC = np.dtype([("key", "<i8", (2,)), ("pos", "<u2"), ("key_nulls", "<u2"), ("nulls", "<u4")])              # cryo_topn_rec
 LZ4_PATH_AUTO, LZ4_PATH_RING, LZ4_PATH_INDEXED, LZ4_PATH_FEW_BLOCKS = 0, 1, 2, 3
 
 DIST_WIDE, DIST_NARROW, DIST_INT4, DIST_RANDOM, DIST_ZEROS = range(5)
@@ -112,6 +119,7 @@ ABI_SYMBOLS = [
     "cryo_codec_agg_batch", "cryo_codec_agg_blocks", "cryo_multi_agg_blocks",
     "cryo_codec_group_batch", "cryo_codec_group_blocks", "cryo_multi_group_blocks",
     "cryo_codec_project_batch", "cryo_codec_project_blocks", "cryo_multi_project_blocks",
+    "cryo_codec_topn_batch", "cryo_codec_topn_blocks", "cryo_multi_topn_blocks",
     "cryo_codec_lz4_index_cap", "cryo_codec_lz4_index_rows", "cryo_codec_debug_fill",
 ]
 
@@ -146,6 +154,11 @@ class CryoGroupB(CryoGroup):
 class CryoProject(C.Structure):
     """cryo_project: cols points to a device array for project_batch, to a host array for project_blocks"""
     _fields_ = [("ncols", C.c_uint32), ("rsv", C.c_uint32), ("cols", C.c_void_p)]
+
+
+class CryoOrder(C.Structure):
+    """cryo_order: by points to a device array for topn_batch, to a host array for topn_blocks"""
+    _fields_ = [("nby", C.c_uint32), ("limit", C.c_uint32), ("by", C.c_void_p)]
 
 
 class TransferCounters(C.Structure):
@@ -255,6 +268,10 @@ def lib():
     L.cryo_codec_project_batch.argtypes = [vp, i32, vp, vp, vp, u32, u64, fp, pp, vp, u64, vp, u64, vp, vp]
     L.cryo_codec_project_blocks.argtypes = [vp, i32, vp, vp, sz, sz, fp, pp, vp, sz, vp, sz, vp, vp]
     L.cryo_multi_project_blocks.argtypes = [vp, i32, vp, vp, sz, sz, fp, pp, vp, sz, vp, sz, vp, vp]
+    op = C.POINTER(CryoOrder)
+    L.cryo_codec_topn_batch.argtypes = [vp, i32, vp, vp, vp, u32, u64, fp, op, pp, vp, vp, u64, vp, vp]
+    L.cryo_codec_topn_blocks.argtypes = [vp, i32, vp, vp, sz, sz, fp, op, pp, vp, vp, sz, vp, vp]
+    L.cryo_multi_topn_blocks.argtypes = [vp, i32, vp, vp, sz, sz, fp, op, pp, vp, vp, sz, vp, vp]
     L.cryo_codec_lz4_index_cap.argtypes = [u32]
     L.cryo_codec_lz4_index_cap.restype = u32
     L.cryo_codec_lz4_index_rows.argtypes = [vp, vp, vp, vp, u32, u64, i32, vp, vp]
@@ -572,6 +589,71 @@ def project_blocks_call(fn, handle, chk, method, comps, block_size, desc, pdesc,
     chk(fn(handle, method, src, szs, n, block_size, C.byref(desc[0]), C.byref(pdesc[0]), rows.ctypes.data if rows.size else None,
            rows.shape[0], rec.ctypes.data if rec.size else None, rec.size, table.ctypes.data, total), "project_blocks")
     return table[:n], rec, rows, (total[0], total[1])
+
+
+def order_desc(by, limit):
+    """the order of a topn call as a host array: by a list of (att, type, flags) (att 1-based; type KEY_INT2 .. KEY_INT8,
+    KEY_FLOAT4, KEY_FLOAT8; flags ORDER_DESC | ORDER_NULLS_FIRST).  Returns (CryoOrder, by array); the struct points into the
+    array, which the caller keeps alive"""
+    a = np.zeros(max(len(by), 1), ORDER_COL)
+    for j, (att, typ, flags) in enumerate(by):
+        a[j] = (att, typ, flags, 0)
+    return CryoOrder(len(by), limit, a.ctypes.data), a
+
+
+def topn_blocks_call(fn, handle, chk, method, comps, block_size, desc, odesc, pdesc, row_bytes, rows=None, rec=None):
+    """cryo_codec_topn_blocks / cryo_multi_topn_blocks (fn) on a list of host streams with the descriptors filter_desc,
+    order_desc and project_desc made; row_bytes: what project_row_layout says.  Returns (table: TOPN_BLOCK array in call order,
+    records: the TOPN_REC buffer, rows: a uint8 buffer of shape (row_cap, row_bytes), total kept rows).  rows / rec: the caller's
+    buffers (the capacity is the shorter one's length), else fresh ones of the worst-case size, min(limit, 290) per block"""
+    n = len(comps)
+    arrs = [np.ascontiguousarray(np.asarray(c, dtype=np.uint8)) for c in comps]
+    src = (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.nbytes else None for a in arrs])
+    szs = (C.c_uint32 * max(n, 1))(*[a.nbytes for a in arrs])
+    per = min(int(odesc[0].limit), 290)
+    if rows is None:
+        rows = np.zeros((max(n, 1) * max(per, 1), row_bytes), np.uint8)
+    if rec is None:
+        rec = np.zeros(max(n, 1) * max(per, 1), TOPN_REC)
+    cap = min(rows.shape[0], rec.size)
+    table = np.zeros(max(n, 1), TOPN_BLOCK)
+    total = C.c_uint64(0)
+    chk(fn(handle, method, src, szs, n, block_size, C.byref(desc[0]), C.byref(odesc[0]), C.byref(pdesc[0]),
+           rows.ctypes.data if cap else None, rec.ctypes.data if cap else None, cap, table.ctypes.data, C.byref(total)), "topn_blocks")
+    return table[:n], rec, rows, total.value
+
+
+def topn_sort_key(by, rec):
+    """what the order of the descriptor (by: a list of (att, type, flags)) compares of a TOPN_REC: per order column (class, key
+    under the direction); Python tuples of these sort as the contract's order does"""
+    out = []
+    for j, (_, _, flags) in enumerate(by):
+        if (int(rec["key_nulls"]) >> j) & 1:
+            out.append((0 if flags & ORDER_NULLS_FIRST else 2, 0))
+        else:
+            k = int(rec["key"][j])
+            out.append((1, ~k if flags & ORDER_DESC else k))
+    return tuple(out)
+
+
+def topn_merge(by, limit, blocks):
+    """the merge of a call's blocks: by as for order_desc, blocks a sequence of (records, rows) -- one block's TOPN_REC array and
+    its rows, in the block's order -- of the blocks the caller's snapshot sees, in the order they are added.  Returns (records,
+    rows) of the first `limit` rows of the whole: ordered by the descriptor over key / key_nulls, ties to the block added earlier,
+    then to the block's own order"""
+    entries = []
+    for b, (recs, rows) in enumerate(blocks):
+        for r in range(len(recs)):
+            entries.append((topn_sort_key(by, recs[r]), b, r))
+    entries.sort()
+    entries = entries[:limit]
+    row_bytes = next((rows.shape[1] for _, rows in blocks if len(rows)), 0)
+    out_rec = np.zeros(len(entries), TOPN_REC)
+    out_rows = np.zeros((len(entries), row_bytes), np.uint8)
+    for i, (_, b, r) in enumerate(entries):
+        out_rec[i] = blocks[b][0][r]
+        out_rows[i] = blocks[b][1][r]
+    return out_rec, out_rows
 
 
 def cell_sum(cell):
@@ -937,6 +1019,27 @@ class Codec:
         n_bad], the row of its k-th match is rows[table[i]["row_first"] + k]"""
         return project_blocks_call(self.L.cryo_codec_project_blocks, self.h, self._chk, method, comps, block_size, desc, pdesc,
                                    row_bytes, rows, rec)
+
+    def topn_batch(self, method, d_src, d_off, d_sizes, block_size, n, natts, d_atts, nkeys, d_keys, nby, limit, d_by, ncols, d_cols,
+                   d_rows, d_rec, row_cap, d_blocks, d_total, truth=None):
+        """test the keys on every tuple of the n stored blocks, rank each block's matches by the nby order columns d_by names
+        (ORDER_COL) and keep the first `limit` of each block: one TOPN_BLOCK row per block in d_blocks, one TOPN_REC in d_rec and
+        one row of row_bytes in d_rows per kept row (at most row_cap of each are written), in rank order, the total of kept rows
+        in d_total (1 x u64).  d_atts, d_keys, d_cols, truth: as for project_batch.  Asynchronous once the descriptors are read
+        back and the kernel's table is in place."""
+        f = CryoFilter(natts, nkeys, *truth_flags(0, truth), d_atts.ptr if d_atts else None, d_keys.ptr if d_keys else None)
+        o = CryoOrder(nby, limit, d_by.ptr if d_by else None)
+        p = CryoProject(ncols, 0, d_cols.ptr if d_cols else None)
+        self._chk(self.L.cryo_codec_topn_batch(self.h, method, d_src.ptr, d_off.ptr, d_sizes.ptr, block_size, n, C.byref(f), C.byref(o),
+                                               C.byref(p), d_rows.ptr if d_rows else None, d_rec.ptr if d_rec else None, row_cap,
+                                               d_blocks.ptr if d_blocks else None, d_total.ptr if d_total else None), "topn_batch")
+
+    def topn_blocks(self, method, comps, block_size, desc, odesc, pdesc, row_bytes, rows=None, rec=None):
+        """ordered scan of host streams (desc: what filter_desc returns, odesc: order_desc, pdesc: project_desc, row_bytes:
+        project_row_layout's); returns (table, records, rows, total): block i's kept rows are records / rows
+        [table[i]["row_first"]:][:table[i]["n_rows"]], in rank order"""
+        return topn_blocks_call(self.L.cryo_codec_topn_blocks, self.h, self._chk, method, comps, block_size, desc, odesc, pdesc,
+                                row_bytes, rows, rec)
 
     def last_verify_failure(self):
         """(block, first mismatch) that made the last host-buffer compress call fail verification, or None"""

@@ -1717,6 +1717,86 @@ static int project_pass(cryo_codec *c, int method, const uint8_t *d_src, const u
     return decode_pass(c, method, B, n, ps);
 }
 
+/* ---- the ordered scan ----
+ * The shared decode loop over the caller's stream table; on every decoded chunk topn.hip tests the keys on every tuple, writes a
+ * row per match to a side area, ranks each block's matches in LDS and writes a record and the row's side-area index per kept row,
+ * places the blocks behind the running total -- which stays in device memory (*d_total) from chunk to chunk -- and gathers records
+ * and rows to their places in the call's output.  Per chunk (own) each block has 24 + row_bytes + 4 bytes per possible item of
+ * side area; the pass's fixed bytes hold the kernel's table -- the order columns, then the projection's column table -- when the
+ * caller's arrays come as device arrays.  The pass waits once, for that table, and then for nothing.  Its decodes count nowhere. */
+namespace {
+/* the kernel's table (launch_topn): entries 0 .. 1 the order columns {att, type, flags, 0}, entries 2 .. 9 ProjectTab's */
+struct TopnTab {
+    cryo_agg_col slots[CRYO_ORDER_MAX_BY + CRYO_PROJECT_MAX_COLS] = {};
+    uint32_t nby = 0, limit = 0, ncols = 0, row_bytes = 0;
+};
+struct TopnIo {
+    ScanDesc sd;
+    TopnTab tt;
+    const void *d_tab = nullptr;         /* device: tt.slots in place already, or null: the pass uploads it */
+    cryo_topn_block *d_blocks = nullptr; /* device: n rows of the block table */
+    void *d_rows = nullptr;              /* device: row_cap rows */
+    cryo_topn_rec *d_rec = nullptr;      /* device: row_cap records */
+    uint64_t row_cap = 0;
+    uint64_t *d_total = nullptr;         /* device: the running total */
+};
+} // namespace
+
+/* the kept rows a block can have under `limit` */
+static uint64_t topn_per_block(uint32_t limit, uint64_t side_stride) { return limit < side_stride ? limit : side_stride; }
+
+/* the ordered scan's descriptor rules (include/cryo_codec.h); every array is host memory here.  *max_att: the highest key,
+ * projected or order column; *tt: the kernel's table, the limit and the row's size */
+static bool topn_desc_ok(const cryo_filter *f, const cryo_att *atts, const cryo_scan_key *keys, const cryo_order *ord,
+                         const cryo_order_col *by, const cryo_project *prj, const cryo_project_col *cols, uint32_t *max_att, TopnTab *tt)
+{
+    ProjectTab pt;
+    if (!project_desc_ok(f, atts, keys, prj, cols, max_att, &pt)) return false;
+    if (!ord || ord->nby == 0 || ord->nby > CRYO_ORDER_MAX_BY || ord->limit == 0 || !by) return false;
+    *tt = TopnTab();
+    for (uint32_t j = 0; j < ord->nby; j++) {
+        const cryo_order_col &q = by[j];
+        if ((q.flags & ~(CRYO_ORDER_DESC | CRYO_ORDER_NULLS_FIRST)) != 0 || q.rsv != 0) return false;
+        const cryo_agg_col as_col = {q.att, q.type, 0, 0};
+        if (!agg_col_ok(f, atts, as_col, max_att, true)) return false;
+        tt->slots[j] = {q.att, q.type, q.flags, 0};
+    }
+    memcpy(tt->slots + CRYO_ORDER_MAX_BY, pt.tab, sizeof pt.tab);
+    tt->nby = ord->nby; tt->limit = ord->limit; tt->ncols = pt.ncols; tt->row_bytes = pt.row_bytes;
+    return true;
+}
+
+static int topn_pass(cryo_codec *c, int method, const uint8_t *d_src, const uint64_t *d_src_off, const uint32_t *d_src_size,
+                     uint32_t B, uint64_t n, const TopnIo &io)
+{
+    static_assert(sizeof(cryo_topn_block) == 2 * sizeof(uint4) && sizeof(cryo_topn_rec) == 24 && sizeof(cryo_order_col) == sizeof(cryo_agg_col) &&
+                      sizeof(cryo_order) == 16,
+                  "the ordered scan's records are the kernels'");
+    const uint64_t S = cryo::filter_side_stride(B);
+    DecodePass ps(d_src, d_src_off, d_src_size, true);
+    ps.fixed = 256u;                                                                         /* the table */
+    ps.own_per_block = (S * (sizeof(cryo_topn_rec) + io.tt.row_bytes + sizeof(uint32_t)) + 7u) & ~(uint64_t)7u; /* the side area */
+    ps.run = [&](const DecodeChunk &ch) -> int {
+        const void *tab = io.d_tab ? io.d_tab : ch.fixed;
+        if (ch.lo == 0) {
+            HIP_TRY(c, hipMemsetAsync(io.d_total, 0, sizeof(uint64_t), c->stream));
+            if (!io.d_tab) { /* io is the call's own: the table is in place before the call goes on */
+                HIP_TRY(c, hipMemcpyAsync(ch.fixed, io.tt.slots, sizeof io.tt.slots, hipMemcpyHostToDevice, c->stream));
+                HIP_TRY(c, hipStreamSynchronize(c->stream));
+            }
+        }
+        /* records and rows are whole words; the order list, of 4-byte entries, lies behind them */
+        uint8_t *side_rec = ch.own, *side_rows = side_rec + ch.K * S * sizeof(cryo_topn_rec);
+        uint8_t *side_ord = side_rows + ch.K * S * io.tt.row_bytes;
+        HIP_TRY(c, cryo::launch_topn(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.sd.d_atts, io.sd.d_keys, io.sd.nkeys, tab, io.tt.slots,
+                                     io.tt.nby, io.tt.ncols, io.tt.row_bytes, io.tt.limit, io.sd.max_att, io.sd.truth, io.sd.floats,
+                                     (uint4 *)(io.d_blocks + ch.lo), side_rec, side_rows, side_ord, io.d_total, io.d_rec, io.d_rows, io.row_cap,
+                                     c->lz4_opts.cus));
+        return CRYO_OK;
+    };
+    return decode_pass(c, method, B, n, ps);
+}
+
 /* ---- recompression ----
  * The shared decode loop over the caller's stream table; every decoded chunk is encoded by cryo_codec_compress_batch -- the
  * path of every compress call, so the handle's encode options (segment mode, checksums, verification) apply as they are --
@@ -1898,10 +1978,12 @@ int cryo_codec_fetch_batch(cryo_codec *c, int method, const void *d_src, const u
  * is queued; the call's totals (total_words of them at d_total; none: 0) cleared; and -- unless the call has no block -- the key
  * table of a descriptor with a byte-string key (key_table_device: without such a key nothing more is queued) and the bucket table
  * of a CRYO_GROUP_BUCKETS group descriptor, whose buckets array is read back beside by (bucket_table_device).  *ncols: the
- * aggregate columns.  prj: the call is a projection (grp and agg null); *pt: its column table */
+ * aggregate columns.  prj: the call is a projection (grp and agg null); *pt: its column table.  ord (with prj): the call is an
+ * ordered scan; *tt: its table, and pt is not looked at */
 static int scan_desc_device(cryo_codec *c, const cryo_filter *f, const cryo_group *grp, const cryo_agg *agg, bool need_agg,
                             uint64_t *d_total, size_t total_words, uint64_t n_blocks, ScanDesc &sd, uint32_t *ncols,
-                            const cryo_project *prj = nullptr, ProjectTab *pt = nullptr)
+                            const cryo_project *prj = nullptr, ProjectTab *pt = nullptr, const cryo_order *ord = nullptr,
+                            TopnTab *tt = nullptr)
 {
     if (!f || f->natts == 0 || f->natts > CRYO_FILTER_MAX_ATTS || f->nkeys > CRYO_FILTER_MAX_KEYS || !f->atts ||
         (f->nkeys > 0 && !f->keys) || ((uintptr_t)f->atts & 3u) != 0 || ((uintptr_t)f->keys & 7u) != 0)
@@ -1915,6 +1997,8 @@ static int scan_desc_device(cryo_codec *c, const cryo_filter *f, const cryo_grou
     if ((need_agg && nc == 0) || nc > CRYO_AGG_MAX_COLS || (nc > 0 && (!agg->cols || ((uintptr_t)agg->cols & 7u) != 0)))
         return CRYO_E_ARG;
     if (prj && (prj->ncols == 0 || prj->ncols > CRYO_PROJECT_MAX_COLS || !prj->cols || ((uintptr_t)prj->cols & 7u) != 0)) return CRYO_E_ARG;
+    if (ord && (ord->nby == 0 || ord->nby > CRYO_ORDER_MAX_BY || ord->limit == 0 || !ord->by || ((uintptr_t)ord->by & 7u) != 0)) return CRYO_E_ARG;
+    cryo_order_col ocols[CRYO_ORDER_MAX_BY];
     cryo_att atts[CRYO_FILTER_MAX_ATTS]; /* 6 400 bytes */
     cryo_scan_key keys[CRYO_FILTER_MAX_KEYS];
     cryo_agg_col by[CRYO_GROUP_MAX_BY], cols[CRYO_AGG_MAX_COLS];
@@ -1927,9 +2011,11 @@ static int scan_desc_device(cryo_codec *c, const cryo_filter *f, const cryo_grou
     if (d_bk) HIP_TRY(c, hipMemcpyAsync(bk, d_bk, grp->nby * sizeof(cryo_bucket), hipMemcpyDeviceToHost, c->stream));
     if (nc) HIP_TRY(c, hipMemcpyAsync(cols, agg->cols, nc * sizeof(cryo_agg_col), hipMemcpyDeviceToHost, c->stream));
     if (prj) HIP_TRY(c, hipMemcpyAsync(pcols, prj->cols, prj->ncols * sizeof(cryo_project_col), hipMemcpyDeviceToHost, c->stream));
+    if (ord) HIP_TRY(c, hipMemcpyAsync(ocols, ord->by, ord->nby * sizeof(cryo_order_col), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     *ncols = nc;
-    const bool ok = prj        ? project_desc_ok(f, atts, keys, prj, pcols, &sd.max_att, pt)
+    const bool ok = ord        ? topn_desc_ok(f, atts, keys, ord, ocols, prj, pcols, &sd.max_att, tt)
+                    : prj      ? project_desc_ok(f, atts, keys, prj, pcols, &sd.max_att, pt)
                     : grp      ? group_desc_ok(f, atts, keys, grp, by, d_bk ? bk : nullptr, agg, cols, &sd.max_att, ncols)
                     : need_agg ? agg_desc_ok(f, atts, keys, agg, cols, &sd.max_att)
                                : filter_desc_ok(f, atts, keys, &sd.max_att);
@@ -2029,6 +2115,25 @@ int cryo_codec_project_batch(cryo_codec *c, int method, const void *d_src, const
         if (rc != CRYO_OK || n_blocks == 0) return rc;
         io.d_blocks = d_blocks; io.d_rows = d_rows; io.row_cap = row_cap; io.d_rec = d_rec; io.rec_cap = rec_cap; io.d_total = d_total;
         return project_pass(c, method, (const uint8_t *)d_src, d_src_off, d_src_size, block_size, n_blocks, io);
+    });
+}
+
+int cryo_codec_topn_batch(cryo_codec *c, int method, const void *d_src, const uint64_t *d_src_off, const uint32_t *d_src_size,
+                          uint32_t block_size, uint64_t n_blocks, const cryo_filter *f, const cryo_order *ord, const cryo_project *prj,
+                          void *d_rows, cryo_topn_rec *d_rec, uint64_t row_cap, cryo_topn_block *d_blocks, uint64_t *d_total)
+{
+    DevGuard dev_(c);
+    if (!c || !method_ok(method) || !check_block_size_ok(block_size)) return CRYO_E_ARG;
+    if (!d_total || ((uintptr_t)d_total & 7u) != 0 || !prj || !ord) return CRYO_E_ARG;
+    if ((((uintptr_t)d_rows | (uintptr_t)d_rec) & 7u) != 0 || ((uintptr_t)d_blocks & 15u) != 0) return CRYO_E_ARG;
+    if (n_blocks > 0 && (!d_src || !d_src_off || !d_src_size || !d_blocks || ((!d_rows || !d_rec) && row_cap > 0))) return CRYO_E_ARG;
+    return guarded([&] {
+        TopnIo io;
+        uint32_t ncols = 0;
+        const int rc = scan_desc_device(c, f, nullptr, nullptr, false, d_total, 1, n_blocks, io.sd, &ncols, prj, nullptr, ord, &io.tt);
+        if (rc != CRYO_OK || n_blocks == 0) return rc;
+        io.d_blocks = d_blocks; io.d_rows = d_rows; io.d_rec = d_rec; io.row_cap = row_cap; io.d_total = d_total;
+        return topn_pass(c, method, (const uint8_t *)d_src, d_src_off, d_src_size, block_size, n_blocks, io);
     });
 }
 
@@ -2957,6 +3062,76 @@ int cryo_codec_project_blocks(cryo_codec *c, int method, const void *const *h_sr
     });
 }
 
+/* what every host-buffer ordered-scan call checks before a device is touched */
+static int topn_blocks_args(int method, size_t block_size, const cryo_filter *f, const cryo_order *ord, const cryo_project *prj,
+                            uint64_t *h_total, uint32_t *max_att, TopnTab *tt)
+{
+    if (!method_ok(method) || !check_block_size_ok(block_size) || !h_total) return CRYO_E_ARG;
+    if (!f || !ord || !prj || ((uintptr_t)ord->by & 7u) != 0 || !topn_desc_ok(f, f->atts, f->keys, ord, ord->by, prj, prj->cols, max_att, tt))
+        return CRYO_E_ARG;
+    return CRYO_OK;
+}
+
+/* the ordered scan of n streams given by pointer: the streams staged and uploaded as the projection's (stage_streams), the
+ * descriptors -- the order columns and the projected columns as the kernel's table -- from the same pinned buffer in a second copy,
+ * both into place before the first decode; the block table of the whole call comes back after the last chunk (topn_pass waits for
+ * nothing here), then -- their number known from the last row -- its records and rows.  w_base: what row_first counts from (a
+ * multi-GPU share's region within the caller's buffers); *h_total is relative to h_rows / h_rec as given here */
+static int topn_blocks_impl(cryo_codec *c, int method, const void *const *h_src, const uint32_t *h_src_size, size_t n, size_t block_size,
+                            const cryo_filter *f, const cryo_order *ord, const cryo_project *prj, void *h_rows, cryo_topn_rec *h_rec,
+                            size_t row_cap, uint64_t w_base, cryo_topn_block *h_blocks, uint64_t *h_total)
+{
+    uint32_t max_att = 0;
+    TopnIo io;
+    int rc = topn_blocks_args(method, block_size, f, ord, prj, h_total, &max_att, &io.tt);
+    if (rc != CRYO_OK || !c) return CRYO_E_ARG;
+    DevGuard dev_(c);
+    *h_total = 0;
+    if (n == 0) return CRYO_OK;
+    if (!h_src || !h_src_size || !h_blocks || ((!h_rows || !h_rec) && row_cap > 0)) return CRYO_E_ARG;
+    ScopedLocalCpus numa_(c, n, block_size);
+    /* the descriptor with the kernel's table [8 x 10] as its extra bytes, then the results: [total 16][table 32 x n]
+     * [records 24 x cap][rows row_bytes x cap], each part 8-byte aligned, the table 16; cap: what the caller has room for, at most
+     * the worst case */
+    const size_t worst = n * (size_t)topn_per_block(io.tt.limit, cryo::filter_side_stride((uint32_t)block_size)), rb = io.tt.row_bytes;
+    const size_t cap = row_cap < worst ? row_cap : worst;
+    const ScanDescLayout L = scan_desc_layout(f, (sizeof io.tt.slots + 15) & ~(size_t)15);
+    const size_t t_total = L.bytes, t_table = t_total + 16, table_bytes = n * sizeof(cryo_topn_block);
+    const size_t t_recs = t_table + table_bytes, t_rows = t_recs + cap * sizeof(cryo_topn_rec);
+    if ((rc = ensure(c, &c->hb_meta, &c->hb_meta_cap, t_rows + cap * rb + 64)) != CRYO_OK) return rc;
+    StagedStreams sg;
+    if ((rc = scan_desc_upload(c, h_src, h_src_size, n, f, max_att, L, io.tt.slots, sg, io.sd)) != CRYO_OK) return rc;
+    io.d_tab = c->hb_meta + L.t_extra;
+    io.d_total = (uint64_t *)(c->hb_meta + t_total);
+    io.d_blocks = (cryo_topn_block *)(c->hb_meta + t_table);
+    io.d_rec = (cryo_topn_rec *)(c->hb_meta + t_recs);
+    io.d_rows = c->hb_meta + t_rows;
+    io.row_cap = cap;
+    rc = topn_pass(c, method, c->hb_src, (const uint64_t *)(c->hb_src + sg.o_off), (const uint32_t *)(c->hb_src + sg.o_sz),
+                   (uint32_t)block_size, n, io);
+    rc = read_back(c, rc, {h_blocks, io.d_blocks, table_bytes}, {}, "hipMemcpyAsync of the block table");
+    if (rc != CRYO_OK) return rc;
+    const cryo_topn_block &last = h_blocks[n - 1];
+    if (last.row_first > worst || last.n_rows > worst - last.row_first) return CRYO_E_HIP; /* not a placement */
+    const uint64_t rows = last.row_first + last.n_rows;
+    *h_total = rows;
+    if (rows > row_cap) return CRYO_E_DSTSIZE;
+    if (rows)
+        rc = read_back(c, rc, {h_rec, io.d_rec, rows * sizeof(cryo_topn_rec)}, {h_rows, io.d_rows, rows * rb}, "hipMemcpyAsync of records and rows");
+    if (rc == CRYO_OK && w_base)
+        for (size_t i = 0; i < n; i++) h_blocks[i].row_first += w_base;
+    return rc;
+}
+
+int cryo_codec_topn_blocks(cryo_codec *c, int method, const void *const *h_src, const uint32_t *h_src_size, size_t n, size_t block_size,
+                           const cryo_filter *f, const cryo_order *ord, const cryo_project *prj, void *h_rows, cryo_topn_rec *h_rec,
+                           size_t row_cap, cryo_topn_block *h_blocks, uint64_t *h_total)
+{
+    return host_call(c, [&] {
+        return topn_blocks_impl(c, method, h_src, h_src_size, n, block_size, f, ord, prj, h_rows, h_rec, row_cap, 0, h_blocks, h_total);
+    });
+}
+
 } /* extern "C" */
 
 /* ---- device-resident block pool ---- */
@@ -3557,6 +3732,40 @@ int cryo_multi_project_blocks(cryo_multi *m, int method, const void *const *h_sr
     if (rc != CRYO_OK) return rc;
     h_total[0] = cryo::last_end(end_w);
     h_total[1] = cryo::last_end(end_r);
+    return CRYO_OK;
+}
+
+/* block i -> handle i mod G; handle g ranks its share, in block order, into one region of min(limit, 290) * (its blocks) entries of
+ * rows and records alike, the regions in handle order; the table comes back in call order with row_first counting from h_rows */
+int cryo_multi_topn_blocks(cryo_multi *m, int method, const void *const *h_src, const uint32_t *h_src_size, size_t n, size_t block_size,
+                           const cryo_filter *f, const cryo_order *ord, const cryo_project *prj, void *h_rows, cryo_topn_rec *h_rec,
+                           size_t row_cap, cryo_topn_block *h_blocks, uint64_t *h_total)
+{
+    uint32_t max_att = 0;
+    TopnTab tt;
+    if (!m || m->h.empty() || topn_blocks_args(method, block_size, f, ord, prj, h_total, &max_att, &tt) != CRYO_OK) return CRYO_E_ARG;
+    const size_t G = m->h.size();
+    if (G == 1) return cryo_codec_topn_blocks(m->h[0], method, h_src, h_src_size, n, block_size, f, ord, prj, h_rows, h_rec, row_cap, h_blocks, h_total);
+    *h_total = 0;
+    if (n == 0) return CRYO_OK;
+    if (!h_src || !h_src_size || !h_blocks || ((!h_rows || !h_rec) && row_cap > 0)) return CRYO_E_ARG;
+    const cryo::RoundRobin deal{n, G};
+    const uint64_t per_block = topn_per_block(tt.limit, cryo::kHeapMaxItems);
+    std::vector<uint64_t> end_w(G, 0);
+    const int rc = multi_run(m, n, [&](cryo_codec *c, size_t g, const std::vector<size_t> &idx) {
+        const cryo::ShareRegion rows(row_cap, deal.before(g), idx.size(), per_block);
+        const ShareStreams in(h_src, h_src_size, idx);
+        std::vector<cryo_topn_block> table(idx.size());
+        uint64_t tot = 0;
+        const int r = topn_blocks_impl(c, method, in.src.data(), in.sz.data(), idx.size(), block_size, f, ord, prj,
+                                       rows.in((uint8_t *)h_rows, tt.row_bytes), rows.in(h_rec), rows.cap, rows.first, table.data(), &tot);
+        if (r != CRYO_OK) return r;
+        cryo::scatter(idx, table.data(), h_blocks);
+        end_w[g] = rows.end(tot);
+        return (int)CRYO_OK;
+    });
+    if (rc != CRYO_OK) return rc;
+    *h_total = cryo::last_end(end_w);
     return CRYO_OK;
 }
 

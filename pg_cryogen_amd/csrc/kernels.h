@@ -335,6 +335,24 @@ hipError_t launch_project(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stri
                           uint32_t ncols, uint32_t row_bytes, uint32_t max_att, uint32_t truth, bool floats, uint4 *d_blocks, void *d_side_rec,
                           void *d_side_rows, uint64_t *d_running, void *d_rec, uint64_t rec_cap, void *d_rows, uint64_t row_cap, int cus);
 
+/* the ordered scan (topn.hip) on one decoded chunk of cnt blocks (laid out as for launch_filter): k_topn_block, k_topn_offsets,
+ * k_topn_copy.  The descriptors are validated by the caller (cryo_codec.cpp, topn_desc_ok): d_atts and d_keys as for
+ * launch_filter; d_slots the staged table, ten entries of 8 bytes (device memory, 8-byte aligned): entries 0 .. 1 the nby (1 .. 2)
+ * order columns {u16 att, u8 type (CRYO_KEY_INT2 .. _INT8, _FLOAT4, _FLOAT8), u8 flags (CRYO_ORDER_*), u32 0}, entries 2 .. 9
+ * launch_project's column table of ncols (1 .. 8) columns, every unused entry all zero, and h_slots the host's copy of the ten
+ * (what the block kernel needs of them after the walk travels as kernel arguments); row_bytes as for launch_project; limit
+ * >= 1; max_att the highest key, order or projected column; truth and floats as for launch_filter (k_topn_block<true> / <false>,
+ * k_topnf_block for a float scan key; an undecided tuple counts in n_bad and is in no ranking).  d_blocks: the chunk's rows of the
+ * block table (cryo_topn_block, 16-byte aligned).  Scratch, per possible item (cnt * filter_side_stride(block_size) items):
+ * d_side_rec 24 bytes and d_side_rows row_bytes bytes (both 8-byte aligned), d_side_ord 4 bytes.  *d_running: the kept rows before
+ * the chunk in, after it out.  The chunk's records go to d_rec and its rows to d_rows (8-byte aligned) at row_first within the
+ * call; nothing at or beyond row_cap is written.  cus as for launch_fetch. */
+hipError_t launch_topn(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
+                       const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,
+                       const void *h_slots, uint32_t nby, uint32_t ncols, uint32_t row_bytes, uint32_t limit, uint32_t max_att,
+                       uint32_t truth, bool floats, uint4 *d_blocks, void *d_side_rec, void *d_side_rows, void *d_side_ord,
+                       uint64_t *d_running, void *d_rec, void *d_rows, uint64_t row_cap, int cus);
+
 } // namespace cryo
 
 #define CRYO_WAVE 64

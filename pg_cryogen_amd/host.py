@@ -42,6 +42,8 @@ GROUP_BLOCKS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p
 PROJECT_BLOCKS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_size_t,
                                 C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
                                 C.POINTER(C.c_uint64))
+TOPN_BLOCKS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_size_t, C.c_size_t,
+                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_uint64))
 CRYO_CHECK_CHAIN, CRYO_CHECK_METHOD = 16, 17   # host-only reasons of check.h (beside cryo_check_reason 0..4)
 
 
@@ -95,6 +97,12 @@ class CryoCodecProjectOps(C.Structure):
     """host/compression.h's one-function table of the projecting scan (PROJECT_BLOCKS_FN), bound beside a CryoCodecOps double
     with cryo_host_set_project_ops (test build)"""
     _fields_ = [("project_blocks", PROJECT_BLOCKS_FN)]
+
+
+class CryoCodecTopnOps(C.Structure):
+    """host/compression.h's one-function table of the ordered scan (TOPN_BLOCKS_FN), bound beside a CryoCodecOps double with
+    cryo_host_set_topn_ops (test build)"""
+    _fields_ = [("topn_blocks", TOPN_BLOCKS_FN)]
 
 
 class CryoRel(C.Structure):
@@ -179,6 +187,23 @@ class CryoProjectTotals(C.Structure):
                                           "bytes_back")]
 
 
+class CryoTopnBlock(C.Structure):
+    _fields_ = [("block", C.c_uint32), ("created_xid", C.c_uint32), ("n_items", C.c_uint32), ("n_match", C.c_uint32),
+                ("n_bad", C.c_uint32), ("n_rows", C.c_uint32), ("rec", C.c_void_p), ("rows", C.c_void_p), ("row_bytes", C.c_uint32)]
+
+
+class CryoTopnTotals(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("blocks", "empty_pages", "items", "matches", "bad", "reports", "codec_calls",
+                                          "bytes_back", "rows")]
+
+
+class CryoTopnMerge(C.Structure):
+    """host/topn.h's merge state: by (2 x cryo_order_col), nby, limit, row_bytes, n, rec, rows"""
+    _fields_ = [("by", C.c_uint64 * 2), ("nby", C.c_uint32), ("limit", C.c_uint32), ("row_bytes", C.c_uint32), ("n", C.c_uint32),
+                ("rec", C.c_void_p), ("rows", C.c_void_p)]
+
+
+TOPN_BLOCK_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(CryoTopnBlock))
 PROJECT_ROW_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(CryoProjectedRow))
 AGG_BLOCK_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(CryoAggBlock))
 GROUP_BLOCK_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(CryoGroupBlock))
@@ -243,6 +268,11 @@ def lib():
         L.cryo_host_set_project_ops.restype = None
         L.cryo_project_set_window.argtypes = [i32, sz]
         L.cryo_project_set_window.restype = None
+    if hasattr(L, "cryo_host_set_topn_ops"):     # test build only
+        L.cryo_host_set_topn_ops.argtypes = [C.POINTER(CryoCodecTopnOps)]
+        L.cryo_host_set_topn_ops.restype = None
+        L.cryo_topn_set_window.argtypes = [i32, sz]
+        L.cryo_topn_set_window.restype = None
     L.cryo_host_codec_error.restype = C.c_char_p
     L.cryo_compat_set_error_handler.argtypes = [ERROR_HANDLER]
     L.cryo_compat_set_error_handler.restype = None
@@ -315,6 +345,13 @@ def lib():
     L.cryo_group_scan.argtypes = [C.POINTER(CryoRel), vp, vp, vp, GROUP_BLOCK_FN, FETCH_REPORT_FN, vp, C.POINTER(CryoGroupTotals)]
     # CryoProjectReport has the layout of the fetch's CryoFetchReport
     L.cryo_project_scan.argtypes = [C.POINTER(CryoRel), vp, vp, PROJECT_ROW_FN, FETCH_REPORT_FN, vp, C.POINTER(CryoProjectTotals)]
+    L.cryo_topn_scan.argtypes = [C.POINTER(CryoRel), vp, vp, vp, TOPN_BLOCK_FN, FETCH_REPORT_FN, vp, C.POINTER(CryoTopnTotals)]
+    L.cryo_topn_merge_init.argtypes = [C.POINTER(CryoTopnMerge), vp, C.c_uint32, C.c_uint32]
+    L.cryo_topn_merge_add.argtypes = [C.POINTER(CryoTopnMerge), vp, vp, C.c_uint32]
+    L.cryo_topn_merge_finish.argtypes = [C.POINTER(CryoTopnMerge), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.cryo_topn_merge_finish.restype = C.c_uint32
+    L.cryo_topn_merge_free.argtypes = [C.POINTER(CryoTopnMerge)]
+    L.cryo_topn_merge_free.restype = None
     for n in ("cryo_cache_hits", "cryo_cache_misses", "cryo_cache_codec_calls"):
         getattr(L, n).restype = C.c_uint64
     _libs[prod] = L
@@ -526,6 +563,67 @@ def project_scan(rel, atts, keys, cols, truth=None):
     if rc != 0:
         raise ProjectScanError(rc, events, totals)
     return events, totals
+
+
+class TopnScanError(RuntimeError):
+    def __init__(self, code, events, totals):
+        self.code, self.events, self.totals = code, events, totals
+        super().__init__("cryo_topn_scan failed: %d" % code)
+
+
+def topn_scan(rel, atts, keys, by, limit, cols, truth=None):
+    """cryo_topn_scan (host/topn.h) with the descriptors codec.filter_desc, codec.order_desc and codec.project_desc make of atts
+    [(attlen, attalign)], keys [(att, type, op, value)], by [(att, type, flags)] and cols [att].  Returns (events, totals): events
+    in delivery order, ("block", block, created_xid, (n_items, n_match, n_bad), records: a TOPN_REC array, rows: a uint8 array of
+    shape (n_rows, row_bytes)) or ("report", block, reason, detail); totals a dict.  A nonzero status raises TopnScanError (which
+    carries what was delivered)."""
+    import numpy as np
+    from . import codec
+    desc, odesc, pdesc = codec.filter_desc(atts, keys, 0, truth), codec.order_desc(by, limit), codec.project_desc(cols)
+    events = []
+
+    def on_block(arg, b):
+        b = b.contents
+        recs = np.frombuffer(C.string_at(b.rec, 24 * b.n_rows), codec.TOPN_REC).copy() if b.n_rows else np.zeros(0, codec.TOPN_REC)
+        rows = np.frombuffer(C.string_at(b.rows, b.row_bytes * b.n_rows), np.uint8).reshape(b.n_rows, b.row_bytes).copy() \
+            if b.n_rows else np.zeros((0, b.row_bytes), np.uint8)
+        events.append(("block", b.block, b.created_xid, (b.n_items, b.n_match, b.n_bad), recs, rows))
+
+    bcb = TOPN_BLOCK_FN(on_block)
+    rcb = FETCH_REPORT_FN(lambda arg, r: events.append(("report", r.contents.block, r.contents.reason, r.contents.detail)))
+    t = CryoTopnTotals()
+    rc = lib().cryo_topn_scan(C.byref(rel), C.byref(desc[0]), C.byref(odesc[0]), C.byref(pdesc[0]), bcb, rcb, None, C.byref(t))
+    totals = {f: getattr(t, f) for f, _ in CryoTopnTotals._fields_}
+    if rc != 0:
+        raise TopnScanError(rc, events, totals)
+    return events, totals
+
+
+def topn_merge(by, limit, blocks):
+    """host/topn.h's merge (cryo_topn_merge_init / _add / _finish / _free) over blocks, a sequence of (TOPN_REC array, rows of
+    shape (n, row_bytes)) in the order they are added: (records, rows) of the first `limit` rows"""
+    import numpy as np
+    from . import codec
+    L = lib()
+    row_bytes = next((np.asarray(rows).shape[1] for _, rows in blocks if len(rows)), 8)
+    odesc = codec.order_desc(by, limit)
+    m = CryoTopnMerge()
+    rc = L.cryo_topn_merge_init(C.byref(m), C.byref(odesc[0]), limit, row_bytes)
+    if rc != 0:
+        raise RuntimeError("cryo_topn_merge_init failed: %d" % rc)
+    try:
+        for recs, rows in blocks:
+            recs, rows = np.ascontiguousarray(recs, codec.TOPN_REC), np.ascontiguousarray(rows, np.uint8)
+            rc = L.cryo_topn_merge_add(C.byref(m), recs.ctypes.data if len(recs) else None, rows.ctypes.data if len(recs) else None, len(recs))
+            if rc != 0:
+                raise RuntimeError("cryo_topn_merge_add failed: %d" % rc)
+        rp, wp = C.c_void_p(), C.c_void_p()
+        n = L.cryo_topn_merge_finish(C.byref(m), C.byref(rp), C.byref(wp))
+        out_rec = np.frombuffer(C.string_at(rp, 24 * n), codec.TOPN_REC).copy() if n else np.zeros(0, codec.TOPN_REC)
+        out_rows = np.frombuffer(C.string_at(wp, row_bytes * n), np.uint8).reshape(n, row_bytes).copy() if n else np.zeros((0, row_bytes), np.uint8)
+        return out_rec, out_rows
+    finally:
+        L.cryo_topn_merge_free(C.byref(m))
 
 
 def transfer_counters():

@@ -169,6 +169,18 @@ static const CryoCodecProjectOps *bound_project_ops; /* the project table of a b
 void cryo_host_set_project_ops(const CryoCodecProjectOps *ops) { bound_project_ops = ops; }
 #endif
 const CryoCodecProjectOps *cryo_host_project_ops(void) { return bound_ops ? bound_project_ops : &hip_project_ops; }
+static int hip_topn_blocks(void *ctx, int method, const void *const *src, const uint32_t *sz, size_t n, size_t bs, const void *filter,
+                           const void *order, const void *project, void *rows, void *rec, size_t row_cap, void *blocks, uint64_t *total)
+{
+    return cryo_multi_topn_blocks((cryo_multi *)ctx, method, src, sz, n, bs, (const cryo_filter *)filter, (const cryo_order *)order,
+                                  (const cryo_project *)project, rows, (cryo_topn_rec *)rec, row_cap, (cryo_topn_block *)blocks, total);
+}
+static const CryoCodecTopnOps hip_topn_ops = {hip_topn_blocks};
+static const CryoCodecTopnOps *bound_topn_ops; /* the topn table of a bound double (CRYO_HOST_TEST_HOOKS builds only) */
+#ifdef CRYO_HOST_TEST_HOOKS
+void cryo_host_set_topn_ops(const CryoCodecTopnOps *ops) { bound_topn_ops = ops; }
+#endif
+const CryoCodecTopnOps *cryo_host_topn_ops(void) { return bound_ops ? bound_topn_ops : &hip_topn_ops; }
 const char *cryo_host_codec_error(void) { return codec_err; }
 
 const CryoCodecOps *cryo_host_codec_ops(void)

@@ -169,6 +169,20 @@ const CryoCodecProjectOps *cryo_host_project_ops(void);
 #ifdef CRYO_HOST_TEST_HOOKS
 void cryo_host_set_project_ops(const CryoCodecProjectOps *ops); /* test builds only: the project table of the bound double, or NULL */
 #endif
+/* the ordered scan (topn.h, cryo_topn_scan) is bound through a table of its own as well.  topn_blocks is cryo_multi_topn_blocks
+ * (include/cryo_codec.h): filter is a const cryo_filter *, order a const cryo_order * and project a const cryo_project *, all with
+ * host arrays; rows gets up to row_cap rows of row_bytes and rec as many cryo_topn_rec (24 bytes), blocks one cryo_topn_block (32
+ * bytes) per stream in call order, *total the end of the last entry used */
+typedef struct CryoCodecTopnOps {
+    int (*topn_blocks)(void *ctx, int method, const void *const *src, const uint32_t *src_size, size_t n, size_t block_size,
+                       const void *filter, const void *order, const void *project, void *rows, void *rec, size_t row_cap,
+                       void *blocks, uint64_t *total);
+} CryoCodecTopnOps;
+/* the topn table that goes with cryo_host_codec_ops(): production's binds the GPU codec; NULL when a bound double has none */
+const CryoCodecTopnOps *cryo_host_topn_ops(void);
+#ifdef CRYO_HOST_TEST_HOOKS
+void cryo_host_set_topn_ops(const CryoCodecTopnOps *ops); /* test builds only: the topn table of the bound double, or NULL */
+#endif
 const CryoCodecOps *cryo_host_codec_ops(void);         /* lazily opens the GPU codec */
 void cryo_host_codec_trim(void);                         /* idle backend: free the binding's device workspace and staging buffers */
 size_t cryo_host_codec_bound(int method, size_t n);      /* cryo_codec_bound (or the bound double's): never opens the GPU */
