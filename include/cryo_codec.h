@@ -650,8 +650,9 @@ int cryo_codec_agg_batch(cryo_codec *c, int method, const void *d_src, const uin
  *
  * Descriptors.  CRYO_E_ARG when: *f breaks one of the filter's descriptor rules above; f->flags is neither 0 nor CRYO_FILTER_TRUTH; nby is 0 or above 2; a
  * group column breaks a rule of an aggregate column above (att outside 1 .. f->natts; a type that is not a cryo_key_type; the
- * column's attlen not the type's size, or its attalign below its attlen; rsv or rsv2 not zero); grp->rsv neither zero nor
- * CRYO_GROUP_BUCKETS ("Bucketed group columns" below); ncols above 4;
+ * column's attlen not the type's size, or its attalign below its attlen; rsv or rsv2 not zero); grp->rsv none of zero,
+ * CRYO_GROUP_BUCKETS ("Bucketed group columns" below) and CRYO_GROUP_TEXT ("Text group columns" below, which alone lets a group
+ * column be a byte string); ncols above 4;
  * with ncols > 0, anything cryo_codec_agg_batch refuses in *agg.  ncols == 0 is allowed here -- agg NULL, or agg->ncols 0 with
  * agg->rsv 0 (agg->cols is not looked at) --: SELECT g, count(*) ... GROUP BY g needs no cell.  A column may be a group column,
  * an aggregate column and a key column at once, and may be named twice.
@@ -713,7 +714,7 @@ typedef struct { int64_t key[2]; uint32_t n_rows, nulls; } cryo_group_rec;      
  * kind of key beside the grouping.  A column may be a bucketed group column, a raw aggregate column and a key at once (min(ts),
  * max(ts) per day), and may be named twice with two different buckets (hour and day).  With every kind CRYO_BUCKET_NONE the
  * result is byte for byte that of the rsv == 0 call.
- * CRYO_E_ARG when: grp->rsv is neither 0 nor 1; buckets is null or not 8-byte aligned; a kind is unknown; WIDTH with value < 1 or
+ * CRYO_E_ARG when: grp->rsv is neither 0 nor 1 (4: "Text group columns" below, without buckets); buckets is null or not 8-byte aligned; a kind is unknown; WIDTH with value < 1 or
  * n != 0; BOUNDS with n == 0, n > CRYO_BUCKET_BOUNDS_MAX, a null address or origin != 0; NONE with flags, n, origin or value not
  * 0; an unknown flag bit, or CRYO_BUCKET_INFINITE with NONE; a bucket's rsv not 0. */
 #define CRYO_GROUP_BUCKETS 1u          /* cryo_group.rsv: the struct is a cryo_group_b */
@@ -724,13 +725,45 @@ typedef struct { int64_t key[2]; uint32_t n_rows, nulls; } cryo_group_rec;      
 #define CRYO_BUCKET_BOUNDS_MAX 1024u   /* the most boundaries of a list: CRYO_KEY_SET_MAX */
 typedef struct { uint8_t kind, flags; uint16_t rsv; uint32_t n; int64_t origin; int64_t value; } cryo_bucket; /* 24 bytes, one per group column */
 typedef struct { uint32_t nby, rsv; const cryo_agg_col *by; const cryo_bucket *buckets; } cryo_group_b;       /* 24 bytes; rsv = CRYO_GROUP_BUCKETS */
+/* Text group columns: SELECT country, count(*), sum(revenue) ... GROUP BY country.  cryo_group keeps its 16 bytes and its meaning:
+ * with rsv == 0 or rsv == CRYO_GROUP_BUCKETS a call is what it was, byte for byte, and a group column of type CRYO_KEY_BYTES is
+ * CRYO_E_ARG there.  With rsv == CRYO_GROUP_TEXT (4) the struct is still a cryo_group, and
+ *   Columns.  A group column's type may be CRYO_KEY_BYTES, on a varlena column (attlen == -1: the column rule of a byte-string
+ *     key; rsv and rsv2 zero, att in 1 .. f->natts).  The other group column, if there is one, may be an integer type or
+ *     CRYO_KEY_BYTES too.  CRYO_KEY_BYTES stays refused as an aggregate column.  With integer group columns only the flag is legal
+ *     and the call returns exactly the bytes of the rsv == 0 call.  ntext below: the group columns of type CRYO_KEY_BYTES, 0 .. 2.
+ *   Value.  A non-NULL value's key is its in-line payload, 0 .. CRYO_GROUP_TEXT_MAX (32) bytes: the bytes behind a 1-byte header
+ *     or behind an uncompressed 4-byte header.  '' is a value, not NULL.  Undecided are: an on-disk TOAST pointer, a value
+ *     compressed in line, and a payload above CRYO_GROUP_TEXT_MAX bytes.  A tuple that passes the keys but has an undecided value in
+ *     any text group column is counted in n_bad and not in n_match, and is in no group and no cell -- the rule of an undecided
+ *     bucket --, so a block's n_rows still sum to its n_match and the caller reads a block with n_bad > 0 through the filter.  A
+ *     tuple that fails the keys is a non-match, whatever its group value.
+ *   Order within a block.  As without the flag: column 1, then column 2, NULLS LAST.  A text column orders by memcmp on unsigned
+ *     bytes over the shorter length, then by length: the order of the byte-string keys ("ab" < "ab\0" < "abc").  Equal keys are
+ *     equal byte strings, so the grouping is exact under any deterministic collation (there equal strings are equal bytes); the
+ *     order of a block's groups is the collation's order under "C" only, and a caller that merges blocks by hashing needs none.
+ *   Results.  Rows and records keep their layout.  For a text column j, key[j] is the value's length in bytes, or 0 when it is
+ *     NULL; bit j of nulls as without the flag.  The bytes come back in the cells array: a group has ncols + ntext cells of 40
+ *     bytes, the ncols aggregate cells as without the flag, then one cryo_group_key per text group column in column order -- cell
+ *     (first_group + g) * (ncols + ntext) + ncols + t for the t-th text column.  A cryo_group_key holds the payload in bytes[0 ..
+ *     len), zeros behind it, len, and rsv 0; a NULL's is all zero.  Wherever the rules of a group call say ncols for the number or
+ *     the place of cells, read ncols + ntext: the capacity of d_cells / h_cells (group_cap * (ncols + ntext) cells), the rule that
+ *     the cells pointer may be null (only when ncols + ntext == 0), the side area (24 + 40 * (ncols + ntext) bytes per possible
+ *     group), the cut-off at group_cap, and what crosses PCIe.
+ * Everything else is unchanged: first_group, group_cap, *total, chunking, float aggregate columns and every kind of key beside
+ * the grouping -- a byte-string key on the group column itself included.
+ * CRYO_E_ARG when: grp->rsv is none of 0, CRYO_GROUP_BUCKETS and CRYO_GROUP_TEXT -- both flags together (5) included: a call
+ * has buckets or text columns --; a CRYO_KEY_BYTES group column on a column whose attlen is not -1, or without the flag. */
+#define CRYO_GROUP_TEXT 4u             /* cryo_group.rsv: group columns may be CRYO_KEY_BYTES */
+#define CRYO_GROUP_TEXT_MAX 32u        /* the longest payload that is a key */
+typedef struct { uint8_t bytes[32]; uint32_t len, rsv; } cryo_group_key; /* 40 bytes: a text group column's cell */
 /* Device buffers.  The structs *f, *grp and *agg are host memory; f->atts, f->keys, grp->by and agg->cols are DEVICE arrays (4-byte
  * / 8-byte / 8-byte / 8-byte aligned).  The host validates the descriptors before anything is queued: it reads the arrays back on
  * the handle's stream (one wait for what the stream held before the call); from there on the call is asynchronous, with no host
  * wait between its internal chunks.  d_blocks (n_blocks rows) 16-byte, d_groups (group_cap records) 8-byte, d_cells (group_cap *
- * ncols cells; may be NULL only when ncols == 0) 8-byte, d_total (one u64, also where the running total lives between the call's
+ * ncols cells; may be NULL only when ncols == 0; under CRYO_GROUP_TEXT ncols + ntext in both places) 8-byte, d_total (one u64, also where the running total lives between the call's
  * internal chunks) 8-byte aligned: CRYO_E_ARG otherwise.  Decode as in the filter: the automatic routes, handle workspace, chunks
- * within CRYO_OPT_WORKSPACE_MAX_BYTES (the workspace also holds a side area of 24 + 40 * ncols bytes per possible group of a chunk:
+ * within CRYO_OPT_WORKSPACE_MAX_BYTES (the workspace also holds a side area of 24 + 40 * ncols bytes -- under CRYO_GROUP_TEXT 24 + 40 * (ncols + ntext) -- per possible group of a chunk:
  * up to 290 per block); the device pool is neither read nor filled, nothing counts in cryo_codec_counters.  CRYO_E_ARG as for
  * cryo_codec_filter_batch (the same block-size rule), a bad descriptor, a null d_total, a null d_blocks, and a null d_groups or
  * (with ncols > 0) a null d_cells with group_cap > 0; n_blocks == 0: CRYO_OK, *d_total = 0, nothing else is written. */
@@ -979,7 +1012,7 @@ int cryo_codec_agg_blocks(cryo_codec *c, int method, const void *const *h_src, c
  *   Return   after the last chunk the rows of the whole call, then -- their number known from the last row -- exactly the call's
  *            records and cells (two waits): d2h_bytes grows by exactly 32 * n_blocks + (24 + 40 * ncols) * *h_total.
  *   Errors   more groups than group_cap: CRYO_E_DSTSIZE, and the outputs hold nothing to rely on (group_cap >= 290 * n_blocks
- *            always fits).  CRYO_E_ARG as cryo_codec_group_batch (h_cells may be NULL only when ncols == 0); a bad descriptor is
+ *            always fits).  CRYO_E_ARG as cryo_codec_group_batch (h_cells may be NULL only when ncols == 0 -- under CRYO_GROUP_TEXT, when ncols + ntext == 0); a bad descriptor is
  *            refused before a device is touched.  n_blocks == 0: CRYO_OK, *h_total = 0.
  * Returns CRYO_OK when the batch ran, whatever the rows say. */
 int cryo_codec_group_blocks(cryo_codec *c, int method, const void *const *h_src, const uint32_t *h_src_size,

@@ -74,6 +74,10 @@ GROUP_BUCKETS = 1           # cryo_group.rsv: the struct is a cryo_group_b
 BUCKET_NONE, BUCKET_WIDTH, BUCKET_BOUNDS = 0, 1, 2
 BUCKET_INFINITE = 1         # a bucket's flag: the column type's extremes are -infinity and +infinity, each its own bucket
 BUCKET_BOUNDS_MAX = 1024
+# text group columns: group columns may be KEY_BYTES; a group then has a GROUP_KEY cell per such column behind its AGG_CELLs
+GROUP_TEXT = 4              # cryo_group.rsv
+GROUP_TEXT_MAX = 32         # the longest payload that is a key
+GROUP_KEY = np.dtype([("bytes", "u1", (32,)), ("len", "<u4"), ("rsv", "<u4")])                                   # cryo_group_key
 BUCKET = np.dtype([("kind", "u1"), ("flags", "u1"), ("rsv", "<u2"), ("n", "<u4"), ("origin", "<i8"), ("value", "<i8")])  # cryo_bucket
 # the projecting scan (include/cryo_codec.h): a block's statuses are the aggregate's, a record's the filter's
 PROJECT_MAX_COLS = 8
@@ -513,19 +517,20 @@ def bucket_array(buckets):
     return b, lists, rebase
 
 
-def group_desc(by, buckets=None):
+def group_desc(by, buckets=None, text=False):
     """the group descriptor of a group call as a host array: by a list of (att, type) (att 1-based; type KEY_*).  Returns
     (CryoGroup, by array); the struct points into the array, which the caller keeps alive.  buckets: one (kind, flags, origin,
     value) per group column (bucket_array) -- the struct is then a CryoGroupB, which holds the buckets array and the lists of
-    boundaries it points into (g.bucket_arr, g.bucket_lists)"""
+    boundaries it points into (g.bucket_arr, g.bucket_lists).  text: the struct's rsv is GROUP_TEXT and a column's type may be
+    KEY_BYTES; with buckets as well the library refuses the descriptor"""
     a = np.zeros(max(len(by), 1), AGG_COL)
     for j, (att, typ) in enumerate(by):
         a[j] = (att, typ, 0, 0)
     if buckets is None:
-        return CryoGroup(len(by), 0, a.ctypes.data), a
+        return CryoGroup(len(by), GROUP_TEXT if text else 0, a.ctypes.data), a
     b, lists, rebase = bucket_array(buckets)
     rebase(lists.ctypes.data)
-    g = CryoGroupB(len(by), GROUP_BUCKETS, a.ctypes.data, b.ctypes.data)
+    g = CryoGroupB(len(by), GROUP_BUCKETS | (GROUP_TEXT if text else 0), a.ctypes.data, b.ctypes.data)
     g.bucket_arr, g.bucket_lists = b, lists
     return g, a
 
@@ -534,8 +539,11 @@ def group_blocks_call(fn, handle, chk, method, comps, block_size, desc, gdesc, a
     """cryo_codec_group_blocks / cryo_multi_group_blocks (fn) on a list of host streams with the descriptors filter_desc,
     group_desc and agg_desc made (adesc None: no aggregate column, a null agg and null cells); returns (rows: GROUP_BLOCK array
     in call order, records: GROUP_REC array of the call's groups, cells: AGG_CELL array of shape (groups, ncols), total).
-    group_cap: the room in records (default: the worst case, 290 per block)"""
+    group_cap: the room in records (default: the worst case, 290 per block).  A GROUP_TEXT descriptor (group_desc(text=True))
+    returns a fifth item: the key cells, a GROUP_KEY array of shape (groups, ntext), one column per KEY_BYTES group column"""
     n, ncols = len(comps), adesc[0].ncols if adesc else 0
+    if gdesc[0].rsv == GROUP_TEXT:
+        return _group_text_blocks_call(fn, handle, chk, method, comps, block_size, desc, gdesc, adesc, group_cap)
     arrs = [np.ascontiguousarray(np.asarray(c, dtype=np.uint8)) for c in comps]
     src = (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.nbytes else None for a in arrs])
     szs = (C.c_uint32 * max(n, 1))(*[a.nbytes for a in arrs])
@@ -547,6 +555,38 @@ def group_blocks_call(fn, handle, chk, method, comps, block_size, desc, gdesc, a
     chk(fn(handle, method, src, szs, n, block_size, C.byref(desc[0]), C.byref(gdesc[0]), C.byref(adesc[0]) if adesc else None,
            rows.ctypes.data, recs.ctypes.data, cap, cells.ctypes.data if ncols else None, C.byref(total)), "group_blocks")
     return rows[:n], recs[:total.value], cells[:total.value, :ncols], total.value
+
+
+def group_text_count(gdesc):
+    """how many of a group descriptor's columns are KEY_BYTES"""
+    return sum(1 for c in gdesc[1][:gdesc[0].nby] if int(c["type"]) == KEY_BYTES)
+
+
+def group_cells_split(cells, ncols, ntext):
+    """the cells of a GROUP_TEXT call, shape (groups, ncols + ntext) of 40 bytes each, as (AGG_CELL (groups, ncols), GROUP_KEY
+    (groups, ntext)): copies"""
+    raw = np.ascontiguousarray(cells).view(np.uint8).reshape(len(cells), (ncols + ntext) * 40)
+    agg = np.frombuffer(raw[:, :ncols * 40].tobytes(), AGG_CELL).reshape(len(cells), ncols).copy()
+    key = np.frombuffer(raw[:, ncols * 40:].tobytes(), GROUP_KEY).reshape(len(cells), ntext).copy()
+    return agg, key
+
+
+def _group_text_blocks_call(fn, handle, chk, method, comps, block_size, desc, gdesc, adesc, group_cap):
+    """group_blocks_call for a GROUP_TEXT descriptor: a group has ncols + ntext cells"""
+    n, ncols, ntext = len(comps), adesc[0].ncols if adesc else 0, group_text_count(gdesc)
+    cpg = ncols + ntext
+    arrs = [np.ascontiguousarray(np.asarray(c, dtype=np.uint8)) for c in comps]
+    src = (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.nbytes else None for a in arrs])
+    szs = (C.c_uint32 * max(n, 1))(*[a.nbytes for a in arrs])
+    cap = 290 * n if group_cap is None else group_cap
+    rows = np.zeros(max(n, 1), GROUP_BLOCK)
+    recs = np.zeros(max(cap, 1), GROUP_REC)
+    cells = np.zeros((max(cap, 1), max(cpg, 1), 40), np.uint8)
+    total = C.c_uint64()
+    chk(fn(handle, method, src, szs, n, block_size, C.byref(desc[0]), C.byref(gdesc[0]), C.byref(adesc[0]) if adesc else None,
+           rows.ctypes.data, recs.ctypes.data, cap, cells.ctypes.data if cpg else None, C.byref(total)), "group_blocks")
+    agg, key = group_cells_split(cells[:total.value, :cpg].reshape(total.value, cpg * 40), ncols, ntext)
+    return rows[:n], recs[:total.value], agg, total.value, key
 
 
 def project_desc(cols):
@@ -972,17 +1012,19 @@ class Codec:
         return agg_blocks_call(self.L.cryo_codec_agg_blocks, self.h, self._chk, method, comps, block_size, desc, adesc)
 
     def group_batch(self, method, d_src, d_off, d_sizes, block_size, n, natts, d_atts, nkeys, d_keys, nby, d_by, ncols, d_cols,
-                    d_blocks, d_groups, group_cap, d_cells, d_total, truth=None, buckets=None):
+                    d_blocks, d_groups, group_cap, d_cells, d_total, truth=None, buckets=None, text=False):
         """test the keys on every tuple of the n stored blocks, partition each block's matches by the nby columns d_by names and
         reduce the ncols columns d_cols names per group (both AGG_COL; d_keys: FILTER_KEY, d_atts: FILTER_ATT, device arrays):
         one GROUP_BLOCK row per block in d_blocks, one GROUP_REC per group in d_groups and ncols AGG_CELL per group in d_cells (at
         most group_cap groups are written), the call's number of groups in d_total (u64).  ncols 0: d_cols and d_cells may be
         None.  truth: as for filter_batch.  buckets: a device array of nby BUCKET entries whose lists of boundaries lie in device
-        memory (bucket_array).  Asynchronous once the descriptors are read back."""
+        memory (bucket_array).  text: the descriptor's rsv is GROUP_TEXT: d_by may name KEY_BYTES columns, and a group then has
+        ncols + ntext cells of 40 bytes in d_cells, a GROUP_KEY per such column behind its AGG_CELLs.  Asynchronous once the
+        descriptors are read back."""
         f = CryoFilter(natts, nkeys, *truth_flags(0, truth), d_atts.ptr if d_atts else None, d_keys.ptr if d_keys else None)
-        g = CryoGroup(nby, 0, d_by.ptr if d_by else None)
+        g = CryoGroup(nby, GROUP_TEXT if text else 0, d_by.ptr if d_by else None)
         if buckets is not None:
-            g = CryoGroupB(nby, GROUP_BUCKETS, d_by.ptr if d_by else None, buckets.ptr)
+            g = CryoGroupB(nby, GROUP_BUCKETS | (GROUP_TEXT if text else 0), d_by.ptr if d_by else None, buckets.ptr)
         a = CryoAgg(ncols, 0, d_cols.ptr if d_cols else None)
         self._chk(self.L.cryo_codec_group_batch(self.h, method, d_src.ptr, d_off.ptr, d_sizes.ptr, block_size, n, C.byref(f),
                                                 C.byref(g), C.byref(a), d_blocks.ptr if d_blocks else None,
@@ -993,7 +1035,7 @@ class Codec:
         """group host streams (desc: what filter_desc returns, gdesc: group_desc, adesc: agg_desc or None); returns (rows,
         records, cells, total): block i's groups are records[rows[i]["first_group"]:][:rows[i]["n_groups"]], cells has one row
         per group and one column per aggregate column; cell_sum gives a cell's 128-bit sum.  buckets: as for group_desc, for
-        gdesc's columns"""
+        gdesc's columns.  A gdesc made with text=True returns the key cells as a fifth item (group_blocks_call)"""
         if buckets is not None:
             gdesc = group_desc([(int(c["att"]), int(c["type"])) for c in gdesc[1][:gdesc[0].nby]], buckets)
         return group_blocks_call(self.L.cryo_codec_group_blocks, self.h, self._chk, method, comps, block_size, desc, gdesc, adesc,

@@ -1158,6 +1158,8 @@ struct ScanDesc {
                                                         the truth table's verdict path alone (truth is not 0 then) */
     const void *d_buckets = nullptr;                 /* device: the grouping's bucket table under CRYO_GROUP_BUCKETS (truth is not 0
                                                         then), else null */
+    uint32_t text = 0;                               /* the grouping's: bit j set when group column j is a byte string
+                                                        (CRYO_GROUP_TEXT; truth is not 0 then) */
 };
 struct FilterIo {
     ScanDesc sd;
@@ -1486,7 +1488,8 @@ static int agg_pass(cryo_codec *c, int method, const uint8_t *d_src, const uint6
  * The shared decode loop over the caller's stream table; on every decoded chunk group.hip tests the keys on every tuple, groups
  * each block's matches in LDS and writes the groups to a side area, places the blocks behind the running total -- which stays in
  * device memory (*d_total) from chunk to chunk -- and copies records and cells to their places in the call's output.  Per chunk
- * (own) each block has 24 + 40 * ncols bytes per possible group of side area; the pass's fixed bytes hold the kernel's six column
+ * (own) each block has 24 + 40 * (ncols + ntext) bytes per possible group of side area (ntext: the text group columns, whose key
+ * cells lie behind a group's aggregate cells); the pass's fixed bytes hold the kernel's six column
  * slots when the caller's descriptors come as two arrays.  The pass waits for nothing.  Its decodes count nowhere. */
 namespace {
 struct GroupIo {
@@ -1496,7 +1499,7 @@ struct GroupIo {
     uint32_t nby = 0, ncols = 0;
     cryo_group_block *d_blocks = nullptr; /* device: n rows */
     cryo_group_rec *d_groups = nullptr;   /* device: group_cap records */
-    cryo_agg_cell *d_cells = nullptr;     /* device: group_cap * ncols cells */
+    cryo_agg_cell *d_cells = nullptr;     /* device: group_cap * (ncols + ntext) cells */
     uint64_t group_cap = 0;
     uint64_t *d_total = nullptr;          /* device: the running total */
 };
@@ -1585,19 +1588,30 @@ static int bucket_table_device(cryo_codec *c, const cryo_bucket *bk, uint32_t nb
     return CRYO_OK;
 }
 
+/* cryo_group.rsv: nothing, buckets, or text group columns -- not both */
+static bool group_rsv_ok(uint32_t rsv) { return rsv == 0 || rsv == CRYO_GROUP_BUCKETS || rsv == CRYO_GROUP_TEXT; }
+
 /* the grouping's descriptor rules (include/cryo_codec.h); every array is host memory here -- bk: the nby buckets of a
  * CRYO_GROUP_BUCKETS descriptor, whose pointer within *grp is held against its rules here too.  *max_att: the highest key, group
- * or aggregate column; *ncols: the aggregate columns (0 with a null agg) */
+ * or aggregate column; *ncols: the aggregate columns (0 with a null agg); *text: bit j set when group column j is a byte string,
+ * which CRYO_GROUP_TEXT alone allows, on a varlena column */
 static bool group_desc_ok(const cryo_filter *f, const cryo_att *atts, const cryo_scan_key *keys, const cryo_group *grp,
                           const cryo_agg_col *by, const cryo_bucket *bk, const cryo_agg *agg, const cryo_agg_col *cols, uint32_t *max_att,
-                          uint32_t *ncols)
+                          uint32_t *ncols, uint32_t *text)
 {
     *ncols = 0;
+    *text = 0;
     if (!filter_desc_ok(f, atts, keys, max_att)) return false;
-    if ((f->flags & ~CRYO_FILTER_TRUTH) != 0 || !grp || grp->nby == 0 || grp->nby > CRYO_GROUP_MAX_BY || grp->rsv > CRYO_GROUP_BUCKETS || !by)
+    if ((f->flags & ~CRYO_FILTER_TRUTH) != 0 || !grp || grp->nby == 0 || grp->nby > CRYO_GROUP_MAX_BY || !group_rsv_ok(grp->rsv) || !by)
         return false;
-    for (uint32_t j = 0; j < grp->nby; j++)
-        if (!agg_col_ok(f, atts, by[j], max_att, false)) return false;
+    for (uint32_t j = 0; j < grp->nby; j++) {
+        const cryo_agg_col &q = by[j];
+        if (grp->rsv == CRYO_GROUP_TEXT && q.type == CRYO_KEY_BYTES) {
+            if (q.rsv != 0 || q.rsv2 != 0 || q.att == 0 || q.att > f->natts || atts[q.att - 1].attlen != -1) return false;
+            if (q.att > *max_att) *max_att = q.att;
+            *text |= 1u << j;
+        } else if (!agg_col_ok(f, atts, q, max_att, false)) return false;
+    }
     if (grp->rsv == CRYO_GROUP_BUCKETS &&
         (!group_buckets(grp) || ((uintptr_t)group_buckets(grp) & 7u) != 0 || !bk || !bucket_desc_ok(bk, grp->nby)))
         return false;
@@ -1617,7 +1631,8 @@ static int group_pass(cryo_codec *c, int method, const uint8_t *d_src, const uin
     const uint64_t S = cryo::filter_side_stride(B);
     DecodePass ps(d_src, d_src_off, d_src_size, true);
     ps.fixed = 256u;                                                 /* the six column slots */
-    ps.own_per_block = S * (sizeof(cryo_group_rec) + io.ncols * sizeof(cryo_agg_cell)); /* the side area */
+    const uint32_t cpg = io.ncols + (uint32_t)__builtin_popcount(io.sd.text); /* a group's cells */
+    ps.own_per_block = S * (sizeof(cryo_group_rec) + cpg * sizeof(cryo_agg_cell)); /* the side area */
     ps.run = [&](const DecodeChunk &ch) -> int {
         const void *slots = io.d_slots ? io.d_slots : ch.fixed;
         if (ch.lo == 0) {
@@ -1632,7 +1647,7 @@ static int group_pass(cryo_codec *c, int method, const uint8_t *d_src, const uin
         uint8_t *side_rec = ch.own, *side_cell = ch.own + ch.K * S * sizeof(cryo_group_rec);
         HIP_TRY(c, cryo::launch_group(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.sd.d_atts, io.sd.d_keys, io.sd.nkeys, slots, io.nby,
                                       io.ncols, io.sd.max_att, io.sd.truth, io.sd.floats, (uint4 *)(io.d_blocks + ch.lo), side_rec, side_cell, io.d_total,
-                                      io.d_groups, io.d_cells, io.group_cap, c->lz4_opts.cus, io.sd.d_buckets));
+                                      io.d_groups, io.d_cells, io.group_cap, c->lz4_opts.cus, io.sd.d_buckets, io.sd.text));
         return CRYO_OK;
     };
     return decode_pass(c, method, B, n, ps);
@@ -1989,7 +2004,7 @@ static int scan_desc_device(cryo_codec *c, const cryo_filter *f, const cryo_grou
         (f->nkeys > 0 && !f->keys) || ((uintptr_t)f->atts & 3u) != 0 || ((uintptr_t)f->keys & 7u) != 0)
         return CRYO_E_ARG;
     if (grp && (grp->nby == 0 || grp->nby > CRYO_GROUP_MAX_BY || !grp->by || ((uintptr_t)grp->by & 7u) != 0)) return CRYO_E_ARG;
-    if (grp && (grp->rsv > CRYO_GROUP_BUCKETS ||
+    if (grp && (!group_rsv_ok(grp->rsv) ||
                 (grp->rsv == CRYO_GROUP_BUCKETS && (!group_buckets(grp) || ((uintptr_t)group_buckets(grp) & 7u) != 0))))
         return CRYO_E_ARG;
     const cryo_bucket *d_bk = grp ? group_buckets(grp) : nullptr; /* device */
@@ -2016,7 +2031,7 @@ static int scan_desc_device(cryo_codec *c, const cryo_filter *f, const cryo_grou
     *ncols = nc;
     const bool ok = ord        ? topn_desc_ok(f, atts, keys, ord, ocols, prj, pcols, &sd.max_att, tt)
                     : prj      ? project_desc_ok(f, atts, keys, prj, pcols, &sd.max_att, pt)
-                    : grp      ? group_desc_ok(f, atts, keys, grp, by, d_bk ? bk : nullptr, agg, cols, &sd.max_att, ncols)
+                    : grp      ? group_desc_ok(f, atts, keys, grp, by, d_bk ? bk : nullptr, agg, cols, &sd.max_att, ncols, &sd.text)
                     : need_agg ? agg_desc_ok(f, atts, keys, agg, cols, &sd.max_att)
                                : filter_desc_ok(f, atts, keys, &sd.max_att);
     if (!ok) return CRYO_E_ARG;
@@ -2027,7 +2042,7 @@ static int scan_desc_device(cryo_codec *c, const cryo_filter *f, const cryo_grou
     int rc = key_table_device(c, keys, f->nkeys, &sd.d_keys, &table_keys);
     if (rc == CRYO_OK && d_bk) rc = bucket_table_device(c, bk, grp->nby, &sd.d_buckets);
     sd.floats = desc_has_float(keys, f->nkeys, cols, *ncols);
-    sd.truth = scan_truth(f, table_keys || sd.floats || d_bk); /* the bucket kernels have the table's verdict path alone */
+    sd.truth = scan_truth(f, table_keys || sd.floats || d_bk || sd.text); /* the bucket and the text kernels have the table's verdict path alone */
     return rc;
 }
 
@@ -2091,6 +2106,7 @@ int cryo_codec_group_batch(cryo_codec *c, int method, const void *d_src, const u
         GroupIo io;
         const int rc = scan_desc_device(c, f, grp, agg, false, d_total, 1, n_blocks, io.sd, &io.ncols);
         if (rc != CRYO_OK || n_blocks == 0) return rc;
+        if (io.sd.text && group_cap > 0 && !d_cells) return (int)CRYO_E_ARG; /* the key cells need the room that ncols == 0 does not */
         io.d_by = grp->by; io.d_cols = ncols ? agg->cols : nullptr; io.nby = grp->nby;
         io.d_blocks = d_blocks; io.d_groups = d_groups; io.d_cells = d_cells; io.group_cap = group_cap; io.d_total = d_total;
         return group_pass(c, method, (const uint8_t *)d_src, d_src_off, d_src_size, block_size, n_blocks, io);
@@ -2902,10 +2918,10 @@ int cryo_codec_agg_blocks(cryo_codec *c, int method, const void *const *h_src, c
 
 /* what every host-buffer group call checks before a device is touched */
 static int group_blocks_args(int method, size_t block_size, const cryo_filter *f, const cryo_group *grp, const cryo_agg *agg,
-                             uint64_t *h_total, uint32_t *max_att, uint32_t *ncols)
+                             uint64_t *h_total, uint32_t *max_att, uint32_t *ncols, uint32_t *text)
 {
     if (!method_ok(method) || !check_block_size_ok(block_size) || !h_total) return CRYO_E_ARG;
-    if (!f || !grp || !group_desc_ok(f, f->atts, f->keys, grp, grp->by, group_buckets(grp), agg, agg ? agg->cols : nullptr, max_att, ncols))
+    if (!f || !grp || !group_desc_ok(f, f->atts, f->keys, grp, grp->by, group_buckets(grp), agg, agg ? agg->cols : nullptr, max_att, ncols, text))
         return CRYO_E_ARG;
     return CRYO_OK;
 }
@@ -2919,17 +2935,18 @@ static int group_blocks_impl(cryo_codec *c, int method, const void *const *h_src
                              cryo_group_block *h_blocks, cryo_group_rec *h_groups, size_t group_cap, cryo_agg_cell *h_cells,
                              uint64_t *h_total)
 {
-    uint32_t max_att = 0, ncols = 0;
-    int rc = group_blocks_args(method, block_size, f, grp, agg, h_total, &max_att, &ncols);
+    uint32_t max_att = 0, ncols = 0, text = 0;
+    int rc = group_blocks_args(method, block_size, f, grp, agg, h_total, &max_att, &ncols, &text);
     if (rc != CRYO_OK || !c) return CRYO_E_ARG;
+    const uint32_t cpg = ncols + (uint32_t)__builtin_popcount(text); /* a group's cells: the aggregate cells, then the key cells */
     DevGuard dev_(c);
     *h_total = 0;
     if (n == 0) return CRYO_OK;
-    if (!h_src || !h_src_size || !h_blocks || (group_cap > 0 && (!h_groups || (ncols > 0 && !h_cells)))) return CRYO_E_ARG;
+    if (!h_src || !h_src_size || !h_blocks || (group_cap > 0 && (!h_groups || (cpg > 0 && !h_cells)))) return CRYO_E_ARG;
     ScopedLocalCpus numa_(c, n, block_size);
     /* the descriptor with the kernel's six slots [by 8 x 2][cols 8 x 4] and -- CRYO_GROUP_BUCKETS -- the bucket table (built for
      * the address it will have in c->hb_meta, from the caller's host lists) as its extra bytes, then the results: [total 16]
-     * [rows 32 x n][records 24 x cap][cells 40 x cap x ncols], each part 8-byte aligned, the rows 16; cap: what the caller has room
+     * [rows 32 x n][records 24 x cap][cells 40 x cap x cpg], each part 8-byte aligned, the rows 16; cap: what the caller has room
      * for, at most the worst case */
     const size_t worst = n * (size_t)cryo::filter_side_stride((uint32_t)block_size);
     const size_t cap = group_cap < worst ? group_cap : worst;
@@ -2941,10 +2958,10 @@ static int group_blocks_impl(cryo_codec *c, int method, const void *const *h_src
     memcpy(slots, grp->by, (size_t)grp->nby * 8);
     if (ncols) memcpy(slots + CRYO_GROUP_MAX_BY, agg->cols, (size_t)ncols * 8);
     ScanDescLayout L = scan_desc_layout(f, extra.size() * 8, slots + CRYO_GROUP_MAX_BY, ncols);
-    if (bk) L.table_keys = true; /* the bucket kernels have the table's verdict path alone */
+    if (bk || text) L.table_keys = true; /* the bucket and the text kernels have the table's verdict path alone */
     const size_t t_total = L.bytes, t_rows = t_total + 16;
     const size_t rows_bytes = n * sizeof(cryo_group_block), t_recs = t_rows + rows_bytes, t_cells = t_recs + cap * sizeof(cryo_group_rec);
-    if ((rc = ensure(c, &c->hb_meta, &c->hb_meta_cap, t_cells + cap * ncols * sizeof(cryo_agg_cell) + 64)) != CRYO_OK) return rc;
+    if ((rc = ensure(c, &c->hb_meta, &c->hb_meta_cap, t_cells + cap * cpg * sizeof(cryo_agg_cell) + 64)) != CRYO_OK) return rc;
     StagedStreams sg;
     GroupIo io;
     if (bk) {
@@ -2955,7 +2972,7 @@ static int group_blocks_impl(cryo_codec *c, int method, const void *const *h_src
         io.sd.d_buckets = d_tab;
     }
     if ((rc = scan_desc_upload(c, h_src, h_src_size, n, f, max_att, L, extra.data(), sg, io.sd)) != CRYO_OK) return rc;
-    io.d_slots = c->hb_meta + L.t_extra; io.nby = grp->nby; io.ncols = ncols;
+    io.d_slots = c->hb_meta + L.t_extra; io.nby = grp->nby; io.ncols = ncols; io.sd.text = text;
     io.d_total = (uint64_t *)(c->hb_meta + t_total);
     io.d_blocks = (cryo_group_block *)(c->hb_meta + t_rows);
     io.d_groups = (cryo_group_rec *)(c->hb_meta + t_recs);
@@ -2972,7 +2989,7 @@ static int group_blocks_impl(cryo_codec *c, int method, const void *const *h_src
     if (total > group_cap) return CRYO_E_DSTSIZE;
     if (total)
         rc = read_back(c, rc, {h_groups, io.d_groups, total * sizeof(cryo_group_rec)},
-                       {h_cells, io.d_cells, total * ncols * sizeof(cryo_agg_cell)}, "hipMemcpyAsync of records and cells");
+                       {h_cells, io.d_cells, total * cpg * sizeof(cryo_agg_cell)}, "hipMemcpyAsync of records and cells");
     return rc;
 }
 
@@ -3649,8 +3666,9 @@ int cryo_multi_group_blocks(cryo_multi *m, int method, const void *const *h_src,
                             cryo_group_block *h_blocks, cryo_group_rec *h_groups, size_t group_cap, cryo_agg_cell *h_cells,
                             uint64_t *h_total)
 {
-    uint32_t max_att = 0, nc = 0;
-    if (!m || m->h.empty() || group_blocks_args(method, block_size, f, grp, agg, h_total, &max_att, &nc) != CRYO_OK) return CRYO_E_ARG;
+    uint32_t max_att = 0, nc = 0, text = 0;
+    if (!m || m->h.empty() || group_blocks_args(method, block_size, f, grp, agg, h_total, &max_att, &nc, &text) != CRYO_OK) return CRYO_E_ARG;
+    nc += (uint32_t)__builtin_popcount(text); /* from here on a group's cells: the key cells travel with the aggregate cells */
     const size_t G = m->h.size();
     if (G == 1)
         return cryo_codec_group_blocks(m->h[0], method, h_src, h_src_size, n, block_size, f, grp, agg, h_blocks, h_groups, group_cap,

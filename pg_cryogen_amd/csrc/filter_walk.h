@@ -26,6 +26,7 @@ constexpr uint32_t kFilterUndecided = 9;       /* a status too: a byte-string ke
 constexpr uint32_t kFilterNoMatch = 0xFFFFu;  /* inside the kernels only: a good tuple that fails a key */
 constexpr uint32_t kKeyBytes = 16u;           /* CRYO_KEY_BYTES */
 constexpr uint32_t kWalkNoBytes = 0xFFFFFFFFu; /* inside the walk only: the payload length of a varlena without in-line bytes */
+constexpr int64_t kWalkTextAway = -1;           /* a TEXT capture: the varlena's bytes are not in the tuple (no place is negative) */
 constexpr uint32_t kOpLt = 1, kOpLe = 2, kOpEq = 3, kOpGe = 4, kOpGt = 5, kOpNe = 6, kOpIsNull = 7, kOpNotNull = 8;
 constexpr uint32_t kOpIn = 9, kOpNotIn = 10;  /* set keys: rsv the members, value their address in the key table */
 constexpr uint32_t kSetLinear = 8u;           /* sets up to this size are scanned, larger ones searched; where the scan stops paying
@@ -187,8 +188,10 @@ __device__ inline bool walk_set_has(const int64_t *__restrict__ set, uint32_t n,
  * W[t | u], undecided otherwise; without BYTES nkeys is the count alone and the keys are ANDed.  NARROW: a captured column may have attlen 1 (the projection's
  * argument rule: attlen 1, 2, 4 or 8 and attalign at least that).  FLOATS (with BYTES alone): a comparison key of type kKeyFloat4 or
  * kKeyFloat8 holds its constant mapped (float_map, the host's rewrite) and the column's value is mapped before the compare;
- * a capture stays the raw bits. */
-template <bool CAPTURE, uint32_t SLOTS = kAggMaxCols, bool BYTES = false, bool NARROW = false, bool FLOATS = false>
+ * a capture stays the raw bits.  TEXT (with BYTES alone; k_groupt_block's, group_text.hip): a captured column of type kKeyBytes is
+ * a varlena, and its slot notes where the payload lies instead of a value: the payload's offset from t in the low half and its
+ * length in the high half, or kWalkTextAway when the bytes are not in the tuple; the walk itself loads none of them. */
+template <bool CAPTURE, uint32_t SLOTS = kAggMaxCols, bool BYTES = false, bool NARROW = false, bool FLOATS = false, bool TEXT = false>
 __device__ inline uint32_t walk_tuple(const uint8_t *__restrict__ t, uint32_t len, bool live, const FilterAtt *__restrict__ atts,
                                       const FilterKey *__restrict__ keys, uint32_t nkeys, uint32_t max_att,
                                       const AggCol *__restrict__ cols, uint32_t ncols,
@@ -279,6 +282,11 @@ __device__ inline uint32_t walk_tuple(const uint8_t *__restrict__ t, uint32_t le
 #pragma unroll
             for (uint32_t j = 0; j < SLOTS; j++) { /* unrolled: v[j] stays in registers */
                 if (j >= ncols || cols[j].att != col) continue; /* uniform */
+                if (TEXT && cols[j].type == kKeyBytes) { /* uniform; [pos, pos + size) lies below len and head <= size */
+                    cap->v[j] = !val ? 0 : head == kWalkNoBytes ? kWalkTextAway : (int64_t)((uint64_t)(pos + head) | (uint64_t)(size - head) << 32);
+                    if (val) cap->has |= 1u << j;
+                    continue;
+                }
                 /* as for a key: the column's [pos, pos + attlen) lies below len, aligned by the aggregate's argument rule */
                 cap->v[j] = !val ? 0 : NARROW ? walk_value_narrow(t + pos, a.attlen) : walk_value(t + pos, a.attlen);
                 if (val) cap->has |= 1u << j;

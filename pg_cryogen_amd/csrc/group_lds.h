@@ -3,6 +3,8 @@
  * records' layout, a wave's matches in LDS, the wave's barrier between its LDS writes and reads, and the two steps that lead up
  * to a kernel's own reduction: the matches into LDS (group_matches) and their ranks (group_rank).  group_bucket.hip's
  * k_groupb_block is a third user: it hands group_matches a step that maps the captured group values (GroupRawKeys: none).
+ * group_text.hip's k_groupt_block keeps the layout (GroupLds inside its own, wider LDS) and the barrier and states steps 1 and 2
+ * for keys that carry a byte string's words: group_matches and group_rank stay as they are for the three kernels above.
  */
 #pragma once
 #include "kernels.h"

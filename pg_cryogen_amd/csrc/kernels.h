@@ -300,18 +300,26 @@ hipError_t launch_aggf(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride,
  * *d_running: the groups before the chunk in, after it out.  The chunk's records go to d_rec and its cells to d_cells (8-byte
  * aligned) at first_group within the call; nothing at or beyond group_cap groups is written.  cus as for launch_fetch.
  * d_buckets: null, or -- a CRYO_GROUP_BUCKETS descriptor -- the staged bucket table (launch_groupb_block), whose kernels run in
- * the block kernel's place; truth is not 0 then. */
+ * the block kernel's place; truth is not 0 then.  text: bit j set when group column j is a byte string (CRYO_GROUP_TEXT); not 0:
+ * group_text.hip's kernels run in the block kernel's place (launch_groupt_block), truth is not 0, d_buckets is null, and a group
+ * has ncols + popcount(text) cells in d_side_cell and d_cells, the aggregate cells first. */
 hipError_t launch_group(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
                         const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,
                         uint32_t nby, uint32_t ncols, uint32_t max_att, uint32_t truth, bool floats, uint4 *d_blocks, void *d_side_rec,
                         void *d_side_cell,
-                        uint64_t *d_running, void *d_rec, void *d_cells, uint64_t group_cap, int cus, const void *d_buckets);
+                        uint64_t *d_running, void *d_rec, void *d_cells, uint64_t group_cap, int cus, const void *d_buckets, uint32_t text);
 /* launch_group's bucket branch (group_bucket.hip): k_groupb_block<floats> alone, on arguments launch_group has checked; truth is
  * not 0; d_buckets the staged bucket table, 8-byte aligned: two entries of 24 bytes (cryo_bucket; a list's n its distinct
  * boundaries and value the device address of the library's sorted copy) */
 hipError_t launch_groupb_block(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
                                const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,
                                const void *d_buckets, uint32_t nby, uint32_t ncols, uint32_t max_att, uint32_t truth, bool floats,
+                               uint32_t side_stride, uint4 *d_blocks, void *d_side_rec, void *d_side_cell);
+/* launch_group's text branch (group_text.hip): k_groupt_block<floats> alone, on arguments launch_group has checked; truth and
+ * text are not 0 */
+hipError_t launch_groupt_block(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
+                               const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,
+                               uint32_t nby, uint32_t ncols, uint32_t text, uint32_t max_att, uint32_t truth, bool floats,
                                uint32_t side_stride, uint4 *d_blocks, void *d_side_rec, void *d_side_cell);
 /* launch_group's float branch (group_float.hip): k_groupf_block alone, on arguments launch_group has checked; truth is not 0 */
 hipError_t launch_groupf_block(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,

@@ -503,26 +503,35 @@ class GroupScanError(RuntimeError):
         super().__init__("cryo_group_scan failed: %d" % code)
 
 
-def group_scan(rel, atts, keys, by, cols=None, truth=None, buckets=None):
+def group_scan(rel, atts, keys, by, cols=None, truth=None, buckets=None, text=False):
     """cryo_group_scan (host/group.h) with the descriptors codec.filter_desc, codec.group_desc and codec.agg_desc make of atts
     [(attlen, attalign)], keys [(att, type, op, value)], by and cols [(att, type)] (cols None: a null aggregate descriptor);
-    buckets: one (kind, flags, origin, value) per group column, as for codec.group_desc.
+    buckets: one (kind, flags, origin, value) per group column, as for codec.group_desc.  text: the descriptor carries
+    codec.GROUP_TEXT, a group column may be (att, codec.KEY_BYTES), and such a column's place in a key tuple holds the value's
+    bytes, taken from the group's key cell.
     Returns (events, totals): events in delivery order, ("block", block, created_xid, n_items, n_match, n_bad, [(key tuple with
     None for NULL, n_rows, [(n, min, max, sum) per column]) per group]) or ("report", block, reason, detail); totals a dict.  A
     nonzero status raises GroupScanError (which carries what was delivered)."""
     from . import codec
-    desc, gdesc = codec.filter_desc(atts, keys, 0, truth), codec.group_desc(by, buckets)
+    desc, gdesc = codec.filter_desc(atts, keys, 0, truth), codec.group_desc(by, buckets, text)
     adesc = None if cols is None else codec.agg_desc(cols)
     nby, ncols = len(by), len(cols or ())
+    texts = [j for j, (_, typ) in enumerate(by) if typ == codec.KEY_BYTES] if text else []
+    cpg = ncols + len(texts)                      # a group's cells: the aggregate cells, then a key cell per text column
     events = []
+
+    def key_bytes(b, g, t):
+        raw = C.string_at(C.addressof(b.cells[g * cpg + ncols + t]), 40)
+        return raw[:int.from_bytes(raw[32:36], "little")]
 
     def on_block(arg, b):
         b = b.contents
         groups = []
         for g in range(b.n_groups):
             r = b.recs[g]
-            key = tuple(None if (r.nulls >> j) & 1 else r.key[j] for j in range(min(nby, 2)))
-            groups.append((key, r.n_rows, [_cell(b.cells[g * ncols + j]) for j in range(ncols)]))
+            key = tuple(None if (r.nulls >> j) & 1 else key_bytes(b, g, texts.index(j)) if j in texts else r.key[j]
+                        for j in range(min(nby, 2)))
+            groups.append((key, r.n_rows, [_cell(b.cells[g * cpg + j]) for j in range(ncols)]))
         events.append(("block", b.block, b.created_xid, b.n_items, b.n_match, b.n_bad, groups))
 
     bcb = GROUP_BLOCK_FN(on_block)

@@ -21,6 +21,17 @@ typedef struct {
     CryoGroupTotals t;
 } Job;
 
+/* the cells of a group: the aggregate cells, then -- CRYO_GROUP_TEXT -- a cryo_group_key per byte-string group column.  A
+ * descriptor the codec will refuse counts as it stands: the call comes back with CRYO_E_ARG before a cell is looked at */
+static uint32_t cells_per_group(const cryo_group *grp, const cryo_agg *agg)
+{
+    uint32_t n = agg ? agg->ncols : 0, c;
+    if (grp->rsv == CRYO_GROUP_TEXT && grp->by)
+        for (c = 0; c < grp->nby && c < CRYO_GROUP_MAX_BY; c++)
+            if (grp->by[c].type == CRYO_KEY_BYTES) n++;
+    return n;
+}
+
 static void say(Job *j, BlockNumber block, uint32 reason, uint32 detail)
 {
     j->t.reports++;
@@ -32,7 +43,7 @@ static void say(Job *j, BlockNumber block, uint32 reason, uint32 detail)
 static int window_flush(void *arg, CryoWindow *w)
 {
     Job *j = arg;
-    const uint32_t nc = j->agg ? j->agg->ncols : 0;
+    const uint32_t nc = cells_per_group(j->grp, j->agg);
     cryo_group_block *rows[2] = {NULL, NULL};
     cryo_group_rec *recs[2] = {NULL, NULL};
     cryo_agg_cell *cells[2] = {NULL, NULL};

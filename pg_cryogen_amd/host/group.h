@@ -19,7 +19,8 @@
  *
  * Where it does not pay: one block per call, and high cardinality -- a block of 290 distinct groups returns 64 + 40 * ncols bytes
  * per tuple, more than the filter returns for a narrow tuple.  More than two group columns, non-integer keys and HAVING go
- * through filter.h.  An aggregate column may be a float column (CRYO_KEY_FLOAT4, CRYO_KEY_FLOAT8): its cell is a cryo_agg_cell_f, and
+ * through filter.h -- a text or bytea group column of short in-line values does not: CRYO_GROUP_TEXT (include/cryo_codec.h, "Text
+ * group columns"; a block with n_bad > 0 holds values that are no key and is read again through filter.h).  An aggregate column may be a float column (CRYO_KEY_FLOAT4, CRYO_KEY_FLOAT8): its cell is a cryo_agg_cell_f, and
  * the cells of one key from several blocks combine in block order with cryo_agg_cell_f_combine (aggregate.h).
  */
 #ifndef CRYO_GROUP_H
@@ -29,7 +30,10 @@
 #include "cryo_codec.h"
 
 /* one block's groups: recs n_groups records in the contract's order (ascending, NULLS LAST), cells n_groups * ncols cells (group
- * g's at g * ncols; NULL when ncols == 0); both valid during the callback only.  n_bad > 0: the block holds damaged items or --
+ * g's at g * ncols; NULL when ncols == 0); both valid during the callback only.  Under CRYO_GROUP_TEXT a group has ncols + ntext
+ * cells (ntext: the group columns of type CRYO_KEY_BYTES): group g's aggregate cells at g * (ncols + ntext), and behind them, at
+ * g * (ncols + ntext) + ncols, one cryo_group_key per text group column in column order, read through a cast -- the key's bytes
+ * and its length, all zero for a NULL; cells is NULL when ncols + ntext == 0.  n_bad > 0: the block holds damaged items or --
  * under a byte-string key -- undecided ones, which are in no group -- cryo_filter_scan lists them */
 typedef struct {
     BlockNumber block;
@@ -50,7 +54,7 @@ typedef struct {
     uint64 bad;          /* bad items (CRYO_FETCH_ITEM, CRYO_FILTER_TUPLE) and undecided ones (CRYO_FILTER_UNDECIDED) */
     uint64 reports;      /* reports made */
     uint64 codec_calls;  /* group_blocks calls */
-    uint64 bytes_back;   /* what the calls brought back: rows, records and cells */
+    uint64 bytes_back;   /* what the calls brought back: rows, records and cells, a text group column's key cells included */
     uint64 groups;       /* per-block groups delivered (the same key counts once per block it occurs in) */
 } CryoGroupTotals;
 
