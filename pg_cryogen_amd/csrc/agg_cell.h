@@ -1,6 +1,7 @@
 /*
  * agg_cell.h -- the 40-byte cell of an aggregate column and an integer column's way into it, shared by the kernels that reduce
- * columns (agg.hip, agg_float.hip, group.hip, group_float.hip; include/cryo_codec.h: "aggregating a scan").  A column's running
+ * columns (agg.hip, agg_float.hip and, through group_lds.h's group_reduce, the grouped scan's block kernels in group.hip,
+ * group_float.hip, group_bucket.hip and group_text.hip; include/cryo_codec.h: "aggregating a scan").  A column's running
  * state is its count n of non-NULL values, their minimum and maximum, and their sum in two 64-bit halves: lo the low 32 bits of
  * every value summed unsigned, hi the high 32 bits summed signed (kept in an unsigned register: it wraps as the signed sum does).
  * A block has at most 290 values, so neither half overflows.  A float column keeps count, minimum and maximum the same way, over

@@ -1,5 +1,5 @@
 /*
- * float_pair.h -- what the two kernels that reduce float columns (agg_float.hip, group_float.hip) share: the double-double sum
+ * float_pair.h -- what the kernels that reduce float columns (agg_float.hip; group_lds.h's group_reduce) share: the double-double sum
  * of include/cryo_codec.h ("A float column's cell", "The reduction") and the fold of a column's state into its cell.
  *
  * The sum is part of the contract, byte for byte, so the helpers are written for the compiler to leave alone: IEEE binary64,

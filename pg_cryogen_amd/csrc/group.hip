@@ -7,18 +7,18 @@
  * few cells per group leave the device:
  *   k_group_block    one wave per block, two blocks per workgroup (a wave's share of LDS is 16 240 bytes): the sweep of
  *                    scan_sweep.h, whose walk runs over the columns 1 .. max(highest key, group, aggregate column) with six
- *                    capture slots, and instead of reducing as it goes the wave
- *                      1. compacts the matches in position order into LDS (group_lds.h, group_matches);
- *                      2. ranks them, which sorts them by key without an exchange and marks every group's head (group_lds.h,
- *                         group_rank);
+ *                    capture slots, and instead of reducing as it goes the wave (group_lds.h, group_block: the three steps are
+ *                    stated there once for every block kernel of the grouped scan)
+ *                      1. compacts the matches in position order into LDS (group_matches);
+ *                      2. ranks them, which sorts them by key without an exchange and marks every group's head (group_rank);
  *                      3. counts the heads in sorted order with a ballot prefix across the turns (n_groups); the lane that holds
  *                         a head walks its run, reduces every aggregate column into the running state of agg_cell.h (a run has
  *                         at most 290 values, a block's), and writes the group's record and cells to the block's row of a side
- *                         area in handle workspace.
+ *                         area in handle workspace (group_reduce).
  *                    A descriptor with a byte-string key runs k_group_block<true>, whose walk compares
  *                    those too and counts an undecided tuple in n_bad; every other descriptor runs k_group_block<false>.
- *   k_group_offsets  one workgroup per chunk: the tiled scan of heap_block.h (offsets_tile) over the blocks' n_groups, from the running
- *                    total the chunk before left in device memory; it writes first_group into the rows.
+ *   k_group_offsets  one workgroup per chunk: the tiled scan of heap_block.h (offsets_of_rows) over the blocks' n_groups, from the
+ *                    running total the chunk before left in device memory; it writes first_group into the rows.
  *   k_group_copy     a grid stride over the blocks: block k's records and cells from the side area to first_group of the call's
  *                    output, word by word, cut off at group_cap.
  * A descriptor with a float key or a float aggregate column runs group_float.hip's k_groupf_block in k_group_block's place
@@ -43,58 +43,8 @@ k_group_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, 
     uint32_t k, lane;
     GroupLds &L = lds[sweep_wave(kGroupWaves, k, lane)];
     if (k >= cnt) return;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    uint32_t n_match = 0, n_bad = 0, n_groups = 0;
-    const uint8_t *__restrict__ p;
-    uint32_t n, upper;
-    const uint32_t status = sweep_open(dec, dec_stride, B, dec_status, k, p, n, upper);
-    /* 1. the matches into LDS in position order, 2. their ranks: group_lds.h */
-    group_matches<BYTES, false>(L, p, B, n, upper, lane, atts, keys, nkeys, max_att, slots, nby, n_match, n_bad);
-    const uint32_t m = n_match;
-    group_rank(L, m, lane);
-    /* 3. one lane per group: the head's lane walks the run up to the next head */
-    GroupRec *out_rec = side_rec + (uint64_t)k * side_stride;
-    AggCell *out_cell = side_cell + (uint64_t)k * side_stride * ncols;
-    for (uint32_t t0 = 0; t0 < m; t0 += 64u) {
-        const uint32_t s = t0 + lane;
-        const uint32_t o = s < m ? L.order[s] : 0u;
-        const bool head = (o >> 16) != 0u;
-        const unsigned long long mh = __ballot(head);
-        if (head) {
-            const uint32_t g = n_groups + (uint32_t)__popcll(mh & below); /* below m <= n <= side_stride */
-            const uint32_t first = o & 0xFFFFu;
-            uint32_t rows = 0;
-            uint32_t cn[kAggMaxCols];
-            int64_t cmin[kAggMaxCols], cmax[kAggMaxCols];
-            uint64_t clo[kAggMaxCols], chi[kAggMaxCols];
-#pragma unroll
-            for (uint32_t j = 0; j < kAggMaxCols; j++) { cn[j] = 0; cmin[j] = INT64_MAX; cmax[j] = INT64_MIN; clo[j] = 0; chi[j] = 0; }
-            for (uint32_t r = s;;) {
-                const uint32_t i = L.order[r] & 0xFFFFu;
-                const uint32_t has = L.meta[i] >> 2;
-                rows++;
-#pragma unroll
-                for (uint32_t j = 0; j < kAggMaxCols; j++)
-                    if (j < ncols && ((has >> j) & 1u) != 0) cell_add(L.val[j][i], cn[j], cmin[j], cmax[j], clo[j], chi[j]); /* a NULL adds nothing */
-                r++;
-                if (r >= m || (L.order[r] >> 16) != 0u) break;
-            }
-            GroupRec rec;
-            rec.key[0] = L.key[0][first];
-            rec.key[1] = L.key[1][first];
-            rec.n_rows = rows;
-            rec.nulls = L.meta[first] & 3u;
-            out_rec[g] = rec;
-#pragma unroll
-            for (uint32_t j = 0; j < kAggMaxCols; j++)
-                if (j < ncols) out_cell[(uint64_t)g * ncols + j] = cell_int(cn[j], cmin[j], cmax[j], clo[j], chi[j]); /* uniform */
-        }
-        n_groups += (uint32_t)__popcll(mh);
-    }
-    if (lane == 0) {
-        blocks[2u * k] = make_uint4(status, n, n_match, n_bad);
-        blocks[2u * k + 1u] = make_uint4(n_groups, 0u, 0u, 0u); /* first_group: k_group_offsets */
-    }
+    group_block<BYTES, false>(L, k, lane, dec, dec_stride, B, dec_status, atts, keys, nkeys, slots, nby, ncols, max_att, side_stride, blocks,
+                              side_rec, side_cell);
 }
 
 /* first_group of every row of the chunk: the groups before block k, counted from the call's start; *running: the total before
@@ -103,19 +53,7 @@ __global__ void __launch_bounds__(256)
 k_group_offsets(uint32_t cnt, uint64_t *__restrict__ running, uint4 *__restrict__ blocks)
 {
     __shared__ uint64_t wave_sum[4];
-    uint64_t run = running[0]; /* the same in every thread; written again only after the tiles' barriers */
-    for (uint32_t t = 0; t < cnt; t += 256u) {
-        const uint32_t k = t + threadIdx.x;
-        const uint64_t a[1] = {k < cnt ? blocks[2u * k + 1u].x : 0u};
-        uint64_t before[1], tile[1];
-        offsets_tile(a, wave_sum, before, tile);
-        if (k < cnt) {
-            const uint64_t first = run + before[0];
-            blocks[2u * k + 1u] = make_uint4((uint32_t)a[0], 0u, (uint32_t)first, (uint32_t)(first >> 32));
-        }
-        run += tile[0];
-    }
-    if (threadIdx.x == 0) running[0] = run;
+    offsets_of_rows(cnt, running, blocks, wave_sum);
 }
 
 /* records (3 words each) and cells (5 words each) of the chunk's blocks from the side area to their places within the call;

@@ -1,14 +1,17 @@
 /*
- * group_lds.h -- what the grouped scan's two block kernels (group.hip: k_group_block; group_float.hip: k_groupf_block) share: the
- * records' layout, a wave's matches in LDS, the wave's barrier between its LDS writes and reads, and the two steps that lead up
- * to a kernel's own reduction: the matches into LDS (group_matches) and their ranks (group_rank).  group_bucket.hip's
- * k_groupb_block is a third user: it hands group_matches a step that maps the captured group values (GroupRawKeys: none).
- * group_text.hip's k_groupt_block keeps the layout (GroupLds inside its own, wider LDS) and the barrier and states steps 1 and 2
- * for keys that carry a byte string's words: group_matches and group_rank stay as they are for the three kernels above.
+ * group_lds.h -- what the grouped scan's block kernels (group.hip: k_group_block; group_float.hip: k_groupf_block;
+ * group_bucket.hip: k_groupb_block; group_text.hip: k_groupt_block) share: the records' layout, a wave's matches in LDS, the
+ * wave's barrier between its LDS writes and reads, and a block kernel's three steps: the matches into LDS (group_matches), their
+ * ranks (group_rank) and the reduction of every group's run into its record and cells (group_reduce).  The first three kernels
+ * are one body (group_block) that differs in the walk's BYTES and FLOATS and in the step that maps the captured group values
+ * (GroupRawKeys: none; group_bucket.hip: to bucket keys).  k_groupt_block keeps the layout (GroupLds inside its own, wider LDS)
+ * and the barrier, states steps 1 and 2 for keys that carry a byte string's words, and hands group_reduce the step that writes
+ * a group's key cells (GroupNoKeyCells: none).
  */
 #pragma once
 #include "kernels.h"
 #include "agg_cell.h"
+#include "float_pair.h"
 #include "scan_sweep.h"
 
 namespace cryo {
@@ -103,6 +106,109 @@ __device__ inline void group_rank(GroupLds &L, uint32_t m, uint32_t lane)
         if (on) L.order[less + same_before] = i | (same_before == 0u ? 1u << 16 : 0u); /* a permutation of 0 .. m - 1 */
     }
     group_wave_sync();
+}
+
+/* group_reduce's step behind a group's aggregate cells: the kernels without a text group column pass this one, which does nothing;
+ * group_text.hip passes the step that writes the key cells.  cell: the index of the group's first cell after the aggregate cells
+ * within the block's row of the side area; first: the group's first match in L */
+struct GroupNoKeyCells { __device__ void operator()(uint64_t, uint32_t) const {} };
+
+/* Step 3, the reduction over the m ranked matches in L: one lane per group.  The heads are counted in sorted order with a ballot
+ * prefix across the turns; the lane that holds a head walks its run in L.order up to the next head (a run has at most 290 values,
+ * a block's) and reduces every aggregate column into the running state of agg_cell.h -- with FLOATS, by a uniform branch on the
+ * column's type, a float column into the count, the minimum and maximum of the mapped values (float_map), three flag bits (+Inf,
+ * -Inf, NaN seen) and the double-double pair over the finite values, started at (+0, +0) and taken in position order, the order
+ * the run has; without FLOATS that branch is not compiled.  The lane writes the group's record to out_rec and its cells to
+ * out_cell, cpg cells a group (the block's rows of the side area; out_cell is not touched when a group has no cell), and
+ * key_cells follows.  The number of groups comes back, the same in all 64 lanes */
+template <bool FLOATS, class KEYCELLS = GroupNoKeyCells>
+__device__ inline uint32_t group_reduce(const GroupLds &L, uint32_t m, uint32_t lane, const AggCol *__restrict__ slots, uint32_t ncols,
+                                        uint32_t cpg, GroupRec *__restrict__ out_rec, AggCell *__restrict__ out_cell,
+                                        const KEYCELLS key_cells = KEYCELLS())
+{
+    const unsigned long long below = (1ull << lane) - 1ull;
+    uint32_t n_groups = 0;
+    for (uint32_t t0 = 0; t0 < m; t0 += 64u) {
+        const uint32_t s = t0 + lane;
+        const uint32_t o = s < m ? L.order[s] : 0u;
+        const bool head = (o >> 16) != 0u;
+        const unsigned long long mh = __ballot(head);
+        if (head) {
+            const uint32_t g = n_groups + (uint32_t)__popcll(mh & below); /* below m <= n <= side_stride */
+            const uint32_t first = o & 0xFFFFu;
+            uint32_t rows = 0;
+            uint32_t cn[kAggMaxCols], flags = 0; /* flags: three bits per float column */
+            int64_t cmin[kAggMaxCols], cmax[kAggMaxCols];
+            uint64_t ca[kAggMaxCols], cb[kAggMaxCols]; /* an integer column's sum halves; a float column's hi and lo bits */
+#pragma unroll
+            for (uint32_t j = 0; j < kAggMaxCols; j++) { cn[j] = 0; cmin[j] = INT64_MAX; cmax[j] = INT64_MIN; ca[j] = 0; cb[j] = 0; }
+            for (uint32_t r = s;;) {
+                const uint32_t i = L.order[r] & 0xFFFFu;
+                const uint32_t has = L.meta[i] >> 2;
+                rows++;
+#pragma unroll
+                for (uint32_t j = 0; j < kAggMaxCols; j++) {
+                    if (j >= ncols || ((has >> j) & 1u) == 0) continue; /* a NULL adds nothing */
+                    int64_t v = L.val[j][i];
+                    cn[j]++;
+                    const uint32_t type = FLOATS ? slots[kGroupMaxBy + j].type : 0u; /* uniform */
+                    if (FLOATS && type >= kKeyFloat4) {
+                        /* the run's values in position order into the pair; what is not finite into the flags alone */
+                        const uint64_t b = float_bits(v, type == kKeyFloat4);
+                        const uint32_t f = float_flag(b);
+                        v = float_map(b);
+                        flags |= f << (3u * j);
+                        if (f == 0u) float_pair_take(b, ca[j], cb[j]);
+                    } else cell_sum(v, ca[j], cb[j]);
+                    cell_minmax(v, cmin[j], cmax[j]);
+                }
+                r++;
+                if (r >= m || (L.order[r] >> 16) != 0u) break;
+            }
+            GroupRec rec;
+            rec.key[0] = L.key[0][first];
+            rec.key[1] = L.key[1][first];
+            rec.n_rows = rows;
+            rec.nulls = L.meta[first] & 3u;
+            out_rec[g] = rec;
+            const uint64_t cell = (uint64_t)g * cpg;
+#pragma unroll
+            for (uint32_t j = 0; j < kAggMaxCols; j++) {
+                if (j >= ncols) continue; /* uniform */
+                AggCell c;
+                if (FLOATS && slots[kGroupMaxBy + j].type >= kKeyFloat4) /* uniform */
+                    float_cell(c.w, cn[j], cmin[j], cmax[j], (flags >> (3u * j)) & 7u, float_pair_of(ca[j], cb[j]));
+                else c = cell_int(cn[j], cmin[j], cmax[j], ca[j], cb[j]);
+                out_cell[cell + j] = c;
+            }
+            key_cells(cell + ncols, first);
+        }
+        n_groups += (uint32_t)__popcll(mh);
+    }
+    return n_groups;
+}
+
+/* A block kernel on GroupLds, all of it: the wave's block opened (scan_sweep.h), steps 1 to 3 with the block's rows of the side
+ * area, and the block's two rows of `blocks`.  The arguments are the kernel's own; keys_of is group_matches' */
+template <bool BYTES, bool FLOATS, class KEYS = GroupRawKeys>
+__device__ inline void group_block(GroupLds &L, uint32_t k, uint32_t lane, const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B,
+                                   const int32_t *__restrict__ dec_status, const FilterAtt *__restrict__ atts,
+                                   const FilterKey *__restrict__ keys, uint32_t nkeys, const AggCol *__restrict__ slots, uint32_t nby,
+                                   uint32_t ncols, uint32_t max_att, uint32_t side_stride, uint4 *__restrict__ blocks,
+                                   GroupRec *__restrict__ side_rec, AggCell *__restrict__ side_cell, const KEYS keys_of = KEYS())
+{
+    uint32_t n_match = 0, n_bad = 0;
+    const uint8_t *__restrict__ p;
+    uint32_t n, upper;
+    const uint32_t status = sweep_open(dec, dec_stride, B, dec_status, k, p, n, upper);
+    group_matches<BYTES, FLOATS>(L, p, B, n, upper, lane, atts, keys, nkeys, max_att, slots, nby, n_match, n_bad, keys_of);
+    group_rank(L, n_match, lane);
+    const uint32_t n_groups = group_reduce<FLOATS>(L, n_match, lane, slots, ncols, ncols, side_rec + (uint64_t)k * side_stride,
+                                                   side_cell + (uint64_t)k * side_stride * ncols);
+    if (lane == 0) {
+        blocks[2u * k] = make_uint4(status, n, n_match, n_bad);
+        blocks[2u * k + 1u] = make_uint4(n_groups, 0u, 0u, 0u); /* first_group: k_group_offsets */
+    }
 }
 
 } // namespace cryo

@@ -15,13 +15,13 @@
  *                     2. group_rank's pass (group_lds.h) on the key (null, words .., length | integer value) per column:
  *                        uniform LDS reads of match j, a per-lane compare, less + same_before, heads marked.  An integer column
  *                        has no words: a uniform branch.
- *                     3. k_groupb_block's step 3 (without FLOATS its float branch is not compiled), and behind a group's
- *                        aggregate cells one key cell per text column in column order: the words back in memory order, the
- *                        length, 0.  A NULL's words and length are 0, so its cell is all zero.
+ *                     3. group_reduce (group_lds.h), every block kernel's, on the GroupLds inside and with the cells of a group
+ *                        as its stride; behind a group's aggregate cells it calls GroupTextKeyCells, which writes one key cell
+ *                        per text column in column order: the words back in memory order, the length, 0.  A NULL's words and
+ *                        length are 0, so its cell is all zero.
  * Every device write is a vector store in plain C++.  No scratch, no global atomics.
  */
 #include "kernels.h"
-#include "float_pair.h"
 #include "group_lds.h"
 
 namespace cryo {
@@ -156,6 +156,26 @@ __device__ inline void groupt_rank(GroupTextLds &L, uint32_t m, uint32_t lane, u
 /* bytes 0 .. 7 of a big-endian word back in memory order for a little-endian store */
 __device__ inline uint64_t groupt_swap(uint64_t x) { return __builtin_bswap64(x); }
 
+/* group_reduce's step for text group columns: behind a group's aggregate cells one key cell per text column in column order */
+struct GroupTextKeyCells {
+    const GroupTextLds &L;
+    AggCell *__restrict__ out_cell;
+    uint32_t text;
+    __device__ void operator()(uint64_t cell, uint32_t first) const
+    {
+#pragma unroll
+        for (uint32_t j = 0; j < kGroupMaxBy; j++) {
+            if (((text >> j) & 1u) == 0) continue; /* uniform */
+            AggCell c; /* cryo_group_key: bytes[32], len, rsv */
+#pragma unroll
+            for (uint32_t q = 0; q < kTextWords; q++) c.w[q] = groupt_swap(L.word[j][q][first]);
+            c.w[4] = (uint64_t)(uint32_t)L.g.key[j][first];
+            out_cell[cell] = c;
+            cell++;
+        }
+    }
+};
+
 template <bool FLOATS>
 __global__ void __launch_bounds__(64)
 k_groupt_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, uint32_t cnt, const int32_t *__restrict__ dec_status,
@@ -167,85 +187,17 @@ k_groupt_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B,
     uint32_t k, lane;
     GroupTextLds &L = lds[sweep_wave(1u, k, lane)];
     if (k >= cnt) return;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    uint32_t n_match = 0, n_bad = 0, n_groups = 0;
+    uint32_t n_match = 0, n_bad = 0;
     const uint8_t *__restrict__ p;
     uint32_t n, upper;
     const uint32_t status = sweep_open(dec, dec_stride, B, dec_status, k, p, n, upper);
     const uint32_t cpg = ncols + (uint32_t)__popc(text); /* a group's cells: the aggregate cells, then the key cells */
-    /* 1. the matches and their text keys into LDS in position order, 2. their ranks */
+    /* 1. the matches and their text keys into LDS in position order, 2. their ranks, 3. group_reduce with the key cells */
     groupt_matches<FLOATS>(L, p, B, n, upper, lane, atts, keys, nkeys, max_att, slots, nby, text, n_match, n_bad);
-    const uint32_t m = n_match;
-    groupt_rank(L, m, lane, text);
-    /* 3. one lane per group: the head's lane walks the run up to the next head */
-    GroupRec *out_rec = side_rec + (uint64_t)k * side_stride;
+    groupt_rank(L, n_match, lane, text);
     AggCell *out_cell = side_cell + (uint64_t)k * side_stride * cpg;
-    for (uint32_t t0 = 0; t0 < m; t0 += 64u) {
-        const uint32_t s = t0 + lane;
-        const uint32_t o = s < m ? L.g.order[s] : 0u;
-        const bool head = (o >> 16) != 0u;
-        const unsigned long long mh = __ballot(head);
-        if (head) {
-            const uint32_t g = n_groups + (uint32_t)__popcll(mh & below); /* below m <= n <= side_stride */
-            const uint32_t first = o & 0xFFFFu;
-            uint32_t rows = 0;
-            uint32_t cn[kAggMaxCols], flags = 0; /* flags: three bits per float column */
-            int64_t cmin[kAggMaxCols], cmax[kAggMaxCols];
-            uint64_t ca[kAggMaxCols], cb[kAggMaxCols]; /* an integer column's sum halves; a float column's hi and lo bits */
-#pragma unroll
-            for (uint32_t j = 0; j < kAggMaxCols; j++) { cn[j] = 0; cmin[j] = INT64_MAX; cmax[j] = INT64_MIN; ca[j] = 0; cb[j] = 0; }
-            for (uint32_t r = s;;) {
-                const uint32_t i = L.g.order[r] & 0xFFFFu;
-                const uint32_t has = L.g.meta[i] >> 2;
-                rows++;
-#pragma unroll
-                for (uint32_t j = 0; j < kAggMaxCols; j++) {
-                    if (j >= ncols || ((has >> j) & 1u) == 0) continue; /* a NULL adds nothing */
-                    int64_t v = L.g.val[j][i];
-                    cn[j]++;
-                    const uint32_t type = FLOATS ? slots[kGroupMaxBy + j].type : 0u; /* uniform */
-                    if (FLOATS && type >= kKeyFloat4) {
-                        /* the run's values in position order into the pair; what is not finite into the flags alone */
-                        const uint64_t b = float_bits(v, type == kKeyFloat4);
-                        const uint32_t f = float_flag(b);
-                        v = float_map(b);
-                        flags |= f << (3u * j);
-                        if (f == 0u) float_pair_take(b, ca[j], cb[j]);
-                    } else cell_sum(v, ca[j], cb[j]);
-                    cell_minmax(v, cmin[j], cmax[j]);
-                }
-                r++;
-                if (r >= m || (L.g.order[r] >> 16) != 0u) break;
-            }
-            GroupRec rec;
-            rec.key[0] = L.g.key[0][first];
-            rec.key[1] = L.g.key[1][first];
-            rec.n_rows = rows;
-            rec.nulls = L.g.meta[first] & 3u;
-            out_rec[g] = rec;
-#pragma unroll
-            for (uint32_t j = 0; j < kAggMaxCols; j++) {
-                if (j >= ncols) continue; /* uniform */
-                AggCell c;
-                if (FLOATS && slots[kGroupMaxBy + j].type >= kKeyFloat4) /* uniform */
-                    float_cell(c.w, cn[j], cmin[j], cmax[j], (flags >> (3u * j)) & 7u, float_pair_of(ca[j], cb[j]));
-                else c = cell_int(cn[j], cmin[j], cmax[j], ca[j], cb[j]);
-                out_cell[(uint64_t)g * cpg + j] = c;
-            }
-            uint32_t kc = ncols; /* the next key cell */
-#pragma unroll
-            for (uint32_t j = 0; j < kGroupMaxBy; j++) {
-                if (((text >> j) & 1u) == 0) continue; /* uniform */
-                AggCell c; /* cryo_group_key: bytes[32], len, rsv */
-#pragma unroll
-                for (uint32_t q = 0; q < kTextWords; q++) c.w[q] = groupt_swap(L.word[j][q][first]);
-                c.w[4] = (uint64_t)(uint32_t)rec.key[j];
-                out_cell[(uint64_t)g * cpg + kc] = c;
-                kc++;
-            }
-        }
-        n_groups += (uint32_t)__popcll(mh);
-    }
+    const uint32_t n_groups = group_reduce<FLOATS>(L.g, n_match, lane, slots, ncols, cpg, side_rec + (uint64_t)k * side_stride, out_cell,
+                                                   GroupTextKeyCells{L, out_cell, text});
     if (lane == 0) {
         blocks[2u * k] = make_uint4(status, n, n_match, n_bad);
         blocks[2u * k + 1u] = make_uint4(n_groups, 0u, 0u, 0u); /* first_group: k_group_offsets */

@@ -7,6 +7,7 @@
  *   heap_item            the ITEM rule: the item id, upper and B in, the tuple's place and length out, or "bad"
  *   offsets_tile         one 256-thread tile of an exclusive scan of uint64_t: the k_*_offsets kernels run it per tile and
  *                        carry the running total themselves
+ *   offsets_of_rows      the whole scan of the two kernels whose blocks bring one count each, in their `blocks` rows
  *   find_last_le         the last index of an ascending uint64_t array with v[i] <= x (the block of a packed byte)
  *   mask_tuple_tail      zeroes the pad in the 8-byte word that holds a tuple's last byte
  * Everything is plain C++; the functions take their inputs by value, so a wave-uniform header stays in scalar registers in
@@ -78,6 +79,27 @@ __device__ inline void offsets_tile(const uint64_t (&a)[N], uint64_t *wave_sum, 
         }
     }
     __syncthreads();
+}
+
+/* The offset scan of a chunk whose blocks bring one count each (k_group_offsets, k_topn_offsets), called by the one workgroup of
+ * 256 threads: block k's count is x of its second row in `blocks`; the row becomes {count, 0, first} with first, in 64 bits, the
+ * counts before block k from the call's start.  *running: the total before the chunk in, after it out.  wave_sum: four words of
+ * LDS, the kernel's */
+__device__ inline void offsets_of_rows(uint32_t cnt, uint64_t *__restrict__ running, uint4 *__restrict__ blocks, uint64_t *wave_sum)
+{
+    uint64_t run = running[0]; /* the same in every thread; written again only after the tiles' barriers */
+    for (uint32_t t = 0; t < cnt; t += 256u) {
+        const uint32_t k = t + threadIdx.x;
+        const uint64_t a[1] = {k < cnt ? blocks[2u * k + 1u].x : 0u};
+        uint64_t before[1], tile[1];
+        offsets_tile(a, wave_sum, before, tile);
+        if (k < cnt) {
+            const uint64_t first = run + before[0];
+            blocks[2u * k + 1u] = make_uint4((uint32_t)a[0], 0u, (uint32_t)first, (uint32_t)(first >> 32));
+        }
+        run += tile[0];
+    }
+    if (threadIdx.x == 0) running[0] = run;
 }
 
 /* the last k in [lo, hi] with v[k] <= x; v[lo] <= x is the caller's */

@@ -21,8 +21,8 @@
  *                   A descriptor with a byte-string key, a set key or a truth table runs k_topn_block<true>, one with a float
  *                   scan key k_topnf_block (the walk's FLOATS); a float ORDER column needs neither: it is mapped here, after
  *                   the capture.
- *   k_topn_offsets  one workgroup per chunk: the tiled scan of heap_block.h (offsets_tile) over n_rows, from the running total
- *                   the chunk before left in device memory; it writes row_first.
+ *   k_topn_offsets  one workgroup per chunk: the tiled scan of heap_block.h (offsets_of_rows, k_group_offsets' too) over n_rows,
+ *                   from the running total the chunk before left in device memory; it writes row_first.
  *   k_topn_copy     a grid stride over the blocks: block k's records to row_first of the call's output, and its kept rows
  *                   gathered through the order list to the same places, 8 bytes per access, cut off at row_cap.
  * Every device write is a vector store in plain C++.  LDS: 24 bytes per possible match and wave.  No scratch, no global atomics.
@@ -217,19 +217,7 @@ __global__ void __launch_bounds__(256)
 k_topn_offsets(uint32_t cnt, uint64_t *__restrict__ running, uint4 *__restrict__ blocks)
 {
     __shared__ uint64_t wave_sum[4];
-    uint64_t run = running[0]; /* the same in every thread; written again only after the tiles' barriers */
-    for (uint32_t t = 0; t < cnt; t += 256u) {
-        const uint32_t k = t + threadIdx.x;
-        const uint64_t a[1] = {k < cnt ? blocks[2u * k + 1u].x : 0u};
-        uint64_t before[1], tile[1];
-        offsets_tile(a, wave_sum, before, tile);
-        if (k < cnt) {
-            const uint64_t first = run + before[0];
-            blocks[2u * k + 1u] = make_uint4((uint32_t)a[0], 0u, (uint32_t)first, (uint32_t)(first >> 32));
-        }
-        run += tile[0];
-    }
-    if (threadIdx.x == 0) running[0] = run;
+    offsets_of_rows(cnt, running, blocks, wave_sum);
 }
 
 /* records (3 words each) of the chunk's blocks from the side area to their places within the call, and the kept rows (row_words

@@ -37,15 +37,18 @@ def pattern_keys(pattern, m):
         return [1000 - 3 * p for p in range(m)]         # descending: the contract's order is the reverse of the position order
     if pattern == "alternate":
         return [5 if p % 2 == 0 else -5 for p in range(m)]
+    if pattern == "straddle":                           # ascending, so a match's place is its position: one run over places 63 .. 65
+        return [63 if 63 <= p <= 65 else p for p in range(m)]
     return runs3(m)
 
 
-def turn_block(pattern, m, interleave=False):
+def turn_block(pattern, m, interleave=False, atts=GX_ATTS, row=None):
     """m matches (g by the pattern, x = the match's number); interleave: behind every second match a tuple the key rejects, behind
-    every seventh a damaged one (its t_hoff is 4)"""
+    every seventh a damaged one (its t_hoff is 4).  atts and row: another row type, row(p, g) the values of match p"""
+    assert row is None or not interleave
     tuples = []
     for p, g in enumerate(pattern_keys(pattern, m)):
-        tuples.append(tc.form_tuple(GX_ATTS, [g, p]))
+        tuples.append(tc.form_tuple(atts, row(p, g) if row else [g, p]))
         if interleave and p % 2 == 1:
             tuples.append(tc.form_tuple(GX_ATTS, [g, -1]))
         if interleave and p % 7 == 6:

@@ -8,8 +8,9 @@ Figures found (hipcc -O3, -Rpass-analysis=kernel-resource-usage; waves per SIMD,
     k_filter_match<true>   8, 0, 46, 84        k_filterf_match   8, 0, 46, 89
     k_project_block<true>  8, 0, 49, 89        k_projectf_block  8, 0, 49, 94
     k_agg_block<true>      7, 0, 71, 77        k_aggf_block      7, 0, 72, 91
-    k_group_block<true>    3, 32480, 62, 82    k_groupf_block    3, 32480, 88, 87
-(the SGPR figures since the kernels share the sweep of scan_sweep.h; 82 / 87, 76 / 88 and 80 / 85 before)
+    k_group_block<true>    3, 32480, 56, 82    k_groupf_block    3, 32480, 74, 87
+(the SGPR figures since the kernels share the sweep of scan_sweep.h; 82 / 87, 76 / 88 and 80 / 85 before; the group kernels' VGPR
+figures since they share group_lds.h's group_reduce; 62 and 88 before)
 k_groupf_block is bound by LDS (two waves' share of 64 KiB is 32 480 bytes: 3 workgroups of 2 waves on 4 SIMDs), not by its
 registers."""
 import pytest

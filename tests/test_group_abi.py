@@ -111,6 +111,8 @@ def test_group_source_is_in_the_build():
     assert '#include "filter_walk.h"' in sweep and len(re.findall(r"\bwalk_tuple<", sweep)) == 1
     lds = open(os.path.join(csrc, "group_lds.h")).read()
     assert '#include "scan_sweep.h"' in lds and "sweep_turn<true, kGroupSlots, BYTES" in lds and "walk_tuple<" not in lds
-    assert '#include "group_lds.h"' in txt and "group_matches<BYTES" in txt and "walk_tuple<" not in txt and "t[22]" not in txt
+    # the kernel is group_lds.h's body, which takes the three steps in turn
+    assert '#include "group_lds.h"' in txt and "group_block<BYTES" in txt and "walk_tuple<" not in txt and "t[22]" not in txt
+    assert all(len(re.findall(r"\b%s<" % step, lds)) == 1 for step in ("group_matches", "group_reduce")) and "group_rank(L" in lds
     hmk = open(os.path.join(ROOT, "pg_cryogen_amd", "host", "Makefile")).read()
     assert re.search(r"^SRCS\s*:=.*\bgroup\.c\b", hmk, flags=re.M)

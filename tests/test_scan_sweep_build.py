@@ -12,7 +12,8 @@ Figures found (waves per SIMD, LDS bytes, VGPRs, SGPRs; SGPRs before -> after wh
     k_group_block<false>    3, 32480, 62, 81 -> 82  k_group_block<true>    3, 32480, 62, 80 -> 82 k_groupf_block    3, 32480, 88, 85 -> 87
 The scalar registers that moved hold the block's status through the sweep: a prologue that hands the status back keeps it live
 where the nested branches it replaced implied it.  k_agg_block<false> has one register of room below the ceiling
-test_truth_key_build.py holds it to, so agg.hip states the status again after its sweep (its comment has the figures)."""
+test_truth_key_build.py holds it to, so agg.hip states the status again after its sweep (its comment has the figures).
+Since the group kernels share their third step as well (group_reduce; test_group_reduce_build.py) they need 56, 56 and 74 VGPRs."""
 import pytest
 
 from test_bytes_key_build import resource_usage
