@@ -413,6 +413,42 @@ int cryo_codec_fetch_batch(cryo_codec *c, int method, const void *d_src, const u
  * otherwise b ^ ((b >> 63, arithmetic) & 0x7FFFFFFFFFFFFFFF), whose integer order is the order above; m is its own inverse apart
  * from the two canonical cases.  The library's own copy of a float key holds m(value) -- the caller's arrays are never written
  * -- and the kernels map a column's value the same way, so the compare, the minimum and the maximum are the integers'.
+ * Pattern keys.  CRYO_OP_LIKE (11) and CRYO_OP_NOT_LIKE (12) match a text / varchar / bytea column against a LIKE pattern (WHERE
+ * url LIKE '%utm_source=%', bundle LIKE 'com.adjust.%', user_agent NOT LIKE '%bot%').  type is CRYO_KEY_BYTES and the column a
+ * varlena (attlen == -1): the byte-string key's column rule.  value is the address of the pattern -- a device address for
+ * cryo_codec_*_batch, a host address for cryo_codec_*_blocks and cryo_multi_*_blocks; any alignment; the caller's memory is only
+ * read.  Bits 0-15 of rsv are the pattern's length n, 0 .. CRYO_KEY_BYTES_MAX; bit 16 of rsv is CRYO_LIKE_UTF8; every other
+ * bit must be 0.
+ *   Pattern syntax: '%' matches any run of characters, the empty run included; '_' matches exactly one character; '\' followed
+ *   by a byte x is x taken literally; every other byte is literal.  Literal bytes are compared as unsigned bytes.  The binder
+ *   rewrites any other ESCAPE character to '\' before the call.
+ *   What a character is: without CRYO_LIKE_UTF8 one byte (bytea, SQL_ASCII and the single-byte encodings).  With CRYO_LIKE_UTF8
+ *   one byte plus every byte 10xxxxxx (0x80 .. 0xBF) that directly follows it, which is PostgreSQL's stepping for UTF-8: '_'
+ *   consumes one character, '%' tries character starts only -- the place where it stands and from there on every place one
+ *   character further --, and literal pattern bytes are always compared bytewise.  On text that is not valid UTF-8 the same rule
+ *   applies and defines the answer.  The pattern is the database's own text and valid UTF-8 under the flag; for a pattern that is
+ *   not -- a '%' or '_' between the bytes of one character -- the answer is defined as that of matching the segments between
+ *   the '%' greedily, each at its leftmost place (tests/like_ref.py: greedy), which there may differ from trying every run.
+ *   CRYO_E_ARG: a type other than CRYO_KEY_BYTES; a column that is not a varlena; n > CRYO_KEY_BYTES_MAX (256); n > 0 with a null
+ *   address; an rsv bit above 16; a pattern whose last byte is an unescaped '\' (PostgreSQL raises for it;
+ *   cryo_filter_like_check of pg_cryogen_amd/host/filter.h tells the binder beforehand) -- in the device-resident calls this last
+ *   one is found after the library has read the pattern back, that is with n_blocks > 0 alone.  (att, CRYO_KEY_INT4, 11, ..) and
+ *   (att, CRYO_KEY_BYTES, 9, ..) stay refused.
+ *   Verdicts: on a NULL column, a column beyond tnatts included, both ops are false.  A value is UNDECIDED when it is a TOAST
+ *   pointer, compressed in line, or its payload is longer than CRYO_LIKE_TEXT_MAX (2048) bytes; an undecided value is what an
+ *   undecided byte-string compare is: CRYO_FILTER_UNDECIDED, n_bad, in no cell, group or row, and under CRYO_FILTER_TRUTH the
+ *   tuple is undecided only when the decided keys do not settle the table.  Otherwise CRYO_OP_LIKE is true iff the whole payload
+ *   matches the whole pattern, and CRYO_OP_NOT_LIKE is its negation.  Only the payload's bytes are read, never the pad behind them.
+ *   Why the cap: a lane matches its tuple's value alone while its wave waits, and the cap bounds a wave's work at about 2 049
+ *   candidate starts times 256 pattern elements whatever the data -- a 1 MiB in-line value cannot stall a shared machine.  The
+ *   caller re-reads the blocks with undecided items, as for toasted values.
+ *   A pattern key counts as one of the four keys; several may be used, also on one column and beside every other kind of key.
+ *   The filter (CRYO_FILTER_COUNT_ONLY included), the aggregate (float columns included), the grouped scan (plain, buckets,
+ *   text), the projection and the ordered scan take them, device-resident, from host buffers and across devices, with or without
+ *   CRYO_FILTER_TRUTH.  The library's device copy of such a key holds the pattern compiled (its segments between the '%', as
+ *   literal bytes and any-one-character elements); the caller's arrays are never written.
+ *   The binder's part, not enforced here: push a LIKE only under a deterministic collation; set CRYO_LIKE_UTF8 iff the database
+ *   encoding is UTF8; never push for any other multibyte encoding; no ILIKE, no SIMILAR TO, no regular expressions.
  * Truth table.  CRYO_FILTER_TRUTH (4) in flags: the keys are not ANDed but combined by any tree of AND and OR (WHERE country =
  * 'de' OR app_id = 3; WHERE ts >= a AND ts < b AND (campaign_id IN (..) OR source IS NULL)).  f->rsv is then not reserved: it
  * holds the truth table W of the tree over its nkeys leaves.  Bit m of W, 0 <= m < 2^nkeys, says whether a tuple matches when
@@ -514,7 +550,8 @@ typedef enum {
 } cryo_key_type;
 typedef enum {
     CRYO_OP_LT = 1, CRYO_OP_LE, CRYO_OP_EQ, CRYO_OP_GE, CRYO_OP_GT, CRYO_OP_NE, CRYO_OP_ISNULL, CRYO_OP_NOTNULL,
-    CRYO_OP_IN = 9, CRYO_OP_NOT_IN = 10 /* a set key: rsv the number of members, value the address of that many int64_t */
+    CRYO_OP_IN = 9, CRYO_OP_NOT_IN = 10, /* a set key: rsv the number of members, value the address of that many int64_t */
+    CRYO_OP_LIKE = 11, CRYO_OP_NOT_LIKE = 12 /* a pattern key: rsv the pattern's length and CRYO_LIKE_UTF8, value its address */
 } cryo_key_op;
 typedef struct { uint16_t att; uint8_t type, op; uint32_t rsv; int64_t value; } cryo_scan_key; /* att 1-based; 16 bytes */
 typedef struct {
@@ -528,6 +565,8 @@ typedef struct {
 #define CRYO_FILTER_UNDECIDED 9u  /* a record's status: a byte-string key met a compressed or external value */
 #define CRYO_KEY_BYTES_MAX 256u   /* the longest constant of a CRYO_KEY_BYTES key */
 #define CRYO_KEY_SET_MAX 1024u    /* the most members of a CRYO_OP_IN / CRYO_OP_NOT_IN list */
+#define CRYO_LIKE_UTF8 0x10000u   /* bit 16 of a pattern key's rsv: a character is a byte and the bytes 10xxxxxx behind it */
+#define CRYO_LIKE_TEXT_MAX 2048u  /* the longest payload a pattern key is matched against; a longer one is undecided */
 #define CRYO_FILTER_MAX_ATTS 1600u
 #define CRYO_FILTER_MAX_KEYS 4u
 typedef struct { uint32_t status, n_items, n_match, n_bad; uint64_t rec_first, off; } cryo_filter_block; /* 32 bytes, one per block */

@@ -53,6 +53,9 @@ KEY_BYTES_MAX = 256
 OP_LT, OP_LE, OP_EQ, OP_GE, OP_GT, OP_NE, OP_ISNULL, OP_NOTNULL = range(1, 9)
 OP_IN, OP_NOT_IN = 9, 10    # a set key: the key's value is a sequence of ints, its type KEY_INT2 / KEY_INT4 / KEY_INT8
 KEY_SET_MAX = 1024
+OP_LIKE, OP_NOT_LIKE = 11, 12   # a pattern key: type KEY_BYTES, the key's value a like(...) object
+LIKE_UTF8 = 0x10000         # bit 16 of a pattern key's rsv: a character is a byte and the bytes 10xxxxxx behind it
+LIKE_TEXT_MAX = 2048        # the longest payload a pattern key is matched against; a longer one is undecided
 FILTER_ATT = np.dtype([("attlen", "<i2"), ("attalign", "u1"), ("rsv", "u1")])                                  # cryo_att
 FILTER_KEY = np.dtype([("att", "<u2"), ("type", "u1"), ("op", "u1"), ("rsv", "<u4"), ("value", "<i8")])        # cryo_scan_key
 FILTER_BLOCK = np.dtype([("status", "<u4"), ("n_items", "<u4"), ("n_match", "<u4"), ("n_bad", "<u4"),
@@ -364,7 +367,8 @@ def truth_flags(flags=0, truth=None):
 def filter_desc(atts, keys=(), flags=0, truth=None):
     """the descriptor of a filter call as host arrays: atts a list of (attlen, attalign), keys a list of (att, type, op, value)
     (att 1-based; type KEY_*, op OP_*; the value of a KEY_BYTES comparison is a bytes object, that of an OP_IN / OP_NOT_IN key
-    a sequence of ints, that of a KEY_FLOAT4 / KEY_FLOAT8 comparison a Python float or, as an int, the 64 bits of a double).  Returns (CryoFilter, atts array,
+    a sequence of ints, that of a KEY_FLOAT4 / KEY_FLOAT8 comparison a Python float or, as an int, the 64 bits of a double, that of an
+    OP_LIKE / OP_NOT_LIKE key -- its type is KEY_BYTES -- a like(pattern, utf8) object).  Returns (CryoFilter, atts array,
     keys array); the struct points into the two arrays, which the caller keeps alive.  The constants of KEY_BYTES keys live in
     one uint8 array the struct holds (f.consts), so they live as long as it does.  truth: a truth table over the keys (truth_dnf):
     FILTER_TRUTH is set in flags and the table goes into rsv"""
@@ -377,6 +381,29 @@ def filter_desc(atts, keys=(), flags=0, truth=None):
     f = CryoFilter(len(atts), len(keys), flags, rsv, a.ctypes.data, k.ctypes.data if len(keys) else None)
     f.consts = consts
     return f, a, k
+
+
+class like:
+    """the value of an OP_LIKE / OP_NOT_LIKE key, so that the key stays (att, KEY_BYTES, op, value): the pattern's bytes ('%',
+    '_' and '\\' as in SQL with ESCAPE '\\'; a str is encoded as UTF-8) and whether a character is a UTF-8 character (utf8) or a
+    byte.  pattern None: no bytes and a null address.  rsv: the key's rsv word as given, for descriptors the library must
+    refuse; otherwise it is the pattern's length with LIKE_UTF8 under utf8"""
+
+    def __init__(self, pattern, utf8=True, rsv=None):
+        self.pattern = None if pattern is None else pattern.encode("utf-8") if isinstance(pattern, str) else bytes(pattern)
+        self.utf8 = bool(utf8)
+        self.rsv = (len(self.pattern or b"") | (LIKE_UTF8 if self.utf8 else 0)) if rsv is None else int(rsv)
+
+    def __len__(self):
+        return len(self.pattern or b"")
+
+    def __repr__(self):
+        return "like(%r, utf8=%r, rsv=0x%x)" % (self.pattern, self.utf8, self.rsv)
+
+
+def _is_like_key(key):
+    """a key whose value is a pattern"""
+    return isinstance(key[3], like)
 
 
 def _is_bytes_key(key):
@@ -398,7 +425,8 @@ def float_key_bits(value):
 
 def _filter_keys(keys):
     """(keys array with rsv = the length and value = the offset of each KEY_BYTES constant, rsv = the number of members and
-    value = the offset of each set key's list -- little-endian int64 --, constants and lists packed back to back)"""
+    value = the offset of each set key's list -- little-endian int64 --, rsv = like.rsv and value = the offset of each pattern
+    key's pattern, constants, lists and patterns packed back to back)"""
     k = np.zeros(max(len(keys), 1), FILTER_KEY)
     parts, at = [], 0
     for i, key in enumerate(keys):
@@ -407,6 +435,10 @@ def _filter_keys(keys):
             value = bytes(value or b"")
             k[i] = (att, typ, op, len(value), at)
             parts.append(value)
+            at += len(value)
+        elif _is_like_key(key):
+            k[i] = (att, typ, op, value.rsv, at)
+            parts.append(value.pattern or b"")
             at += len(value)
         elif _is_set_key(key):
             value = () if value is None else value
@@ -425,7 +457,7 @@ def _filter_keys(keys):
 def _rebase_keys(k, keys, base):
     """offsets into the packed constants -> addresses from `base` on; an empty constant keeps a null address"""
     for i, key in enumerate(keys):
-        if _is_bytes_key(key) or _is_set_key(key):
+        if _is_bytes_key(key) or _is_set_key(key) or _is_like_key(key):
             k[i]["value"] = base + int(k[i]["value"]) if (key[3] is not None and len(key[3])) else 0
 
 

@@ -71,12 +71,15 @@ k_agg_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, ui
 
 hipError_t launch_agg(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
                       const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_cols,
-                      uint32_t ncols, uint32_t max_att, uint32_t truth, bool floats, uint4 *d_blocks, void *d_cells)
+                      uint32_t ncols, uint32_t max_att, uint32_t truth, bool floats, bool like, uint4 *d_blocks, void *d_cells)
 {
     if (cnt == 0) return hipSuccess;
     if (!scan_launch_ok(dec_stride, d_dec, d_blocks, d_atts, d_keys, (uintptr_t)d_cells | (uintptr_t)d_cols, block_size, nkeys, truth,
-                        floats) || ncols == 0u || ncols > kAggMaxCols)
+                        floats || like) || ncols == 0u || ncols > kAggMaxCols)
         return hipErrorInvalidValue;
+    if (like) /* a pattern key: agg_float.hip's second unit */
+        return launch_aggl(s, d_dec, dec_stride, block_size, cnt, d_dec_status, d_atts, d_keys, nkeys, d_cols, ncols, max_att, truth,
+                           d_blocks, d_cells);
     if (floats) /* a float key or a float aggregate column: agg_float.hip's kernel */
         return launch_aggf(s, d_dec, dec_stride, block_size, cnt, d_dec_status, d_atts, d_keys, nkeys, d_cols, ncols, max_att, truth,
                            d_blocks, d_cells);

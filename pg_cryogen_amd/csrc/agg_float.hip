@@ -20,13 +20,12 @@
 
 namespace cryo {
 
-/* the wave count asked for: without it the scheduler spends 86 registers on the same code (5 waves per SIMD); with it the kernel
- * needs 72 and runs 7, as k_agg_block<true> does, without scratch */
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6)))
-k_aggf_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, uint32_t cnt, const int32_t *__restrict__ dec_status,
-             const FilterAtt *__restrict__ atts, const FilterKey *__restrict__ keys, uint32_t nkeys,
-             const AggCol *__restrict__ cols, uint32_t ncols, uint32_t max_att, uint4 *__restrict__ blocks,
-             AggCell *__restrict__ cells)
+/* the body of k_aggf_block and -- LIKE -- of k_aggl_block */
+template <bool LIKE>
+__device__ inline void aggf_block_body(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, uint32_t cnt,
+                                       const int32_t *__restrict__ dec_status, const FilterAtt *__restrict__ atts,
+                                       const FilterKey *__restrict__ keys, uint32_t nkeys, const AggCol *__restrict__ cols, uint32_t ncols,
+                                       uint32_t max_att, uint4 *__restrict__ blocks, AggCell *__restrict__ cells)
 {
     uint32_t k, lane;
     sweep_wave(4u, k, lane);
@@ -42,8 +41,8 @@ k_aggf_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, u
     const uint32_t status = sweep_open(dec, dec_stride, B, dec_status, k, p, n, upper);
     for (uint32_t t0 = 0; t0 < n; t0 += 64u) {
         WalkCapture cap;
-        const SweepItem it = sweep_turn<true, kAggMaxCols, true, false, true>(p, B, n, upper, t0 + lane, atts, keys, nkeys, max_att, cols,
-                                                                             ncols, &cap);
+        const SweepItem it = sweep_turn<true, kAggMaxCols, true, false, true, false, LIKE>(p, B, n, upper, t0 + lane, atts, keys, nkeys,
+                                                                                           max_att, cols, ncols, &cap);
         n_match += (uint32_t)__popcll(__ballot(it.match));
         n_bad += (uint32_t)__popcll(__ballot(it.bad));
 #pragma unroll
@@ -96,6 +95,18 @@ k_aggf_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, u
     }
 }
 
+#ifndef CRYO_LIKE_UNIT
+/* the wave count asked for: without it the scheduler spends 86 registers on the same code (5 waves per SIMD); with it the kernel
+ * needs 72 and runs 7, as k_agg_block<true> does, without scratch */
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6)))
+k_aggf_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, uint32_t cnt, const int32_t *__restrict__ dec_status,
+             const FilterAtt *__restrict__ atts, const FilterKey *__restrict__ keys, uint32_t nkeys,
+             const AggCol *__restrict__ cols, uint32_t ncols, uint32_t max_att, uint4 *__restrict__ blocks,
+             AggCell *__restrict__ cells)
+{
+    aggf_block_body<false>(dec, dec_stride, B, cnt, dec_status, atts, keys, nkeys, cols, ncols, max_att, blocks, cells);
+}
+
 hipError_t launch_aggf(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
                        const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_cols,
                        uint32_t ncols, uint32_t max_att, uint32_t truth, uint4 *d_blocks, void *d_cells)
@@ -107,5 +118,32 @@ hipError_t launch_aggf(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride,
                        d_blocks, (AggCell *)d_cells);
     return hipGetLastError();
 }
+
+#else /* CRYO_LIKE_UNIT */
+/* k_aggf_block whose walk also matches the patterns of CRYO_OP_LIKE / CRYO_OP_NOT_LIKE keys (walk_like), for every descriptor
+ * with such a key, integer columns or float: a kernel of its own name, because the matcher's registers come on top of the
+ * walk's and the four cells' -- no wave count is asked for here, the kernel takes the registers it needs.  Built from this
+ * source compiled a second time with CRYO_LIKE_UNIT (agg_float_like.o) */
+__global__ void __launch_bounds__(256)
+k_aggl_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, uint32_t cnt, const int32_t *__restrict__ dec_status,
+             const FilterAtt *__restrict__ atts, const FilterKey *__restrict__ keys, uint32_t nkeys,
+             const AggCol *__restrict__ cols, uint32_t ncols, uint32_t max_att, uint4 *__restrict__ blocks,
+             AggCell *__restrict__ cells)
+{
+    aggf_block_body<true>(dec, dec_stride, B, cnt, dec_status, atts, keys, nkeys, cols, ncols, max_att, blocks, cells);
+}
+
+hipError_t launch_aggl(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
+                       const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_cols,
+                       uint32_t ncols, uint32_t max_att, uint32_t truth, uint4 *d_blocks, void *d_cells)
+{
+    /* the arguments are launch_agg's, which checked them; the one verdict path needs a table */
+    if (truth == 0u) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_aggl_block, dim3((cnt + 3u) / 4u), dim3(256), 0, s, d_dec, dec_stride, block_size, cnt, d_dec_status,
+                       (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys | truth << 16, (const AggCol *)d_cols, ncols, max_att,
+                       d_blocks, (AggCell *)d_cells);
+    return hipGetLastError();
+}
+#endif
 
 } // namespace cryo

@@ -1156,6 +1156,8 @@ struct ScanDesc {
                                                         truth table of the <true> one (scan_truth) */
     bool floats = false;                             /* a float key or a float aggregate column: the float kernels, which have
                                                         the truth table's verdict path alone (truth is not 0 then) */
+    bool like = false;                               /* a pattern key (CRYO_OP_LIKE, CRYO_OP_NOT_LIKE): the pattern kernels, which
+                                                        also do what the float kernels do (truth is not 0 then) */
     const void *d_buckets = nullptr;                 /* device: the grouping's bucket table under CRYO_GROUP_BUCKETS (truth is not 0
                                                         then), else null */
     uint32_t text = 0;                               /* the grouping's: bit j set when group column j is a byte string
@@ -1221,7 +1223,59 @@ static bool desc_has_float(const cryo_scan_key *keys, uint32_t nkeys, const cryo
     return false;
 }
 
-/* the descriptor's rules (include/cryo_codec.h); atts and keys are host memory here.  *max_att: the highest key column */
+/* ---- pattern keys ---- */
+static bool key_is_like(const cryo_scan_key &q) { return q.op == CRYO_OP_LIKE || q.op == CRYO_OP_NOT_LIKE; }
+/* whether a (valid) descriptor needs the pattern kernels: keys is host memory */
+static bool desc_has_like(const cryo_scan_key *keys, uint32_t nkeys)
+{
+    for (uint32_t k = 0; k < nkeys; k++)
+        if (key_is_like(keys[k])) return true;
+    return false;
+}
+/* the room a pattern of n bytes gets in the key table: its compiled form (like_compile) takes at most 4 n + 8 bytes -- a segment
+ * of e elements costs 4 + 4 ceil(e / 2) bytes and at least e + 1 bytes of pattern, its '%' counted, the last segment e bytes,
+ * and the closing word 4 */
+static size_t like_room(uint32_t n) { return 4 * (size_t)n + 16; }
+static constexpr uint32_t kLikeAny = 0x100u, kLikeUtf8 = 1u << 29, kLikeHead = 1u << 30, kLikeTail = 1u << 31; /* filter_walk.h's */
+/* The n pattern bytes at pat compiled for walk_like (filter_walk.h) into the zeroed like_room(n) bytes at out, or -- out null --
+ * only checked.  False: the pattern ends in an unescaped '\', and nothing is promised of out.  The pattern is cut at its
+ * unescaped '%' into segments; a run of '%' cuts once.  An element is 16 bits: a literal byte (any byte behind '\', and any byte
+ * that is not '%', '_' or '\'), or kLikeAny for '_'.  A segment is the word {element count in bits 0-15, first element in bits
+ * 16-24, kLikeUtf8 (the key's CRYO_LIKE_UTF8), kLikeHead when no '%' stands before it, kLikeTail when none stands behind it}
+ * and then its elements, two a word; segments have an element at least, but the pattern without any '%' is one segment of
+ * head and tail even when it is empty.  A word 0 ends the program: the room is zeroed, so it is there. */
+static bool like_compile(const uint8_t *pat, uint32_t n, bool utf8, uint32_t *out)
+{
+    uint16_t el[CRYO_KEY_BYTES_MAX];
+    uint32_t ne = 0, w = 0;
+    bool cut = false; /* a '%' stands before the segment being read */
+    const auto flush = [&](bool tail) {
+        if (out) {
+            out[w] = ne | (ne ? (uint32_t)el[0] << 16 : 0u) | (utf8 ? kLikeUtf8 : 0u) | (cut ? 0u : kLikeHead) | (tail ? kLikeTail : 0u);
+            for (uint32_t e = 0; e < ne; e++) out[w + 1 + (e >> 1)] |= (uint32_t)el[e] << (16 * (e & 1));
+        }
+        w += 1 + ((ne + 1) >> 1);
+        ne = 0;
+    };
+    for (uint32_t i = 0; i < n; i++) {
+        const uint8_t ch = pat[i];
+        if (ch == '%') {
+            if (ne) flush(false);
+            cut = true;
+        } else if (ch == '_') el[ne++] = kLikeAny;
+        else if (ch == '\\') {
+            if (++i == n) return false;
+            el[ne++] = pat[i];
+        } else el[ne++] = ch;
+    }
+    if (ne || !cut) flush(true);
+    return true;
+}
+
+/* the descriptor's rules (include/cryo_codec.h); atts and keys are host memory here.  *max_att: the highest key column.  In the
+ * host-buffer calls keys is f->keys itself, and the address in a pattern key's value is host memory: the pattern is looked at
+ * here.  In the device-resident calls keys is the library's copy of a device array and the pattern is looked at once it has
+ * been read back (key_table_device) */
 static bool filter_desc_ok(const cryo_filter *f, const cryo_att *atts, const cryo_scan_key *keys, uint32_t *max_att)
 {
     *max_att = 0;
@@ -1238,13 +1292,22 @@ static bool filter_desc_ok(const cryo_filter *f, const cryo_att *atts, const cry
     for (uint32_t k = 0; k < f->nkeys; k++) {
         const cryo_scan_key &q = keys[k];
         const bool cmp = q.op >= CRYO_OP_LT && q.op <= CRYO_OP_NE, set = q.op == CRYO_OP_IN || q.op == CRYO_OP_NOT_IN;
-        if ((q.rsv != 0 && !(cmp && q.type == CRYO_KEY_BYTES) && !set) || q.att == 0 || q.att > f->natts || q.op < CRYO_OP_LT ||
-            q.op > CRYO_OP_NOT_IN)
+        const bool like = key_is_like(q);
+        if ((q.rsv != 0 && !(cmp && q.type == CRYO_KEY_BYTES) && !set && !like) || q.att == 0 || q.att > f->natts || q.op < CRYO_OP_LT ||
+            q.op > CRYO_OP_NOT_LIKE)
             return false;
         if (q.att > *max_att) *max_att = q.att;
         if (q.op == CRYO_OP_ISNULL || q.op == CRYO_OP_NOTNULL) continue;
         /* a set key: rsv the members, value their address, not looked at here beyond null; the members are never looked at */
         if (set && (q.rsv == 0 || q.rsv > CRYO_KEY_SET_MAX || q.value == 0)) return false;
+        if (like) { /* rsv: the pattern's length and CRYO_LIKE_UTF8; value: the pattern's address */
+            const uint32_t n = q.rsv & 0xFFFFu;
+            if (q.type != CRYO_KEY_BYTES || atts[q.att - 1].attlen != -1 || (q.rsv & ~(0xFFFFu | CRYO_LIKE_UTF8)) != 0 ||
+                n > CRYO_KEY_BYTES_MAX || (n > 0 && q.value == 0))
+                return false;
+            if (keys == f->keys && !like_compile((const uint8_t *)(uintptr_t)q.value, n, false, nullptr)) return false;
+            continue;
+        }
         if (q.type == CRYO_KEY_BYTES && !set) { /* rsv: the constant's length; value: its address, not looked at here beyond null */
             if (atts[q.att - 1].attlen != -1 || q.rsv > CRYO_KEY_BYTES_MAX || (q.rsv > 0 && q.value == 0)) return false;
             continue;
@@ -1274,8 +1337,11 @@ static bool filter_desc_ok(const cryo_filter *f, const cryo_att *atts, const cry
  * ascending as signed 64-bit integers, in the room of the rsv members the caller named; the table's copy of the key has rsv
  * rewritten to the distinct count and value to the set's device address.  A float key (CRYO_KEY_FLOAT4, CRYO_KEY_FLOAT8) has no
  * constant behind the keys, but the table's copy of it has value rewritten to the mapped form of the double (float_map_host),
- * which the kernels compare as an integer.  A descriptor without any of these kinds of key has no table: its keys go to the
- * device as they are. */
+ * which the kernels compare as an integer.  A pattern key (CRYO_OP_LIKE, CRYO_OP_NOT_LIKE) travels compiled: the pattern's n
+ * bytes stay with the caller, and among the constants lie like_room(n) = 4 n + 16 bytes -- a room that n alone decides, so that
+ * the table's size is known before a device-resident pattern has been read back --, 8-byte aligned, holding the program of
+ * like_compile and zeros behind it; the table's copy of the key has value rewritten to the program's device address and keeps
+ * its rsv.  A descriptor without any of these kinds of key has no table: its keys go to the device as they are. */
 static constexpr size_t kKeyConstMax = 8u * CRYO_KEY_SET_MAX; /* the most bytes one key's constant or list takes */
 static_assert(kKeyConstMax >= CRYO_KEY_BYTES_MAX, "a list is the largest constant");
 static constexpr size_t kKeyTableBytes = CRYO_FILTER_MAX_KEYS * (sizeof(cryo_scan_key) + kKeyConstMax);
@@ -1288,8 +1354,14 @@ static_assert(kKeyTableBytes % 16 == 0 && kBucketTableBytes % 16 == 0, "both tab
 static bool key_is_bytes(const cryo_scan_key &q) { return q.type == CRYO_KEY_BYTES && q.op >= CRYO_OP_LT && q.op <= CRYO_OP_NE; }
 static bool key_is_set(const cryo_scan_key &q) { return q.op == CRYO_OP_IN || q.op == CRYO_OP_NOT_IN; }
 static bool key_is_float(const cryo_scan_key &q) { return type_is_float(q.type) && q.op >= CRYO_OP_LT && q.op <= CRYO_OP_NE; }
-/* the bytes at a (valid) key's address: a byte-string constant's, a list's; 0: the key has none */
-static size_t key_const_len(const cryo_scan_key &q) { return key_is_set(q) ? (size_t)q.rsv * 8 : key_is_bytes(q) ? (size_t)q.rsv : 0; }
+/* the bytes at a (valid) key's address: a byte-string constant's, a list's, a pattern's; 0: the key has none */
+static size_t key_raw_len(const cryo_scan_key &q)
+{
+    return key_is_set(q) ? (size_t)q.rsv * 8 : key_is_bytes(q) ? (size_t)q.rsv : key_is_like(q) ? (size_t)(q.rsv & 0xFFFFu) : 0;
+}
+/* the bytes a (valid) key takes among the table's constants, before they are rounded up to 8: what lies at its address, but a
+ * pattern's room */
+static size_t key_const_len(const cryo_scan_key &q) { return key_is_like(q) ? like_room(q.rsv & 0xFFFFu) : key_raw_len(q); }
 
 /* the bytes the constants take behind the keys of a (valid) descriptor, a multiple of 16; *any: some key needs the table */
 static size_t key_consts_bytes(const cryo_scan_key *keys, uint32_t nkeys, bool *any)
@@ -1297,14 +1369,17 @@ static size_t key_consts_bytes(const cryo_scan_key *keys, uint32_t nkeys, bool *
     size_t b = 0;
     *any = false;
     for (uint32_t k = 0; k < nkeys; k++)
-        if (key_is_bytes(keys[k]) || key_is_set(keys[k])) { *any = true; b += (key_const_len(keys[k]) + 7) & ~(size_t)7; }
+        if (key_is_bytes(keys[k]) || key_is_set(keys[k]) || key_is_like(keys[k])) { *any = true; b += (key_const_len(keys[k]) + 7) & ~(size_t)7; }
         else if (key_is_float(keys[k])) *any = true;
     return (b + 15) & ~(size_t)15;
 }
 
 /* the key table of a (valid) descriptor at tab (zeroed, nkeys * 16 + key_consts_bytes bytes), which will lie at device address
- * d_tab; consts[k]: where the host finds the constant of key k */
-static void key_table_fill(uint8_t *tab, uint64_t d_tab, const cryo_scan_key *keys, uint32_t nkeys, const void *const *consts)
+ * d_tab; consts[k]: where the host finds the constant of key k.  A pattern key's room holds, from its first byte on, 32-bit
+ * words: per segment of the pattern {ne | first element << 16 | kLikeUtf8 | kLikeHead | kLikeTail} and ceil(ne / 2) words of two
+ * 16-bit elements each (a literal byte, or kLikeAny), the low half first; then a word 0, and zeros to the room's end
+ * (like_compile).  False: a pattern ends in an unescaped '\' -- the device-resident calls learn it here */
+static bool key_table_fill(uint8_t *tab, uint64_t d_tab, const cryo_scan_key *keys, uint32_t nkeys, const void *const *consts)
 {
     size_t at = (size_t)nkeys * sizeof(cryo_scan_key);
     for (uint32_t k = 0; k < nkeys; k++) {
@@ -1322,10 +1397,16 @@ static void key_table_fill(uint8_t *tab, uint64_t d_tab, const cryo_scan_key *ke
             if (q.rsv) memcpy(tab + at, consts[k], q.rsv);
             q.value = (int64_t)(d_tab + at);
             at += ((size_t)q.rsv + 7) & ~(size_t)7;
+        } else if (key_is_like(q)) { /* at is a multiple of 8, and so is the room rounded up */
+            const uint32_t n = q.rsv & 0xFFFFu;
+            if (!like_compile((const uint8_t *)consts[k], n, (q.rsv & CRYO_LIKE_UTF8) != 0, reinterpret_cast<uint32_t *>(tab + at))) return false;
+            q.value = (int64_t)(d_tab + at);
+            at += (like_room(n) + 7) & ~(size_t)7;
         } else if (key_is_float(q))
             q.value = float_map_host((uint64_t)q.value);
         memcpy(tab + (size_t)k * sizeof(cryo_scan_key), &q, sizeof q);
     }
+    return true;
 }
 
 /* the device-resident calls: keys (host copy, validated) name constants and lists in DEVICE memory.  Reads them back together (at
@@ -1338,34 +1419,34 @@ static int key_table_device(cryo_codec *c, const cryo_scan_key *keys, uint32_t n
     std::vector<uint8_t> consts(CRYO_FILTER_MAX_KEYS * kKeyConstMax), tab((size_t)nkeys * sizeof(cryo_scan_key) + cb, 0);
     const void *where[CRYO_FILTER_MAX_KEYS] = {nullptr, nullptr, nullptr, nullptr};
     for (uint32_t k = 0; k < nkeys; k++) {
-        const size_t len = key_const_len(keys[k]);
+        const size_t len = key_raw_len(keys[k]);
         if (len == 0) continue;
         where[k] = consts.data() + (size_t)k * kKeyConstMax;
         HIP_TRY(c, hipMemcpyAsync((void *)where[k], (const void *)(uintptr_t)keys[k].value, len, hipMemcpyDeviceToHost, c->stream));
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (!c->d_keytab) HIP_TRY(c, hipMalloc(&c->d_keytab, kDescTablesBytes));
-    key_table_fill(tab.data(), (uint64_t)(uintptr_t)c->d_keytab, keys, nkeys, where);
+    if (!key_table_fill(tab.data(), (uint64_t)(uintptr_t)c->d_keytab, keys, nkeys, where)) return CRYO_E_ARG;
     HIP_TRY(c, hipMemcpyAsync(c->d_keytab, tab.data(), tab.size(), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream)); /* tab is the call's own: gone when it returns */
     *d_keys = c->d_keytab;
     return CRYO_OK;
 }
 
-/* the host-buffer calls: the table into the pinned copy of the descriptor at pin_keys, which the upload puts at d_keys.  Returns
- * whether the descriptor has a key that needs the table */
+/* the host-buffer calls: the table into the pinned copy of the descriptor at pin_keys, which the upload puts at d_keys.  False:
+ * a pattern does not compile (filter_desc_ok refuses it first when it is handed f->keys; a caller that was not is told here,
+ * and uploads nothing) */
 static bool key_table_host(uint8_t *pin_keys, const uint8_t *d_keys, const cryo_filter *f)
 {
     bool any = false;
     (void)key_consts_bytes(f->keys, f->nkeys, &any);
     if (!any) {
         if (f->nkeys) memcpy(pin_keys, f->keys, (size_t)f->nkeys * sizeof(cryo_scan_key));
-        return false;
+        return true;
     }
     const void *where[CRYO_FILTER_MAX_KEYS] = {nullptr, nullptr, nullptr, nullptr};
     for (uint32_t k = 0; k < f->nkeys; k++) where[k] = (const void *)(uintptr_t)f->keys[k].value;
-    key_table_fill(pin_keys, (uint64_t)(uintptr_t)d_keys, f->keys, f->nkeys, where);
-    return true;
+    return key_table_fill(pin_keys, (uint64_t)(uintptr_t)d_keys, f->keys, f->nkeys, where);
 }
 
 static int filter_pass(cryo_codec *c, int method, const uint8_t *d_src, const uint64_t *d_src_off, const uint32_t *d_src_size,
@@ -1388,7 +1469,7 @@ static int filter_pass(cryo_codec *c, int method, const uint8_t *d_src, const ui
         cryo_filter_rec *st_rec = (cryo_filter_rec *)(st_dst + row * ch.K);
         if (ch.lo == 0) HIP_TRY(c, hipMemsetAsync(running, 0, 2 * sizeof(uint64_t), c->stream));
         HIP_TRY(c, cryo::launch_filter(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.sd.d_atts, io.sd.d_keys, io.sd.nkeys, io.sd.max_att,
-                                       io.sd.truth, io.sd.floats, io.count_only, (uint4 *)(io.d_blocks + ch.lo), side, sum, base, running,
+                                       io.sd.truth, io.sd.floats, io.sd.like, io.count_only, (uint4 *)(io.d_blocks + ch.lo), side, sum, base, running,
                                        stage ? st_dst : io.d_dst, stage ? ch.K * row : io.dst_cap,
                                        stage ? (uint2 *)st_rec : (uint2 *)io.d_rec, stage ? ch.K * S : io.rec_cap, host,
                                        c->lz4_opts.cus));
@@ -1477,7 +1558,7 @@ static int agg_pass(cryo_codec *c, int method, const uint8_t *d_src, const uint6
     DecodePass ps(d_src, d_src_off, d_src_size, true);
     ps.run = [&](const DecodeChunk &ch) -> int {
         HIP_TRY(c, cryo::launch_agg(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.sd.d_atts, io.sd.d_keys, io.sd.nkeys, io.d_cols,
-                                    io.ncols, io.sd.max_att, io.sd.truth, io.sd.floats, (uint4 *)(io.d_blocks + ch.lo),
+                                    io.ncols, io.sd.max_att, io.sd.truth, io.sd.floats, io.sd.like, (uint4 *)(io.d_blocks + ch.lo),
                                     io.d_cells + ch.lo * io.ncols));
         return CRYO_OK;
     };
@@ -1646,7 +1727,7 @@ static int group_pass(cryo_codec *c, int method, const uint8_t *d_src, const uin
         }
         uint8_t *side_rec = ch.own, *side_cell = ch.own + ch.K * S * sizeof(cryo_group_rec);
         HIP_TRY(c, cryo::launch_group(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.sd.d_atts, io.sd.d_keys, io.sd.nkeys, slots, io.nby,
-                                      io.ncols, io.sd.max_att, io.sd.truth, io.sd.floats, (uint4 *)(io.d_blocks + ch.lo), side_rec, side_cell, io.d_total,
+                                      io.ncols, io.sd.max_att, io.sd.truth, io.sd.floats, io.sd.like, (uint4 *)(io.d_blocks + ch.lo), side_rec, side_cell, io.d_total,
                                       io.d_groups, io.d_cells, io.group_cap, c->lz4_opts.cus, io.sd.d_buckets, io.sd.text));
         return CRYO_OK;
     };
@@ -1725,7 +1806,7 @@ static int project_pass(cryo_codec *c, int method, const uint8_t *d_src, const u
         }
         uint8_t *side_rec = ch.own, *side_rows = ch.own + ch.K * S * sizeof(cryo_project_rec);
         HIP_TRY(c, cryo::launch_project(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.sd.d_atts, io.sd.d_keys, io.sd.nkeys, tab,
-                                        io.pt.ncols, io.pt.row_bytes, io.sd.max_att, io.sd.truth, io.sd.floats, (uint4 *)(io.d_blocks + ch.lo),
+                                        io.pt.ncols, io.pt.row_bytes, io.sd.max_att, io.sd.truth, io.sd.floats, io.sd.like, (uint4 *)(io.d_blocks + ch.lo),
                                         side_rec, side_rows, io.d_total, io.d_rec, io.rec_cap, io.d_rows, io.row_cap, c->lz4_opts.cus));
         return CRYO_OK;
     };
@@ -1804,7 +1885,7 @@ static int topn_pass(cryo_codec *c, int method, const uint8_t *d_src, const uint
         uint8_t *side_rec = ch.own, *side_rows = side_rec + ch.K * S * sizeof(cryo_topn_rec);
         uint8_t *side_ord = side_rows + ch.K * S * io.tt.row_bytes;
         HIP_TRY(c, cryo::launch_topn(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.sd.d_atts, io.sd.d_keys, io.sd.nkeys, tab, io.tt.slots,
-                                     io.tt.nby, io.tt.ncols, io.tt.row_bytes, io.tt.limit, io.sd.max_att, io.sd.truth, io.sd.floats,
+                                     io.tt.nby, io.tt.ncols, io.tt.row_bytes, io.tt.limit, io.sd.max_att, io.sd.truth, io.sd.floats, io.sd.like,
                                      (uint4 *)(io.d_blocks + ch.lo), side_rec, side_rows, side_ord, io.d_total, io.d_rec, io.d_rows, io.row_cap,
                                      c->lz4_opts.cus));
         return CRYO_OK;
@@ -2042,6 +2123,7 @@ static int scan_desc_device(cryo_codec *c, const cryo_filter *f, const cryo_grou
     int rc = key_table_device(c, keys, f->nkeys, &sd.d_keys, &table_keys);
     if (rc == CRYO_OK && d_bk) rc = bucket_table_device(c, bk, grp->nby, &sd.d_buckets);
     sd.floats = desc_has_float(keys, f->nkeys, cols, *ncols);
+    sd.like = desc_has_like(keys, f->nkeys);
     sd.truth = scan_truth(f, table_keys || sd.floats || d_bk || sd.text); /* the bucket and the text kernels have the table's verdict path alone */
     return rc;
 }
@@ -2764,12 +2846,13 @@ int cryo_codec_fetch_blocks(cryo_codec *c, int method, const void *const *h_src,
 /* The descriptor of a host-buffer scan call: [atts 4 x natts][keys 16 x nkeys][byte-string constants][the call's extra bytes:
  * the aggregate's columns, the group's six slots], each part 16-byte aligned.  It takes the first `bytes` of c->hb_meta, where
  * the call's results follow it */
-struct ScanDescLayout { size_t t_keys = 0, t_extra = 0, bytes = 0; bool table_keys = false, floats = false; };
+struct ScanDescLayout { size_t t_keys = 0, t_extra = 0, bytes = 0; bool table_keys = false, floats = false, like = false; };
 /* cols: the call's ncols aggregate columns, where it has some */
 static ScanDescLayout scan_desc_layout(const cryo_filter *f, size_t extra_bytes, const cryo_agg_col *cols = nullptr, uint32_t ncols = 0)
 {
     ScanDescLayout L;
     L.floats = desc_has_float(f->keys, f->nkeys, cols, ncols);
+    L.like = desc_has_like(f->keys, f->nkeys);
     L.t_keys = ((size_t)f->natts * 4 + 15) & ~(size_t)15;
     L.t_extra = L.t_keys + (size_t)f->nkeys * 16 + key_consts_bytes(f->keys, f->nkeys, &L.table_keys);
     L.bytes = L.t_extra + extra_bytes;
@@ -2786,11 +2869,11 @@ static int scan_desc_upload(cryo_codec *c, const void *const *h_src, const uint3
     uint8_t *pin = (uint8_t *)c->pin + sg.o_tail;
     memset(pin, 0, L.bytes);
     memcpy(pin, f->atts, (size_t)f->natts * 4);
-    (void)key_table_host(pin + L.t_keys, c->hb_meta + L.t_keys, f);
+    if (!key_table_host(pin + L.t_keys, c->hb_meta + L.t_keys, f)) return CRYO_E_ARG;
     if (L.bytes > L.t_extra) memcpy(pin + L.t_extra, extra, L.bytes - L.t_extra);
     HIP_TRY(c, hipMemcpyAsync(c->hb_meta, pin, L.bytes, hipMemcpyHostToDevice, c->stream));
     c->xfer_ctr.h2d_bytes += L.bytes;
-    sd.d_atts = c->hb_meta; sd.d_keys = c->hb_meta + L.t_keys; sd.nkeys = f->nkeys; sd.max_att = max_att; sd.floats = L.floats; sd.truth = scan_truth(f, L.table_keys || L.floats);
+    sd.d_atts = c->hb_meta; sd.d_keys = c->hb_meta + L.t_keys; sd.nkeys = f->nkeys; sd.max_att = max_att; sd.floats = L.floats; sd.like = L.like; sd.truth = scan_truth(f, L.table_keys || L.floats);
     return CRYO_OK;
 }
 

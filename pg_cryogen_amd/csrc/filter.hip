@@ -29,12 +29,10 @@
 
 namespace cryo {
 
-constexpr uint32_t kFilterPiece = 256u * 8u;  /* packed bytes one workgroup copies per turn */
-
 /* One sweep over a block's items.  WRITE = false: the sums {MAXALIGNed bytes of the matches, matches, bad items}.  WRITE = true:
  * the side table's entries in position order; `overlap` drops the matches.  An undecided tuple is a bad item: counted, and listed
  * with its status and no bytes. */
-template <bool WRITE, bool BYTES, bool FLOATS = false>
+template <bool WRITE, bool BYTES, bool FLOATS = false, bool LIKE = false>
 __device__ inline void filter_sweep(const uint8_t *__restrict__ p, uint32_t B, uint32_t n, uint32_t upper, uint32_t lane,
                                     const FilterAtt *__restrict__ atts, const FilterKey *__restrict__ keys, uint32_t nkeys,
                                     uint32_t max_att, bool overlap, uint4 *__restrict__ side, uint64_t &bytes, uint32_t &n_match,
@@ -44,8 +42,8 @@ __device__ inline void filter_sweep(const uint8_t *__restrict__ p, uint32_t B, u
     uint32_t recs = 0, matches = 0, bads = 0;
     for (uint32_t t0 = 0; t0 < n; t0 += 64u) {
         const uint32_t i = t0 + lane;
-        const SweepItem it = sweep_turn<false, kAggMaxCols, BYTES, false, FLOATS>(p, B, n, upper, i, atts, keys, nkeys, max_att, nullptr, 0u,
-                                                                                 nullptr); /* the walk without capture */
+        const SweepItem it = sweep_turn<false, kAggMaxCols, BYTES, false, FLOATS, false, LIKE>(p, B, n, upper, i, atts, keys, nkeys, max_att,
+                                                                                              nullptr, 0u, nullptr); /* the walk without capture */
         const uint32_t status = it.verdict, len = it.len, src = it.src;
         const bool match = it.match, bad = it.bad;
         const unsigned long long mm = __ballot(match), mb = __ballot(bad);
@@ -79,8 +77,9 @@ __device__ inline void filter_sweep(const uint8_t *__restrict__ p, uint32_t B, u
     n_bad = bads;
 }
 
-/* the body of k_filter_match and of k_filterf_match, the kernel of descriptors with a float key */
-template <bool BYTES, bool FLOATS>
+/* the body of k_filter_match, of k_filterf_match, the kernel of descriptors with a float key, and of k_filterl_match, the kernel
+ * of descriptors with a pattern key */
+template <bool BYTES, bool FLOATS, bool LIKE = false>
 __device__ inline void filter_block_body(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, uint32_t cnt,
                                          const int32_t *__restrict__ dec_status, const FilterAtt *__restrict__ atts,
                                          const FilterKey *__restrict__ keys, uint32_t nkeys, uint32_t max_att, uint32_t count_only,
@@ -96,12 +95,12 @@ __device__ inline void filter_block_body(const uint8_t *__restrict__ dec, uint64
     uint32_t n, upper; /* lower <= B: n <= side_stride */
     uint32_t status = sweep_open(dec, dec_stride, B, dec_status, k, p, n, upper);
     if (status == 0u) {
-        filter_sweep<false, BYTES, FLOATS>(p, B, n, upper, lane, atts, keys, nkeys, max_att, false, nullptr, bytes, n_match, n_bad);
+        filter_sweep<false, BYTES, FLOATS, LIKE>(p, B, n, upper, lane, atts, keys, nkeys, max_att, false, nullptr, bytes, n_match, n_bad);
         if (!count_only) {
             const bool overlap = bytes > (uint64_t)(B - upper);
             uint64_t b2;
             uint32_t m2, x2;
-            filter_sweep<true, BYTES, FLOATS>(p, B, n, upper, lane, atts, keys, nkeys, max_att, overlap, side + (uint64_t)k * side_stride, b2,
+            filter_sweep<true, BYTES, FLOATS, LIKE>(p, B, n, upper, lane, atts, keys, nkeys, max_att, overlap, side + (uint64_t)k * side_stride, b2,
                                               m2, x2);
             if (overlap) { status = kFilterOverlap; n_match = 0; bytes = 0; }
         }
@@ -115,6 +114,9 @@ __device__ inline void filter_block_body(const uint8_t *__restrict__ dec, uint64
         }
     }
 }
+
+#ifndef CRYO_LIKE_UNIT
+constexpr uint32_t kFilterPiece = 256u * 8u;  /* packed bytes one workgroup copies per turn */
 
 template <bool BYTES>
 __global__ void __launch_bounds__(256)
@@ -223,20 +225,24 @@ k_filter_copy(uint32_t cnt, const uint8_t *__restrict__ dec, uint64_t dec_stride
 
 hipError_t launch_filter(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
                          const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, uint32_t max_att,
-                         uint32_t truth, bool floats, bool count_only, uint4 *d_blocks, uint4 *d_side, uint64_t *d_sum, uint64_t *d_base, uint64_t *d_running,
+                         uint32_t truth, bool floats, bool like, bool count_only, uint4 *d_blocks, uint4 *d_side, uint64_t *d_sum, uint64_t *d_base, uint64_t *d_running,
                          uint8_t *d_dst, uint64_t dst_cap, uint2 *d_rec, uint64_t rec_cap, bool chunk_relative, int cus)
 {
     if (cnt == 0) return hipSuccess;
-    if (!scan_launch_ok(dec_stride, d_dec, d_blocks, d_atts, d_keys, (uintptr_t)d_dst | (uintptr_t)d_rec, block_size, nkeys, truth, floats) ||
+    if (!scan_launch_ok(dec_stride, d_dec, d_blocks, d_atts, d_keys, (uintptr_t)d_dst | (uintptr_t)d_rec, block_size, nkeys, truth, floats || like) ||
         ((uintptr_t)d_side & 15u) != 0)
         return hipErrorInvalidValue;
     const uint32_t stride = filter_side_stride(block_size);
     /* the integer-only descriptor keeps its own instantiation: the code it had before byte-string keys; a float key has a kernel
-     * of its own */
-    hipLaunchKernelGGL(floats ? k_filterf_match : truth ? k_filter_match<true> : k_filter_match<false>, dim3((cnt + 3u) / 4u), dim3(256), 0, s, d_dec,
-                       dec_stride, block_size, cnt, d_dec_status, (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys | truth << 16, max_att,
-                       count_only ? 1u : 0u, stride, d_blocks, d_side, d_sum);
-    hipError_t e = hipGetLastError();
+     * of its own, and a pattern key one in a unit of its own (below) */
+    hipError_t e;
+    if (like) e = launch_filterl_match(s, d_dec, dec_stride, block_size, cnt, d_dec_status, d_atts, d_keys, nkeys, max_att, truth, count_only, stride, d_blocks, d_side, d_sum);
+    else {
+        hipLaunchKernelGGL(floats ? k_filterf_match : truth ? k_filter_match<true> : k_filter_match<false>, dim3((cnt + 3u) / 4u), dim3(256), 0, s, d_dec,
+                           dec_stride, block_size, cnt, d_dec_status, (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys | truth << 16, max_att,
+                           count_only ? 1u : 0u, stride, d_blocks, d_side, d_sum);
+        e = hipGetLastError();
+    }
     if (e != hipSuccess || count_only) return e;
     hipLaunchKernelGGL(k_filter_offsets, dim3(1), dim3(256), 0, s, cnt, d_sum, d_base, d_running, d_blocks);
     e = hipGetLastError();
@@ -250,5 +256,33 @@ hipError_t launch_filter(hipStream_t s, const uint8_t *d_dec, uint64_t dec_strid
                        dst_cap, d_rec, rec_cap, chunk_relative ? 1u : 0u);
     return hipGetLastError();
 }
+
+#else /* CRYO_LIKE_UNIT */
+/* k_filterf_match whose walk also matches the patterns of CRYO_OP_LIKE / CRYO_OP_NOT_LIKE keys (walk_like): a kernel of its own
+ * name, because the matcher inlined costs the walk registers -- k_filter_match<true> and k_filterf_match would fall from eight
+ * waves per SIMD to seven -- and a descriptor without such a key must run what it ran.  It is built from this source compiled
+ * a second time with CRYO_LIKE_UNIT (filter_like.o, the Makefile's rule), which holds this kernel and its launcher alone */
+__global__ void __launch_bounds__(256)
+k_filterl_match(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, uint32_t cnt,
+                const int32_t *__restrict__ dec_status, const FilterAtt *__restrict__ atts, const FilterKey *__restrict__ keys,
+                uint32_t nkeys, uint32_t max_att, uint32_t count_only, uint32_t side_stride, uint4 *__restrict__ blocks,
+                uint4 *__restrict__ side, uint64_t *__restrict__ sum)
+{
+    filter_block_body<true, true, true>(dec, dec_stride, B, cnt, dec_status, atts, keys, nkeys, max_att, count_only, side_stride, blocks,
+                                        side, sum);
+}
+
+hipError_t launch_filterl_match(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
+                                const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, uint32_t max_att,
+                                uint32_t truth, bool count_only, uint32_t side_stride, uint4 *d_blocks, uint4 *d_side, uint64_t *d_sum)
+{
+    /* the arguments are launch_filter's, which checked them; the one verdict path needs a table */
+    if (truth == 0u) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_filterl_match, dim3((cnt + 3u) / 4u), dim3(256), 0, s, d_dec, dec_stride, block_size, cnt, d_dec_status,
+                       (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys | truth << 16, max_att, count_only ? 1u : 0u, side_stride,
+                       d_blocks, d_side, d_sum);
+    return hipGetLastError();
+}
+#endif
 
 } // namespace cryo

@@ -14,6 +14,9 @@
  * descriptors (k_filterf_match, k_projectf_block, k_aggf_block, k_groupf_block) set it, every other instantiation is textually
  * what it was.  With it a loaded column value is mapped onto the signed integer whose order is the float order (float_map)
  * when the key's type is a float type; the host has mapped the key's constant the same way, so the compare is filter_compare's.
+ * Pattern keys (CRYO_OP_LIKE, CRYO_OP_NOT_LIKE) are the last parameter, LIKE: the kernels of descriptors with such a key set it
+ * (k_filterl_match, k_aggl_block, k_groupl_block, k_groupbl_block, k_grouptl_block, k_projectl_block, k_topnl_block, each in a
+ * unit of its own), and the walk then matches the noted payloads against the library's compiled patterns (walk_like).
  */
 #pragma once
 #include <hip/hip_runtime.h>
@@ -29,6 +32,11 @@ constexpr uint32_t kWalkNoBytes = 0xFFFFFFFFu; /* inside the walk only: the payl
 constexpr int64_t kWalkTextAway = -1;           /* a TEXT capture: the varlena's bytes are not in the tuple (no place is negative) */
 constexpr uint32_t kOpLt = 1, kOpLe = 2, kOpEq = 3, kOpGe = 4, kOpGt = 5, kOpNe = 6, kOpIsNull = 7, kOpNotNull = 8;
 constexpr uint32_t kOpIn = 9, kOpNotIn = 10;  /* set keys: rsv the members, value their address in the key table */
+constexpr uint32_t kOpLike = 11, kOpNotLike = 12; /* pattern keys: value the address of the compiled pattern in the key table */
+constexpr uint32_t kLikeTextMax = 2048u;      /* CRYO_LIKE_TEXT_MAX: a longer payload leaves a pattern key undecided */
+constexpr uint32_t kLikeNone = 0xFFFFFFFFu;   /* inside walk_like only: no position */
+constexpr uint32_t kLikeUtf8 = 1u << 29, kLikeHead = 1u << 30, kLikeTail = 1u << 31; /* in a compiled pattern's segment word */
+constexpr uint32_t kLikeAny = 0x100u;         /* a pattern element that is no literal byte: any one character */
 constexpr uint32_t kSetLinear = 8u;           /* sets up to this size are scanned, larger ones searched; where the scan stops paying
                                                  is not measured: tools/set_key_cost.py reports both sides of this figure */
 constexpr uint32_t kAggMaxCols = 4u;
@@ -175,6 +183,62 @@ __device__ inline bool walk_set_has(const int64_t *__restrict__ set, uint32_t n,
     return on && set[lo] == v;
 }
 
+/* One character on from s < plen in the plen bytes at p: one byte and every byte behind it whose top two bits are 10 under the mask cont --
+ * 0xC0: the bytes 10xxxxxx, the UTF-8 rule; 0: none, a character is a byte.  Nothing at or past plen is read */
+__device__ inline uint32_t like_next(const uint8_t *__restrict__ p, uint32_t plen, uint32_t s, uint32_t cont)
+{
+    s++;
+    while (s < plen && (p[s] & cont) >> 6 == 2u) s++;
+    return s;
+}
+
+/* Whether the plen payload bytes at p match the compiled pattern at prog (the host's copy, key_table_fill: 32-bit words, the
+ * first 8-byte aligned).  A pattern is its segments -- the stretches between its unescaped '%' -- in order, then a word 0.  A
+ * segment is one word and its elements: the word holds the element count ne in bits 0-15, the first element in bits 16-24,
+ * kLikeUtf8 (the character rule), kLikeHead (the segment is matched at the payload's start and nowhere else) and kLikeTail (it
+ * must end at the payload's end); the elements follow two a word, 16 bits each: a literal byte, or kLikeAny for any one
+ * character.  '%' alone has no segment; the empty pattern has one without elements, head and tail.  Greedy by segments, no
+ * backtracking: a head segment is matched at the payload's start; every other segment at its leftmost character start at or
+ * after the end of the one before; a tail segment is searched the same way, and the start from which it ends exactly at plen is
+ * the one accepted.  The segment and the element loops run on uniform counters and read the program with uniform loads; the
+ * search for a start is per lane and runs while any lane still searches: at most plen + 1 starts a segment, so a wave does at
+ * most (plen + 1) times the pattern's elements element steps whatever the data -- with kLikeTextMax the bound is 2 049 x 256.
+ * The payload is read bytewise and never at or past plen; a lane that is not `on` or has failed loads nothing. */
+__device__ inline bool walk_like(const uint8_t *__restrict__ p, uint32_t plen, bool on, const uint32_t *__restrict__ prog)
+{
+    uint32_t pos = on ? 0u : kLikeNone, w = 0; /* pos: where the segment before ended, kLikeNone in a lane that is out; w: the segment's word, uniform */
+#pragma nounroll
+    for (uint32_t sh = prog[0]; sh != 0u; sh = prog[w]) { /* uniform */
+        const uint32_t ne = sh & 0xFFFFu, first = (sh >> 16) & 0x1FFu;
+        const uint32_t cont = (sh & kLikeUtf8) ? 0xC0u : 0u, lit = (first & kLikeAny) ? 0u : 0xFFu; /* masks; 0: that test is off */
+        uint32_t s = pos; /* the start this lane tries next; kLikeNone: it searches no more */
+        pos = kLikeNone;  /* until a start matches */
+        for (bool again = false; __ballot(s != kLikeNone) != 0; again = true) {
+            if (again) { /* uniform.  On to the next character start, and to one whose byte can be the segment's first */
+                while (s < plen) {
+                    const uint32_t b = p[s];
+                    if ((b & cont) >> 6 != 2u && (b & lit) == (first & lit)) break;
+                    s++;
+                }
+            }
+            if (s != kLikeNone && plen - s < ne) s = kLikeNone; /* s <= plen; an element takes a byte at least: no later start fits either */
+            uint32_t q = s; /* kLikeNone: an element did not match */
+#pragma nounroll
+            for (uint32_t e = 0; e < ne; e++) {
+                const uint32_t el = (prog[w + 1u + (e >> 1)] >> (16u * (e & 1u))) & 0xFFFFu; /* uniform */
+                if (q >= plen) q = kLikeNone; /* kLikeNone is above every plen */
+                else if (el & kLikeAny) q = like_next(p, plen, q, cont);
+                else q = p[q] == el ? q + 1u : kLikeNone;
+            }
+            if (s == kLikeNone) continue;
+            if (q != kLikeNone && (!(sh & kLikeTail) || q == plen)) { pos = q; s = kLikeNone; }
+            else s = (sh & kLikeHead) || s >= plen ? kLikeNone : s + 1u;
+        }
+        w += 1u + ((ne + 1u) >> 1);
+    }
+    return pos != kLikeNone;
+}
+
 /* The verdict on one tuple of len bytes at t (8-byte aligned): 0 a match, kFilterNoMatch, kFilterTuple or -- BYTES alone --
  * kFilterUndecided.  `live` is false in
  * lanes without a tuple: they make the same trips and load nothing.  Invariant of the walk: hoff + o <= len.  CAPTURE: the walk
@@ -190,8 +254,14 @@ __device__ inline bool walk_set_has(const int64_t *__restrict__ set, uint32_t n,
  * kKeyFloat8 holds its constant mapped (float_map, the host's rewrite) and the column's value is mapped before the compare;
  * a capture stays the raw bits.  TEXT (with BYTES alone; k_groupt_block's, group_text.hip): a captured column of type kKeyBytes is
  * a varlena, and its slot notes where the payload lies instead of a value: the payload's offset from t in the low half and its
- * length in the high half, or kWalkTextAway when the bytes are not in the tuple; the walk itself loads none of them. */
-template <bool CAPTURE, uint32_t SLOTS = kAggMaxCols, bool BYTES = false, bool NARROW = false, bool FLOATS = false, bool TEXT = false>
+ * length in the high half, or kWalkTextAway when the bytes are not in the tuple; the walk itself loads none of them.  LIKE (with
+ * BYTES alone; the kernels of descriptors with a pattern key, k_filterl_match and its six siblings): a key of op kOpLike /
+ * kOpNotLike matches the in-line payload of its column, of up to kLikeTextMax bytes, against the compiled pattern at value
+ * (walk_like); an external, a compressed and a longer payload leave the key undecided, as a byte-string compare's.  The column
+ * loop only notes where the payload lies; the match runs behind it, where the loop's scalar state is dead -- inside it the
+ * matcher's own made the compiler spill.  Without LIKE no key has those ops, and every instantiation is textually what it was. */
+template <bool CAPTURE, uint32_t SLOTS = kAggMaxCols, bool BYTES = false, bool NARROW = false, bool FLOATS = false, bool TEXT = false,
+          bool LIKE = false>
 __device__ inline uint32_t walk_tuple(const uint8_t *__restrict__ t, uint32_t len, bool live, const FilterAtt *__restrict__ atts,
                                       const FilterKey *__restrict__ keys, uint32_t nkeys, uint32_t max_att,
                                       const AggCol *__restrict__ cols, uint32_t ncols,
@@ -200,6 +270,11 @@ __device__ inline uint32_t walk_tuple(const uint8_t *__restrict__ t, uint32_t le
     uint32_t tnatts = 0, hoff = 0, tmask = 0, umask = 0; /* tmask, umask: BYTES alone */
     bool hasnull = false, bad = false, pass = true;
     const uint32_t truth = BYTES ? nkeys >> 16 : 0u; /* uniform */
+    uint32_t like_at[4], like_len[4]; /* LIKE alone: where the payload of pattern key k lies from t, and its length or kLikeNone */
+    if (LIKE) {
+#pragma unroll
+        for (uint32_t j = 0; j < 4u; j++) { like_at[j] = 0; like_len[j] = kLikeNone; }
+    }
     if (BYTES) nkeys &= 0xFFFFu;
     if (live) {
         if (len < 23u) bad = true;
@@ -257,7 +332,16 @@ __device__ inline uint32_t walk_tuple(const uint8_t *__restrict__ t, uint32_t le
             if (key.att != col) continue;
             if (key.op == kOpIsNull) walk_note<BYTES>(pass, tmask, k, isnull);
             else if (key.op == kOpNotNull) walk_note<BYTES>(pass, tmask, k, !isnull);
-            else if (BYTES && key.op >= kOpIn) {
+            else if (LIKE && key.op >= kOpLike) { /* uniform.  The column is a varlena (the argument rule), as for a byte-string compare */
+                const bool can = val && head != kWalkNoBytes && size - head <= kLikeTextMax;
+                if (val && !can) umask |= 1u << k; /* external, compressed in line, or too long to search here */
+#pragma unroll
+                for (uint32_t j = 0; j < 4u; j++) { /* unrolled: both stay in registers */
+                    if (j != k) continue; /* uniform */
+                    like_at[j] = pos + head;
+                    like_len[j] = can ? size - head : kLikeNone;
+                }
+            } else if (BYTES && key.op >= kOpIn) {
                 /* the column rule is the comparison key's: the same load.  Never undecided; false on a NULL column */
                 const int64_t v = val ? walk_value(t + pos, a.attlen) : 0;
                 const bool in = walk_set_has(reinterpret_cast<const int64_t *>(key.value), key.rsv, v, val);
@@ -293,6 +377,19 @@ __device__ inline uint32_t walk_tuple(const uint8_t *__restrict__ t, uint32_t le
             }
         }
         if (val) pos += size;
+    }
+    if (LIKE) { /* the pattern keys, now that the walk's own state is done with: what they note is walk_note's */
+        for (uint32_t k = 0; k < nkeys; k++) {
+            const uint32_t op = keys[k].op; /* uniform */
+            if (op < kOpLike) continue;
+            uint32_t at = 0, plen = kLikeNone;
+#pragma unroll
+            for (uint32_t j = 0; j < 4u; j++)
+                if (j == k) { at = like_at[j]; plen = like_len[j]; } /* uniform */
+            const bool can = plen != kLikeNone; /* a good tuple, the column not NULL, its payload in the tuple and within the cap */
+            const bool hit = walk_like(t + (can ? at : 0u), can ? plen : 0u, can, reinterpret_cast<const uint32_t *>(keys[k].value));
+            if (can && hit == (op == kOpLike)) tmask |= 1u << k;
+        }
     }
     if (BYTES) /* tmask and umask are below 16: both shifts stay within the table's 16 bits */
         return bad ? kFilterTuple : ((truth >> tmask) & 1u) ? 0u : ((truth >> (tmask | umask)) & 1u) ? kFilterUndecided : kFilterNoMatch;

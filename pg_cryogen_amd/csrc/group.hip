@@ -80,7 +80,7 @@ k_group_copy(uint32_t cnt, uint32_t side_stride, uint32_t ncols, const uint4 *__
 
 hipError_t launch_group(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
                         const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,
-                        uint32_t nby, uint32_t ncols, uint32_t max_att, uint32_t truth, bool floats, uint4 *d_blocks, void *d_side_rec, void *d_side_cell,
+                        uint32_t nby, uint32_t ncols, uint32_t max_att, uint32_t truth, bool floats, bool like, uint4 *d_blocks, void *d_side_rec, void *d_side_cell,
                         uint64_t *d_running, void *d_rec, void *d_cells, uint64_t group_cap, int cus, const void *d_buckets, uint32_t text)
 {
     if (cnt == 0) return hipSuccess;
@@ -88,18 +88,27 @@ hipError_t launch_group(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride
     if (!scan_launch_ok(dec_stride, d_dec, d_blocks, d_atts, d_keys,
                         (uintptr_t)d_rec | (uintptr_t)d_cells | (uintptr_t)d_slots | (uintptr_t)d_side_rec | (uintptr_t)d_side_cell |
                             (uintptr_t)d_running,
-                        block_size, nkeys, truth, floats) ||
+                        block_size, nkeys, truth, floats || like) ||
         nby == 0u || nby > kGroupMaxBy || ncols > kAggMaxCols || (text >> nby) != 0u || (text != 0u && d_buckets) ||
         !d_slots || !d_side_rec || !d_running || (cpg > 0u && !d_side_cell) || (group_cap > 0u && (!d_rec || (cpg > 0u && !d_cells))))
         return hipErrorInvalidValue;
     const uint32_t stride = filter_side_stride(block_size);
     hipError_t e;
-    if (text) /* a byte-string group column: group_text.hip's block kernels, then the same two on cpg cells a group */
+    if (text && like) /* a byte-string group column and a pattern key: group_text.hip's second unit, then the same two on cpg cells */
+        e = launch_grouptl_block(s, d_dec, dec_stride, block_size, cnt, d_dec_status, d_atts, d_keys, nkeys, d_slots, nby, ncols, text,
+                                 max_att, truth, stride, d_blocks, d_side_rec, d_side_cell);
+    else if (text) /* a byte-string group column: group_text.hip's block kernels, then the same two on cpg cells a group */
         e = launch_groupt_block(s, d_dec, dec_stride, block_size, cnt, d_dec_status, d_atts, d_keys, nkeys, d_slots, nby, ncols, text,
                                 max_att, truth, floats, stride, d_blocks, d_side_rec, d_side_cell);
+    else if (d_buckets && like) /* buckets and a pattern key: group_bucket.hip's second unit, then the same two */
+        e = launch_groupbl_block(s, d_dec, dec_stride, block_size, cnt, d_dec_status, d_atts, d_keys, nkeys, d_slots, d_buckets, nby, ncols,
+                                 max_att, truth, stride, d_blocks, d_side_rec, d_side_cell);
     else if (d_buckets) /* a CRYO_GROUP_BUCKETS descriptor: group_bucket.hip's block kernels, then the same two */
         e = launch_groupb_block(s, d_dec, dec_stride, block_size, cnt, d_dec_status, d_atts, d_keys, nkeys, d_slots, d_buckets, nby, ncols,
                                 max_att, truth, floats, stride, d_blocks, d_side_rec, d_side_cell);
+    else if (like) /* a pattern key: group_float.hip's second unit, then the same two */
+        e = launch_groupl_block(s, d_dec, dec_stride, block_size, cnt, d_dec_status, d_atts, d_keys, nkeys, d_slots, nby, ncols, max_att,
+                                truth, stride, d_blocks, d_side_rec, d_side_cell);
     else if (floats) /* a float key or a float aggregate column: group_float.hip's block kernel, then the same two */
         e = launch_groupf_block(s, d_dec, dec_stride, block_size, cnt, d_dec_status, d_atts, d_keys, nkeys, d_slots, nby, ncols, max_att,
                                 truth, stride, d_blocks, d_side_rec, d_side_cell);

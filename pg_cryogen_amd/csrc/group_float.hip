@@ -19,6 +19,7 @@
 
 namespace cryo {
 
+#ifndef CRYO_LIKE_UNIT
 __global__ void __launch_bounds__(64 * kGroupWaves)
 k_groupf_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, uint32_t cnt, const int32_t *__restrict__ dec_status,
                const FilterAtt *__restrict__ atts, const FilterKey *__restrict__ keys, uint32_t nkeys,
@@ -46,5 +47,39 @@ hipError_t launch_groupf_block(hipStream_t s, const uint8_t *d_dec, uint64_t dec
                        (AggCell *)d_side_cell);
     return hipGetLastError();
 }
+
+#else /* CRYO_LIKE_UNIT */
+/* k_groupf_block whose walk also matches the patterns of CRYO_OP_LIKE / CRYO_OP_NOT_LIKE keys (walk_like), for every descriptor
+ * with such a key that has neither buckets nor a text group column: a kernel of its own name, so that k_group_block<true> and
+ * k_groupf_block stay the code they were.  Built from this source compiled a second time with CRYO_LIKE_UNIT
+ * (group_float_like.o) */
+__global__ void __launch_bounds__(64 * kGroupWaves)
+k_groupl_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, uint32_t cnt, const int32_t *__restrict__ dec_status,
+               const FilterAtt *__restrict__ atts, const FilterKey *__restrict__ keys, uint32_t nkeys,
+               const AggCol *__restrict__ slots, uint32_t nby, uint32_t ncols, uint32_t max_att, uint32_t side_stride,
+               uint4 *__restrict__ blocks, GroupRec *__restrict__ side_rec, AggCell *__restrict__ side_cell)
+{
+    __shared__ GroupLds lds[kGroupWaves];
+    uint32_t k, lane;
+    GroupLds &L = lds[sweep_wave(kGroupWaves, k, lane)];
+    if (k >= cnt) return;
+    group_block<true, true, true>(L, k, lane, dec, dec_stride, B, dec_status, atts, keys, nkeys, slots, nby, ncols, max_att, side_stride,
+                                  blocks, side_rec, side_cell);
+}
+
+hipError_t launch_groupl_block(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
+                               const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,
+                               uint32_t nby, uint32_t ncols, uint32_t max_att, uint32_t truth, uint32_t side_stride, uint4 *d_blocks,
+                               void *d_side_rec, void *d_side_cell)
+{
+    /* the arguments are launch_group's, which checked them; the one verdict path needs a table */
+    if (truth == 0u) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_groupl_block, dim3((cnt + kGroupWaves - 1u) / kGroupWaves), dim3(64 * kGroupWaves), 0, s, d_dec, dec_stride,
+                       block_size, cnt, d_dec_status, (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys | truth << 16,
+                       (const AggCol *)d_slots, nby, ncols, max_att, side_stride, d_blocks, (GroupRec *)d_side_rec,
+                       (AggCell *)d_side_cell);
+    return hipGetLastError();
+}
+#endif
 
 } // namespace cryo

@@ -46,10 +46,10 @@ __device__ inline void group_wave_sync()
 struct GroupRawKeys { __device__ void operator()(WalkCaptureN<kGroupSlots> &, SweepItem &) const {} };
 
 /* Step 1 of a block kernel: the sweep of scan_sweep.h over an opened block, with six capture slots (slots: the nby group columns,
- * then the aggregate columns) and the walk's BYTES and FLOATS as the kernel's.  The wave compacts the matches in position order
+ * then the aggregate columns) and the walk's BYTES, FLOATS and LIKE as the kernel's.  The wave compacts the matches in position order
  * into L (ballot + popcount prefix): per match the two group values, the null bits and the captured aggregate values.  keys_of
  * sees every turn's capture and verdict first, the same call in all 64 lanes */
-template <bool BYTES, bool FLOATS, class KEYS = GroupRawKeys>
+template <bool BYTES, bool FLOATS, bool LIKE = false, class KEYS = GroupRawKeys>
 __device__ inline void group_matches(GroupLds &L, const uint8_t *__restrict__ p, uint32_t B, uint32_t n, uint32_t upper, uint32_t lane,
                                      const FilterAtt *__restrict__ atts, const FilterKey *__restrict__ keys, uint32_t nkeys,
                                      uint32_t max_att, const AggCol *__restrict__ slots, uint32_t nby, uint32_t &n_match, uint32_t &n_bad,
@@ -59,8 +59,8 @@ __device__ inline void group_matches(GroupLds &L, const uint8_t *__restrict__ p,
     const uint32_t by_mask = (1u << nby) - 1u;
     for (uint32_t t0 = 0; t0 < n; t0 += 64u) {
         WalkCaptureN<kGroupSlots> cap;
-        SweepItem it = sweep_turn<true, kGroupSlots, BYTES, false, FLOATS>(p, B, n, upper, t0 + lane, atts, keys, nkeys, max_att, slots,
-                                                                          kGroupSlots, &cap);
+        SweepItem it = sweep_turn<true, kGroupSlots, BYTES, false, FLOATS, false, LIKE>(p, B, n, upper, t0 + lane, atts, keys, nkeys, max_att,
+                                                                                       slots, kGroupSlots, &cap);
         keys_of(cap, it);
         const unsigned long long mm = __ballot(it.match);
         if (it.match) {
@@ -190,7 +190,7 @@ __device__ inline uint32_t group_reduce(const GroupLds &L, uint32_t m, uint32_t 
 
 /* A block kernel on GroupLds, all of it: the wave's block opened (scan_sweep.h), steps 1 to 3 with the block's rows of the side
  * area, and the block's two rows of `blocks`.  The arguments are the kernel's own; keys_of is group_matches' */
-template <bool BYTES, bool FLOATS, class KEYS = GroupRawKeys>
+template <bool BYTES, bool FLOATS, bool LIKE = false, class KEYS = GroupRawKeys>
 __device__ inline void group_block(GroupLds &L, uint32_t k, uint32_t lane, const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B,
                                    const int32_t *__restrict__ dec_status, const FilterAtt *__restrict__ atts,
                                    const FilterKey *__restrict__ keys, uint32_t nkeys, const AggCol *__restrict__ slots, uint32_t nby,
@@ -201,7 +201,7 @@ __device__ inline void group_block(GroupLds &L, uint32_t k, uint32_t lane, const
     const uint8_t *__restrict__ p;
     uint32_t n, upper;
     const uint32_t status = sweep_open(dec, dec_stride, B, dec_status, k, p, n, upper);
-    group_matches<BYTES, FLOATS>(L, p, B, n, upper, lane, atts, keys, nkeys, max_att, slots, nby, n_match, n_bad, keys_of);
+    group_matches<BYTES, FLOATS, LIKE>(L, p, B, n, upper, lane, atts, keys, nkeys, max_att, slots, nby, n_match, n_bad, keys_of);
     group_rank(L, n_match, lane);
     const uint32_t n_groups = group_reduce<FLOATS>(L, n_match, lane, slots, ncols, ncols, side_rec + (uint64_t)k * side_stride,
                                                    side_cell + (uint64_t)k * side_stride * ncols);

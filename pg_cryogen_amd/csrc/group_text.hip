@@ -37,7 +37,7 @@ static_assert(sizeof(cryo_group_key) == sizeof(AggCell) && CRYO_GROUP_TEXT_MAX =
 static_assert(sizeof(GroupTextLds) <= 65536u, "a workgroup's LDS stays within 64 KiB");
 
 /* Step 1: group_matches with the text columns' bytes.  text: bit j set when group column j is a byte string */
-template <bool FLOATS>
+template <bool FLOATS, bool LIKE>
 __device__ inline void groupt_matches(GroupTextLds &L, const uint8_t *__restrict__ p, uint32_t B, uint32_t n, uint32_t upper, uint32_t lane,
                                       const FilterAtt *__restrict__ atts, const FilterKey *__restrict__ keys, uint32_t nkeys,
                                       uint32_t max_att, const AggCol *__restrict__ slots, uint32_t nby, uint32_t text, uint32_t &n_match,
@@ -47,8 +47,8 @@ __device__ inline void groupt_matches(GroupTextLds &L, const uint8_t *__restrict
     const uint32_t by_mask = (1u << nby) - 1u;
     for (uint32_t t0 = 0; t0 < n; t0 += 64u) {
         WalkCaptureN<kGroupSlots> cap;
-        SweepItem it = sweep_turn<true, kGroupSlots, true, false, FLOATS, true>(p, B, n, upper, t0 + lane, atts, keys, nkeys, max_att, slots,
-                                                                                kGroupSlots, &cap);
+        SweepItem it = sweep_turn<true, kGroupSlots, true, false, FLOATS, true, LIKE>(p, B, n, upper, t0 + lane, atts, keys, nkeys, max_att,
+                                                                                      slots, kGroupSlots, &cap);
         /* what the slots of the text columns noted: a match whose payload is away or too long is undecided */
         uint32_t at[kGroupMaxBy], len[kGroupMaxBy];
         bool undecided = false;
@@ -176,6 +176,32 @@ struct GroupTextKeyCells {
     }
 };
 
+/* the body of k_groupt_block and -- LIKE -- of k_grouptl_block */
+template <bool FLOATS, bool LIKE>
+__device__ inline void groupt_block_body(GroupTextLds &L, uint32_t k, uint32_t lane, const uint8_t *__restrict__ dec, uint64_t dec_stride,
+                                         uint32_t B, const int32_t *__restrict__ dec_status, const FilterAtt *__restrict__ atts,
+                                         const FilterKey *__restrict__ keys, uint32_t nkeys, const AggCol *__restrict__ slots, uint32_t nby,
+                                         uint32_t ncols, uint32_t text, uint32_t max_att, uint32_t side_stride, uint4 *__restrict__ blocks,
+                                         GroupRec *__restrict__ side_rec, AggCell *__restrict__ side_cell)
+{
+    uint32_t n_match = 0, n_bad = 0;
+    const uint8_t *__restrict__ p;
+    uint32_t n, upper;
+    const uint32_t status = sweep_open(dec, dec_stride, B, dec_status, k, p, n, upper);
+    const uint32_t cpg = ncols + (uint32_t)__popc(text); /* a group's cells: the aggregate cells, then the key cells */
+    /* 1. the matches and their text keys into LDS in position order, 2. their ranks, 3. group_reduce with the key cells */
+    groupt_matches<FLOATS, LIKE>(L, p, B, n, upper, lane, atts, keys, nkeys, max_att, slots, nby, text, n_match, n_bad);
+    groupt_rank(L, n_match, lane, text);
+    AggCell *out_cell = side_cell + (uint64_t)k * side_stride * cpg;
+    const uint32_t n_groups = group_reduce<FLOATS>(L.g, n_match, lane, slots, ncols, cpg, side_rec + (uint64_t)k * side_stride, out_cell,
+                                                   GroupTextKeyCells{L, out_cell, text});
+    if (lane == 0) {
+        blocks[2u * k] = make_uint4(status, n, n_match, n_bad);
+        blocks[2u * k + 1u] = make_uint4(n_groups, 0u, 0u, 0u); /* first_group: k_group_offsets */
+    }
+}
+
+#ifndef CRYO_LIKE_UNIT
 template <bool FLOATS>
 __global__ void __launch_bounds__(64)
 k_groupt_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, uint32_t cnt, const int32_t *__restrict__ dec_status,
@@ -187,21 +213,8 @@ k_groupt_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B,
     uint32_t k, lane;
     GroupTextLds &L = lds[sweep_wave(1u, k, lane)];
     if (k >= cnt) return;
-    uint32_t n_match = 0, n_bad = 0;
-    const uint8_t *__restrict__ p;
-    uint32_t n, upper;
-    const uint32_t status = sweep_open(dec, dec_stride, B, dec_status, k, p, n, upper);
-    const uint32_t cpg = ncols + (uint32_t)__popc(text); /* a group's cells: the aggregate cells, then the key cells */
-    /* 1. the matches and their text keys into LDS in position order, 2. their ranks, 3. group_reduce with the key cells */
-    groupt_matches<FLOATS>(L, p, B, n, upper, lane, atts, keys, nkeys, max_att, slots, nby, text, n_match, n_bad);
-    groupt_rank(L, n_match, lane, text);
-    AggCell *out_cell = side_cell + (uint64_t)k * side_stride * cpg;
-    const uint32_t n_groups = group_reduce<FLOATS>(L.g, n_match, lane, slots, ncols, cpg, side_rec + (uint64_t)k * side_stride, out_cell,
-                                                   GroupTextKeyCells{L, out_cell, text});
-    if (lane == 0) {
-        blocks[2u * k] = make_uint4(status, n, n_match, n_bad);
-        blocks[2u * k + 1u] = make_uint4(n_groups, 0u, 0u, 0u); /* first_group: k_group_offsets */
-    }
+    groupt_block_body<FLOATS, false>(L, k, lane, dec, dec_stride, B, dec_status, atts, keys, nkeys, slots, nby, ncols, text, max_att,
+                                     side_stride, blocks, side_rec, side_cell);
 }
 
 hipError_t launch_groupt_block(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
@@ -217,5 +230,37 @@ hipError_t launch_groupt_block(hipStream_t s, const uint8_t *d_dec, uint64_t dec
                        (AggCell *)d_side_cell);
     return hipGetLastError();
 }
+
+#else /* CRYO_LIKE_UNIT */
+/* k_groupt_block<true> whose walk also matches the patterns of CRYO_OP_LIKE / CRYO_OP_NOT_LIKE keys (walk_like): a kernel of its
+ * own name, so that k_groupt_block stays the code it was.  Built from this source compiled a second time with CRYO_LIKE_UNIT
+ * (group_text_like.o) */
+__global__ void __launch_bounds__(64)
+k_grouptl_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, uint32_t cnt, const int32_t *__restrict__ dec_status,
+                const FilterAtt *__restrict__ atts, const FilterKey *__restrict__ keys, uint32_t nkeys,
+                const AggCol *__restrict__ slots, uint32_t nby, uint32_t ncols, uint32_t text, uint32_t max_att,
+                uint32_t side_stride, uint4 *__restrict__ blocks, GroupRec *__restrict__ side_rec, AggCell *__restrict__ side_cell)
+{
+    __shared__ GroupTextLds lds[1];
+    uint32_t k, lane;
+    GroupTextLds &L = lds[sweep_wave(1u, k, lane)];
+    if (k >= cnt) return;
+    groupt_block_body<true, true>(L, k, lane, dec, dec_stride, B, dec_status, atts, keys, nkeys, slots, nby, ncols, text, max_att,
+                                  side_stride, blocks, side_rec, side_cell);
+}
+
+hipError_t launch_grouptl_block(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
+                                const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,
+                                uint32_t nby, uint32_t ncols, uint32_t text, uint32_t max_att, uint32_t truth, uint32_t side_stride,
+                                uint4 *d_blocks, void *d_side_rec, void *d_side_cell)
+{
+    /* the other arguments are launch_group's, which checked them; the one verdict path needs a table */
+    if (truth == 0u || text == 0u || (text >> nby) != 0u) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_grouptl_block, dim3(cnt), dim3(64), 0, s, d_dec, dec_stride, block_size, cnt, d_dec_status,
+                       (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys | truth << 16, (const AggCol *)d_slots, nby, ncols, text,
+                       max_att, side_stride, d_blocks, (GroupRec *)d_side_rec, (AggCell *)d_side_cell);
+    return hipGetLastError();
+}
+#endif
 
 } // namespace cryo

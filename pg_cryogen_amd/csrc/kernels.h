@@ -249,6 +249,12 @@ hipError_t launch_fetch(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride
  * (filter_walk.h).  floats (here and in launch_agg, launch_group, launch_project): a key has a float type (CRYO_KEY_FLOAT4,
  * CRYO_KEY_FLOAT8; its value in the key table is the mapped constant, float_map) or an aggregate column has one; truth is then
  * not 0 and the float kernel runs in the <true> one's place (k_filterf_match, k_aggf_block, k_groupf_block, k_projectf_block).
+ * like (in all five launchers): a key has op CRYO_OP_LIKE or CRYO_OP_NOT_LIKE (its value in the key table is the device address
+ * of its compiled pattern, walk_like); truth is then not 0 and the pattern kernel runs in every other's place, float keys and
+ * float columns or not (k_filterl_match, k_aggl_block, k_groupl_block, k_groupbl_block, k_grouptl_block, k_projectl_block,
+ * k_topnl_block): kernels of their own names, so that a descriptor without such a key runs the code it ran.  Each lives
+ * with its launcher (launch_*l_*, at the end of this header) in a unit of its own: the source of its float sibling compiled a
+ * second time with CRYO_LIKE_UNIT, which then holds nothing else (the Makefile's %_like.o).
  * An undecided tuple gets a
  * record {pos, 9, 0} and counts in n_bad.  d_blocks: the chunk's rows of the block table (cryo_filter_block, 16-byte aligned).  Scratch: d_side
  * 16 bytes per possible item (cnt * filter_side_stride(block_size) entries), d_sum 2 * cnt and d_base 2 * (cnt + 1) entries.
@@ -272,7 +278,7 @@ inline bool scan_launch_ok(uint64_t dec_stride, const void *d_dec, const void *d
 }
 hipError_t launch_filter(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
                          const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, uint32_t max_att,
-                         uint32_t truth, bool floats, bool count_only, uint4 *d_blocks, uint4 *d_side, uint64_t *d_sum, uint64_t *d_base, uint64_t *d_running,
+                         uint32_t truth, bool floats, bool like, bool count_only, uint4 *d_blocks, uint4 *d_side, uint64_t *d_sum, uint64_t *d_base, uint64_t *d_running,
                          uint8_t *d_dst, uint64_t dst_cap, uint2 *d_rec, uint64_t rec_cap, bool chunk_relative, int cus);
 
 /* the scan aggregate (agg.hip) on one decoded chunk of cnt blocks (laid out as for launch_filter): k_agg_block alone.  The
@@ -284,7 +290,7 @@ hipError_t launch_filter(hipStream_t s, const uint8_t *d_dec, uint64_t dec_strid
  * over it asks the shared decode loop for no bytes of its own. */
 hipError_t launch_agg(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
                       const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_cols,
-                      uint32_t ncols, uint32_t max_att, uint32_t truth, bool floats, uint4 *d_blocks, void *d_cells);
+                      uint32_t ncols, uint32_t max_att, uint32_t truth, bool floats, bool like, uint4 *d_blocks, void *d_cells);
 /* launch_agg's float branch (agg_float.hip): k_aggf_block alone, on arguments launch_agg has checked; truth is not 0 */
 hipError_t launch_aggf(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
                        const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_cols,
@@ -305,8 +311,8 @@ hipError_t launch_aggf(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride,
  * has ncols + popcount(text) cells in d_side_cell and d_cells, the aggregate cells first. */
 hipError_t launch_group(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
                         const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,
-                        uint32_t nby, uint32_t ncols, uint32_t max_att, uint32_t truth, bool floats, uint4 *d_blocks, void *d_side_rec,
-                        void *d_side_cell,
+                        uint32_t nby, uint32_t ncols, uint32_t max_att, uint32_t truth, bool floats, bool like, uint4 *d_blocks,
+                        void *d_side_rec, void *d_side_cell,
                         uint64_t *d_running, void *d_rec, void *d_cells, uint64_t group_cap, int cus, const void *d_buckets, uint32_t text);
 /* launch_group's bucket branch (group_bucket.hip): k_groupb_block<floats> alone, on arguments launch_group has checked; truth is
  * not 0; d_buckets the staged bucket table, 8-byte aligned: two entries of 24 bytes (cryo_bucket; a list's n its distinct
@@ -340,8 +346,9 @@ hipError_t launch_groupf_block(hipStream_t s, const uint8_t *d_dec, uint64_t dec
  * the call; no record at or beyond rec_cap and no row at or beyond row_cap is written.  cus as for launch_fetch. */
 hipError_t launch_project(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
                           const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_cols,
-                          uint32_t ncols, uint32_t row_bytes, uint32_t max_att, uint32_t truth, bool floats, uint4 *d_blocks, void *d_side_rec,
-                          void *d_side_rows, uint64_t *d_running, void *d_rec, uint64_t rec_cap, void *d_rows, uint64_t row_cap, int cus);
+                          uint32_t ncols, uint32_t row_bytes, uint32_t max_att, uint32_t truth, bool floats, bool like, uint4 *d_blocks,
+                          void *d_side_rec, void *d_side_rows, uint64_t *d_running, void *d_rec, uint64_t rec_cap, void *d_rows,
+                          uint64_t row_cap, int cus);
 
 /* the ordered scan (topn.hip) on one decoded chunk of cnt blocks (laid out as for launch_filter): k_topn_block, k_topn_offsets,
  * k_topn_copy.  The descriptors are validated by the caller (cryo_codec.cpp, topn_desc_ok): d_atts and d_keys as for
@@ -358,8 +365,38 @@ hipError_t launch_project(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stri
 hipError_t launch_topn(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
                        const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,
                        const void *h_slots, uint32_t nby, uint32_t ncols, uint32_t row_bytes, uint32_t limit, uint32_t max_att,
-                       uint32_t truth, bool floats, uint4 *d_blocks, void *d_side_rec, void *d_side_rows, void *d_side_ord,
+                       uint32_t truth, bool floats, bool like, uint4 *d_blocks, void *d_side_rec, void *d_side_rows, void *d_side_ord,
                        uint64_t *d_running, void *d_rec, void *d_rows, uint64_t row_cap, int cus);
+
+/* the block kernels of descriptors with a pattern key (above: `like`), each alone in its unit *_like.o.  Their arguments are
+ * those of the launcher that branches to them -- launch_filter, launch_agg, launch_group, launch_project, launch_topn --, which
+ * has checked them, and of the block kernel they stand in for; truth is not 0 */
+hipError_t launch_filterl_match(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
+                                const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, uint32_t max_att,
+                                uint32_t truth, bool count_only, uint32_t side_stride, uint4 *d_blocks, uint4 *d_side, uint64_t *d_sum);
+hipError_t launch_aggl(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
+                       const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_cols,
+                       uint32_t ncols, uint32_t max_att, uint32_t truth, uint4 *d_blocks, void *d_cells);
+hipError_t launch_groupl_block(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
+                               const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,
+                               uint32_t nby, uint32_t ncols, uint32_t max_att, uint32_t truth, uint32_t side_stride, uint4 *d_blocks,
+                               void *d_side_rec, void *d_side_cell);
+hipError_t launch_groupbl_block(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
+                                const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,
+                                const void *d_buckets, uint32_t nby, uint32_t ncols, uint32_t max_att, uint32_t truth,
+                                uint32_t side_stride, uint4 *d_blocks, void *d_side_rec, void *d_side_cell);
+hipError_t launch_grouptl_block(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
+                                const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,
+                                uint32_t nby, uint32_t ncols, uint32_t text, uint32_t max_att, uint32_t truth, uint32_t side_stride,
+                                uint4 *d_blocks, void *d_side_rec, void *d_side_cell);
+hipError_t launch_projectl_block(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
+                                 const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_cols,
+                                 uint32_t ncols, uint32_t max_att, uint32_t truth, uint32_t row_words, uint32_t side_stride, uint4 *d_blocks,
+                                 void *d_side_rec, void *d_side_rows);
+hipError_t launch_topnl_block(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
+                              const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,
+                              uint32_t ord_bits, uint64_t row_map, uint32_t limit, uint32_t max_att, uint32_t truth, uint32_t row_words,
+                              uint32_t side_stride, uint4 *d_blocks, void *d_side_rec, void *d_side_rows, void *d_side_ord);
 
 } // namespace cryo
 

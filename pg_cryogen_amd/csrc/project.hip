@@ -33,8 +33,9 @@ constexpr uint32_t kProjectMaxCols = 8u; /* CRYO_PROJECT_MAX_COLS */
 /* The staged column table: entry j is an AggCol to the walk (which reads att alone) and carries in `type` the column's width
  * w_j (1, 2, 4, 8) and in `rsv` its offset o_j within the row (0 .. 56, a multiple of w_j): launch_project's rule */
 
-/* the body of k_project_block and of k_projectf_block, the kernel of descriptors with a float key */
-template <bool BYTES, bool FLOATS>
+/* the body of k_project_block, of k_projectf_block, the kernel of descriptors with a float key, and of k_projectl_block, the
+ * kernel of descriptors with a pattern key */
+template <bool BYTES, bool FLOATS, bool LIKE = false>
 __device__ inline void project_block_body(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, uint32_t cnt,
                                           const int32_t *__restrict__ dec_status, const FilterAtt *__restrict__ atts,
                                           const FilterKey *__restrict__ keys, uint32_t nkeys, const AggCol *__restrict__ cols,
@@ -55,8 +56,8 @@ __device__ inline void project_block_body(const uint8_t *__restrict__ dec, uint6
     for (uint32_t t0 = 0; t0 < n; t0 += 64u) {
         const uint32_t i = t0 + lane;
         WalkCaptureN<kProjectMaxCols> cap;
-        const SweepItem it = sweep_turn<true, kProjectMaxCols, BYTES, true, FLOATS>(p, B, n, upper, i, atts, keys, nkeys, max_att, cols,
-                                                                                     ncols, &cap);
+        const SweepItem it = sweep_turn<true, kProjectMaxCols, BYTES, true, FLOATS, false, LIKE>(p, B, n, upper, i, atts, keys, nkeys,
+                                                                                                  max_att, cols, ncols, &cap);
         const unsigned long long mm = __ballot(it.match), mb = __ballot(it.bad);
         if (it.match || it.bad) { /* records in position order: the rank among the matches and the bad items */
             const uint32_t r = n_match + n_bad + (uint32_t)__popcll((mm | mb) & below); /* below n <= side_stride */
@@ -113,6 +114,7 @@ __device__ inline void project_block_body(const uint8_t *__restrict__ dec, uint6
     }
 }
 
+#ifndef CRYO_LIKE_UNIT
 template <bool BYTES>
 __global__ void __launch_bounds__(256)
 k_project_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, uint32_t cnt, const int32_t *__restrict__ dec_status,
@@ -188,23 +190,29 @@ k_project_copy(uint32_t cnt, uint32_t side_stride, uint32_t row_words, const uin
 
 hipError_t launch_project(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
                           const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_cols,
-                          uint32_t ncols, uint32_t row_bytes, uint32_t max_att, uint32_t truth, bool floats, uint4 *d_blocks, void *d_side_rec,
+                          uint32_t ncols, uint32_t row_bytes, uint32_t max_att, uint32_t truth, bool floats, bool like, uint4 *d_blocks, void *d_side_rec,
                           void *d_side_rows, uint64_t *d_running, void *d_rec, uint64_t rec_cap, void *d_rows, uint64_t row_cap, int cus)
 {
     if (cnt == 0) return hipSuccess;
     if (!scan_launch_ok(dec_stride, d_dec, d_blocks, d_atts, d_keys,
                         (uintptr_t)d_rec | (uintptr_t)d_rows | (uintptr_t)d_cols | (uintptr_t)d_side_rec | (uintptr_t)d_side_rows |
                             (uintptr_t)d_running,
-                        block_size, nkeys, truth, floats) ||
+                        block_size, nkeys, truth, floats || like) ||
         ncols == 0u || ncols > kProjectMaxCols || row_bytes < 8u ||
         row_bytes > 8u * kProjectMaxCols || (row_bytes & 7u) != 0 || !d_cols || !d_side_rec || !d_side_rows || !d_running ||
         (rec_cap > 0u && !d_rec) || (row_cap > 0u && !d_rows))
         return hipErrorInvalidValue;
     const uint32_t stride = filter_side_stride(block_size), row_words = row_bytes / 8u;
-    hipLaunchKernelGGL(floats ? k_projectf_block : truth ? k_project_block<true> : k_project_block<false>, dim3((cnt + 3u) / 4u), dim3(256), 0, s, d_dec,
-                       dec_stride, block_size, cnt, d_dec_status, (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys | truth << 16,
-                       (const AggCol *)d_cols, ncols, max_att, row_words, stride, d_blocks, (uint2 *)d_side_rec, (uint2 *)d_side_rows);
-    hipError_t e = hipGetLastError();
+    hipError_t e;
+    if (like) /* a pattern key: the kernel of this source's second unit */
+        e = launch_projectl_block(s, d_dec, dec_stride, block_size, cnt, d_dec_status, d_atts, d_keys, nkeys, d_cols, ncols, max_att, truth,
+                                  row_words, stride, d_blocks, d_side_rec, d_side_rows);
+    else {
+        hipLaunchKernelGGL(floats ? k_projectf_block : truth ? k_project_block<true> : k_project_block<false>, dim3((cnt + 3u) / 4u), dim3(256), 0, s, d_dec,
+                           dec_stride, block_size, cnt, d_dec_status, (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys | truth << 16,
+                           (const AggCol *)d_cols, ncols, max_att, row_words, stride, d_blocks, (uint2 *)d_side_rec, (uint2 *)d_side_rows);
+        e = hipGetLastError();
+    }
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_project_offsets, dim3(1), dim3(256), 0, s, cnt, d_running, d_blocks);
     e = hipGetLastError();
@@ -216,5 +224,33 @@ hipError_t launch_project(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stri
                        (const uint2 *)d_side_rec, (const uint2 *)d_side_rows, (uint2 *)d_rec, rec_cap, (uint2 *)d_rows, row_cap);
     return hipGetLastError();
 }
+
+#else /* CRYO_LIKE_UNIT */
+/* k_projectf_block whose walk also matches the patterns of CRYO_OP_LIKE / CRYO_OP_NOT_LIKE keys (walk_like): a kernel of its own
+ * name, as k_filterl_match is -- inlined into k_project_block<true> and k_projectf_block the matcher would take them from eight
+ * waves per SIMD to seven --, built from this source compiled a second time with CRYO_LIKE_UNIT (project_like.o) */
+__global__ void __launch_bounds__(256)
+k_projectl_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, uint32_t cnt, const int32_t *__restrict__ dec_status,
+                 const FilterAtt *__restrict__ atts, const FilterKey *__restrict__ keys, uint32_t nkeys,
+                 const AggCol *__restrict__ cols, uint32_t ncols, uint32_t max_att, uint32_t row_words, uint32_t side_stride,
+                 uint4 *__restrict__ blocks, uint2 *__restrict__ side_rec, uint2 *__restrict__ side_rows)
+{
+    project_block_body<true, true, true>(dec, dec_stride, B, cnt, dec_status, atts, keys, nkeys, cols, ncols, max_att, row_words,
+                                         side_stride, blocks, side_rec, side_rows);
+}
+
+hipError_t launch_projectl_block(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
+                                 const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_cols,
+                                 uint32_t ncols, uint32_t max_att, uint32_t truth, uint32_t row_words, uint32_t side_stride, uint4 *d_blocks,
+                                 void *d_side_rec, void *d_side_rows)
+{
+    /* the arguments are launch_project's, which checked them; the one verdict path needs a table */
+    if (truth == 0u) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_projectl_block, dim3((cnt + 3u) / 4u), dim3(256), 0, s, d_dec, dec_stride, block_size, cnt, d_dec_status,
+                       (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys | truth << 16, (const AggCol *)d_cols, ncols, max_att,
+                       row_words, side_stride, d_blocks, (uint2 *)d_side_rec, (uint2 *)d_side_rows);
+    return hipGetLastError();
+}
+#endif
 
 } // namespace cryo

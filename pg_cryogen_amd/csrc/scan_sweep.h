@@ -52,8 +52,8 @@ struct SweepItem { uint32_t verdict, src, len; bool match, bad; };
 
 /* One turn of the sweep for item i of an opened block (i >= n: a lane without an item, which makes the same trips and loads
  * nothing).  The template parameters and atts .. cols, ncols are walk_tuple's; *cap is cleared, then filled (CAPTURE alone: the
- * filter passes null; TEXT is the walk's too).  Without BYTES no tuple is undecided: the float kernels, which always run the table's path, are BYTES */
-template <bool CAPTURE, uint32_t SLOTS, bool BYTES, bool NARROW, bool FLOATS, bool TEXT = false>
+ * filter passes null; TEXT and LIKE are the walk's too).  Without BYTES no tuple is undecided: the float kernels, which always run the table's path, are BYTES */
+template <bool CAPTURE, uint32_t SLOTS, bool BYTES, bool NARROW, bool FLOATS, bool TEXT = false, bool LIKE = false>
 __device__ inline SweepItem sweep_turn(const uint8_t *__restrict__ p, uint32_t B, uint32_t n, uint32_t upper, uint32_t i,
                                        const FilterAtt *__restrict__ atts, const FilterKey *__restrict__ keys, uint32_t nkeys,
                                        uint32_t max_att, const AggCol *__restrict__ cols, uint32_t ncols,
@@ -73,7 +73,7 @@ __device__ inline SweepItem sweep_turn(const uint8_t *__restrict__ p, uint32_t B
 #pragma unroll
         for (uint32_t j = 0; j < SLOTS; j++) cap->v[j] = 0;
     }
-    const uint32_t walked = walk_tuple<CAPTURE, SLOTS, BYTES, NARROW, FLOATS, TEXT>(p + it.src, it.len, live, atts, keys, nkeys, max_att, cols,
+    const uint32_t walked = walk_tuple<CAPTURE, SLOTS, BYTES, NARROW, FLOATS, TEXT, LIKE>(p + it.src, it.len, live, atts, keys, nkeys, max_att, cols,
                                                                               ncols, cap, WalkKeys<BYTES>());
     if (live) it.verdict = walked;
     it.match = it.verdict == 0u;

@@ -58,7 +58,7 @@ static_assert(sizeof(TopnLds) * kTopnWaves <= 32480u, "a workgroup's LDS stays w
 /* The staged table (launch_topn's rule): entries 0 .. 1 the order columns {att, type, flags, 0}, entries 2 .. 9 the projection's
  * column table {att, width, offset within the row, 0}; unused entries all zero.  The walk reads it as AggCol and looks at att */
 
-template <bool BYTES, bool FLOATS>
+template <bool BYTES, bool FLOATS, bool LIKE = false>
 __device__ inline void topn_block_body(TopnLds &L, uint32_t k, uint32_t lane, const uint8_t *__restrict__ dec, uint64_t dec_stride,
                                        uint32_t B, const int32_t *__restrict__ dec_status, const FilterAtt *__restrict__ atts,
                                        const FilterKey *__restrict__ keys, uint32_t nkeys, const AggCol *__restrict__ slots,
@@ -77,8 +77,8 @@ __device__ inline void topn_block_body(TopnLds &L, uint32_t k, uint32_t lane, co
     for (uint32_t t0 = 0; t0 < n; t0 += 64u) {
         const uint32_t i = t0 + lane;
         WalkCaptureN<kTopnSlots> cap;
-        const SweepItem it = sweep_turn<true, kTopnSlots, BYTES, true, FLOATS>(p, B, n, upper, i, atts, keys, nkeys, max_att, slots,
-                                                                               kTopnSlots, &cap);
+        const SweepItem it = sweep_turn<true, kTopnSlots, BYTES, true, FLOATS, false, LIKE>(p, B, n, upper, i, atts, keys, nkeys, max_att,
+                                                                                            slots, kTopnSlots, &cap);
         const unsigned long long mm = __ballot(it.match);
         /* no instruction: the three stay what they are, but the compiler may not know it, so that it keeps them alone over the
          * walk and not the several dozen compares and shifts it would derive from them once and for all turns */
@@ -181,6 +181,7 @@ __device__ inline void topn_block_body(TopnLds &L, uint32_t k, uint32_t lane, co
     }
 }
 
+#ifndef CRYO_LIKE_UNIT
 template <bool BYTES>
 __global__ void __launch_bounds__(64 * kTopnWaves)
 k_topn_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, uint32_t cnt, const int32_t *__restrict__ dec_status,
@@ -248,14 +249,14 @@ k_topn_copy(uint32_t cnt, uint32_t side_stride, uint32_t row_words, const uint4 
 hipError_t launch_topn(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
                        const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,
                        const void *h_slots, uint32_t nby, uint32_t ncols, uint32_t row_bytes, uint32_t limit, uint32_t max_att,
-                       uint32_t truth, bool floats, uint4 *d_blocks, void *d_side_rec, void *d_side_rows, void *d_side_ord,
+                       uint32_t truth, bool floats, bool like, uint4 *d_blocks, void *d_side_rec, void *d_side_rows, void *d_side_ord,
                        uint64_t *d_running, void *d_rec, void *d_rows, uint64_t row_cap, int cus)
 {
     if (cnt == 0) return hipSuccess;
     if (!scan_launch_ok(dec_stride, d_dec, d_blocks, d_atts, d_keys,
                         (uintptr_t)d_rec | (uintptr_t)d_rows | (uintptr_t)d_slots | (uintptr_t)d_side_rec | (uintptr_t)d_side_rows |
                             (uintptr_t)d_running,
-                        block_size, nkeys, truth, floats) ||
+                        block_size, nkeys, truth, floats || like) ||
         nby == 0u || nby > kTopnMaxBy || limit == 0u || ncols == 0u || ncols > kTopnMaxCols || row_bytes < 8u ||
         row_bytes > 8u * kTopnMaxCols || (row_bytes & 7u) != 0 || !d_slots || !h_slots || !d_side_rec || !d_side_rows || !d_side_ord ||
         ((uintptr_t)d_side_ord & 3u) != 0 || !d_running || (row_cap > 0u && (!d_rec || !d_rows)))
@@ -277,12 +278,18 @@ hipError_t launch_topn(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride,
         row_map |= (uint64_t)(o | (w == 8u ? 3u : w == 4u ? 2u : w == 2u ? 1u : 0u) << 6) << (8u * j);
     }
     const uint32_t stride = filter_side_stride(block_size), row_words = row_bytes / 8u;
-    hipLaunchKernelGGL(floats ? k_topnf_block : truth ? k_topn_block<true> : k_topn_block<false>,
-                       dim3((cnt + kTopnWaves - 1u) / kTopnWaves), dim3(64 * kTopnWaves), 0, s, d_dec, dec_stride, block_size, cnt,
-                       d_dec_status, (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys | truth << 16, (const AggCol *)d_slots,
-                       ord_bits, row_map, limit, max_att, row_words, stride, d_blocks, (TopnRec *)d_side_rec, (uint2 *)d_side_rows,
-                       (uint32_t *)d_side_ord);
-    hipError_t e = hipGetLastError();
+    hipError_t e;
+    if (like) /* a pattern key: the kernel of this source's second unit */
+        e = launch_topnl_block(s, d_dec, dec_stride, block_size, cnt, d_dec_status, d_atts, d_keys, nkeys, d_slots, ord_bits, row_map, limit,
+                               max_att, truth, row_words, stride, d_blocks, d_side_rec, d_side_rows, d_side_ord);
+    else {
+        hipLaunchKernelGGL(floats ? k_topnf_block : truth ? k_topn_block<true> : k_topn_block<false>,
+                           dim3((cnt + kTopnWaves - 1u) / kTopnWaves), dim3(64 * kTopnWaves), 0, s, d_dec, dec_stride, block_size, cnt,
+                           d_dec_status, (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys | truth << 16, (const AggCol *)d_slots,
+                           ord_bits, row_map, limit, max_att, row_words, stride, d_blocks, (TopnRec *)d_side_rec, (uint2 *)d_side_rows,
+                           (uint32_t *)d_side_ord);
+        e = hipGetLastError();
+    }
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_topn_offsets, dim3(1), dim3(256), 0, s, cnt, d_running, d_blocks);
     e = hipGetLastError();
@@ -295,5 +302,38 @@ hipError_t launch_topn(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride,
                        (uint2 *)d_rows, row_cap);
     return hipGetLastError();
 }
+
+#else /* CRYO_LIKE_UNIT */
+/* k_topnf_block whose walk also matches the patterns of CRYO_OP_LIKE / CRYO_OP_NOT_LIKE keys (walk_like): a kernel of its own
+ * name, as k_filterl_match is, built from this source compiled a second time with CRYO_LIKE_UNIT (topn_like.o): this unit
+ * holds its three block kernels and no other */
+__global__ void __launch_bounds__(64 * kTopnWaves)
+k_topnl_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, uint32_t cnt, const int32_t *__restrict__ dec_status,
+              const FilterAtt *__restrict__ atts, const FilterKey *__restrict__ keys, uint32_t nkeys, const AggCol *__restrict__ slots,
+              uint32_t ord_bits, uint64_t row_map, uint32_t limit, uint32_t max_att, uint32_t row_words, uint32_t side_stride,
+              uint4 *__restrict__ blocks, TopnRec *__restrict__ side_rec, uint2 *__restrict__ side_rows, uint32_t *__restrict__ side_ord)
+{
+    __shared__ TopnLds lds[kTopnWaves];
+    uint32_t k, lane;
+    TopnLds &L = lds[sweep_wave(kTopnWaves, k, lane)];
+    if (k >= cnt) return;
+    topn_block_body<true, true, true>(L, k, lane, dec, dec_stride, B, dec_status, atts, keys, nkeys, slots, ord_bits, row_map, limit,
+                                      max_att, row_words, side_stride, blocks, side_rec, side_rows, side_ord);
+}
+
+hipError_t launch_topnl_block(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
+                              const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,
+                              uint32_t ord_bits, uint64_t row_map, uint32_t limit, uint32_t max_att, uint32_t truth, uint32_t row_words,
+                              uint32_t side_stride, uint4 *d_blocks, void *d_side_rec, void *d_side_rows, void *d_side_ord)
+{
+    /* the arguments are launch_topn's, which checked and packed them; the one verdict path needs a table */
+    if (truth == 0u) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_topnl_block, dim3((cnt + kTopnWaves - 1u) / kTopnWaves), dim3(64 * kTopnWaves), 0, s, d_dec, dec_stride, block_size,
+                       cnt, d_dec_status, (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys | truth << 16, (const AggCol *)d_slots,
+                       ord_bits, row_map, limit, max_att, row_words, side_stride, d_blocks, (TopnRec *)d_side_rec, (uint2 *)d_side_rows,
+                       (uint32_t *)d_side_ord);
+    return hipGetLastError();
+}
+#endif
 
 } // namespace cryo

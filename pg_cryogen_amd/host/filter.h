@@ -82,6 +82,23 @@ static inline cryo_scan_key cryo_filter_float_key(uint16_t att, uint8_t type, ui
     return k;
 }
 
+/* What the codec would hold against the n bytes at pattern as the pattern of a CRYO_OP_LIKE / CRYO_OP_NOT_LIKE key
+ * (include/cryo_codec.h, "Pattern keys"), so that the binder raises PostgreSQL's own error, or keeps the qual to itself, before
+ * any call: 0 -- nothing; CRYO_LIKE_CHECK_LENGTH -- n is above CRYO_KEY_BYTES_MAX, or n > 0 and pattern is null;
+ * CRYO_LIKE_CHECK_ESCAPE -- the last byte is an unescaped '\' ("LIKE pattern must not end with escape character").  The
+ * ESCAPE character has been rewritten to '\' by then.  In the header, as cryo_filter_truth_dnf is: a binder needs no codec for it. */
+#define CRYO_LIKE_CHECK_LENGTH 1
+#define CRYO_LIKE_CHECK_ESCAPE 2
+static inline int cryo_filter_like_check(const void *pattern, uint32_t n)
+{
+    const uint8_t *p = (const uint8_t *)pattern;
+    uint32_t i;
+    if (n > CRYO_KEY_BYTES_MAX || (n > 0 && !p)) return CRYO_LIKE_CHECK_LENGTH;
+    for (i = 0; i < n; i++)
+        if (p[i] == '\\' && ++i == n) return CRYO_LIKE_CHECK_ESCAPE; /* the byte behind an escape is skipped, whatever it is */
+    return 0;
+}
+
 static inline uint32_t cryo_filter_truth_dnf(const uint32_t *terms, uint32_t nterms, uint32_t nkeys)
 {
     uint32_t w = 0, i, m;
