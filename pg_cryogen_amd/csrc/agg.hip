@@ -12,7 +12,7 @@
  *                 nothing to place, so one sweep suffices.  A lane keeps, per aggregate column, the running state of agg_cell.h.
  *                 After the sweep a butterfly (__shfl_xor) reduces the five words per column across the wave; lane 0 writes the
  *                 block's row and its cells straight to the call's output.
- * A descriptor with a float key or a float aggregate column runs agg_float.hip's k_aggf_block instead (launch_agg's `floats`).
+ * A descriptor with a float key or a float aggregate column runs agg_float.hip's k_aggf_block instead (ScanDesc::floats).
  * Every device write is a vector store in plain C++.  No LDS, no scratch, no atomics; no running totals, no second kernel.
  */
 #include "kernels.h"
@@ -69,24 +69,17 @@ k_agg_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, ui
     }
 }
 
-hipError_t launch_agg(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
-                      const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_cols,
-                      uint32_t ncols, uint32_t max_att, uint32_t truth, bool floats, bool like, uint4 *d_blocks, void *d_cells)
+hipError_t launch_agg(const ScanChunk &c, const ScanDesc &d, const AggLaunch &a)
 {
-    if (cnt == 0) return hipSuccess;
-    if (!scan_launch_ok(dec_stride, d_dec, d_blocks, d_atts, d_keys, (uintptr_t)d_cells | (uintptr_t)d_cols, block_size, nkeys, truth,
-                        floats || like) || ncols == 0u || ncols > kAggMaxCols)
-        return hipErrorInvalidValue;
-    if (like) /* a pattern key: agg_float.hip's second unit */
-        return launch_aggl(s, d_dec, dec_stride, block_size, cnt, d_dec_status, d_atts, d_keys, nkeys, d_cols, ncols, max_att, truth,
-                           d_blocks, d_cells);
-    if (floats) /* a float key or a float aggregate column: agg_float.hip's kernel */
-        return launch_aggf(s, d_dec, dec_stride, block_size, cnt, d_dec_status, d_atts, d_keys, nkeys, d_cols, ncols, max_att, truth,
-                           d_blocks, d_cells);
-    hipLaunchKernelGGL(truth ? k_agg_block<true> : k_agg_block<false>, dim3((cnt + 3u) / 4u), dim3(256), 0, s, d_dec, dec_stride,
-                       block_size, cnt, d_dec_status, (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys | truth << 16,
-                       (const AggCol *)d_cols, ncols, max_att, d_blocks, (AggCell *)d_cells);
-    return hipGetLastError();
+    if (c.cnt == 0) return hipSuccess;
+    if (!agg_launch_ok(c, d, a)) return hipErrorInvalidValue;
+    switch (scan_route(d.truth, d.floats, d.like)) {
+    case kRouteLike: return launch_aggl(c, d, a);  /* a pattern key: agg_float.hip's second unit */
+    case kRouteFloat: return launch_aggf(c, d, a); /* a float key or a float aggregate column: agg_float.hip's kernel */
+    case kRouteTable: return agg_launch(k_agg_block<true>, true, c, d, a);
+    case kRoutePlain: return agg_launch(k_agg_block<false>, false, c, d, a);
+    }
+    return hipErrorInvalidValue;
 }
 
 } // namespace cryo

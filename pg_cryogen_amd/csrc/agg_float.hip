@@ -107,17 +107,7 @@ k_aggf_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, u
     aggf_block_body<false>(dec, dec_stride, B, cnt, dec_status, atts, keys, nkeys, cols, ncols, max_att, blocks, cells);
 }
 
-hipError_t launch_aggf(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
-                       const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_cols,
-                       uint32_t ncols, uint32_t max_att, uint32_t truth, uint4 *d_blocks, void *d_cells)
-{
-    /* the arguments are launch_agg's, which checked them; the one verdict path needs a table */
-    if (truth == 0u) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_aggf_block, dim3((cnt + 3u) / 4u), dim3(256), 0, s, d_dec, dec_stride, block_size, cnt, d_dec_status,
-                       (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys | truth << 16, (const AggCol *)d_cols, ncols, max_att,
-                       d_blocks, (AggCell *)d_cells);
-    return hipGetLastError();
-}
+hipError_t launch_aggf(const ScanChunk &c, const ScanDesc &d, const AggLaunch &a) { return agg_launch(k_aggf_block, true, c, d, a); }
 
 #else /* CRYO_LIKE_UNIT */
 /* k_aggf_block whose walk also matches the patterns of CRYO_OP_LIKE / CRYO_OP_NOT_LIKE keys (walk_like), for every descriptor
@@ -133,17 +123,7 @@ k_aggl_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, u
     aggf_block_body<true>(dec, dec_stride, B, cnt, dec_status, atts, keys, nkeys, cols, ncols, max_att, blocks, cells);
 }
 
-hipError_t launch_aggl(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
-                       const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_cols,
-                       uint32_t ncols, uint32_t max_att, uint32_t truth, uint4 *d_blocks, void *d_cells)
-{
-    /* the arguments are launch_agg's, which checked them; the one verdict path needs a table */
-    if (truth == 0u) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_aggl_block, dim3((cnt + 3u) / 4u), dim3(256), 0, s, d_dec, dec_stride, block_size, cnt, d_dec_status,
-                       (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys | truth << 16, (const AggCol *)d_cols, ncols, max_att,
-                       d_blocks, (AggCell *)d_cells);
-    return hipGetLastError();
-}
+hipError_t launch_aggl(const ScanChunk &c, const ScanDesc &d, const AggLaunch &a) { return agg_launch(k_aggl_block, true, c, d, a); }
 #endif
 
 } // namespace cryo

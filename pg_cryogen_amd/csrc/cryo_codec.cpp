@@ -1147,22 +1147,16 @@ static int fetch_pass(cryo_codec *c, int method, const uint8_t *d_src, const uin
  * matches and the records out.  Per chunk (own) each block has 16 bytes per possible item of side table, its two sums and bases
  * and, for the host-buffer call, a row of the chunk's staging areas for packed bytes and for records; the pass's fixed bytes hold
  * the host-buffer call's running totals.  Its decodes count nowhere. */
+using cryo::ScanDesc; /* kernels.h: what every scan call tells its kernels about the relation and the keys */
+
+/* what the launchers of the scan calls are told about a decoded chunk (kernels.h) */
+static cryo::ScanChunk scan_chunk(const cryo_codec *c, const DecodeChunk &ch, uint32_t B)
+{
+    return {.stream = c->stream, .d_dec = ch.dec, .dec_stride = ch.Bp, .block_size = B, .cnt = ch.cnt, .d_dec_status = ch.dec_st,
+            .cus = c->lz4_opts.cus};
+}
+
 namespace {
-/* what every scan call (filter, aggregate, group) tells its kernels about the relation and the keys */
-struct ScanDesc {
-    const void *d_atts = nullptr, *d_keys = nullptr; /* device */
-    uint32_t nkeys = 0, max_att = 0;                 /* max_att: the highest column the walk has to reach */
-    uint32_t truth = 0;                              /* 0: the keys are ANDed by the kernels' <false> instantiation; otherwise the
-                                                        truth table of the <true> one (scan_truth) */
-    bool floats = false;                             /* a float key or a float aggregate column: the float kernels, which have
-                                                        the truth table's verdict path alone (truth is not 0 then) */
-    bool like = false;                               /* a pattern key (CRYO_OP_LIKE, CRYO_OP_NOT_LIKE): the pattern kernels, which
-                                                        also do what the float kernels do (truth is not 0 then) */
-    const void *d_buckets = nullptr;                 /* device: the grouping's bucket table under CRYO_GROUP_BUCKETS (truth is not 0
-                                                        then), else null */
-    uint32_t text = 0;                               /* the grouping's: bit j set when group column j is a byte string
-                                                        (CRYO_GROUP_TEXT; truth is not 0 then) */
-};
 struct FilterIo {
     ScanDesc sd;
     bool count_only = false;
@@ -1468,11 +1462,11 @@ static int filter_pass(cryo_codec *c, int method, const uint8_t *d_src, const ui
         uint8_t *st_dst = ch.own + (16u * S + 48u) * ch.K;
         cryo_filter_rec *st_rec = (cryo_filter_rec *)(st_dst + row * ch.K);
         if (ch.lo == 0) HIP_TRY(c, hipMemsetAsync(running, 0, 2 * sizeof(uint64_t), c->stream));
-        HIP_TRY(c, cryo::launch_filter(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.sd.d_atts, io.sd.d_keys, io.sd.nkeys, io.sd.max_att,
-                                       io.sd.truth, io.sd.floats, io.sd.like, io.count_only, (uint4 *)(io.d_blocks + ch.lo), side, sum, base, running,
-                                       stage ? st_dst : io.d_dst, stage ? ch.K * row : io.dst_cap,
-                                       stage ? (uint2 *)st_rec : (uint2 *)io.d_rec, stage ? ch.K * S : io.rec_cap, host,
-                                       c->lz4_opts.cus));
+        HIP_TRY(c, cryo::launch_filter(scan_chunk(c, ch, B), io.sd,
+                                       {.count_only = io.count_only, .d_blocks = (uint4 *)(io.d_blocks + ch.lo), .d_side = side, .d_sum = sum,
+                                        .d_base = base, .d_running = running, .d_dst = stage ? st_dst : io.d_dst,
+                                        .dst_cap = stage ? ch.K * row : io.dst_cap, .d_rec = stage ? (uint2 *)st_rec : (uint2 *)io.d_rec,
+                                        .rec_cap = stage ? ch.K * S : io.rec_cap, .chunk_relative = host}));
         if (!host) return CRYO_OK;
         /* the chunk's rows of the table; then -- their number known from the rows -- its records; then -- their total known from
          * the last row and the last block's records -- its bytes */
@@ -1557,9 +1551,9 @@ static int agg_pass(cryo_codec *c, int method, const uint8_t *d_src, const uint6
                   "the aggregate's records are the kernel's");
     DecodePass ps(d_src, d_src_off, d_src_size, true);
     ps.run = [&](const DecodeChunk &ch) -> int {
-        HIP_TRY(c, cryo::launch_agg(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.sd.d_atts, io.sd.d_keys, io.sd.nkeys, io.d_cols,
-                                    io.ncols, io.sd.max_att, io.sd.truth, io.sd.floats, io.sd.like, (uint4 *)(io.d_blocks + ch.lo),
-                                    io.d_cells + ch.lo * io.ncols));
+        HIP_TRY(c, cryo::launch_agg(scan_chunk(c, ch, B), io.sd,
+                                    {.d_cols = io.d_cols, .ncols = io.ncols, .d_blocks = (uint4 *)(io.d_blocks + ch.lo),
+                                     .d_cells = io.d_cells + ch.lo * io.ncols}));
         return CRYO_OK;
     };
     return decode_pass(c, method, B, n, ps);
@@ -1726,9 +1720,10 @@ static int group_pass(cryo_codec *c, int method, const uint8_t *d_src, const uin
             }
         }
         uint8_t *side_rec = ch.own, *side_cell = ch.own + ch.K * S * sizeof(cryo_group_rec);
-        HIP_TRY(c, cryo::launch_group(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.sd.d_atts, io.sd.d_keys, io.sd.nkeys, slots, io.nby,
-                                      io.ncols, io.sd.max_att, io.sd.truth, io.sd.floats, io.sd.like, (uint4 *)(io.d_blocks + ch.lo), side_rec, side_cell, io.d_total,
-                                      io.d_groups, io.d_cells, io.group_cap, c->lz4_opts.cus, io.sd.d_buckets, io.sd.text));
+        HIP_TRY(c, cryo::launch_group(scan_chunk(c, ch, B), io.sd,
+                                      {.d_slots = slots, .nby = io.nby, .ncols = io.ncols, .d_blocks = (uint4 *)(io.d_blocks + ch.lo),
+                                       .d_side_rec = side_rec, .d_side_cell = side_cell, .d_running = io.d_total, .d_rec = io.d_groups,
+                                       .d_cells = io.d_cells, .group_cap = io.group_cap}));
         return CRYO_OK;
     };
     return decode_pass(c, method, B, n, ps);
@@ -1805,9 +1800,10 @@ static int project_pass(cryo_codec *c, int method, const uint8_t *d_src, const u
             }
         }
         uint8_t *side_rec = ch.own, *side_rows = ch.own + ch.K * S * sizeof(cryo_project_rec);
-        HIP_TRY(c, cryo::launch_project(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.sd.d_atts, io.sd.d_keys, io.sd.nkeys, tab,
-                                        io.pt.ncols, io.pt.row_bytes, io.sd.max_att, io.sd.truth, io.sd.floats, io.sd.like, (uint4 *)(io.d_blocks + ch.lo),
-                                        side_rec, side_rows, io.d_total, io.d_rec, io.rec_cap, io.d_rows, io.row_cap, c->lz4_opts.cus));
+        HIP_TRY(c, cryo::launch_project(scan_chunk(c, ch, B), io.sd,
+                                        {.d_cols = tab, .ncols = io.pt.ncols, .row_bytes = io.pt.row_bytes, .d_blocks = (uint4 *)(io.d_blocks + ch.lo),
+                                         .d_side_rec = side_rec, .d_side_rows = side_rows, .d_running = io.d_total, .d_rec = io.d_rec,
+                                         .rec_cap = io.rec_cap, .d_rows = io.d_rows, .row_cap = io.row_cap}));
         return CRYO_OK;
     };
     return decode_pass(c, method, B, n, ps);
@@ -1884,10 +1880,11 @@ static int topn_pass(cryo_codec *c, int method, const uint8_t *d_src, const uint
         /* records and rows are whole words; the order list, of 4-byte entries, lies behind them */
         uint8_t *side_rec = ch.own, *side_rows = side_rec + ch.K * S * sizeof(cryo_topn_rec);
         uint8_t *side_ord = side_rows + ch.K * S * io.tt.row_bytes;
-        HIP_TRY(c, cryo::launch_topn(c->stream, ch.dec, ch.Bp, B, ch.cnt, ch.dec_st, io.sd.d_atts, io.sd.d_keys, io.sd.nkeys, tab, io.tt.slots,
-                                     io.tt.nby, io.tt.ncols, io.tt.row_bytes, io.tt.limit, io.sd.max_att, io.sd.truth, io.sd.floats, io.sd.like,
-                                     (uint4 *)(io.d_blocks + ch.lo), side_rec, side_rows, side_ord, io.d_total, io.d_rec, io.d_rows, io.row_cap,
-                                     c->lz4_opts.cus));
+        HIP_TRY(c, cryo::launch_topn(scan_chunk(c, ch, B), io.sd,
+                                     {.d_slots = tab, .h_slots = io.tt.slots, .nby = io.tt.nby, .ncols = io.tt.ncols, .row_bytes = io.tt.row_bytes,
+                                      .limit = io.tt.limit, .d_blocks = (uint4 *)(io.d_blocks + ch.lo), .d_side_rec = side_rec,
+                                      .d_side_rows = side_rows, .d_side_ord = side_ord, .d_running = io.d_total, .d_rec = io.d_rec,
+                                      .d_rows = io.d_rows, .row_cap = io.row_cap}));
         return CRYO_OK;
     };
     return decode_pass(c, method, B, n, ps);

@@ -223,37 +223,27 @@ k_filter_copy(uint32_t cnt, const uint8_t *__restrict__ dec, uint64_t dec_stride
     }
 }
 
-hipError_t launch_filter(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
-                         const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, uint32_t max_att,
-                         uint32_t truth, bool floats, bool like, bool count_only, uint4 *d_blocks, uint4 *d_side, uint64_t *d_sum, uint64_t *d_base, uint64_t *d_running,
-                         uint8_t *d_dst, uint64_t dst_cap, uint2 *d_rec, uint64_t rec_cap, bool chunk_relative, int cus)
+hipError_t launch_filter(const ScanChunk &c, const ScanDesc &d, const FilterLaunch &f)
 {
-    if (cnt == 0) return hipSuccess;
-    if (!scan_launch_ok(dec_stride, d_dec, d_blocks, d_atts, d_keys, (uintptr_t)d_dst | (uintptr_t)d_rec, block_size, nkeys, truth, floats || like) ||
-        ((uintptr_t)d_side & 15u) != 0)
-        return hipErrorInvalidValue;
-    const uint32_t stride = filter_side_stride(block_size);
+    if (c.cnt == 0) return hipSuccess;
+    if (!filter_launch_ok(c, d, f)) return hipErrorInvalidValue;
     /* the integer-only descriptor keeps its own instantiation: the code it had before byte-string keys; a float key has a kernel
      * of its own, and a pattern key one in a unit of its own (below) */
-    hipError_t e;
-    if (like) e = launch_filterl_match(s, d_dec, dec_stride, block_size, cnt, d_dec_status, d_atts, d_keys, nkeys, max_att, truth, count_only, stride, d_blocks, d_side, d_sum);
-    else {
-        hipLaunchKernelGGL(floats ? k_filterf_match : truth ? k_filter_match<true> : k_filter_match<false>, dim3((cnt + 3u) / 4u), dim3(256), 0, s, d_dec,
-                           dec_stride, block_size, cnt, d_dec_status, (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys | truth << 16, max_att,
-                           count_only ? 1u : 0u, stride, d_blocks, d_side, d_sum);
-        e = hipGetLastError();
+    hipError_t e = hipErrorInvalidValue;
+    switch (scan_route(d.truth, d.floats, d.like)) {
+    case kRouteLike: e = launch_filterl_match(c, d, f); break;
+    case kRouteFloat: e = filter_launch(k_filterf_match, true, c, d, f); break;
+    case kRouteTable: e = filter_launch(k_filter_match<true>, true, c, d, f); break;
+    case kRoutePlain: e = filter_launch(k_filter_match<false>, false, c, d, f); break;
     }
-    if (e != hipSuccess || count_only) return e;
-    hipLaunchKernelGGL(k_filter_offsets, dim3(1), dim3(256), 0, s, cnt, d_sum, d_base, d_running, d_blocks);
+    if (e != hipSuccess || f.count_only) return e;
+    hipLaunchKernelGGL(k_filter_offsets, dim3(1), dim3(256), 0, c.stream, c.cnt, f.d_sum, f.d_base, f.d_running, f.d_blocks);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    /* four workgroups per compute unit, but never more than the chunk's worst case has pieces (or blocks, for the records) */
-    const uint64_t worst = ((uint64_t)cnt * block_size + kFilterPiece - 1u) / kFilterPiece;
-    uint64_t grid = (uint64_t)(cus > 0 ? cus : 256) * 4u;
-    if (grid > worst) grid = worst;
-    if (grid < 1u) grid = 1u;
-    hipLaunchKernelGGL(k_filter_copy, dim3((uint32_t)grid), dim3(256), 0, s, cnt, d_dec, dec_stride, stride, d_base, d_side, d_dst,
-                       dst_cap, d_rec, rec_cap, chunk_relative ? 1u : 0u);
+    /* never more workgroups than the chunk's worst case has pieces (or blocks, for the records) */
+    const uint64_t worst = ((uint64_t)c.cnt * c.block_size + kFilterPiece - 1u) / kFilterPiece;
+    hipLaunchKernelGGL(k_filter_copy, dim3(scan_copy_grid(c.cus, worst)), dim3(256), 0, c.stream, c.cnt, c.d_dec, c.dec_stride,
+                       filter_side_stride(c.block_size), f.d_base, f.d_side, f.d_dst, f.dst_cap, f.d_rec, f.rec_cap, f.chunk_relative ? 1u : 0u);
     return hipGetLastError();
 }
 
@@ -272,16 +262,9 @@ k_filterl_match(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B
                                         side, sum);
 }
 
-hipError_t launch_filterl_match(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
-                                const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, uint32_t max_att,
-                                uint32_t truth, bool count_only, uint32_t side_stride, uint4 *d_blocks, uint4 *d_side, uint64_t *d_sum)
+hipError_t launch_filterl_match(const ScanChunk &c, const ScanDesc &d, const FilterLaunch &f)
 {
-    /* the arguments are launch_filter's, which checked them; the one verdict path needs a table */
-    if (truth == 0u) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_filterl_match, dim3((cnt + 3u) / 4u), dim3(256), 0, s, d_dec, dec_stride, block_size, cnt, d_dec_status,
-                       (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys | truth << 16, max_att, count_only ? 1u : 0u, side_stride,
-                       d_blocks, d_side, d_sum);
-    return hipGetLastError();
+    return filter_launch(k_filterl_match, true, c, d, f);
 }
 #endif
 

@@ -247,7 +247,7 @@ __device__ inline bool walk_like(const uint8_t *__restrict__ p, uint32_t plen, b
  * depend on the loop counters only.  BYTES: a key of type kKeyBytes compares the column's in-line payload with the rsv bytes at
  * value (walk_bytes_sign), and a key of op kOpIn / kOpNotIn tests the column's value against the rsv sorted members at value
  * (walk_set_has); without BYTES no key has that type or those ops.  BYTES again: nkeys is the key count in its low half and the
- * truth table W in its high half (bit m of W: a match when exactly the keys of mask m are true; monotone, the host's rule), and
+ * truth table W in its high half (kernels.h, scan_nkeys_arg, packs them; bit m of W: a match when exactly the keys of mask m are true; monotone, the host's rule), and
  * the verdict on a good tuple with t the keys that are true and u those that are undecided is a match if W[t], no match if not
  * W[t | u], undecided otherwise; without BYTES nkeys is the count alone and the keys are ANDed.  NARROW: a captured column may have attlen 1 (the projection's
  * argument rule: attlen 1, 2, 4 or 8 and attalign at least that).  FLOATS (with BYTES alone): a comparison key of type kKeyFloat4 or

@@ -22,9 +22,9 @@
  *   k_group_copy     a grid stride over the blocks: block k's records and cells from the side area to first_group of the call's
  *                    output, word by word, cut off at group_cap.
  * A descriptor with a float key or a float aggregate column runs group_float.hip's k_groupf_block in k_group_block's place
- * (launch_group's `floats`), a descriptor with bucketed group columns group_bucket.hip's k_groupb_block (launch_group's
- * d_buckets), a descriptor with a byte-string group column group_text.hip's k_groupt_block (launch_group's text); the other two
- * kernels serve all of them.
+ * (ScanDesc::floats), a descriptor with bucketed group columns group_bucket.hip's k_groupb_block (ScanDesc::d_buckets), a
+ * descriptor with a byte-string group column group_text.hip's k_groupt_block (ScanDesc::text); the other two kernels serve all
+ * of them.
  * Every device write is a vector store in plain C++.  No scratch, no global atomics.
  */
 #include "kernels.h"
@@ -57,7 +57,7 @@ k_group_offsets(uint32_t cnt, uint64_t *__restrict__ running, uint4 *__restrict_
 }
 
 /* records (3 words each) and cells (5 words each) of the chunk's blocks from the side area to their places within the call;
- * ncols: the cells of a group (with a text group column its key cells count, launch_group) */
+ * ncols: the cells of a group (with a text group column its key cells count: launch_group's cpg) */
 __global__ void __launch_bounds__(256)
 k_group_copy(uint32_t cnt, uint32_t side_stride, uint32_t ncols, const uint4 *__restrict__ blocks,
              const uint64_t *__restrict__ side_rec, const uint64_t *__restrict__ side_cell, uint64_t *__restrict__ rec,
@@ -78,56 +78,33 @@ k_group_copy(uint32_t cnt, uint32_t side_stride, uint32_t ncols, const uint4 *__
     }
 }
 
-hipError_t launch_group(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
-                        const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,
-                        uint32_t nby, uint32_t ncols, uint32_t max_att, uint32_t truth, bool floats, bool like, uint4 *d_blocks, void *d_side_rec, void *d_side_cell,
-                        uint64_t *d_running, void *d_rec, void *d_cells, uint64_t group_cap, int cus, const void *d_buckets, uint32_t text)
+hipError_t launch_group(const ScanChunk &c, const ScanDesc &d, const GroupLaunch &g)
 {
-    if (cnt == 0) return hipSuccess;
-    const uint32_t cpg = ncols + (uint32_t)__builtin_popcount(text); /* a group's cells: ncols unless it has key cells */
-    if (!scan_launch_ok(dec_stride, d_dec, d_blocks, d_atts, d_keys,
-                        (uintptr_t)d_rec | (uintptr_t)d_cells | (uintptr_t)d_slots | (uintptr_t)d_side_rec | (uintptr_t)d_side_cell |
-                            (uintptr_t)d_running,
-                        block_size, nkeys, truth, floats || like) ||
-        nby == 0u || nby > kGroupMaxBy || ncols > kAggMaxCols || (text >> nby) != 0u || (text != 0u && d_buckets) ||
-        !d_slots || !d_side_rec || !d_running || (cpg > 0u && !d_side_cell) || (group_cap > 0u && (!d_rec || (cpg > 0u && !d_cells))))
-        return hipErrorInvalidValue;
-    const uint32_t stride = filter_side_stride(block_size);
-    hipError_t e;
-    if (text && like) /* a byte-string group column and a pattern key: group_text.hip's second unit, then the same two on cpg cells */
-        e = launch_grouptl_block(s, d_dec, dec_stride, block_size, cnt, d_dec_status, d_atts, d_keys, nkeys, d_slots, nby, ncols, text,
-                                 max_att, truth, stride, d_blocks, d_side_rec, d_side_cell);
-    else if (text) /* a byte-string group column: group_text.hip's block kernels, then the same two on cpg cells a group */
-        e = launch_groupt_block(s, d_dec, dec_stride, block_size, cnt, d_dec_status, d_atts, d_keys, nkeys, d_slots, nby, ncols, text,
-                                max_att, truth, floats, stride, d_blocks, d_side_rec, d_side_cell);
-    else if (d_buckets && like) /* buckets and a pattern key: group_bucket.hip's second unit, then the same two */
-        e = launch_groupbl_block(s, d_dec, dec_stride, block_size, cnt, d_dec_status, d_atts, d_keys, nkeys, d_slots, d_buckets, nby, ncols,
-                                 max_att, truth, stride, d_blocks, d_side_rec, d_side_cell);
-    else if (d_buckets) /* a CRYO_GROUP_BUCKETS descriptor: group_bucket.hip's block kernels, then the same two */
-        e = launch_groupb_block(s, d_dec, dec_stride, block_size, cnt, d_dec_status, d_atts, d_keys, nkeys, d_slots, d_buckets, nby, ncols,
-                                max_att, truth, floats, stride, d_blocks, d_side_rec, d_side_cell);
-    else if (like) /* a pattern key: group_float.hip's second unit, then the same two */
-        e = launch_groupl_block(s, d_dec, dec_stride, block_size, cnt, d_dec_status, d_atts, d_keys, nkeys, d_slots, nby, ncols, max_att,
-                                truth, stride, d_blocks, d_side_rec, d_side_cell);
-    else if (floats) /* a float key or a float aggregate column: group_float.hip's block kernel, then the same two */
-        e = launch_groupf_block(s, d_dec, dec_stride, block_size, cnt, d_dec_status, d_atts, d_keys, nkeys, d_slots, nby, ncols, max_att,
-                                truth, stride, d_blocks, d_side_rec, d_side_cell);
-    else {
-        hipLaunchKernelGGL(truth ? k_group_block<true> : k_group_block<false>, dim3((cnt + kGroupWaves - 1u) / kGroupWaves), dim3(64 * kGroupWaves), 0, s, d_dec, dec_stride,
-                           block_size, cnt, d_dec_status, (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys | truth << 16,
-                           (const AggCol *)d_slots, nby, ncols, max_att, stride, d_blocks, (GroupRec *)d_side_rec,
-                           (AggCell *)d_side_cell);
-        e = hipGetLastError();
+    if (c.cnt == 0) return hipSuccess;
+    if (!group_launch_ok(c, d, g)) return hipErrorInvalidValue;
+    /* the block kernel of the descriptor's route (kernels.h: the table), then the same two for all: on ncols cells a group, and
+     * behind group_text.hip's kernels on the key cells too */
+    hipError_t e = hipErrorInvalidValue;
+    switch (group_route(d.text, d.d_buckets != nullptr, d.truth, d.floats, d.like)) {
+    case kGroupTextLike: e = launch_grouptl_block(c, d, g); break;
+    case kGroupText:
+    case kGroupTextFloat: e = launch_groupt_block(c, d, g); break;
+    case kGroupBucketLike: e = launch_groupbl_block(c, d, g); break;
+    case kGroupBucket:
+    case kGroupBucketFloat: e = launch_groupb_block(c, d, g); break;
+    case kGroupLike: e = launch_groupl_block(c, d, g); break;
+    case kGroupFloat: e = launch_groupf_block(c, d, g); break;
+    case kGroupTable: e = group_launch(k_group_block<true>, true, c, d, g); break;
+    case kGroupPlain: e = group_launch(k_group_block<false>, false, c, d, g); break;
     }
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_group_offsets, dim3(1), dim3(256), 0, s, cnt, d_running, d_blocks);
+    hipLaunchKernelGGL(k_group_offsets, dim3(1), dim3(256), 0, c.stream, c.cnt, g.d_running, g.d_blocks);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    /* four workgroups per compute unit, but never more than the chunk has blocks */
-    uint64_t grid = (uint64_t)(cus > 0 ? cus : 256) * 4u;
-    if (grid > cnt) grid = cnt;
-    hipLaunchKernelGGL(k_group_copy, dim3((uint32_t)grid), dim3(256), 0, s, cnt, stride, cpg, (const uint4 *)d_blocks,
-                       (const uint64_t *)d_side_rec, (const uint64_t *)d_side_cell, (uint64_t *)d_rec, (uint64_t *)d_cells, group_cap);
+    const uint32_t cpg = g.ncols + (uint32_t)__builtin_popcount(d.text); /* a group's cells: ncols unless it has key cells */
+    hipLaunchKernelGGL(k_group_copy, dim3(scan_copy_grid(c.cus, c.cnt)), dim3(256), 0, c.stream, c.cnt, filter_side_stride(c.block_size), cpg,
+                       (const uint4 *)g.d_blocks, (const uint64_t *)g.d_side_rec, (const uint64_t *)g.d_side_cell, (uint64_t *)g.d_rec,
+                       (uint64_t *)g.d_cells, g.group_cap);
     return hipGetLastError();
 }
 

@@ -130,18 +130,9 @@ k_groupb_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B,
                               side_rec, side_cell, GroupBucketKeys{buckets, slots, nby});
 }
 
-hipError_t launch_groupb_block(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
-                               const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,
-                               const void *d_buckets, uint32_t nby, uint32_t ncols, uint32_t max_att, uint32_t truth, bool floats,
-                               uint32_t side_stride, uint4 *d_blocks, void *d_side_rec, void *d_side_cell)
+hipError_t launch_groupb_block(const ScanChunk &c, const ScanDesc &d, const GroupLaunch &g)
 {
-    /* the other arguments are launch_group's, which checked them; the one verdict path needs a table */
-    if (truth == 0u || !d_buckets || ((uintptr_t)d_buckets & 7u) != 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(floats ? k_groupb_block<true> : k_groupb_block<false>, dim3((cnt + kGroupWaves - 1u) / kGroupWaves),
-                       dim3(64 * kGroupWaves), 0, s, d_dec, dec_stride, block_size, cnt, d_dec_status, (const FilterAtt *)d_atts,
-                       (const FilterKey *)d_keys, nkeys | truth << 16, (const AggCol *)d_slots, (const GroupBucket *)d_buckets, nby,
-                       ncols, max_att, side_stride, d_blocks, (GroupRec *)d_side_rec, (AggCell *)d_side_cell);
-    return hipGetLastError();
+    return group_launch(d.floats ? k_groupb_block<true> : k_groupb_block<false>, true, c, d, g);
 }
 
 #else /* CRYO_LIKE_UNIT */
@@ -162,19 +153,7 @@ k_groupbl_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B
                                   blocks, side_rec, side_cell, GroupBucketKeys{buckets, slots, nby});
 }
 
-hipError_t launch_groupbl_block(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
-                                const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,
-                                const void *d_buckets, uint32_t nby, uint32_t ncols, uint32_t max_att, uint32_t truth,
-                                uint32_t side_stride, uint4 *d_blocks, void *d_side_rec, void *d_side_cell)
-{
-    /* the other arguments are launch_group's, which checked them; the one verdict path needs a table */
-    if (truth == 0u || !d_buckets || ((uintptr_t)d_buckets & 7u) != 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_groupbl_block, dim3((cnt + kGroupWaves - 1u) / kGroupWaves), dim3(64 * kGroupWaves), 0, s, d_dec, dec_stride,
-                       block_size, cnt, d_dec_status, (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys | truth << 16,
-                       (const AggCol *)d_slots, (const GroupBucket *)d_buckets, nby, ncols, max_att, side_stride, d_blocks,
-                       (GroupRec *)d_side_rec, (AggCell *)d_side_cell);
-    return hipGetLastError();
-}
+hipError_t launch_groupbl_block(const ScanChunk &c, const ScanDesc &d, const GroupLaunch &g) { return group_launch(k_groupbl_block, true, c, d, g); }
 #endif
 
 } // namespace cryo

@@ -6,7 +6,8 @@
  * are one body (group_block) that differs in the walk's BYTES and FLOATS and in the step that maps the captured group values
  * (GroupRawKeys: none; group_bucket.hip: to bucket keys).  k_groupt_block keeps the layout (GroupLds inside its own, wider LDS)
  * and the barrier, states steps 1 and 2 for keys that carry a byte string's words, and hands group_reduce the step that writes
- * a group's key cells (GroupNoKeyCells: none).
+ * a group's key cells (GroupNoKeyCells: none).  And, for the host, the launch of such a kernel (group_launch), which the four
+ * units' launchers share.
  */
 #pragma once
 #include "kernels.h"
@@ -210,5 +211,29 @@ __device__ inline void group_block(GroupLds &L, uint32_t k, uint32_t lane, const
         blocks[2u * k + 1u] = make_uint4(n_groups, 0u, 0u, 0u); /* first_group: k_group_offsets */
     }
 }
+
+/* ---- the host's side: the block-kernel launch of the grouped scan (scan_sweep.h: scan_block_launch), one per parameter list.
+ * Behind the slots the kernels on GroupLds take nby, ncols, max_att, the bucket kernels the bucket table first, and the text
+ * kernels, of one wave per workgroup, the text mask behind ncols; all end alike ---- */
+struct GroupBucket; /* group_bucket.hip */
+inline hipError_t group_launch(ScanKernel<const AggCol *, uint32_t, uint32_t, uint32_t, uint32_t, uint4 *, GroupRec *, AggCell *> kernel, bool table,
+                               const ScanChunk &c, const ScanDesc &d, const GroupLaunch &g)
+{
+    return scan_block_launch(kernel, kGroupWaves, table, c, d, (const AggCol *)g.d_slots, g.nby, g.ncols, d.max_att,
+                             filter_side_stride(c.block_size), g.d_blocks, (GroupRec *)g.d_side_rec, (AggCell *)g.d_side_cell);
+}
+inline hipError_t group_launch(ScanKernel<const AggCol *, const GroupBucket *, uint32_t, uint32_t, uint32_t, uint32_t, uint4 *, GroupRec *, AggCell *> kernel,
+                               bool table, const ScanChunk &c, const ScanDesc &d, const GroupLaunch &g)
+{
+    return scan_block_launch(kernel, kGroupWaves, table, c, d, (const AggCol *)g.d_slots, (const GroupBucket *)d.d_buckets, g.nby, g.ncols, d.max_att,
+                             filter_side_stride(c.block_size), g.d_blocks, (GroupRec *)g.d_side_rec, (AggCell *)g.d_side_cell);
+}
+inline hipError_t group_launch(ScanKernel<const AggCol *, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint4 *, GroupRec *, AggCell *> kernel,
+                               bool table, const ScanChunk &c, const ScanDesc &d, const GroupLaunch &g)
+{
+    return scan_block_launch(kernel, 1u, table, c, d, (const AggCol *)g.d_slots, g.nby, g.ncols, d.text, d.max_att,
+                             filter_side_stride(c.block_size), g.d_blocks, (GroupRec *)g.d_side_rec, (AggCell *)g.d_side_cell);
+}
+static_assert(kGroupMaxBy == CRYO_GROUP_MAX_BY && kAggMaxCols == CRYO_AGG_MAX_COLS, "group_launch_ok's limits (kernels.h) are the kernels'");
 
 } // namespace cryo

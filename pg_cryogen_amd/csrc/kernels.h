@@ -10,6 +10,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "cryo_codec.h"
 #include "heap_block.h"
 
 /* Tuning and debugging switches read from the environment exist in -DCRYO_DEBUG builds only (the A/B builds under
@@ -238,165 +239,271 @@ hipError_t launch_fetch(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride
                         uint4 *d_result, uint2 *d_side, uint64_t *d_sum, uint64_t *d_base, uint64_t *d_running, uint8_t *d_dst,
                         uint64_t dst_cap, bool chunk_relative, int cus);
 
-/* the scan filter (filter.hip) on one decoded chunk of cnt blocks (laid out as for launch_fetch): k_filter_match,
- * k_filter_offsets, k_filter_copy.  The descriptor is validated by the caller (cryo_codec.cpp, filter_desc_ok): d_atts natts
- * entries of {i16 attlen, u8 attalign, u8 0}, d_keys nkeys <= 4 entries of cryo_scan_key (device memory), max_att the highest
- * key column (0: no key).  A key may have type CRYO_KEY_BYTES or be a set key (CRYO_OP_IN, CRYO_OP_NOT_IN: rsv distinct members, ascending, at the device address in value) when d_keys is the library's key table (cryo_codec.cpp,
- * key_table_fill): the value of such a key is the device address of its constant, 8-byte aligned and zero-padded to a multiple
- * of 8.  truth: 0 -- the keys are ANDed and none is of those kinds: k_filter_match<false>, which knows no such key and no table;
- * otherwise the descriptor's truth table (CRYO_FILTER_TRUTH; the AND table 1 << (2^nkeys - 1) for a descriptor without the flag
- * that has such a key), at most 16 bits: k_filter_match<true> runs and finds it in the high half of its nkeys argument
- * (filter_walk.h).  floats (here and in launch_agg, launch_group, launch_project): a key has a float type (CRYO_KEY_FLOAT4,
- * CRYO_KEY_FLOAT8; its value in the key table is the mapped constant, float_map) or an aggregate column has one; truth is then
- * not 0 and the float kernel runs in the <true> one's place (k_filterf_match, k_aggf_block, k_groupf_block, k_projectf_block).
- * like (in all five launchers): a key has op CRYO_OP_LIKE or CRYO_OP_NOT_LIKE (its value in the key table is the device address
- * of its compiled pattern, walk_like); truth is then not 0 and the pattern kernel runs in every other's place, float keys and
- * float columns or not (k_filterl_match, k_aggl_block, k_groupl_block, k_groupbl_block, k_grouptl_block, k_projectl_block,
- * k_topnl_block): kernels of their own names, so that a descriptor without such a key runs the code it ran.  Each lives
- * with its launcher (launch_*l_*, at the end of this header) in a unit of its own: the source of its float sibling compiled a
- * second time with CRYO_LIKE_UNIT, which then holds nothing else (the Makefile's %_like.o).
- * An undecided tuple gets a
- * record {pos, 9, 0} and counts in n_bad.  d_blocks: the chunk's rows of the block table (cryo_filter_block, 16-byte aligned).  Scratch: d_side
- * 16 bytes per possible item (cnt * filter_side_stride(block_size) entries), d_sum 2 * cnt and d_base 2 * (cnt + 1) entries.
- * d_running: the two totals {bytes, records} before the chunk in, after it out.  The chunk's tuples go to d_dst (8-byte aligned)
- * and its records to d_rec at their places within the call, or -- chunk_relative -- at those less the chunk's first; a tuple that
- * would end beyond dst_cap and a record at or beyond rec_cap are not written.  count_only: k_filter_match alone; rec_first and
- * off of the table are 0 and nothing else is written. */
+/* ---- the five scan calls: filter (filter.hip), aggregate (agg.hip), group (group.hip), project (project.hip), top-N (topn.hip) ----
+ * Each works on one decoded chunk (ScanChunk) under one descriptor (ScanDesc) and takes what is its own in a struct of its
+ * own; a call site names the fields it sets.  The caller (cryo_codec.cpp, *_desc_ok) has validated the descriptor; X_launch_ok
+ * below is what launch_X asks of its arguments beyond that.  Which block kernel runs is scan_route's and group_route's; the
+ * block-kernel launch itself is stated once per call, where the call's units share it (scan_sweep.h: scan_block_launch,
+ * filter_launch, agg_launch, project_launch; group_lds.h: group_launch; topn.hip: topn_launch). */
+
+/* what a launcher is told about the decoded chunk and the device: cnt blocks, block k at d_dec + k * dec_stride (16-byte aligned
+ * rows), its decoder status in d_dec_status[k]; cus: compute units of the device (0: an MI355X's 256) */
+struct ScanChunk {
+    hipStream_t stream = nullptr;
+    const uint8_t *d_dec = nullptr;
+    uint64_t dec_stride = 0;
+    uint32_t block_size = 0, cnt = 0;
+    const int32_t *d_dec_status = nullptr;
+    int cus = 0;
+};
+
+/* what every scan call tells its kernels about the relation and the keys (the host fills it: cryo_codec.cpp, scan_desc_device,
+ * key_table_device).  d_atts: natts entries of {i16 attlen, u8 attalign, u8 0}; d_keys: nkeys <= 4 entries of cryo_scan_key.  A key
+ * may have type CRYO_KEY_BYTES, a float type, or be a set key or a pattern key when d_keys is the library's key table
+ * (key_table_fill): its value is then the mapped constant (float_map) or the device address of its constant, its sorted members
+ * or its compiled pattern, 8-byte aligned and zero-padded to a multiple of 8 */
+struct ScanDesc {
+    const void *d_atts = nullptr, *d_keys = nullptr; /* device */
+    uint32_t nkeys = 0, max_att = 0;                 /* max_att: the highest column the walk has to reach */
+    uint32_t truth = 0;                              /* 0: the keys are ANDed by the kernels' <false> instantiation; otherwise the
+                                                        truth table of the <true> one (scan_truth), at most 16 bits */
+    bool floats = false;                             /* a float key or a float aggregate column: the float kernels, which have
+                                                        the truth table's verdict path alone (truth is not 0 then) */
+    bool like = false;                               /* a pattern key (CRYO_OP_LIKE, CRYO_OP_NOT_LIKE): the pattern kernels, which
+                                                        also do what the float kernels do (truth is not 0 then) */
+    const void *d_buckets = nullptr;                 /* device: the grouping's bucket table under CRYO_GROUP_BUCKETS (truth is not 0
+                                                        then), else null: two entries of 24 bytes (cryo_bucket; a list's n its distinct
+                                                        boundaries and value the device address of the library's sorted copy) */
+    uint32_t text = 0;                               /* the grouping's: bit j set when group column j is a byte string
+                                                        (CRYO_GROUP_TEXT; truth is not 0 then) */
+};
+
+/* The block kernel a descriptor reaches.  like goes over floats goes over a table: a pattern kernel also does what the float
+ * kernel does, a float kernel what the <true> one does.  The pattern kernels have names of their own and live, each with its
+ * launcher (launch_*l_*), in a unit of their own -- the source of the float sibling compiled a second time with CRYO_LIKE_UNIT
+ * (the Makefile's %_like.o) --, so that a descriptor without such a key runs the code it ran.
+ *   route        filter                 aggregate           project                 top-N
+ *   kRoutePlain  k_filter_match<false>  k_agg_block<false>  k_project_block<false>  k_topn_block<false>   truth == 0
+ *   kRouteTable  k_filter_match<true>   k_agg_block<true>   k_project_block<true>   k_topn_block<true>    truth != 0
+ *   kRouteFloat  k_filterf_match        k_aggf_block        k_projectf_block        k_topnf_block         floats
+ *   kRouteLike   k_filterl_match        k_aggl_block        k_projectl_block        k_topnl_block         like */
+enum ScanRoute { kRoutePlain, kRouteTable, kRouteFloat, kRouteLike };
+inline ScanRoute scan_route(uint32_t truth, bool floats, bool like)
+{
+    return like ? kRouteLike : floats ? kRouteFloat : truth ? kRouteTable : kRoutePlain;
+}
+/* The grouped scan's: a byte-string group column (text) goes over buckets, and either over the four routes above.
+ *   route                                                 text    buckets  floats  like
+ *   kGroupPlain / kGroupTable  k_group_block<false> / <true>  0   no       no      no    (truth == 0 / != 0)
+ *   kGroupFloat        k_groupf_block                     0       no       yes     no
+ *   kGroupLike         k_groupl_block                     0       no       any     yes
+ *   kGroupBucket       k_groupb_block<false>              0       yes      no      no
+ *   kGroupBucketFloat  k_groupb_block<true>               0       yes      yes     no
+ *   kGroupBucketLike   k_groupbl_block                    0       yes      any     yes
+ *   kGroupText         k_groupt_block<false>              not 0   any      no      no
+ *   kGroupTextFloat    k_groupt_block<true>               not 0   any      yes     no
+ *   kGroupTextLike     k_grouptl_block                    not 0   any      any     yes
+ * (text with buckets never gets here: group_launch_ok) */
+enum GroupRoute {
+    kGroupPlain, kGroupTable, kGroupFloat, kGroupLike, kGroupBucket, kGroupBucketFloat, kGroupBucketLike, kGroupText, kGroupTextFloat,
+    kGroupTextLike
+};
+inline GroupRoute group_route(uint32_t text, bool has_buckets, uint32_t truth, bool floats, bool like)
+{
+    if (text) return like ? kGroupTextLike : floats ? kGroupTextFloat : kGroupText;
+    if (has_buckets) return like ? kGroupBucketLike : floats ? kGroupBucketFloat : kGroupBucket;
+    return like ? kGroupLike : floats ? kGroupFloat : truth ? kGroupTable : kGroupPlain;
+}
+
+/* the block kernels' nkeys argument: the key count below the truth table, which the <true>, float and pattern kernels find in
+ * its high half (filter_walk.h, walk_tuple) */
+inline uint32_t scan_nkeys_arg(uint32_t nkeys, uint32_t truth) { return nkeys | truth << 16; }
+
+/* the grid of a call's copy kernel: four workgroups per compute unit (256 units when cus is 0), at most cap, at least one */
+inline uint32_t scan_copy_grid(int cus, uint64_t cap)
+{
+    const uint64_t grid = (uint64_t)(cus > 0 ? cus : 256) * 4u;
+    return (uint32_t)(grid > cap ? (cap > 0u ? cap : 1u) : grid);
+}
+
+/* a block's row of every side area: the items it can hold */
 inline uint32_t filter_side_stride(uint32_t block_size)
 {
     const uint32_t fit = (block_size - 8u) / 8u; /* lower <= B: no more item ids than this */
     return fit < kHeapMaxItems ? fit : kHeapMaxItems;
 }
-/* what the launchers of the four scan calls ask of their arguments alike: the chunk and the block table 16-byte aligned, the
+
+/* what the launchers of the five scan calls ask of their arguments alike: the chunk and the block table 16-byte aligned, the
  * keys and -- eight: the call's other 8-byte tables and outputs, ORed -- 8-byte aligned, the column descriptor 4-byte aligned, a
- * block that holds a header and an item, at most four keys, a table of 16 bits, and a table wherever a float kernel runs */
-inline bool scan_launch_ok(uint64_t dec_stride, const void *d_dec, const void *d_blocks, const void *d_atts, const void *d_keys,
-                           uintptr_t eight, uint32_t block_size, uint32_t nkeys, uint32_t truth, bool floats)
+ * block that holds a header and an item, at most four keys, a table of 16 bits, and a table wherever a float or pattern kernel runs */
+inline bool scan_launch_ok(const ScanChunk &c, const ScanDesc &d, const void *d_blocks, uintptr_t eight)
 {
-    return (dec_stride & 15u) == 0 && (((uintptr_t)d_dec | (uintptr_t)d_blocks) & 15u) == 0 && (((uintptr_t)d_keys | eight) & 7u) == 0 &&
-           ((uintptr_t)d_atts & 3u) == 0 && block_size >= 16u && nkeys <= 4u && truth <= 0xFFFFu && !(floats && truth == 0u);
+    return (c.dec_stride & 15u) == 0 && (((uintptr_t)c.d_dec | (uintptr_t)d_blocks) & 15u) == 0 && (((uintptr_t)d.d_keys | eight) & 7u) == 0 &&
+           ((uintptr_t)d.d_atts & 3u) == 0 && c.block_size >= 16u && d.nkeys <= 4u && d.truth <= 0xFFFFu &&
+           !((d.floats || d.like) && d.truth == 0u);
 }
-hipError_t launch_filter(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
-                         const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, uint32_t max_att,
-                         uint32_t truth, bool floats, bool like, bool count_only, uint4 *d_blocks, uint4 *d_side, uint64_t *d_sum, uint64_t *d_base, uint64_t *d_running,
-                         uint8_t *d_dst, uint64_t dst_cap, uint2 *d_rec, uint64_t rec_cap, bool chunk_relative, int cus);
 
-/* the scan aggregate (agg.hip) on one decoded chunk of cnt blocks (laid out as for launch_filter): k_agg_block alone.  The
- * descriptors are validated by the caller (cryo_codec.cpp, agg_desc_ok): d_atts and d_keys as for launch_filter, d_cols ncols
- * (1 .. 4) entries of cryo_agg_col (device memory, 8-byte aligned), max_att the highest key or aggregate column, truth as
- * for launch_filter (k_agg_block<true> / <false>; an undecided tuple counts in n_bad and is in no cell).  d_blocks: the
- * chunk's rows (cryo_agg_block, 16-byte aligned); d_cells: its cnt * ncols cells (cryo_agg_cell, 8-byte aligned), block k's at
- * k * ncols.  Workspace rule: none -- the kernel keeps everything in registers and writes only the rows and the cells, so a pass
- * over it asks the shared decode loop for no bytes of its own. */
-hipError_t launch_agg(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
-                      const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_cols,
-                      uint32_t ncols, uint32_t max_att, uint32_t truth, bool floats, bool like, uint4 *d_blocks, void *d_cells);
-/* launch_agg's float branch (agg_float.hip): k_aggf_block alone, on arguments launch_agg has checked; truth is not 0 */
-hipError_t launch_aggf(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
-                       const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_cols,
-                       uint32_t ncols, uint32_t max_att, uint32_t truth, uint4 *d_blocks, void *d_cells);
+/* the scan filter: k_filter_match, k_filter_offsets, k_filter_copy.  An undecided tuple gets a record {pos, 9, 0} and counts in
+ * n_bad.  d_blocks: the chunk's rows of the block table (cryo_filter_block).  Scratch: d_side 16 bytes per possible item (cnt *
+ * filter_side_stride(block_size) entries, 16-byte aligned), d_sum 2 * cnt and d_base 2 * (cnt + 1) entries.  d_running: the two
+ * totals {bytes, records} before the chunk in, after it out.  The chunk's tuples go to d_dst and its records to d_rec at their
+ * places within the call, or -- chunk_relative -- at those less the chunk's first; a tuple that would end beyond dst_cap and a
+ * record at or beyond rec_cap are not written.  count_only: k_filter_match alone; rec_first and off of the table are 0 and
+ * nothing else is written */
+struct FilterLaunch {
+    bool count_only = false;
+    uint4 *d_blocks = nullptr, *d_side = nullptr;
+    uint64_t *d_sum = nullptr, *d_base = nullptr, *d_running = nullptr;
+    uint8_t *d_dst = nullptr;
+    uint64_t dst_cap = 0;
+    uint2 *d_rec = nullptr;
+    uint64_t rec_cap = 0;
+    bool chunk_relative = false;
+};
+inline bool filter_launch_ok(const ScanChunk &c, const ScanDesc &d, const FilterLaunch &f)
+{
+    return scan_launch_ok(c, d, f.d_blocks, (uintptr_t)f.d_dst | (uintptr_t)f.d_rec) && ((uintptr_t)f.d_side & 15u) == 0;
+}
+hipError_t launch_filter(const ScanChunk &c, const ScanDesc &d, const FilterLaunch &f);
+hipError_t launch_filterl_match(const ScanChunk &c, const ScanDesc &d, const FilterLaunch &f); /* filter_like.o */
 
-/* the grouped scan (group.hip) on one decoded chunk of cnt blocks (laid out as for launch_filter): k_group_block,
- * k_group_offsets, k_group_copy.  The descriptors are validated by the caller (cryo_codec.cpp, group_desc_ok): d_atts and d_keys as
- * for launch_filter; d_slots six entries of cryo_agg_col (device memory, 8-byte aligned): the nby (1 .. 2) group columns in
- * entries 0 .. 1, the ncols (0 .. 4) aggregate columns in entries 2 .. 5, every unused entry all zero; max_att the highest key,
- * group or aggregate column; truth as for launch_filter (k_group_block<true> / <false>; an undecided tuple counts in n_bad
- * and is in no group).  d_blocks: the chunk's rows (cryo_group_block, 16-byte aligned).  Scratch: d_side_rec 24 bytes and
- * d_side_cell 40 * ncols bytes per possible group (cnt * filter_side_stride(block_size) groups; both 8-byte aligned).
- * *d_running: the groups before the chunk in, after it out.  The chunk's records go to d_rec and its cells to d_cells (8-byte
- * aligned) at first_group within the call; nothing at or beyond group_cap groups is written.  cus as for launch_fetch.
- * d_buckets: null, or -- a CRYO_GROUP_BUCKETS descriptor -- the staged bucket table (launch_groupb_block), whose kernels run in
- * the block kernel's place; truth is not 0 then.  text: bit j set when group column j is a byte string (CRYO_GROUP_TEXT); not 0:
- * group_text.hip's kernels run in the block kernel's place (launch_groupt_block), truth is not 0, d_buckets is null, and a group
- * has ncols + popcount(text) cells in d_side_cell and d_cells, the aggregate cells first. */
-hipError_t launch_group(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
-                        const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,
-                        uint32_t nby, uint32_t ncols, uint32_t max_att, uint32_t truth, bool floats, bool like, uint4 *d_blocks,
-                        void *d_side_rec, void *d_side_cell,
-                        uint64_t *d_running, void *d_rec, void *d_cells, uint64_t group_cap, int cus, const void *d_buckets, uint32_t text);
-/* launch_group's bucket branch (group_bucket.hip): k_groupb_block<floats> alone, on arguments launch_group has checked; truth is
- * not 0; d_buckets the staged bucket table, 8-byte aligned: two entries of 24 bytes (cryo_bucket; a list's n its distinct
- * boundaries and value the device address of the library's sorted copy) */
-hipError_t launch_groupb_block(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
-                               const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,
-                               const void *d_buckets, uint32_t nby, uint32_t ncols, uint32_t max_att, uint32_t truth, bool floats,
-                               uint32_t side_stride, uint4 *d_blocks, void *d_side_rec, void *d_side_cell);
-/* launch_group's text branch (group_text.hip): k_groupt_block<floats> alone, on arguments launch_group has checked; truth and
- * text are not 0 */
-hipError_t launch_groupt_block(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
-                               const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,
-                               uint32_t nby, uint32_t ncols, uint32_t text, uint32_t max_att, uint32_t truth, bool floats,
-                               uint32_t side_stride, uint4 *d_blocks, void *d_side_rec, void *d_side_cell);
-/* launch_group's float branch (group_float.hip): k_groupf_block alone, on arguments launch_group has checked; truth is not 0 */
-hipError_t launch_groupf_block(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
-                               const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,
-                               uint32_t nby, uint32_t ncols, uint32_t max_att, uint32_t truth, uint32_t side_stride, uint4 *d_blocks,
-                               void *d_side_rec, void *d_side_cell);
+/* the scan aggregate: the block kernel alone.  d_cols: ncols (1 .. 4) entries of cryo_agg_col; ScanDesc::max_att reaches the
+ * highest aggregate column too; an undecided tuple counts in n_bad and is in no cell.  d_blocks: the chunk's rows
+ * (cryo_agg_block); d_cells: its cnt * ncols cells (cryo_agg_cell), block k's at k * ncols.  No workspace: the kernel keeps
+ * everything in registers and writes only the rows and the cells */
+struct AggLaunch {
+    const void *d_cols = nullptr;
+    uint32_t ncols = 0;
+    uint4 *d_blocks = nullptr;
+    void *d_cells = nullptr;
+};
+inline bool agg_launch_ok(const ScanChunk &c, const ScanDesc &d, const AggLaunch &a)
+{
+    return scan_launch_ok(c, d, a.d_blocks, (uintptr_t)a.d_cells | (uintptr_t)a.d_cols) && a.ncols != 0u && a.ncols <= CRYO_AGG_MAX_COLS;
+}
+hipError_t launch_agg(const ScanChunk &c, const ScanDesc &d, const AggLaunch &a);
+hipError_t launch_aggf(const ScanChunk &c, const ScanDesc &d, const AggLaunch &a); /* agg_float.o */
+hipError_t launch_aggl(const ScanChunk &c, const ScanDesc &d, const AggLaunch &a); /* agg_float_like.o */
 
-/* the projecting scan (project.hip) on one decoded chunk of cnt blocks (laid out as for launch_filter): k_project_block,
- * k_project_offsets, k_project_copy.  The descriptors are validated by the caller (cryo_codec.cpp, project_desc_ok): d_atts and
- * d_keys as for launch_filter; d_cols the staged column table, ncols (1 .. 8) entries of 8 bytes (device memory, 8-byte aligned):
- * {u16 att, u8 width (the column's attlen: 1, 2, 4, 8), u8 offset within the row (a multiple of the width, below row_bytes), u32
- * 0} -- the walk reads it as cryo_agg_col and looks at att alone; row_bytes the row's size, 8 .. 64 and a multiple of 8 (both from
- * CRYO_PROJECT_COL_OFFSET / CRYO_PROJECT_ROW_BYTES); max_att the highest key or projected column; truth as for launch_filter (k_project_block<true> /
- * <false>; an undecided tuple gets a record {pos, 9, 0}, counts in n_bad and has no row).  d_blocks: the chunk's rows of the
- * block table (cryo_project_block, 16-byte aligned).  Scratch: d_side_rec 8 bytes and d_side_rows row_bytes bytes per possible
- * item (cnt * filter_side_stride(block_size) items; both 8-byte aligned).  d_running: the two totals {rows, records} before the
- * chunk in, after it out.  The chunk's records go to d_rec and its rows to d_rows (8-byte aligned) at rec_first / row_first within
- * the call; no record at or beyond rec_cap and no row at or beyond row_cap is written.  cus as for launch_fetch. */
-hipError_t launch_project(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
-                          const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_cols,
-                          uint32_t ncols, uint32_t row_bytes, uint32_t max_att, uint32_t truth, bool floats, bool like, uint4 *d_blocks,
-                          void *d_side_rec, void *d_side_rows, uint64_t *d_running, void *d_rec, uint64_t rec_cap, void *d_rows,
-                          uint64_t row_cap, int cus);
+/* the grouped scan: the block kernel, k_group_offsets, k_group_copy.  d_slots: six entries of cryo_agg_col, the nby (1 .. 2)
+ * group columns in entries 0 .. 1, the ncols (0 .. 4) aggregate columns in entries 2 .. 5, every unused entry all zero; an
+ * undecided tuple counts in n_bad and is in no group.  d_blocks: the chunk's rows (cryo_group_block).  A group has cpg = ncols +
+ * popcount(ScanDesc::text) cells, the aggregate cells first.  Scratch: d_side_rec 24 bytes and d_side_cell 40 * cpg bytes per
+ * possible group (cnt * filter_side_stride(block_size) groups).  *d_running: the groups before the chunk in, after it out.  The
+ * chunk's records go to d_rec and its cells to d_cells at first_group within the call; nothing at or beyond group_cap groups is
+ * written */
+struct GroupLaunch {
+    const void *d_slots = nullptr;
+    uint32_t nby = 0, ncols = 0;
+    uint4 *d_blocks = nullptr;
+    void *d_side_rec = nullptr, *d_side_cell = nullptr;
+    uint64_t *d_running = nullptr;
+    void *d_rec = nullptr, *d_cells = nullptr;
+    uint64_t group_cap = 0;
+};
+inline bool group_launch_ok(const ScanChunk &c, const ScanDesc &d, const GroupLaunch &g)
+{
+    const uint32_t cpg = g.ncols + (uint32_t)__builtin_popcount(d.text); /* a group's cells: ncols unless it has key cells */
+    return scan_launch_ok(c, d, g.d_blocks,
+                          (uintptr_t)g.d_rec | (uintptr_t)g.d_cells | (uintptr_t)g.d_slots | (uintptr_t)g.d_side_rec |
+                              (uintptr_t)g.d_side_cell | (uintptr_t)g.d_running | (uintptr_t)d.d_buckets) &&
+           !(g.nby == 0u || g.nby > CRYO_GROUP_MAX_BY || g.ncols > CRYO_AGG_MAX_COLS || (d.text >> g.nby) != 0u || (d.text != 0u && d.d_buckets) ||
+             ((d.text != 0u || d.d_buckets) && d.truth == 0u) || !g.d_slots || !g.d_side_rec || !g.d_running || (cpg > 0u && !g.d_side_cell) ||
+             (g.group_cap > 0u && (!g.d_rec || (cpg > 0u && !g.d_cells))));
+}
+hipError_t launch_group(const ScanChunk &c, const ScanDesc &d, const GroupLaunch &g);
+/* launch_group's block kernels in other units, on arguments it has checked */
+hipError_t launch_groupf_block(const ScanChunk &c, const ScanDesc &d, const GroupLaunch &g);  /* group_float.o */
+hipError_t launch_groupl_block(const ScanChunk &c, const ScanDesc &d, const GroupLaunch &g);  /* group_float_like.o */
+hipError_t launch_groupb_block(const ScanChunk &c, const ScanDesc &d, const GroupLaunch &g);  /* group_bucket.o: <d.floats> */
+hipError_t launch_groupbl_block(const ScanChunk &c, const ScanDesc &d, const GroupLaunch &g); /* group_bucket_like.o */
+hipError_t launch_groupt_block(const ScanChunk &c, const ScanDesc &d, const GroupLaunch &g);  /* group_text.o: <d.floats> */
+hipError_t launch_grouptl_block(const ScanChunk &c, const ScanDesc &d, const GroupLaunch &g); /* group_text_like.o */
 
-/* the ordered scan (topn.hip) on one decoded chunk of cnt blocks (laid out as for launch_filter): k_topn_block, k_topn_offsets,
- * k_topn_copy.  The descriptors are validated by the caller (cryo_codec.cpp, topn_desc_ok): d_atts and d_keys as for
- * launch_filter; d_slots the staged table, ten entries of 8 bytes (device memory, 8-byte aligned): entries 0 .. 1 the nby (1 .. 2)
- * order columns {u16 att, u8 type (CRYO_KEY_INT2 .. _INT8, _FLOAT4, _FLOAT8), u8 flags (CRYO_ORDER_*), u32 0}, entries 2 .. 9
- * launch_project's column table of ncols (1 .. 8) columns, every unused entry all zero, and h_slots the host's copy of the ten
- * (what the block kernel needs of them after the walk travels as kernel arguments); row_bytes as for launch_project; limit
- * >= 1; max_att the highest key, order or projected column; truth and floats as for launch_filter (k_topn_block<true> / <false>,
- * k_topnf_block for a float scan key; an undecided tuple counts in n_bad and is in no ranking).  d_blocks: the chunk's rows of the
- * block table (cryo_topn_block, 16-byte aligned).  Scratch, per possible item (cnt * filter_side_stride(block_size) items):
- * d_side_rec 24 bytes and d_side_rows row_bytes bytes (both 8-byte aligned), d_side_ord 4 bytes.  *d_running: the kept rows before
- * the chunk in, after it out.  The chunk's records go to d_rec and its rows to d_rows (8-byte aligned) at row_first within the
- * call; nothing at or beyond row_cap is written.  cus as for launch_fetch. */
-hipError_t launch_topn(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
-                       const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,
-                       const void *h_slots, uint32_t nby, uint32_t ncols, uint32_t row_bytes, uint32_t limit, uint32_t max_att,
-                       uint32_t truth, bool floats, bool like, uint4 *d_blocks, void *d_side_rec, void *d_side_rows, void *d_side_ord,
-                       uint64_t *d_running, void *d_rec, void *d_rows, uint64_t row_cap, int cus);
+/* the projecting scan: the block kernel, k_project_offsets, k_project_copy.  d_cols: the staged column table, ncols (1 .. 8)
+ * entries of 8 bytes {u16 att, u8 width (the column's attlen: 1, 2, 4, 8), u8 offset within the row (a multiple of the width,
+ * below row_bytes), u32 0} -- the walk reads it as cryo_agg_col and looks at att alone; row_bytes the row's size, 8 .. 64 and a
+ * multiple of 8 (both from CRYO_PROJECT_COL_OFFSET / CRYO_PROJECT_ROW_BYTES); an undecided tuple gets a record {pos, 9, 0},
+ * counts in n_bad and has no row.  d_blocks: the chunk's rows of the block table (cryo_project_block).  Scratch: d_side_rec 8
+ * bytes and d_side_rows row_bytes bytes per possible item (cnt * filter_side_stride(block_size) items).  d_running: the two
+ * totals {rows, records} before the chunk in, after it out.  The chunk's records go to d_rec and its rows to d_rows at rec_first
+ * / row_first within the call; no record at or beyond rec_cap and no row at or beyond row_cap is written */
+struct ProjectLaunch {
+    const void *d_cols = nullptr;
+    uint32_t ncols = 0, row_bytes = 0;
+    uint4 *d_blocks = nullptr;
+    void *d_side_rec = nullptr, *d_side_rows = nullptr;
+    uint64_t *d_running = nullptr;
+    void *d_rec = nullptr;
+    uint64_t rec_cap = 0;
+    void *d_rows = nullptr;
+    uint64_t row_cap = 0;
+};
+inline bool project_launch_ok(const ScanChunk &c, const ScanDesc &d, const ProjectLaunch &p)
+{
+    return scan_launch_ok(c, d, p.d_blocks,
+                          (uintptr_t)p.d_rec | (uintptr_t)p.d_rows | (uintptr_t)p.d_cols | (uintptr_t)p.d_side_rec | (uintptr_t)p.d_side_rows |
+                              (uintptr_t)p.d_running) &&
+           !(p.ncols == 0u || p.ncols > CRYO_PROJECT_MAX_COLS || p.row_bytes < 8u || p.row_bytes > 8u * CRYO_PROJECT_MAX_COLS ||
+             (p.row_bytes & 7u) != 0 || !p.d_cols || !p.d_side_rec || !p.d_side_rows || !p.d_running || (p.rec_cap > 0u && !p.d_rec) ||
+             (p.row_cap > 0u && !p.d_rows));
+}
+hipError_t launch_project(const ScanChunk &c, const ScanDesc &d, const ProjectLaunch &p);
+hipError_t launch_projectl_block(const ScanChunk &c, const ScanDesc &d, const ProjectLaunch &p); /* project_like.o */
 
-/* the block kernels of descriptors with a pattern key (above: `like`), each alone in its unit *_like.o.  Their arguments are
- * those of the launcher that branches to them -- launch_filter, launch_agg, launch_group, launch_project, launch_topn --, which
- * has checked them, and of the block kernel they stand in for; truth is not 0 */
-hipError_t launch_filterl_match(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
-                                const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, uint32_t max_att,
-                                uint32_t truth, bool count_only, uint32_t side_stride, uint4 *d_blocks, uint4 *d_side, uint64_t *d_sum);
-hipError_t launch_aggl(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
-                       const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_cols,
-                       uint32_t ncols, uint32_t max_att, uint32_t truth, uint4 *d_blocks, void *d_cells);
-hipError_t launch_groupl_block(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
-                               const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,
-                               uint32_t nby, uint32_t ncols, uint32_t max_att, uint32_t truth, uint32_t side_stride, uint4 *d_blocks,
-                               void *d_side_rec, void *d_side_cell);
-hipError_t launch_groupbl_block(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
-                                const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,
-                                const void *d_buckets, uint32_t nby, uint32_t ncols, uint32_t max_att, uint32_t truth,
-                                uint32_t side_stride, uint4 *d_blocks, void *d_side_rec, void *d_side_cell);
-hipError_t launch_grouptl_block(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
-                                const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,
-                                uint32_t nby, uint32_t ncols, uint32_t text, uint32_t max_att, uint32_t truth, uint32_t side_stride,
-                                uint4 *d_blocks, void *d_side_rec, void *d_side_cell);
-hipError_t launch_projectl_block(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
-                                 const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_cols,
-                                 uint32_t ncols, uint32_t max_att, uint32_t truth, uint32_t row_words, uint32_t side_stride, uint4 *d_blocks,
-                                 void *d_side_rec, void *d_side_rows);
-hipError_t launch_topnl_block(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
-                              const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,
-                              uint32_t ord_bits, uint64_t row_map, uint32_t limit, uint32_t max_att, uint32_t truth, uint32_t row_words,
-                              uint32_t side_stride, uint4 *d_blocks, void *d_side_rec, void *d_side_rows, void *d_side_ord);
+/* the ordered scan: the block kernel, k_topn_offsets, k_topn_copy.  d_slots: the staged table, ten entries of 8 bytes: entries
+ * 0 .. 1 the nby (1 .. 2) order columns {u16 att, u8 type (CRYO_KEY_INT2 .. _INT8, _FLOAT4, _FLOAT8), u8 flags (CRYO_ORDER_*),
+ * u32 0}, entries 2 .. 9 ProjectLaunch's column table of ncols (1 .. 8) columns, every unused entry all zero; h_slots: the host's
+ * copy of the ten (topn_pack); row_bytes as ProjectLaunch's; limit >= 1; an undecided tuple counts in n_bad and is in no ranking.
+ * d_blocks: the chunk's rows of the block table (cryo_topn_block).  Scratch, per possible item (cnt *
+ * filter_side_stride(block_size) items): d_side_rec 24 bytes, d_side_rows row_bytes bytes, d_side_ord 4 bytes.  *d_running: the
+ * kept rows before the chunk in, after it out.  The chunk's records go to d_rec and its rows to d_rows at row_first within the
+ * call; nothing at or beyond row_cap is written */
+struct TopnLaunch {
+    const void *d_slots = nullptr, *h_slots = nullptr;
+    uint32_t nby = 0, ncols = 0, row_bytes = 0, limit = 0;
+    uint4 *d_blocks = nullptr;
+    void *d_side_rec = nullptr, *d_side_rows = nullptr, *d_side_ord = nullptr;
+    uint64_t *d_running = nullptr;
+    void *d_rec = nullptr, *d_rows = nullptr;
+    uint64_t row_cap = 0;
+};
+inline bool topn_launch_ok(const ScanChunk &c, const ScanDesc &d, const TopnLaunch &t)
+{
+    return scan_launch_ok(c, d, t.d_blocks,
+                          (uintptr_t)t.d_rec | (uintptr_t)t.d_rows | (uintptr_t)t.d_slots | (uintptr_t)t.d_side_rec | (uintptr_t)t.d_side_rows |
+                              (uintptr_t)t.d_running) &&
+           !(t.nby == 0u || t.nby > CRYO_ORDER_MAX_BY || t.limit == 0u || t.ncols == 0u || t.ncols > CRYO_PROJECT_MAX_COLS || t.row_bytes < 8u ||
+             t.row_bytes > 8u * CRYO_PROJECT_MAX_COLS || (t.row_bytes & 7u) != 0 || !t.d_slots || !t.h_slots || !t.d_side_rec || !t.d_side_rows ||
+             !t.d_side_ord || ((uintptr_t)t.d_side_ord & 3u) != 0 || !t.d_running || (t.row_cap > 0u && (!t.d_rec || !t.d_rows)));
+}
+/* What the top-N block kernel needs of its table after the walk rides in two arguments, packed from the host's copy (topn.hip:
+ * why).  ord_bits: byte j (j = 0, 1) describes order column j with the bits below, byte 2 is the mask of the projected columns;
+ * row_map: byte j is projected column j's place in the row, its offset (0 .. 56) in bits 0 .. 5 and log2 of its width above.
+ * False: a projected column whose width is not 1, 2, 4 or 8, whose offset is no multiple of it, or that ends beyond the row */
+constexpr uint32_t kOrdPresent = 1u, kOrdFloat = 2u, kOrdFloat4 = 4u, kOrdNullsFirst = 8u, kOrdDesc = 16u;
+inline bool topn_pack(const TopnLaunch &t, uint32_t &ord_bits, uint64_t &row_map)
+{
+    const cryo_agg_col *h_slots = (const cryo_agg_col *)t.h_slots;
+    ord_bits = ((1u << t.ncols) - 1u) << 16;
+    row_map = 0;
+    for (uint32_t j = 0; j < t.nby; j++) {
+        const cryo_agg_col &q = h_slots[j];
+        const bool f4 = q.type == CRYO_KEY_FLOAT4, f8 = q.type == CRYO_KEY_FLOAT8;
+        ord_bits |= (kOrdPresent | (f4 || f8 ? kOrdFloat : 0u) | (f4 ? kOrdFloat4 : 0u) | ((q.rsv & CRYO_ORDER_NULLS_FIRST) ? kOrdNullsFirst : 0u) |
+                     ((q.rsv & CRYO_ORDER_DESC) ? kOrdDesc : 0u))
+                    << (8u * j);
+    }
+    for (uint32_t j = 0; j < t.ncols; j++) {
+        const cryo_agg_col &q = h_slots[CRYO_ORDER_MAX_BY + j];
+        const uint32_t w = q.type, o = q.rsv;
+        if ((w != 1u && w != 2u && w != 4u && w != 8u) || (o & (w - 1u)) != 0 || o + w > t.row_bytes) return false;
+        row_map |= (uint64_t)(o | (w == 8u ? 3u : w == 4u ? 2u : w == 2u ? 1u : 0u) << 6) << (8u * j);
+    }
+    return true;
+}
+hipError_t launch_topn(const ScanChunk &c, const ScanDesc &d, const TopnLaunch &t);
+hipError_t launch_topnl_block(const ScanChunk &c, const ScanDesc &d, const TopnLaunch &t); /* topn_like.o */
 
 } // namespace cryo
 

@@ -31,7 +31,7 @@ namespace cryo {
 constexpr uint32_t kProjectMaxCols = 8u; /* CRYO_PROJECT_MAX_COLS */
 
 /* The staged column table: entry j is an AggCol to the walk (which reads att alone) and carries in `type` the column's width
- * w_j (1, 2, 4, 8) and in `rsv` its offset o_j within the row (0 .. 56, a multiple of w_j): launch_project's rule */
+ * w_j (1, 2, 4, 8) and in `rsv` its offset o_j within the row (0 .. 56, a multiple of w_j): ProjectLaunch's rule (kernels.h) */
 
 /* the body of k_project_block, of k_projectf_block, the kernel of descriptors with a float key, and of k_projectl_block, the
  * kernel of descriptors with a pattern key */
@@ -188,40 +188,26 @@ k_project_copy(uint32_t cnt, uint32_t side_stride, uint32_t row_words, const uin
     }
 }
 
-hipError_t launch_project(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
-                          const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_cols,
-                          uint32_t ncols, uint32_t row_bytes, uint32_t max_att, uint32_t truth, bool floats, bool like, uint4 *d_blocks, void *d_side_rec,
-                          void *d_side_rows, uint64_t *d_running, void *d_rec, uint64_t rec_cap, void *d_rows, uint64_t row_cap, int cus)
+static_assert(kProjectMaxCols == CRYO_PROJECT_MAX_COLS, "project_launch_ok's limit (kernels.h) is the kernels'");
+
+hipError_t launch_project(const ScanChunk &c, const ScanDesc &d, const ProjectLaunch &p)
 {
-    if (cnt == 0) return hipSuccess;
-    if (!scan_launch_ok(dec_stride, d_dec, d_blocks, d_atts, d_keys,
-                        (uintptr_t)d_rec | (uintptr_t)d_rows | (uintptr_t)d_cols | (uintptr_t)d_side_rec | (uintptr_t)d_side_rows |
-                            (uintptr_t)d_running,
-                        block_size, nkeys, truth, floats || like) ||
-        ncols == 0u || ncols > kProjectMaxCols || row_bytes < 8u ||
-        row_bytes > 8u * kProjectMaxCols || (row_bytes & 7u) != 0 || !d_cols || !d_side_rec || !d_side_rows || !d_running ||
-        (rec_cap > 0u && !d_rec) || (row_cap > 0u && !d_rows))
-        return hipErrorInvalidValue;
-    const uint32_t stride = filter_side_stride(block_size), row_words = row_bytes / 8u;
-    hipError_t e;
-    if (like) /* a pattern key: the kernel of this source's second unit */
-        e = launch_projectl_block(s, d_dec, dec_stride, block_size, cnt, d_dec_status, d_atts, d_keys, nkeys, d_cols, ncols, max_att, truth,
-                                  row_words, stride, d_blocks, d_side_rec, d_side_rows);
-    else {
-        hipLaunchKernelGGL(floats ? k_projectf_block : truth ? k_project_block<true> : k_project_block<false>, dim3((cnt + 3u) / 4u), dim3(256), 0, s, d_dec,
-                           dec_stride, block_size, cnt, d_dec_status, (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys | truth << 16,
-                           (const AggCol *)d_cols, ncols, max_att, row_words, stride, d_blocks, (uint2 *)d_side_rec, (uint2 *)d_side_rows);
-        e = hipGetLastError();
+    if (c.cnt == 0) return hipSuccess;
+    if (!project_launch_ok(c, d, p)) return hipErrorInvalidValue;
+    hipError_t e = hipErrorInvalidValue;
+    switch (scan_route(d.truth, d.floats, d.like)) {
+    case kRouteLike: e = launch_projectl_block(c, d, p); break; /* a pattern key: the kernel of this source's second unit */
+    case kRouteFloat: e = project_launch(k_projectf_block, true, c, d, p); break;
+    case kRouteTable: e = project_launch(k_project_block<true>, true, c, d, p); break;
+    case kRoutePlain: e = project_launch(k_project_block<false>, false, c, d, p); break;
     }
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_project_offsets, dim3(1), dim3(256), 0, s, cnt, d_running, d_blocks);
+    hipLaunchKernelGGL(k_project_offsets, dim3(1), dim3(256), 0, c.stream, c.cnt, p.d_running, p.d_blocks);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    /* four workgroups per compute unit, but never more than the chunk has blocks */
-    uint64_t grid = (uint64_t)(cus > 0 ? cus : 256) * 4u;
-    if (grid > cnt) grid = cnt;
-    hipLaunchKernelGGL(k_project_copy, dim3((uint32_t)grid), dim3(256), 0, s, cnt, stride, row_words, (const uint4 *)d_blocks,
-                       (const uint2 *)d_side_rec, (const uint2 *)d_side_rows, (uint2 *)d_rec, rec_cap, (uint2 *)d_rows, row_cap);
+    hipLaunchKernelGGL(k_project_copy, dim3(scan_copy_grid(c.cus, c.cnt)), dim3(256), 0, c.stream, c.cnt, filter_side_stride(c.block_size),
+                       p.row_bytes / 8u, (const uint4 *)p.d_blocks, (const uint2 *)p.d_side_rec, (const uint2 *)p.d_side_rows, (uint2 *)p.d_rec,
+                       p.rec_cap, (uint2 *)p.d_rows, p.row_cap);
     return hipGetLastError();
 }
 
@@ -239,17 +225,9 @@ k_projectl_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t 
                                          side_stride, blocks, side_rec, side_rows);
 }
 
-hipError_t launch_projectl_block(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
-                                 const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_cols,
-                                 uint32_t ncols, uint32_t max_att, uint32_t truth, uint32_t row_words, uint32_t side_stride, uint4 *d_blocks,
-                                 void *d_side_rec, void *d_side_rows)
+hipError_t launch_projectl_block(const ScanChunk &c, const ScanDesc &d, const ProjectLaunch &p)
 {
-    /* the arguments are launch_project's, which checked them; the one verdict path needs a table */
-    if (truth == 0u) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_projectl_block, dim3((cnt + 3u) / 4u), dim3(256), 0, s, d_dec, dec_stride, block_size, cnt, d_dec_status,
-                       (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys | truth << 16, (const AggCol *)d_cols, ncols, max_att,
-                       row_words, side_stride, d_blocks, (uint2 *)d_side_rec, (uint2 *)d_side_rows);
-    return hipGetLastError();
+    return project_launch(k_projectl_block, true, c, d, p);
 }
 #endif
 

@@ -12,8 +12,11 @@
  *   sweep_wave   which block the wave takes and the lane's number in it
  *   sweep_open   STREAM, HEADER, or the block's items and tuples
  *   sweep_turn   one item: ITEM, the walk, and the verdict sorted into match / bad / neither
+ * And, for the host, the launch of such a kernel: scan_block_launch, and on it the helpers of the three calls whose units share
+ * this header alone (filter_launch, agg_launch, project_launch; the grouped scan's is group_lds.h's, the ordered scan's topn.hip's).
  */
 #pragma once
+#include "kernels.h"
 #include "heap_block.h"
 #include "filter_walk.h"
 
@@ -79,6 +82,41 @@ __device__ inline SweepItem sweep_turn(const uint8_t *__restrict__ p, uint32_t B
     it.match = it.verdict == 0u;
     it.bad = it.verdict == kFilterItem || it.verdict == kFilterTuple || (BYTES && it.verdict == kFilterUndecided);
     return it;
+}
+
+/* ---- the host's side: the block-kernel launch of the scan calls (kernels.h: ScanChunk, ScanDesc, the calls' own structs) ---- */
+
+/* a block kernel: the eight arguments every one begins with -- the chunk, the descriptor and the keys, scan_nkeys_arg --, then
+ * the call's own */
+template <class... OWN>
+using ScanKernel = void (*)(const uint8_t *, uint64_t, uint32_t, uint32_t, const int32_t *, const FilterAtt *, const FilterKey *, uint32_t, OWN...);
+
+/* The launch, all of it: one wave per block and `waves` blocks per workgroup; the eight arguments, then `own`.  table: the kernel
+ * has the truth table's verdict path alone -- every kernel but a call's <false> one --, which needs a table */
+template <class... OWN, class... ARGS>
+inline hipError_t scan_block_launch(ScanKernel<OWN...> kernel, uint32_t waves, bool table, const ScanChunk &c, const ScanDesc &d, ARGS... own)
+{
+    if (table && d.truth == 0u) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(kernel, dim3((c.cnt + waves - 1u) / waves), dim3(64u * waves), 0, c.stream, c.d_dec, c.dec_stride, c.block_size, c.cnt,
+                       c.d_dec_status, (const FilterAtt *)d.d_atts, (const FilterKey *)d.d_keys, scan_nkeys_arg(d.nkeys, d.truth), own...);
+    return hipGetLastError();
+}
+
+/* the filter's, the aggregate's and the projection's block kernels: four blocks per workgroup */
+template <class K> inline hipError_t filter_launch(K kernel, bool table, const ScanChunk &c, const ScanDesc &d, const FilterLaunch &f)
+{
+    return scan_block_launch(kernel, 4u, table, c, d, d.max_att, f.count_only ? 1u : 0u, filter_side_stride(c.block_size), f.d_blocks, f.d_side,
+                             f.d_sum);
+}
+struct AggCell; /* agg_cell.h */
+template <class K> inline hipError_t agg_launch(K kernel, bool table, const ScanChunk &c, const ScanDesc &d, const AggLaunch &a)
+{
+    return scan_block_launch(kernel, 4u, table, c, d, (const AggCol *)a.d_cols, a.ncols, d.max_att, a.d_blocks, (AggCell *)a.d_cells);
+}
+template <class K> inline hipError_t project_launch(K kernel, bool table, const ScanChunk &c, const ScanDesc &d, const ProjectLaunch &p)
+{
+    return scan_block_launch(kernel, 4u, table, c, d, (const AggCol *)p.d_cols, p.ncols, d.max_att, p.row_bytes / 8u,
+                             filter_side_stride(c.block_size), p.d_blocks, (uint2 *)p.d_side_rec, (uint2 *)p.d_side_rows);
 }
 
 } // namespace cryo

@@ -37,10 +37,9 @@ constexpr uint32_t kTopnMaxCols = 8u; /* CRYO_PROJECT_MAX_COLS */
 constexpr uint32_t kTopnSlots = kTopnMaxBy + kTopnMaxCols; /* capture slots: the order columns, then the projected columns */
 constexpr uint32_t kTopnWaves = 2u;   /* blocks per workgroup */
 /* what the block kernel needs of the descriptors after the walk rides in two arguments, not in loads from the staged table that
- * the compiler would hoist over the item loop and keep in scalar registers the walk has none to spare of (launch_topn packs them):
- * ord_bits: byte j (j = 0, 1) describes order column j with the bits below, byte 2 is the mask of the projected columns;
- * row_map: byte j is projected column j's place in the row, its offset (0 .. 56) in bits 0 .. 5 and log2 of its width above */
-constexpr uint32_t kOrdPresent = 1u, kOrdFloat = 2u, kOrdFloat4 = 4u, kOrdNullsFirst = 8u, kOrdDesc = 16u;
+ * the compiler would hoist over the item loop and keep in scalar registers the walk has none to spare of: ord_bits and row_map,
+ * with the kOrd* bits, as topn_pack (kernels.h) packs them from the host's copy of the table */
+static_assert(kTopnMaxBy == CRYO_ORDER_MAX_BY && kTopnMaxCols == CRYO_PROJECT_MAX_COLS, "topn_launch_ok's limits (kernels.h) are the kernels'");
 
 struct TopnRec { int64_t key[2]; uint16_t pos, key_nulls; uint32_t nulls; }; /* cryo_topn_rec */
 static_assert(sizeof(TopnRec) == 24 && sizeof(cryo_topn_rec) == 24, "the record's layout is the header's");
@@ -55,7 +54,7 @@ struct TopnLds {
 };
 static_assert(sizeof(TopnLds) * kTopnWaves <= 32480u, "a workgroup's LDS stays within k_group_block's");
 
-/* The staged table (launch_topn's rule): entries 0 .. 1 the order columns {att, type, flags, 0}, entries 2 .. 9 the projection's
+/* The staged table (TopnLaunch's rule, kernels.h): entries 0 .. 1 the order columns {att, type, flags, 0}, entries 2 .. 9 the projection's
  * column table {att, width, offset within the row, 0}; unused entries all zero.  The walk reads it as AggCol and looks at att */
 
 template <bool BYTES, bool FLOATS, bool LIKE = false>
@@ -181,6 +180,17 @@ __device__ inline void topn_block_body(TopnLds &L, uint32_t k, uint32_t lane, co
     }
 }
 
+/* the host's side: the block-kernel launch of both units (scan_sweep.h: scan_block_launch), with the two packed arguments */
+template <class K> inline hipError_t topn_launch(K kernel, bool table, const ScanChunk &c, const ScanDesc &d, const TopnLaunch &t)
+{
+    uint32_t ord_bits;
+    uint64_t row_map;
+    if (!topn_pack(t, ord_bits, row_map)) return hipErrorInvalidValue;
+    return scan_block_launch(kernel, kTopnWaves, table, c, d, (const AggCol *)t.d_slots, ord_bits, row_map, t.limit, d.max_att, t.row_bytes / 8u,
+                             filter_side_stride(c.block_size), t.d_blocks, (TopnRec *)t.d_side_rec, (uint2 *)t.d_side_rows,
+                             (uint32_t *)t.d_side_ord);
+}
+
 #ifndef CRYO_LIKE_UNIT
 template <bool BYTES>
 __global__ void __launch_bounds__(64 * kTopnWaves)
@@ -246,60 +256,24 @@ k_topn_copy(uint32_t cnt, uint32_t side_stride, uint32_t row_words, const uint4 
     }
 }
 
-hipError_t launch_topn(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
-                       const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,
-                       const void *h_slots, uint32_t nby, uint32_t ncols, uint32_t row_bytes, uint32_t limit, uint32_t max_att,
-                       uint32_t truth, bool floats, bool like, uint4 *d_blocks, void *d_side_rec, void *d_side_rows, void *d_side_ord,
-                       uint64_t *d_running, void *d_rec, void *d_rows, uint64_t row_cap, int cus)
+hipError_t launch_topn(const ScanChunk &c, const ScanDesc &d, const TopnLaunch &t)
 {
-    if (cnt == 0) return hipSuccess;
-    if (!scan_launch_ok(dec_stride, d_dec, d_blocks, d_atts, d_keys,
-                        (uintptr_t)d_rec | (uintptr_t)d_rows | (uintptr_t)d_slots | (uintptr_t)d_side_rec | (uintptr_t)d_side_rows |
-                            (uintptr_t)d_running,
-                        block_size, nkeys, truth, floats || like) ||
-        nby == 0u || nby > kTopnMaxBy || limit == 0u || ncols == 0u || ncols > kTopnMaxCols || row_bytes < 8u ||
-        row_bytes > 8u * kTopnMaxCols || (row_bytes & 7u) != 0 || !d_slots || !h_slots || !d_side_rec || !d_side_rows || !d_side_ord ||
-        ((uintptr_t)d_side_ord & 3u) != 0 || !d_running || (row_cap > 0u && (!d_rec || !d_rows)))
-        return hipErrorInvalidValue;
-    /* the two packed arguments of the block kernel, from the host's copy of the staged table */
-    uint32_t ord_bits = ((1u << ncols) - 1u) << 16;
-    uint64_t row_map = 0;
-    for (uint32_t j = 0; j < nby; j++) {
-        const AggCol &q = ((const AggCol *)h_slots)[j];
-        const bool f4 = q.type == kKeyFloat4, f8 = q.type == kKeyFloat8;
-        ord_bits |= (kOrdPresent | (f4 || f8 ? kOrdFloat : 0u) | (f4 ? kOrdFloat4 : 0u) | ((q.rsv & CRYO_ORDER_NULLS_FIRST) ? kOrdNullsFirst : 0u) |
-                     ((q.rsv & CRYO_ORDER_DESC) ? kOrdDesc : 0u))
-                    << (8u * j);
-    }
-    for (uint32_t j = 0; j < ncols; j++) {
-        const AggCol &q = ((const AggCol *)h_slots)[kTopnMaxBy + j];
-        const uint32_t w = q.type, o = q.rsv;
-        if ((w != 1u && w != 2u && w != 4u && w != 8u) || (o & (w - 1u)) != 0 || o + w > row_bytes) return hipErrorInvalidValue;
-        row_map |= (uint64_t)(o | (w == 8u ? 3u : w == 4u ? 2u : w == 2u ? 1u : 0u) << 6) << (8u * j);
-    }
-    const uint32_t stride = filter_side_stride(block_size), row_words = row_bytes / 8u;
-    hipError_t e;
-    if (like) /* a pattern key: the kernel of this source's second unit */
-        e = launch_topnl_block(s, d_dec, dec_stride, block_size, cnt, d_dec_status, d_atts, d_keys, nkeys, d_slots, ord_bits, row_map, limit,
-                               max_att, truth, row_words, stride, d_blocks, d_side_rec, d_side_rows, d_side_ord);
-    else {
-        hipLaunchKernelGGL(floats ? k_topnf_block : truth ? k_topn_block<true> : k_topn_block<false>,
-                           dim3((cnt + kTopnWaves - 1u) / kTopnWaves), dim3(64 * kTopnWaves), 0, s, d_dec, dec_stride, block_size, cnt,
-                           d_dec_status, (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys | truth << 16, (const AggCol *)d_slots,
-                           ord_bits, row_map, limit, max_att, row_words, stride, d_blocks, (TopnRec *)d_side_rec, (uint2 *)d_side_rows,
-                           (uint32_t *)d_side_ord);
-        e = hipGetLastError();
+    if (c.cnt == 0) return hipSuccess;
+    if (!topn_launch_ok(c, d, t)) return hipErrorInvalidValue;
+    hipError_t e = hipErrorInvalidValue;
+    switch (scan_route(d.truth, d.floats, d.like)) {
+    case kRouteLike: e = launch_topnl_block(c, d, t); break; /* a pattern key: the kernel of this source's second unit */
+    case kRouteFloat: e = topn_launch(k_topnf_block, true, c, d, t); break;
+    case kRouteTable: e = topn_launch(k_topn_block<true>, true, c, d, t); break;
+    case kRoutePlain: e = topn_launch(k_topn_block<false>, false, c, d, t); break;
     }
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_topn_offsets, dim3(1), dim3(256), 0, s, cnt, d_running, d_blocks);
+    hipLaunchKernelGGL(k_topn_offsets, dim3(1), dim3(256), 0, c.stream, c.cnt, t.d_running, t.d_blocks);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    /* four workgroups per compute unit, but never more than the chunk has blocks */
-    uint64_t grid = (uint64_t)(cus > 0 ? cus : 256) * 4u;
-    if (grid > cnt) grid = cnt;
-    hipLaunchKernelGGL(k_topn_copy, dim3((uint32_t)grid), dim3(256), 0, s, cnt, stride, row_words, (const uint4 *)d_blocks,
-                       (const uint64_t *)d_side_rec, (const uint2 *)d_side_rows, (const uint32_t *)d_side_ord, (uint64_t *)d_rec,
-                       (uint2 *)d_rows, row_cap);
+    hipLaunchKernelGGL(k_topn_copy, dim3(scan_copy_grid(c.cus, c.cnt)), dim3(256), 0, c.stream, c.cnt, filter_side_stride(c.block_size),
+                       t.row_bytes / 8u, (const uint4 *)t.d_blocks, (const uint64_t *)t.d_side_rec, (const uint2 *)t.d_side_rows,
+                       (const uint32_t *)t.d_side_ord, (uint64_t *)t.d_rec, (uint2 *)t.d_rows, t.row_cap);
     return hipGetLastError();
 }
 
@@ -321,19 +295,7 @@ k_topnl_block(const uint8_t *__restrict__ dec, uint64_t dec_stride, uint32_t B, 
                                       max_att, row_words, side_stride, blocks, side_rec, side_rows, side_ord);
 }
 
-hipError_t launch_topnl_block(hipStream_t s, const uint8_t *d_dec, uint64_t dec_stride, uint32_t block_size, uint32_t cnt,
-                              const int32_t *d_dec_status, const void *d_atts, const void *d_keys, uint32_t nkeys, const void *d_slots,
-                              uint32_t ord_bits, uint64_t row_map, uint32_t limit, uint32_t max_att, uint32_t truth, uint32_t row_words,
-                              uint32_t side_stride, uint4 *d_blocks, void *d_side_rec, void *d_side_rows, void *d_side_ord)
-{
-    /* the arguments are launch_topn's, which checked and packed them; the one verdict path needs a table */
-    if (truth == 0u) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_topnl_block, dim3((cnt + kTopnWaves - 1u) / kTopnWaves), dim3(64 * kTopnWaves), 0, s, d_dec, dec_stride, block_size,
-                       cnt, d_dec_status, (const FilterAtt *)d_atts, (const FilterKey *)d_keys, nkeys | truth << 16, (const AggCol *)d_slots,
-                       ord_bits, row_map, limit, max_att, row_words, side_stride, d_blocks, (TopnRec *)d_side_rec, (uint2 *)d_side_rows,
-                       (uint32_t *)d_side_ord);
-    return hipGetLastError();
-}
+hipError_t launch_topnl_block(const ScanChunk &c, const ScanDesc &d, const TopnLaunch &t) { return topn_launch(k_topnl_block, true, c, d, t); }
 #endif
 
 } // namespace cryo
